@@ -22,6 +22,12 @@ Prints ONE JSON line (rank 0) with
   cpu_baseline  the CPU oracle ("port", 1 core) on a bounded prefix sample of the same workload
 and the same accounting for the other groups (roofline_groups), per-pass scatter efficiency (pass_efficiency),
 and the 101 MB configs[1] figure as an extra key.
+
+A plain run (`python bench.py --gpus N --steps K --warmup W`) does only what the headline needs: it generates the workload,
+warms up, times the K steps and prints the line, with `roofline` and `cpu_baseline` null.  `--full` adds everything
+listed above (the profiled step, the image md5, the CLI end-to-end leg, the 101 MB figure, the CPU baseline and, at N > 1,
+the comparison with a single-GPU build).  `--dump-outputs DIR` writes what the last timed step left for a caller (the .rl_bwt
+image; see dump_outputs) as .npy files, so that two builds of the project can be compared output for output.
 """
 import argparse
 import json
@@ -176,6 +182,49 @@ def pmc_traffic_stale(kernel_fragments):
     return [f for f in kernel_fragments if f not in OPTIONAL_KERNELS and not any(f in n for n in names)]
 
 
+DUMP_SAMPLE_BLOCKS, DUMP_BLOCK = 128, 1 << 16     # 8 MiB of image bytes -> 32 MB of float32
+DUMP_SUM_BLOCKS, DUMP_SUM_ROWS = 4096, 64          # rows summed per pass: 64 blocks of int64 at a time (~1 GB at 10 GB)
+
+
+def dump_outputs(out_dir, ctx, dev, seed=20260101):
+    """--dump-outputs: the .rl_bwt image the last timed step left in HBM -- all of it, or at N > 1 rank 0's part (what
+    grlbwt_result_device_ptr gives a caller) -- as .npy files of 33 MB at most, whatever the image's size:
+      image_size.npy        float64 [image bytes, runs, part offset, part bytes]
+      image_sample.npy      float32 image bytes: the first 64 KiB (header and first runs) and 127 more 64 KiB blocks at offsets
+                            drawn from `seed` (the whole part when it holds 8 MiB or less)
+      image_block_sums.npy  float64 [4096, 2]: for 4096 consecutive blocks that together cover every byte of the part, the byte
+                            sum and the sum weighted by (position in the block mod 255) + 1
+    The caller has synchronised the device after the step."""
+    import numpy as np
+    import torch
+    from grlbwt_amd import dist as gdist
+    nb_img, nr_img = ctx.result_size()
+    off, nb = ctx.result_part()
+    img = gdist._view(ctx.result_device_ptr(), nb, dev)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "image_size.npy"), np.array([nb_img, nr_img, off, nb], dtype=np.float64))
+
+    if nb <= DUMP_SAMPLE_BLOCKS * DUMP_BLOCK:
+        sample = img
+    else:
+        starts = np.random.default_rng(seed).integers(DUMP_BLOCK, nb - DUMP_BLOCK + 1, size=DUMP_SAMPLE_BLOCKS - 1)
+        starts = torch.from_numpy(np.concatenate([[0], np.sort(starts)])).to(dev)
+        sample = img[(starts[:, None] + torch.arange(DUMP_BLOCK, device=dev)).reshape(-1)]
+    np.save(os.path.join(out_dir, "image_sample.npy"), sample.float().cpu().numpy())
+
+    blk = max(1, -(-nb // DUMP_SUM_BLOCKS))
+    weight = torch.arange(blk, device=dev) % 255 + 1
+    rows = torch.empty(DUMP_SUM_ROWS * blk, dtype=torch.uint8, device=dev)
+    sums = []
+    for b in range(0, DUMP_SUM_BLOCKS, DUMP_SUM_ROWS):
+        lo, hi = min(nb, b * blk), min(nb, (b + DUMP_SUM_ROWS) * blk)
+        rows.zero_()
+        rows[:hi - lo] = img[lo:hi]
+        r = rows.view(DUMP_SUM_ROWS, blk).long()
+        sums.append(torch.stack([r.sum(1), (r * weight).sum(1)], 1))
+    np.save(os.path.join(out_dir, "image_block_sums.npy"), torch.cat(sums).cpu().numpy().astype(np.float64))
+
+
 def spawn_ranks(args, argv):
     """--gpus N without a launcher: start N ranks as a CHILD (this process has not imported torch or touched the
     GPU), relay rank 0's line, exit with the child's code."""
@@ -214,6 +263,11 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extra", action="store_true", help="skip the 101 MB configs[1] side measurement")
     ap.add_argument("--no-cli", action="store_true", help="skip the end-to-end leg through the grlbwt executable (file in -> .rl_bwt file closed)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the profiled step (roofline, per-site figures), the image md5, the CLI leg, "
+                         "the 101 MB figure, the CPU baseline and (N > 1) the single-GPU comparison; a plain run only times the steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (the .rl_bwt image; rank 0's part at N > 1) to DIR/*.npy")
     args = ap.parse_args()
     if args.reads is None:
         args.reads = 66225166 if args.workload == "illumina" else 1000000
@@ -342,12 +396,71 @@ def main():
     comm_timed = (comm.n_allgather, comm.n_alltoall, comm.bytes_moved, comm.seconds) if comm is not None else None
     ms_per_step = dt / args.steps * 1e3
     value = total_bytes * args.steps / dt / 1e6
+    parts_span = ctx.result_part() if keep_parts else None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, ctx, dev)
+
+    def result_line(roofline=None, cpu=None, cli_e2e=None):
+        """The headline keys (a plain run prints only these; --full adds its measurements to the same dict)."""
+        if args.workload == "illumina":
+            wl = ("%d x 150 bp Illumina-style reads (%d bytes) from a %d bp genome, 0.5%% substitutions; BASELINE configs[3]%s"
+                  % (args.reads, total_bytes, args.genome, "" if args.reads == 66225166 else " shape (reduced read count)"))
+        else:
+            wl = ("%d x %d bp uniform ACGT reads (%d bytes), sigma=5, byte alphabet; BASELINE configs[1]%s"
+                  % (args.reads, args.read_len, total_bytes, "" if (args.reads, args.read_len) == (1000000, 100) else " shape"))
+        out = {
+            "metric": "input MB/s building BCR BWT on 10 GB DNA reads, 1/2/4/8 MI355X", "value": round(value, 3), "unit": "MB/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3),
+            # (scaling: ONE collection of fixed size -- strong scaling at N > 1; at N = 1 neither word applies)
+            "higher_is_better": True, "scaling": "strong" if world > 1 else "single", "vs_baseline": None, "dtype": "u8",
+            "data": "synthetic", "full": args.full,
+            # value = the build with the input resident in HBM (the contract of this bench); value_cli = the same bytes through the
+            # grlbwt executable, file in the page cache -> .rl_bwt file closed (SURVEY 8(d)'s wording of the metric; median run)
+            "value_cli": (cli_e2e or {}).get("MBps_wall"),
+            "config": {"workload": wl, "input_resident": "HBM",
+                       "output": (".rl_bwt image in HBM" if not keep_parts else
+                                  ".rl_bwt image in HBM, in %d parts on the ranks that induced them (rank 0: bytes [%d, %d)); gathered after the "
+                                  "timed region for the md5 / single-GPU comparison of --full" % (world, parts_span[0], parts_span[0] + parts_span[1])),
+                       "value_is": "HBM-resident build (value); value_cli = wall time of the CLI, file in -> .rl_bwt file closed, median of the timed runs",
+                       "parallelism": ("1 GPU" if world == 1 else
+                                       "the ONE collection sharded by record over %d GPUs (%d reads each): local LMS parsing/hashing/emission, "
+                                       "hash-partitioned dictionary merge (all-to-all) + key-range-sharded dictionary stage per round, induction "
+                                       "sharded by output piece (cells and BWT_{r+1} windows cross the fabric once per level), RCCL" % (world, hi - lo))},
+            # what the TIMED steps leave behind: the whole image on one device (N = 1, and N > 1 with GRLBWT_BENCH_GATHER_IMAGE=1), or -- the
+            # definition of the metric at N > 1 since round 5 -- the image in parts on the ranks that induced them (rounds 1-4 timed the
+            # all-gather to every rank as well: SCALE records of r01-r04 and of r05 on are not comparable)
+            "image_layout": "parts" if keep_parts else "whole",
+            "roofline": roofline, "cpu_baseline": cpu,
+            # per-GPU view of the same run (the collection is fixed, so this is NOT a weak-scaling measurement: a rank's work
+            # includes the replicated parts of the dictionary stage, which do not shrink with N)
+            "per_gpu": {"shard_bytes_rank0": n_bytes, "value_per_gpu": round(value / world, 3)},
+            "devices": devices,
+            "distinct_devices": len({d.get("uuid") or d.get("pci_bus_id") or (d["local_rank"], d["hip_device"]) for d in devices}),
+        }
+        if comm is not None:     # rank 0's totals over the warm-up and timed steps (comm_timed), per step
+            nsteps = max(1, args.warmup + args.steps)
+            out["collectives_per_step"] = {"allgather": comm_timed[0] // nsteps, "alltoallv": comm_timed[1] // nsteps,
+                                           "bytes": comm_timed[2] // nsteps, "ms_in_callbacks": round(comm_timed[3] / nsteps * 1e3, 3)}
+        return out
+
+    def finish(out):
+        try:
+            ctx.close()
+        except Exception:
+            pass
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        if rank == 0:
+            os.write(result_fd, (json.dumps(out) + "\n").encode())
+
+    if not args.full:
+        finish(result_line() if rank == 0 else None)
+        return
 
     # the image the timed steps produced (outside the timed region): size, runs, md5 -- so that a driver run and a lease run
     # can be compared, and tests/test_gpu_parity.py::test_headline_10GB_round_trip decodes exactly this image
-    parts_span = None
     if keep_parts:
-        parts_span = ctx.result_part()
         step(parts=False)                 # (untimed, every rank: the whole image on every rank from here on)
         barrier()
     image = None
@@ -567,35 +680,9 @@ def main():
                "host_cpus": os.cpu_count()}
 
     if rank == 0:
-        if args.workload == "illumina":
-            wl = ("%d x 150 bp Illumina-style reads (%d bytes) from a %d bp genome, 0.5%% substitutions; BASELINE configs[3]%s"
-                  % (args.reads, total_bytes, args.genome, "" if args.reads == 66225166 else " shape (reduced read count)"))
-        else:
-            wl = ("%d x %d bp uniform ACGT reads (%d bytes), sigma=5, byte alphabet; BASELINE configs[1]%s"
-                  % (args.reads, args.read_len, total_bytes, "" if (args.reads, args.read_len) == (1000000, 100) else " shape"))
-        out = {
-            "metric": "input MB/s building BCR BWT on 10 GB DNA reads, 1/2/4/8 MI355X", "value": round(value, 3), "unit": "MB/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3),
-            # (scaling: ONE collection of fixed size -- strong scaling at N > 1; at N = 1 neither word applies)
-            "higher_is_better": True, "scaling": "strong" if world > 1 else "single", "vs_baseline": None, "dtype": "u8",
-            "data": "synthetic",
-            # value = the build with the input resident in HBM (the contract of this bench); value_cli = the same bytes through the
-            # grlbwt executable, file in the page cache -> .rl_bwt file closed (SURVEY 8(d)'s wording of the metric; median run)
-            "value_cli": (cli_e2e or {}).get("MBps_wall"),
-            "config": {"workload": wl, "input_resident": "HBM",
-                       "output": (".rl_bwt image in HBM" if not keep_parts else
-                                  ".rl_bwt image in HBM, in %d parts on the ranks that induced them (rank 0: bytes [%d, %d)); gathered after the "
-                                  "timed region for the md5 / single-GPU comparison" % (world, parts_span[0], parts_span[0] + parts_span[1])),
-                       "value_is": "HBM-resident build (value); value_cli = wall time of the CLI, file in -> .rl_bwt file closed, median of the timed runs",
-                       "parallelism": ("1 GPU" if world == 1 else
-                                       "the ONE collection sharded by record over %d GPUs (%d reads each): local LMS parsing/hashing/emission, "
-                                       "hash-partitioned dictionary merge (all-to-all) + key-range-sharded dictionary stage per round, induction "
-                                       "sharded by output piece (cells and BWT_{r+1} windows cross the fabric once per level), RCCL" % (world, hi - lo))},
-            # what the TIMED steps leave behind: the whole image on one device (N = 1, and N > 1 with GRLBWT_BENCH_GATHER_IMAGE=1), or -- the
-            # definition of the metric at N > 1 since round 5 -- the image in parts on the ranks that induced them (rounds 1-4 timed the
-            # all-gather to every rank as well: SCALE records of r01-r04 and of r05 on are not comparable)
-            "image_layout": "parts" if keep_parts else "whole",
-            "roofline": roofline, "cpu_baseline": cpu, "image": image, "cli_end_to_end": cli_e2e,
+        out = result_line(roofline, cpu, cli_e2e)
+        out.update({
+            "image": image, "cli_end_to_end": cli_e2e,
             "roofline_groups": groups, "pass_efficiency": pass_eff[:12],
             "stage_seconds": {k: round(v, 5) for k, v in cnt.items() if k.startswith("t_")},
             "top_sites": top, "rounds": nr,
@@ -607,16 +694,8 @@ def main():
             "kernel_ms_total": round(total_kernel_ms, 3),
             "device_memory": {"peak_live_bytes": mem["peak_live_bytes"], "reserved_bytes": mem["reserved_bytes"]},
             "idx_bytes": cnt["idx_bytes"], "extra_configs1_101MB": extra,
-            # per-GPU view of the same run (the collection is fixed, so this is NOT a weak-scaling measurement: a rank's work
-            # includes the replicated parts of the dictionary stage, which do not shrink with N)
-            "per_gpu": {"shard_bytes_rank0": n_bytes, "value_per_gpu": round(value / world, 3)},
-        }
-        out["devices"] = devices
-        out["distinct_devices"] = len({d.get("uuid") or d.get("pci_bus_id") or (d["local_rank"], d["hip_device"]) for d in devices})
-        if comm is not None:     # totals over warmup + timed + profile steps on rank 0
-            nsteps = max(1, args.warmup + args.steps)
-            out["collectives_per_step"] = {"allgather": comm_timed[0] // nsteps, "alltoallv": comm_timed[1] // nsteps,
-                                           "bytes": comm_timed[2] // nsteps, "ms_in_callbacks": round(comm_timed[3] / nsteps * 1e3, 3)}
+        })
+        if comm is not None:
             # the sharded result against a single-GPU build of the WHOLE collection on this rank (outside the timed region;
             # the other ranks wait at the final barrier): the .rl_bwt images must be the same bytes
             if os.environ.get("GRLBWT_BENCH_VERIFY", "1") != "0":
@@ -634,15 +713,7 @@ def main():
                     del full
                 except Exception as e:        # (memory on a smaller device, ...): reported, never fatal for the measurement
                     out["sharded_image_equals_single_gpu"] = "not checked: %r" % (e,)
-    try:
-        ctx.close()
-    except Exception:
-        pass
-    if dist is not None:
-        dist.barrier()
-        dist.destroy_process_group()
-    if rank == 0:
-        os.write(result_fd, (json.dumps(out) + "\n").encode())
+    finish(out)
 
 
 if __name__ == "__main__":

@@ -70,3 +70,47 @@ def test_traffic_groups_against_the_committed_pmc_summary():
              if "prim::k_" in n and not any(f in n for fr in b.GROUP_KERNELS.values() for f in fr)
              and not any(s in n for s in ("k_reduce", "k_scan_tile", "k_pack_records", "k_byte_hist", "k_rs_chunk_sums", "k_rs_tile_offsets", "DictMetaInitFn", "DiffFn", "PackPhraseInfoFn", "ClaimSlotsFn"))]
     assert all(bytes_ < 5e9 for bytes_, _ in loose), sorted(loose, reverse=True)[:5]
+
+
+def test_dump_outputs_cover_the_image(tmp_path):
+    """--dump-outputs: float arrays of at most 64 MB whatever the image's size, the same for the same image, every byte in the
+    block sums and the header in the sample (host tensors stand in for the image in HBM)."""
+    import numpy as np
+    import torch
+    b = load_bench()
+
+    class Ctx:
+        def __init__(self, a):
+            self.a = a
+
+        def result_size(self):
+            return self.a.size, 7
+
+        def result_part(self):
+            return 0, self.a.size
+
+        def result_device_ptr(self):
+            return self.a.ctypes.data
+
+    for n in (0, 100000, 9 * (1 << 20) + 7):
+        a = np.random.default_rng(n).integers(0, 256, n, dtype=np.uint8)
+        d1, d2 = tmp_path / ("a%d" % n), tmp_path / ("b%d" % n)
+        b.dump_outputs(str(d1), Ctx(a), torch.device("cpu"))
+        b.dump_outputs(str(d2), Ctx(a), torch.device("cpu"))
+        files = sorted(os.listdir(d1))
+        assert files == ["image_block_sums.npy", "image_sample.npy", "image_size.npy"]
+        assert sum(os.path.getsize(d1 / f) for f in files) <= 64 << 20
+        got = {f: np.load(d1 / f) for f in files}
+        assert all(g.dtype in (np.float32, np.float64) for g in got.values())
+        assert all(np.array_equal(got[f], np.load(d2 / f)) for f in files)
+        assert list(got["image_size.npy"]) == [n, 7, 0, n]
+        blk = max(1, -(-n // b.DUMP_SUM_BLOCKS))
+        rows = np.zeros(b.DUMP_SUM_BLOCKS * blk, np.int64)
+        rows[:n] = a
+        rows = rows.reshape(b.DUMP_SUM_BLOCKS, blk)
+        assert np.array_equal(got["image_block_sums.npy"], np.stack([rows.sum(1), (rows * (np.arange(blk) % 255 + 1)).sum(1)], 1))
+        sample = got["image_sample.npy"]
+        if n <= b.DUMP_SAMPLE_BLOCKS * b.DUMP_BLOCK:
+            assert np.array_equal(sample, a)
+        else:
+            assert sample.size == b.DUMP_SAMPLE_BLOCKS * b.DUMP_BLOCK and np.array_equal(sample[:b.DUMP_BLOCK], a[:b.DUMP_BLOCK])

@@ -12,7 +12,7 @@ for v in "$@"; do
     if [[ $rest == dev:* ]]; then rest=${rest#dev:}; envs+=("GRLBWT_HIP_LIB=$R/tools/_build/libgrlbwt_dev.so"); fi
     IFS=',' read -ra kv <<< "$rest"
     for e in "${kv[@]}"; do [[ -n $e ]] && envs+=("$e"); done
-    env "${envs[@]}" GRLBWT_BENCH_DETAIL=2 python3 "$R/bench.py" --steps ${STEPS:-3} --warmup 1 --no-cpu-baseline --no-cli --no-extra > "$OUT/bench_$name.json" 2> "$OUT/sites_$name.txt"
+    env "${envs[@]}" GRLBWT_BENCH_DETAIL=2 python3 "$R/bench.py" --full --steps ${STEPS:-3} --warmup 1 --no-cpu-baseline --no-cli --no-extra > "$OUT/bench_$name.json" 2> "$OUT/sites_$name.txt"
     python3 - "$OUT/bench_$name.json" "$name" <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))
