@@ -30,8 +30,10 @@ struct grlbwt_ctx {
 
 namespace {
 
+// Every C-API call that runs engine or primitive work goes through here: it takes the switch snapshot the call runs with.
 template <class Fn>
 int guarded(grlbwt_ctx *ctx, Fn fn) {
+    prim::take_switches();
     try {
         fn();
         return GRLBWT_OK;
@@ -161,12 +163,10 @@ constexpr uint64_t kIoChunk = (uint64_t)64 << 20;
 constexpr int kIoBufs = 3;
 // reader / writer threads per chunk: page-cache copies run at about 2 GB/s per thread (GRLBWT_IO_THREADS overrides)
 int io_threads() {
-    static const int n = [] {
-        if (const char *e = getenv("GRLBWT_IO_THREADS")) { int v = atoi(e); if (v >= 1 && v <= 64) return v; }
-        const unsigned hc = std::thread::hardware_concurrency();
-        return (int)std::min<unsigned>(std::max<unsigned>(hc / 2, 4u), 16u);      // (pread from the page cache: 99 GB/s with 8 threads, 118 with 16, 97 with 32 on a 256-core host)
-    }();
-    return n;
+    const int v = prim::sw().io_threads;
+    if (v >= 1 && v <= 64) return v;
+    const unsigned hc = std::thread::hardware_concurrency();
+    return (int)std::min<unsigned>(std::max<unsigned>(hc / 2, 4u), 16u);      // (pread from the page cache: 99 GB/s with 8 threads, 118 with 16, 97 with 32 on a 256-core host)
 }
 
 // file -> HBM: chunk k+1 is read from the file while chunk k travels over PCIe; for byte cells the histogram of
@@ -228,7 +228,7 @@ struct ReadPool {
     }
 };
 // GRLBWT_IO_TRACE=1: where the loader and the image writer spend their time (stderr)
-inline bool io_trace() { static const bool on = getenv("GRLBWT_IO_TRACE") != nullptr; return on; }
+inline bool io_trace() { return prim::init_sw().io_trace; }
 inline double io_now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 template <class E>
 void load_file_into(E &e, int fd, uint64_t base, uint64_t bytes, int w) {      // bytes [base, base + bytes) of the file
@@ -815,22 +815,21 @@ const char *grlbwt_last_error(const grlbwt_ctx *ctx) { return ctx ? ctx->err.c_s
 // The GRLBWT_* environment switches choose between forms of one computation (tests force most of them and compare the image
 // with the oracle: none changes the output) -- but several change what a run COSTS by integer factors (GRLBWT_NOPOOL,
 // GRLBWT_NO_PART, GRLBWT_DIST_REPLICATED_*).  A run that has any of them set says so, once per process, on stderr.
-// (GRLBWT_QUIET_ENV=1 silences the note: the test suites set switches on purpose.)
+// (GRLBWT_QUIET_ENV=1 silences the note: the test suites set switches on purpose.)  Named are the variables of switches.hpp.
 static void warn_env_switches_once() {
     static bool done = false;
     if (done) return;
     done = true;
-    if (getenv("GRLBWT_QUIET_ENV")) return;
+    if (prim::sw().quiet_env) return;
     extern char **environ;
     std::string names;
     int n = 0;
     for (char **e = environ; e && *e; e++) {
-        if (strncmp(*e, "GRLBWT_", 7) != 0) continue;
         const char *eq = strchr(*e, '=');
-        std::string name(*e, eq ? (size_t)(eq - *e) : strlen(*e));
-        // the bench's / tests' own bookkeeping variables are not switches of the library
-        if (name.rfind("GRLBWT_BENCH_", 0) == 0 || name == "GRLBWT_HIP_LIB" || name == "GRLBWT_E2E_TMP" || name == "GRLBWT_SIM_LIB") continue;
-        names += (n++ ? ", " : "") + name;
+        const std::string name(*e, eq ? (size_t)(eq - *e) : strlen(*e));
+        bool known = false;
+        prim::Switches::for_each_name([&](const char *sw_name) { known = known || name == sw_name; });
+        if (known) names += (n++ ? ", " : "") + name;
     }
     if (n) fprintf(stderr, "[grlbwt] note: %d GRLBWT_* switch%s set in the environment (%s): the image is the same, time and memory of this run may not be\n",
                    n, n == 1 ? "" : "es", names.c_str());
@@ -839,12 +838,12 @@ static void warn_env_switches_once() {
 int grlbwt_ctx_create(int device_id, uint32_t flags, grlbwt_ctx **out) {
     if (!out) return GRLBWT_EINVAL;
     *out = nullptr;
-    warn_env_switches_once();
     grlbwt_ctx *c = new (std::nothrow) grlbwt_ctx();
     if (!c) return GRLBWT_ENOMEM;
     c->flags = flags;
     c->device = device_id;
     int rc = guarded(c, [&] {
+        warn_env_switches_once();
         prim::init(device_id);            // refuses a second device while contexts are alive (one GPU per process)
         if (flags & GRLBWT_FLAG_CLASSIC_POOL) prim::pool_classic();
         if (flags & GRLBWT_FLAG_SYNC_DEBUG) prim::rt().sync_each_launch = true;

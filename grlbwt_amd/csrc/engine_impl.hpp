@@ -33,6 +33,8 @@
 // width, text_r (r>=1) as u32 cells  (rank<<2 | rep<<1 | is_terminator);
 // run-length BWTs as struct-of-arrays (u32 sym[], idx_t len[]).
 
+#include "switches.hpp"
+
 namespace GRL_NS {
 
 using prim::u8;
@@ -70,9 +72,9 @@ static inline unsigned bitlen64(u64 v) { return v == 0 ? 0 : 64 - (unsigned)__bu
 // Fault injection for the multi-rank failure-agreement tests (tests/test_dist_gloo.py): compiled into the serial test stand-in
 // only (prim::kIsDevice is false there).  The product library never reads these variables: no environment can make a
 // production rank throw "injected by the test".
-static inline bool test_fail_rank(const char *var, int me) {
-    if constexpr (prim::kIsDevice) { (void)var; (void)me; return false; }
-    else { const char *fr = getenv(var); return fr && atoi(fr) == me; }
+static inline bool test_fail_rank(int fail_rank, int me) {
+    if constexpr (prim::kIsDevice) { (void)fail_rank; (void)me; return false; }
+    else return fail_rank == me;
 }
 
 // ----------------------------------------------------------------- searches
@@ -1073,10 +1075,6 @@ struct SampleKey0Fn {     // keys at strided positions: the splitter sample of t
     const u32 *dict_sym; const u32 *dict_phr; const u32 *ph_off; int K, b; u64 stride; u64 *out; RunKeys rk;
     GRL_DEV void operator()(u64 i) const { const u64 q = i * stride; out[i] = suffix_key0(dict_sym, q, ph_off[dict_phr[q] + 1], K, b, rk); }
 };
-struct SampleWeightFn {   // ... and the frequency of the phrase each sampled suffix belongs to (splitters by symbols described, not by suffixes)
-    const u32 *dict_phr; const idx_t *ph_freq; u64 stride; u64 *out;
-    GRL_DEV void operator()(u64 i) const { out[i] = (u64)ph_freq[dict_phr[i * stride]]; }
-};
 struct PhraseDropIn {     // 1 for a phrase whose last-cell suffix is left out (one scan over the PHRASES then places every kept suffix)
     const u32 *ph_off; const u8 *ph_lastT; bool all = false;
     GRL_DEV u32 operator()(u64 k) const { return (!all && !ph_lastT[k] && ph_off[k + 1] - ph_off[k] > 1) ? 1u : 0u; }
@@ -1167,6 +1165,7 @@ struct FirstUnresolvedFn { // after the first sort: member of a group of > 1 suf
 // A group of at most kSegCap members is ordered by counting (every member counts the smaller keys of its group: the keys sit
 // in neighbouring words); larger groups take two stable radix sorts together, by key and then by group.
 static constexpr u32 kSegCap = 64;
+static_assert(prim::Switches{}.seg_cap == (int)kSegCap, "GRLBWT_SEG_CAP defaults to kSegCap");
 struct GroupStartsFn {    // gstart[dense group id] = head slot ; gstart[G] = S
     const u8 *hflag; const u32 *ex; u64 S; u32 *gstart;
     GRL_DEV void operator()(u64 t) const {
@@ -3181,15 +3180,14 @@ class Engine {
         // (prim::rec_dedupe), and the phrases' values travel back through the sort's passes in reverse (emit_local).  Only the
         // longer phrases (1 % at level 1, ~12 % at levels 2-3 of the 10 GB build) still go through the hash table below.
         // Round 2's table took 3 random HBM accesses per occurrence (probe, verification, count atomic: 51 / 51 / 18 G/s) and the
-        // emission a fourth; this path streams.  GRLBWT_NO_PART=1 switches it off; GRLBWT_PART_MIN_OCC sets the smallest level.
+        // emission a fourth; this path streams.  GRLBWT_PART_MIN_OCC sets the smallest level (GRLBWT_NO_PART=1, development builds: no partitions).
         int rec_b = 0;
         u32 rec_cmax = 0;
         bool part = false;
-        if (allow_part && !FIRST && sizeof(cell_t) == 4 && !prim::dev_env("GRLBWT_NO_PART")) {
+        if (allow_part && !FIRST && sizeof(cell_t) == 4 && !prim::sw().no_part) {
             rec_b = (int)bitlen64(L.sigma > 1 ? (u64)L.sigma - 1 : 1);
             rec_cmax = (u32)std::min<int>(7, 124 / rec_b);
-            const u64 min_occ = getenv("GRLBWT_PART_MIN_OCC") ? (u64)atoll(getenv("GRLBWT_PART_MIN_OCC")) : ((u64)1 << 20);
-            part = rec_cmax >= 2 && n_occ >= min_occ;
+            part = rec_cmax >= 2 && n_occ >= prim::sw().part_min_occ;
             if (!part) rec_cmax = 0;
         }
         int part_bits = 0;
@@ -3198,7 +3196,7 @@ class Engine {
             part_bits = 4;
             while (part_bits < 20 && (n_occ >> part_bits) > 5000) part_bits++;
             // (GRLBWT_PART_BITS: the tests make partitions too large for their table, to take the fallback on the device)
-            if (const char *pb = getenv("GRLBWT_PART_BITS")) part_bits = std::max(1, std::min(20, atoi(pb)));
+            if (prim::sw().part_bits) part_bits = std::max(1, std::min(20, prim::sw().part_bits));
         }
 
         // ---- a3: hash every phrase occurrence ------------------------------
@@ -3256,14 +3254,7 @@ class Engine {
                 cap = 4096;
                 while (cap < want) cap <<= 1;
                 if (cap > cap_max) cap = cap_max;
-                if (const char *ov = prim::dev_env("GRLBWT_TABLE_LOG2")) {      // experiments: "l0,l1,..." log2 of the slots per level (0 = keep)
-                    int lvl = prim::rt().tag, k = 0;
-                    const char *q = ov;
-                    while (k < lvl && *q) { if (*q == ',') k++; q++; }
-                    const int lg = (k == lvl) ? atoi(q) : 0;
-                    if (lg >= 10 && lg <= 40) cap = std::min<u64>((u64)1 << lg, cap_max);
-                }
-                if (getenv("GRLBWT_TABLE_TRACE")) fprintf(stderr, "[grlbwt] level %d: sample %llu occurrences, %llu distinct -> table %llu slots for %llu occurrences\n",
+                if (prim::sw().table_trace) fprintf(stderr, "[grlbwt] level %d: sample %llu occurrences, %llu distinct -> table %llu slots for %llu occurrences\n",
                                                           prim::rt().tag, (unsigned long long)occ_s, (unsigned long long)d_s, (unsigned long long)cap, (unsigned long long)n_occ);
             }
         }
@@ -3273,7 +3264,7 @@ class Engine {
         // LDS pre-aggregation of the counts pays when few distinct phrases take most occurrences (level 0 of
         // DNA: 20 k phrases, 30 M occurrences); with mostly-distinct phrases the cache only thrashes.
         // (GRLBWT_FORCE_DIRECT_INDEX=1: the tests take the direct index -- below -- on texts too small for a sample)
-        const bool force_direct = HashInsertFn<cell_t, FIRST>::kExact && !part && getenv("GRLBWT_FORCE_DIRECT_INDEX") != nullptr;
+        const bool force_direct = HashInsertFn<cell_t, FIRST>::kExact && !part && prim::sw().force_direct_index;
         const bool aggregate = frac < 0.25 || force_direct;
         // Table layout.  With few hot phrases the keys stay on lines of their own (the atomics on a hot count would keep
         // invalidating the key every probe reads: measured 4x slower interleaved).  With mostly-distinct phrases every
@@ -3293,7 +3284,7 @@ class Engine {
         bool direct = false;
         u32 dir_b[3] = {0, 0, 0};
         u64 sym_of_code = 0;
-        if (HashInsertFn<cell_t, FIRST>::kExact && aggregate && (s_n || force_direct) && !part && sym_present_known && !prim::test_env("GRLBWT_NO_DIRECT_INDEX")) {
+        if (HashInsertFn<cell_t, FIRST>::kExact && aggregate && (s_n || force_direct) && !part && sym_present_known && !prim::sw().no_direct_index) {
             int syms[256], ns = 0;
             for (int i = 0; i < 256; i++) if ((sym_present[i >> 6] >> (i & 63)) & 1ull) syms[ns++] = i;
             for (u32 a = 0; a < 8 && !direct && ns <= 8; a++) for (u32 b = a + 1; b < 8 && !direct; b++) for (u32 c = b + 1; c < 8 && !direct; c++) {
@@ -3321,15 +3312,15 @@ class Engine {
             cap_hot = HashInsertFn<cell_t, FIRST>::kDirectSlots;
             if (cap_max > (1ull << 30)) cap_max = 1ull << 30;             // slot ids of both regions stay below 2^31
             if (cap > cap_max) cap = cap_max;
-            if (getenv("GRLBWT_TABLE_TRACE")) fprintf(stderr, "[grlbwt] level %d: direct index on bits %u, %u, %u of a cell (%llu slots in front of the table)\n", prim::rt().tag,
+            if (prim::sw().table_trace) fprintf(stderr, "[grlbwt] level %d: direct index on bits %u, %u, %u of a cell (%llu slots in front of the table)\n", prim::rt().tag,
                                                       dir_b[0], dir_b[1], dir_b[2], (unsigned long long)cap_hot);
         } else
-        if (aggregate && s_n && !part && !prim::test_env("GRLBWT_NO_HOT_TABLE")) {
+        if (aggregate && s_n && !part && !prim::sw().no_hot_table) {
             cap_hot = 1024;
             while (cap_hot < 4 * s_distinct) cap_hot <<= 1;               // load <= 0.25: short probe chains
             if (cap_max > (1ull << 30)) cap_max = 1ull << 30;             // slot ids of both tables stay below 2^31
             if (cap > cap_max) cap = cap_max;
-            if (getenv("GRLBWT_TABLE_TRACE")) fprintf(stderr, "[grlbwt] level %d: hot table of %llu slots for the %llu phrases of the sample\n", prim::rt().tag,
+            if (prim::sw().table_trace) fprintf(stderr, "[grlbwt] level %d: hot table of %llu slots for the %llu phrases of the sample\n", prim::rt().tag,
                                                       (unsigned long long)cap_hot, (unsigned long long)s_distinct);
         }
         {
@@ -3363,7 +3354,7 @@ class Engine {
                     f.hot_keys = keys.p; f.hot_mask = cap_hot - 1; f.slot_base = (u32)cap_hot;
                 }
                 if constexpr (!FIRST) {
-                    if (part && !getenv("GRLBWT_PART_ONE_PASS")) {
+                    if (part && !prim::sw().part_one_pass) {
                         // the records by a lean streaming pass of their own, the long phrases from a list through the table
                         prim::dev_memset(P.next_text.p, 0, n_occ * sizeof(u32));
                         DBuf<u64> lbits(nwords + 1);
@@ -3387,7 +3378,7 @@ class Engine {
                         lbits.release(); lbase.release();
                         if (nl) prim::for_each_agg(nl, ListedFn<HF>{f, lpos.p, claim.p}, SlotCountAdd{cnt, cs}, false, "hash_long_phrases");
                     } else launch_hash<cell_t, FIRST>(f, cnt, cs, n, aggregate);
-                } else if (direct && n_occ < 0xFFFFFFF0ull && !prim::dev_env("GRLBWT_NO_NAME_STREAM")) {
+                } else if (direct && n_occ < 0xFFFFFFF0ull && !prim::sw().no_name_stream) {
                     // the direct index in a kernel of its own (prim::name_stream): what it cannot name -- phrases of more than 7 cells,
                     // the last cells of the text -- is marked and takes the general code from a list afterwards
                     DBuf<u64> lbits(nwords + 1);
@@ -3441,7 +3432,7 @@ class Engine {
             if (ovf.get(0)) {
                 // a partition with more distinct phrases than its LDS table takes (or an injected limit in the tests): this level
                 // goes through the hash table after all
-                if (getenv("GRLBWT_TABLE_TRACE")) fprintf(stderr, "[grlbwt] level %d: a phrase partition overflowed, falling back to the hash table\n", prim::rt().tag);
+                if (prim::sw().table_trace) fprintf(stderr, "[grlbwt] level %d: a phrase partition overflowed, falling back to the hash table\n", prim::rt().tag);
                 L.info.table_retries++;
                 skey.release(); shi.release(); dkey.release(); dhi.release(); keys.release(); counts.release(); rep_pos.release(); claim.release();
                 startbits.release(); wordbase.release(); dcnt.release();
@@ -3540,7 +3531,7 @@ class Engine {
         // count matrix): blocks above the limit go in several rounds, the same number on every rank.  (torch 2.10 + RCCL
         // 2.26 delivers HALF of an all-to-all block of 2 GB, silently, and is fine at 1 GiB: tools/gpu_rccl_sizes.py.)
         void alltoall(const void *send, const std::vector<u64> &scnt, void *recv, const std::vector<u64> &rcnt, u64 elem, u64 max_block) const {
-            static const u64 limit = prim::test_env("GRLBWT_A2A_BLOCK") ? (u64)atoll(prim::test_env("GRLBWT_A2A_BLOCK")) : ((u64)256 << 20);
+            const u64 limit = prim::sw().a2a_block;
             const u64 per = std::max<u64>(limit / elem, 1);
             const u64 rounds = std::max<u64>((max_block + per - 1) / per, 1);
             std::vector<u64> sb(size), so(size), rb(size), ro(size), sbase(size + 1, 0), rbase(size + 1, 0);
@@ -3548,7 +3539,7 @@ class Engine {
             account((sbase[size] - scnt[rank]) * elem);
             // my own block never leaves the device: a plain copy (GRLBWT_A2A_SELF_VIA_COMM=1: through the callback like the
             // others -- the tests do that so that a one-rank RCCL run still moves data through RCCL)
-            static const bool self_via_comm = getenv("GRLBWT_A2A_SELF_VIA_COMM") != nullptr;
+            const bool self_via_comm = prim::sw().a2a_self_via_comm;
             if (!self_via_comm) {
                 if (scnt[rank] != rcnt[rank]) throw prim::Error(-71, "alltoallv: my own block has two sizes");
                 prim::d2d((char *)recv + rbase[rank] * elem, (const char *)send + sbase[rank] * elem, scnt[rank] * elem);
@@ -3582,10 +3573,10 @@ class Engine {
             account(count * sizeof(T) * (u64)(size - 1));
             DBuf<T> dense;
             if (!dest) { dense.alloc(base[size]); dest = dense.p; }
-            static const bool self_via_comm = getenv("GRLBWT_A2A_SELF_VIA_COMM") != nullptr;
+            const bool self_via_comm = prim::sw().a2a_self_via_comm;
             if (!self_via_comm || !a2a) prim::d2d(dest + base[rank], send, count * sizeof(T));
             if ((size == 1 && !self_via_comm) || !a2a) return dense;
-            static const u64 limit = prim::test_env("GRLBWT_A2A_BLOCK") ? (u64)atoll(prim::test_env("GRLBWT_A2A_BLOCK")) : ((u64)256 << 20);
+            const u64 limit = prim::sw().a2a_block;
             const u64 per = std::max<u64>(limit / sizeof(T), 1);
             u64 mx = 0;
             for (int g = 0; g < size; g++) mx = std::max(mx, base[g + 1] - base[g]);
@@ -3611,10 +3602,7 @@ class Engine {
     // (dsb = sbase[0..N] on the device); cnt[d] = records for rank d.
     // (own_of given: positions travel as (owner, offset in the owner's part) -- own_of[i] is record i's owner, the position field its
     // offset; that is how a dictionary of 2^32 symbols and more is addressed with 32-bit fields)
-    static u64 test_dict_part_pad() {
-        static const u64 pad = prim::test_env("GRLBWT_TEST_DICT_PART_PAD") ? (u64)atoll(prim::test_env("GRLBWT_TEST_DICT_PART_PAD")) : 0;
-        return pad;
-    }
+    static u64 test_dict_part_pad() { return prim::sw().test_dict_part_pad; }
     void bucket_by_owner(const Comm &C, const u64 *dsb, DBuf<u64> &rec, u64 n, std::vector<u64> &cnt, const char *name, DBuf<u32> *own_of = nullptr) {
         const int N = C.size;
         int obits = (int)bitlen64((u64)N - 1);
@@ -3686,11 +3674,11 @@ class Engine {
         // its (key, position) record in the sample-sort exchange: no round trip for them afterwards (24 bytes per suffix over the
         // fabric and a gather pass on the owner -- 3.3 GB and ~14 ms per rank at N = 8 of the 10 GB collection).  The values a rank
         // sorts are then ARRIVAL INDICES; pos_arr[] / rec_arr[] give the position and the record of an arrival.
-        static const bool rec_round_trip = prim::test_env("GRLBWT_DIST_REC_ROUND_TRIP") != nullptr;
+        const bool rec_round_trip = prim::sw().dist_rec_round_trip;
         const bool carry = sharded && maxfreq < 0xFFFFFFFFull && !rec_round_trip;
         // In this form a position is (owner, OFFSET in the owner's part): the owner of an arrival is the rank it came from (arrivals
         // sit in sender order), so 32-bit fields address a dictionary whose parts are each below 2^32 symbols, whatever their sum.
-        if (sharded && !carry && S >= 0xFFFFFFF0ull) throw prim::Error(-75, "dictionary too large (>= 2^32 symbols and a phrase frequency >= 2^32, or GRLBWT_DIST_REC_ROUND_TRIP)");
+        if (sharded && !carry && S >= 0xFFFFFFF0ull) throw prim::Error(-75, "dictionary too large (>= 2^32 symbols and a phrase frequency >= 2^32, or the records' round trip forced by a test)");
         const u64 sq = carry ? 0 : s0;           // what the owner subtracts from a position it is asked about
         DBuf<u32> pos_arr, perm_ai, pown;        // (carry) offset of every arrival; the sorted arrival indices once perm holds offsets again; owner by slot
         DBuf<u64> abounds;                       // (carry) arrivals [abounds[g], abounds[g + 1]) came from rank g
@@ -3720,19 +3708,19 @@ class Engine {
             // as many symbols as fit 64 key bits per pass (up to 8 radix passes over all suffixes in the first one)
             // run-aware keys (RunKeys) for levels with long phrases, i.e. long runs of one symbol (GRLBWT_RUN_KEYS_MIN: from which
             // phrase length on; the tests set 0)
-            static const u64 run_min = getenv("GRLBWT_RUN_KEYS_MIN") ? (u64)atoll(getenv("GRLBWT_RUN_KEYS_MIN")) : 512;
+            const u64 run_min = prim::sw().run_keys_min;
             RunKeys rk;
             DBuf<u32> run_rem, run_skip;
             if ((u64)maxlen >= run_min && S > 0) rk.rb = 1 + (int)bitlen64((u64)maxlen);
             // long phrases on one GPU: every suffix keeps its slot (no "last cell" suffixes left out), so that the refinement can
             // switch to doubling rounds (DoubleKeyFn) when the symbol extension does not finish in GRLBWT_DOUBLING_AFTER rounds
             const bool longmode = !C && (u64)maxlen >= run_min && S > 0;
-            static const u64 dbl_after = getenv("GRLBWT_DOUBLING_AFTER") ? (u64)atoll(getenv("GRLBWT_DOUBLING_AFTER")) : 24;
+            const u64 dbl_after = prim::sw().doubling_after;
             int K = (64 - rk.rb) / b;
             if (K < 1) K = 1;
             if (K > 16) K = 16;
             // (GRLBWT_SORT_KMAX: fewer symbols in the first sort's key -- fewer radix passes, more left to the refinement)
-            static const int kmax = prim::dev_env("GRLBWT_SORT_KMAX") ? atoi(prim::dev_env("GRLBWT_SORT_KMAX")) : 16;
+            const int kmax = prim::sw().sort_kmax;
             if (kmax >= 1 && K > kmax) K = kmax;
             if ((u64)K > (u64)maxlen + 1) K = (int)maxlen + 1;
             if (rk.rb && K * b + rk.rb > 64) rk.rb = 0;                     // (symbols too wide to share a key with a run field: plain keys)
@@ -3747,7 +3735,7 @@ class Engine {
             const int kbits = K * b + rk.rb;                                // sort bits of a key
             const u64 sent = ((1ull << b) - 1ull) << rk.rb;                 // (the last symbol of a key's window: all ones = the phrase has ended)
             // (GRLBWT_SEG_CAP: the tests lower the limit so that ordinary inputs take the large-group path too)
-            static const u32 cap = getenv("GRLBWT_SEG_CAP") ? (u32)atoi(getenv("GRLBWT_SEG_CAP")) : kSegCap;
+            const u32 cap = (u32)prim::sw().seg_cap;
             DBuf<u64> ka;
             {
                 const SufKeep keep{dict_phr.p, ph_off, ph_lastT, longmode};
@@ -3769,7 +3757,7 @@ class Engine {
                     // 4.6 GB over ONE xGMI link at level 2 of the 10 GB build, 40-75 ms -- to save 10 ms of key computation.  Below
                     // GRLBWT_SORT_EXCHANGE_MIN ranks (default 4) every rank looks at all S positions and keeps its own key range:
                     // two replicated streaming passes, nothing on the wire.
-                    static const int xmin = prim::test_env("GRLBWT_SORT_EXCHANGE_MIN") ? atoi(prim::test_env("GRLBWT_SORT_EXCHANGE_MIN")) : 4;
+                    const int xmin = prim::sw().sort_exchange_min;
                     const bool exchange = N >= xmin;
                     std::vector<u64> scnt(N, 0), rcnt(N, 0);
                     DBuf<u64> sk;
@@ -3777,36 +3765,19 @@ class Engine {
                     u64 Sown = 0;
                     try {
                         // (GRLBWT_TEST_FAIL_RANK_SORT=<rank>: the tests make one rank fail here)
-                        if (test_fail_rank("GRLBWT_TEST_FAIL_RANK_SORT", me)) throw prim::Error(-71, "suffix refinement does not terminate (injected by the test)");
+                        if (test_fail_rank(prim::sw().test_fail_rank_sort, me)) throw prim::Error(-71, "suffix refinement does not terminate (injected by the test)");
                         const u64 ns = S < 8192 ? S : 8192, stride = S / ns;
                         DBuf<u64> samp(ns), dspl(N);
                         prim::for_each(ns, SampleKey0Fn{dict_sym.p, dict_phr.p, ph_off, K, b, stride, samp.p, rk}, "dist.sample_keys");
                         std::vector<u64> hs = samp.to_host(ns), spl(N, 0);
                         // A key range is also the rank's piece of the level's OUTPUT (the pre-BWT stays where it was sorted, round 5).
                         // Where the dictionary is small against the text -- level 0 of read collections: 10^6 suffixes for 10^10 symbols --
-                        // the dictionary stage costs nothing and the induction everything: the splitters then cut the sample by the
-                        // symbols its suffixes stand for (phrase frequencies), not by their number.  Measured on the 10 GB collection at
+                        // the dictionary stage costs nothing and the induction everything.  Splitters that cut the sample by the symbols
+                        // its suffixes stand for (phrase frequencies), not by their number, were measured on the 10 GB collection at
                         // N = 8 (profiles/r05): pass C of a piece costs by its cells and runs, not by its symbols -- slowest / fastest rank of
-                        // the induction 55 / 35 ms by count, 55 / 32 ms by mass, largest image part 1.9 -> 2.5 GB: left off.
-                        if (S * 16 < L.info.n_in && prim::dev_env("GRLBWT_DIST_SPLIT_BY_MASS")) {      // (opt-in: measured no better -- see below)
-                            DBuf<u64> sw(ns);
-                            prim::for_each(ns, SampleWeightFn{dict_phr.p, ph_freq, stride, sw.p}, "dist.sample_keys");
-                            std::vector<u64> hw = sw.to_host(ns);
-                            std::vector<std::pair<u64, u64>> kw(ns);
-                            u64 tot = 0;
-                            for (u64 i = 0; i < ns; i++) { kw[i] = {hs[i], hw[i]}; tot += hw[i]; }
-                            std::sort(kw.begin(), kw.end());
-                            u64 acc = 0;
-                            int d = 1;
-                            for (u64 i = 0; i < ns && d < N; i++) {
-                                while (d < N && acc >= tot / (u64)N * (u64)d) { spl[d] = kw[i].first; d++; }
-                                acc += kw[i].second;
-                            }
-                            for (; d < N; d++) spl[d] = ~0ull;                             // (nothing left for the last ranks)
-                        } else {
+                        // the induction 55 / 35 ms by count, 55 / 32 ms by mass, largest image part 1.9 -> 2.5 GB: not adopted, by count.
                         std::sort(hs.begin(), hs.end());
                         for (int d = 1; d < N; d++) spl[d] = hs[(u64)d * ns / N];          // rank d owns keys in [spl[d], spl[d + 1])
-                        }
                         prim::h2d(dspl.p, spl.data(), (u64)N * 8);
                         if (!exchange) {
                             DBuf<u8> mine(S);
@@ -3943,19 +3914,19 @@ class Engine {
             int K = 64 / b;
             if (K < 1) K = 1;
             if (K > 16) K = 16;
-            static const int kmax = prim::dev_env("GRLBWT_SORT_KMAX") ? atoi(prim::dev_env("GRLBWT_SORT_KMAX")) : 16;
+            const int kmax = prim::sw().sort_kmax;
             if (kmax >= 1 && K > kmax) K = kmax;
             if ((u64)K > (u64)maxlen + 1) K = (int)maxlen + 1;
             const int kbits = K * b;
             const u64 sent = (1ull << b) - 1ull;
-            static const u32 cap = getenv("GRLBWT_SEG_CAP") ? (u32)atoi(getenv("GRLBWT_SEG_CAP")) : kSegCap;
+            const u32 cap = (u32)prim::sw().seg_cap;
             const SufKeep keep{dict_phr.p, ph_off, ph_lastT, false};
             // splitters from a sample every rank takes of its own part
             u64 nsl = 0;
             DBuf<u64> samp;
             local([&] {
                 // (GRLBWT_TEST_FAIL_RANK_SORT=<rank>: the tests make one rank fail here)
-                if (test_fail_rank("GRLBWT_TEST_FAIL_RANK_SORT", me)) throw prim::Error(-71, "suffix refinement does not terminate (injected by the test)");
+                if (test_fail_rank(prim::sw().test_fail_rank_sort, me)) throw prim::Error(-71, "suffix refinement does not terminate (injected by the test)");
                 nsl = Sl < 64 ? Sl : std::max<u64>(64, 8192 / (u64)N);
                 if (nsl > Sl) nsl = Sl;
                 samp.alloc(nsl);
@@ -4137,7 +4108,7 @@ class Engine {
             if (fused_vals || carry) gphr.alloc(G); else pslot.alloc(D);      // (carry: gphr[g] = slot of the group's whole-phrase member)
             if (C && !carry) pslot.fill_ff();    // (sharded: phrases whose whole-phrase suffix sorted elsewhere keep the mark)
             {
-                static const int fly_min = prim::test_env("GRLBWT_DIST_REC_FLY_MIN") ? atoi(prim::test_env("GRLBWT_DIST_REC_FLY_MIN")) : 8;
+                const int fly_min = prim::sw().dist_rec_fly_min;
                 const bool fly = C && C->size >= fly_min;
                 DBuf<SufRec> rec;
                 DBuf<u32> coff(G + 1);
@@ -4204,7 +4175,7 @@ class Engine {
             // 8.9 GB sent per rank of the 10 GB collection at N = 2, 17.8 GB received at any N -- and every rank merged and
             // scanned the WHOLE pre-BWT; GRLBWT_DIST_REPLICATED_PREBWT=1 keeps that form.)  Runs are merged inside a piece
             // only: a run cut by a piece boundary stays two runs, which describe the same symbols.
-            static const bool replicated_pre = prim::test_env("GRLBWT_DIST_REPLICATED_PREBWT") != nullptr || prim::test_env("GRLBWT_DIST_REPLICATED_INDUCTION") != nullptr;      // (the replicated induction wants the whole pre-BWT)
+            const bool replicated_pre = prim::sw().dist_replicated_prebwt || prim::sw().dist_replicated_induction;      // (the replicated induction wants the whole pre-BWT)
             const bool pre_local = C && !replicated_pre;
             prim::for_each(G, GroupEmitFn{gflag.p, grank.p, pidx.p, gmin.p, gacc.p, gstart.p, carry ? nullptr : perm.p, bwt_code, hocc_code, pre_local ? 0u : (u32)Moff,
                                           pre_local ? 0u : (u32)P0off, psym0.p, plen0.p, L.has_hocc.p, repq.p, u_to_p0.p, pu0.p}, "prebwt_emit");
@@ -4232,7 +4203,7 @@ class Engine {
             {
                 DBuf<u32> ginfo(G);
                 prim::for_each(G, PackGroupInfoFn{grank.p, gflag.p, (u32)Moff, ginfo.p}, "grammar_ginfo");
-                static const bool replicated_grammar = prim::test_env("GRLBWT_DIST_REPLICATED_GRAMMAR") != nullptr;
+                const bool replicated_grammar = prim::sw().dist_replicated_grammar;
                 if (C && sbase && (!replicated_grammar || sharded)) {      // (a dictionary sharded by owner has no other form)
                     // Sharded by the owner of the dictionary position (round 5): I hold dm[] of MY part of the dictionary only.  The marks
                     // of my groups go to the owners of their positions, the walks of my metasymbols are done by the owners of their
@@ -4281,7 +4252,7 @@ class Engine {
                         prim::for_each(nmr, ApplyMetaPairsFn{mine.p, dm.p, s0}, "grammar_marks");
                         mine.release();
                         DBuf<u64> stops;             // (very long phrases only: the walks jump to their stops)
-                        if (maxlen >= 4096 || prim::test_env("GRLBWT_GRAMMAR_JUMP")) {
+                        if (maxlen >= 4096 || prim::sw().grammar_jump) {
                             stops.alloc((Sme + 63) / 64 + 1);
                             prim::for_each((Sme + 63) / 64, DmStopBitsFn{dm.p, Sme, stops.p}, "grammar_marks");
                         }
@@ -4307,7 +4278,7 @@ class Engine {
                     prim::for_each(bb[C->size], ApplyMetaPairsFn{all.p, dm.p}, "grammar_marks");
                 }
                 DBuf<u64> stops;                 // (very long phrases only: the walks jump to their stops)
-                if (maxlen >= 4096 || prim::test_env("GRLBWT_GRAMMAR_JUMP")) {
+                if (maxlen >= 4096 || prim::sw().grammar_jump) {
                     stops.alloc((S + 63) / 64 + 1);
                     prim::for_each((S + 63) / 64, DmStopBitsFn{dm.p, S, stops.p}, "grammar_marks");
                 }
@@ -4544,13 +4515,13 @@ class Engine {
             // Whenever bucket, run length and symbol fit 64 bits together (always at DNA scales), the cell IS the sort
             // key: the split moves 8 bytes per cell and pass instead of 12, and holds 16 instead of 24 bytes per cell.
             // (GRLBWT_CELL_LAYOUT=packed|separate: the tests take the wider layouts on inputs that would never need them)
-            const char *force = getenv("GRLBWT_CELL_LAYOUT");
+            const char force = prim::sw().cell_layout;
             const bool fused = kb + lb + sbits <= 64 && !force;
-            const bool cell32 = fused && kb + lb + sbits <= 32 && kb < 32 && !getenv("GRLBWT_NO_CELL32");
-            if (getenv("GRLBWT_TABLE_TRACE")) fprintf(stderr, "[grlbwt] induction level %d: %llu runs, longest %llu, cell bits: bucket %d + length %d + symbol %d\n",
+            const bool cell32 = fused && kb + lb + sbits <= 32 && kb < 32 && !prim::sw().no_cell32;
+            if (prim::sw().table_trace) fprintf(stderr, "[grlbwt] induction level %d: %llu runs, longest %llu, cell bits: bucket %d + length %d + symbol %d\n",
                                                       prim::rt().tag, (unsigned long long)R, (unsigned long long)maxrun, kb, lb, sbits);
             // otherwise the payload (sym, len) rides through the split as one u64 whenever every run length fits 32 bits
-            const bool packed = !fused && maxrun < 0xFFFFFFFFull && !(force && force[0] == 's');
+            const bool packed = !fused && maxrun < 0xFFFFFFFFull && force != 's';
             bool done = false;
             if (fused) {
                 // chain expansion fused with the first pass of the bucket split (prim::expand_*): the cells are never
@@ -4773,8 +4744,8 @@ class Engine {
         // with tiles of 2048 (GRLBWT_DEV_SM1_SPT=8) -- and needs 12 bytes per SEGMENT of upper-bound arrays (32 GB at level 0 of the
         // 10 GB build, where the runs take 20): the two-pass form stays.
         // (GRLBWT_ASM_ONE_WALK=1: the tests take the one-walk form at every level, plain or not)
-        const bool two_pass = getenv("GRLBWT_ASM_TWO_PASS") != nullptr;
-        const bool plain_too = getenv("GRLBWT_ASM_ONE_WALK") != nullptr;
+        const bool two_pass = prim::sw().asm_two_pass;
+        const bool plain_too = prim::sw().asm_one_walk;
         const bool mostly_plain = NH * 64 < G;
         bool done = false;
         if (!two_pass && (!mostly_plain || plain_too)) {
@@ -4789,7 +4760,7 @@ class Engine {
                 out.sym.shrink(Ro); out.pos.shrink(Ro + 1);
             } else {
                 out.sym.release(); out.pos.release();
-                if (getenv("GRLBWT_TABLE_TRACE")) fprintf(stderr, "[grlbwt] level %d: the one-walk form of pass C gave up, taking count + emit\n", r);
+                if (prim::sw().table_trace) fprintf(stderr, "[grlbwt] level %d: the one-walk form of pass C gave up, taking count + emit\n", r);
             }
         }
         if (!done) {
@@ -4910,9 +4881,9 @@ class Engine {
             // counts: Comm::fail)
             try {
                 // (GRLBWT_TEST_FAIL_RANK=<rank>: the tests make one rank fail here)
-                if (test_fail_rank("GRLBWT_TEST_FAIL_RANK", me)) throw prim::Error(-28, "phrase hash table overflow (injected by the test)");
+                if (test_fail_rank(prim::sw().test_fail_rank, me)) throw prim::Error(-28, "phrase hash table overflow (injected by the test)");
                 // (levels above 0: partitioned naming as on one GPU -- short phrases are records in P.ph_key, not text positions)
-                hash_local<cell_t, FIRST>(t, n, ops, P, L, !prim::dev_env("GRLBWT_DIST_NO_PART"));
+                hash_local<cell_t, FIRST>(t, n, ops, P, L, !prim::sw().dist_no_part);
                 if (P.n_occ >= 0xFFFFFFF0ull) throw prim::Error(-75, "a shard's parse has >= 2^32 phrases (its frequencies travel as u32): use more ranks");
                 DBuf<u32> owner(P.D), owner2(P.D), idx(P.D), idx2(P.D), soff(P.D + 1);
                 DBuf<u64> bound(2 * ((u64)N + 1));
@@ -4980,7 +4951,7 @@ class Engine {
             DBuf<u64> goff, o_pos; DBuf<idx_t> o_freq; DBuf<u32> o_len, o_off; DBuf<u8> o_lastT;
             try {
                 // (GRLBWT_TEST_FAIL_RANK_MERGE=<rank>: the tests make one rank fail here)
-                if (test_fail_rank("GRLBWT_TEST_FAIL_RANK_MERGE", me)) throw prim::Error(-28, "merged phrase table overflow (injected by the test)");
+                if (test_fail_rank(prim::sw().test_fail_rank_merge, me)) throw prim::Error(-28, "merged phrase table overflow (injected by the test)");
                 goff.alloc(Dr + 1);
                 const u64 chk = prim::exclusive_scan<u64>(Dr, LenIn{rlen.p}, goff.p, true, "dist.list_offsets");
                 if (chk != Sr) throw prim::Error(-71, "dictionary exchange: cell count mismatch");
@@ -5039,13 +5010,13 @@ class Engine {
                 u64 mx = 0, fs = 0;
                 for (int g = 0; g < N; g++) { mx = std::max(mx, mf[3 * g]); fs += mf[3 * g + 1]; maxfreq = std::max(maxfreq, mf[3 * g + 2]); }
                 if (fs != occ_total) throw prim::Error(-71, "merged phrase frequencies do not add up to the global parse size");
-                static const u64 run_min = getenv("GRLBWT_RUN_KEYS_MIN") ? (u64)atoll(getenv("GRLBWT_RUN_KEYS_MIN")) : 512;
-                static const bool gathered = getenv("GRLBWT_DIST_GATHERED_DICT") != nullptr || prim::test_env("GRLBWT_DIST_REPLICATED_DICT") != nullptr;
+                const u64 run_min = prim::sw().run_keys_min;
+                const bool gathered = prim::sw().dist_gathered_dict || prim::sw().dist_replicated_dict;
                 // (GRLBWT_DIST_SHARDED_DICT_MIN=<ranks>: from how many ranks on -- see the figures in DESIGN.md section 6)
-                static const int sd_min = getenv("GRLBWT_DIST_SHARDED_DICT_MIN") ? atoi(getenv("GRLBWT_DIST_SHARDED_DICT_MIN")) : 4;
+                const int sd_min = prim::sw().dist_sharded_dict_min;
                 // (... and from how many dictionary symbols on: a small dictionary's all-gather costs less than the collectives of the
                 // refinement rounds -- the 1 GB collection at N = 8: 35.7 ms gathered, 40.3 ms sharded, 216 vs 349 collectives)
-                static const u64 sd_syms = getenv("GRLBWT_DIST_SHARDED_DICT_MIN_SYMS") ? (u64)atoll(getenv("GRLBWT_DIST_SHARDED_DICT_MIN_SYMS")) : ((u64)1 << 27);
+                const u64 sd_syms = prim::sw().dist_sharded_dict_min_syms;
                 if (!gathered && mx < run_min && ((N >= sd_min && sbase[N] >= sd_syms) || wide_dict)) {
                     sharded_dict = true;
                     maxlen = (u32)mx;
@@ -5081,7 +5052,7 @@ class Engine {
         }
         // ---- dictionary stage: suffix sort + group stage sharded by key range, grammar passes and dictionary by owner ----
         DBuf<u32> gval;
-        dict_stage<u32, false>(prim::test_env("GRLBWT_DIST_REPLICATED_DICT") ? nullptr : &C, gcells.p, CellOps<u32, false>{0u}, D, S, maxlen, ph_pos.p, ph_freq.p,
+        dict_stage<u32, false>(prim::sw().dist_replicated_dict ? nullptr : &C, gcells.p, CellOps<u32, false>{0u}, D, S, maxlen, ph_pos.p, ph_freq.p,
                                ph_off.p, ph_lastT.p, sigma, L, gval, nullptr, nullptr, nullptr, 0, 0, 0, &dbase, &sbase, sharded_dict, maxfreq);
         // ---- back to the shards: the value of every phrase I merged returns to its sender, in the order it came ----
         DBuf<u32> lval(P.D);
@@ -5201,7 +5172,7 @@ class Engine {
             term.alloc(R);
             split.alloc(4 * ((u64)N + 1));
             // (GRLBWT_TEST_FAIL_RANK_INDUCE=<rank>: the tests make one rank fail here)
-            if (test_fail_rank("GRLBWT_TEST_FAIL_RANK_INDUCE", me)) throw prim::Error(-12, "out of device memory (injected by the test)");
+            if (test_fail_rank(prim::sw().test_fail_rank_induce, me)) throw prim::Error(-12, "out of device memory (injected by the test)");
             E = expand_split(L, term, maxrun, kb, lb);
             I.E = E;
             StageTimer st(&tm.ind_assemble, "ind_assemble");
@@ -5302,7 +5273,7 @@ class Engine {
                 for (int g = 0; g < N; g++) for (int d = 0; d < N; d++) maxc = std::max(maxc, mat[(u64)g * 2 * N + d]);
                 const int bits = kb;
                 // (the received blocks are bucket-sorted: merged by block offsets; GRLBWT_MERGE_CELLS=sort keeps the stable radix sort)
-                static const bool merge_by_blocks = !(prim::test_env("GRLBWT_MERGE_CELLS") && prim::test_env("GRLBWT_MERGE_CELLS")[0] == 's');
+                const bool merge_by_blocks = prim::sw().merge_cells != 's';
                 const u32 mu0 = (u32)sp[4 * me + 1], mu1 = (u32)sp[4 * (me + 1) + 1];
                 if (c_sfused32.p) {
                     DBuf<u32> rf(Er);
@@ -5478,7 +5449,7 @@ class Engine {
     void dist_build(const Comm &C) {
         dist_stats(C);
         while (!dist_parse_round(C)) {}
-        if (prim::test_env("GRLBWT_DIST_REPLICATED_INDUCTION")) dist_induce_replicated(C);
+        if (prim::sw().dist_replicated_induction) dist_induce_replicated(C);
         else dist_induce(C);
     }
 
@@ -5604,7 +5575,7 @@ class Engine {
         // run) otherwise -- the 10 GB headline image needs 360 GB in the first form and ~100 GB in the second.
         // GRLBWT_INVERT=runs|positions forces one (the tests take both on small inputs).
         bool by_runs = (n_total_hint ? n_total_hint : capacity_cells) * (12 + 3 * (u64)sizeof(idx_t)) > prim::mem_available() / 2;
-        if (const char *f = getenv("GRLBWT_INVERT")) by_runs = f[0] == 'r';
+        if (prim::sw().invert) by_runs = prim::sw().invert == 'r';
         if (by_runs) {
             switch (cell_bytes) {
                 case 1: return invert_runs_t<u8>(img, R, (u32)sb, (u32)fb, (u8 *)dev_text_out, capacity_cells);

@@ -21,6 +21,9 @@
 #include <utility>
 #include <type_traits>
 
+#define GRLBWT_PRIM_HIP 1        // (the device library: switches.hpp leaves the test tier out; capi_impl.hpp: the in-library RCCL transport)
+#include "switches.hpp"
+
 #define GRL_HD __host__ __device__ __forceinline__
 #define GRL_DEV __device__ __forceinline__
 
@@ -32,7 +35,6 @@ typedef uint32_t u32;
 typedef uint64_t u64;
 
 static constexpr bool kIsDevice = true;
-#define GRLBWT_PRIM_HIP 1        // (capi_impl.hpp: the in-library RCCL transport exists in this build only)
 
 struct Error : std::runtime_error {
     int code;
@@ -47,21 +49,6 @@ struct Error : std::runtime_error {
                                       " at " + __FILE__ + ":" + std::to_string(__LINE__));  \
     } while (0)
 
-// Experiment switches (tile shapes, alternative kernels measured against each other) exist in DEVELOPMENT builds only:
-// tools/build_dev.sh compiles the library with -DGRLBWT_DEV_SWITCHES into tools/_build/ (bench.py takes it through
-// GRLBWT_HIP_LIB).  The product library reads none of them -- dev_env() is a constant there and the names do not reach the binary.
-inline const char *dev_env(const char *name) {
-#ifdef GRLBWT_DEV_SWITCHES
-    return getenv(name);
-#else
-    (void)name;
-    return nullptr;
-#endif
-}
-// Switches that only the CPU test suites set -- older forms of the collection-level flow kept as references for the multi-rank
-// tests, limits lowered so that small inputs take a branch -- are read by the serial test stand-in of this header alone
-// (tests/hostsim/prim_sim.hpp returns getenv there).  The device library never looks at them.
-inline const char *test_env(const char *) { return nullptr; }
 
 // ---------------------------------------------------------------- runtime state
 struct Runtime {
@@ -109,7 +96,7 @@ inline void init(int device) {
     hipDeviceProp_t p;
     GRL_HIP_CHECK(hipGetDeviceProperties(&p, device));
     R.device = device;
-    if (const char *t = getenv("GRLBWT_TRACE")) { R.trace = t[0] == '1'; R.sync_each_launch = R.trace; }
+    if (const char t = init_sw().trace) { R.trace = t == '1'; R.sync_each_launch = R.trace; }
     R.num_cus = p.multiProcessorCount > 0 ? p.multiProcessorCount : 256;
     if (!R.stream) {
         if (!R.own_stream) GRL_HIP_CHECK(hipStreamCreateWithFlags(&R.own_stream, hipStreamNonBlocking));
@@ -124,7 +111,7 @@ inline void sync() {
     if (!rt().stages.empty()) stages_collect();
     if (rt().profile) {
         // (the last launch name is read before prof_collect() empties the pending list)
-        static const bool by_site = getenv("GRLBWT_SYNC_SITES") != nullptr;      // which launch sites the host waited behind
+        const bool by_site = init_sw().sync_sites;      // which launch sites the host waited behind
         std::string last = by_site && !rt().pending.empty() ? rt().pending.back().name : std::string();
         prof_collect();
         rt().prof["@host_sync"].launches += 1;    // how often the host waited for the stream (no kernel of that name)
@@ -256,8 +243,7 @@ inline u64 pool_stage_begin() {
 }
 inline void pool_stage_end(u64 old_peak, const void *stage_name) {
     Pool &P = pool();
-    static const bool trace = getenv("GRLBWT_MEM_TRACE") != nullptr;
-    if (trace) fprintf(stderr, "[grlbwt] stage %-12s %c%d: peak live %.2f GB (live at end %.2f GB)\n", (const char *)stage_name, rt().phase ? rt().phase : '-', rt().tag,
+    if (init_sw().mem_trace) fprintf(stderr, "[grlbwt] stage %-12s %c%d: peak live %.2f GB (live at end %.2f GB)\n", (const char *)stage_name, rt().phase ? rt().phase : '-', rt().tag,
                        P.peak_bytes / 1e9, P.live_bytes / 1e9);
     if (old_peak > P.peak_bytes) P.peak_bytes = old_peak;
 }
@@ -271,10 +257,7 @@ inline u64 mem_available() {
     const Pool &P = pool();
     return (u64)fr + (u64)(P.slab_bytes > P.live_bytes ? P.slab_bytes - P.live_bytes : 0);
 }
-inline bool pool_disabled() {
-    static int d = getenv("GRLBWT_NOPOOL") ? 1 : 0;
-    return d != 0;
-}
+inline bool pool_disabled() { return init_sw().nopool; }
 inline void pool_trim() {                    // give every fully free hipMalloc slab back to the runtime
     Pool &P = pool();
     // The arena stays mapped for the life of the process and is reused by the next context.  Returning its backing
@@ -296,7 +279,7 @@ inline void pool_trim() {                    // give every fully free hipMalloc 
 // ---- arena: reserve once, back on demand
 inline bool arena_create(Pool &P) {
     if (P.arena_state != 0) return P.arena_state > 0;
-    if (P.classic || getenv("GRLBWT_POOL_CLASSIC")) return false;
+    if (P.classic || init_sw().pool_classic) return false;
     P.arena_state = -1;
     size_t fr = 0, tot = 0;
     if (hipMemGetInfo(&fr, &tot) != hipSuccess || tot == 0) { (void)hipGetLastError(); return false; }
@@ -313,7 +296,7 @@ inline bool arena_create(Pool &P) {
 }
 // back at least `more` further bytes of the arena (slab 0); false when the device has no memory left for it
 struct PoolTrace {                            // GRLBWT_POOL_TRACE=1: what backing the arena cost this process, printed at exit
-    bool on = getenv("GRLBWT_POOL_TRACE") != nullptr;
+    bool on = init_sw().pool_trace;
     double grow_s = 0, malloc_s = 0;
     u64 grows = 0, grow_fail = 0, mallocs = 0, malloc_bytes = 0;
     ~PoolTrace() {
@@ -630,12 +613,13 @@ __global__ void __launch_bounds__(kBlock) k_for_each(u64 n, F f) {
 // first 5 are done and run at low occupancy.  GRLBWT_FOR_EACH_GRID=fixed keeps 8 per CU; =2x launches twice the resident number.)
 template <class F>
 inline unsigned grid_for_each(u64 n) {
-    static const int mode = dev_env("GRLBWT_FOR_EACH_GRID") ? (dev_env("GRLBWT_FOR_EACH_GRID")[0] == 'f' ? 0 : 2) : 1;
-    static const u64 per_cu = [] {
-        int occ = 0;
-        if (mode == 0 || hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_for_each<F>, kBlock, 0) != hipSuccess || occ < 1) { (void)hipGetLastError(); return (u64)8; }
-        return (u64)(occ >= 8 ? 8 : occ * mode);
+    const int mode = sw().for_each_grid ? (sw().for_each_grid == 'f' ? 0 : 2) : 1;
+    static const int occ = [] {
+        int o = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, k_for_each<F>, kBlock, 0) != hipSuccess || o < 1) { (void)hipGetLastError(); return 0; }
+        return o;
     }();
+    const u64 per_cu = mode == 0 || occ < 1 ? (u64)8 : (u64)(occ >= 8 ? 8 : occ * mode);
     u64 blocks = (n + kBlock - 1) / kBlock;
     const u64 cap = (u64)rt().num_cus * per_cu;
     if (blocks > cap) blocks = cap;
@@ -1209,8 +1193,6 @@ __global__ void __launch_bounds__(kBlock) k_name_stream(u64 n, u64 per_block, F 
 // 29.3 at 12 (tools/_build sweep, 10 GB build).  (GRLBWT_SPAN_BLOCKS_PER_CU overrides.)
 template <class K>
 inline u64 span_blocks_per_cu(K kernel, int threads) {
-    static const u64 forced = dev_env("GRLBWT_SPAN_BLOCKS_PER_CU") ? (u64)atoll(dev_env("GRLBWT_SPAN_BLOCKS_PER_CU")) : 0;
-    if (forced) return forced;
     int occ = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kernel, threads, 0) != hipSuccess || occ < 1) { (void)hipGetLastError(); return 8; }
     return (u64)occ * 2;
@@ -1218,7 +1200,8 @@ inline u64 span_blocks_per_cu(K kernel, int threads) {
 template <class F, class A>
 inline void name_stream(u64 n, F f, A add, u64 *defer_bits, const char *name = "name_stream") {
     if (n == 0) return;
-    static const u64 per_cu = span_blocks_per_cu(k_name_stream<2048, F, A>, kBlock);
+    static const u64 per_cu_occ = span_blocks_per_cu(k_name_stream<2048, F, A>, kBlock);
+    const u64 per_cu = sw().span_blocks_per_cu ? sw().span_blocks_per_cu : per_cu_occ;
     u64 blocks = (u64)rt().num_cus * per_cu;
     u64 per_block = ((n + blocks - 1) / blocks + kAggChunk - 1) / kAggChunk * kAggChunk;
     if (per_block / (kBlock / 64) >= 0xFFFFFF00ull) throw Error(-75, "name_stream: a wave's span has >= 2^32 positions");
@@ -1229,30 +1212,12 @@ inline void name_stream(u64 n, F f, A add, u64 *defer_bits, const char *name = "
     after_launch(name);
 }
 template <class F, class A>
-struct NoAggFn {
-    F f; A add;
-    GRL_DEV void operator()(u64 i) const {
-        u32 s = f(i);
-        if (s != kNoBucket) {
-            if constexpr (F::kClaims) {
-                if (f.claim_bits) {
-                    const u64 cp = f.claim_pos(i);
-                    if (s & kClaimBit) atomicOr(reinterpret_cast<unsigned long long *>(&f.claim_bits[cp >> 6]), 1ull << (cp & 63));
-                    s &= ~kClaimBit;
-                }
-            }
-            add(s, 1u);
-            agg_first_seen(f, s, i, 0);
-        }
-    }
-};
-template <class F, class A>
 inline void for_each_agg(u64 n, F f, A add, bool aggregate, const char *name = "for_each_agg") {
     if (n == 0) return;
-    if (dev_env("GRLBWT_NOAGG")) { for_each(n, NoAggFn<F, A>{f, add}, name); return; }
     // (measured on the 10 GB build: the list passes of the levels above 0 -- no LDS count cache -- 11.0 -> 8.7 ms with twice the
     // resident workgroups per CU instead of 8; the level-0 kernel with the cache 40.4 -> 43.2 ms: it keeps 8)
-    static const u64 per_cu_plain = span_blocks_per_cu(k_for_each_agg<2048, false, F, A>, kBlock);
+    static const u64 per_cu_occ = span_blocks_per_cu(k_for_each_agg<2048, false, F, A>, kBlock);
+    const u64 per_cu_plain = sw().span_blocks_per_cu ? sw().span_blocks_per_cu : per_cu_occ;
     u64 blocks = (u64)rt().num_cus * (aggregate ? (u64)8 : per_cu_plain);
     u64 per_block = ((n + blocks - 1) / blocks + kAggChunk - 1) / kAggChunk * kAggChunk;
     blocks = (n + per_block - 1) / per_block;
@@ -2040,8 +2005,8 @@ __global__ void __launch_bounds__(TB)
 // i.e. 32-64-byte runs of keys and 16-32-byte runs of values at the write front: suffix_sort0 at level 2, 7 passes x 5.5 ms
 // vs 6 x 7.2 ms; whole build 1005 / 1010 / 1011 ms at 8 / 9 / 10 bits.
 inline int rs_max_digit() {
-    static const int d = [] { const char *e = dev_env("GRLBWT_SORT_DIGIT"); int v = e ? atoi(e) : 8; return v < 8 ? 8 : (v > 10 ? 10 : v); }();
-    return d;
+    const int v = sw().sort_digit;
+    return v < 8 ? 8 : (v > 10 ? 10 : v);
 }
 // (a caller may widen the digits of ONE sort: expand_sort takes 9-bit digits for a bucket split whose pass count that lowers)
 inline int &rs_digit_override() { static int d = 0; return d; }
@@ -2101,13 +2066,6 @@ struct XsPlan {
         cnt8 = nullptr; counts = nullptr; offsets = nullptr;
     }
 };
-// workgroup -> tile so that every XCD (workgroups are dealt to the 8 XCDs round-robin) takes a CONTIGUOUS range of
-// tiles: neighbouring tiles write neighbouring pieces of every digit's run, and the partially written lines then meet
-// in one L2 instead of two
-GRL_DEV u32 xcd_tile(u32 b, u32 g) {
-    const u32 per = g >> 3, rem = g & 7u, x = b & 7u, k = b >> 3;
-    return x * per + (x < rem ? x : rem) + k;
-}
 template <class GEN, int DB, int TI = 4096>
 __global__ void __launch_bounds__(kBlock) k_xs_count(u64 n, GEN gen, u32 dmask, u8 *cnt8, u32 *counts, u32 *scal /*[0] max keys per item*/) {
     constexpr int kXsTileItems = TI;
@@ -2175,8 +2133,7 @@ __global__ void __launch_bounds__(kBlock) k_xs_count(u64 n, GEN gen, u32 dmask, 
 // (MINB = workgroups per CU the register budget is cut for: see expand_sort)
 // (K = u64, or u32 when a whole key fits 32 bits: half the bytes in LDS, in the write-out and in every later pass)
 template <class GEN, int DB, int MINB = 3, class K = u64, int IPT = 4, int TI = 4096>
-__global__ void __launch_bounds__(kBlock, MINB) k_xs_scatter(u64 n, GEN gen, u32 dmask, const u8 *cnt8, const u64 *offsets /*[tiles][NB]*/, K *out,
-                                                       int xcd_aware) {
+__global__ void __launch_bounds__(kBlock, MINB) k_xs_scatter(u64 n, GEN gen, u32 dmask, const u8 *cnt8, const u64 *offsets /*[tiles][NB]*/, K *out) {
     constexpr int NB = 1 << DB, BPT = NB / kBlock > 0 ? NB / kBlock : 1;     // bins per thread (contiguous)
     constexpr int ROWS = kXsWin / kBlock;                                   // 16 rows of 64 keys per wave and round
     constexpr int kXsBatch = kBlock * IPT, kWalks = TI / kXsBatch;
@@ -2188,7 +2145,7 @@ __global__ void __launch_bounds__(kBlock, MINB) k_xs_scatter(u64 n, GEN gen, u32
     __shared__ u64 s_w[4];
     __shared__ u32 s_wsum[4];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const u32 tile = xcd_aware ? xcd_tile(blockIdx.x, gridDim.x) : blockIdx.x;
+    const u32 tile = blockIdx.x;
     for (int d = threadIdx.x; d < NB; d += kBlock) s_goff[d] = offsets[(u64)tile * NB + d];
     const u64 base = (u64)tile * TI;
     // A ROUND = walks until the window is full, then one ranking + write-out.  Walk b covers the items [i0, i0 + 256 IPT) of the tile;
@@ -2364,7 +2321,7 @@ inline u64 expand_count(u64 n, GEN gen, int bits, XsPlan &plan, const char *name
         // ~30 % more than an 8-bit one, a pass saved is a pass saved: 14.1 -> 11.3 ms for the passes of level 1 of the 10 GB build)
         const int passes_a = 1 + (bits > plan.db ? (bits - plan.db + md - 1) / md : 0);
         const int passes_b = bits > 9 ? 1 + (bits - 9 + 8) / 9 : 99;
-        if (md == 8 && passes_b < passes_a && !dev_env("GRLBWT_XS_DIGIT8")) { plan.db = 9; plan.md = 9; }
+        if (md == 8 && passes_b < passes_a && !sw().xs_digit8) { plan.db = 9; plan.md = 9; }
     }
     const int NB = 1 << plan.db;
     const u32 dmask = bits >= plan.db ? (u32)NB - 1u : (1u << bits) - 1u;
@@ -2390,8 +2347,7 @@ inline u64 expand_count(u64 n, GEN gen, int bits, XsPlan &plan, const char *name
     plan.maxc = (u32)h[0];
     plan.E = h[1];
     // (GRLBWT_XS_MAXC: the tests lower the limit so that ordinary inputs take the caller's unfused branch)
-    const char *lim = getenv("GRLBWT_XS_MAXC");
-    plan.ok = plan.maxc <= (lim ? (u32)atoi(lim) : 32u);
+    plan.ok = plan.maxc <= (u32)sw().xs_maxc;
     return plan.E;
 }
 // Phase 2: generate + first pass into buf_a, remaining passes ping-pong; returns 0 if the result is in buf_a, 1 if in buf_b
@@ -2401,9 +2357,8 @@ inline int expand_sort(GEN gen, XsPlan &plan, K *buf_a, K *buf_b, const char *na
     if (plan.n == 0) return 0;                 // (with E == 0 the walk still runs: cells() has side effects)
     const int NB = 1 << plan.db;
     const u32 dmask = plan.bits >= plan.db ? (u32)NB - 1u : (1u << plan.bits) - 1u;
-    // XCD-contiguous tile ranges were measured 7 % SLOWER for this kernel on the 10 GB build (32.8 vs 30.6 ms at level 0,
-    // 16.9 vs 14.8 at level 1): the round-robin deal already lets the 8 L2s share every digit's write front; opt-in only
-    static const int xcd_aware = dev_env("GRLBWT_XCD_MAP") ? 1 : 0;      // (development builds)
+    // (XCD-contiguous tile ranges were measured 7 % SLOWER for this kernel on the 10 GB build (32.8 vs 30.6 ms at level 0,
+    // 16.9 vs 14.8 at level 1): the round-robin deal already lets the 8 L2s share every digit's write front; not adopted)
     prof_begin(std::string(name) + ".xscatter", plan.E * sizeof(K));
     // (three workgroups per CU: at two the kernel keeps everything in registers, at three it spills ~100 bytes per lane and is the
     // faster one -- it hides its gathers with waves, not with registers: round 3)
@@ -2411,8 +2366,8 @@ inline int expand_sort(GEN gen, XsPlan &plan, K *buf_a, K *buf_b, const char *na
     // a DNA collection): FOUR (round 6: 137 -> 128 registers, nothing spilled; level 0 of the 10 GB build 19.2 -> 16.2 ms) -- the kernel
     // hides its chain gathers with waves, not with registers (round 3: two per CU, everything in registers, was the slower form).
     constexpr int kOcc = sizeof(K) == 4 ? 4 : 3;
-    if (plan.db == 9) hipLaunchKernelGGL((k_xs_scatter<GEN, 9, kOcc, K>), dim3(plan.tiles), dim3(kBlock), 0, rt().stream, plan.n, gen, dmask, plan.cnt8, plan.offsets, buf_a, xcd_aware);
-    else hipLaunchKernelGGL((k_xs_scatter<GEN, 8, kOcc, K>), dim3(plan.tiles), dim3(kBlock), 0, rt().stream, plan.n, gen, dmask, plan.cnt8, plan.offsets, buf_a, xcd_aware);
+    if (plan.db == 9) hipLaunchKernelGGL((k_xs_scatter<GEN, 9, kOcc, K>), dim3(plan.tiles), dim3(kBlock), 0, rt().stream, plan.n, gen, dmask, plan.cnt8, plan.offsets, buf_a);
+    else hipLaunchKernelGGL((k_xs_scatter<GEN, 8, kOcc, K>), dim3(plan.tiles), dim3(kBlock), 0, rt().stream, plan.n, gen, dmask, plan.cnt8, plan.offsets, buf_a);
     prof_end();
     after_launch(name);
     if (plan.bits <= plan.db || plan.E == 0) return 0;
@@ -2438,12 +2393,10 @@ inline void rs_pass(const K *kin, const V *vin, K *kout, V *vout, u64 n, int shi
 // over 8-byte keys -- the passes run at the rate of their scattered writes (tools/sortbench.hip: uniform digits 2.2-2.5 TB/s,
 // skewed digits 4.5 TB/s with the same kernel).  Records above 12 bytes keep 4096-key tiles (LDS).
 inline int rs_threads_override() {
-    static const int v = [] { const char *e = dev_env("GRLBWT_RS_THREADS"); return e ? atoi(e) : 0; }();
-    return v;
+    return sw().rs_threads;
 }
 inline int rs_threads_override_xs() {      // (SITE 1: the passes behind the fused expansion of the induction)
-    static const int v = [] { const char *e = dev_env("GRLBWT_RS_THREADS_XS"); return e ? atoi(e) : 0; }();
-    return v;
+    return sw().rs_threads_xs;
 }
 template <class K, class V, int SITE, int TB>
 inline int sort_pairs_tb(K *keys_a, V *vals_a, K *keys_b, V *vals_b, u64 n, int begin_bit, int end_bit, const char *name) {
@@ -3374,7 +3327,7 @@ inline void stream_merge_count(u64 G, SEG seg, SmPlan<IDX> &plan, const char *na
     plan = SmPlan<IDX>();
     plan.G = G;
     if (G == 0) return;
-    static const int spt_env = dev_env("GRLBWT_SM_SPT") ? atoi(dev_env("GRLBWT_SM_SPT")) : 0;      // (experiments: 4 or 8 segments per thread at every level)
+    const int spt_env = sw().sm_spt;      // (experiments: 4 or 8 segments per thread at every level)
     plan.spt = spt_env == 4 || spt_env == 8 ? spt_env : (mostly_plain ? 4 : 8);
     const u64 kSmTile = (u64)kBlock * plan.spt;
     plan.tiles = (G + kSmTile - 1) / kSmTile;
@@ -3465,7 +3418,7 @@ inline bool stream_merge_onepass(u64 G, SEG seg, SmPlan<IDX> &plan, u32 *osym, I
     plan = SmPlan<IDX>();
     plan.G = G;
     if (G == 0) return true;
-    static const int spt_dev = dev_env("GRLBWT_DEV_SM1_SPT") ? atoi(dev_env("GRLBWT_DEV_SM1_SPT")) : 0;
+    const int spt_dev = sw().dev_sm1_spt;
     plan.spt = spt_dev == 4 || spt_dev == 8 ? spt_dev : (mostly_plain ? 4 : 8);
     const u64 kSmTile = (u64)kBlock * plan.spt;
     plan.tiles = (G + kSmTile - 1) / kSmTile;
@@ -3486,8 +3439,7 @@ inline bool stream_merge_onepass(u64 G, SEG seg, SmPlan<IDX> &plan, u32 *osym, I
     dev_memset(st, 0, (T + 2) * sizeof(u64));
     SmLb lbk;
     lbk.st_head = st; lbk.res = st + T;
-    lbk.patience = 200000000ull;                        // two seconds of the 100 MHz clock
-    if (const char *pt = dev_env("GRLBWT_DEV_LB_PATIENCE")) lbk.patience = (u64)atoll(pt);      // (development builds: tools/gpu_lookback_giveup.py makes the tiles give up)
+    lbk.patience = sw().dev_lb_patience;                // two seconds of the 100 MHz clock (development builds: tools/gpu_lookback_giveup.py makes the tiles give up)
     SmWide<IDX> *queue = (SmWide<IDX> *)dev_alloc((queue_cap ? queue_cap : 1) * sizeof(SmWide<IDX>));
     unsigned long long *wide = (unsigned long long *)(dres + 4);      // [1] atoms of the queued segments, [2] queue fill
     (void)out_cap;

@@ -97,18 +97,28 @@ def test_fault_injection_is_not_in_the_product(hip_lib):
     assert b"injected by the test" not in blob
 
 
+def _switch_names(tier):
+    """The names of one tier of grlbwt_amd/csrc/switches.hpp (the X-macro list GRLBWT_SWITCHES_<TIER>)."""
+    txt = open(os.path.join(ROOT, "grlbwt_amd", "csrc", "switches.hpp")).read()
+    m = re.search(r"#define GRLBWT_SWITCHES_%s\(X\)((?:.*\\\n)*.*\n)" % tier, txt)
+    assert m, tier
+    return set(re.findall(r"\bX\((GRLBWT_[A-Z0-9_]+),", m.group(1)))
+
+
 def test_environment_switches_of_the_product_are_few(hip_lib):
     """Every GRLBWT_* variable the device library reads is a diagnostic (traces), a debugging aid of the allocator, or a limit the
-    GPU tests lower to send small inputs down a large-input branch.  Experiment switches live in development builds
-    (prim::dev_env, tools/build_dev.sh), the switches of the CPU suites in the test stand-in (prim::test_env): neither reaches
-    the product binary (56 names, a dozen of them rejected experiments)."""
+    GPU tests lower to send small inputs down a large-input branch -- the product and init tiers of switches.hpp, exactly.
+    Experiment switches (dev tier, tools/build_dev.sh) and the switches of the CPU suites (test tier, the serial stand-in) do not
+    reach the product binary (56 names, a dozen of them rejected experiments)."""
+    product = _switch_names("PRODUCT") | _switch_names("INIT")
+    assert _switch_names("TEST") and _switch_names("DEV")
     blob = open(hip_lib, "rb").read()
     names = set(m.decode() for m in re.findall(rb"GRLBWT_[A-Z0-9_]+", blob))
     names -= {"GRLBWT_FLAG_CLASSIC_POOL", "GRLBWT_FLAG_FORCE_IDX64", "GRLBWT_BENCH_", "GRLBWT_HIP_LIB", "GRLBWT_E2E_TMP", "GRLBWT_SIM_LIB", "GRLBWT_"}
     assert not [n for n in names if n.startswith("GRLBWT_DEV_")], names
     assert len(names) <= 35, sorted(names)
-    src = ""
+    assert names == product, (sorted(names - product), sorted(product - names))
+    # the switches are read in switches.hpp alone
     for f in ("engine_impl.hpp", "prim_hip.hpp", "capi_impl.hpp"):
-        src += open(os.path.join(ROOT, "grlbwt_amd", "csrc", f)).read()
-    read = set(re.findall(r'(?<![a-z_])getenv\("(GRLBWT_[A-Z0-9_]+)"\)', src))
-    assert len(read) <= 35, sorted(read)
+        src = open(os.path.join(ROOT, "grlbwt_amd", "csrc", f)).read()
+        assert not re.findall(r"\b(?:getenv|test_env|dev_env)\(", src), f

@@ -288,6 +288,24 @@ def test_doubling_rounds_of_the_suffix_refinement(sim, oracle_mod, monkeypatch):
                 parity.check_final(sim, d, w)
 
 
+def test_switches_are_read_per_call(sim, oracle_mod, monkeypatch):
+    """A switch set between two builds of one process applies to the second (switches.hpp: one snapshot per API call, nothing
+    latched per template instantiation)."""
+    monkeypatch.delenv("GRLBWT_RUN_KEYS_MIN", raising=False)
+    monkeypatch.delenv("GRLBWT_DOUBLING_AFTER", raising=False)
+    cells = _shared_ramps(3000, 5)
+    iters = []
+    for after in (None, "2"):
+        if after:
+            monkeypatch.setenv("GRLBWT_DOUBLING_AFTER", after)
+        with engine.Context(0, 0, sim) as ctx:
+            ctx.upload(cells.tobytes(), 4)
+            ctx.build()
+            assert ctx.result_bytes() == oracle_mod.rl_bwt(cells.tobytes(), 4)
+            iters.append(ctx.round_info(0)["sort_iters"])
+    assert iters[1] < iters[0], iters
+
+
 def test_device_side_generators_match_host():
     """The torch generators of the large test inputs (run on the GPU there) produce the host generators' bytes."""
     a = workloads.repetitive_copies(5, 30011)

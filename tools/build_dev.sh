@@ -1,5 +1,5 @@
 #!/bin/bash
-# Development build of the device library: the experiment switches (prim::dev_env, GRLBWT_DEV_*) are compiled in, the
+# Development build of the device library: the experiment switches (dev tier of grlbwt_amd/csrc/switches.hpp) are compiled in, the
 # register / scratch / LDS report of every kernel is kept beside it (tools/kernel_resources.py reads it).
 #   tools/build_dev.sh            -> tools/_build/libgrlbwt_dev.so, tools/_build/kernel_resources.txt
 #   GRLBWT_HIP_LIB=tools/_build/libgrlbwt_dev.so GRLBWT_DEV_...=... python bench.py ...

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Run ON THE GPU BOX: the bench command once per variant, same box, same process layout.  A variant is "name:ENV=VAL,ENV=VAL" (dev: prefix ->
 # the development library tools/_build/libgrlbwt_dev.so).  Writes gpurun_out/<tag>/bench_<name>.json + sites_<name>.txt and a summary line each.
-#   tools/gpu_ab.sh r06b base: two:GRLBWT_ASM_TWO_PASS=1 ipt3:dev:GRLBWT_DEV_XS_IPT=3
+#   tools/gpu_ab.sh r06b base: two:GRLBWT_ASM_TWO_PASS=1 spt4:dev:GRLBWT_SM_SPT=4
 TAG=$1; shift
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 OUT=$R/gpurun_out/$TAG
