@@ -911,6 +911,26 @@ int grlbwt_fastx_convert_device(grlbwt_ctx *ctx, const void *dev_in, uint64_t n_
         if (n_strings) *n_strings = info.n_strings;
     });
 }
+int grlbwt_alphabet_size(const grlbwt_ctx *ctx, uint64_t *n_distinct) {
+    if (!HAS_ENG(ctx) || !n_distinct) return GRLBWT_EINVAL;
+    *n_distinct = ENG(ctx, alpha_n);
+    return GRLBWT_OK;
+}
+int grlbwt_alphabet_download(const grlbwt_ctx *ctx, uint64_t *values_out) {
+    if (!HAS_ENG(ctx) || !values_out || ENG(ctx, alpha_n) == 0) return GRLBWT_EINVAL;
+    return guarded(const_cast<grlbwt_ctx *>(ctx), [&] { prim::d2h(values_out, ENG(ctx, alpha.p), ENG(ctx, alpha_n) * 8); });
+}
+int grlbwt_alphabet_compact_device(grlbwt_ctx *ctx, const void *dev_cells, uint64_t n_cells, int cell_bytes, void *dev_ranks_u32,
+                                   void *dev_values_u64, uint64_t capacity_values, uint64_t *n_distinct) {
+    if (!ctx || !dev_cells || !dev_ranks_u32 || !dev_values_u64 || n_cells == 0 || !(cell_bytes == 4 || cell_bytes == 8)) return GRLBWT_EINVAL;
+    return guarded(ctx, [&] {
+        const bool big = n_cells >= 0xFFFFFF00ull || (ctx->flags & GRLBWT_FLAG_FORCE_IDX64);
+        uint64_t k = big ? grl64::Engine::alphabet_compact_device(dev_cells, n_cells, cell_bytes, (uint32_t *)dev_ranks_u32, (uint64_t *)dev_values_u64, capacity_values)
+                         : grl32::Engine::alphabet_compact_device(dev_cells, n_cells, cell_bytes, (uint32_t *)dev_ranks_u32, (uint64_t *)dev_values_u64, capacity_values);
+        if (n_distinct) *n_distinct = k;
+        if (k > capacity_values) throw prim::Error(GRLBWT_EINVAL, "alphabet compaction: more distinct values than the output buffer holds");
+    });
+}
 int grlbwt_text_load_fastx(grlbwt_ctx *ctx, const char *path, uint32_t fx_flags, uint64_t *n_strings) {
     if (!ctx || !path) return GRLBWT_EINVAL;
     return guarded(ctx, [&] { load_fastx(ctx, path, fx_flags, n_strings); });

@@ -1339,7 +1339,7 @@ template <int IB> struct SufRecT;
 template <> struct alignas(8) SufRecT<4> { u32 freq; u32 left; GRL_HD void set_phr(u32) {} GRL_HD u32 phr(const u32 *dict_phr, u32 q) const { return dict_phr[q]; } };
 template <> struct alignas(16) SufRecT<8> { u64 freq; u32 left; u32 k; GRL_HD void set_phr(u32 v) { k = v; } GRL_HD u32 phr(const u32 *, u32) const { return k; } };
 typedef SufRecT<sizeof(idx_t)> SufRec;      // one 8/16-byte gather per sorted suffix
-// left carries two flags above the symbol (symbols are < 2^30): the suffix is the last cell of its phrase, and that
+// left carries two flags above the symbol (level-0 symbols or their ranks are < 2^30): the suffix is the last cell of its phrase, and that
 // phrase ends a string -- what the group decision needs from the group's first member.
 // What the group fold reads per sorted suffix: from the array SuffixRecFn streamed out (RecArray), or computed where it is
 // needed (RecCompute: five gathers per member instead of one, no array over the whole dictionary -- the collection-level mode
@@ -1556,7 +1556,7 @@ struct MetaPairFn {        // (position << 32 | metasymbol) of the marked slots,
     }
 };
 // The grammar walk reads ONE array: dm[q] = meta << 32 | last-cell-of-its-phrase << 31 | that-phrase-ends-a-string << 30 | symbol
-// (symbols and metasymbols are < 2^30).  A walk then touches one or two neighbouring 64-byte lines per metasymbol.  (Rounds 1-2 kept
+// (level-0 symbols or their ranks, and metasymbols, are < 2^30).  A walk then touches one or two neighbouring 64-byte lines per metasymbol.  (Rounds 1-2 kept
 // meta[], dict_sym[], the phrase-start bit-vector, dict_phr[] and ph_lastT[] apart: five random lines for 8 bytes of
 // output, 161 GB fetched to write 4 GB at 10 GB -- 46 ms.)
 static constexpr u32 kDmEnd = 0x80000000u, kDmLastT = 0x40000000u, kDmSym = 0x3FFFFFFFu;
@@ -1960,7 +1960,7 @@ struct StoreFn {          // out[i] = f(i): materialise an expensive scan input 
 
 // ----------------------------------------------------- a13/a14: induction
 // Grammar cell of a metasymbol for the chain walks: g0 | has_hocc<<31 in the low word, g1 in the high word, so that a
-// chain step is ONE random 8-byte load (symbols are < 2^30).
+// chain step is ONE random 8-byte load (level-0 symbols or their ranks are < 2^30).
 struct PackGrammarFn {
     const u32 *g0; const u32 *g1; const u8 *has_hocc; u64 *gp;
     GRL_DEV void operator()(u64 u) const { gp[u] = ((u64)g1[u] << 32) | (u64)(g0[u] | (has_hocc[u] ? 0x80000000u : 0u)); }
@@ -2209,16 +2209,18 @@ struct AsmSeg {
 };
 
 // ------------------------------------------------------- a16: .rl_bwt image
+// (alpha: the values of a compacted alphabet -- the run's symbol is a rank then; null: the symbol itself)
 struct RunRecordFn {      // sym | len << (8 sb): the record of run i as one word (sb + fb <= 8)
-    const u32 *sym; RunLen len; u32 sb;
-    GRL_DEV u64 operator()(u64 i) const { return (u64)sym[i] | ((u64)len(i) << (8 * sb)); }
+    const u32 *sym; RunLen len; u32 sb; const u64 *alpha = nullptr;
+    GRL_DEV u64 operator()(u64 i) const { return (alpha ? alpha[sym[i]] : (u64)sym[i]) | ((u64)len(i) << (8 * sb)); }
 };
 struct PackRunsFn {
     const u32 *sym; RunLen len; u32 sb, fb; u8 *out; u32 hdr;      // hdr: bytes in front of the first record (16, or 0 for a part)
+    const u64 *alpha = nullptr;
     GRL_DEV void operator()(u64 i) const {
         const u32 rec = sb + fb;
         u8 *p = out + hdr + i * (u64)rec;
-        u64 s = sym[i], l = len(i);
+        u64 s = alpha ? alpha[sym[i]] : (u64)sym[i], l = len(i);
         // records of 4 or 8 bytes (DNA: 1+3; tokens: 2+2 ... ) are one aligned store, not `rec` byte stores
         if (rec == 4 && ((uintptr_t)out & 3) == 0) { *reinterpret_cast<u32 *>(p) = (u32)(s | (l << (8 * sb))); return; }
         if (rec == 8 && ((uintptr_t)out & 7) == 0) { *reinterpret_cast<u64 *>(p) = s | (l << (8 * sb)); return; }
@@ -2246,6 +2248,66 @@ struct CellIn {
     const cell_t *t;
     GRL_DEV u64 operator()(u64 i) const { return (u64)t[i]; }
 };
+
+// ------------------------------------------- alphabet compaction, the general regime
+// The BWT of a collection depends only on the order and the equality of its symbols, so a text whose symbols do not fit the
+// engine's 30 bits is replaced by the ranks of its values among its distinct values (an order-preserving dense alphabet of
+// at most n symbols) and the values come back when the image is packed.  This is the form that is always right: a radix sort
+// of (value, position), head flags, their scan, the rank scattered to the position.  The device library has faster regimes
+// for alphabets that fit a hash table (prim_hip.hpp, ac_collect / ac_rank) and falls through to this one.
+template <class cell_t>
+struct AcKeyPosFn {
+    const cell_t *t; u64 *key; idx_t *pos;
+    GRL_DEV void operator()(u64 i) const { key[i] = (u64)t[i]; pos[i] = (idx_t)i; }
+};
+struct AcHeadIn {         // 1 where a sorted value differs from the one in front of it
+    const u64 *key;
+    GRL_DEV idx_t operator()(u64 j) const { return (idx_t)(j > 0 && key[j] != key[j - 1] ? 1 : 0); }
+};
+struct AcScatterFn {      // heads[j] = heads in front of j
+    const u64 *key; const idx_t *pos; const idx_t *heads; u32 *ranks; u64 *values;
+    GRL_DEV void operator()(u64 j) const {
+        const bool head = j == 0 || key[j] != key[j - 1];
+        const u64 r = (u64)heads[j] + (j > 0 && head ? 1 : 0);
+        ranks[pos[j]] = (u32)r;
+        if (head) values[r] = key[j];
+    }
+};
+// Largest alphabet of a compacted text: its ranks take the place of level-0 symbols, which the engine carries in 30 bits.
+static constexpr u64 kAlphaMax = (1ull << 30) - 16;
+// t[0, n) -> ranks[0, n) and the sorted distinct values (allocated here); max_sym = the largest value.  Returns their number.
+template <class cell_t>
+static u64 alphabet_compact(const cell_t *t, u64 n, u64 max_sym, u32 *ranks, DBuf<u64> &values) {
+    if (max_sym > ~0ull - 4) throw prim::Error(-75, "symbols above 2^64 - 5 are not supported (the header width is taken from max_sym + 4)");
+    int bits = (int)bitlen64(max_sym);
+    if (bits < 1) bits = 1;
+#ifdef GRLBWT_PRIM_HIP
+    {
+        prim::AcPlan P;
+        struct Guard { prim::AcPlan &p; ~Guard() { p.release(); } } guard{P};
+        prim::ac_collect<cell_t>(t, n, P);
+        if (!P.overflow) {
+            if (P.sigma >= kAlphaMax) throw prim::Error(-75, "too many distinct symbols (2^30 - 16 or more)");
+            values.alloc(P.sigma);
+            prim::ac_rank<cell_t>(t, n, P, bits, values.p, ranks);
+            return P.sigma;
+        }
+    }
+#endif
+    DBuf<u64> ka(n), kb(n);
+    DBuf<idx_t> pa(n), pb(n);
+    prim::for_each(n, AcKeyPosFn<cell_t>{t, ka.p, pa.p}, "alpha.keys");
+    const int res = prim::sort_pairs<u64, idx_t>(ka.p, pa.p, kb.p, pb.p, n, 0, bits, "alpha.sort_pairs");
+    const u64 *key = res ? kb.p : ka.p;
+    const idx_t *pos = res ? pb.p : pa.p;
+    (res ? ka : kb).release();
+    DBuf<idx_t> heads(n + 1);
+    const u64 sigma = (u64)prim::exclusive_scan<idx_t>(n, AcHeadIn{key}, heads.p, true, "alpha.heads") + 1;
+    if (sigma >= kAlphaMax) throw prim::Error(-75, "too many distinct symbols (2^30 - 16 or more)");
+    values.alloc(sigma);
+    prim::for_each(n, AcScatterFn{key, pos, heads.p, ranks, values.p}, "alpha.scatter");
+    return sigma;
+}
 
 // ------------------------------------------- collection-level multi-GPU pieces
 // The per-round dictionary merge (join_thread_phrases, parsing_strategies.h:277-386) is partitioned by content: a hash of
@@ -2822,6 +2884,19 @@ struct UnpackRunsFn {     // (sym: sb bytes LE, len: fb bytes LE) records -> arr
         sym[i] = (u32)s; len[i] = (idx_t)l;
     }
 };
+struct ImageSymIn {        // run symbol straight from the packed records, all 64 bits of it
+    const u8 *img; u32 sb, fb;
+    GRL_DEV u64 operator()(u64 i) const {
+        const u8 *p = img + 16 + i * (u64)(sb + fb);
+        u64 s = 0;
+        for (u32 b = 0; b < sb; b++) s |= (u64)p[b] << (8 * b);
+        return s;
+    }
+};
+struct UnpackSymFn {
+    ImageSymIn in; u64 *sym;
+    GRL_DEV void operator()(u64 i) const { sym[i] = in(i); }
+};
 struct ImageLenIn {        // run length straight from the packed records (64-bit sum: decides the index width of a consumer)
     const u8 *img; u32 sb, fb;
     GRL_DEV u64 operator()(u64 i) const {
@@ -2915,12 +2990,13 @@ struct InvertLenFn {      // string i: backward LF walk from row i until its own
     }
 };
 template <class cell_t>
-struct InvertWriteFn {
-    const u32 *bwt; const idx_t *lf; const idx_t *off; u32 sep; cell_t *text;
+struct InvertWriteFn {      // (alpha: the values of a compacted alphabet, the walk runs on their ranks; null: the symbols themselves)
+    const u32 *bwt; const idx_t *lf; const idx_t *off; u32 sep; cell_t *text; const u64 *alpha = nullptr;
+    GRL_DEV cell_t val(u32 c) const { return alpha ? (cell_t)alpha[c] : (cell_t)c; }
     GRL_DEV void operator()(u64 i) const {
         u64 end = off[i + 1] - 1, row = i;
-        text[end] = (cell_t)sep;
-        for (u32 c = bwt[row]; c != sep; c = bwt[row]) { text[--end] = (cell_t)c; row = lf[row]; }
+        text[end] = val(sep);
+        for (u32 c = bwt[row]; c != sep; c = bwt[row]) { text[--end] = val(c); row = lf[row]; }
     }
 };
 
@@ -2972,25 +3048,27 @@ struct RunInvertLenFn {
 };
 template <class cell_t>
 struct RunInvertWriteFn {
-    const RankCell *rc; const RunRec *rec; const idx_t *off; u32 sep; cell_t *text;
+    const RankCell *rc; const RunRec *rec; const idx_t *off; u32 sep; cell_t *text; const u64 *alpha = nullptr;
+    GRL_DEV cell_t val(u32 c) const { return alpha ? (cell_t)alpha[c] : (cell_t)c; }
     GRL_DEV void operator()(u64 i) const {
         u64 end = off[i + 1] - 1;
         idx_t row = (idx_t)i;
-        text[end] = (cell_t)sep;
+        text[end] = val(sep);
         RunRec r = rec[run_of_row(rc, (u64)row)];
-        while (r.sym != sep) { text[--end] = (cell_t)r.sym; row = (idx_t)(row + (idx_t)r.delta); r = rec[run_of_row(rc, (u64)row)]; }
+        while (r.sym != sep) { text[--end] = val(r.sym); row = (idx_t)(row + (idx_t)r.delta); r = rec[run_of_row(rc, (u64)row)]; }
     }
 };
 
 template <class cell_t>
 struct RunInvertTailFn {    // the last `tail` cells of string i (separator included), right-aligned in slot i of `tail` cells; the rest of the slot stays as it was
-    const RankCell *rc; const RunRec *rec; u32 sep; u64 tail; cell_t *out; idx_t *got;
+    const RankCell *rc; const RunRec *rec; u32 sep; u64 tail; cell_t *out; idx_t *got; const u64 *alpha = nullptr;
+    GRL_DEV cell_t val(u32 c) const { return alpha ? (cell_t)alpha[c] : (cell_t)c; }
     GRL_DEV void operator()(u64 i) const {
         u64 end = (i + 1) * tail - 1, l = 1;
         idx_t row = (idx_t)i;
-        out[end] = (cell_t)sep;
+        out[end] = val(sep);
         RunRec r = rec[run_of_row(rc, (u64)row)];
-        while (r.sym != sep && l < tail) { out[--end] = (cell_t)r.sym; l++; row = (idx_t)(row + (idx_t)r.delta); r = rec[run_of_row(rc, (u64)row)]; }
+        while (r.sym != sep && l < tail) { out[--end] = val(r.sym); l++; row = (idx_t)(row + (idx_t)r.delta); r = rec[run_of_row(rc, (u64)row)]; }
         got[i] = (idx_t)l;
     }
 };
@@ -3045,8 +3123,15 @@ class Engine {
   public:
     ~Engine() { prim::stages_drop(); }   // open stage clocks point into tm
     int cell_bytes = 1;
-    const void *text0 = nullptr;      // device pointer (owned by own0 or borrowed)
+    const void *text0 = nullptr;      // device pointer (owned by own0 or rank0, or borrowed)
     DBuf<u8> own0;
+    // A text with symbols of 2^30 - 8 and more is built on the ranks of its values (alphabet_compact): rank0 is the level-0 text
+    // (cell_bytes 4, separator 0), alpha the sorted values the ranks stand for; the statistics and the image speak of the values,
+    // everything in between (round_info[0].sigma, grammar, pre-BWT, the level-0 BWT of the stage-wise inspection) of the ranks
+    DBuf<u32> rank0;
+    DBuf<u64> alpha;
+    u64 alpha_n = 0;
+    u64 sep0() const { return alpha_n ? 0 : stats.min_sym; }
     u64 n0 = 0;
     Stats stats;
     Timers tm;
@@ -3094,7 +3179,14 @@ class Engine {
         }
         if ((u64)sep != mn) throw prim::Error(-84, "Error: the file is ill formed");   // utils.cpp:177-180
         stats.n_syms = n; stats.min_sym = mn; stats.max_sym = mx; stats.max_sym_freq = F;
-        if (mx + 8 >= (1ull << 30)) throw prim::Error(-75, "symbols >= 2^30 are not supported by this build");
+        if (mx >= (1ull << 30) - 8) {
+            if constexpr (sizeof(cell_t) >= 4) {
+                rank0.alloc(n + 4);
+                alpha_n = alphabet_compact<cell_t>(t, n, mx, rank0.p, alpha);
+                if ((const void *)t == (const void *)own0.p) own0.release();      // (a borrowed text is left alone and not read again)
+                text0 = rank0.p; cell_bytes = 4;
+            }
+        }
         stats.sb = (bitlen64(mx + 4) + 7) / 8;                                          // a17
         stats.fb = (bitlen64(F) + 7) / 8;
     }
@@ -3109,6 +3201,7 @@ class Engine {
         prim::pool_reserve((size_t)(n * (u64)w) * (sizeof(idx_t) == 4 ? 22 : 30));
         levels.clear(); linfo.clear(); kept_texts.clear(); kept_bwts.clear();
         parse_done = false; bwt_level = -1; image_bytes = 0;
+        rank0.release(); alpha.release(); alpha_n = 0;
         tm = Timers();
         switch (w) {
             case 1: stats_t<u8>((const u8 *)dev_cells, n, hist256); break;
@@ -3117,7 +3210,7 @@ class Engine {
             default: stats_t<u64>((const u64 *)dev_cells, n); break;
         }
         cur_n = n;
-        cur_sigma = (u32)(stats.max_sym + 1);
+        cur_sigma = alpha_n ? (u32)alpha_n : (u32)(stats.max_sym + 1);
     }
     void upload_text(const void *host_cells, u64 n, int w) {
         own0.alloc(n * (u64)w + 16);
@@ -4436,10 +4529,10 @@ class Engine {
         if (parse_done) return true;
         if (levels.empty()) {
             switch (cell_bytes) {
-                case 1: par_round_t<u8, true>((const u8 *)text0, n0, cur_sigma, (u8)stats.min_sym); break;
-                case 2: par_round_t<u16, true>((const u16 *)text0, n0, cur_sigma, (u16)stats.min_sym); break;
-                case 4: par_round_t<u32, true>((const u32 *)text0, n0, cur_sigma, (u32)stats.min_sym); break;
-                default: par_round_t<u64, true>((const u64 *)text0, n0, cur_sigma, (u64)stats.min_sym); break;
+                case 1: par_round_t<u8, true>((const u8 *)text0, n0, cur_sigma, (u8)sep0()); break;
+                case 2: par_round_t<u16, true>((const u16 *)text0, n0, cur_sigma, (u16)sep0()); break;
+                case 4: par_round_t<u32, true>((const u32 *)text0, n0, cur_sigma, (u32)sep0()); break;
+                default: par_round_t<u64, true>((const u64 *)text0, n0, cur_sigma, (u64)sep0()); break;
             }
         } else {
             DBuf<u32> t = std::move(cur_text);
@@ -4803,8 +4896,8 @@ class Engine {
         // records of up to 8 bytes go through prim::pack_records (tiles assembled in LDS, 16-byte stores); wider ones one lane per run.
         // (Four runs per lane, their 4 x 5 bytes put together in registers, was measured at 15.5 ms against 9 for one lane per run on
         // the 1.66 G runs of the 10 GB image: the loads of a lane's four runs are what is 20 bytes apart then.)
-        if (sb + fb <= 8 && fb < 8) prim::pack_records(bwt.R, RunRecordFn{bwt.sym.p, run_len(), sb}, sb + fb, image.p + 16, "pack_rl_bwt");
-        else prim::for_each(bwt.R, PackRunsFn{bwt.sym.p, run_len(), sb, fb, image.p, 16u}, "pack_rl_bwt");
+        if (sb + fb <= 8 && fb < 8) prim::pack_records(bwt.R, RunRecordFn{bwt.sym.p, run_len(), sb, alpha.p}, sb + fb, image.p + 16, "pack_rl_bwt");
+        else prim::for_each(bwt.R, PackRunsFn{bwt.sym.p, run_len(), sb, fb, image.p, 16u, alpha.p}, "pack_rl_bwt");
         image_runs = bwt.R;
         image_part_off = 0; image_part_bytes = image_bytes;
         // "results are complete when a call returns" (include/grlbwt_hip.h): the image pointer may be handed to another
@@ -4849,6 +4942,9 @@ class Engine {
         if (cell_bytes == 1) { F = 0; for (int i = 0; i < 256; i++) if (hist[i] > F) F = hist[i]; }
         if (sizeof(idx_t) == 4 && n >= 0xFFFFFF00ull)
             throw prim::Error(-75, "collection too large for the 32-bit index build: create every context with GRLBWT_FLAG_FORCE_IDX64");
+        // (from the gathered maximum: a shard of small symbols beside a shard of wide ones refuses like every other rank)
+        if (mx >= (1ull << 30) - 8)
+            throw prim::Error(-75, "symbols >= 2^30 - 8 are single-GPU for now: the collection-level mode has no global alphabet compaction yet");
         g_n_strings = ns; g_n_syms = n;
         stats.max_sym = mx; stats.max_sym_freq = F;
         stats.sb = (bitlen64(mx + 4) + 7) / 8;
@@ -5071,10 +5167,10 @@ class Engine {
         if (parse_done) return true;
         if (levels.empty()) {
             switch (cell_bytes) {
-                case 1: dist_round_t<u8, true>(C, (const u8 *)text0, n0, cur_sigma, (u8)stats.min_sym); break;
-                case 2: dist_round_t<u16, true>(C, (const u16 *)text0, n0, cur_sigma, (u16)stats.min_sym); break;
-                case 4: dist_round_t<u32, true>(C, (const u32 *)text0, n0, cur_sigma, (u32)stats.min_sym); break;
-                default: dist_round_t<u64, true>(C, (const u64 *)text0, n0, cur_sigma, (u64)stats.min_sym); break;
+                case 1: dist_round_t<u8, true>(C, (const u8 *)text0, n0, cur_sigma, (u8)sep0()); break;
+                case 2: dist_round_t<u16, true>(C, (const u16 *)text0, n0, cur_sigma, (u16)sep0()); break;
+                case 4: dist_round_t<u32, true>(C, (const u32 *)text0, n0, cur_sigma, (u32)sep0()); break;
+                default: dist_round_t<u64, true>(C, (const u64 *)text0, n0, cur_sigma, (u64)sep0()); break;
             }
         } else {
             DBuf<u32> t = std::move(cur_text);
@@ -5455,11 +5551,35 @@ class Engine {
 
     // ---- consumers of the .rl_bwt image (validation): grl2plain + reverse_bwt on the device ----------
     // Rebuilds the collection (strings in input order) from an image in device memory.
+    // The run symbols of an image are read as 64 bits.  Where the largest is 2^30 or more they are compacted like a wide text
+    // (R values, not n): the LF walk runs on ranks and the write functors put alpha[rank] into the text.
+    struct WideSyms { DBuf<u32> ranks; DBuf<u64> alpha; };
+    static void image_symbols(const u8 *img, u64 R, u32 sb, u32 fb, int cell_bytes, WideSyms &W) {
+        const ImageSymIn in{img, sb, fb};
+        const u64 mx = prim::reduce_max<u64>(R, in, "inv.max_sym");
+        if (cell_bytes < 8 && (mx >> (8 * cell_bytes))) throw prim::Error(-22, "inversion: the image's largest symbol does not fit the cell width");
+        if (mx < (1ull << 30)) return;
+        DBuf<u64> s64(R);
+        prim::for_each(R, UnpackSymFn{in, s64.p}, "inv.unpack_syms");
+        W.ranks.alloc(R);
+        alphabet_compact<u64>(s64.p, R, mx, W.ranks.p, W.alpha);
+    }
+    // the primitive alone (grlbwt_alphabet_compact_device): returns the number of distinct values; they are copied out when they fit
+    static u64 alphabet_compact_device(const void *cells, u64 n, int w, u32 *ranks, u64 *values_out, u64 capacity) {
+        if (n >= kPosMask) throw prim::Error(-75, "input too large");
+        const u64 mx = w == 4 ? prim::reduce_max<u64>(n, CellIn<u32>{(const u32 *)cells}, "alpha.max") : prim::reduce_max<u64>(n, CellIn<u64>{(const u64 *)cells}, "alpha.max");
+        DBuf<u64> values;
+        const u64 k = w == 4 ? alphabet_compact<u32>((const u32 *)cells, n, mx, ranks, values) : alphabet_compact<u64>((const u64 *)cells, n, mx, ranks, values);
+        if (k <= capacity) prim::d2d(values_out, values.p, k * 8);
+        prim::sync();
+        return k;
+    }
     template <class cell_t>
-    static u64 invert_t(const u8 *img, u64 R, u32 sb, u32 fb, cell_t *text_out, u64 capacity) {
+    static u64 invert_t(const u8 *img, u64 R, u32 sb, u32 fb, cell_t *text_out, u64 capacity, const WideSyms &W) {
         DBuf<u32> rsym(R);
         DBuf<idx_t> rlen(R), rpos(R + 1);
         prim::for_each(R, UnpackRunsFn{img, sb, fb, rsym.p, rlen.p}, "inv.unpack");
+        if (W.alpha.p) d2d_copy(rsym.p, W.ranks.p, R);
         u64 n = (u64)prim::exclusive_scan<idx_t>(R, IdxIn<idx_t>{rlen.p}, rpos.p, true, "inv.positions");
         if (n > capacity) throw prim::Error(-22, "inversion: output buffer too small");
         u32 sep = prim::reduce_min<u32>(R, PtrU32In{rsym.p}, "inv.sep");
@@ -5484,7 +5604,7 @@ class Engine {
         prim::for_each(k, InvertLenFn{bwt.p, lf.p, sep, slen.p}, "inv.lengths");
         u64 tot = (u64)prim::exclusive_scan<idx_t>(k, IdxIn<idx_t>{slen.p}, slen.p, true, "inv.offsets");
         if (tot != n) throw prim::Error(-71, "inversion: string lengths do not add up to the BWT length");
-        prim::for_each(k, InvertWriteFn<cell_t>{bwt.p, lf.p, slen.p, sep, text_out}, "inv.write");
+        prim::for_each(k, InvertWriteFn<cell_t>{bwt.p, lf.p, slen.p, sep, text_out, W.alpha.p}, "inv.write");
         prim::sync();
         return n;
     }
@@ -5492,10 +5612,11 @@ class Engine {
     static void d2d_copy(T *dst, const T *src, u64 n) { prim::d2d(dst, src, n * sizeof(T)); }
     // the run-indexed form (functor block "the same inversion indexed by RUNS")
     template <class cell_t>
-    static u64 invert_runs_t(const u8 *img, u64 R, u32 sb, u32 fb, cell_t *text_out, u64 capacity, u64 tail = 0, u64 *n_strings_out = nullptr) {
+    static u64 invert_runs_t(const u8 *img, u64 R, u32 sb, u32 fb, cell_t *text_out, u64 capacity, const WideSyms &W, u64 tail = 0, u64 *n_strings_out = nullptr) {
         DBuf<u32> rsym(R);
         DBuf<idx_t> rlen(R), rpos(R + 1);
         prim::for_each(R, UnpackRunsFn{img, sb, fb, rsym.p, rlen.p}, "inv.unpack");
+        if (W.alpha.p) d2d_copy(rsym.p, W.ranks.p, R);
         const u64 n = (u64)prim::exclusive_scan<idx_t>(R, IdxIn<idx_t>{rlen.p}, rpos.p, true, "inv.positions");
         if (!tail && n > capacity) throw prim::Error(-22, "inversion: output buffer too small");
         const u32 sep = prim::reduce_min<u32>(R, PtrU32In{rsym.p}, "inv.sep");
@@ -5530,7 +5651,7 @@ class Engine {
             // strings of 249 M cells are 249 M dependent steps each): `tail` LF steps per string from its terminator's row
             if (k * tail > capacity) throw prim::Error(-22, "inversion: output buffer too small");
             DBuf<idx_t> got(k);
-            prim::for_each(k, RunInvertTailFn<cell_t>{rc.p, rec.p, sep, tail, text_out, got.p}, "inv.tails");
+            prim::for_each(k, RunInvertTailFn<cell_t>{rc.p, rec.p, sep, tail, text_out, got.p, W.alpha.p}, "inv.tails");
             prim::sync();
             if (n_strings_out) *n_strings_out = k;
             return (u64)prim::reduce_sum<u64>(k, IdxIn<idx_t>{got.p}, "inv.tails");
@@ -5539,7 +5660,7 @@ class Engine {
         prim::for_each(k, RunInvertLenFn{rc.p, rec.p, sep, slen.p}, "inv.lengths");
         const u64 tot = (u64)prim::exclusive_scan<idx_t>(k, IdxIn<idx_t>{slen.p}, slen.p, true, "inv.offsets");
         if (tot != n) throw prim::Error(-71, "inversion: string lengths do not add up to the BWT length");
-        prim::for_each(k, RunInvertWriteFn<cell_t>{rc.p, rec.p, slen.p, sep, text_out}, "inv.write");
+        prim::for_each(k, RunInvertWriteFn<cell_t>{rc.p, rec.p, slen.p, sep, text_out, W.alpha.p}, "inv.write");
         prim::sync();
         return n;
     }
@@ -5553,11 +5674,14 @@ class Engine {
         if (sb == 0 || sb > 8 || fb == 0 || fb > 8 || (image_bytes - 16) % (sb + fb)) throw prim::Error(-22, "bad .rl_bwt header");
         const u64 R = (image_bytes - 16) / (sb + fb);
         const u8 *img = (const u8 *)dev_image;
+        if (!(cell_bytes == 1 || cell_bytes == 2 || cell_bytes == 4 || cell_bytes == 8)) throw prim::Error(-22, "bad cell width");
+        WideSyms W;
+        image_symbols(img, R, (u32)sb, (u32)fb, cell_bytes, W);
         switch (cell_bytes) {
-            case 1: return invert_runs_t<u8>(img, R, (u32)sb, (u32)fb, (u8 *)dev_out, capacity_cells, tail, n_strings_out);
-            case 2: return invert_runs_t<u16>(img, R, (u32)sb, (u32)fb, (u16 *)dev_out, capacity_cells, tail, n_strings_out);
-            case 4: return invert_runs_t<u32>(img, R, (u32)sb, (u32)fb, (u32 *)dev_out, capacity_cells, tail, n_strings_out);
-            case 8: return invert_runs_t<u64>(img, R, (u32)sb, (u32)fb, (u64 *)dev_out, capacity_cells, tail, n_strings_out);
+            case 1: return invert_runs_t<u8>(img, R, (u32)sb, (u32)fb, (u8 *)dev_out, capacity_cells, W, tail, n_strings_out);
+            case 2: return invert_runs_t<u16>(img, R, (u32)sb, (u32)fb, (u16 *)dev_out, capacity_cells, W, tail, n_strings_out);
+            case 4: return invert_runs_t<u32>(img, R, (u32)sb, (u32)fb, (u32 *)dev_out, capacity_cells, W, tail, n_strings_out);
+            case 8: return invert_runs_t<u64>(img, R, (u32)sb, (u32)fb, (u64 *)dev_out, capacity_cells, W, tail, n_strings_out);
             default: throw prim::Error(-22, "bad cell width");
         }
     }
@@ -5570,6 +5694,9 @@ class Engine {
         if (sb == 0 || sb > 8 || fb == 0 || fb > 8 || (image_bytes - 16) % (sb + fb)) throw prim::Error(-22, "bad .rl_bwt header");
         u64 R = (image_bytes - 16) / (sb + fb);
         const u8 *img = (const u8 *)dev_image;
+        if (!(cell_bytes == 1 || cell_bytes == 2 || cell_bytes == 4 || cell_bytes == 8)) throw prim::Error(-22, "bad cell width");
+        WideSyms W;
+        image_symbols(img, R, (u32)sb, (u32)fb, cell_bytes, W);
         // Two index forms.  Per POSITION (LF array: one gather per symbol of a string, (12 + 3 * sizeof(idx_t)) bytes per symbol
         // while it is built) when that fits the device comfortably; per RUN (two dependent gathers per symbol, 30-50 bytes per
         // run) otherwise -- the 10 GB headline image needs 360 GB in the first form and ~100 GB in the second.
@@ -5578,18 +5705,18 @@ class Engine {
         if (prim::sw().invert) by_runs = prim::sw().invert == 'r';
         if (by_runs) {
             switch (cell_bytes) {
-                case 1: return invert_runs_t<u8>(img, R, (u32)sb, (u32)fb, (u8 *)dev_text_out, capacity_cells);
-                case 2: return invert_runs_t<u16>(img, R, (u32)sb, (u32)fb, (u16 *)dev_text_out, capacity_cells);
-                case 4: return invert_runs_t<u32>(img, R, (u32)sb, (u32)fb, (u32 *)dev_text_out, capacity_cells);
-                case 8: return invert_runs_t<u64>(img, R, (u32)sb, (u32)fb, (u64 *)dev_text_out, capacity_cells);
+                case 1: return invert_runs_t<u8>(img, R, (u32)sb, (u32)fb, (u8 *)dev_text_out, capacity_cells, W);
+                case 2: return invert_runs_t<u16>(img, R, (u32)sb, (u32)fb, (u16 *)dev_text_out, capacity_cells, W);
+                case 4: return invert_runs_t<u32>(img, R, (u32)sb, (u32)fb, (u32 *)dev_text_out, capacity_cells, W);
+                case 8: return invert_runs_t<u64>(img, R, (u32)sb, (u32)fb, (u64 *)dev_text_out, capacity_cells, W);
                 default: throw prim::Error(-22, "bad cell width");
             }
         }
         switch (cell_bytes) {
-            case 1: return invert_t<u8>(img, R, (u32)sb, (u32)fb, (u8 *)dev_text_out, capacity_cells);
-            case 2: return invert_t<u16>(img, R, (u32)sb, (u32)fb, (u16 *)dev_text_out, capacity_cells);
-            case 4: return invert_t<u32>(img, R, (u32)sb, (u32)fb, (u32 *)dev_text_out, capacity_cells);
-            case 8: return invert_t<u64>(img, R, (u32)sb, (u32)fb, (u64 *)dev_text_out, capacity_cells);
+            case 1: return invert_t<u8>(img, R, (u32)sb, (u32)fb, (u8 *)dev_text_out, capacity_cells, W);
+            case 2: return invert_t<u16>(img, R, (u32)sb, (u32)fb, (u16 *)dev_text_out, capacity_cells, W);
+            case 4: return invert_t<u32>(img, R, (u32)sb, (u32)fb, (u32 *)dev_text_out, capacity_cells, W);
+            case 8: return invert_t<u64>(img, R, (u32)sb, (u32)fb, (u64 *)dev_text_out, capacity_cells, W);
             default: throw prim::Error(-22, "bad cell width");
         }
     }
@@ -5775,6 +5902,9 @@ class Engine {
         if (bits < 1 || bits > 63) throw prim::Error(-22, "split_runs: bits must be in [1, 63]");
         const u64 L = (1ull << bits) - 1, B = block_size, R = h.R;
         const u32 fb2 = (u32)((bits + 7) / 8);
+        // (the pieces carry their symbol in 32 bits: a wider one is refused, not cut)
+        if (h.sb > 4 && prim::reduce_max<u64>(R, ImageSymIn{(const u8 *)dev_image, (u32)h.sb, (u32)h.fb}, "split.max_sym") >> 32)
+            throw prim::Error(-22, "split_runs: symbols >= 2^32 are not supported");
         DBuf<u32> rsym(R);
         DBuf<idx_t> rlen(R), rpos(R + 1), jbase(R + 1);
         prim::for_each(R, UnpackRunsFn{(const u8 *)dev_image, (u32)h.sb, (u32)h.fb, rsym.p, rlen.p}, "split.unpack");

@@ -3029,7 +3029,7 @@ GRL_DEV bool lb_lookback(const u64 *status, u64 t, u64 patience, u64 &excl) {
 }
 template <class LT, int SPT> struct SmShared {
     static constexpr int kSmTile = kBlock * SPT;
-    u32 sym[kSmTile + kSmTile / 32];            // bit 31: TAKE (symbols are < 2^30); skewed by one slot per 32.  Emit: the staged heads' symbols
+    u32 sym[kSmTile + kSmTile / 32];            // bit 31: TAKE (level-0 symbols or their ranks, and metasymbols, are < 2^30); skewed by one slot per 32.  Emit: the staged heads' symbols
     LT len[kSmTile + kSmTile / 32];             // ... and their positions
     Pair<LT, LT> w2[4];
     u32 w1[4];
@@ -3474,6 +3474,187 @@ inline bool stream_merge_onepass(u64 G, SEG seg, SmPlan<IDX> &plan, u32 *osym, I
     }
     dev_free(queue);
     return true;
+}
+
+// ------------------------------------------------------------------ alphabet compaction
+// n cells of 4 or 8 bytes -> the sorted distinct values and, for every cell, the rank of its value among them (u32).
+// ac_collect gathers the distinct values in a global open-addressing table of 2^bits slots of 16 bytes (key, rank).  A
+// workgroup first looks a value up in a set of its own in LDS (kAcSetSlots words): a value costs one global compare-and-swap
+// per workgroup that meets it, not one per occurrence.  No workgroup waits for another; every probe loop is bounded by its
+// table's size.  When the table passes its fill limit (half the slots) a flag is raised, the lanes stop inserting and the
+// caller takes the general regime (a radix sort of (value, position): engine_impl.hpp, alphabet_compact).
+// ac_rank then sorts the collected values and ranks the cells: by binary search in a copy of the sorted values in LDS while
+// they fit (kAcLdsValues), through the ranks written beside the table's keys otherwise.
+// ~0 never occurs in a text (max_sym <= 2^64 - 5 is checked before) and is the empty word of both tables.
+static constexpr u64 kAcEmpty = ~0ull;
+static constexpr int kAcSetSlots = 4096;       // 32 KiB of LDS per workgroup
+static constexpr int kAcSetProbes = 16;        // a value that finds neither itself nor a free word in that many goes to the global table
+static constexpr u32 kAcLdsValues = 4096;      // 32 KiB of sorted values per workgroup (at 8192 the table's ranks were faster: DESIGN.md 3a)
+GRL_DEV u64 ac_slot(u64 v, int bits) { return (v * kMixMul) >> (64 - bits); }
+
+struct AcPlan {
+    u64 *tab = nullptr;        // [2 << bits]: key, rank
+    u32 *scal = nullptr;       // [0] distinct values in the table, [1] the table passed its fill limit
+    int bits = 0;
+    u64 sigma = 0;
+    bool overflow = false;
+    void release() { if (tab) dev_free(tab); if (scal) dev_free(scal); tab = nullptr; scal = nullptr; }
+};
+
+template <class cell_t>
+__global__ void __launch_bounds__(kBlock) k_ac_collect(const cell_t *t, u64 n, u64 *tab, int bits, u32 limit, u32 *scal) {
+    __shared__ u64 s_set[kAcSetSlots];
+    for (int i = threadIdx.x; i < kAcSetSlots; i += kBlock) s_set[i] = kAcEmpty;
+    __syncthreads();
+    const u64 cap = (u64)1 << bits, stride = (u64)gridDim.x * kBlock;
+    for (u64 i = (u64)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
+        const u64 v = (u64)t[i];
+        const u64 h = v * kMixMul;
+        bool seen = false;
+        u32 s = (u32)(h >> 52) & (kAcSetSlots - 1);
+        for (int p = 0; p < kAcSetProbes; p++, s = (s + 1) & (kAcSetSlots - 1)) {
+            u64 cur = s_set[s];
+            if (cur == kAcEmpty) cur = atomic_cas(&s_set[s], kAcEmpty, v);
+            if (cur == v) { seen = true; break; }
+            if (cur == kAcEmpty) break;                       // mine now: new to this workgroup
+        }
+        if (seen) continue;
+        if (load_relaxed(&scal[1])) continue;                 // the call is going to take the general regime
+        u64 g = h >> (64 - bits);
+        bool placed = false;
+        for (u64 p = 0; p < cap; p++, g = (g + 1) & (cap - 1)) {
+            u64 cur = load_relaxed(&tab[2 * g]);
+            if (cur == kAcEmpty) {
+                cur = atomic_cas(&tab[2 * g], kAcEmpty, v);
+                if (cur == kAcEmpty) {
+                    if (atomic_add(&scal[0], 1u) + 1u > limit) atomic_max(&scal[1], 1u);
+                    placed = true;
+                    break;
+                }
+            }
+            if (cur == v) { placed = true; break; }
+        }
+        if (!placed) atomic_max(&scal[1], 1u);
+    }
+}
+struct AcGatherFn {       // the table's keys, in any order
+    const u64 *tab; u64 *out; u32 *cnt;
+    GRL_DEV void operator()(u64 s) const {
+        const u64 k = tab[2 * s];
+        if (k != kAcEmpty) out[atomic_add(cnt, 1u)] = k;
+    }
+};
+struct AcSlotRankFn {     // sorted value j -> its rank beside its key
+    u64 *tab; const u64 *vals; int bits;
+    GRL_DEV void operator()(u64 j) const {
+        const u64 v = vals[j], cap = (u64)1 << bits;
+        u64 g = ac_slot(v, bits);
+        for (u64 p = 0; p < cap; p++, g = (g + 1) & (cap - 1))
+            if (tab[2 * g] == v) { tab[2 * g + 1] = j; return; }
+    }
+};
+template <class cell_t>
+struct alignas(16) AcVec { cell_t c[16 / sizeof(cell_t)]; };
+// four cells per lane: 16-byte loads of cells and one 16-byte store of ranks where both arrays are aligned (vec)
+template <class cell_t, bool LDS>
+__global__ void __launch_bounds__(kBlock) k_ac_rank(const cell_t *t, u64 n, const u64 *vals, u32 sigma, const u64 *tab, int bits, u32 *ranks, bool vec) {
+    extern __shared__ __attribute__((aligned(16))) u64 s_vals[];
+    if (LDS) {
+        for (u32 i = threadIdx.x; i < sigma; i += kBlock) s_vals[i] = vals[i];
+        __syncthreads();
+    }
+    constexpr int PER = 16 / (int)sizeof(cell_t);
+    const u64 groups = (n + 3) / 4, stride = (u64)gridDim.x * kBlock, cap = (u64)1 << bits;
+    for (u64 g = (u64)blockIdx.x * kBlock + threadIdx.x; g < groups; g += stride) {
+        const u64 b = g * 4;
+        const bool full = vec && b + 4 <= n;
+        u64 v[4];
+        u32 r[4];
+        if (full) {
+#pragma unroll
+            for (int q = 0; q < 4 / PER; q++) {
+                const AcVec<cell_t> x = reinterpret_cast<const AcVec<cell_t> *>(t + b)[q];
+#pragma unroll
+                for (int k = 0; k < PER; k++) v[q * PER + k] = (u64)x.c[k];
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; k++) v[k] = b + k < n ? (u64)t[b + k] : 0;
+        }
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            if (LDS) {
+                u32 lo = 0, hi = sigma;
+                while (lo < hi) { const u32 mid = (lo + hi) >> 1; if (s_vals[mid] < v[k]) lo = mid + 1; else hi = mid; }
+                r[k] = lo;
+            } else {
+                r[k] = 0;
+                if (b + k < n) {
+                    u64 s = ac_slot(v[k], bits);
+                    for (u64 p = 0; p < cap; p++, s = (s + 1) & (cap - 1)) {
+                        const ulonglong2 e = reinterpret_cast<const ulonglong2 *>(tab)[s];
+                        if (e.x == v[k]) { r[k] = (u32)e.y; break; }
+                    }
+                }
+            }
+        }
+        if (full) *reinterpret_cast<uint4 *>(ranks + b) = make_uint4(r[0], r[1], r[2], r[3]);
+        else {
+#pragma unroll
+            for (int k = 0; k < 4; k++) if (b + k < n) ranks[b + k] = r[k];
+        }
+    }
+}
+
+inline int ac_table_bits() {
+    const int b = sw().alpha_table_bits;
+    return b < 2 ? 2 : (b > 26 ? 26 : b);
+}
+// the distinct values of t[0, n) into a fresh table; P.overflow: more than half its slots would be taken
+template <class cell_t>
+inline void ac_collect(const cell_t *t, u64 n, AcPlan &P) {
+    P.release();
+    P.bits = ac_table_bits();
+    const u64 cap = (u64)1 << P.bits;
+    P.tab = (u64 *)dev_alloc(cap * 16);
+    P.scal = (u32 *)dev_alloc(16);
+    dev_memset(P.tab, 0xFF, cap * 16);
+    dev_memset(P.scal, 0, 16);
+    prof_begin("alpha.collect", n * sizeof(cell_t));
+    hipLaunchKernelGGL((k_ac_collect<cell_t>), dim3(grid_for(n, kBlock)), dim3(kBlock), 0, rt().stream, t, n, P.tab, P.bits, (u32)(cap / 2), P.scal);
+    prof_end();
+    after_launch("alpha.collect");
+    u32 h[2];
+    d2h(h, P.scal, 8);
+    P.sigma = h[0];
+    P.overflow = h[1] != 0;
+}
+// values[P.sigma] = the sorted distinct values, ranks[i] = the rank of t[i]
+template <class cell_t>
+inline void ac_rank(const cell_t *t, u64 n, AcPlan &P, int key_bits, u64 *values, u32 *ranks) {
+    const u64 cap = (u64)1 << P.bits, sigma = P.sigma;
+    u64 *tmp = (u64 *)dev_alloc((sigma ? sigma : 1) * 8);
+    dev_memset(P.scal, 0, 16);
+    for_each(cap, AcGatherFn{P.tab, values, P.scal}, "alpha.values");
+    if (sort_keys<u64>(values, tmp, sigma, 0, key_bits < 1 ? 1 : key_bits, "alpha.sort")) d2d(values, tmp, sigma * 8);
+    dev_free(tmp);
+    const bool vec = (((uintptr_t)t | (uintptr_t)ranks) & 15) == 0;
+    const bool lds = sigma <= kAcLdsValues;
+    const unsigned grid = grid_for((n + 3) / 4, kBlock);
+    if (lds) {
+        prof_begin("alpha.rank_lds", n * (sizeof(cell_t) + 4));
+        hipLaunchKernelGGL((k_ac_rank<cell_t, true>), dim3(grid), dim3(kBlock), (size_t)sigma * 8, rt().stream, t, n, (const u64 *)values, (u32)sigma,
+                           (const u64 *)P.tab, P.bits, ranks, vec);
+        prof_end();
+        after_launch("alpha.rank_lds");
+    } else {
+        for_each(sigma, AcSlotRankFn{P.tab, values, P.bits}, "alpha.slot_ranks");
+        prof_begin("alpha.rank_table", n * (sizeof(cell_t) + 4));
+        hipLaunchKernelGGL((k_ac_rank<cell_t, false>), dim3(grid), dim3(kBlock), 0, rt().stream, t, n, (const u64 *)values, (u32)sigma,
+                           (const u64 *)P.tab, P.bits, ranks, vec);
+        prof_end();
+        after_launch("alpha.rank_table");
+    }
 }
 
 }   // namespace prim

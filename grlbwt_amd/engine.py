@@ -32,6 +32,7 @@ ABI_SYMBOLS = [
     "grlbwt_selftest", "grlbwt_profile_enable", "grlbwt_profile_dump", "grlbwt_dist_build", "grlbwt_memory_usage", "grlbwt_invert_image", "grlbwt_invert_image_tails",
     "grlbwt_image_plain", "grlbwt_image_rle", "grlbwt_image_stats_get", "grlbwt_image_split_runs",
     "grlbwt_level_grammar_size", "grlbwt_level_grammar_download",
+    "grlbwt_alphabet_size", "grlbwt_alphabet_download", "grlbwt_alphabet_compact_device",
 ]
 
 
@@ -174,6 +175,9 @@ def load_library(path=None, allow_test_standin=False):
     L.grlbwt_image_rle.argtypes = [vp, vp, u64, vp, vp, u64, C.POINTER(u64)]
     L.grlbwt_image_stats_get.argtypes = [vp, vp, u64, C.POINTER(ImageStats)]
     L.grlbwt_image_split_runs.argtypes = [vp, vp, u64, i32, u64, vp, u64, C.POINTER(SplitInfo)]
+    L.grlbwt_alphabet_size.argtypes = [vp, C.POINTER(u64)]
+    L.grlbwt_alphabet_download.argtypes = [vp, vp]
+    L.grlbwt_alphabet_compact_device.argtypes = [vp, vp, u64, i32, vp, vp, u64, C.POINTER(u64)]
     L.grlbwt_profile_enable.argtypes = [vp, i32]
     L.grlbwt_profile_dump.argtypes = [vp, C.c_char_p, u64]
     _libs[path] = L
@@ -259,6 +263,27 @@ class Context:
         s = Stats()
         self._ck(self.L.grlbwt_get_stats(self._h, C.byref(s)))
         return _as_dict(s)
+
+    def alphabet_size(self):
+        """Distinct values of a text that was compacted when it was loaded (a symbol of 2^30 - 8 or more); 0: not compacted."""
+        n = C.c_uint64()
+        self._ck(self.L.grlbwt_alphabet_size(self._h, C.byref(n)))
+        return n.value
+
+    def alphabet_download(self):
+        """The sorted distinct values of a compacted text: rank r of the stage-wise inspection stands for values[r]."""
+        import numpy as np
+        out = np.zeros(self.alphabet_size(), dtype=np.uint64)
+        self._ck(self.L.grlbwt_alphabet_download(self._h, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def alphabet_compact(self, src_ptr, n_cells, cell_bytes, ranks_ptr, values_ptr, capacity_values):
+        """The compaction alone, device buffer to device buffer: ranks (uint32 per cell) and sorted distinct values (uint64);
+        returns their number."""
+        k = C.c_uint64(0)
+        self._ck(self.L.grlbwt_alphabet_compact_device(self._h, C.c_void_p(src_ptr), n_cells, cell_bytes, C.c_void_p(ranks_ptr),
+                                                       C.c_void_p(values_ptr), capacity_values, C.byref(k)))
+        return k.value
 
     # ---- phases (names follow the reference) -----------------------------
     def parse_round(self):

@@ -91,6 +91,37 @@ def zipf_tokens(n_cells, doc_len=1000, vocab=65000, s=1.1, seed=20260005):
     return out.reshape(-1)
 
 
+def wide_tokens(n_cells, doc_len=1000, vocab=65000, bits=64, seed=20260007, s=1.1, with_ids=False):
+    """Token documents with wide ids (-a 4 for bits <= 32, -a 8 above): zipf_tokens' documents whose ids 0..vocab are sent
+    through a seeded injective scramble into `bits`-bit values, so that the order of the values is unrelated to their
+    frequency.  The separator is the smallest of the values; none is above 2^bits - 5.
+    with_ids: (cells, ids, table) with cells == table[ids]."""
+    if not 8 <= bits <= 64:
+        raise ValueError("bits must be in [8, 64]")
+    if vocab + 1 > (1 << bits) // 4:
+        raise ValueError("vocab does not fit the value range")
+    n_docs = n_cells // (doc_len + 1)
+    w = np.arange(1, vocab + 1, dtype=np.float64) ** (-s)
+    cdf = np.cumsum(w)
+    cdf /= cdf[-1]
+    z = splitmix64(seed, n_docs * doc_len)
+    u = (z >> np.uint64(11)).astype(np.float64) * (1.0 / (1 << 53))
+    tok = np.minimum(np.searchsorted(cdf, u) + 1, vocab).reshape(n_docs, doc_len)
+    ids = np.zeros((n_docs, doc_len + 1), dtype=np.int64)
+    ids[:, :doc_len] = tok
+    # the scramble: the first vocab + 1 distinct values of a splitmix64 stream, in the order of the stream
+    cand = splitmix64(seed + 1, 4 * (vocab + 1)) >> np.uint64(64 - bits)
+    cand = cand[cand <= np.uint64((1 << bits) - 5)]
+    vals, first = np.unique(cand, return_index=True)
+    table = vals[np.argsort(first, kind="stable")][:vocab + 1].copy()
+    if len(table) < vocab + 1:
+        raise ValueError("scramble ran out of distinct values")
+    m = int(np.argmin(table))
+    table[0], table[m] = table[m], table[0]
+    cells = table[ids.reshape(-1)].astype(np.uint32 if bits <= 32 else np.uint64)
+    return (cells, ids.reshape(-1), table) if with_ids else cells
+
+
 def uniform_reads_torch(n_reads, read_len, seed=20260001, device="cuda", chunk_reads=4_000_000):
     """Same bytes as uniform_reads(), generated on `device` with torch (for multi-GB inputs that
     should never exist on the host).  int64 arithmetic wraps like uint64; shifts are masked to be logical."""

@@ -42,7 +42,10 @@ extern "C" {
 #define GRLBWT_EILLFORMED (-84) /* reference: "Error: the file is ill formed", exit(1) (utils.cpp:177-180) */
 #define GRLBWT_ERANGE (-75)     /* input beyond what this build supports -- the limits, all checked:
                                  *   collection            < 2^40 cells (64-bit positions from 2^32 - 256 cells on);
-                                 *   symbols, and the alphabet of every level (metasymbols of a round)       < 2^30;
+                                 *   symbols: any value up to 2^64 - 5 (the header width comes from max_sym + 4), fewer than 2^30 - 16 DISTINCT ones --
+                                 *   a text with a symbol of 2^30 - 8 or more is built on the ranks of its values (grlbwt_alphabet_size),
+                                 *   single-GPU only: grlbwt_dist_build refuses it on every rank;
+                                 *   the alphabet of every level >= 1 (metasymbols of a round)               < 2^30;
                                  *   distinct phrases of one round < 2^32, their symbols (the round's dictionary) < 2^32
                                  *   (collection-level mode: per rank's part of the merged dictionary and per key range of its
                                  *   suffixes, while every phrase frequency is < 2^32 and no phrase has >= 512 cells);
@@ -135,6 +138,20 @@ int grlbwt_text_load_file_range(grlbwt_ctx *ctx, const char *path, uint64_t offs
  * that was not there fails with GRLBWT_EINVAL; other changes give the image of neither text). */
 int grlbwt_text_attach_device(grlbwt_ctx *ctx, const void *dev_cells, uint64_t n_cells, int cell_bytes);
 int grlbwt_get_stats(const grlbwt_ctx *ctx, grlbwt_stats *out);
+
+/* ---- wide symbols: the BWT depends only on the order and the equality of the symbols, so a text of 4- or 8-byte cells with a
+ * symbol of 2^30 - 8 or more is replaced, when it is loaded, by the ranks of its values among its distinct values; the
+ * statistics and the image carry the values.  With GRLBWT_FLAG_KEEP_LEVELS everything at level 0 of such a build is in RANK
+ * space: round_info[0].sigma is the number of distinct values, the grammar cells, the pre-BWT and the level-0 BWT of the
+ * stage-wise inspection hold ranks (the separator is rank 0) and codes above them.
+ * grlbwt_alphabet_size: *n_distinct = 0 when the loaded text was not compacted.  grlbwt_alphabet_download: the sorted values. */
+int grlbwt_alphabet_size(const grlbwt_ctx *ctx, uint64_t *n_distinct);
+int grlbwt_alphabet_download(const grlbwt_ctx *ctx, uint64_t *values_out);
+/* the compaction alone, device buffer to device buffer: dev_ranks_u32[i] = the rank of cell i (n_cells words), dev_values_u64 =
+ * the sorted distinct values (GRLBWT_EINVAL when there are more than capacity_values; *n_distinct is set all the same).
+ * cell_bytes 4 or 8. */
+int grlbwt_alphabet_compact_device(grlbwt_ctx *ctx, const void *dev_cells, uint64_t n_cells, int cell_bytes, void *dev_ranks_u32,
+                                   void *dev_values_u64, uint64_t capacity_values, uint64_t *n_distinct);
 
 /* ---- FASTA/FASTQ ingestion: replaces is_fastx / check_gzip (external/cdt/lib/utils.cpp:13-30,53-60)
  * and fastx2plain_format (external/bioparsers/lib/fastx_handler.cpp:7-58, kseq.h:179-220), which the reference's
