@@ -3619,6 +3619,23 @@ class Engine {
             }
             return out;
         }
+        // A rank-local section: skipped once a failure is pending; a prim::Error it raises is recorded (fail()).
+        template <class F>
+        void local(F &&fn) const { if (!pending) { try { fn(); } catch (const prim::Error &e) { fail(e); } } }
+        // One counter exchange for an all-to-all: scnt[d] = what I send to rank d.  rcnt[g] = what rank g sends me, their sum, the
+        // largest block of the whole exchange, and the matrix itself (mat[g * size + d] = what g sends to d).
+        // (unpack: the same from a matrix that sits in the columns [off, off + size) of gathered rows `row` wide)
+        struct Counts { std::vector<u64> rcnt; u64 total = 0, maxb = 0; std::vector<u64> mat; };
+        Counts unpack(const std::vector<u64> &mat, u64 row, u64 off) const {
+            Counts c;
+            c.rcnt.assign(size, 0);
+            for (int g = 0; g < size; g++) {
+                c.rcnt[g] = mat[(u64)g * row + off + rank]; c.total += c.rcnt[g];
+                for (int d = 0; d < size; d++) c.maxb = std::max(c.maxb, mat[(u64)g * row + off + d]);
+            }
+            return c;
+        }
+        Counts counts(const std::vector<u64> &scnt) const { std::vector<u64> m = allgather_u64(scnt); Counts c = unpack(m, size, 0); c.mat = std::move(m); return c; }
         // counts in elements of `elem` bytes; send blocks packed in destination order, receive blocks in source order.
         // `max_block` = the largest block of the whole exchange in elements (all ranks pass the same value: they hold the
         // count matrix): blocks above the limit go in several rounds, the same number on every rank.  (torch 2.10 + RCCL
@@ -3698,8 +3715,7 @@ class Engine {
     static u64 test_dict_part_pad() { return prim::sw().test_dict_part_pad; }
     void bucket_by_owner(const Comm &C, const u64 *dsb, DBuf<u64> &rec, u64 n, std::vector<u64> &cnt, const char *name, DBuf<u32> *own_of = nullptr) {
         const int N = C.size;
-        int obits = (int)bitlen64((u64)N - 1);
-        if (obits < 1) obits = 1;
+        const int obits = std::max((int)bitlen64((u64)N - 1), 1);
         DBuf<u32> own, own2(n);
         DBuf<u64> rec2(n), bound(2 * ((u64)N + 1));
         if (own_of) own = std::move(*own_of);
@@ -3716,16 +3732,12 @@ class Engine {
     // this rank can have (memory, an internal check) is agreed on at the counter exchanges: every rank raises.
     template <class A, class F>
     void owner_round_trip(const Comm &C, const u64 *dsb, DBuf<u64> &req, u64 n, DBuf<A> &back, F answer, const char *name, const char *xname, DBuf<u32> *own_of = nullptr) {
-        const int N = C.size, me = C.rank;
-        std::vector<u64> scnt(N, 0), rcnt(N, 0);
+        std::vector<u64> scnt(C.size, 0);
         try { bucket_by_owner(C, dsb, req, n, scnt, name, own_of); }
         catch (const prim::Error &e) { C.fail(e); std::fill(scnt.begin(), scnt.end(), 0); }
-        std::vector<u64> mat = C.allgather_u64(scnt);            // (raises on every rank if one of them failed above)
-        u64 nr = 0, maxb = 0;
-        for (int g = 0; g < N; g++) {
-            rcnt[g] = mat[(u64)g * N + me]; nr += rcnt[g];
-            for (int d = 0; d < N; d++) maxb = std::max(maxb, mat[(u64)g * N + d]);
-        }
+        const auto cn = C.counts(scnt);                          // (raises on every rank if one of them failed above)
+        const std::vector<u64> &rcnt = cn.rcnt;
+        const u64 nr = cn.total, maxb = cn.maxb;
         DBuf<u64> mine;
         DBuf<A> ans;
         try { mine.alloc(nr); ans.alloc(nr); back.alloc(n); } catch (const prim::Error &e) { C.fail(e); }
@@ -3736,6 +3748,7 @@ class Engine {
         C.named(xname).alltoall(ans.p, rcnt, back.p, scnt, sizeof(A), maxb);
     }
 
+    // ---- the dictionary stage: a5-a9 -------------------------------------------------------------------------------------------
     // a5-a8 on D distinct phrases given as (position in t, length, frequency, ends-with-terminator);
     // fills L (grammar, has_hocc, pre-BWT, M) and phrase_val[k] = rank<<2 | (freq>1)<<1 | lastT.
     // With a communicator (collection-level mode: t, ph_* are the MERGED dictionary, identical on every rank) the suffix
@@ -3743,80 +3756,210 @@ class Engine {
     // keys, so a group never spans two ranks and rank order = sorted order; the refinement reads only the dictionary, so every
     // rank finishes its own key range without talking to the others; the group stage's outputs are all-gathered.  The O(S)
     // streaming passes (dictionary, grammar walk) stay replicated.  Same kernels in both modes.
+    // dict_stage() at the end is the list of steps; DictIn is what it is given, DictStage holds what the steps share and the steps.
     template <class cell_t, bool FIRST>
-    void dict_stage(const Comm *C, const cell_t *t, CellOps<cell_t, FIRST> ops, u64 D, u64 S, u32 maxlen, const u64 *ph_pos, const idx_t *ph_freq,
-                    const u32 *ph_off, const u8 *ph_lastT, u32 sigma, LevelData &L, DBuf<u32> &phrase_val,
-                    const u32 *fused_ph_slot = nullptr, u32 *fused_slot_val = nullptr,        // (both set: the values go straight to the slots)
-                    const prim::U128 *pkeys = nullptr, u64 pDs = 0, int pkb = 0,              // (phrases [0, pDs) given by their records)
-                    u32 pslot0 = 0,                                   // (... and their slots are pslot0 + k: GroupPhraseValFn)
-                    const std::vector<u64> *dbase = nullptr,          // (collection-level mode: rank g merged the phrases [dbase[g], dbase[g + 1])
-                    const std::vector<u64> *sbase = nullptr,          //  = the dictionary positions [sbase[g], sbase[g + 1]))
-                    bool sharded_dict = false,                        // (t, ph_* describe MY part of the dictionary only: see below)
-                    u64 maxfreq = ~0ull) {                            // (the largest phrase frequency of the round, where the caller knows it)
-        L.info.D = D; L.info.S = S; L.info.max_phrase_len = maxlen;
-        // DICTIONARY SHARDED BY OWNER (collection-level mode, round 5): every rank holds the phrases it merged and nothing of the
-        // others' -- t, ph_pos, ph_freq, ph_off, ph_lastT are LOCAL arrays of Dl phrases / Sl symbols, a dictionary position
-        // travels as the global number s0 + local offset, a phrase as d0 + local number.  What a rank needs to know about a position
-        // it does not own it ASKS of the owner (owner_round_trip): the next K symbols of an unresolved suffix in every refinement
-        // round, and what the group fold reads per member (frequency, left symbol, flags, phrase).  No replicated dictionary, no
-        // all-gather of the merged phrases, no O(S) or O(D) pass that every rank repeats.
-        const bool sharded = C && sharded_dict && dbase && sbase;
-        const u64 d0 = sharded ? (*dbase)[C->rank] : 0, s0 = sharded ? (*sbase)[C->rank] : 0;
-        const u64 Dl = sharded ? (*dbase)[C->rank + 1] - d0 : D, Sl = sharded ? (*sbase)[C->rank + 1] - s0 - test_dict_part_pad() : S;
-        // With every frequency below 2^32 the 8 bytes the group fold reads about a suffix (frequency, left symbol, flags) travel WITH
-        // its (key, position) record in the sample-sort exchange: no round trip for them afterwards (24 bytes per suffix over the
-        // fabric and a gather pass on the owner -- 3.3 GB and ~14 ms per rank at N = 8 of the 10 GB collection).  The values a rank
-        // sorts are then ARRIVAL INDICES; pos_arr[] / rec_arr[] give the position and the record of an arrival.
-        const bool rec_round_trip = prim::sw().dist_rec_round_trip;
-        const bool carry = sharded && maxfreq < 0xFFFFFFFFull && !rec_round_trip;
-        // In this form a position is (owner, OFFSET in the owner's part): the owner of an arrival is the rank it came from (arrivals
-        // sit in sender order), so 32-bit fields address a dictionary whose parts are each below 2^32 symbols, whatever their sum.
-        if (sharded && !carry && S >= 0xFFFFFFF0ull) throw prim::Error(-75, "dictionary too large (>= 2^32 symbols and a phrase frequency >= 2^32, or the records' round trip forced by a test)");
-        const u64 sq = carry ? 0 : s0;           // what the owner subtracts from a position it is asked about
-        DBuf<u32> pos_arr, perm_ai, pown;        // (carry) offset of every arrival; the sorted arrival indices once perm holds offsets again; owner by slot
-        DBuf<u64> abounds;                       // (carry) arrivals [abounds[g], abounds[g + 1]) came from rank g
-        DBuf<u64> rec_arr;                       // (carry) record of every arrival
-        DBuf<u64> dsb;                           // sbase[] on the device (owner of a position)
-        if (C && sbase) { dsb.alloc((u64)C->size + 1); prim::h2d(dsb.p, sbase->data(), ((u64)C->size + 1) * 8); }
-        DBuf<u32> dict_sym(Sl), dict_phr(Sl);
-        RankBits pbits;                          // phrase starts over the dictionary positions (dictionary build, suffix refinement)
-        {
-            StageTimer st(&tm.dict_sort, "dict_sort");
-            build_rankbits32(pbits, ph_off, Dl, Sl + 1, "dict_build");
-            // (4 positions per lane: 16 per lane, four phrases walked one after the other, was latency-bound -- 42 ms at 10 GB)
-            prim::for_each((Sl + 3) / 4, DictBuildFn<cell_t, FIRST, 4>{t, ops, ph_off, Dl, Sl, ph_pos, dict_sym.p, dict_phr.p, pbits.words.p, pbits.base.p,
-                                                                       pkeys, pDs, pkb}, "dict_build");
+    struct DictIn {
+        const Comm *C = nullptr;                          // (nullptr: this engine holds the whole collection)
+        const cell_t *t = nullptr; CellOps<cell_t, FIRST> ops{};
+        u64 D = 0, S = 0; u32 maxlen = 0, sigma = 0;
+        const u64 *ph_pos = nullptr; const idx_t *ph_freq = nullptr; const u32 *ph_off = nullptr; const u8 *ph_lastT = nullptr;
+        const u32 *fused_ph_slot = nullptr; u32 *fused_slot_val = nullptr;        // (both set: the values go straight to the slots)
+        const prim::U128 *pkeys = nullptr; u64 pDs = 0; int pkb = 0;              // (phrases [0, pDs) given by their records)
+        u32 pslot0 = 0;                                   // (... and their slots are pslot0 + k: GroupPhraseValFn)
+        const std::vector<u64> *dbase = nullptr;          // (collection-level mode: rank g merged the phrases [dbase[g], dbase[g + 1])
+        const std::vector<u64> *sbase = nullptr;          //  = the dictionary positions [sbase[g], sbase[g + 1]))
+        bool sharded_dict = false;                        // (t, ph_* describe MY part of the dictionary only: see dict_stage)
+        u64 maxfreq = ~0ull;                              // (the largest phrase frequency of the round, where the caller knows it)
+    };
+    // -- the pieces that the two suffix sorts and the branches of the later steps share --
+    // Shape of a first-pass key: as many symbols of b bits as fit 64 key bits per pass (up to 8 radix passes over all suffixes in the
+    // first one), above `rb` bits of run field (RunKeys; 0 = plain keys).  Symbols too wide to share a key with a run field: rb = 0.
+    struct SortKeyShape { int b, K, rb, kbits; u64 sent; };
+    static SortKeyShape sort_key_shape(u32 sigma, u32 maxlen, int rb) {
+        SortKeyShape s;
+        s.b = std::max((int)bitlen64(sigma), 1); s.K = std::min(std::max((64 - rb) / s.b, 1), 16);
+        // (GRLBWT_SORT_KMAX, dev tier: fewer symbols in the first sort's key -- fewer radix passes, more left to the refinement)
+        const int kmax = prim::sw().sort_kmax;
+        if (kmax >= 1 && s.K > kmax) s.K = kmax;
+        if ((u64)s.K > (u64)maxlen + 1) s.K = (int)maxlen + 1;
+        s.rb = (rb && s.K * s.b + rb > 64) ? 0 : rb;
+        s.kbits = s.K * s.b + s.rb;                                   // sort bits of a key
+        s.sent = ((1ull << s.b) - 1ull) << s.rb;                      // (the last symbol of a key's window: all ones = the phrase has ended)
+        return s;
+    }
+    // The (key, position) records of the kept suffixes among the positions [q0, q0 + nq), ordered (stable) by the rank that owns
+    // their key range (splitters dspl[]): sk/sp (and sr, the records the group fold reads, where they travel along), scnt[d] of
+    // them for rank d.
+    static void key_records_by_owner(const SufKeep &keep, const u32 *dict_sym, u64 q0, u64 nq, const SortKeyShape &ks, const RunKeys &rk, const u64 *dspl, int N,
+                              u32 pos_base, const idx_t *ph_freq, u32 bwt_code, DBuf<u64> &sk, DBuf<u32> &sp, DBuf<u64> *sr, std::vector<u64> &scnt) {
+        DBuf<u32> kex(nq + 1);
+        const u64 nk = prim::exclusive_scan<u32>(nq, KeepRangeIn{keep, q0}, kex.p, false, "suffix_keep");
+        DBuf<u64> lk(nk), bound(2 * ((u64)N + 1));
+        DBuf<u32> lp(nk), own(nk), own2(nk), idx(nk), idx2(nk);
+        DBuf<u64> lr;
+        if (sr) lr.alloc(nk);
+        prim::for_each(nq, KeyRangeFn{keep, kex.p, q0, dict_sym, ks.K, ks.b, dspl, N, lk.p, lp.p, own.p, idx.p, rk, pos_base,
+                                      sr ? lr.p : nullptr, ph_freq, bwt_code}, "suffix_keys0");
+        const int obits = std::max((int)bitlen64((u64)N - 1), 1);
+        const int res = prim::sort_pairs<u32, u32>(own.p, idx.p, own2.p, idx2.p, nk, 0, obits, "dist.key_owner_sort");
+        sk.alloc(nk); sp.alloc(nk);
+        prim::for_each(nk, GatherKeyPosFn{res ? idx2.p : idx.p, lk.p, lp.p, sk.p, sp.p}, "dist.key_owner_sort");
+        if (sr) { sr->alloc(nk); prim::for_each(nk, GatherU64Fn{res ? idx2.p : idx.p, lr.p, sr->p}, "dist.key_owner_sort"); }
+        prim::for_each((u64)N + 1, KeyBoundFn{res ? own2.p : own.p, nk, nullptr, bound.p}, "dist.owner_bounds");
+        std::vector<u64> bh = bound.to_host(2 * ((u64)N + 1));
+        for (int d = 0; d < N; d++) scnt[d] = bh[2 * (d + 1)] - bh[2 * d];
+    }
+    // The first sort of the Sg (key, value) pairs ka[]/perm[] and what the refinement starts from: group heads and the suffixes
+    // the key did not resolve.  (No host synchronisation: the buffers that go out of scope here are reused in stream order.)
+    static void first_sort_and_flags(DBuf<u64> &ka, DBuf<u32> &perm, u64 Sg, const SortKeyShape &ks, const RunKeys &rk, u8 *hflag, u8 *uflag) {
+        DBuf<u64> kb(Sg);
+        DBuf<u32> vb(Sg);
+        const u64 *k = ka.p;
+        if (prim::sort_pairs<u64, u32>(ka.p, perm.p, kb.p, vb.p, Sg, 0, ks.kbits, "suffix_sort0")) {
+            std::swap(perm, vb);                 // the result sits in the second buffer: take it, no copy
+            k = kb.p;
         }
-        // ---- a6: sort all phrase suffixes (radix on the first K symbols + refinement by symbol extension) ----------
-        u64 Sg = S;                              // my slots of the sorted order (all of them without a communicator)
+        if (rk.rb) prim::for_each(Sg, InitSkipFn{perm.p, rk.rem, (u32)ks.K, rk.skip}, "suffix_runs");
+        prim::for_each(Sg, HeadFlagFn{k, hflag}, "suffix_heads");
+        prim::for_each(Sg, FirstUnresolvedFn{k, hflag, Sg, ks.sent, uflag}, "suffix_unresolved");
+    }
+    // One refinement round: the U unresolved suffixes (slot, position, extension key, head of its group so far) are ordered inside
+    // their groups; perm[] / hflag[] take the new order and heads, unext[] says who is still unresolved (key ends in sent_r).
+    // (GRLBWT_SEG_CAP, product tier: the tests lower the limit so that ordinary inputs take the large-group path too)
+    static void order_segments(u64 U, const u8 *uhead, u32 *hex, const u64 *ukey, const u32 *uslot, const u32 *uq, u64 sent_r, int kbits_r, u32 cap,
+                        u32 *perm, u8 *hflag, u8 *unext) {
+        const u64 nseg = prim::exclusive_scan<u32>(U, ByteIn{uhead}, hex, false, "suffix_heads");
+        DBuf<u32> seg_start(nseg + 1), bex(U + 1);
+        prim::for_each(U, SegStartFn{uhead, hex, U, seg_start.p}, "suffix_gstart");
+        prim::for_each(U, SegSortSmallFn{uhead, hex, seg_start.p, uslot, uq, ukey, sent_r, cap, perm, hflag, unext}, "suffix_sort.small");
+        const u64 NB = prim::exclusive_scan<u32>(U, SegBigIn{uhead, hex, seg_start.p, cap}, bex.p, false, "suffix_sort.big_scan");
+        if (NB) {                                // groups above the cap: by key, then (stable) by group
+            DBuf<u32> bitem(NB), bidx(NB), bidx2(NB), key2(NB), key2b(NB);
+            DBuf<u64> bkey(NB), bkey2(NB);
+            prim::for_each(U, SegBigGatherFn{uhead, hex, seg_start.p, bex.p, ukey, cap, bitem.p, bkey.p, bidx.p}, "suffix_sort.big_gather");
+            const u32 *i1 = prim::sort_pairs<u64, u32>(bkey.p, bidx.p, bkey2.p, bidx2.p, NB, 0, kbits_r, "suffix_sort") ? bidx2.p : bidx.p;
+            u32 *i1o = (i1 == bidx.p) ? bidx2.p : bidx.p;
+            prim::for_each(NB, SegBigSegKeyFn{i1, bitem.p, uhead, hex, key2.p}, "suffix_sort.big_groups");
+            const int sbits = std::max((int)bitlen64(nseg), 1);
+            const int res = prim::sort_pairs<u32, u32>(key2.p, (u32 *)i1, key2b.p, i1o, NB, 0, sbits, "suffix_sort");
+            prim::for_each(NB, SegBigWriteFn{res ? key2b.p : key2.p, res ? i1o : i1, bitem.p, ukey, uq, uslot, NB, sent_r, perm, hflag, unext}, "suffix_refine");
+        }
+    }
+    // The sorted slots are cut into groups of equal suffixes at the heads: gstart[], gid[]; returns the number of groups.
+    static u64 close_groups(const u8 *hflag, u32 *ex, u64 Sg, u32 *gstart, u32 *gid) {
+        const u64 G = prim::exclusive_scan<u32>(Sg, ByteIn{hflag}, ex, false, "suffix_heads");
+        prim::for_each(Sg, GroupStartsFn{hflag, ex, Sg, gstart}, "suffix_gstart");
+        prim::for_each(Sg, DenseGidFn{hflag, ex, gid}, "suffix_gid");
+        return G;
+    }
+    // (very long phrases only: the grammar walks jump to their stops; empty otherwise)
+    static DBuf<u64> grammar_stop_bits(const u64 *dm, u64 n, u32 maxlen) {
+        DBuf<u64> stops;
+        if (maxlen >= 4096 || prim::sw().grammar_jump) {
+            stops.alloc((n + 63) / 64 + 1);
+            prim::for_each((n + 63) / 64, DmStopBitsFn{dm, n, stops.p}, "grammar_marks");
+        }
+        return stops;
+    }
+    // Every owner must be sent exactly its phrases.  (Checked for EVERY rank's column on every rank -- the matrix and the owners'
+    // phrase ranges are known to all: a rank that threw alone here would leave the others waiting in the exchange that follows.)
+    static void check_phrase_columns(const std::vector<u64> &mat, const std::vector<u64> &dbase) {
+        const u64 N = dbase.size() - 1;
+        for (u64 d = 0, col = 0; d < N; d++, col = 0) {
+            for (u64 g = 0; g < N; g++) col += mat[g * N + d];
+            if (col != dbase[d + 1] - dbase[d]) throw prim::Error(-71, "dist dictionary: whole-phrase suffix count does not match the phrase count");
+        }
+    }
+    // The stage as an object: what its steps share (work state) and the steps, in the order dict_stage() below calls them.
+    template <class cell_t, bool FIRST>
+    struct DictStage {
+        Engine &E; const DictIn<cell_t, FIRST> &I; LevelData &L; const Comm *const C;
+        bool sharded = false, carry = false, fused_vals = false;
+        u64 d0 = 0, s0 = 0, Dl = 0, Sl = 0;
+        u64 sq = 0;                              // what the owner subtracts from a position it is asked about
+        u32 bwt_code = 0, hocc_code = 0, sigma3 = 0;
+        DBuf<u32> dict_sym, dict_phr;
+        RankBits pbits;                          // phrase starts over the dictionary positions (dictionary build, suffix refinement)
+        DBuf<u64> dsb;                           // sbase[] on the device (owner of a position)
+        DBuf<u32> pos_arr, perm_ai, pown;        // (carry) offset of every arrival; the sorted arrival indices once perm holds offsets again; owner by slot
+        DBuf<u64> abounds, rec_arr;              // (carry) arrivals [abounds[g], abounds[g + 1]) came from rank g; the record of every arrival
+        u64 Sg = 0, G = 0;                       // my slots of the sorted order (all of them without a communicator), their groups
         DBuf<u32> perm, gid, gstart;
-        u64 G = 0;
-        // (with a communicator the sort and the group stage below work on THIS rank's key range -- sizes, memory and
-        // termination differ from rank to rank: a failure is recorded (Comm::fail) and raised by every rank at the counter
-        // exchange behind the group stage)
-        auto sort_local = [&] {
-            StageTimer st(&tm.dict_sort, "dict_sort");
-            int b = (int)bitlen64(sigma);
-            if (b < 1) b = 1;
-            // as many symbols as fit 64 key bits per pass (up to 8 radix passes over all suffixes in the first one)
-            // run-aware keys (RunKeys) for levels with long phrases, i.e. long runs of one symbol (GRLBWT_RUN_KEYS_MIN: from which
-            // phrase length on; the tests set 0)
+        DBuf<SufRecT<8>> recs;                   // (sharded, records fetched: what the owners answered, by slot)
+        DBuf<u32> grank, pidx, gmin, gmax; DBuf<idx_t> gacc; DBuf<u8> gfull, gflag;
+        DBuf<u32> repq, pslot;                   // pslot[k] = my group holding phrase k's whole-phrase suffix (all ones: not mine)
+        DBuf<u32> gphr;                          // ... or, single-GPU rounds, gphr[g] = the whole phrase of group g (see GroupPhraseValFn)
+        u64 M = 0, P0 = 0, Ml = 0, P0l = 0, Moff = 0, P0off = 0;
+        std::vector<u64> bbM, bbP;
+        // (the emitted pre-BWT before the merge: dead after prebwt(), held to the end of the stage as before the stage was split
+        // into steps -- releasing them earlier changes buffer lifetimes, which is a change of its own)
+        DBuf<u32> psym0, u_to_p0, pu0, merged; DBuf<idx_t> plen0;
+        DictStage(Engine &e, const DictIn<cell_t, FIRST> &in, LevelData &l) : E(e), I(in), L(l), C(in.C) {
+            L.info.D = I.D; L.info.S = I.S; L.info.max_phrase_len = I.maxlen;
+            // DICTIONARY SHARDED BY OWNER (collection-level mode, round 5): every rank holds the phrases it merged and nothing of the
+            // others' -- t, ph_pos, ph_freq, ph_off, ph_lastT are LOCAL arrays of Dl phrases / Sl symbols, a dictionary position
+            // travels as the global number s0 + local offset, a phrase as d0 + local number.  What a rank needs to know about a position
+            // it does not own it ASKS of the owner (owner_round_trip): the next K symbols of an unresolved suffix in every refinement
+            // round, and what the group fold reads per member (frequency, left symbol, flags, phrase).  No replicated dictionary, no
+            // all-gather of the merged phrases, no O(S) or O(D) pass that every rank repeats.
+            Sg = I.S;
+            sharded = C && I.sharded_dict && I.dbase && I.sbase;
+            d0 = sharded ? (*I.dbase)[C->rank] : 0; s0 = sharded ? (*I.sbase)[C->rank] : 0;
+            Dl = sharded ? (*I.dbase)[C->rank + 1] - d0 : I.D; Sl = sharded ? (*I.sbase)[C->rank + 1] - s0 - test_dict_part_pad() : I.S;
+            // With every frequency below 2^32 the 8 bytes the group fold reads about a suffix (frequency, left symbol, flags) travel WITH
+            // its (key, position) record in the sample-sort exchange: no round trip for them afterwards (24 bytes per suffix over the
+            // fabric and a gather pass on the owner -- 3.3 GB and ~14 ms per rank at N = 8 of the 10 GB collection).  The values a rank
+            // sorts are then ARRIVAL INDICES; pos_arr[] / rec_arr[] give the position and the record of an arrival.
+            // (GRLBWT_DIST_REC_ROUND_TRIP, test tier, keeps the round trip)
+            carry = sharded && I.maxfreq < 0xFFFFFFFFull && !prim::sw().dist_rec_round_trip;
+            // In this form a position is (owner, OFFSET in the owner's part): the owner of an arrival is the rank it came from (arrivals
+            // sit in sender order), so 32-bit fields address a dictionary whose parts are each below 2^32 symbols, whatever their sum.
+            if (sharded && !carry && I.S >= 0xFFFFFFF0ull) throw prim::Error(-75, "dictionary too large (>= 2^32 symbols and a phrase frequency >= 2^32, or the records' round trip forced by a test)");
+            sq = carry ? 0 : s0;
+            bwt_code = I.sigma + 1; hocc_code = I.sigma + 2; sigma3 = I.sigma + 3;
+            fused_vals = !C && I.fused_ph_slot && I.fused_slot_val;
+            if (C && I.sbase) { dsb.alloc((u64)C->size + 1); prim::h2d(dsb.p, I.sbase->data(), ((u64)C->size + 1) * 8); }
+            dict_sym.alloc(Sl); dict_phr.alloc(Sl);
+        }
+        // The group fold for one source of member records: one lane per small group, the chunks of the large ones.  idx[] = what the
+        // records are read by (perm, or the arrival indices); GroupDecideFn follows at the caller, with the record source of its flow.
+        template <class Rec>
+        void fold_groups(const u32 *idx, const Rec &rec, const u32 *phr_of, bool slot_mode) {
+            prim::for_each(G, GroupAccumSmallFn<Rec>{idx, gstart.p, rec, phr_of, bwt_code, gmin.p, gmax.p, gacc.p, gfull.p, gflag.p,
+                                                        pslot.p, gphr.p, slot_mode}, "group_accum");
+            DBuf<u32> coff(G + 1);
+            const u64 NC = prim::exclusive_scan<u32>(G, GroupChunksIn{gstart.p}, coff.p, true, "group_accum_large");
+            prim::for_each(NC, GroupAccumLargeFn<Rec>{idx, coff.p, G, gstart.p, rec, phr_of, bwt_code, gmin.p, gmax.p, gacc.p, gfull.p,
+                                                       pslot.p, gphr.p, slot_mode}, "group_accum_large");
+        }
+        // a5: the dictionary: symbol and phrase of every dictionary position
+        void build_dictionary() {
+            StageTimer st(&E.tm.dict_sort, "dict_sort");
+            build_rankbits32(pbits, I.ph_off, Dl, Sl + 1, "dict_build");
+            // (4 positions per lane: 16 per lane, four phrases walked one after the other, was latency-bound -- 42 ms at 10 GB)
+            prim::for_each((Sl + 3) / 4, DictBuildFn<cell_t, FIRST, 4>{I.t, I.ops, I.ph_off, Dl, Sl, I.ph_pos, dict_sym.p, dict_phr.p,
+                                                                       pbits.words.p, pbits.base.p, I.pkeys, I.pDs, I.pkb}, "dict_build");
+        }
+        // a6: sort all phrase suffixes (radix on the first K symbols + refinement by symbol extension), one GPU or the dictionary
+        // replicated over a communicator.
+        // (with a communicator the sort and the group stage work on THIS rank's key range -- sizes, memory and termination differ
+        // from rank to rank: a failure is recorded (Comm::fail) and raised by every rank at the counter exchange behind the group
+        // stage)
+        void suffix_sort_local() {
+            StageTimer st(&E.tm.dict_sort, "dict_sort");
+            const u64 S = I.S, D = I.D, maxlen = I.maxlen;
+            // run-aware keys (RunKeys) for levels with long phrases, i.e. long runs of one symbol (GRLBWT_RUN_KEYS_MIN, product tier:
+            // from which phrase length on; the tests set 0)
             const u64 run_min = prim::sw().run_keys_min;
             RunKeys rk;
             DBuf<u32> run_rem, run_skip;
-            if ((u64)maxlen >= run_min && S > 0) rk.rb = 1 + (int)bitlen64((u64)maxlen);
             // long phrases on one GPU: every suffix keeps its slot (no "last cell" suffixes left out), so that the refinement can
             // switch to doubling rounds (DoubleKeyFn) when the symbol extension does not finish in GRLBWT_DOUBLING_AFTER rounds
             const bool longmode = !C && (u64)maxlen >= run_min && S > 0;
             const u64 dbl_after = prim::sw().doubling_after;
-            int K = (64 - rk.rb) / b;
-            if (K < 1) K = 1;
-            if (K > 16) K = 16;
-            // (GRLBWT_SORT_KMAX: fewer symbols in the first sort's key -- fewer radix passes, more left to the refinement)
-            const int kmax = prim::sw().sort_kmax;
-            if (kmax >= 1 && K > kmax) K = kmax;
-            if ((u64)K > (u64)maxlen + 1) K = (int)maxlen + 1;
-            if (rk.rb && K * b + rk.rb > 64) rk.rb = 0;                     // (symbols too wide to share a key with a run field: plain keys)
+            const SortKeyShape ks = sort_key_shape(I.sigma, I.maxlen, (maxlen >= run_min && S > 0) ? 1 + (int)bitlen64(maxlen) : 0);
+            const int K = ks.K, b = ks.b;
+            rk.rb = ks.rb;                                               // (symbols too wide to share a key with a run field: plain keys)
             if (rk.rb) {
                 DBuf<u32> rex(S), ends(S);
                 run_rem.alloc(S); run_skip.alloc(S);
@@ -3825,16 +3968,13 @@ class Engine {
                 prim::for_each(S, RunRemFn{rex.p, ends.p, run_rem.p}, "suffix_runs");
                 rk.rem = run_rem.p; rk.skip = run_skip.p;
             }
-            const int kbits = K * b + rk.rb;                                // sort bits of a key
-            const u64 sent = ((1ull << b) - 1ull) << rk.rb;                 // (the last symbol of a key's window: all ones = the phrase has ended)
-            // (GRLBWT_SEG_CAP: the tests lower the limit so that ordinary inputs take the large-group path too)
             const u32 cap = (u32)prim::sw().seg_cap;
             DBuf<u64> ka;
             {
-                const SufKeep keep{dict_phr.p, ph_off, ph_lastT, longmode};
+                const SufKeep keep{dict_phr.p, I.ph_off, I.ph_lastT, longmode};
                 if (!C) {
                     DBuf<u32> dropcnt(D + 1);
-                    const u64 dropped = prim::exclusive_scan<u32>(D, PhraseDropIn{ph_off, ph_lastT, longmode}, dropcnt.p, true, "suffix_keep");
+                    const u64 dropped = prim::exclusive_scan<u32>(D, PhraseDropIn{I.ph_off, I.ph_lastT, longmode}, dropcnt.p, true, "suffix_keep");
                     Sg = S - dropped;
                     ka.alloc(Sg); perm.alloc(Sg);
                     prim::for_each(S, Key0KeepFn{keep, dropcnt.p, dict_sym.p, K, b, ka.p, perm.p, rk}, "suffix_keys0");
@@ -3848,20 +3988,19 @@ class Engine {
                     const int N = C->size, me = C->rank;
                     // With few ranks the exchange costs more than it saves: at N = 2 every rank would send half of its records --
                     // 4.6 GB over ONE xGMI link at level 2 of the 10 GB build, 40-75 ms -- to save 10 ms of key computation.  Below
-                    // GRLBWT_SORT_EXCHANGE_MIN ranks (default 4) every rank looks at all S positions and keeps its own key range:
-                    // two replicated streaming passes, nothing on the wire.
-                    const int xmin = prim::sw().sort_exchange_min;
-                    const bool exchange = N >= xmin;
-                    std::vector<u64> scnt(N, 0), rcnt(N, 0);
+                    // GRLBWT_SORT_EXCHANGE_MIN ranks (test tier; default 4) every rank looks at all S positions and keeps its own
+                    // key range: two replicated streaming passes, nothing on the wire.
+                    const bool exchange = N >= prim::sw().sort_exchange_min;
+                    std::vector<u64> scnt(N, 0);
                     DBuf<u64> sk;
                     DBuf<u32> sp;
                     u64 Sown = 0;
                     try {
-                        // (GRLBWT_TEST_FAIL_RANK_SORT=<rank>: the tests make one rank fail here)
+                        // (GRLBWT_TEST_FAIL_RANK_SORT=<rank>, test tier: the tests make one rank fail here)
                         if (test_fail_rank(prim::sw().test_fail_rank_sort, me)) throw prim::Error(-71, "suffix refinement does not terminate (injected by the test)");
                         const u64 ns = S < 8192 ? S : 8192, stride = S / ns;
                         DBuf<u64> samp(ns), dspl(N);
-                        prim::for_each(ns, SampleKey0Fn{dict_sym.p, dict_phr.p, ph_off, K, b, stride, samp.p, rk}, "dist.sample_keys");
+                        prim::for_each(ns, SampleKey0Fn{dict_sym.p, dict_phr.p, I.ph_off, K, b, stride, samp.p, rk}, "dist.sample_keys");
                         std::vector<u64> hs = samp.to_host(ns), spl(N, 0);
                         // A key range is also the rank's piece of the level's OUTPUT (the pre-BWT stays where it was sorted, round 5).
                         // Where the dictionary is small against the text -- level 0 of read collections: 10^6 suffixes for 10^10 symbols --
@@ -3879,58 +4018,28 @@ class Engine {
                             ka.alloc(Sown); perm.alloc(Sown);
                             prim::exclusive_scan_emit<u32>(S, ByteIn{mine.p}, OwnKeyEmitFn{keep, dict_sym.p, K, b, ka.p, perm.p, rk}, "suffix_keys0");
                         }
-                        const u64 q0 = exchange ? S * (u64)me / (u64)N : 0, q1 = exchange ? S * (u64)(me + 1) / (u64)N : 0, nq = q1 - q0;
-                        DBuf<u32> kex(nq + 1);
-                        const u64 nk = prim::exclusive_scan<u32>(nq, KeepRangeIn{keep, q0}, kex.p, false, "suffix_keep");
-                        DBuf<u64> lk(nk), bound(2 * ((u64)N + 1));
-                        DBuf<u32> lp(nk), own(nk), own2(nk), idx(nk), idx2(nk);
-                        prim::for_each(nq, KeyRangeFn{keep, kex.p, q0, dict_sym.p, K, b, dspl.p, N, lk.p, lp.p, own.p, idx.p, rk}, "suffix_keys0");
-                        int obits = (int)bitlen64((u64)N - 1);
-                        if (obits < 1) obits = 1;
-                        const int res = prim::sort_pairs<u32, u32>(own.p, idx.p, own2.p, idx2.p, nk, 0, obits, "dist.key_owner_sort");
-                        sk.alloc(nk); sp.alloc(nk);
-                        prim::for_each(nk, GatherKeyPosFn{res ? idx2.p : idx.p, lk.p, lp.p, sk.p, sp.p}, "dist.key_owner_sort");
-                        prim::for_each((u64)N + 1, KeyBoundFn{res ? own2.p : own.p, nk, nullptr, bound.p}, "dist.owner_bounds");
-                        std::vector<u64> bh = bound.to_host(2 * ((u64)N + 1));
-                        for (int d = 0; d < N; d++) scnt[d] = bh[2 * (d + 1)] - bh[2 * d];
+                        const u64 q0 = exchange ? S * (u64)me / (u64)N : 0, q1 = exchange ? S * (u64)(me + 1) / (u64)N : 0;
+                        key_records_by_owner(keep, dict_sym.p, q0, q1 - q0, ks, rk, dspl.p, N, 0, nullptr, 0, sk, sp, nullptr, scnt);
                     } catch (const prim::Error &e) { C->fail(e); std::fill(scnt.begin(), scnt.end(), 0); }
-                    std::vector<u64> mat = C->allgather_u64(scnt);           // (raises on every rank if one of them failed above)
+                    const auto cn = C->counts(scnt);                         // (raises on every rank if one of them failed above)
                     if (exchange) {
-                        u64 maxb = 0;
-                        Sg = 0;
-                        for (int g = 0; g < N; g++) {
-                            rcnt[g] = mat[(u64)g * N + me];
-                            Sg += rcnt[g];
-                            for (int d = 0; d < N; d++) maxb = std::max(maxb, mat[(u64)g * N + d]);
-                        }
+                        Sg = cn.total;
                         try { ka.alloc(Sg); perm.alloc(Sg); } catch (const prim::Error &e) { C->fail(e); }
                         C->allgather_u64({});                                // (the bulk exchanges below have no way back)
-                        C->named("sort.sample_keys").alltoall(sk.p, scnt, ka.p, rcnt, 8, maxb);
-                        C->named("sort.sample_pos").alltoall(sp.p, scnt, perm.p, rcnt, 4, maxb);
+                        C->named("sort.sample_keys").alltoall(sk.p, scnt, ka.p, cn.rcnt, 8, cn.maxb);
+                        C->named("sort.sample_pos").alltoall(sp.p, scnt, perm.p, cn.rcnt, 4, cn.maxb);
                     } else Sg = Sown;
                 }
             }
             gid.alloc(Sg); gstart.alloc(Sg + 1);
             DBuf<u8> hflag(Sg), uflag(Sg);
             DBuf<u32> ex(Sg + 1);
-            {
-                DBuf<u64> kb(Sg);
-                DBuf<u32> vb(Sg);
-                const u64 *ks = ka.p;
-                if (prim::sort_pairs<u64, u32>(ka.p, perm.p, kb.p, vb.p, Sg, 0, kbits, "suffix_sort0")) {
-                    std::swap(perm, vb);         // the result sits in the second buffer: take it, no copy
-                    ks = kb.p;
-                }
-                if (rk.rb) prim::for_each(Sg, InitSkipFn{perm.p, rk.rem, (u32)K, rk.skip}, "suffix_runs");
-                prim::for_each(Sg, HeadFlagFn{ks, hflag.p}, "suffix_heads");
-                prim::for_each(Sg, FirstUnresolvedFn{ks, hflag.p, Sg, sent, uflag.p}, "suffix_unresolved");
-            }                                   // (no host synchronisation: the buffers that go out of scope here are reused in stream order)
+            first_sort_and_flags(ka, perm, Sg, ks, rk, hflag.p, uflag.p);
             ka.release();
             u64 Lres = (u64)K, iters = 1;        // Lres symbols (incl. a possible sentinel) resolved so far
             DBuf<u32> act;                       // slots still unresolved (empty = all slots), ascending
             u64 A = Sg;
-            bool refined = false;
-            bool doubling = false;               // (see DoubleKeyFn)
+            bool refined = false, doubling = false;      // (doubling: see DoubleKeyFn)
             u64 Ld = 0, dbl_rounds = 0;
             DBuf<u32> slot_of, rank_ex, nskip;
             DBuf<u8> ures;
@@ -3955,75 +4064,45 @@ class Engine {
                 if (doubling) {
                     prim::exclusive_scan_nosync<u32>(Sg, ByteIn{hflag.p}, rank_ex.p, false, "suffix_doubling");      // group numbers of all slots
                     nskip.alloc(U);
-                    prim::for_each(A, DoubleKeyFn{refined ? act.p : nullptr, uflag.p, uex.p, perm.p, hflag.p, dict_phr.p, ph_off, slot_of.p, rank_ex.p,
+                    prim::for_each(A, DoubleKeyFn{refined ? act.p : nullptr, uflag.p, uex.p, perm.p, hflag.p, dict_phr.p, I.ph_off, slot_of.p, rank_ex.p,
                                                   ures.p, rk.skip, Ld, Sg, uslot.p, uq.p, ukey.p, uhead.p, nskip.p}, "suffix_doubling");
                     dbl_rounds++;
                 } else
                 prim::for_each(A, ExtKeyFn{refined ? act.p : nullptr, uflag.p, uex.p, perm.p, hflag.p, dict_sym.p, pbits.words.p, S, Lres, K, b,
                                            uslot.p, uq.p, ukey.p, uhead.p, rk}, "suffix_keys");
-                const u64 sent_r = doubling ? 1ull : sent;                    // "still unresolved" bit(s) of a key
-                const int kbits_r = doubling ? (int)bitlen64((Sg << 1) | 1ull) : kbits;
-                const u64 nseg = prim::exclusive_scan<u32>(U, ByteIn{uhead.p}, hex.p, false, "suffix_heads");
-                DBuf<u32> seg_start(nseg + 1), bex(U + 1);
-                prim::for_each(U, SegStartFn{uhead.p, hex.p, U, seg_start.p}, "suffix_gstart");
-                prim::for_each(U, SegSortSmallFn{uhead.p, hex.p, seg_start.p, uslot.p, uq.p, ukey.p, sent_r, cap, perm.p, hflag.p, unext.p}, "suffix_sort.small");
-                const u64 NB = prim::exclusive_scan<u32>(U, SegBigIn{uhead.p, hex.p, seg_start.p, cap}, bex.p, false, "suffix_sort.big_scan");
-                if (NB) {                        // groups above kSegCap: by key, then (stable) by group
-                    DBuf<u32> bitem(NB), bidx(NB), bidx2(NB), key2(NB), key2b(NB);
-                    DBuf<u64> bkey(NB), bkey2(NB);
-                    prim::for_each(U, SegBigGatherFn{uhead.p, hex.p, seg_start.p, bex.p, ukey.p, cap, bitem.p, bkey.p, bidx.p}, "suffix_sort.big_gather");
-                    const u32 *i1 = prim::sort_pairs<u64, u32>(bkey.p, bidx.p, bkey2.p, bidx2.p, NB, 0, kbits_r, "suffix_sort") ? bidx2.p : bidx.p;
-                    u32 *i1o = (i1 == bidx.p) ? bidx2.p : bidx.p;
-                    prim::for_each(NB, SegBigSegKeyFn{i1, bitem.p, uhead.p, hex.p, key2.p}, "suffix_sort.big_groups");
-                    int sbits = (int)bitlen64(nseg);
-                    if (sbits < 1) sbits = 1;
-                    const int res = prim::sort_pairs<u32, u32>(key2.p, (u32 *)i1, key2b.p, i1o, NB, 0, sbits, "suffix_sort");
-                    prim::for_each(NB, SegBigWriteFn{res ? key2b.p : key2.p, res ? i1o : i1, bitem.p, ukey.p, uq.p, uslot.p, NB, sent_r,
-                                                     perm.p, hflag.p, unext.p}, "suffix_refine");
-                }
+                // ("still unresolved" bit(s) of a key and its sort bits: the doubling rounds' keys are group numbers)
+                order_segments(U, uhead.p, hex.p, ukey.p, uslot.p, uq.p, doubling ? 1ull : ks.sent, doubling ? (int)bitlen64((Sg << 1) | 1ull) : ks.kbits, cap,
+                               perm.p, hflag.p, unext.p);
                 if (doubling) prim::for_each(U, AfterDoubleFn{uq.p, nskip.p, uslot.p, perm.p, unext.p, rk.skip, slot_of.p, ures.p}, "suffix_doubling");
-                act = std::move(uslot);
-                uflag = std::move(unext);
-                A = U;
-                refined = true;
+                act = std::move(uslot); uflag = std::move(unext);
+                A = U; refined = true;
                 if (!doubling) Lres += (u64)K;
                 iters++;
             }
             pbits.base.release();
-            G = prim::exclusive_scan<u32>(Sg, ByteIn{hflag.p}, ex.p, false, "suffix_heads");
-            prim::for_each(Sg, GroupStartsFn{hflag.p, ex.p, Sg, gstart.p}, "suffix_gstart");
-            prim::for_each(Sg, DenseGidFn{hflag.p, ex.p, gid.p}, "suffix_gid");
+            G = close_groups(hflag.p, ex.p, Sg, gstart.p, gid.p);
             L.info.sort_iters = iters;
-        };
+        }
         // The same with the dictionary sharded by owner.  Every rank runs the same sequence of collectives (the refinement goes on
         // until NO rank has an unresolved suffix left); a failure only this rank can have is recorded and raised by every rank at
-        // the next counter exchange, and the rank-local sections in between are skipped once one is pending.
-        auto sort_sharded = [&] {
-            StageTimer st(&tm.dict_sort, "dict_sort");
+        // the next counter exchange, and the rank-local sections in between are skipped once one is pending (Comm::local).
+        void suffix_sort_sharded() {
+            StageTimer st(&E.tm.dict_sort, "dict_sort");
             const int N = C->size, me = C->rank;
-            auto local = [&](auto &&fn) { if (!C->pending) { try { fn(); } catch (const prim::Error &e) { C->fail(e); } } };
-            int b = (int)bitlen64(sigma);
-            if (b < 1) b = 1;
-            int K = 64 / b;
-            if (K < 1) K = 1;
-            if (K > 16) K = 16;
-            const int kmax = prim::sw().sort_kmax;
-            if (kmax >= 1 && K > kmax) K = kmax;
-            if ((u64)K > (u64)maxlen + 1) K = (int)maxlen + 1;
-            const int kbits = K * b;
-            const u64 sent = (1ull << b) - 1ull;
+            const u64 maxlen = I.maxlen;
+            const SortKeyShape ks = sort_key_shape(I.sigma, I.maxlen, 0);
+            const int K = ks.K, b = ks.b;
             const u32 cap = (u32)prim::sw().seg_cap;
-            const SufKeep keep{dict_phr.p, ph_off, ph_lastT, false};
-            // splitters from a sample every rank takes of its own part
-            u64 nsl = 0;
+            const SufKeep keep{dict_phr.p, I.ph_off, I.ph_lastT, false};
+            u64 nsl = 0;                             // splitters from a sample every rank takes of its own part
             DBuf<u64> samp;
-            local([&] {
-                // (GRLBWT_TEST_FAIL_RANK_SORT=<rank>: the tests make one rank fail here)
+            C->local([&] {
+                // (GRLBWT_TEST_FAIL_RANK_SORT=<rank>, test tier: the tests make one rank fail here)
                 if (test_fail_rank(prim::sw().test_fail_rank_sort, me)) throw prim::Error(-71, "suffix refinement does not terminate (injected by the test)");
                 nsl = Sl < 64 ? Sl : std::max<u64>(64, 8192 / (u64)N);
                 if (nsl > Sl) nsl = Sl;
                 samp.alloc(nsl);
-                if (nsl) prim::for_each(nsl, SampleKey0Fn{dict_sym.p, dict_phr.p, ph_off, K, b, Sl / nsl, samp.p, RunKeys()}, "dist.sample_keys");
+                if (nsl) prim::for_each(nsl, SampleKey0Fn{dict_sym.p, dict_phr.p, I.ph_off, K, b, Sl / nsl, samp.p, RunKeys()}, "dist.sample_keys");
             });
             if (C->pending) nsl = 0;
             std::vector<u64> sbb;
@@ -4031,41 +4110,21 @@ class Engine {
             std::vector<u64> hs = alls.to_host(sbb[N]), spl(N, 0);
             std::sort(hs.begin(), hs.end());
             if (!hs.empty()) for (int d = 1; d < N; d++) spl[d] = hs[(u64)d * hs.size() / N];
-            std::vector<u64> scnt(N, 0), rcnt(N, 0);
+            std::vector<u64> scnt(N, 0);
             DBuf<u64> sk, ka, sr;
             DBuf<u32> sp;
-            local([&] {
+            C->local([&] {
                 DBuf<u64> dspl(N);
                 prim::h2d(dspl.p, spl.data(), (u64)N * 8);
-                DBuf<u32> kex(Sl + 1);
-                const u64 nk = prim::exclusive_scan<u32>(Sl, KeepRangeIn{keep, 0}, kex.p, false, "suffix_keep");
-                DBuf<u64> lk(nk), bound(2 * ((u64)N + 1));
-                DBuf<u32> lp(nk), own(nk), own2(nk), idx(nk), idx2(nk);
-                DBuf<u64> lr(carry ? nk : 0);
-                prim::for_each(Sl, KeyRangeFn{keep, kex.p, 0, dict_sym.p, K, b, dspl.p, N, lk.p, lp.p, own.p, idx.p, RunKeys(), (u32)sq,
-                                              carry ? lr.p : nullptr, ph_freq, sigma + 1}, "suffix_keys0");
-                int obits = (int)bitlen64((u64)N - 1);
-                if (obits < 1) obits = 1;
-                const int res = prim::sort_pairs<u32, u32>(own.p, idx.p, own2.p, idx2.p, nk, 0, obits, "dist.key_owner_sort");
-                sk.alloc(nk); sp.alloc(nk);
-                prim::for_each(nk, GatherKeyPosFn{res ? idx2.p : idx.p, lk.p, lp.p, sk.p, sp.p}, "dist.key_owner_sort");
-                if (carry) { sr.alloc(nk); prim::for_each(nk, GatherU64Fn{res ? idx2.p : idx.p, lr.p, sr.p}, "dist.key_owner_sort"); }
-                prim::for_each((u64)N + 1, KeyBoundFn{res ? own2.p : own.p, nk, nullptr, bound.p}, "dist.owner_bounds");
-                std::vector<u64> bh = bound.to_host(2 * ((u64)N + 1));
-                for (int d = 0; d < N; d++) scnt[d] = bh[2 * (d + 1)] - bh[2 * d];
+                key_records_by_owner(keep, dict_sym.p, 0, Sl, ks, RunKeys(), dspl.p, N, (u32)sq, I.ph_freq, bwt_code, sk, sp, carry ? &sr : nullptr, scnt);
             });
             if (C->pending) std::fill(scnt.begin(), scnt.end(), 0);
-            std::vector<u64> mat = C->allgather_u64(scnt);           // (raises on every rank if one of them failed above)
-            u64 maxb = 0;
-            Sg = 0;
-            for (int g = 0; g < N; g++) {
-                rcnt[g] = mat[(u64)g * N + me];
-                Sg += rcnt[g];
-                for (int d = 0; d < N; d++) maxb = std::max(maxb, mat[(u64)g * N + d]);
-            }
+            const auto cn = C->counts(scnt);                         // (raises on every rank if one of them failed above)
+            const std::vector<u64> &rcnt = cn.rcnt;
+            Sg = cn.total;
             // (known to every rank alike: slots are 32-bit)
-            for (int d = 0; d < N; d++) { u64 sd = 0; for (int g = 0; g < N; g++) sd += mat[(u64)g * N + d]; if (sd >= 0xFFFFFFF0ull) throw prim::Error(-75, "a key range of the dictionary's suffixes has >= 2^32 of them: use more ranks"); }
-            local([&] {
+            for (int d = 0; d < N; d++) { u64 sd = 0; for (int g = 0; g < N; g++) sd += cn.mat[(u64)g * N + d]; if (sd >= 0xFFFFFFF0ull) throw prim::Error(-75, "a key range of the dictionary's suffixes has >= 2^32 of them: use more ranks"); }
+            C->local([&] {
                 ka.alloc(Sg); perm.alloc(Sg);
                 if (carry) {
                     pos_arr.alloc(Sg); rec_arr.alloc(Sg); abounds.alloc((u64)N + 1);
@@ -4075,21 +4134,15 @@ class Engine {
                 }
             });
             C->allgather_u64({});                                // (the bulk exchanges below have no way back)
-            C->named("sort.sample_keys").alltoall(sk.p, scnt, ka.p, rcnt, 8, maxb);
-            C->named("sort.sample_pos").alltoall(sp.p, scnt, carry ? pos_arr.p : perm.p, rcnt, 4, maxb);
-            if (carry) C->named("sort.sample_rec").alltoall(sr.p, scnt, rec_arr.p, rcnt, 8, maxb);
+            C->named("sort.sample_keys").alltoall(sk.p, scnt, ka.p, rcnt, 8, cn.maxb);
+            C->named("sort.sample_pos").alltoall(sp.p, scnt, carry ? pos_arr.p : perm.p, rcnt, 4, cn.maxb);
+            if (carry) C->named("sort.sample_rec").alltoall(sr.p, scnt, rec_arr.p, rcnt, 8, cn.maxb);
             sk.release(); sp.release(); sr.release();
-            if (carry) local([&] { prim::for_each(Sg, IotaU32Fn{perm.p}, "suffix_keys0"); });      // the values of the sort: arrival indices
-            DBuf<u8> hflag, uflag;
-            DBuf<u32> ex;
-            local([&] {
+            if (carry) C->local([&] { prim::for_each(Sg, IotaU32Fn{perm.p}, "suffix_keys0"); });      // the values of the sort: arrival indices
+            DBuf<u8> hflag, uflag; DBuf<u32> ex;
+            C->local([&] {
                 gid.alloc(Sg); gstart.alloc(Sg + 1); hflag.alloc(Sg); uflag.alloc(Sg); ex.alloc(Sg + 1);
-                DBuf<u64> kb(Sg);
-                DBuf<u32> vb(Sg);
-                const u64 *ks = ka.p;
-                if (prim::sort_pairs<u64, u32>(ka.p, perm.p, kb.p, vb.p, Sg, 0, kbits, "suffix_sort0")) { std::swap(perm, vb); ks = kb.p; }
-                prim::for_each(Sg, HeadFlagFn{ks, hflag.p}, "suffix_heads");
-                prim::for_each(Sg, FirstUnresolvedFn{ks, hflag.p, Sg, sent, uflag.p}, "suffix_unresolved");
+                first_sort_and_flags(ka, perm, Sg, ks, RunKeys(), hflag.p, uflag.p);
             });
             ka.release();
             u64 Lres = (u64)K, iters = 1, A = Sg;
@@ -4098,17 +4151,15 @@ class Engine {
             for (;;) {
                 u64 U = 0;
                 DBuf<u32> uex;
-                local([&] { uex.alloc(A + 1); U = A ? prim::exclusive_scan<u32>(A, ByteIn{uflag.p}, uex.p, false, "suffix_unresolved_scan") : 0; });
+                C->local([&] { uex.alloc(A + 1); U = A ? prim::exclusive_scan<u32>(A, ByteIn{uflag.p}, uex.p, false, "suffix_unresolved_scan") : 0; });
                 if (C->pending) U = 0;
                 std::vector<u64> us = C->allgather_u64({U});     // (every rank goes on while ANY rank has unresolved suffixes: the owners answer)
                 u64 Uany = 0;
                 for (u64 v : us) Uany = std::max(Uany, v);
                 if (Uany == 0) break;
                 if (Lres > (u64)maxlen + (u64)K) throw prim::Error(-71, "suffix refinement does not terminate");      // (the same on every rank)
-                DBuf<u32> uslot, uq, hex, uown;
-                DBuf<u64> ukey, req, back;
-                DBuf<u8> uhead, unext;
-                local([&] {
+                DBuf<u32> uslot, uq, hex, uown; DBuf<u64> ukey, req, back; DBuf<u8> uhead, unext;
+                C->local([&] {
                     uslot.alloc(U); uq.alloc(U); hex.alloc(U + 1); ukey.alloc(U); req.alloc(U); uhead.alloc(U); unext.alloc(U);
                     if (carry) uown.alloc(U);
                     if (carry) prim::for_each(A, ExtCompactAiFn{refined ? act.p : nullptr, uflag.p, uex.p, perm.p, hflag.p, pos_arr.p, uslot.p, uq.p, uhead.p, req.p,
@@ -4116,43 +4167,22 @@ class Engine {
                     else prim::for_each(A, ExtCompactFn{refined ? act.p : nullptr, uflag.p, uex.p, perm.p, hflag.p, uslot.p, uq.p, uhead.p, req.p}, "suffix_keys");
                 });
                 if (C->pending) U = 0;
-                owner_round_trip<u64>(*C, dsb.p, req, U, back, [&](const u64 *rq, u64 nrq, u64 *out) {
+                E.owner_round_trip<u64>(*C, dsb.p, req, U, back, [&](const u64 *rq, u64 nrq, u64 *out) {
                     prim::for_each(nrq, ExtKeyOwnerFn{rq, dict_sym.p, pbits.words.p, Sl, sq, Lres, K, b, out}, "suffix_keys");
                 }, "dist.ext_owner_sort", "sort.ext_keys", carry && !C->pending && uown.p ? &uown : nullptr);
-                local([&] {
+                C->local([&] {
                     if (U == 0) { act = std::move(uslot); uflag = std::move(unext); A = 0; refined = true; return; }      // (nothing of mine left: I only answer)
                     prim::for_each(U, ExtAnswerFn{req.p, back.p, ukey.p}, "suffix_keys");
-                    const u64 nseg = prim::exclusive_scan<u32>(U, ByteIn{uhead.p}, hex.p, false, "suffix_heads");
-                    DBuf<u32> seg_start(nseg + 1), bex(U + 1);
-                    prim::for_each(U, SegStartFn{uhead.p, hex.p, U, seg_start.p}, "suffix_gstart");
-                    prim::for_each(U, SegSortSmallFn{uhead.p, hex.p, seg_start.p, uslot.p, uq.p, ukey.p, sent, cap, perm.p, hflag.p, unext.p}, "suffix_sort.small");
-                    const u64 NB = prim::exclusive_scan<u32>(U, SegBigIn{uhead.p, hex.p, seg_start.p, cap}, bex.p, false, "suffix_sort.big_scan");
-                    if (NB) {                        // groups above kSegCap: by key, then (stable) by group
-                        DBuf<u32> bitem(NB), bidx(NB), bidx2(NB), key2(NB), key2b(NB);
-                        DBuf<u64> bkey(NB), bkey2(NB);
-                        prim::for_each(U, SegBigGatherFn{uhead.p, hex.p, seg_start.p, bex.p, ukey.p, cap, bitem.p, bkey.p, bidx.p}, "suffix_sort.big_gather");
-                        const u32 *i1 = prim::sort_pairs<u64, u32>(bkey.p, bidx.p, bkey2.p, bidx2.p, NB, 0, kbits, "suffix_sort") ? bidx2.p : bidx.p;
-                        u32 *i1o = (i1 == bidx.p) ? bidx2.p : bidx.p;
-                        prim::for_each(NB, SegBigSegKeyFn{i1, bitem.p, uhead.p, hex.p, key2.p}, "suffix_sort.big_groups");
-                        int sbits = (int)bitlen64(nseg);
-                        if (sbits < 1) sbits = 1;
-                        const int res = prim::sort_pairs<u32, u32>(key2.p, (u32 *)i1, key2b.p, i1o, NB, 0, sbits, "suffix_sort");
-                        prim::for_each(NB, SegBigWriteFn{res ? key2b.p : key2.p, res ? i1o : i1, bitem.p, ukey.p, uq.p, uslot.p, NB, sent,
-                                                         perm.p, hflag.p, unext.p}, "suffix_refine");
-                    }
-                    act = std::move(uslot);
-                    uflag = std::move(unext);
-                    A = U;
-                    refined = true;
+                    order_segments(U, uhead.p, hex.p, ukey.p, uslot.p, uq.p, ks.sent, ks.kbits, cap, perm.p, hflag.p, unext.p);
+                    act = std::move(uslot); uflag = std::move(unext);
+                    A = U; refined = true;
                 });
                 Lres += (u64)K;
                 iters++;
             }
             pbits.base.release();
-            local([&] {
-                G = prim::exclusive_scan<u32>(Sg, ByteIn{hflag.p}, ex.p, false, "suffix_heads");
-                prim::for_each(Sg, GroupStartsFn{hflag.p, ex.p, Sg, gstart.p}, "suffix_gstart");
-                prim::for_each(Sg, DenseGidFn{hflag.p, ex.p, gid.p}, "suffix_gid");
+            C->local([&] {
+                G = close_groups(hflag.p, ex.p, Sg, gstart.p, gid.p);
                 if (carry) {                     // from here on perm[] holds positions (offsets, owner in pown[]) again; the arrival indices stay for the fold's records
                     DBuf<u32> pp(Sg);
                     pown.alloc(Sg);
@@ -4164,90 +4194,52 @@ class Engine {
                 }
             });
             L.info.sort_iters = iters;
-        };
-        if (!C) sort_local();
-        else if (sharded) sort_sharded();
-        else { try { sort_local(); } catch (const prim::Error &e) { C->fail(e); } }
-
-        // ---- a7: equal-suffix groups -> pre-BWT, ranks -----------------------
-        const u32 bwt_code = sigma + 1, hocc_code = sigma + 2, sigma3 = sigma + 3;
-        DBuf<u32> grank, pidx, gmin, gmax;
-        DBuf<idx_t> gacc;
-        DBuf<u8> gfull, gflag;
-        DBuf<u32> repq, pslot;                   // pslot[k] = my group holding phrase k's whole-phrase suffix (all ones: not mine)
-        DBuf<u32> gphr;                          // ... or, single-GPU rounds, gphr[g] = the whole phrase of group g (see GroupPhraseValFn)
-        const bool fused_vals = !C && fused_ph_slot && fused_slot_val;
-        u64 M, P0;
-        {
-            StageTimer st(&tm.dict_groups, "dict_groups");
-            u64 Ml = 0, P0l = 0;
-            // (dictionary sharded by owner: what the fold reads per member comes from the owners of the members' positions, by slot)
-            DBuf<SufRecT<8>> recs;
-            if (sharded && !carry) {
-                DBuf<u64> rq;
-                DBuf<SufRecT<8>> back;
-                u64 nrq = 0;
-                if (!C->pending) { try { rq.alloc(Sg); prim::for_each(Sg, RecRequestFn{perm.p, rq.p}, "suffix_records"); nrq = Sg; } catch (const prim::Error &e) { C->fail(e); nrq = 0; } }
-                const RecCompute rcl{dict_sym.p, dict_phr.p, ph_off, ph_freq, ph_lastT, sigma + 1, (u32)d0};
-                owner_round_trip<SufRecT<8>>(*C, dsb.p, rq, nrq, back, [&](const u64 *r, u64 nr, SufRecT<8> *out) {
-                    DBuf<SufRecT<8>> mine(Sl);
-                    prim::for_each(Sl, RecLocalFn{rcl, mine.p}, "suffix_records");
-                    prim::for_each(nr, RecOwnerFn{r, mine.p, s0, out}, "suffix_records.answers");
-                }, "dist.rec_owner_sort", "group.records");
-                if (!C->pending) { try { recs.alloc(Sg); prim::for_each(nrq, RecAnswerFn{rq.p, back.p, recs.p}, "suffix_records"); } catch (const prim::Error &e) { C->fail(e); } }
-            }
-            auto groups_local = [&] {
+        }
+        // a7, first half: the fold over every group of equal suffixes (min/max of the left symbol, summed frequency, whole phrase), the
+        // group decision, and the ranks of the ranked groups / pre-BWT index of the valid ones.  Rank-local: sets Ml, P0l.
+        // Where a member's record comes from: it came with the suffix (carry) | the owners answered by slot (recs) | an array over
+        // the dictionary | computed at the member (from GRLBWT_DIST_REC_FLY_MIN ranks on: test tier, default 8).
+        void group_fold() {
             grank.alloc(G + 1); pidx.alloc(G + 1); gmin.alloc(G); gmax.alloc(G); gacc.alloc(G); gfull.alloc(G); gflag.alloc(G);
-            if (fused_vals || carry) gphr.alloc(G); else pslot.alloc(D);      // (carry: gphr[g] = slot of the group's whole-phrase member)
+            if (fused_vals || carry) gphr.alloc(G); else pslot.alloc(I.D);      // (carry: gphr[g] = slot of the group's whole-phrase member)
             if (C && !carry) pslot.fill_ff();    // (sharded: phrases whose whole-phrase suffix sorted elsewhere keep the mark)
-            {
-                const int fly_min = prim::sw().dist_rec_fly_min;
-                const bool fly = C && C->size >= fly_min;
-                DBuf<SufRec> rec;
-                DBuf<u32> coff(G + 1);
-                if (carry) {
-                    prim::for_each(G, GroupAccumSmallFn<RecWire>{perm_ai.p, gstart.p, RecWire{rec_arr.p}, nullptr, bwt_code,
-                                                                 gmin.p, gmax.p, gacc.p, gfull.p, gflag.p, nullptr, gphr.p, true}, "group_accum");
-                } else if (sharded) {
-                    prim::for_each(G, GroupAccumSmallFn<RecSlot>{perm.p, gstart.p, RecSlot{recs.p}, nullptr, bwt_code,
-                                                                 gmin.p, gmax.p, gacc.p, gfull.p, gflag.p, pslot.p, gphr.p}, "group_accum");
-                } else if (!fly) {
-                    rec.alloc(S);
-                    prim::for_each(S, SuffixRecFn{dict_sym.p, dict_phr.p, ph_off, ph_freq, ph_lastT, bwt_code, rec.p}, "suffix_records");
-                    prim::for_each(G, GroupAccumSmallFn<RecArray>{perm.p, gstart.p, RecArray{rec.p}, dict_phr.p, bwt_code,
-                                                                  gmin.p, gmax.p, gacc.p, gfull.p, gflag.p, pslot.p, gphr.p}, "group_accum");
-                } else {
-                    const RecCompute rc{dict_sym.p, dict_phr.p, ph_off, ph_freq, ph_lastT, bwt_code};
-                    prim::for_each(G, GroupAccumSmallFn<RecCompute>{perm.p, gstart.p, rc, dict_phr.p, bwt_code,
-                                                                    gmin.p, gmax.p, gacc.p, gfull.p, gflag.p, pslot.p, gphr.p}, "group_accum");
-                }
-                const u64 NC = prim::exclusive_scan<u32>(G, GroupChunksIn{gstart.p}, coff.p, true, "group_accum_large");
-                if (carry) {
-                    prim::for_each(NC, GroupAccumLargeFn<RecWire>{perm_ai.p, coff.p, G, gstart.p, RecWire{rec_arr.p}, nullptr, bwt_code,
-                                                                  gmin.p, gmax.p, gacc.p, gfull.p, nullptr, gphr.p, true}, "group_accum_large");
-                    prim::for_each(G, GroupDecideFn<RecWire>{perm_ai.p, gstart.p, RecWire{rec_arr.p}, gmin.p, gmax.p, gfull.p, gflag.p}, "group_decide");
-                } else if (sharded) {
-                    prim::for_each(NC, GroupAccumLargeFn<RecSlot>{perm.p, coff.p, G, gstart.p, RecSlot{recs.p}, nullptr, bwt_code,
-                                                                  gmin.p, gmax.p, gacc.p, gfull.p, pslot.p, gphr.p}, "group_accum_large");
-                    prim::for_each(G, GroupDecideFn<RecSlot>{perm.p, gstart.p, RecSlot{recs.p}, gmin.p, gmax.p, gfull.p, gflag.p}, "group_decide");
-                } else
-                if (!fly) prim::for_each(NC, GroupAccumLargeFn<RecArray>{perm.p, coff.p, G, gstart.p, RecArray{rec.p}, dict_phr.p, bwt_code,
-                                                                         gmin.p, gmax.p, gacc.p, gfull.p, pslot.p, gphr.p}, "group_accum_large");
-                else prim::for_each(NC, GroupAccumLargeFn<RecCompute>{perm.p, coff.p, G, gstart.p, RecCompute{dict_sym.p, dict_phr.p, ph_off, ph_freq, ph_lastT, bwt_code},
-                                                                      dict_phr.p, bwt_code, gmin.p, gmax.p, gacc.p, gfull.p, pslot.p, gphr.p}, "group_accum_large");
-            }
-            if (!sharded) prim::for_each(G, GroupDecideFn<RecCompute>{perm.p, gstart.p, RecCompute{dict_sym.p, dict_phr.p, ph_off, ph_freq, ph_lastT, bwt_code},
-                                                                       gmin.p, gmax.p, gfull.p, gflag.p}, "group_decide");
-            {   // ranks of the ranked groups and pre-BWT index of the valid ones: one scan of pairs (one host synchronisation)
-                const prim::Pair<u32, u32> tot = prim::exclusive_scan_emit<prim::Pair<u32, u32>>(G, RankedValidIn{gflag.p}, SplitPairEmitFn{grank.p, pidx.p}, "group_ranks");
-                Ml = tot.a; P0l = tot.b;
-            }
-            };
-            if (!C) groups_local();
-            else if (!C->pending) { try { groups_local(); } catch (const prim::Error &e) { C->fail(e); Ml = 0; P0l = 0; } }
-            u64 Moff = 0, P0off = 0;
+            const RecCompute rc{dict_sym.p, dict_phr.p, I.ph_off, I.ph_freq, I.ph_lastT, bwt_code};
+            if (carry) {
+                fold_groups(perm_ai.p, RecWire{rec_arr.p}, nullptr, true);
+                prim::for_each(G, GroupDecideFn<RecWire>{perm_ai.p, gstart.p, RecWire{rec_arr.p}, gmin.p, gmax.p, gfull.p, gflag.p}, "group_decide");
+            } else if (sharded) {
+                fold_groups(perm.p, RecSlot{recs.p}, nullptr, false);
+                prim::for_each(G, GroupDecideFn<RecSlot>{perm.p, gstart.p, RecSlot{recs.p}, gmin.p, gmax.p, gfull.p, gflag.p}, "group_decide");
+            } else if (!(C && C->size >= prim::sw().dist_rec_fly_min)) {
+                DBuf<SufRec> rec(I.S);
+                prim::for_each(I.S, SuffixRecFn{dict_sym.p, dict_phr.p, I.ph_off, I.ph_freq, I.ph_lastT, bwt_code, rec.p}, "suffix_records");
+                fold_groups(perm.p, RecArray{rec.p}, dict_phr.p, false);
+            } else fold_groups(perm.p, rc, dict_phr.p, false);
+            // (the flows with the whole dictionary decide from the dictionary itself: the record array is gone by now)
+            if (!sharded) prim::for_each(G, GroupDecideFn<RecCompute>{perm.p, gstart.p, rc, gmin.p, gmax.p, gfull.p, gflag.p}, "group_decide");
+            // ranks of the ranked groups and pre-BWT index of the valid ones: one scan of pairs (one host synchronisation)
+            const prim::Pair<u32, u32> tot = prim::exclusive_scan_emit<prim::Pair<u32, u32>>(G, RankedValidIn{gflag.p}, SplitPairEmitFn{grank.p, pidx.p}, "group_ranks");
+            Ml = tot.a; P0l = tot.b;
+        }
+        // (dictionary sharded by owner, records not carried: what the fold reads per member comes from the owners of the members'
+        // positions, by slot -> recs)
+        void fetch_records() {
+            DBuf<u64> rq;
+            DBuf<SufRecT<8>> back;
+            u64 nrq = 0;
+            C->local([&] { rq.alloc(Sg); prim::for_each(Sg, RecRequestFn{perm.p, rq.p}, "suffix_records"); nrq = Sg; });
+            if (C->pending) nrq = 0;
+            const RecCompute rcl{dict_sym.p, dict_phr.p, I.ph_off, I.ph_freq, I.ph_lastT, bwt_code, (u32)d0};
+            E.owner_round_trip<SufRecT<8>>(*C, dsb.p, rq, nrq, back, [&](const u64 *r, u64 nr, SufRecT<8> *out) {
+                DBuf<SufRecT<8>> mine(Sl);
+                prim::for_each(Sl, RecLocalFn{rcl, mine.p}, "suffix_records");
+                prim::for_each(nr, RecOwnerFn{r, mine.p, s0, out}, "suffix_records.answers");
+            }, "dist.rec_owner_sort", "group.records");
+            C->local([&] { recs.alloc(Sg); prim::for_each(nrq, RecAnswerFn{rq.p, back.p, recs.p}, "suffix_records"); });
+        }
+        // every rank's (Ml, P0l): where my metasymbols and my pre-BWT runs start among all, and the level's totals
+        void group_counts() {
             M = Ml; P0 = P0l;
-            std::vector<u64> bbM, bbP;
             if (C) {
                 std::vector<u64> cnts = C->allgather_u64({Ml, P0l});
                 bbM.assign(C->size + 1, 0); bbP.assign(C->size + 1, 0);
@@ -4257,21 +4249,23 @@ class Engine {
             }
             if ((u64)sigma3 + M + 8 >= (1ull << 30)) throw prim::Error(-75, "alphabet of the next level >= 2^30");
             L.M = (u32)M;
+        }
+        // a7, second half: the groups emit their pre-BWT runs, which are gathered (replicated form only) and merged.
+        // Collection-level mode: the pre-BWT stays where its groups were sorted (round 5).  My key range's groups are a
+        // contiguous piece of the sorted order, so what they emit is a contiguous piece of the level's pre-BWT: the induction
+        // takes exactly these pieces as the ranks' output pieces (dist_induce_level) and nobody needs anybody else's runs.
+        // (Rounds 1-4 all-gathered the emitted runs, their metasymbol counts and the metasymbol -> run map to every rank --
+        // 8.9 GB sent per rank of the 10 GB collection at N = 2, 17.8 GB received at any N -- and every rank merged and
+        // scanned the WHOLE pre-BWT; GRLBWT_DIST_REPLICATED_PREBWT=1 (test tier) keeps that form.)  Runs are merged inside a
+        // piece only: a run cut by a piece boundary stays two runs, which describe the same symbols.
+        void prebwt() {
             L.has_hocc.alloc(Ml); repq.alloc(Ml);
-            DBuf<u32> psym0(P0l);
-            DBuf<idx_t> plen0(P0l);
-            DBuf<u32> u_to_p0(Ml), pu0(P0l);
-            // Collection-level mode: the pre-BWT stays where its groups were sorted (round 5).  My key range's groups are a
-            // contiguous piece of the sorted order, so what they emit is a contiguous piece of the level's pre-BWT: the induction
-            // takes exactly these pieces as the ranks' output pieces (dist_induce_level) and nobody needs anybody else's runs.
-            // (Rounds 1-4 all-gathered the emitted runs, their metasymbol counts and the metasymbol -> run map to every rank --
-            // 8.9 GB sent per rank of the 10 GB collection at N = 2, 17.8 GB received at any N -- and every rank merged and
-            // scanned the WHOLE pre-BWT; GRLBWT_DIST_REPLICATED_PREBWT=1 keeps that form.)  Runs are merged inside a piece
-            // only: a run cut by a piece boundary stays two runs, which describe the same symbols.
+            psym0.alloc(P0l); plen0.alloc(P0l);
+            u_to_p0.alloc(Ml); pu0.alloc(P0l);
             const bool replicated_pre = prim::sw().dist_replicated_prebwt || prim::sw().dist_replicated_induction;      // (the replicated induction wants the whole pre-BWT)
             const bool pre_local = C && !replicated_pre;
-            prim::for_each(G, GroupEmitFn{gflag.p, grank.p, pidx.p, gmin.p, gacc.p, gstart.p, carry ? nullptr : perm.p, bwt_code, hocc_code, pre_local ? 0u : (u32)Moff,
-                                          pre_local ? 0u : (u32)P0off, psym0.p, plen0.p, L.has_hocc.p, repq.p, u_to_p0.p, pu0.p}, "prebwt_emit");
+            prim::for_each(G, GroupEmitFn{gflag.p, grank.p, pidx.p, gmin.p, gacc.p, gstart.p, carry ? nullptr : perm.p, bwt_code, hocc_code,
+                                            pre_local ? 0u : (u32)Moff, pre_local ? 0u : (u32)P0off, psym0.p, plen0.p, L.has_hocc.p, repq.p, u_to_p0.p, pu0.p}, "prebwt_emit");
             if (C) {                             // every rank's (Ml, P0l) is known: one exchange per array
                 if (!pre_local) {
                     psym0 = C->named("prebwt.sym").template allgather_v<u32>(psym0.p, P0l, bbP, true);
@@ -4283,189 +4277,188 @@ class Engine {
             }
             const u64 P0e = pre_local ? P0l : P0, Me = pre_local ? Ml : M;      // what this rank's pre-BWT arrays describe
             L.pre_local = pre_local; L.u0 = pre_local ? (u32)Moff : 0u; L.Ml = (u32)Me;
-            DBuf<u32> merged(P0e);
+            merged.alloc(P0e);
             L.prebwt = merge_runs(psym0.p, plen0.p, P0e, merged.p);
             L.prebwt.pos.release();
             L.u_to_p.alloc(Me);
             prim::for_each(Me, ComposeMapFn{u_to_p0.p, merged.p, L.u_to_p.p}, "prebwt_map");
             L.p_to_u.alloc(L.prebwt.R);
             prim::for_each(P0e, PreToMetaFn{pu0.p, merged.p, L.p_to_u.p}, "prebwt_map");
-            // ---- a8: grammar ------------------------------------------------
-            L.g0.alloc(M); L.g1.alloc(M);
-            u32 MD = sigma3 + (u32)M + 1;
-            {
-                DBuf<u32> ginfo(G);
-                prim::for_each(G, PackGroupInfoFn{grank.p, gflag.p, (u32)Moff, ginfo.p}, "grammar_ginfo");
-                const bool replicated_grammar = prim::sw().dist_replicated_grammar;
-                if (C && sbase && (!replicated_grammar || sharded)) {      // (a dictionary sharded by owner has no other form)
-                    // Sharded by the owner of the dictionary position (round 5): I hold dm[] of MY part of the dictionary only.  The marks
-                    // of my groups go to the owners of their positions, the walks of my metasymbols are done by the owners of their
-                    // representatives and the answers come back.  (Rounds 1-4: dm[] of the WHOLE dictionary on every rank, every rank's
-                    // marks all-gathered to everybody and applied by everybody -- at every N: 24 + 8 ms and 10 GB per rank at N = 8 of the
-                    // 10 GB collection, 4.8 GB of pairs sent per rank.)
-                    const int N = C->size, me = C->rank;
-                    const u64 s0 = carry ? 0 : (*sbase)[me], Sme = (*sbase)[me + 1] - (*sbase)[me] - test_dict_part_pad();      // (carry: positions are offsets in the owner's part)
-                    DBuf<u64> dm;
-                    // records (position << 32 | payload) -> sorted by the owner of the position, counts per owner
-                    auto by_owner = [&](DBuf<u64> &rec, u64 n, std::vector<u64> &cnt, const char *name, DBuf<u32> *own_of) {
-                        bucket_by_owner(*C, dsb.p, rec, n, cnt, name, own_of);
-                    };
-                    std::vector<u64> mcnt(N, 0), wcnt(N, 0), mrc(N, 0), wrc(N, 0);
-                    DBuf<u64> mp, wq;
-                    try {
-                        DBuf<u32> mown, wown;
-                        dm.alloc(Sme);
-                        prim::for_each(Sme, DictMetaInitFn{dict_sym.p, dict_phr.p, ph_off, ph_lastT, dm.p, sharded ? 0 : s0}, "grammar_init");      // (sharded dictionary: the arrays are my part already)
-                        DBuf<u32> mex(Sg + 1);
-                        const u64 nm = prim::exclusive_scan<u32>(Sg, MarkedIn{gid.p, ginfo.p}, mex.p, false, "dist.mark_scan");
-                        mp.alloc(nm);
-                        if (carry) { mown.alloc(nm); wown.alloc(Ml); }
-                        prim::for_each(Sg, MetaPairFn{perm.p, gid.p, ginfo.p, mex.p, sigma3, mp.p, pown.p, mown.p}, "dist.mark_pairs");
-                        by_owner(mp, nm, mcnt, "dist.mark_owner_sort", carry ? &mown : nullptr);
-                        wq.alloc(Ml);
-                        prim::for_each(Ml, WalkRequestFn{repq.p, wq.p, perm.p, pown.p, wown.p}, "dist.walk_requests");
-                        by_owner(wq, Ml, wcnt, "dist.walk_owner_sort", carry ? &wown : nullptr);
-                    } catch (const prim::Error &e) { C->fail(e); std::fill(mcnt.begin(), mcnt.end(), 0); std::fill(wcnt.begin(), wcnt.end(), 0); }
-                    std::vector<u64> both(mcnt);
-                    both.insert(both.end(), wcnt.begin(), wcnt.end());
-                    std::vector<u64> mat = C->allgather_u64(both);           // (raises on every rank if one of them failed above)
-                    u64 nmr = 0, nwr = 0, maxm = 0, maxw = 0;
-                    for (int g = 0; g < N; g++) {
-                        mrc[g] = mat[(u64)g * 2 * N + me]; wrc[g] = mat[(u64)g * 2 * N + N + me];
-                        nmr += mrc[g]; nwr += wrc[g];
-                        for (int d = 0; d < N; d++) { maxm = std::max(maxm, mat[(u64)g * 2 * N + d]); maxw = std::max(maxw, mat[(u64)g * 2 * N + N + d]); }
-                    }
-                    DBuf<u64> mine, wmine, wans, wback;
-                    try { mine.alloc(nmr); wmine.alloc(nwr); wans.alloc(nwr); wback.alloc(Ml); } catch (const prim::Error &e) { C->fail(e); }
-                    C->allgather_u64({});                                    // (the bulk exchanges below have no way back)
-                    C->named("grammar.mark_pairs").alltoall(mp.p, mcnt, mine.p, mrc, 8, maxm);
-                    C->named("grammar.walk_requests").alltoall(wq.p, wcnt, wmine.p, wrc, 8, maxw);
-                    mp.release();
-                    try {
-                        prim::for_each(nmr, ApplyMetaPairsFn{mine.p, dm.p, s0}, "grammar_marks");
-                        mine.release();
-                        DBuf<u64> stops;             // (very long phrases only: the walks jump to their stops)
-                        if (maxlen >= 4096 || prim::sw().grammar_jump) {
-                            stops.alloc((Sme + 63) / 64 + 1);
-                            prim::for_each((Sme + 63) / 64, DmStopBitsFn{dm.p, Sme, stops.p}, "grammar_marks");
-                        }
-                        prim::for_each(nwr, GrammarFn{nullptr, dm.p, MD, nullptr, nullptr, stops.p, Sme, wmine.p, s0, wans.p}, "grammar");
-                    } catch (const prim::Error &e) { C->fail(e); }
-                    C->allgather_u64({});
-                    C->named("grammar.walk_answers").alltoall(wans.p, wrc, wback.p, wcnt, 8, maxw);
-                    DBuf<u32> g0l(Ml), g1l(Ml);
-                    prim::for_each(Ml, WalkAnswerFn{wq.p, wback.p, g0l.p, g1l.p}, "grammar");
-                    C->named("grammar.g0").template allgather_v<u32>(g0l.p, Ml, bbM, true, L.g0.p);
-                    C->named("grammar.g1").template allgather_v<u32>(g1l.p, Ml, bbM, true, L.g1.p);
-                } else {
-                DBuf<u64> dm(S);
-                prim::for_each(S, DictMetaInitFn{dict_sym.p, dict_phr.p, ph_off, ph_lastT, dm.p}, "grammar_init");
-                if (!C) prim::for_each(Sg, MetaPosFn{perm.p, gid.p, ginfo.p, sigma3, dm.p}, "grammar_marks");
-                else {                           // the marked positions of every rank's groups, as (position, metasymbol) pairs
-                    DBuf<u32> mex(Sg + 1);
-                    const u64 nm = prim::exclusive_scan<u32>(Sg, MarkedIn{gid.p, ginfo.p}, mex.p, false, "dist.mark_scan");
-                    DBuf<u64> mp(nm);
-                    prim::for_each(Sg, MetaPairFn{perm.p, gid.p, ginfo.p, mex.p, sigma3, mp.p}, "dist.mark_pairs");
-                    std::vector<u64> bb;
-                    DBuf<u64> all = C->named("grammar.mark_pairs").template allgather_v<u64>(mp.p, nm, bb);
-                    prim::for_each(bb[C->size], ApplyMetaPairsFn{all.p, dm.p}, "grammar_marks");
-                }
-                DBuf<u64> stops;                 // (very long phrases only: the walks jump to their stops)
-                if (maxlen >= 4096 || prim::sw().grammar_jump) {
-                    stops.alloc((S + 63) / 64 + 1);
-                    prim::for_each((S + 63) / 64, DmStopBitsFn{dm.p, S, stops.p}, "grammar_marks");
-                }
-                if (!C) prim::for_each(M, GrammarFn{repq.p, dm.p, MD, L.g0.p, L.g1.p, stops.p, S}, "grammar");
-                else {                           // every rank walks for its own metasymbols; the cells are all-gathered
-                    DBuf<u32> g0l(Ml), g1l(Ml);
-                    prim::for_each(Ml, GrammarFn{repq.p, dm.p, MD, g0l.p, g1l.p, stops.p, S}, "grammar");
-                    C->named("grammar.g0").template allgather_v<u32>(g0l.p, Ml, bbM, true, L.g0.p);
-                    C->named("grammar.g1").template allgather_v<u32>(g1l.p, Ml, bbM, true, L.g1.p);
-                }
-                }
+        }
+        // a8: the grammar, sharded by the owner of the dictionary position (round 5): I hold dm[] of MY part of the dictionary only.
+        // The marks of my groups go to the owners of their positions, the walks of my metasymbols are done by the owners of their
+        // representatives and the answers come back.  (Rounds 1-4: dm[] of the WHOLE dictionary on every rank, every rank's
+        // marks all-gathered to everybody and applied by everybody -- at every N: 24 + 8 ms and 10 GB per rank at N = 8 of the
+        // 10 GB collection, 4.8 GB of pairs sent per rank.)
+        void grammar_by_owner(const u32 *ginfo, u32 MD) {
+            const int N = C->size, me = C->rank;
+            const u64 s0 = carry ? 0 : (*I.sbase)[me], Sme = (*I.sbase)[me + 1] - (*I.sbase)[me] - test_dict_part_pad();      // (carry: positions are offsets in the owner's part)
+            DBuf<u64> dm;
+            std::vector<u64> mcnt(N, 0), wcnt(N, 0);
+            DBuf<u64> mp, wq;
+            try {
+                DBuf<u32> mown, wown;
+                dm.alloc(Sme);
+                prim::for_each(Sme, DictMetaInitFn{dict_sym.p, dict_phr.p, I.ph_off, I.ph_lastT, dm.p, sharded ? 0 : s0}, "grammar_init");      // (sharded dictionary: the arrays are my part already)
+                DBuf<u32> mex(Sg + 1);
+                const u64 nm = prim::exclusive_scan<u32>(Sg, MarkedIn{gid.p, ginfo}, mex.p, false, "dist.mark_scan");
+                mp.alloc(nm);
+                if (carry) { mown.alloc(nm); wown.alloc(Ml); }
+                prim::for_each(Sg, MetaPairFn{perm.p, gid.p, ginfo, mex.p, sigma3, mp.p, pown.p, mown.p}, "dist.mark_pairs");
+                // records (position << 32 | payload) -> sorted by the owner of the position, counts per owner
+                E.bucket_by_owner(*C, dsb.p, mp, nm, mcnt, "dist.mark_owner_sort", carry ? &mown : nullptr);
+                wq.alloc(Ml);
+                prim::for_each(Ml, WalkRequestFn{repq.p, wq.p, perm.p, pown.p, wown.p}, "dist.walk_requests");
+                E.bucket_by_owner(*C, dsb.p, wq, Ml, wcnt, "dist.walk_owner_sort", carry ? &wown : nullptr);
+            } catch (const prim::Error &e) { C->fail(e); std::fill(mcnt.begin(), mcnt.end(), 0); std::fill(wcnt.begin(), wcnt.end(), 0); }
+            std::vector<u64> both(mcnt);
+            both.insert(both.end(), wcnt.begin(), wcnt.end());
+            std::vector<u64> mat = C->allgather_u64(both);           // (raises on every rank if one of them failed above)
+            const auto cm = C->unpack(mat, 2 * (u64)N, 0), cw = C->unpack(mat, 2 * (u64)N, N);      // marks | walks
+            const std::vector<u64> &mrc = cm.rcnt, &wrc = cw.rcnt;
+            const u64 nmr = cm.total, nwr = cw.total, maxm = cm.maxb, maxw = cw.maxb;
+            DBuf<u64> mine, wmine, wans, wback;
+            try { mine.alloc(nmr); wmine.alloc(nwr); wans.alloc(nwr); wback.alloc(Ml); } catch (const prim::Error &e) { C->fail(e); }
+            C->allgather_u64({});                                    // (the bulk exchanges below have no way back)
+            C->named("grammar.mark_pairs").alltoall(mp.p, mcnt, mine.p, mrc, 8, maxm);
+            C->named("grammar.walk_requests").alltoall(wq.p, wcnt, wmine.p, wrc, 8, maxw);
+            mp.release();
+            try {
+                prim::for_each(nmr, ApplyMetaPairsFn{mine.p, dm.p, s0}, "grammar_marks");
+                mine.release();
+                DBuf<u64> stops = grammar_stop_bits(dm.p, Sme, I.maxlen);
+                prim::for_each(nwr, GrammarFn{nullptr, dm.p, MD, nullptr, nullptr, stops.p, Sme, wmine.p, s0, wans.p}, "grammar");
+            } catch (const prim::Error &e) { C->fail(e); }
+            C->allgather_u64({});
+            C->named("grammar.walk_answers").alltoall(wans.p, wrc, wback.p, wcnt, 8, maxw);
+            DBuf<u32> g0l(Ml), g1l(Ml);
+            prim::for_each(Ml, WalkAnswerFn{wq.p, wback.p, g0l.p, g1l.p}, "grammar");
+            C->named("grammar.g0").template allgather_v<u32>(g0l.p, Ml, bbM, true, L.g0.p);
+            C->named("grammar.g1").template allgather_v<u32>(g1l.p, Ml, bbM, true, L.g1.p);
+        }
+        // a8 with dm[] over the whole dictionary: one GPU, or replicated on every rank (GRLBWT_DIST_REPLICATED_GRAMMAR, test tier)
+        void grammar_replicated(const u32 *ginfo, u32 MD) {
+            const u64 S = I.S;
+            DBuf<u64> dm(S);
+            prim::for_each(S, DictMetaInitFn{dict_sym.p, dict_phr.p, I.ph_off, I.ph_lastT, dm.p}, "grammar_init");
+            if (!C) prim::for_each(Sg, MetaPosFn{perm.p, gid.p, ginfo, sigma3, dm.p}, "grammar_marks");
+            else {                           // the marked positions of every rank's groups, as (position, metasymbol) pairs
+                DBuf<u32> mex(Sg + 1);
+                const u64 nm = prim::exclusive_scan<u32>(Sg, MarkedIn{gid.p, ginfo}, mex.p, false, "dist.mark_scan");
+                DBuf<u64> mp(nm);
+                prim::for_each(Sg, MetaPairFn{perm.p, gid.p, ginfo, mex.p, sigma3, mp.p}, "dist.mark_pairs");
+                std::vector<u64> bb;
+                DBuf<u64> all = C->named("grammar.mark_pairs").template allgather_v<u64>(mp.p, nm, bb);
+                prim::for_each(bb[C->size], ApplyMetaPairsFn{all.p, dm.p}, "grammar_marks");
             }
-            // ---- a9: metasymbol of every phrase --------------------------------
+            DBuf<u64> stops = grammar_stop_bits(dm.p, S, I.maxlen);
+            if (!C) prim::for_each(M, GrammarFn{repq.p, dm.p, MD, L.g0.p, L.g1.p, stops.p, S}, "grammar");
+            else {                           // every rank walks for its own metasymbols; the cells are all-gathered
+                DBuf<u32> g0l(Ml), g1l(Ml);
+                prim::for_each(Ml, GrammarFn{repq.p, dm.p, MD, g0l.p, g1l.p, stops.p, S}, "grammar");
+                C->named("grammar.g0").template allgather_v<u32>(g0l.p, Ml, bbM, true, L.g0.p);
+                C->named("grammar.g1").template allgather_v<u32>(g1l.p, Ml, bbM, true, L.g1.p);
+            }
+        }
+        void grammar() {
+            L.g0.alloc(M); L.g1.alloc(M);
+            const u32 MD = sigma3 + (u32)M + 1;
+            DBuf<u32> ginfo(G);
+            prim::for_each(G, PackGroupInfoFn{grank.p, gflag.p, (u32)Moff, ginfo.p}, "grammar_ginfo");
+            // (a dictionary sharded by owner has no other form)
+            if (I.C && I.sbase && (!prim::sw().dist_replicated_grammar || sharded)) grammar_by_owner(ginfo.p, MD);
+            else grammar_replicated(ginfo.p, MD);
+        }
+        // a9: metasymbol of every phrase: fused into the slots | one GPU | (carry) by the position of the whole-phrase member | by
+        // (phrase, metasymbol) pairs
+        void phrase_values(DBuf<u32> &phrase_val) {
+            const u64 D = I.D;
             if (fused_vals) {
-                const u64 Dt = D - pDs;                  // the table phrases: (slot, flags) packed for one gather
+                const u64 Dt = D - I.pDs;                // the table phrases: (slot, flags) packed for one gather
                 DBuf<u64> pinfo(Dt);
-                prim::for_each(Dt, PackPhraseInfoFn{fused_ph_slot + pDs, ph_freq + pDs, ph_lastT + pDs, pinfo.p}, "phrase_values");
-                prim::for_each(G, GroupPhraseValFn{gfull.p, gphr.p, grank.p, pinfo.p, fused_slot_val, pDs, pslot0}, "slot_values");
-            } else phrase_val.alloc(sharded ? Dl : D);
-            if (fused_vals) {}
-            else if (!C) prim::for_each(D, PhraseValFn{pslot.p, ph_freq, ph_lastT, grank.p, phrase_val.p}, "phrase_values");
+                prim::for_each(Dt, PackPhraseInfoFn{I.fused_ph_slot + I.pDs, I.ph_freq + I.pDs, I.ph_lastT + I.pDs, pinfo.p}, "phrase_values");
+                prim::for_each(G, GroupPhraseValFn{gfull.p, gphr.p, grank.p, pinfo.p, I.fused_slot_val, I.pDs, I.pslot0}, "slot_values");
+                return;
+            }
+            phrase_val.alloc(sharded ? Dl : D);
+            if (!C) prim::for_each(D, PhraseValFn{pslot.p, I.ph_freq, I.ph_lastT, grank.p, phrase_val.p}, "phrase_values");
             else if (carry) {
                 // the groups that hold a whole phrase know the POSITION of that member: (position, metasymbol) pairs go to the owner of the
                 // position, which knows the phrase that starts there -- no array over all D phrases on any rank
-                const int N = C->size, me = C->rank;
-                std::vector<u64> scnt(N, 0), rcnt(N, 0);
+                std::vector<u64> scnt(C->size, 0);
                 DBuf<u64> fp;
-                if (!C->pending) { try {
+                C->local([&] {
                     DBuf<u32> gex(G + 1);
                     const u64 nf = prim::exclusive_scan<u32>(G, ByteIn{gfull.p}, gex.p, false, "dist.full_scan");
                     fp.alloc(nf);
                     DBuf<u32> fown(nf);
                     prim::for_each(G, GroupPosPairFn{gfull.p, gphr.p, grank.p, (u32)Moff, gex.p, fp.p, perm.p, pown.p, fown.p}, "dist.full_pairs");
-                    bucket_by_owner(*C, dsb.p, fp, nf, scnt, "dist.full_pairs", &fown);
-                } catch (const prim::Error &e) { C->fail(e); std::fill(scnt.begin(), scnt.end(), 0); } }
-                std::vector<u64> mat = C->allgather_u64(scnt);
-                u64 got = 0, maxb = 0;
-                for (int g = 0; g < N; g++) { rcnt[g] = mat[(u64)g * N + me]; got += rcnt[g]; for (int d = 0; d < N; d++) maxb = std::max(maxb, mat[(u64)g * N + d]); }
-                // (checked for EVERY rank's column on every rank -- the matrix and the owners' phrase ranges are known to all: a rank that
-                // threw alone here would leave the others waiting in the exchange below)
-                for (int d = 0; d < N; d++) {
-                    u64 col = 0;
-                    for (int g = 0; g < N; g++) col += mat[(u64)g * N + d];
-                    if (col != (*dbase)[d + 1] - (*dbase)[d]) throw prim::Error(-71, "dist dictionary: whole-phrase suffix count does not match the phrase count");
-                }
-                DBuf<u64> mine(got);
+                    E.bucket_by_owner(*C, dsb.p, fp, nf, scnt, "dist.full_pairs", &fown);
+                });
+                if (C->pending) std::fill(scnt.begin(), scnt.end(), 0);
+                const auto cn = C->counts(scnt);
+                check_phrase_columns(cn.mat, *I.dbase);
+                DBuf<u64> mine(cn.total);
                 DBuf<u32> phrase_rank(Dl);
-                C->named("phrase.rank_pairs").alltoall(fp.p, scnt, mine.p, rcnt, 8, maxb);
-                prim::for_each(got, ApplyPosPairsFn{mine.p, dict_phr.p, 0, phrase_rank.p}, "dist.apply_phrase_ranks");      // (offsets in my part)
-                prim::for_each(Dl, PhraseValDistFn{phrase_rank.p, ph_freq, ph_lastT, phrase_val.p}, "phrase_values");
+                C->named("phrase.rank_pairs").alltoall(fp.p, scnt, mine.p, cn.rcnt, 8, cn.maxb);
+                prim::for_each(cn.total, ApplyPosPairsFn{mine.p, dict_phr.p, 0, phrase_rank.p}, "dist.apply_phrase_ranks");      // (offsets in my part)
+                prim::for_each(Dl, PhraseValDistFn{phrase_rank.p, I.ph_freq, I.ph_lastT, phrase_val.p}, "phrase_values");
             } else {                             // a whole-phrase suffix sits on the rank that owns its key: (phrase, metasymbol) pairs
                 DBuf<u32> phrase_rank(sharded ? Dl : D), fex(D + 1);
                 const u64 nf = prim::exclusive_scan<u32>(D, OwnPhraseIn{pslot.p}, fex.p, true, "dist.full_scan");
                 DBuf<u64> fp(nf);
                 prim::for_each(D, OwnPhrasePairFn{pslot.p, fex.p, grank.p, (u32)Moff, fp.p}, "dist.full_pairs");
-                if (dbase) {
+                if (I.dbase) {
                     // The value of a phrase is wanted by ONE rank: the one that merged it and answers its senders (dist_round_t).  The
                     // pairs are in phrase order and the owners' phrases are contiguous ranges, so every owner's pairs are one block:
                     // an all-to-all of 8 bytes per phrase in all, where rounds 1-4 all-gathered all D pairs to every rank.
+                    const std::vector<u64> &dbase = *I.dbase;
                     const int N = C->size, me = C->rank;
-                    std::vector<u64> scnt(N, 0), rcnt(N, 0);
+                    std::vector<u64> scnt(N, 0);
                     u64 prev = 0;
                     for (int g = 0; g < N; g++) {
-                        const u64 hi = (*dbase)[g + 1] ? (u64)fex.get((*dbase)[g + 1]) : 0;
+                        const u64 hi = dbase[g + 1] ? (u64)fex.get(dbase[g + 1]) : 0;
                         scnt[g] = hi - prev; prev = hi;
                     }
-                    std::vector<u64> mat = C->allgather_u64(scnt);
-                    u64 got = 0, maxb = 0;
-                    for (int g = 0; g < N; g++) { rcnt[g] = mat[(u64)g * N + me]; got += rcnt[g]; for (int d = 0; d < N; d++) maxb = std::max(maxb, mat[(u64)g * N + d]); }
-                    for (int d = 0; d < N; d++) {      // (every rank's column on every rank: see above)
-                        u64 col = 0;
-                        for (int g = 0; g < N; g++) col += mat[(u64)g * N + d];
-                        if (col != (*dbase)[d + 1] - (*dbase)[d]) throw prim::Error(-71, "dist dictionary: whole-phrase suffix count does not match the phrase count");
-                    }
+                    const auto cn = C->counts(scnt);
+                    check_phrase_columns(cn.mat, dbase);
+                    const u64 got = cn.total;
                     DBuf<u64> mine(got);
-                    C->named("phrase.rank_pairs").alltoall(fp.p, scnt, mine.p, rcnt, 8, maxb);
-                    if (sharded) {               // (my phrases' arrays are local: ranks, frequencies and values by local phrase number)
-                        prim::for_each(got, ApplyPairsFn{mine.p, phrase_rank.p, d0}, "dist.apply_phrase_ranks");
-                        prim::for_each(got, PhraseValDistFn{phrase_rank.p, ph_freq, ph_lastT, phrase_val.p}, "phrase_values");
-                    } else {
-                    prim::for_each(got, ApplyPairsFn{mine.p, phrase_rank.p}, "dist.apply_phrase_ranks");
-                    // (only my own range of phrase_val is filled and read)
-                    prim::for_each(got, PhraseValDistFn{phrase_rank.p + (*dbase)[me], ph_freq + (*dbase)[me], ph_lastT + (*dbase)[me], phrase_val.p + (*dbase)[me]}, "phrase_values");
-                    }
+                    C->named("phrase.rank_pairs").alltoall(fp.p, scnt, mine.p, cn.rcnt, 8, cn.maxb);
+                    // (sharded: my phrases' arrays are local -- ranks, frequencies and values by local phrase number; otherwise only my own
+                    // range of phrase_val is filled and read)
+                    const u64 off = sharded ? 0 : dbase[me];
+                    prim::for_each(got, ApplyPairsFn{mine.p, phrase_rank.p, sharded ? d0 : 0}, "dist.apply_phrase_ranks");
+                    prim::for_each(got, PhraseValDistFn{phrase_rank.p + off, I.ph_freq + off, I.ph_lastT + off, phrase_val.p + off}, "phrase_values");
                 } else {
-                std::vector<u64> bb;
-                DBuf<u64> allf = C->named("phrase.rank_pairs").template allgather_v<u64>(fp.p, nf, bb);
-                if (bb[C->size] != D) throw prim::Error(-71, "dist dictionary: whole-phrase suffix count does not match the phrase count");
-                prim::for_each(D, ApplyPairsFn{allf.p, phrase_rank.p}, "dist.apply_phrase_ranks");
-                prim::for_each(D, PhraseValDistFn{phrase_rank.p, ph_freq, ph_lastT, phrase_val.p}, "phrase_values");
+                    std::vector<u64> bb;
+                    DBuf<u64> allf = C->named("phrase.rank_pairs").template allgather_v<u64>(fp.p, nf, bb);
+                    if (bb[C->size] != D) throw prim::Error(-71, "dist dictionary: whole-phrase suffix count does not match the phrase count");
+                    prim::for_each(D, ApplyPairsFn{allf.p, phrase_rank.p}, "dist.apply_phrase_ranks");
+                    prim::for_each(D, PhraseValDistFn{phrase_rank.p, I.ph_freq, I.ph_lastT, phrase_val.p}, "phrase_values");
                 }
             }
         }
-        L.info.M = M;
+    };
+    template <class cell_t, bool FIRST>
+    void dict_stage(const DictIn<cell_t, FIRST> &I, LevelData &L, DBuf<u32> &phrase_val) {
+        DictStage<cell_t, FIRST> Z(*this, I, L);
+        const Comm *C = I.C;
+        Z.build_dictionary();
+        if (!C) Z.suffix_sort_local();
+        else if (Z.sharded) Z.suffix_sort_sharded();
+        else { try { Z.suffix_sort_local(); } catch (const prim::Error &e) { C->fail(e); } }
+        {
+            StageTimer st(&tm.dict_groups, "dict_groups");
+            if (Z.sharded && !Z.carry) Z.fetch_records();
+            if (!C) Z.group_fold();
+            else C->local([&] { Z.group_fold(); });
+            Z.group_counts();
+            Z.prebwt();
+            Z.grammar();
+            Z.phrase_values(phrase_val);
+        }
+        L.info.M = Z.M;
     }
 
     // a10: the local parse: slot id of every occurrence -> (rank<<2 | rep<<1 | T) of its phrase
@@ -4518,8 +4511,11 @@ class Engine {
         LocalParse P;
         hash_local<cell_t, FIRST>(t, n, ops, P, L, true);
         DBuf<u32> phrase_val, slot_val(P.cap);
-        dict_stage<cell_t, FIRST>(nullptr, t, ops, P.D, P.S, P.maxlen, P.ph_pos.p, P.ph_freq.p, P.ph_off.p, P.ph_lastT.p, sigma, L, phrase_val,
-                                  P.ph_slot.p, slot_val.p, P.ph_key.p, P.Ds, P.rec_b, P.slot0);
+        DictIn<cell_t, FIRST> I;
+        I.t = t; I.ops = ops; I.D = P.D; I.S = P.S; I.maxlen = P.maxlen; I.sigma = sigma;
+        I.ph_pos = P.ph_pos.p; I.ph_freq = P.ph_freq.p; I.ph_off = P.ph_off.p; I.ph_lastT = P.ph_lastT.p;
+        I.fused_ph_slot = P.ph_slot.p; I.fused_slot_val = slot_val.p; I.pkeys = P.ph_key.p; I.pDs = P.Ds; I.pkb = P.rec_b; I.pslot0 = P.slot0;
+        dict_stage(I, L, phrase_val);
         emit_local(P, nullptr, &slot_val, true);
         finish_round(P, L, stats.n_strings, P.n_occ);
     }
@@ -4985,8 +4981,7 @@ class Engine {
                 DBuf<u64> bound(2 * ((u64)N + 1));
                 prim::for_each(P.D, PhraseOwnerFn<cell_t, FIRST>{t, ops, P.ph_pos.p, P.ph_len.p, (u32)N, owner.p, idx.p, P.ph_key.p, P.Ds, P.rec_b},
                                "dist.phrase_owner");
-                int obits = (int)bitlen64((u64)N - 1);
-                if (obits < 1) obits = 1;
+                const int obits = std::max((int)bitlen64((u64)N - 1), 1);
                 const int res = prim::sort_pairs<u32, u32>(owner.p, idx.p, owner2.p, idx2.p, P.D, 0, obits, "dist.owner_sort");
                 order = std::move(res ? idx2 : idx);
                 const u32 *okey = res ? owner2.p : owner.p;
@@ -5013,13 +5008,10 @@ class Engine {
             }
             const u64 w = mine.size();
             std::vector<u64> mat = C.allgather_u64(mine);
-            u64 maxc = 0;
-            for (int g = 0; g < N; g++) {
-                rpc[g] = mat[g * w + me]; rcc[g] = mat[g * w + N + me];
-                Dr += rpc[g]; Sr += rcc[g];
-                occ_total += mat[g * w + 2 * N]; n_total += mat[g * w + 2 * N + 1];
-                for (int d = 0; d < N; d++) { maxp = std::max(maxp, mat[g * w + d]); maxc = std::max(maxc, mat[g * w + N + d]); }
-            }
+            const auto cp = C.unpack(mat, w, 0), cq = C.unpack(mat, w, N);      // phrases | cells
+            rpc = cp.rcnt; rcc = cq.rcnt; Dr = cp.total; Sr = cq.total; maxp = cp.maxb;
+            const u64 maxc = cq.maxb;
+            for (int g = 0; g < N; g++) { occ_total += mat[g * w + 2 * N]; n_total += mat[g * w + 2 * N + 1]; }
             rlen.alloc(Dr); rfreq.alloc(Dr); rcells.alloc(Sr);
             C.named("dict.phrase_len").alltoall(slen.p, pc, rlen.p, rpc, 4, maxp);
             C.named("dict.phrase_freq").alltoall(sfreq.p, pc, rfreq.p, rpc, 4, maxp);
@@ -5097,11 +5089,11 @@ class Engine {
             // does GRLBWT_DIST_GATHERED_DICT=1 (rounds 1-4).
             {
                 u64 ml = 0, fl = 0, fm = 0;
-                if (!C.pending) { try {
+                C.local([&] {
                     ml = Do ? (u64)prim::reduce_max<u32>(Do, LenIn{o_len.p}, "dist.maxlen") : 0;
                     fl = prim::reduce_sum<u64>(Do, IdxIn<idx_t>{o_freq.p}, "dist.freq_check");
                     fm = Do ? (u64)prim::reduce_max<u64>(Do, IdxIn<idx_t>{o_freq.p}, "dist.freq_check") : 0;
-                } catch (const prim::Error &e) { C.fail(e); } }
+                });
                 std::vector<u64> mf = C.allgather_u64({ml, fl, fm});
                 u64 mx = 0, fs = 0;
                 for (int g = 0; g < N; g++) { mx = std::max(mx, mf[3 * g]); fs += mf[3 * g + 1]; maxfreq = std::max(maxfreq, mf[3 * g + 2]); }
@@ -5148,8 +5140,12 @@ class Engine {
         }
         // ---- dictionary stage: suffix sort + group stage sharded by key range, grammar passes and dictionary by owner ----
         DBuf<u32> gval;
-        dict_stage<u32, false>(prim::sw().dist_replicated_dict ? nullptr : &C, gcells.p, CellOps<u32, false>{0u}, D, S, maxlen, ph_pos.p, ph_freq.p,
-                               ph_off.p, ph_lastT.p, sigma, L, gval, nullptr, nullptr, nullptr, 0, 0, 0, &dbase, &sbase, sharded_dict, maxfreq);
+        DictIn<u32, false> I;
+        I.C = prim::sw().dist_replicated_dict ? nullptr : &C;
+        I.t = gcells.p; I.ops = CellOps<u32, false>{0u}; I.D = D; I.S = S; I.maxlen = maxlen; I.sigma = sigma;
+        I.ph_pos = ph_pos.p; I.ph_freq = ph_freq.p; I.ph_off = ph_off.p; I.ph_lastT = ph_lastT.p;
+        I.dbase = &dbase; I.sbase = &sbase; I.sharded_dict = sharded_dict; I.maxfreq = maxfreq;
+        dict_stage(I, L, gval);
         // ---- back to the shards: the value of every phrase I merged returns to its sender, in the order it came ----
         DBuf<u32> lval(P.D);
         {
@@ -5332,9 +5328,9 @@ class Engine {
                     std::vector<u64> kch = kc.to_host(2 * (u64)N);
                     for (int d = 0; d < N; d++) { scnt[d] = kch[2 * d + 1]; soff[d + 1] = soff[d] + scnt[d]; }
                 } catch (const prim::Error &e) { C.fail(e); std::fill(scnt.begin(), scnt.end(), 0); std::fill(soff.begin(), soff.end(), 0); }
-                std::vector<u64> rc = C.allgather_u64(scnt);     // rc[s*N + d]
-                for (int g = 0; g < N; g++) { rcnt[g] = rc[(u64)g * N + me]; Rw += rcnt[g]; }
-                const u64 maxw = *std::max_element(rc.begin(), rc.end());
+                const auto cn = C.counts(scnt);
+                rcnt = cn.rcnt; Rw = cn.total;
+                const u64 maxw = cn.maxb;
                 // (the lengths travel as u32 whenever the level's longest run fits -- the ranks agreed on `maxrun` for the cell layout)
                 const bool narrow = sizeof(idx_t) == 8 && maxrun < 0xFFFFFFFFull;
                 DBuf<u32> ssym, slen32, wlen32; DBuf<idx_t> slen;
@@ -5361,12 +5357,10 @@ class Engine {
             bwt.sym.release(); bwt.len.release(); bwt.pos.release();
             // (4) the cells of my buckets, from every rank; rank order inside a bucket = order of the slices
             {
-                std::vector<u64> scnt(N), rcnt(N);
-                u64 Er = 0;
-                for (int d = 0; d < N; d++) scnt[d] = v[d];
-                for (int g = 0; g < N; g++) { rcnt[g] = mat[(u64)g * 2 * N + me]; Er += rcnt[g]; }
-                u64 maxc = 0;
-                for (int g = 0; g < N; g++) for (int d = 0; d < N; d++) maxc = std::max(maxc, mat[(u64)g * 2 * N + d]);
+                const std::vector<u64> scnt(v.begin(), v.begin() + N);
+                const auto cn = C.unpack(mat, 2 * (u64)N, 0);
+                const std::vector<u64> &rcnt = cn.rcnt;
+                const u64 Er = cn.total, maxc = cn.maxb;
                 const int bits = kb;
                 // (the received blocks are bucket-sorted: merged by block offsets; GRLBWT_MERGE_CELLS=sort keeps the stable radix sort)
                 const bool merge_by_blocks = prim::sw().merge_cells != 's';

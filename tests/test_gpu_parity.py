@@ -223,6 +223,18 @@ def test_doubling_rounds_of_the_suffix_refinement(hip, oracle_mod, monkeypatch):
             parity.check_final(hip, d, w)
 
 
+@pytest.mark.parametrize("cap", ["1", "4"])
+def test_large_group_refinement_branch(hip, oracle_mod, monkeypatch, cap):
+    """GRLBWT_SEG_CAP lowered: the groups of a refinement round that ordinary inputs order by counting take the large-group path
+    (two radix sorts: by key, then stable by group) -- in the symbol-extension rounds of both index widths and, with the long-run
+    collection, behind the long-phrase forms of the sort (run-aware keys, doubling rounds where a level takes them)."""
+    from tests.test_engine_logic_sim import _long_run_collection
+    monkeypatch.setenv("GRLBWT_SEG_CAP", cap)
+    parity.check_stagewise(hip, workloads.sampled_reads(20000, 100, 100000, seed=11).tobytes(), 1)
+    parity.check_stagewise(hip, workloads.zipf_tokens(200000, doc_len=500, vocab=20000).tobytes(), 2, engine.FLAG_FORCE_IDX64)
+    parity.check_final(hip, _long_run_collection(2000, 4, 5), 1)
+
+
 def test_stagewise_idx64(hip, oracle_mod):
     parity.check_stagewise(hip, workloads.sampled_reads(5000, 80, 30000, seed=2).tobytes(), 1, engine.FLAG_FORCE_IDX64)
 
