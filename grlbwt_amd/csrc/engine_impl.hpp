@@ -1143,16 +1143,15 @@ struct GatherKeyPosFn {   // records in owner order
     const u32 *order; const u64 *lk; const u32 *lp; u64 *sk; u32 *sp;
     GRL_DEV void operator()(u64 j) const { const u32 i = order[j]; sk[j] = lk[i]; sp[j] = lp[i]; }
 };
-struct HeadFlagFn {       // hflag[t] = 1 where the sorted key changes
-    const u64 *k; u8 *hflag;
-    GRL_DEV void operator()(u64 t) const { hflag[t] = (t == 0 || k[t] != k[t - 1]) ? 1 : 0; }
-};
-struct FirstUnresolvedFn { // after the first sort: member of a group of > 1 suffixes whose key holds no sentinel (the suffix is at
-                           // least K symbols long): what the refinement below has to look at again
-    const u64 *k; const u8 *hflag; u64 S; u64 sent; u8 *uflag;
+struct HeadFlagFn {       // after the first sort: hflag[t] = 1 where the sorted key changes; uflag[t] = 1 for a member of a group of > 1
+                          // suffixes whose key holds no sentinel (the suffix is at least K symbols long): what the refinement
+                          // below has to look at again.  (One pass over the keys: k[t-1], k[t], k[t+1] decide both.)
+    const u64 *k; u64 S; u64 sent; u8 *hflag; u8 *uflag;
     GRL_DEV void operator()(u64 t) const {
-        bool multi = !hflag[t] || (t + 1 < S && !hflag[t + 1]);
-        uflag[t] = (multi && (k[t] & sent) != sent) ? 1 : 0;
+        const u64 kt = k[t];
+        const bool head = t == 0 || k[t - 1] != kt, tied_next = t + 1 < S && k[t + 1] == kt;
+        hflag[t] = head ? 1 : 0;
+        uflag[t] = ((!head || tied_next) && (kt & sent) != sent) ? 1 : 0;
     }
 };
 // Refinement by SYMBOL EXTENSION.  After the first pass a group of equal keys whose suffixes have not ended is re-sorted,
@@ -1163,9 +1162,12 @@ struct FirstUnresolvedFn { // after the first sort: member of a group of > 1 suf
 // key ranges.  (Rounds 1 and 2 used prefix doubling over positional ranks: every pass scattered the ranks of the re-sorted
 // suffixes to their dictionary positions -- 85 ms of the 10 GB build -- and in the collection-level mode all-gathered them.)
 // A group of at most kSegCap members is ordered by counting (every member counts the smaller keys of its group: the keys sit
-// in neighbouring words); larger groups take two stable radix sorts together, by key and then by group.
+// in neighbouring words).  A group of at most GRLBWT_SEG_LDS_CAP members is ordered in LDS by one workgroup (its members are
+// neighbours in the item list: read once, written once); the still larger ones take two stable radix sorts together, by key and
+// then by group.
 static constexpr u32 kSegCap = 64;
 static_assert(prim::Switches{}.seg_cap == (int)kSegCap, "GRLBWT_SEG_CAP defaults to kSegCap");
+static constexpr u32 kSegLdsShort = 512;       // LDS tier: groups up to here take a workgroup of one wave, the others one of four
 struct GroupStartsFn {    // gstart[dense group id] = head slot ; gstart[G] = S
     const u8 *hflag; const u32 *ex; u64 S; u32 *gstart;
     GRL_DEV void operator()(u64 t) const {
@@ -1249,13 +1251,43 @@ struct SegSortSmallFn {   // one lane per item of a group of at most kSegCap ite
         }
     }
 };
-struct SegBigIn {         // 1 for the items of groups above kSegCap
-    const u8 *uhead; const u32 *hex; const u32 *seg_start; u32 cap;
-    GRL_DEV u32 operator()(u64 j) const { const u32 s = hex[j] + uhead[j] - 1; return (seg_start[s + 1] - seg_start[s] > cap) ? 1u : 0u; }
+// One scan classifies a round's items.  a: items of the groups above both limits (low word), items of the LDS tier (high word);
+// b: heads of the LDS tier's groups, short ones in the low word, long ones in the high.
+typedef prim::Pair<u64, u64> SegTiers;
+struct SegBigIn {
+    const u8 *uhead; const u32 *hex; const u32 *seg_start; u32 cap, lds_cap;
+    GRL_DEV SegTiers operator()(u64 j) const {
+        const u32 s = hex[j] + uhead[j] - 1, n = seg_start[s + 1] - seg_start[s];
+        const bool mid = n > cap && n <= lds_cap;
+        return SegTiers(mid ? 1ull << 32 : (n > cap ? 1ull : 0ull), (mid && uhead[j]) ? (n <= kSegLdsShort ? 1ull : 1ull << 32) : 0ull);
+    }
+};
+struct SegBigEmitFn {     // bex[]: the large items counted; mid[]: the groups of the LDS tier, short ones from the front, long ones from the back
+    static constexpr bool kWaveEmit = false;
+    const u32 *hex; u32 *bex; u32 *mid; u64 nmid;
+    GRL_DEV void operator()(u64 j, SegTiers ex, SegTiers v) const {
+        bex[j] = (u32)ex.a;
+        if (v.b & 0xffffffffull) mid[ex.b & 0xffffffffull] = hex[j];
+        else if (v.b) mid[nmid - 1 - (ex.b >> 32)] = hex[j];
+    }
+};
+struct SegBigLdsFn {      // the LDS tier's segments and what a sorted position writes (what SegBigWriteFn writes)
+    const u32 *mid; const u32 *seg_start; const u64 *ukey; const u32 *uslot; const u32 *uq; u64 sent;
+    u32 *perm; u8 *hflag; u8 *unext;
+    GRL_DEV u32 begin(u64 b) const { return seg_start[mid[b]]; }
+    GRL_DEV u32 end(u64 b) const { return seg_start[mid[b] + 1]; }
+    GRL_DEV u64 key(u32 j) const { return ukey[j]; }
+    // position pos takes item src (key k); head: first of its key, not of the group; tied: an equal key stands beside it
+    GRL_DEV void write(u32 pos, u32 src, u64 k, bool head, bool tied) const {
+        const u32 dst = uslot[pos];
+        perm[dst] = uq[src];
+        if (head) hflag[dst] = 1;
+        unext[pos] = (tied && (k & sent) != sent) ? 1 : 0;
+    }
 };
 struct SegBigGatherFn {
     const u8 *uhead; const u32 *hex; const u32 *seg_start; const u32 *bex; const u64 *ukey; u32 cap; u32 *bitem; u64 *bkey; u32 *bidx;
-    GRL_DEV void operator()(u64 j) const {
+    GRL_DEV void operator()(u64 j) const {       // (cap: the larger of the two limits)
         const u32 s = hex[j] + uhead[j] - 1;
         if (seg_start[s + 1] - seg_start[s] > cap) { const u32 p = bex[j]; bitem[p] = (u32)j; bkey[p] = ukey[j]; bidx[p] = p; }
     }
@@ -3820,23 +3852,37 @@ class Engine {
             k = kb.p;
         }
         if (rk.rb) prim::for_each(Sg, InitSkipFn{perm.p, rk.rem, (u32)ks.K, rk.skip}, "suffix_runs");
-        prim::for_each(Sg, HeadFlagFn{k, hflag}, "suffix_heads");
-        prim::for_each(Sg, FirstUnresolvedFn{k, hflag, Sg, ks.sent, uflag}, "suffix_unresolved");
+        prim::for_each(Sg, HeadFlagFn{k, Sg, ks.sent, hflag, uflag}, "suffix_heads");
     }
     // One refinement round: the U unresolved suffixes (slot, position, extension key, head of its group so far) are ordered inside
     // their groups; perm[] / hflag[] take the new order and heads, unext[] says who is still unresolved (key ends in sent_r).
-    // (GRLBWT_SEG_CAP, product tier: the tests lower the limit so that ordinary inputs take the large-group path too)
+    // (GRLBWT_SEG_CAP and GRLBWT_SEG_LDS_CAP, product tier: the tests lower the limits so that ordinary inputs take every tier)
     static void order_segments(u64 U, const u8 *uhead, u32 *hex, const u64 *ukey, const u32 *uslot, const u32 *uq, u64 sent_r, int kbits_r, u32 cap,
                         u32 *perm, u8 *hflag, u8 *unext) {
         const u64 nseg = prim::exclusive_scan<u32>(U, ByteIn{uhead}, hex, false, "suffix_heads");
-        DBuf<u32> seg_start(nseg + 1), bex(U + 1);
+        u32 lds_cap = (u32)std::max(prim::sw().seg_lds_cap, 0);
+#ifdef GRLBWT_PRIM_HIP
+        lds_cap = std::min(lds_cap, prim::seg_sort_lds_max());
+#endif
+        const u32 big_cap = std::max(cap, lds_cap);
+        const u64 nmid = U / ((u64)cap + 1) + 1;     // (no more groups above cap than this)
+        DBuf<u32> seg_start(nseg + 1), bex(U + 1), mid(nmid);
         prim::for_each(U, SegStartFn{uhead, hex, U, seg_start.p}, "suffix_gstart");
         prim::for_each(U, SegSortSmallFn{uhead, hex, seg_start.p, uslot, uq, ukey, sent_r, cap, perm, hflag, unext}, "suffix_sort.small");
-        const u64 NB = prim::exclusive_scan<u32>(U, SegBigIn{uhead, hex, seg_start.p, cap}, bex.p, false, "suffix_sort.big_scan");
-        if (NB) {                                // groups above the cap: by key, then (stable) by group
+        // the large items counted and the LDS tier's groups listed by one scan (one host synchronisation)
+        const SegTiers tot = prim::exclusive_scan_emit<SegTiers>(U, SegBigIn{uhead, hex, seg_start.p, cap, lds_cap},
+                                                                 SegBigEmitFn{hex, bex.p, mid.p, nmid}, "suffix_sort.big_scan");
+        const u64 NB = tot.a & 0xffffffffull, n_short = tot.b & 0xffffffffull, n_long = tot.b >> 32;
+        if (prim::sw().table_trace)
+            fprintf(stderr, "[grlbwt] level %d refinement round: %llu items in %llu groups; counting %llu, LDS %llu (%llu short + %llu long groups), radix %llu\n",
+                    prim::rt().tag, (unsigned long long)U, (unsigned long long)nseg, (unsigned long long)(U - NB - (tot.a >> 32)), (unsigned long long)(tot.a >> 32),
+                    (unsigned long long)n_short, (unsigned long long)n_long, (unsigned long long)NB);
+        order_segments_lds(n_short, SegBigLdsFn{mid.p, seg_start.p, ukey, uslot, uq, sent_r, perm, hflag, unext}, false, std::min(lds_cap, kSegLdsShort));
+        order_segments_lds(n_long, SegBigLdsFn{mid.p + (nmid - n_long), seg_start.p, ukey, uslot, uq, sent_r, perm, hflag, unext}, true, lds_cap);
+        if (NB) {                                // groups above the limits: by key, then (stable) by group
             DBuf<u32> bitem(NB), bidx(NB), bidx2(NB), key2(NB), key2b(NB);
             DBuf<u64> bkey(NB), bkey2(NB);
-            prim::for_each(U, SegBigGatherFn{uhead, hex, seg_start.p, bex.p, ukey, cap, bitem.p, bkey.p, bidx.p}, "suffix_sort.big_gather");
+            prim::for_each(U, SegBigGatherFn{uhead, hex, seg_start.p, bex.p, ukey, big_cap, bitem.p, bkey.p, bidx.p}, "suffix_sort.big_gather");
             const u32 *i1 = prim::sort_pairs<u64, u32>(bkey.p, bidx.p, bkey2.p, bidx2.p, NB, 0, kbits_r, "suffix_sort") ? bidx2.p : bidx.p;
             u32 *i1o = (i1 == bidx.p) ? bidx2.p : bidx.p;
             prim::for_each(NB, SegBigSegKeyFn{i1, bitem.p, uhead, hex, key2.p}, "suffix_sort.big_groups");
@@ -3844,6 +3890,30 @@ class Engine {
             const int res = prim::sort_pairs<u32, u32>(key2.p, (u32 *)i1, key2b.p, i1o, NB, 0, sbits, "suffix_sort");
             prim::for_each(NB, SegBigWriteFn{res ? key2b.p : key2.p, res ? i1o : i1, bitem.p, ukey, uq, uslot, NB, sent_r, perm, hflag, unext}, "suffix_refine");
         }
+    }
+    // The n listed groups of the LDS tier (each of at most max_items members): stable order by key inside each, then the write-out.
+    static void order_segments_lds(u64 n, const SegBigLdsFn &f, bool wide, u32 max_items) {
+        if (n == 0) return;
+#ifdef GRLBWT_PRIM_HIP
+        if (wide) prim::seg_sort_lds<256>(n, f, max_items, "suffix_sort.lds");
+        else prim::seg_sort_lds<64>(n, f, max_items, "suffix_sort.lds");
+#else
+        // (the serial stand-in: the same order and the same write-out, one group after the other)
+        (void)wide;
+        std::vector<u32> ord;
+        for (u64 b = 0; b < n; b++) {
+            const u32 a = f.begin(b), e = f.end(b);
+            if (e - a > max_items) throw prim::Error(-71, "LDS tier: a listed group is larger than its limit");
+            ord.resize(e - a);
+            for (u32 i = 0; i < e - a; i++) ord[i] = a + i;
+            std::stable_sort(ord.begin(), ord.end(), [&](u32 x, u32 y) { return f.key(x) < f.key(y); });
+            for (u32 p = 0; p < e - a; p++) {
+                const u64 k = f.key(ord[p]);
+                const bool eq_prev = p > 0 && f.key(ord[p - 1]) == k, eq_next = p + 1 < e - a && f.key(ord[p + 1]) == k;
+                f.write(a + p, ord[p], k, p > 0 && !eq_prev, eq_prev || eq_next);
+            }
+        }
+#endif
     }
     // The sorted slots are cut into groups of equal suffixes at the heads: gstart[], gid[]; returns the number of groups.
     static u64 close_groups(const u8 *hflag, u32 *ex, u64 Sg, u32 *gstart, u32 *gid) {

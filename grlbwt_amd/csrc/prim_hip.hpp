@@ -57,6 +57,7 @@ struct Runtime {
     int device = -1;                  // device the stream and the slabs belong to (-1: not initialised)
     int live_ctx = 0;                 // contexts alive in this process (they share stream and allocator)
     int num_cus = 256;
+    u32 lds_bytes = 65536;            // LDS one workgroup may take
     u64 bytes_allocated = 0, peak_bytes = 0;
     bool sync_each_launch = false;   // debug: catch faults at the launch site
     // per-kernel timing with HIP events on the engine's stream (bench.py roofline leg)
@@ -98,6 +99,7 @@ inline void init(int device) {
     R.device = device;
     if (const char t = init_sw().trace) { R.trace = t == '1'; R.sync_each_launch = R.trace; }
     R.num_cus = p.multiProcessorCount > 0 ? p.multiProcessorCount : 256;
+    R.lds_bytes = p.sharedMemPerBlock >= 65536 ? (u32)std::min<size_t>(p.sharedMemPerBlock, (size_t)160 << 10) : 65536u;
     if (!R.stream) {
         if (!R.own_stream) GRL_HIP_CHECK(hipStreamCreateWithFlags(&R.own_stream, hipStreamNonBlocking));
         R.stream = R.own_stream;
@@ -1555,6 +1557,61 @@ inline T exclusive_scan(u64 n, F in, T *out, bool store_total_at_n = false, cons
 template <class T, class F>
 inline void exclusive_scan_nosync(u64 n, F in, T *out, bool store_total_at_n = false, const char *name = "scan") {
     exclusive_scan_async<T, F>(n, in, out, nullptr, store_total_at_n ? out + n : nullptr, name);
+}
+
+// ------------------------------------------------- segments ordered in LDS
+// One workgroup per listed segment [f.begin(b), f.end(b)) of at most max_items items.  The keys f.key(item) and the items'
+// places in the segment go to LDS (8 + 2 bytes per item, padded with the largest key to the next power of two of the segment's
+// OWN size); a bitonic network orders the (key, place) pairs -- the place as the low part of the comparison makes it the stable
+// order by key, and keeps the padding behind the items --; then f.write(position, source item, key, first of its key but not of
+// the segment, an equal key stands beside it) runs for every position.  Segments up to a few hundred items take TB = 64 (a wave
+// and 5 KB: a CU holds many), the longer ones TB = 256.
+static constexpr u32 kSegLdsItemBytes = 10;
+inline u32 seg_sort_lds_max() {          // the largest segment a workgroup's LDS holds (a power of two, the places are 16-bit)
+    u32 m = 1024;
+    while (m < 32768 && (u64)m * 2 * kSegLdsItemBytes <= rt().lds_bytes) m *= 2;
+    return m;
+}
+template <int TB, class F>
+__global__ void __launch_bounds__(TB) k_seg_sort_lds(F f, u32 pmax) {
+    extern __shared__ u64 s_seg[];
+    u64 *s_k = s_seg;
+    u16 *s_i = reinterpret_cast<u16 *>(s_seg + pmax);
+    const u32 a = f.begin(blockIdx.x), n = f.end(blockIdx.x) - a;
+    u32 P = 2;
+    while (P < n) P <<= 1;
+    if (P <= pmax) {                       // (uniform in the workgroup; the lists hold no longer segment)
+        for (u32 i = threadIdx.x; i < P; i += TB) { s_k[i] = i < n ? f.key(a + i) : ~0ull; s_i[i] = (u16)i; }
+        for (u32 k = 2; k <= P; k <<= 1) {
+            for (u32 j = k >> 1; j > 0; j >>= 1) {
+                __syncthreads();
+                for (u32 t = threadIdx.x; t < (P >> 1); t += TB) {
+                    const u32 lo = ((t & ~(j - 1)) << 1) | (t & (j - 1)), hi = lo | j;
+                    const u64 kl = s_k[lo], kh = s_k[hi];
+                    const u16 il = s_i[lo], ih = s_i[hi];
+                    const bool gt = kl > kh || (kl == kh && il > ih);
+                    if (gt == ((lo & k) == 0)) { s_k[lo] = kh; s_k[hi] = kl; s_i[lo] = ih; s_i[hi] = il; }
+                }
+            }
+        }
+        __syncthreads();
+        for (u32 p = threadIdx.x; p < n; p += TB) {
+            const u64 k = s_k[p];
+            const bool eq_prev = p > 0 && s_k[p - 1] == k, eq_next = p + 1 < n && s_k[p + 1] == k;
+            f.write(a + p, a + (u32)s_i[p], k, p > 0 && !eq_prev, eq_prev || eq_next);
+        }
+    }
+}
+template <int TB, class F>
+inline void seg_sort_lds(u64 nseg, F f, u32 max_items, const char *name = "seg_sort_lds") {
+    if (nseg == 0) return;
+    u32 pmax = 2;
+    while (pmax < max_items) pmax <<= 1;
+    if (pmax > seg_sort_lds_max() || nseg > 0x7fffffffull) throw Error(-22, std::string(name) + ": segments too long or too many for the LDS sort");
+    prof_begin(name);
+    hipLaunchKernelGGL((k_seg_sort_lds<TB, F>), dim3((unsigned)nseg), dim3(TB), (size_t)pmax * kSegLdsItemBytes, rt().stream, f, pmax);
+    prof_end();
+    after_launch(name);
 }
 
 // ------------------------------------------------------------- byte histogram

@@ -27,7 +27,8 @@
     X(GRLBWT_A2A_SELF_VIA_COMM, a2a_self_via_comm, bool, false, "a rank's own all-to-all block goes through the callback too")    \
     X(GRLBWT_RUN_KEYS_MIN, run_keys_min, uint64_t, 512, "phrase length from which the suffix sort takes run-aware keys")         \
     X(GRLBWT_DOUBLING_AFTER, doubling_after, uint64_t, 24, "refinement rounds of a long-phrase level before doubling rounds")     \
-    X(GRLBWT_SEG_CAP, seg_cap, int, 64, "largest suffix group ordered by counting (kSegCap); larger ones by two radix sorts")    \
+    X(GRLBWT_SEG_CAP, seg_cap, int, 64, "largest suffix group ordered by counting (kSegCap); larger ones in LDS or by two radix sorts") \
+    X(GRLBWT_SEG_LDS_CAP, seg_lds_cap, int, 4096, "largest suffix group ordered in LDS (above: two radix sorts; 0: no LDS tier)") \
     X(GRLBWT_CELL_LAYOUT, cell_layout, char, 0, "p[acked] | s[eparate]: a wider induction cell layout than the input needs")     \
     X(GRLBWT_NO_CELL32, no_cell32, bool, false, "induction cells of one word in 64 bits even where 32 would do")               \
     X(GRLBWT_ASM_TWO_PASS, asm_two_pass, bool, false, "pass C always as count + emit (no one-walk form)")                       \
