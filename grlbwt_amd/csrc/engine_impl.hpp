@@ -3275,322 +3275,299 @@ class Engine {
         }
     };
 
-    // phrase hashing launch: one lane per text position, counts pre-aggregated in LDS when few phrases dominate
-    // (a tiled variant -- 64 positions per lane, text staged in LDS, per-tile de-duplication of <= 7-byte phrases --
-    // was built and measured at 1.9-3.2 ms vs 2.2 ms for this form on 101 MB of reads, and dropped)
-    template <class cell_t, bool FIRST>
-    void launch_hash(HashInsertFn<cell_t, FIRST> f, idx_t *counts, u64 cs, u64 n, bool aggregate) {
-        prim::for_each_agg(n, f, SlotCountAdd{counts, cs}, aggregate, "hash_phrases");
+    // ---- the phrase naming stage (a2-a5 on THIS text) ------------------------------------------------------------------
+    // hash_local() at the end is the list of steps; NameStage holds what the steps share, the plans and the steps, in the order
+    // they are called.  A plan is filled once, by the step named beside it, and only read afterwards.
+    // PartPlan (plan_partitions) -- partitioned naming (levels above 0): a phrase of <= rec_cmax cells is a 128-bit record; the
+    // records are grouped by a hash prefix into partitions that fit an LDS table (prim::RecSort), de-duplicated and counted there
+    // (prim::rec_dedupe), and the phrases' values travel back through the sort's passes in reverse (emit_local).  Only the
+    // longer phrases (1 % at level 1, ~12 % at levels 2-3 of the 10 GB build) still go through the hash table.
+    // Round 2's table took 3 random HBM accesses per occurrence (probe, verification, count atomic: 51 / 51 / 18 G/s) and the
+    // emission a fourth; this path streams.
+    struct PartPlan { bool on = false; int rec_b = 0; u32 rec_cmax = 0; int part_bits = 0; };
+    // SamplePlan (sample_table) -- the sample (blocks of blk cells, stride apart, n cells in all; n = 0: the text is too small for
+    // one), its distinct phrases and their fraction of its occurrences, and (partitioned naming) its occurrences too long for a record
+    struct SamplePlan { u64 blk = 0, stride = 0, n = 0, distinct = 0, long_occ = 0; double frac = 1.0; };
+    // TablePlan (plan_table; cap_max and the first cap are sample_table's, and cap grows in hash_local when a pass overflows) --
+    // slots [0, cap_hot) in front of the table are the hot table or the direct index; ks / cs: the strides of the interleaved layout
+    struct TablePlan { u64 cap = 0, cap_max = 0, cap_hot = 0; bool aggregate = false, interleaved = false, direct = false; int ks = 0; u64 cs = 1; u32 dir_b[3] = {0, 0, 0}; u64 sym_of_code = 0; };
+    // The three cell bits of the direct index (host arithmetic, no device call): sym_present has one bit per byte value of the
+    // text.  With at most 8 values that three of their bits tell apart: true, bits[] = the first such triple (ascending),
+    // byte k of sym_of_code = the value whose code is k.
+    static bool direct_index_bits(const u64 sym_present[4], u32 bits[3], u64 &sym_of_code) {
+        int syms[256], ns = 0;
+        for (int i = 0; i < 256; i++) if ((sym_present[i >> 6] >> (i & 63)) & 1ull) syms[ns++] = i;
+        if (ns > 8) return false;
+        for (u32 a = 0; a < 8; a++) for (u32 b = a + 1; b < 8; b++) for (u32 c = b + 1; c < 8; c++) {
+            u32 seen = 0; bool ok = true; u64 soc = 0;
+            for (int k = 0; k < ns && ok; k++) {
+                const u32 code = ((syms[k] >> a) & 1u) | (((syms[k] >> b) & 1u) << 1) | (((syms[k] >> c) & 1u) << 2);
+                if (seen & (1u << code)) ok = false;
+                seen |= 1u << code;
+                soc |= (u64)syms[k] << (8 * code);
+            }
+            if (ok) { bits[0] = a; bits[1] = b; bits[2] = c; sym_of_code = soc; return true; }
+        }
+        return false;
     }
-
     template <class cell_t, bool FIRST>
-    void hash_local(const cell_t *t, u64 n, CellOps<cell_t, FIRST> ops, LocalParse &P, LevelData &L, bool allow_part = false) {
-        const u64 nwords = (n + 63) / 64;
-        DBuf<u64> startbits(nwords + 1);
-        DBuf<idx_t> wordbase(nwords + 1);
-        u64 n_occ;
-        {
-            StageTimer st(&tm.classify, "classify");
-            prim::start_bitvector(n, t, ops, StartPred<cell_t, FIRST>{t, ops}, startbits.p, "lms_breaks");
-            n_occ = (u64)prim::exclusive_scan<idx_t>(nwords, PopcIn{startbits.p}, wordbase.p, true, "phrase_ordinals");
+    struct NameStage {
+        typedef HashInsertFn<cell_t, FIRST> HF;
+        Engine &E; const cell_t *const t; const u64 n; const CellOps<cell_t, FIRST> ops; LocalParse &P; LevelData &L;
+        const u64 nwords, giant_cap;              // (giant_cap: a listed phrase has more than kLongWalk cells of its own)
+        u64 n_occ = 0;
+        PartPlan part; SamplePlan smp; TablePlan tab;
+        // (declared in the order the function's locals had before the stage was split into steps: the end of the stage releases
+        // them in the reverse order.  Dead earlier, and releasable there as a change of its own: scal and giant_list after the last
+        // hash_pass(), startbits after compact_dictionary()'s "table_compact" launches.)
+        DBuf<u64> startbits; DBuf<idx_t> wordbase;
+        DBuf<u32> scal;                           // [1] error flag, [2..3] debug, [4] giant phrases listed
+        DBuf<u64> giant_list, keys, rep_pos;
+        DBuf<u64> claim;                          // bit p: the phrase occurrence starting at p created its table entry
+        DBuf<idx_t> counts; idx_t *cnt = nullptr; // (cnt: the counts of the current table -- counts.p, or the second half of keys' slots)
+        DBuf<u64> rec_k, rec_hi;
+        u64 Ds = 0; DBuf<u32> dcnt; DBuf<u64> dkey, dhi;      // the partitions' distinct records (staging: partition p's at pstart[p] ..)
+        NameStage(Engine &e, const cell_t *t_, u64 n_, CellOps<cell_t, FIRST> ops_, LocalParse &p, LevelData &l) : E(e), t(t_), n(n_), ops(ops_), P(p), L(l),
+            nwords((n_ + 63) / 64), giant_cap(n_ / HF::kLongWalk + 2), startbits(nwords + 1), wordbase(nwords + 1) {}
+        // a2: phrase starts and the ordinal of every phrase occurrence
+        void classify() {
+            {
+                StageTimer st(&E.tm.classify, "classify");
+                prim::start_bitvector(n, t, ops, StartPred<cell_t, FIRST>{t, ops}, startbits.p, "lms_breaks");
+                n_occ = (u64)prim::exclusive_scan<idx_t>(nwords, PopcIn{startbits.p}, wordbase.p, true, "phrase_ordinals");
+            }
+            P.n_occ = L.info.parse_size = n_occ;
+            // (phrase ordinals are idx_t: the 64-bit build takes parses of 2^32 phrases and more -- level 0 of a 24.9 GB collection has
+            // 7.3 G; what stays 32 bits wide are slot ids, dictionary positions and a shard's frequencies on the wire: checked where they are made)
+            if (sizeof(idx_t) == 4 && n_occ >= 0xFFFFFFF0ull) throw prim::Error(-75, "parse too large for u32 phrase ordinals");
         }
-        P.n_occ = n_occ;
-        L.info.parse_size = n_occ;
-        // (phrase ordinals are idx_t: the 64-bit build takes parses of 2^32 phrases and more -- level 0 of a 24.9 GB collection has
-        // 7.3 G; what stays 32 bits wide are slot ids, dictionary positions and a shard's frequencies on the wire: checked where they are made)
-        if (sizeof(idx_t) == 4 && n_occ >= 0xFFFFFFF0ull) throw prim::Error(-75, "parse too large for u32 phrase ordinals");
-
-        // ---- partitioned naming (levels above 0, single-GPU rounds): a phrase of <= cmax cells is a 128-bit record; the records
-        // are grouped by a hash prefix into partitions that fit an LDS table (prim::RecSort), de-duplicated and counted there
-        // (prim::rec_dedupe), and the phrases' values travel back through the sort's passes in reverse (emit_local).  Only the
-        // longer phrases (1 % at level 1, ~12 % at levels 2-3 of the 10 GB build) still go through the hash table below.
-        // Round 2's table took 3 random HBM accesses per occurrence (probe, verification, count atomic: 51 / 51 / 18 G/s) and the
-        // emission a fourth; this path streams.  GRLBWT_PART_MIN_OCC sets the smallest level (GRLBWT_NO_PART=1, development builds: no partitions).
-        int rec_b = 0;
-        u32 rec_cmax = 0;
-        bool part = false;
-        if (allow_part && !FIRST && sizeof(cell_t) == 4 && !prim::sw().no_part) {
-            rec_b = (int)bitlen64(L.sigma > 1 ? (u64)L.sigma - 1 : 1);
-            rec_cmax = (u32)std::min<int>(7, 124 / rec_b);
-            part = rec_cmax >= 2 && n_occ >= prim::sw().part_min_occ;
-            if (!part) rec_cmax = 0;
-        }
-        int part_bits = 0;
-        if (part) {
+        // Partitioned naming or not (see PartPlan).  GRLBWT_PART_MIN_OCC (product tier) sets the smallest level that takes it;
+        // GRLBWT_NO_PART (dev tier) takes it from every level.
+        void plan_partitions(bool allow_part) {
+            if (!(allow_part && !FIRST && sizeof(cell_t) == 4 && !prim::sw().no_part)) return;
+            part.rec_b = (int)bitlen64(L.sigma > 1 ? (u64)L.sigma - 1 : 1);
+            part.rec_cmax = (u32)std::min<int>(7, 124 / part.rec_b);
+            part.on = part.rec_cmax >= 2 && n_occ >= prim::sw().part_min_occ;
+            if (!part.on) { part.rec_cmax = 0; return; }
             // partitions of at most ~5000 records: even a level whose phrases are ALL distinct fits the LDS tables (8192 entries)
-            part_bits = 4;
-            while (part_bits < 20 && (n_occ >> part_bits) > 5000) part_bits++;
-            // (GRLBWT_PART_BITS: the tests make partitions too large for their table, to take the fallback on the device)
-            if (prim::sw().part_bits) part_bits = std::max(1, std::min(20, prim::sw().part_bits));
+            part.part_bits = 4;
+            while (part.part_bits < 20 && (n_occ >> part.part_bits) > 5000) part.part_bits++;
+            // (GRLBWT_PART_BITS, product tier: the tests make partitions too large for their table, to take the fallback on the device)
+            if (prim::sw().part_bits) part.part_bits = std::max(1, std::min(20, prim::sw().part_bits));
         }
-
-        // ---- a3: hash every phrase occurrence ------------------------------
-        // table capacity: the number of distinct phrases is unknown and usually << the number of
-        // occurrences (20 k vs 30 M at level 0 of DNA reads): estimate the distinct fraction on a prefix,
-        // size the table for load <= ~0.6, and grow x4 (re-running the pass) if a lane runs out of
-        // probes because the prefix was not representative; cap_max = 2*n_occ always fits.
-        u64 cap_max = 1024;
-        while (cap_max < 2 * n_occ && cap_max < (1ull << 31)) cap_max <<= 1;      // slot ids are u32 with bit 31 spare (prim::kClaimBit)
-        P.next_text.alloc(n_occ);
-        DBuf<u32> scal(8);                        // [1] error flag, [2..3] debug, [4] giant phrases listed
-        const u64 giant_cap = n / HashInsertFn<cell_t, FIRST>::kLongWalk + 2;      // (a listed phrase has more than kLongWalk cells of its own)
-        DBuf<u64> giant_list(giant_cap);
-        u64 cap = cap_max;
-        double frac = 1.0;
-        u64 s_blk = 0, s_stride = 0, s_n = 0, s_distinct = 0;      // the sample (blocks of s_blk cells, s_stride apart) and its distinct phrases
-        u64 s_long = 0;                                             // partitioned naming: phrase occurrences of the sample that are too long for a record
-        {
+        // a3, table capacity: the number of distinct phrases is unknown and usually << the number of occurrences (20 k vs 30 M at level 0 of
+        // DNA reads): estimate the distinct fraction on a sample, size the table for load <= ~0.6, and grow x4 (re-running the pass) if a
+        // lane runs out of probes because the sample was not representative; cap_max = 2*n_occ always fits.
+        void sample_table() {
+            tab.cap_max = 1024;
+            while (tab.cap_max < 2 * n_occ && tab.cap_max < (1ull << 31)) tab.cap_max <<= 1;      // slot ids are u32 with bit 31 spare (prim::kClaimBit)
+            tab.cap = tab.cap_max;
+            P.next_text.alloc(n_occ); scal.alloc(8); giant_list.alloc(giant_cap);
             // Table capacity from a sample of 2^20 cells (256 blocks spread evenly over the text) hashed into a table of its
             // own: its distinct fraction `frac`, extrapolated to the whole text.  That over-sizes the table whenever repetition
             // is global rather than local (level 1 of the 10 GB build: 964 M occurrences of 101 M phrases, 90 % distinct within
             // any 2^20 cells -> 2^31 slots), and measured that is the better side to err on: the pass runs FASTER on the sparse
             // table (75 ms at 2^31 slots, 83 ms at 2^28: fewer probes), zeroing it costs what that gains, and the compaction
-            // afterwards does not scan the table (claim bits, below).  Estimating the number of distinct phrases from the
+            // afterwards does not scan the table (claim bits).  Estimating the number of distinct phrases from the
             // sample's abundance classes (Chao1) was tried and is 10-20x too low on this data (heterogeneous abundances):
             // two overflow re-runs per level.  An exact count (one more hashing pass over a 1/64 slice of the hash space)
             // costs about what a right-sized table saves.
-            StageTimer st(&tm.hash, "hash");
-            // (first level of a large text: 2^22 cells, so that the sample's phrases -- the hot table below -- cover the occurrences well)
-            const u64 want_s = (FIRST && n >= (1ull << 26)) ? (1ull << 22) : (1ull << 20);
-            const u64 n_s = n < want_s ? n : want_s;
-            if (n_s < n) {
-                const u64 blk = 4096, nblk = n_s / blk, stride = n / nblk;
-                s_blk = blk; s_stride = stride; s_n = n_s;
-                u64 cap_s = 1024;
-                while (cap_s < 2 * n_s) cap_s <<= 1;
-                DBuf<u64> tk(cap_s), trep;
-                DBuf<idx_t> tc(cap_s);
-                if (HashInsertFn<cell_t, FIRST>::kExact) trep.alloc(cap_s);
-                tk.zero(); tc.zero(); scal.zero();
-                typedef HashInsertFn<cell_t, FIRST> HF;
-                HF fs{t, ops, startbits.p, wordbase.p, tk.p, cap_s - 1, cap_s, 0, P.next_text.p, scal.p, n, n_occ, trep.p};
-                fs.rec_b = rec_b; fs.rec_cmax = rec_cmax;       // (partitioned naming: only the long phrases reach the sample's table)
-                fs.walk_cap = HF::kLongWalk;        // (the sample leaves the long phrases out: they are listed and hashed by waves in the real pass)
-                prim::for_each_agg(n_s, SampledFn<HF>{fs, blk, stride}, SlotCountAdd{tc.p, 1}, true, "hash_sample");
-                const prim::Pair<u64, u64> so = prim::reduce_sum<prim::Pair<u64, u64>>(cap_s, SampleCountIn{tk.p, tc.p}, "hash_sample_count");      // (one reduction: one synchronisation)
-                const u64 d_s = so.a;
-                const u64 occ_s = std::max<u64>(so.b, 1);
-                if (part) s_long = occ_s;
-                frac = (double)d_s / (double)occ_s;
-                if (frac > 1.0) frac = 1.0;
-                s_distinct = d_s;
-                u64 want = (u64)(1.7 * frac * (double)n_occ) + 4096;            // target load <= ~0.6 if the sample is representative
-                if (part) want = (u64)(3.0 * (double)s_long * ((double)n / (double)n_s)) + 4096;   // the table only sees the long phrases: room for all of them being distinct
-                cap = 4096;
-                while (cap < want) cap <<= 1;
-                if (cap > cap_max) cap = cap_max;
-                if (prim::sw().table_trace) fprintf(stderr, "[grlbwt] level %d: sample %llu occurrences, %llu distinct -> table %llu slots for %llu occurrences\n",
-                                                          prim::rt().tag, (unsigned long long)occ_s, (unsigned long long)d_s, (unsigned long long)cap, (unsigned long long)n_occ);
-            }
+            StageTimer st(&E.tm.hash, "hash");
+            // (first level of a large text: 2^22 cells, so that the sample's phrases -- the hot table -- cover the occurrences well)
+            const u64 want_s = (FIRST && n >= (1ull << 26)) ? (1ull << 22) : (1ull << 20), n_s = n < want_s ? n : want_s;
+            if (n_s >= n) return;
+            smp.blk = 4096; smp.stride = n / (n_s / smp.blk); smp.n = n_s;
+            u64 cap_s = 1024; while (cap_s < 2 * n_s) cap_s <<= 1;
+            DBuf<u64> tk(cap_s), trep; DBuf<idx_t> tc(cap_s);
+            if (HF::kExact) trep.alloc(cap_s);
+            tk.zero(); tc.zero(); scal.zero();
+            HF fs{t, ops, startbits.p, wordbase.p, tk.p, cap_s - 1, cap_s, 0, P.next_text.p, scal.p, n, n_occ, trep.p};
+            fs.rec_b = part.rec_b; fs.rec_cmax = part.rec_cmax;       // (partitioned naming: only the long phrases reach the sample's table)
+            fs.walk_cap = HF::kLongWalk;        // (the sample leaves the long phrases out: they are listed and hashed by waves in the real pass)
+            prim::for_each_agg(n_s, SampledFn<HF>{fs, smp.blk, smp.stride}, SlotCountAdd{tc.p, 1}, true, "hash_sample");
+            const prim::Pair<u64, u64> so = prim::reduce_sum<prim::Pair<u64, u64>>(cap_s, SampleCountIn{tk.p, tc.p}, "hash_sample_count");      // (one reduction: one synchronisation)
+            const u64 occ_s = std::max<u64>(so.b, 1);
+            smp.distinct = so.a;
+            if (part.on) smp.long_occ = occ_s;
+            smp.frac = std::min(1.0, (double)smp.distinct / (double)occ_s);
+            u64 want = (u64)(1.7 * smp.frac * (double)n_occ) + 4096;            // target load <= ~0.6 if the sample is representative
+            if (part.on) want = (u64)(3.0 * (double)smp.long_occ * ((double)n / (double)n_s)) + 4096;   // the table only sees the long phrases: room for all of them being distinct
+            tab.cap = 4096; while (tab.cap < want) tab.cap <<= 1;
+            if (tab.cap > tab.cap_max) tab.cap = tab.cap_max;
+            if (prim::sw().table_trace) fprintf(stderr, "[grlbwt] level %d: sample %llu occurrences, %llu distinct -> table %llu slots for %llu occurrences\n",
+                                                      prim::rt().tag, (unsigned long long)occ_s, (unsigned long long)smp.distinct, (unsigned long long)tab.cap, (unsigned long long)n_occ);
         }
-        DBuf<u64> keys, rep_pos;
-        DBuf<u64> claim(nwords + 1);             // bit p: the phrase occurrence starting at p created its table entry
-        DBuf<idx_t> counts;
-        // LDS pre-aggregation of the counts pays when few distinct phrases take most occurrences (level 0 of
-        // DNA: 20 k phrases, 30 M occurrences); with mostly-distinct phrases the cache only thrashes.
-        // (GRLBWT_FORCE_DIRECT_INDEX=1: the tests take the direct index -- below -- on texts too small for a sample)
-        const bool force_direct = HashInsertFn<cell_t, FIRST>::kExact && !part && prim::sw().force_direct_index;
-        const bool aggregate = frac < 0.25 || force_direct;
-        // Table layout.  With few hot phrases the keys stay on lines of their own (the atomics on a hot count would keep
-        // invalidating the key every probe reads: measured 4x slower interleaved).  With mostly-distinct phrases every
-        // occurrence fetches a random key AND a random count: 16-byte (key, count) slots make that one line.
-        const bool interleaved = !aggregate;      // (10 GB build: 0.6 % faster than separate arrays on the same box)
-        const int ks = interleaved ? 1 : 0;
-        const u64 cs = interleaved ? 16 / sizeof(idx_t) : 1;
-        const idx_t *counts_p = nullptr;
-        // Hot table (HashInsertFn::hot_keys): when few phrases dominate, the phrases of the sample get a small dense table of
-        // their own in front of the big one -- slots [0, cap_hot) -- filled by hashing the sample once more (claims on: they
-        // are dictionary phrases like the others) and read-only in the pass over the text.  GRLBWT_NO_HOT_TABLE=1 switches it off.
-        u64 cap_hot = 0;
-        DBuf<u64> rec_k, rec_hi;
-        if (part) { rec_k.alloc(n_occ); rec_hi.alloc(n_occ); }
-        // Direct index instead (HashInsertFn::direct_index): byte texts with at most 8 distinct cell values, told apart by three of
-        // their bits.  GRLBWT_NO_DIRECT_INDEX=1 keeps the hot table.
-        bool direct = false;
-        u32 dir_b[3] = {0, 0, 0};
-        u64 sym_of_code = 0;
-        if (HashInsertFn<cell_t, FIRST>::kExact && aggregate && (s_n || force_direct) && !part && sym_present_known && !prim::sw().no_direct_index) {
-            int syms[256], ns = 0;
-            for (int i = 0; i < 256; i++) if ((sym_present[i >> 6] >> (i & 63)) & 1ull) syms[ns++] = i;
-            for (u32 a = 0; a < 8 && !direct && ns <= 8; a++) for (u32 b = a + 1; b < 8 && !direct; b++) for (u32 c = b + 1; c < 8 && !direct; c++) {
-                u32 seen = 0; bool ok = true; u64 soc = 0;
-                for (int k = 0; k < ns && ok; k++) {
-                    const u32 code = ((syms[k] >> a) & 1u) | (((syms[k] >> b) & 1u) << 1) | (((syms[k] >> c) & 1u) << 2);
-                    if (seen & (1u << code)) ok = false;
-                    seen |= 1u << code;
-                    soc |= (u64)syms[k] << (8 * code);
+        // The layout of the table and what stands in front of it: the direct index, the hot table or nothing.
+        void plan_table() {
+            // (the buffers of the pass that outlive it are allocated here, ahead of the "hash_prepare" reduction, as before the stage was split)
+            claim.alloc(nwords + 1);
+            if (part.on) { rec_k.alloc(n_occ); rec_hi.alloc(n_occ); }
+            // LDS pre-aggregation of the counts pays when few distinct phrases take most occurrences (level 0 of
+            // DNA: 20 k phrases, 30 M occurrences); with mostly-distinct phrases the cache only thrashes.
+            // (GRLBWT_FORCE_DIRECT_INDEX, product tier: the tests take the direct index on texts too small for a sample)
+            const bool force_direct = HF::kExact && !part.on && prim::sw().force_direct_index;
+            tab.aggregate = smp.frac < 0.25 || force_direct;
+            // With few hot phrases the keys stay on lines of their own (the atomics on a hot count would keep
+            // invalidating the key every probe reads: measured 4x slower interleaved).  With mostly-distinct phrases every
+            // occurrence fetches a random key AND a random count: 16-byte (key, count) slots make that one line.
+            tab.interleaved = !tab.aggregate;      // (10 GB build: 0.6 % faster than separate arrays on the same box)
+            tab.ks = tab.interleaved ? 1 : 0; tab.cs = tab.interleaved ? 16 / sizeof(idx_t) : 1;
+            // Direct index (HashInsertFn::direct_index): byte texts with at most 8 distinct cell values, told apart by three of their
+            // bits.  GRLBWT_NO_DIRECT_INDEX (test tier: a constant in the device library) takes the hot table instead.
+            if (HF::kExact && tab.aggregate && (smp.n || force_direct) && !part.on && E.sym_present_known && !prim::sw().no_direct_index)
+                tab.direct = direct_index_bits(E.sym_present, tab.dir_b, tab.sym_of_code);
+            if (tab.direct && (const void *)t == E.text0 && E.text0 != (const void *)E.own0.p) {      // (level 0 of a text the caller lent)
+                // The direct index trusts the set of cell values the statistics found: a value outside it would take another symbol's
+                // code and two phrases one slot.  The engine's own copies cannot change; a buffer the caller lent (grlbwt_text_attach_device)
+                // must not -- a strided sample of it is looked at again here (the whole text would cost another 4 ms per 10 GB).
+                if constexpr (sizeof(cell_t) == 1) {
+                    const u64 stride = n >= (1ull << 22) ? n >> 20 : 1, m = n / stride;
+                    const u64 foreign = prim::reduce_sum<u64>(m, ForeignByteIn{(const u8 *)t, stride, E.sym_present[0], E.sym_present[1], E.sym_present[2], E.sym_present[3]}, "hash_prepare");
+                    if (foreign) throw prim::Error(-22, "the attached text has changed since its statistics were taken (a cell value that was not there)");
                 }
-                if (ok) { direct = true; dir_b[0] = a; dir_b[1] = b; dir_b[2] = c; sym_of_code = soc; }
             }
+            // Hot table (HashInsertFn::hot_keys): when few phrases dominate, the phrases of the sample get a small dense table of
+            // their own in front of the big one, filled by hashing the sample once more (fill_hot_table) and read-only in the pass
+            // over the text.  GRLBWT_NO_HOT_TABLE (test tier: a constant in the device library) leaves it out.
+            const bool hot = !tab.direct && tab.aggregate && smp.n && !part.on && !prim::sw().no_hot_table;
+            if (!tab.direct && !hot) return;
+            if (tab.direct) tab.cap_hot = HF::kDirectSlots;
+            else for (tab.cap_hot = 1024; tab.cap_hot < 4 * smp.distinct;) tab.cap_hot <<= 1;      // load <= 0.25: short probe chains
+            if (tab.cap_max > (1ull << 30)) tab.cap_max = 1ull << 30;             // slot ids of both regions stay below 2^31
+            if (tab.cap > tab.cap_max) tab.cap = tab.cap_max;
+            if (!prim::sw().table_trace) return;
+            if (tab.direct) fprintf(stderr, "[grlbwt] level %d: direct index on bits %u, %u, %u of a cell (%llu slots in front of the table)\n", prim::rt().tag,
+                                    tab.dir_b[0], tab.dir_b[1], tab.dir_b[2], (unsigned long long)tab.cap_hot);
+            else fprintf(stderr, "[grlbwt] level %d: hot table of %llu slots for the %llu phrases of the sample\n", prim::rt().tag,
+                         (unsigned long long)tab.cap_hot, (unsigned long long)smp.distinct);
         }
-        if (direct && (const void *)t == text0 && text0 != (const void *)own0.p) {      // (level 0 of a text the caller lent)
-            // The direct index trusts the set of cell values the statistics found: a value outside it would take another symbol's
-            // code and two phrases one slot.  The engine's own copies cannot change; a buffer the caller lent (grlbwt_text_attach_device)
-            // must not -- a strided sample of it is looked at again here (the whole text would cost another 4 ms per 10 GB).
-            if constexpr (sizeof(cell_t) == 1) {
-                const u64 stride = n >= (1ull << 22) ? n >> 20 : 1, m = n / stride;
-                const u64 foreign = prim::reduce_sum<u64>(m, ForeignByteIn{(const u8 *)t, stride, sym_present[0], sym_present[1], sym_present[2], sym_present[3]}, "hash_prepare");
-                if (foreign) throw prim::Error(-22, "the attached text has changed since its statistics were taken (a cell value that was not there)");
-            }
+        // -- the pieces of one hashing pass --
+        void alloc_table() {
+            if (tab.interleaved) { keys.alloc(2 * tab.cap); keys.zero(); }
+            else { keys.alloc(tab.cap_hot + tab.cap); counts.alloc(tab.cap_hot + tab.cap); keys.zero(); counts.zero(); }
+            cnt = tab.interleaved ? (idx_t *)(keys.p + 1) : counts.p;      // (interleaved: the count lives in the second half of the slot)
+            if (HF::kExact) rep_pos.alloc(tab.cap_hot + tab.cap);                      // (written by the lanes that claim a slot)
+            scal.zero(); claim.zero();
         }
-        if (direct) {
-            cap_hot = HashInsertFn<cell_t, FIRST>::kDirectSlots;
-            if (cap_max > (1ull << 30)) cap_max = 1ull << 30;             // slot ids of both regions stay below 2^31
-            if (cap > cap_max) cap = cap_max;
-            if (prim::sw().table_trace) fprintf(stderr, "[grlbwt] level %d: direct index on bits %u, %u, %u of a cell (%llu slots in front of the table)\n", prim::rt().tag,
-                                                      dir_b[0], dir_b[1], dir_b[2], (unsigned long long)cap_hot);
-        } else
-        if (aggregate && s_n && !part && !prim::sw().no_hot_table) {
-            cap_hot = 1024;
-            while (cap_hot < 4 * s_distinct) cap_hot <<= 1;               // load <= 0.25: short probe chains
-            if (cap_max > (1ull << 30)) cap_max = 1ull << 30;             // slot ids of both tables stay below 2^31
-            if (cap > cap_max) cap = cap_max;
-            if (prim::sw().table_trace) fprintf(stderr, "[grlbwt] level %d: hot table of %llu slots for the %llu phrases of the sample\n", prim::rt().tag,
-                                                      (unsigned long long)cap_hot, (unsigned long long)s_distinct);
+        // the sample hashed once more, into slots [0, cap_hot) (claims on: they are dictionary phrases like the others); f reads them
+        void fill_hot_table(HF &f) {
+            HF fh{t, ops, startbits.p, wordbase.p, keys.p, tab.cap_hot - 1, tab.cap_hot, 0, P.next_text.p, scal.p, n, n_occ, rep_pos.p, claim.p};
+            fh.walk_cap = HF::kLongWalk;            // (a phrase of thousands of cells has no business in the hot table: the pass over the text
+                                                    // would find it there and compare it cell by cell with itself)
+            prim::for_each_agg(smp.n, SampledFn<HF>{fh, smp.blk, smp.stride, claim.p}, NoCountAdd{}, false, "hash_hot");
+            f.hot_keys = keys.p; f.hot_mask = tab.cap_hot - 1; f.slot_base = (u32)tab.cap_hot;
         }
-        {
-            StageTimer st(&tm.hash, "hash");
-            typedef HashInsertFn<cell_t, FIRST> HF;
-            for (;;) {
-                idx_t *cnt;
-                if (interleaved) {
-                    keys.alloc(2 * cap); keys.zero();
-                    cnt = (idx_t *)(keys.p + 1);          // the count lives in the second half of the slot
-                } else {
-                    keys.alloc(cap_hot + cap); counts.alloc(cap_hot + cap);
-                    keys.zero(); counts.zero();
-                    cnt = counts.p;
-                }
-                counts_p = cnt;
-                if (HF::kExact) rep_pos.alloc(cap_hot + cap);                          // (written by the lanes that claim a slot)
-                scal.zero();
-                claim.zero();
-                u64 probe_limit = (cap == cap_max) ? cap : 96;
-                HF f{t, ops, startbits.p, wordbase.p, keys.p + cap_hot, cap - 1, probe_limit, ks,
-                     P.next_text.p, scal.p, n, n_occ, rep_pos.p ? rep_pos.p + cap_hot : nullptr, claim.p};
-                if (part) { f.rec_k = rec_k.p; f.rec_hi = rec_hi.p; f.rec_b = rec_b; f.rec_cmax = rec_cmax; }
-                f.giant_list = giant_list.p; f.giant_n = scal.p + 4; f.giant_cap = (u32)std::min<u64>(giant_cap, 0xFFFFFFFFull);
-                if (direct) { f.dir_on = 1; f.dir_b0 = dir_b[0]; f.dir_b1 = dir_b[1]; f.dir_b2 = dir_b[2]; f.dir_rep = rep_pos.p; f.slot_base = (u32)cap_hot; }
-                else if (cap_hot) {
-                    HF fh{t, ops, startbits.p, wordbase.p, keys.p, cap_hot - 1, cap_hot, 0, P.next_text.p, scal.p, n, n_occ, rep_pos.p, claim.p};
-                    fh.walk_cap = HF::kLongWalk;            // (a phrase of thousands of cells has no business in the hot table: the pass over the text
-                                                            // would find it there and compare it cell by cell with itself)
-                    prim::for_each_agg(s_n, SampledFn<HF>{fh, s_blk, s_stride, claim.p}, NoCountAdd{}, false, "hash_hot");
-                    f.hot_keys = keys.p; f.hot_mask = cap_hot - 1; f.slot_base = (u32)cap_hot;
-                }
-                if constexpr (!FIRST) {
-                    if (part && !prim::sw().part_one_pass) {
-                        // the records by a lean streaming pass of their own, the long phrases from a list through the table
-                        prim::dev_memset(P.next_text.p, 0, n_occ * sizeof(u32));
-                        DBuf<u64> lbits(nwords + 1);
-                        lbits.zero();
-                        auto records = [&](auto bw) {
-                            prim::for_each_set_bit<idx_t>(n, startbits.p, wordbase.p, PhraseRecordFn<cell_t, decltype(bw)::value>{t, ops, startbits.p, wordbase.p, n, n_occ,
-                                                                                                                           rec_k.p, rec_hi.p, rec_b, rec_cmax, lbits.p, scal.p}, "hash_phrases");
-                        };
-                        switch (rec_b) {
+        // the phrase occurrences a kernel of its own marked in lbits instead of naming them: listed, and through the general code
+        void hash_listed(const HF &f, DBuf<u64> &lbits, bool aggregate) {
+            DBuf<u32> lbase(nwords + 1);
+            const u64 nl = (u64)prim::exclusive_scan<u32>(nwords, PopcIn32{lbits.p}, lbase.p, false, "hash_long_list");
+            DBuf<u64> lpos(nl ? nl : 1);
+            if (nl) prim::for_each(nwords, BitPositionsFn{lbits.p, lbase.p, lpos.p}, "hash_long_list");
+            lbits.release(); lbase.release();
+            if (nl) prim::for_each_agg(nl, ListedFn<HF>{f, lpos.p, claim.p}, SlotCountAdd{cnt, tab.cs}, aggregate, "hash_long_phrases");
+        }
+        // partitioned naming: the records by a lean streaming pass of their own, the long phrases from a list through the table
+        // (GRLBWT_PART_ONE_PASS, product tier: both by the general pass instead)
+        void records_and_long_phrases(const HF &f) {
+            prim::dev_memset(P.next_text.p, 0, n_occ * sizeof(u32));
+            DBuf<u64> lbits(nwords + 1); lbits.zero();
+            auto records = [&](auto bw) {
+                prim::for_each_set_bit<idx_t>(n, startbits.p, wordbase.p, PhraseRecordFn<cell_t, decltype(bw)::value>{t, ops, startbits.p, wordbase.p, n, n_occ,
+                                                                                                               rec_k.p, rec_hi.p, part.rec_b, part.rec_cmax, lbits.p, scal.p}, "hash_phrases");
+            };
+            switch (part.rec_b) {
 #define GRL_REC_CASE(BW) case BW: records(std::integral_constant<int, BW>()); break;
-                            GRL_REC_CASE(10) GRL_REC_CASE(11) GRL_REC_CASE(12) GRL_REC_CASE(13) GRL_REC_CASE(14) GRL_REC_CASE(15) GRL_REC_CASE(16)
-                            GRL_REC_CASE(17) GRL_REC_CASE(18) GRL_REC_CASE(19) GRL_REC_CASE(20) GRL_REC_CASE(21) GRL_REC_CASE(22) GRL_REC_CASE(23)
-                            GRL_REC_CASE(24) GRL_REC_CASE(25) GRL_REC_CASE(26) GRL_REC_CASE(27) GRL_REC_CASE(28) GRL_REC_CASE(29) GRL_REC_CASE(30)
+                GRL_REC_CASE(10) GRL_REC_CASE(11) GRL_REC_CASE(12) GRL_REC_CASE(13) GRL_REC_CASE(14) GRL_REC_CASE(15) GRL_REC_CASE(16)
+                GRL_REC_CASE(17) GRL_REC_CASE(18) GRL_REC_CASE(19) GRL_REC_CASE(20) GRL_REC_CASE(21) GRL_REC_CASE(22) GRL_REC_CASE(23)
+                GRL_REC_CASE(24) GRL_REC_CASE(25) GRL_REC_CASE(26) GRL_REC_CASE(27) GRL_REC_CASE(28) GRL_REC_CASE(29) GRL_REC_CASE(30)
 #undef GRL_REC_CASE
-                            default: records(std::integral_constant<int, 0>()); break;      // (narrow symbols: small levels)
-                        }
-                        DBuf<u32> lbase(nwords + 1);
-                        const u64 nl = (u64)prim::exclusive_scan<u32>(nwords, PopcIn32{lbits.p}, lbase.p, false, "hash_long_list");
-                        DBuf<u64> lpos(nl ? nl : 1);
-                        if (nl) prim::for_each(nwords, BitPositionsFn{lbits.p, lbase.p, lpos.p}, "hash_long_list");
-                        lbits.release(); lbase.release();
-                        if (nl) prim::for_each_agg(nl, ListedFn<HF>{f, lpos.p, claim.p}, SlotCountAdd{cnt, cs}, false, "hash_long_phrases");
-                    } else launch_hash<cell_t, FIRST>(f, cnt, cs, n, aggregate);
-                } else if (direct && n_occ < 0xFFFFFFF0ull && !prim::sw().no_name_stream) {
-                    // the direct index in a kernel of its own (prim::name_stream): what it cannot name -- phrases of more than 7 cells,
-                    // the last cells of the text -- is marked and takes the general code from a list afterwards
-                    DBuf<u64> lbits(nwords + 1);
-                    lbits.zero();
-                    prim::name_stream(n, f, SlotCountAdd{cnt, cs}, lbits.p, "hash_phrases");
-                    DBuf<u32> lbase(nwords + 1);
-                    const u64 nl = (u64)prim::exclusive_scan<u32>(nwords, PopcIn32{lbits.p}, lbase.p, false, "hash_long_list");
-                    DBuf<u64> lpos(nl ? nl : 1);
-                    if (nl) prim::for_each(nwords, BitPositionsFn{lbits.p, lbase.p, lpos.p}, "hash_long_list");
-                    lbits.release(); lbase.release();
-                    if (nl) prim::for_each_agg(nl, ListedFn<HF>{f, lpos.p, claim.p}, SlotCountAdd{cnt, cs}, aggregate, "hash_long_phrases");
-                } else launch_hash<cell_t, FIRST>(f, cnt, cs, n, aggregate);
-                std::vector<u32> sc = scal.to_host(8);
-                if (sc[4] && !sc[1]) {            // the phrases too long for one lane: one wave each
-                    prim::for_each_giant((u64)sc[4], giant_list.p, f, SlotCountAdd{cnt, cs}, "hash_giant_phrases");
-                    sc = scal.to_host(8);
-                }
-                if (sc[1] == 1) {
-                    if (cap == cap_max) throw prim::Error(-28, "phrase hash table overflow");
-                    cap = cap * 4 > cap_max ? cap_max : cap * 4;
-                    L.info.table_retries++;
-                    continue;
-                }
-                if (sc[1]) throw prim::Error(-71, "phrase hashing: consistency check " + std::to_string(sc[1]) + " failed (" +
-                                                       std::to_string(sc[2]) + ", " + std::to_string(sc[3]) + ")");
-                if (direct) prim::for_each(cap_hot, DirectFixFn{counts_p, keys.p, rep_pos.p, claim.p, sym_of_code}, "hash_direct_fix");
-                break;
+                default: records(std::integral_constant<int, 0>()); break;      // (narrow symbols: small levels)
             }
+            hash_listed(f, lbits, false);
         }
-        P.cap = cap_hot + cap;
-
-        // ---- partitioned naming: group the records, de-duplicate and count per partition -------------------------------
-        u64 Ds = 0;
-        DBuf<u32> dcnt;
-        DBuf<u64> dkey, dhi;                      // the partitions' distinct records (staging: partition p's at pstart[p] ..)
-        if (part) {
-            StageTimer st(&tm.hash, "hash");
+        // the direct index in a kernel of its own (prim::name_stream): what it cannot name -- phrases of more than 7 cells,
+        // the last cells of the text -- is marked and takes the general code from a list afterwards
+        // (GRLBWT_NO_NAME_STREAM, dev tier: the general pass instead)
+        void name_stream_and_long_phrases(const HF &f) {
+            DBuf<u64> lbits(nwords + 1); lbits.zero();
+            prim::name_stream(n, f, SlotCountAdd{cnt, tab.cs}, lbits.p, "hash_phrases");
+            hash_listed(f, lbits, tab.aggregate);
+        }
+        // a3: every phrase occurrence through a table of tab.cap slots -- one attempt.  False: a lane ran out of probes (the caller grows
+        // the table and comes back).  One lane per text position, counts pre-aggregated in LDS when few phrases dominate (a tiled variant
+        // -- 64 positions per lane, text staged in LDS, per-tile de-duplication of <= 7-byte phrases -- was built and measured at
+        // 1.9-3.2 ms vs 2.2 ms for this form on 101 MB of reads, and dropped)
+        bool hash_pass() {
+            alloc_table();
+            HF f{t, ops, startbits.p, wordbase.p, keys.p + tab.cap_hot, tab.cap - 1, (tab.cap == tab.cap_max) ? tab.cap : 96 /* probes */, tab.ks,
+                 P.next_text.p, scal.p, n, n_occ, rep_pos.p ? rep_pos.p + tab.cap_hot : nullptr, claim.p};
+            if (part.on) { f.rec_k = rec_k.p; f.rec_hi = rec_hi.p; f.rec_b = part.rec_b; f.rec_cmax = part.rec_cmax; }
+            f.giant_list = giant_list.p; f.giant_n = scal.p + 4; f.giant_cap = (u32)std::min<u64>(giant_cap, 0xFFFFFFFFull);
+            if (tab.direct) { f.dir_on = 1; f.dir_b0 = tab.dir_b[0]; f.dir_b1 = tab.dir_b[1]; f.dir_b2 = tab.dir_b[2]; f.dir_rep = rep_pos.p; f.slot_base = (u32)tab.cap_hot; }
+            else if (tab.cap_hot) fill_hot_table(f);
+            if constexpr (!FIRST) {
+                if (part.on && !prim::sw().part_one_pass) records_and_long_phrases(f);
+                else prim::for_each_agg(n, f, SlotCountAdd{cnt, tab.cs}, tab.aggregate, "hash_phrases");
+            } else if (tab.direct && n_occ < 0xFFFFFFF0ull && !prim::sw().no_name_stream) name_stream_and_long_phrases(f);
+            else prim::for_each_agg(n, f, SlotCountAdd{cnt, tab.cs}, tab.aggregate, "hash_phrases");
+            std::vector<u32> sc = scal.to_host(8);
+            if (sc[4] && !sc[1]) {            // the phrases too long for one lane: one wave each
+                prim::for_each_giant((u64)sc[4], giant_list.p, f, SlotCountAdd{cnt, tab.cs}, "hash_giant_phrases");
+                sc = scal.to_host(8);
+            }
+            if (sc[1] == 1) return false;
+            if (sc[1]) throw prim::Error(-71, "phrase hashing: consistency check " + std::to_string(sc[1]) + " failed (" +
+                                                   std::to_string(sc[2]) + ", " + std::to_string(sc[3]) + ")");
+            if (tab.direct) prim::for_each(tab.cap_hot, DirectFixFn{cnt, keys.p, rep_pos.p, claim.p, tab.sym_of_code}, "hash_direct_fix");
+            P.cap = tab.cap_hot + tab.cap;
+            return true;
+        }
+        // partitioned naming: group the records, de-duplicate and count per partition.  False: a partition has more distinct phrases
+        // than its LDS table takes (or the tests injected a limit) -- this level goes through the hash table after all.
+        bool dedupe_partitions() {
+            StageTimer st(&E.tm.hash, "hash");
             DBuf<u64> rec_k2(n_occ), rec_hi2(n_occ);
-            const int res = P.psort.forward(rec_k.p, rec_hi.p, rec_k2.p, rec_hi2.p, n_occ, part_bits, "phrase_part");
+            const int res = P.psort.forward(rec_k.p, rec_hi.p, rec_k2.p, rec_hi2.p, n_occ, part.part_bits, "phrase_part");
             DBuf<u64> skey, shi;
             if (res) { skey = std::move(rec_k2); shi = std::move(rec_hi2); dkey = std::move(rec_k); dhi = std::move(rec_hi); }
             else { skey = std::move(rec_k); shi = std::move(rec_hi); dkey = std::move(rec_k2); dhi = std::move(rec_hi2); }
-            const u64 nparts = (u64)1 << part_bits;
-            DBuf<u64> &pstart = P.pstart;
-            pstart.alloc(nparts + 1);
-            prim::for_each(nparts + 1, prim::RecBoundsFn{skey.p, n_occ, part_bits, nparts, pstart.p}, "phrase_part.bounds");
+            const u64 nparts = (u64)1 << part.part_bits;
+            P.pstart.alloc(nparts + 1);
+            prim::for_each(nparts + 1, prim::RecBoundsFn{skey.p, n_occ, part.part_bits, nparts, P.pstart.p}, "phrase_part.bounds");
             P.lid.alloc(n_occ); P.pbase.alloc(nparts + 1); dcnt.alloc(n_occ);
-            DBuf<u32> pcount(nparts), ovf(1);
-            ovf.zero();
-            prim::rec_dedupe(nparts, pstart.p, skey.p, shi.p, RecValid{}, P.lid.p, pcount.p, dkey.p, dhi.p, dcnt.p, ovf.p, "phrase_dedupe");
+            DBuf<u32> pcount(nparts), ovf(1); ovf.zero();
+            prim::rec_dedupe(nparts, P.pstart.p, skey.p, shi.p, RecValid{}, P.lid.p, pcount.p, dkey.p, dhi.p, dcnt.p, ovf.p, "phrase_dedupe");
             if (ovf.get(0)) {
-                // a partition with more distinct phrases than its LDS table takes (or an injected limit in the tests): this level
-                // goes through the hash table after all
                 if (prim::sw().table_trace) fprintf(stderr, "[grlbwt] level %d: a phrase partition overflowed, falling back to the hash table\n", prim::rt().tag);
                 L.info.table_retries++;
-                skey.release(); shi.release(); dkey.release(); dhi.release(); keys.release(); counts.release(); rep_pos.release(); claim.release();
-                startbits.release(); wordbase.release(); dcnt.release();
-                P.clear();
-                hash_local<cell_t, FIRST>(t, n, ops, P, L, false);
-                return;
+                return false;
             }
             Ds = (u64)prim::exclusive_scan<u32>(nparts, PtrU32In{pcount.p}, P.pbase.p, true, "phrase_dedupe.scan");
             skey.release(); shi.release();                // the sorted records are no longer needed (the emission walks the partitions: pstart, lid)
-            P.Ds = Ds; P.part_bits = part_bits; P.rec_b = rec_b; P.slot0 = (u32)P.cap;
+            P.Ds = Ds; P.part_bits = part.part_bits; P.rec_b = part.rec_b; P.slot0 = (u32)P.cap;
             if (P.cap + Ds >= (1ull << 32)) throw prim::Error(-75, "phrase tables beyond 2^32 entries");
             P.cap += Ds;                                  // values of the record phrases live behind the table's slots
+            return true;
         }
-
-        // ---- a5: distinct phrases of this text (from the claim bits: the table itself is not scanned) -------------------
-        {
-            StageTimer st(&tm.dict_sort, "dict_sort");
+        // a5: distinct phrases of this text (from the claim bits: the table itself is not scanned)
+        void compact_dictionary() {
+            StageTimer st(&E.tm.dict_sort, "dict_sort");
             DBuf<idx_t> cbase(nwords + 1);
             const u64 Dl = (u64)prim::exclusive_scan<idx_t>(nwords, PopcIn{claim.p}, cbase.p, false, "table_compact");
             const u64 D = Ds + Dl;
             if (D >= 0xFFFFFFF0ull) throw prim::Error(-75, "dictionary too large (>= 2^32 phrases)");
             P.D = D;
             P.ph_pos.alloc(D); P.ph_freq.alloc(D); P.ph_len.alloc(D); P.ph_slot.alloc(D); P.ph_lastT.alloc(D); P.ph_off.alloc(D + 1);
-            if (part) {                                   // phrases [0, Ds): from the partitions' staging areas
+            if (part.on) {                                // phrases [0, Ds): from the partitions' staging areas
                 P.ph_key.alloc(Ds); P.ph_vflag.alloc(Ds);
-                prim::for_each(((u64)1 << part_bits) * 64, PartPhraseFn{P.pbase.p, P.pstart.p, dkey.p, dhi.p, dcnt.p, P.slot0, P.ph_key.p, P.ph_pos.p, P.ph_freq.p,
-                                                                     P.ph_len.p, P.ph_slot.p, P.ph_lastT.p, P.ph_vflag.p}, "phrase_dedupe.phrases");
+                prim::for_each(((u64)1 << part.part_bits) * 64, PartPhraseFn{P.pbase.p, P.pstart.p, dkey.p, dhi.p, dcnt.p, P.slot0, P.ph_key.p, P.ph_pos.p, P.ph_freq.p,
+                                                                          P.ph_len.p, P.ph_slot.p, P.ph_lastT.p, P.ph_vflag.p}, "phrase_dedupe.phrases");
                 dkey.release(); dhi.release(); dcnt.release();
             }
             // ... and the phrases of the table behind them
             prim::for_each(nwords, ClaimSlotsFn{claim.p, cbase.p, startbits.p, wordbase.p, P.next_text.p, P.ph_slot.p + Ds}, "table_compact");
-            prim::for_each(Dl, ClaimCompactFn<cell_t, FIRST>{CompactTableFn<cell_t, FIRST>{t, ops, startbits.p, keys.p, counts_p, P.ph_pos.p + Ds,
-                                                             P.ph_freq.p + Ds, P.ph_len.p + Ds, P.ph_slot.p + Ds, P.ph_lastT.p + Ds, ks, cs, rep_pos.p, n}}, "table_compact");
+            prim::for_each(Dl, ClaimCompactFn<cell_t, FIRST>{CompactTableFn<cell_t, FIRST>{t, ops, startbits.p, keys.p, cnt, P.ph_pos.p + Ds,
+                                                             P.ph_freq.p + Ds, P.ph_len.p + Ds, P.ph_slot.p + Ds, P.ph_lastT.p + Ds, tab.ks, tab.cs, rep_pos.p, n}}, "table_compact");
             wordbase.release(); claim.release();
             // (frequencies and lengths summed by ONE reduction, the offsets by a scan whose total is known already: two host
             // synchronisations instead of four)
@@ -3598,10 +3575,32 @@ class Engine {
             if (fl.a != n_occ) throw prim::Error(-71, "phrase frequencies (" + std::to_string(fl.a) + ") do not add up to the parse size (" +
                                                            std::to_string(n_occ) + ")");
             P.maxlen = prim::reduce_max<u32>(D, LenIn{P.ph_len.p}, "dict_maxlen");   // (an atomicMax per insert serialised on one address)
-            const u64 S64 = fl.b;
-            if (S64 >= 0xFFFFFFF0ull) throw prim::Error(-75, "dictionary too large (>= 2^32 symbols)");
+            if (fl.b >= 0xFFFFFFF0ull) throw prim::Error(-75, "dictionary too large (>= 2^32 symbols)");
             prim::exclusive_scan_nosync<u32>(D, LenIn{P.ph_len.p}, P.ph_off.p, true, "dict_offsets");
-            P.S = S64;
+            P.S = fl.b;
+        }
+    };
+    template <class cell_t, bool FIRST>
+    void hash_local(const cell_t *t, u64 n, CellOps<cell_t, FIRST> ops, LocalParse &P, LevelData &L, bool allow_part = false) {
+        // (second turn: a partition overflowed -- the first stage and what it held are gone, the parse is cleared, and the level is
+        // named once more, through the hash table alone)
+        for (;; allow_part = false, P.clear()) {
+            NameStage<cell_t, FIRST> Z(*this, t, n, ops, P, L);
+            Z.classify();
+            Z.plan_partitions(allow_part);
+            Z.sample_table();
+            Z.plan_table();
+            {
+                StageTimer st(&tm.hash, "hash");
+                while (!Z.hash_pass()) {      // a lane ran out of probes: a table four times the size, and the pass again
+                    if (Z.tab.cap == Z.tab.cap_max) throw prim::Error(-28, "phrase hash table overflow");
+                    Z.tab.cap = std::min(Z.tab.cap * 4, Z.tab.cap_max);
+                    L.info.table_retries++;
+                }
+            }
+            if (Z.part.on && !Z.dedupe_partitions()) continue;      // (Z goes out of scope before P.clear() runs)
+            Z.compact_dictionary();
+            return;
         }
     }
 

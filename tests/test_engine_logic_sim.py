@@ -368,13 +368,18 @@ def test_table_sizing_from_a_sample(sim, oracle_mod, capfd, monkeypatch):
     parity.check_final(sim, rep + workloads.uniform_reads(6000, 100, seed=77).tobytes(), 1)
 
 
+def _few_documents_u16():
+    """30 000 draws from 40 documents of 20-60 uint16 cells: a little over 2^20 cells."""
+    rng = np.random.default_rng(3)
+    docs = [np.concatenate([rng.integers(1, 50, size=int(rng.integers(20, 60))), [0]]).astype(np.uint16) for _ in range(40)]
+    return np.concatenate([docs[int(i)] for i in rng.integers(0, 40, size=30000)])
+
+
 def test_hot_table_with_generic_keys(sim, oracle_mod, capfd, monkeypatch):
     """uint16 cells (no exact keys): a text above 2^20 cells made of few distinct documents -- the generic (hash tag + compare)
     keys through the hot table, and the mixed case where half of the text never shows up in the sample."""
     monkeypatch.setenv("GRLBWT_TABLE_TRACE", "1")
-    rng = np.random.default_rng(3)
-    docs = [np.concatenate([rng.integers(1, 50, size=int(rng.integers(20, 60))), [0]]).astype(np.uint16) for _ in range(40)]
-    cells = np.concatenate([docs[int(i)] for i in rng.integers(0, 40, size=30000)])
+    cells = _few_documents_u16()
     assert cells.size > (1 << 20)
     parity.check_final(sim, cells.tobytes(), 2)
     assert "hot table of" in capfd.readouterr().err
@@ -408,26 +413,34 @@ def test_partitioned_phrase_naming(sim, oracle_mod, monkeypatch, capfd):
     assert "falling back to the hash table" in capfd.readouterr().err
 
 
+def _direct_index_texts():
+    """The byte texts of the direct-index tests: reads with N (303 000 cells), five texts of 40 001 cells over chosen alphabets,
+    and a text of 43 bytes whose phrases have every length around 7 and end the text."""
+    rng = np.random.default_rng(5)
+    dna = workloads.sampled_reads(3000, 100, 20000, seed=11).copy()
+    dna[rng.integers(0, dna.size, size=300)] = ord("N")
+    dna[dna.size - 1] = 10
+    dna[np.flatnonzero(workloads.sampled_reads(3000, 100, 20000, seed=11) == 10)] = 10
+    # (values told apart by bits 0, 3, 6 -- all 8 codes in use; by bits 1, 4, 7; three values; 9 values: no direct index;
+    # 8 one-hot values: no three bits tell them apart, no direct index either)
+    alphabets = []
+    for alphabet in (bytes([0, 1, 8, 9, 64, 65, 72, 73]), bytes([0x20, 0x22, 0x30, 0x32, 0xA0, 0xA2]), b"\x00ab", bytes(range(10, 19)),
+                     bytes([1, 2, 4, 8, 16, 32, 64, 128])):
+        vals = np.frombuffer(alphabet, dtype=np.uint8)
+        body = vals[1:][rng.integers(0, len(vals) - 1, size=40000)]
+        body[rng.integers(0, body.size, size=700)] = vals[0]
+        alphabets.append(np.concatenate([body, vals[:1]]).tobytes())
+    return dna.tobytes(), alphabets, b"ACGTACG\nACGTACGT\nAC\nA\n\nACGTAC\nGATTACA\n"
+
+
 def test_direct_index_of_short_phrases(sim, oracle_mod, monkeypatch):
     """Byte texts with at most 8 distinct cell values: a phrase of <= 7 cells is named by its own number (three bits per cell,
     HashInsertFn::direct_index) -- no table.  Forced on texts too small for a sample, stage by stage against the oracle: DNA with
     N, an alphabet whose codes need non-adjacent bits, exactly 8 values, phrases of every length around 7 and at the very end of the
     text (the walk path must give the same slot as the batch path); 9 values fall back to the table."""
     monkeypatch.setenv("GRLBWT_FORCE_DIRECT_INDEX", "1")
-    rng = np.random.default_rng(5)
-    dna = workloads.sampled_reads(3000, 100, 20000, seed=11).copy()
-    dna[rng.integers(0, dna.size, size=300)] = ord("N")
-    dna[dna.size - 1] = 10
-    dna[np.flatnonzero(workloads.sampled_reads(3000, 100, 20000, seed=11) == 10)] = 10
-    parity.check_stagewise(sim, dna.tobytes(), 1)
-    # (values told apart by bits 0, 3, 6 -- all 8 codes in use; by bits 1, 4, 7; three values; 9 values: no direct index;
-    # 8 one-hot values: no three bits tell them apart, no direct index either)
-    for alphabet in (bytes([0, 1, 8, 9, 64, 65, 72, 73]), bytes([0x20, 0x22, 0x30, 0x32, 0xA0, 0xA2]), b"\x00ab", bytes(range(10, 19)),
-                     bytes([1, 2, 4, 8, 16, 32, 64, 128])):
-        vals = np.frombuffer(alphabet, dtype=np.uint8)
-        body = vals[1:][rng.integers(0, len(vals) - 1, size=40000)]
-        body[rng.integers(0, body.size, size=700)] = vals[0]
-        text = np.concatenate([body, vals[:1]])
-        parity.check_stagewise(sim, text.tobytes(), 1)
-    parity.check_final(sim, b"ACGTACG\nACGTACGT\nAC\nA\n\nACGTAC\nGATTACA\n", 1)
-
+    dna, alphabets, tiny = _direct_index_texts()
+    parity.check_stagewise(sim, dna, 1)
+    for text in alphabets:
+        parity.check_stagewise(sim, text, 1)
+    parity.check_final(sim, tiny, 1)

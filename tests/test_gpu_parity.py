@@ -142,6 +142,31 @@ def test_partitioned_phrase_naming(hip, oracle_mod, monkeypatch, capfd, part_bit
     assert "falling back to the hash table" in capfd.readouterr().err
 
 
+def test_direct_index_forced_on_small_texts(hip, oracle_mod, monkeypatch):
+    """(see tests/test_engine_logic_sim.py::test_direct_index_of_short_phrases, same inputs) the direct index forced on texts too
+    small for a sample, on the device: prim::k_name_stream, the list of what it cannot name through the general code, DirectFixFn,
+    and the alphabets for which no three bits tell the values apart (9 values, 8 one-hot values: the plain table)."""
+    from tests.test_engine_logic_sim import _direct_index_texts
+    monkeypatch.setenv("GRLBWT_FORCE_DIRECT_INDEX", "1")
+    dna, alphabets, tiny = _direct_index_texts()
+    parity.check_stagewise(hip, dna, 1)
+    for text in alphabets:
+        parity.check_stagewise(hip, text, 1)
+    parity.check_final(hip, tiny, 1)
+
+
+def test_hot_table_with_generic_keys(hip, oracle_mod, monkeypatch, capfd):
+    """(see tests/test_engine_logic_sim.py, same input) uint16 cells, few distinct documents, above 2^20 cells: the sample's phrases
+    fill the hot table (site hash_hot) and the pass over the text reads it with generic (hash tag + compare) keys."""
+    from tests.test_engine_logic_sim import _few_documents_u16
+    monkeypatch.setenv("GRLBWT_TABLE_TRACE", "1")
+    cells = _few_documents_u16()
+    assert cells.size > (1 << 20)
+    capfd.readouterr()
+    parity.check_final(hip, cells.tobytes(), 2)
+    assert "hot table of" in capfd.readouterr().err
+
+
 def test_run_aware_suffix_keys(hip, oracle_mod, monkeypatch):
     """Long runs of one symbol (an N gap of 150 k cells in six copies, runs ending a string, runs followed by smaller / larger
     symbols): ONE phrase per run, and the dictionary suffix sort must not take run / K refinement rounds for each of the run's
