@@ -116,10 +116,11 @@ void grammar_download(const E &e, int level, uint64_t *g0, uint64_t *g1, uint8_t
 #define ENG(ctx, expr) ((ctx)->e32 ? (ctx)->e32->expr : (ctx)->e64->expr)
 #define HAS_ENG(ctx) ((ctx) && ((ctx)->e32 || (ctx)->e64))
 
+static constexpr uint64_t kIdx32Limit = 0xFFFFFF00ull;      // texts of this many cells or more take the 64-bit index build
 void load(grlbwt_ctx *ctx, const void *cells, uint64_t n, int w, bool host) {
     ctx->e32.reset();
     ctx->e64.reset();
-    bool big = (n >= 0xFFFFFF00ull) || (ctx->flags & GRLBWT_FLAG_FORCE_IDX64);
+    bool big = (n >= kIdx32Limit) || (ctx->flags & GRLBWT_FLAG_FORCE_IDX64);
     bool keep = ctx->flags & GRLBWT_FLAG_KEEP_LEVELS;
     if (big) {
         std::unique_ptr<grl64::Engine> e(new grl64::Engine());
@@ -295,7 +296,7 @@ void load_file(grlbwt_ctx *ctx, const char *path, int w, uint64_t base = 0, uint
             bytes = range_bytes;
         } else base = 0;
         const uint64_t n = bytes / (uint64_t)w;
-        bool big = (n >= 0xFFFFFF00ull) || (ctx->flags & GRLBWT_FLAG_FORCE_IDX64);
+        bool big = (n >= kIdx32Limit) || (ctx->flags & GRLBWT_FLAG_FORCE_IDX64);
         bool keep = ctx->flags & GRLBWT_FLAG_KEEP_LEVELS;
         if (big) {
             std::unique_ptr<grl64::Engine> e(new grl64::Engine());
@@ -444,7 +445,7 @@ void load_fastx(grlbwt_ctx *ctx, const char *path, uint32_t fx_flags, uint64_t *
     if (n_strings) *n_strings = info.n_strings;
     if (info.n_out == 0) throw prim::Error(GRLBWT_EILLFORMED, "Error: the file is ill formed");      // no record at all
     const uint64_t n = info.n_out;
-    bool big = (n >= 0xFFFFFF00ull) || (ctx->flags & GRLBWT_FLAG_FORCE_IDX64);
+    bool big = (n >= kIdx32Limit) || (ctx->flags & GRLBWT_FLAG_FORCE_IDX64);
     bool keep = ctx->flags & GRLBWT_FLAG_KEEP_LEVELS;
     if (big) {
         std::unique_ptr<grl64::Engine> e(new grl64::Engine());
@@ -709,6 +710,696 @@ int test_part(uint64_t n, uint64_t seed, int pbits) {
     return 0;
 }
 
+// ---- self-test, second part: stream merge, LDS segment sort, record packing, set-bit walk ------------------------------
+// Every section has a host reference of its own written from plain arrays (none goes through the functors handed to the device,
+// prim::sm_walk or the serial stand-in), poisons what the device may write and checks that nothing else changed.  A mismatch
+// prints one line with everything needed to find it; the return code names the section (-2xx, -3xx, -4xx, -5xx).
+GRL_HD uint64_t self_mix(uint64_t z) {
+    z += 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+uint64_t self_size(uint64_t n) { return std::min<uint64_t>(n, ((uint64_t)1 << 21) + n % 4099); }      // sizes taken from n stay bounded
+template <class T>
+void self_upload(grl32::DBuf<T> &d, const std::vector<T> &h) {
+    d.alloc(h.size());
+    prim::h2d(d.p, h.data(), h.size() * sizeof(T));
+}
+struct alignas(16) SelfRank { uint64_t w, b; };      // a word of a bit-vector and the set bits in front of it
+std::vector<SelfRank> self_rank_cells(const std::vector<uint64_t> &words) {
+    std::vector<SelfRank> c(words.size());
+    uint64_t b = 0;
+    for (size_t i = 0; i < words.size(); i++) { c[i].w = words[i]; c[i].b = b; b += (uint64_t)__builtin_popcountll(words[i]); }
+    return c;
+}
+
+// ---- 1: stream merge
+// The segment stream in the shape of the engine's AsmSeg: "pre" runs and "cells" (two record arrays), a bit-vector over the
+// segment axis that says which is which, and T given by its maximal runs (start bits with ranks, symbols, positions).
+// Lengths are >= 1: a TAKE of no symbols would underflow the kernel's `kb - 1 - ka`, and the engine makes none.
+static constexpr uint32_t kSelfTake = 0x3FFFFFFFu;
+static const uint32_t kSelfSyms[3] = {0u, 1u, 0x3FFFFFFEu};
+template <class IDX>
+struct SelfSeg {
+    const SelfRank *kinds; const uint32_t *pre_sym; const IDX *pre_len; const uint32_t *cell_sym; const IDX *cell_len; uint32_t take_code;
+    const SelfRank *tstarts; const uint32_t *esym_; const IDX *epos_;
+    struct Ref { uint64_t idx; bool pre; };
+    GRL_DEV static uint64_t rank(const SelfRank *rc, uint64_t x) {
+        const SelfRank c = rc[x >> 6];
+        return c.b + (uint64_t)__builtin_popcountll(c.w & ((1ull << (x & 63)) - 1ull));
+    }
+    GRL_DEV Ref locate(uint64_t g) const {
+        const uint64_t ord = rank(kinds, g);
+        const bool pre = (kinds[g >> 6].w >> (g & 63)) & 1ull;
+        return Ref{pre ? ord : g - ord, pre};
+    }
+    GRL_DEV void fetch(const Ref &r, uint32_t &sym, IDX &len, bool &take) const {
+        if (r.pre) { sym = pre_sym[r.idx]; len = pre_len[r.idx]; }
+        else { sym = cell_sym[r.idx]; len = cell_len[r.idx]; }
+        take = sym == take_code;
+    }
+    GRL_DEV uint64_t pre_before(uint64_t g) const { return rank(kinds, g); }
+    GRL_DEV Ref plain(uint64_t t) const { return Ref{t, false}; }
+    GRL_DEV uint64_t erank(uint64_t x) const { return rank(tstarts, x); }
+    GRL_DEV void eword(uint64_t w, uint64_t &bits, uint64_t &before) const { const SelfRank c = tstarts[w]; bits = c.w; before = c.b; }
+    GRL_DEV uint32_t esym(uint64_t k) const { return esym_[k]; }
+    GRL_DEV uint64_t epos(uint64_t k) const { return (uint64_t)epos_[k]; }
+};
+// A scenario: the segments in output order and T's maximal runs.  T grows as the TAKE segments consume it, so the TAKE lengths
+// always tile it; a new run never repeats the symbol of the one in front of it, so the runs are maximal.
+struct SmScn {
+    const char *name = "";
+    std::vector<uint8_t> pre;              // segment g is a pre run (else a cell)
+    std::vector<uint32_t> sym;             // kSelfTake: a TAKE
+    std::vector<uint64_t> len;
+    std::vector<uint32_t> tsym;
+    std::vector<uint64_t> tlen;
+    uint32_t tcur = 0xFFFFFFFFu;           // symbol of T's run in progress
+    uint64_t trem = 0;                     // symbols it still has to hand out
+    uint32_t tmaxrun = 4;
+    uint64_t rng = 1;
+    int idx_only = 0;                      // 4 / 8: the scenario is made for one index width
+    // what the scenario is there for: each must be seen at least once (per tile size) or the scenario has lost its point
+    bool need_plain = false, need_mixed = false, need_unstaged = false, need_queued = false, need_staged_queued = false, need_wide = false,
+         need_exact = false, need_zero = false, need_ends = false, need_one_run = false, need_inner = false;
+    int ends_hit = 0;
+    uint64_t r() { return sm64(rng); }
+    void lit(uint32_t s, uint64_t l, bool p) { pre.push_back(p ? 1 : 0); sym.push_back(s); len.push_back(l); }
+    void t_run(uint32_t s, uint64_t l) { tsym.push_back(s); tlen.push_back(0); tcur = s; trem = l; }      // (s differs from tcur; the run in progress ends where it is)
+    uint32_t other(uint32_t s) { uint32_t o; do o = kSelfSyms[r() % 3]; while (o == s); return o; }
+    void take(uint64_t l, bool p) {
+        pre.push_back(p ? 1 : 0); sym.push_back(kSelfTake); len.push_back(l);
+        while (l) {
+            if (!trem) t_run(other(tcur), 1 + r() % tmaxrun);
+            const uint64_t c = std::min(l, trem);
+            tlen.back() += c; trem -= c; l -= c;
+        }
+    }
+    // the literal at `giant` gets the length that makes the segments [a, b) describe exactly `total` symbols
+    void fit(uint64_t a, uint64_t b, uint64_t giant, uint64_t total) {
+        uint64_t s = 0;
+        for (uint64_t g = a; g < b && g < len.size(); g++) if (g != giant) s += len[g];
+        len[giant] = total - s;
+    }
+};
+struct SmRef {
+    std::vector<uint32_t> rsym;
+    std::vector<uint64_t> rstart;
+    std::vector<uint64_t> run0;            // [G + 1] runs in front of segment g
+    std::vector<uint32_t> inner;           // [G] runs of T a TAKE touches behind the first
+    uint64_t take_total = 0, len_total = 0, atoms = 0;
+};
+// the run-level serial walk: literal runs and the pieces of T's runs the TAKE segments cut out, equal neighbours merged
+void sm_reference(const SmScn &sc, SmRef &R) {
+    const uint64_t G = sc.sym.size();
+    R.run0.assign(G + 1, 0);
+    R.inner.assign(G, 0);
+    uint64_t x = 0, L = 0, tstart = 0;
+    size_t tk = 0;
+    uint32_t prev = 0xFFFFFFFFu;
+    for (uint64_t g = 0; g < G; g++) {
+        R.run0[g] = R.rsym.size();
+        if (sc.sym[g] != kSelfTake) {
+            R.atoms++;
+            if (sc.sym[g] != prev) { R.rsym.push_back(sc.sym[g]); R.rstart.push_back(L); }
+            prev = sc.sym[g];
+        } else {
+            const uint64_t end = x + sc.len[g];
+            uint32_t pieces = 0;
+            for (uint64_t at = x; at < end;) {
+                while (tstart + sc.tlen[tk] <= at) { tstart += sc.tlen[tk]; tk++; }      // the run of T that holds `at`
+                const uint32_t s = sc.tsym[tk];
+                R.atoms++; pieces++;
+                if (s != prev) { R.rsym.push_back(s); R.rstart.push_back(L + (at - x)); }
+                prev = s;
+                at = std::min(end, tstart + sc.tlen[tk]);
+            }
+            R.inner[g] = pieces - 1;
+            x = end;
+        }
+        L += sc.len[g];
+    }
+    R.run0[G] = R.rsym.size();
+    R.take_total = x; R.len_total = L;
+}
+// the same from the symbol string itself (small totals): expand T, expand the segments, run-length encode
+bool sm_reference_agrees_with_expansion(const SmScn &sc, const SmRef &R) {
+    std::vector<uint32_t> T, S;
+    T.reserve(R.take_total); S.reserve(R.len_total);
+    for (size_t k = 0; k < sc.tsym.size(); k++) T.insert(T.end(), sc.tlen[k], sc.tsym[k]);
+    if (T.size() != R.take_total) return false;
+    uint64_t x = 0;
+    for (size_t g = 0; g < sc.sym.size(); g++) {
+        if (sc.sym[g] != kSelfTake) S.insert(S.end(), sc.len[g], sc.sym[g]);
+        else { S.insert(S.end(), T.begin() + x, T.begin() + x + sc.len[g]); x += sc.len[g]; }
+    }
+    if (S.size() != R.len_total || x != R.take_total) return false;
+    size_t k = 0;
+    for (uint64_t i = 0; i < S.size(); i++) {
+        if (i && S[i] == S[i - 1]) continue;
+        if (k >= R.rsym.size() || R.rsym[k] != S[i] || R.rstart[k] != i) return false;
+        k++;
+    }
+    return k == R.rsym.size();
+}
+struct SmTileStats { uint64_t tiles = 0, plain = 0, mixed = 0, unstaged = 0, queued = 0, staged_queued = 0, wide = 0, exact_fe = 0, exact_ff = 0, zero = 0; };
+SmTileStats sm_tile_stats(const SmScn &sc, const SmRef &R, int spt, int idx_bytes) {
+    const uint64_t G = sc.sym.size(), tile = 256ull * (uint64_t)spt;
+    SmTileStats st;
+    for (uint64_t a = 0; a < G; a += tile) {
+        const uint64_t b = std::min(G, a + tile), heads = R.run0[b] - R.run0[a];
+        uint64_t npre = 0, total = 0, q = 0;
+        for (uint64_t g = a; g < b; g++) { npre += sc.pre[g]; total += sc.len[g]; if (R.inner[g] > 8) q++; }
+        st.tiles++;
+        if (npre) st.mixed++; else st.plain++;
+        if (heads > tile) st.unstaged++;
+        else if (a > 0) st.staged_queued += q;
+        st.queued += q;
+        if (idx_bytes == 8 && total >= 0xFFFFFFFFull) st.wide++;
+        if (total == 0xFFFFFFFEull) st.exact_fe++;
+        if (total == 0xFFFFFFFFull) st.exact_ff++;
+        if (heads == 0) st.zero++;
+    }
+    return st;
+}
+// 0, or what the scenario declared and did not get
+const char *sm_scenario_lost(const SmScn &sc, const SmRef &R, int spt, int idx_bytes) {
+    const SmTileStats st = sm_tile_stats(sc, R, spt, idx_bytes);
+    if (sc.need_plain && st.plain < 3) return "plain tiles";
+    if (sc.need_mixed && !st.mixed) return "mixed tiles";
+    if (sc.need_unstaged && !st.unstaged) return "tiles with more heads than segments";
+    if (sc.need_queued && !st.queued) return "queued segments";
+    if (sc.need_staged_queued && !st.staged_queued) return "queued segments in a staged tile behind the first";
+    if (sc.need_wide && !st.wide) return "tiles in the 64-bit form";
+    if (sc.need_exact && (!st.exact_fe || !st.exact_ff)) return "tiles of exactly 2^32 - 2 and 2^32 - 1 symbols";
+    if (sc.need_zero && st.zero + 1 != st.tiles) return "tiles without a head";
+    if (sc.need_ends && sc.ends_hit != 5) return "TAKE ends at T bits 63, 64, 65, 127, 128";
+    if (sc.need_one_run && R.rsym.size() != 1) return "a single run";
+    if (sc.need_inner) {
+        bool seen[10] = {false};
+        for (uint32_t v : R.inner) if (v < 10) seen[v] = true;
+        if (!seen[0] || !seen[1] || !seen[8] || !seen[9]) return "TAKEs with 0, 1, 8 and 9 inner runs";
+    }
+    return nullptr;
+}
+
+SmScn sm_scn_mix(uint64_t G, uint64_t seed) {
+    SmScn sc;
+    sc.name = "mix"; sc.rng = seed;
+    static const uint64_t ends[5] = {63, 64, 65, 127, 128};      // a TAKE's end in the word of its start, at its last bit, in the next word
+    uint64_t x = 0, left = 3000 + sc.r() % 2000;
+    bool mixed = true, first = true;
+    for (uint64_t g = 0; g < G; g++) {
+        if (!left) { mixed = !mixed; first = true; left = mixed ? 3000 + sc.r() % 2000 : 4 * 2048 + sc.r() % 3000; }
+        const bool p = mixed && (first || sc.r() % 3 == 0);
+        if (sc.r() % 4 == 0) {
+            uint64_t l = 1 + sc.r() % 5;
+            if (sc.ends_hit < 5 && x < ends[sc.ends_hit] && ends[sc.ends_hit] - x <= 5) l = ends[sc.ends_hit] - x;
+            sc.take(l, p);
+            x += l;
+            if (sc.ends_hit < 5 && x == ends[sc.ends_hit]) sc.ends_hit++;
+        } else sc.lit(kSelfSyms[sc.r() % 3], 1 + sc.r() % 5, p);
+        first = false; left--;
+    }
+    sc.need_mixed = true;
+    sc.need_plain = G >= 16384;          // (a mixed stretch is at most 5000 segments, the plain one behind it at least four large tiles)
+    sc.need_ends = G >= 4096;
+    return sc;
+}
+SmScn sm_scn_one_run(uint64_t seed) {
+    SmScn sc;
+    sc.name = "one run"; sc.rng = seed;
+    for (uint64_t g = 0; g < 3 * 2048 + 5; g++) sc.lit(kSelfSyms[1], 1 + sc.r() % 3, sc.r() % 3 == 0);
+    sc.need_zero = sc.need_one_run = sc.need_mixed = true;
+    return sc;
+}
+SmScn sm_scn_seam(uint64_t seed) {
+    SmScn sc;
+    sc.name = "tile seam"; sc.rng = seed;
+    const uint64_t G = 5 * 1024 + 17;
+    uint32_t forced = 0xFFFFFFFFu;
+    for (uint64_t g = 0; g < G; g++) {
+        const bool p = sc.r() % 3 == 0;
+        if ((g + 1) % 1024 == 0) {           // the last segment of a small tile, of a large one too where (g + 1) / 1024 is even
+            const uint64_t k = (g + 1) / 1024;
+            const uint32_t s = sc.other(sc.tcur);
+            sc.t_run(s, 5);                  // the TAKE takes two of its five symbols: it ends inside the run
+            sc.take(2, p);
+            forced = (k == 3 || k == 4) ? sc.other(s) : s;
+        } else if (forced != 0xFFFFFFFFu) { sc.lit(forced, 1 + sc.r() % 3, p); forced = 0xFFFFFFFFu; }
+        else if (sc.r() % 4 == 0) sc.take(1 + sc.r() % 5, p);
+        else sc.lit(kSelfSyms[sc.r() % 3], 1 + sc.r() % 3, p);
+    }
+    sc.need_mixed = true;
+    return sc;
+}
+SmScn sm_scn_wide(uint64_t seed) {
+    SmScn sc;
+    sc.name = "wide"; sc.rng = seed; sc.tmaxrun = 1;       // runs of one symbol: a TAKE of l symbols has l - 1 inner runs
+    const uint64_t G = 4 * 2048 + 100;
+    static const uint64_t lens[4] = {1, 2, 9, 10};
+    uint32_t forced = 0xFFFFFFFFu, last = kSelfSyms[0];
+    for (uint64_t g = 0; g < G; g++) {
+        const bool p = sc.r() % 3 == 0;
+        if (g == 0 || g == 4095 || g == 4096 + 100 || g == 4096 + 600) { sc.take(5001, p); forced = sc.tcur; }
+        else if (forced != 0xFFFFFFFFu) { sc.lit(forced, 1 + sc.r() % 3, p); last = forced; forced = 0xFFFFFFFFu; }
+        else if (sc.r() % 16 == 0) sc.take(lens[sc.r() % 4], p);
+        else { if (sc.r() % 2) last = kSelfSyms[sc.r() % 3]; sc.lit(last, 1 + sc.r() % 3, p); }
+    }
+    sc.need_unstaged = sc.need_queued = sc.need_staged_queued = sc.need_inner = sc.need_mixed = true;
+    return sc;
+}
+SmScn sm_scn_random(const char *name, uint64_t G, uint64_t seed) {
+    SmScn sc;
+    sc.name = name; sc.rng = seed;
+    for (uint64_t g = 0; g < G; g++) {
+        const bool p = sc.r() % 3 == 0;
+        if (sc.r() % 4 == 0) sc.take(1 + sc.r() % 5, p);
+        else sc.lit(kSelfSyms[sc.r() % 3], 1 + sc.r() % 3, p);
+    }
+    return sc;
+}
+SmScn sm_scn_wide64(uint64_t seed) {
+    // Counted in small tiles of 1024 segments (small tile b lies in large tile b / 2).  A giant literal makes large tile 1 and small
+    // tile 6 describe exactly 2^32 - 2 symbols (the last tiles of the 32-bit form), large tile 5 and small tile 14 exactly 2^32 - 1
+    // (the first of the 64-bit form), and small tiles 18 and 19 hold literals of 2^31 .. 2^33.  The tiles between them stay small.
+    // A giant takes the place of the first literal at or behind its offset, so the TAKE segments and the T axis stay as drawn.
+    SmScn sc = sm_scn_random("64-bit tiles", 21 * 1024 + 300, seed);
+    sc.idx_only = 8;
+    auto lit_at = [&](uint64_t g) { while (sc.sym[g] == kSelfTake) g++; return g; };
+    const uint64_t g1 = lit_at(2 * 1024 + 5), g2 = lit_at(6 * 1024 + 5), g3 = lit_at(10 * 1024 + 5), g4 = lit_at(14 * 1024 + 5);
+    sc.fit(2 * 1024, 4 * 1024, g1, 0xFFFFFFFEull);
+    sc.fit(6 * 1024, 7 * 1024, g2, 0xFFFFFFFEull);
+    sc.fit(10 * 1024, 12 * 1024, g3, 0xFFFFFFFFull);
+    sc.fit(14 * 1024, 15 * 1024, g4, 0xFFFFFFFFull);
+    sc.len[lit_at(18 * 1024 + 5)] = 1ull << 33;
+    sc.len[lit_at(18 * 1024 + 500)] = 1ull << 31;
+    sc.len[lit_at(19 * 1024 + 7)] = 1ull << 32;
+    sc.len[lit_at(19 * 1024 + 900)] = 1ull << 33;
+    sc.need_wide = sc.need_exact = sc.need_mixed = true;
+    return sc;
+}
+SmScn sm_scn_limit32(uint64_t seed) {
+    SmScn sc = sm_scn_random("32-bit limit", 3 * 2048 + 11, seed);
+    sc.idx_only = 4;
+    uint64_t g = 2048 + 5;
+    while (sc.sym[g] == kSelfTake) g++;
+    sc.fit(0, sc.len.size(), g, kIdx32Limit - 1);       // the longest text load() gives the 32-bit engine
+    sc.need_mixed = true;
+    return sc;
+}
+
+static constexpr uint8_t kSmPoison = 0xA5;
+template <class IDX>
+struct SmDevice {
+    grl32::DBuf<SelfRank> kinds, tstarts;
+    grl32::DBuf<uint32_t> pre_sym, cell_sym, esym;
+    grl32::DBuf<IDX> pre_len, cell_len, epos;
+    uint64_t G = 0, Re = 0, queued = 0;
+    SelfSeg<IDX> seg;
+    void upload(const SmScn &sc, const SmRef &R) {
+        G = sc.sym.size(); Re = sc.tsym.size();
+        std::vector<uint64_t> kw(G / 64 + 1, 0), tw(R.take_total / 64 + 1, 0);      // (one word more than the bits need: ranks at the end of an axis read it)
+        std::vector<uint32_t> ps, cs;
+        std::vector<IDX> pl, cl, ep;
+        for (uint64_t g = 0; g < G; g++) {
+            if (sc.pre[g]) { kw[g >> 6] |= 1ull << (g & 63); ps.push_back(sc.sym[g]); pl.push_back((IDX)sc.len[g]); }
+            else { cs.push_back(sc.sym[g]); cl.push_back((IDX)sc.len[g]); }
+            if (R.inner[g] > 8) queued++;
+        }
+        uint64_t x = 0;
+        for (uint64_t k = 0; k < Re; k++) { tw[x >> 6] |= 1ull << (x & 63); ep.push_back((IDX)x); x += sc.tlen[k]; }
+        std::vector<uint32_t> es = sc.tsym;
+        if (ps.empty()) { ps.push_back(0); pl.push_back(0); }
+        if (cs.empty()) { cs.push_back(0); cl.push_back(0); }
+        if (es.empty()) { es.push_back(0); ep.push_back(0); }
+        self_upload(kinds, self_rank_cells(kw)); self_upload(tstarts, self_rank_cells(tw));
+        self_upload(pre_sym, ps); self_upload(pre_len, pl); self_upload(cell_sym, cs); self_upload(cell_len, cl);
+        self_upload(esym, es); self_upload(epos, ep);
+        seg = SelfSeg<IDX>{kinds.p, pre_sym.p, pre_len.p, cell_sym.p, cell_len.p, kSelfTake, tstarts.p, esym.p, epos.p};
+    }
+};
+// 0, or 3: a total differs, 4: a run differs, 5: an entry behind the runs was written
+template <class IDX>
+int sm_compare(const SmScn &sc, const SmRef &R, int spt, const char *form, const prim::SmPlan<IDX> &plan, const grl32::DBuf<uint32_t> &osym,
+               const grl32::DBuf<IDX> &ostart, bool arrays) {
+    const int ib = (int)sizeof(IDX);
+    if (plan.take_total != R.take_total || plan.len_total != R.len_total || plan.heads != R.rsym.size() || plan.atoms != R.atoms) {
+        fprintf(stderr, "[grlbwt] selftest stream merge: scenario '%s', %d-byte index, %d segments per thread, %s: totals (TAKE symbols, symbols, runs, atoms) "
+                "expected (%llu, %llu, %llu, %llu), got (%llu, %llu, %llu, %llu)\n", sc.name, ib, spt, form,
+                (unsigned long long)R.take_total, (unsigned long long)R.len_total, (unsigned long long)R.rsym.size(), (unsigned long long)R.atoms,
+                (unsigned long long)plan.take_total, (unsigned long long)plan.len_total, (unsigned long long)plan.heads, (unsigned long long)plan.atoms);
+        return 3;
+    }
+    if (!arrays) return 0;
+    const std::vector<uint32_t> hs = osym.to_host(osym.n);
+    const std::vector<IDX> hp = ostart.to_host(ostart.n);
+    const uint64_t heads = R.rsym.size();
+    for (uint64_t k = 0; k < heads; k++) {
+        if (hs[k] != R.rsym[k] || hp[k] != (IDX)R.rstart[k]) {
+            fprintf(stderr, "[grlbwt] selftest stream merge: scenario '%s', %d-byte index, %d segments per thread, %s: run %llu of %llu expected (symbol %u, start %llu), "
+                    "got (%u, %llu)\n", sc.name, ib, spt, form, (unsigned long long)k, (unsigned long long)heads, R.rsym[k], (unsigned long long)R.rstart[k],
+                    hs[k], (unsigned long long)hp[k]);
+            return 4;
+        }
+    }
+    IDX poison;
+    memset(&poison, kSmPoison, sizeof(IDX));
+    for (uint64_t k = heads; k < osym.n; k++) {
+        if (hs[k] != 0xA5A5A5A5u || hp[k] != poison) {
+            fprintf(stderr, "[grlbwt] selftest stream merge: scenario '%s', %d-byte index, %d segments per thread, %s: entry %llu behind the %llu runs was written: "
+                    "(%u, %llu)\n", sc.name, ib, spt, form, (unsigned long long)k, (unsigned long long)heads, hs[k], (unsigned long long)hp[k]);
+            return 5;
+        }
+    }
+    return 0;
+}
+template <class IDX>
+void sm_poison(grl32::DBuf<uint32_t> &osym, grl32::DBuf<IDX> &ostart, uint64_t n) {
+    osym.alloc(n); ostart.alloc(n);
+    prim::dev_memset(osym.p, kSmPoison, n * sizeof(uint32_t));
+    prim::dev_memset(ostart.p, kSmPoison, n * sizeof(IDX));
+}
+// count + emit; the totals are compared before the emit pass runs (its arrays are sized from the reference)
+template <class IDX>
+int sm_two_pass(const SmScn &sc, const SmRef &R, const SmDevice<IDX> &D, bool mostly_plain, const char *form) {
+    const int spt = mostly_plain ? 4 : 8;
+    prim::SmPlan<IDX> plan;
+    grl32::DBuf<uint32_t> osym;
+    grl32::DBuf<IDX> ostart;
+    int rc = 0;
+    try {
+        prim::stream_merge_count<SelfSeg<IDX>, IDX>(D.G, D.seg, plan, "selftest.sm", mostly_plain);
+        rc = sm_compare<IDX>(sc, R, spt, form, plan, osym, ostart, false);
+        if (!rc) {
+            sm_poison<IDX>(osym, ostart, R.rsym.size() + 64);
+            prim::stream_merge_emit<SelfSeg<IDX>, IDX>(D.seg, plan, osym.p, ostart.p, "selftest.sm");
+            rc = sm_compare<IDX>(sc, R, spt, form, plan, osym, ostart, true);
+        }
+    } catch (...) { plan.release(); throw; }
+    plan.release();
+    return rc;
+}
+// the one walk.  how: 0 = as the engine calls it, 1 = a queue one entry short (must give up), 2 = no patience (may give up)
+template <class IDX>
+int sm_one_walk(const SmScn &sc, const SmRef &R, const SmDevice<IDX> &D, bool mostly_plain, int how) {
+    const int spt = mostly_plain ? 4 : 8;
+    const char *form = how == 0 ? "one walk" : (how == 1 ? "one walk, queue one entry short" : "one walk, no patience");
+    const uint64_t cap = D.G + D.Re + 1;      // (an upper bound of the runs: the kernel does not bound its stores by it)
+    prim::SmPlan<IDX> plan;
+    grl32::DBuf<uint32_t> osym;
+    grl32::DBuf<IDX> ostart;
+    sm_poison<IDX>(osym, ostart, cap);
+    int rc = 0;
+    bool done = false;
+    try {
+        const uint64_t qcap = how == 1 ? D.queued - 1 : D.queued;
+        // (the fall-backs run on the device only, so the patience goes to the device library alone: the serial walk waits for nobody)
+#ifdef GRLBWT_PRIM_HIP
+        if (how == 2) done = prim::stream_merge_onepass<SelfSeg<IDX>, IDX>(D.G, D.seg, plan, osym.p, ostart.p, cap, qcap, "selftest.sm1", mostly_plain, (uint64_t)0);
+        else
+#endif
+        done = prim::stream_merge_onepass<SelfSeg<IDX>, IDX>(D.G, D.seg, plan, osym.p, ostart.p, cap, qcap, "selftest.sm1", mostly_plain);
+        if (done) {
+            if (how == 1) {
+                fprintf(stderr, "[grlbwt] selftest stream merge: scenario '%s', %d-byte index, %d segments per thread, %s: the walk did not give up\n", sc.name, (int)sizeof(IDX), spt, form);
+                rc = 7;
+            } else rc = sm_compare<IDX>(sc, R, spt, form, plan, osym, ostart, true);
+        }
+    } catch (...) { plan.release(); throw; }
+    if (!done) {
+        // gave up: the plan holds nothing but G, and count + emit give the result
+        bool empty = plan.G == D.G && plan.heads == 0 && plan.atoms == 0 && plan.take_total == 0 && plan.len_total == 0;
+        if constexpr (prim::kIsDevice) empty = empty && !plan.xbase && !plan.lbase && !plan.hbase && !plan.tlast;
+        const uint64_t tiles = (D.G + 256ull * spt - 1) / (256ull * spt);
+        if (!empty) {
+            fprintf(stderr, "[grlbwt] selftest stream merge: scenario '%s', %d-byte index, %d segments per thread, %s: gave up and left a plan behind\n", sc.name, (int)sizeof(IDX), spt, form);
+            rc = 7;
+        } else if (prim::kIsDevice && how == 0 && tiles <= 256) {      // (every tile resident at once: nobody waits for a tile that has not started)
+            fprintf(stderr, "[grlbwt] selftest stream merge: scenario '%s', %d-byte index, %d segments per thread, %s: gave up in a grid of %llu tiles\n", sc.name, (int)sizeof(IDX), spt, form,
+                    (unsigned long long)tiles);
+            rc = 6;
+        } else {
+            if (how == 0) fprintf(stderr, "[grlbwt] selftest stream merge: scenario '%s', %d-byte index, %d segments per thread: 1 give-up at the default patience in a grid of %llu tiles\n",
+                                  sc.name, (int)sizeof(IDX), spt, (unsigned long long)tiles);
+            plan.release();
+            rc = sm_two_pass<IDX>(sc, R, D, mostly_plain, how == 0 ? "count + emit behind a give-up" : (how == 1 ? "count + emit behind a full queue" : "count + emit behind no patience"));
+        }
+    }
+    plan.release();
+    return rc;
+}
+template <class IDX>
+int sm_check(const SmScn &sc, const SmRef &R, bool fallbacks) {
+    if (sc.idx_only && sc.idx_only != (int)sizeof(IDX)) return 0;
+    SmDevice<IDX> D;
+    D.upload(sc, R);
+    for (int mp = 0; mp < 2; mp++) {
+        if (int rc = sm_two_pass<IDX>(sc, R, D, mp != 0, "count + emit")) return 200 + rc;
+        if (int rc = sm_one_walk<IDX>(sc, R, D, mp != 0, 0)) return 210 + rc;
+        if (prim::kIsDevice && fallbacks) {
+            if (D.queued) if (int rc = sm_one_walk<IDX>(sc, R, D, mp != 0, 1)) return 220 + rc;
+            if (int rc = sm_one_walk<IDX>(sc, R, D, mp != 0, 2)) return 230 + rc;
+        }
+    }
+    return 0;
+}
+int test_stream_merge(uint64_t n, uint64_t seed) {
+    SmScn scn[6] = {sm_scn_mix(self_size(n), seed + 20), sm_scn_one_run(seed + 21), sm_scn_seam(seed + 22), sm_scn_wide(seed + 23), sm_scn_wide64(seed + 24),
+                    sm_scn_limit32(seed + 25)};
+    for (SmScn &sc : scn) {
+        SmRef R;
+        sm_reference(sc, R);
+        uint64_t tt = 0;
+        for (uint64_t l : sc.tlen) tt += l;
+        if (tt != R.take_total) return -202;
+        if (R.len_total <= ((uint64_t)1 << 24) && !sm_reference_agrees_with_expansion(sc, R)) {
+            fprintf(stderr, "[grlbwt] selftest stream merge: scenario '%s': the reference walk and the expanded string disagree\n", sc.name);
+            return -202;
+        }
+        for (int spt = 4; spt <= 8; spt += 4)
+            for (int ib = 4; ib <= 8; ib += 4) {
+                if (sc.idx_only && sc.idx_only != ib) continue;
+                if (const char *lost = sm_scenario_lost(sc, R, spt, ib)) {
+                    fprintf(stderr, "[grlbwt] selftest stream merge: scenario '%s', %d-byte index, %d segments per thread: the input has no %s\n", sc.name, ib, spt, lost);
+                    return -201;
+                }
+            }
+        const bool fallbacks = sc.need_queued || sc.need_plain || sc.need_zero;      // (wide, mix at its full size, one run)
+        if (int rc = sm_check<uint32_t>(sc, R, fallbacks)) return -rc;
+        if (int rc = sm_check<uint64_t>(sc, R, fallbacks)) return -(rc + 40);
+    }
+    return 0;
+}
+
+// ---- 2: groups ordered in LDS (device library only: the stand-in has no such primitive)
+#ifdef GRLBWT_PRIM_HIP
+struct SelfSegSortFn {
+    const uint32_t *bounds; const uint64_t *keys; uint32_t *src; uint64_t *okey; uint8_t *flag; uint32_t *hits;
+    GRL_DEV uint32_t begin(uint64_t b) const { return bounds[2 * b]; }
+    GRL_DEV uint32_t end(uint64_t b) const { return bounds[2 * b + 1]; }
+    GRL_DEV uint64_t key(uint32_t i) const { return keys[i]; }
+    GRL_DEV void write(uint32_t pos, uint32_t item, uint64_t k, bool first, bool beside) const {
+        src[pos] = item; okey[pos] = k; flag[pos] = (uint8_t)((first ? 1 : 0) | (beside ? 2 : 0));
+        atomicAdd(&hits[pos], 1u);
+    }
+};
+// groups of the sizes in (lo, hi] (and of 2 and 3 items, shorter than the padded length the launch allows), four kinds of keys each
+template <int TB>
+int test_seg_sort(const std::vector<uint32_t> &sizes, uint32_t lo, uint32_t hi, uint64_t seed) {
+    static constexpr uint32_t kGap = 5;
+    std::vector<uint32_t> bounds;
+    std::vector<uint64_t> keys;
+    uint64_t s = seed;
+    for (uint32_t sz : sizes) {
+        if (!((sz > lo && sz <= hi) || sz <= 3)) continue;
+        for (int kind = 0; kind < 4; kind++) {
+            for (uint32_t g = 0; g < kGap; g++) keys.push_back(0);
+            bounds.push_back((uint32_t)keys.size());
+            const uint64_t salt = sm64(s), run = 1 + sm64(s) % 7;
+            for (uint32_t i = 0; i < sz; i++) {
+                uint64_t k;
+                if (kind == 0) k = self_mix(salt + i);                                  // all distinct (the mix is a bijection)
+                else if (kind == 1) k = salt;                                           // all equal
+                else if (kind == 2) k = self_mix(salt + i / run) % 97;                 // runs of duplicates, and duplicates apart
+                else k = (self_mix(salt + i) % 3 == 0) ? ~0ull : self_mix(salt + i) % 5;      // the padding key among the keys
+                keys.push_back(k);
+            }
+            bounds.push_back((uint32_t)keys.size());
+        }
+    }
+    for (uint32_t g = 0; g < kGap; g++) keys.push_back(0);
+    const uint64_t N = keys.size(), nseg = bounds.size() / 2;
+    grl32::DBuf<uint32_t> db, dsrc(N), dhits(N);
+    grl32::DBuf<uint64_t> dk, dok(N);
+    grl32::DBuf<uint8_t> dfl(N);
+    self_upload(db, bounds); self_upload(dk, keys);
+    prim::dev_memset(dsrc.p, 0xA5, N * 4); prim::dev_memset(dok.p, 0xA5, N * 8); prim::dev_memset(dfl.p, 0xA5, N); dhits.zero();
+    try {
+        prim::seg_sort_lds<TB>(nseg, SelfSegSortFn{db.p, dk.p, dsrc.p, dok.p, dfl.p, dhits.p}, hi, "selftest.seg_sort");
+        prim::sync();
+    } catch (const prim::Error &e) {
+        fprintf(stderr, "[grlbwt] selftest seg_sort_lds: %d threads, groups of up to %u items: %s\n", TB, hi, e.what());
+        return 1;
+    }
+    const std::vector<uint32_t> hsrc = dsrc.to_host(N), hhits = dhits.to_host(N);
+    const std::vector<uint64_t> hok = dok.to_host(N);
+    const std::vector<uint8_t> hfl = dfl.to_host(N);
+    std::vector<uint8_t> covered(N, 0);
+    std::vector<uint32_t> ord;
+    for (uint64_t b = 0; b < nseg; b++) {
+        const uint32_t a = bounds[2 * b], e = bounds[2 * b + 1], sz = e - a;
+        ord.resize(sz);
+        for (uint32_t i = 0; i < sz; i++) ord[i] = a + i;
+        std::stable_sort(ord.begin(), ord.end(), [&](uint32_t x, uint32_t y) { return keys[x] < keys[y]; });
+        for (uint32_t p = 0; p < sz; p++) {
+            const uint64_t k = keys[ord[p]];
+            const bool eq_prev = p > 0 && keys[ord[p - 1]] == k, eq_next = p + 1 < sz && keys[ord[p + 1]] == k;
+            const uint8_t fl = (uint8_t)(((p > 0 && !eq_prev) ? 1 : 0) | ((eq_prev || eq_next) ? 2 : 0));
+            covered[a + p] = 1;
+            int bad = 0;
+            if (hsrc[a + p] != ord[p]) bad = 2; else if (hok[a + p] != k) bad = 3; else if (hfl[a + p] != fl) bad = 4; else if (hhits[a + p] != 1) bad = 5;
+            if (bad) {
+                fprintf(stderr, "[grlbwt] selftest seg_sort_lds: %d threads, padded to %u, group %llu of %u items (keys of kind %llu), position %u: expected item %u key %llx flags %u, "
+                        "got item %u key %llx flags %u, written %u times\n", TB, hi, (unsigned long long)b, sz, (unsigned long long)(b % 4), p, ord[p] - a, (unsigned long long)k, fl,
+                        hsrc[a + p] - a, (unsigned long long)hok[a + p], hfl[a + p], hhits[a + p]);
+                return bad;
+            }
+        }
+    }
+    for (uint64_t i = 0; i < N; i++)
+        if (!covered[i] && (hsrc[i] != 0xA5A5A5A5u || hfl[i] != 0xA5 || hhits[i] != 0)) {
+            fprintf(stderr, "[grlbwt] selftest seg_sort_lds: %d threads, padded to %u: entry %llu between the groups was written\n", TB, hi, (unsigned long long)i);
+            return 6;
+        }
+    return 0;
+}
+int test_seg_sort_all(uint64_t seed) {
+    const uint32_t mx = prim::seg_sort_lds_max();
+    static bool said = false;
+    if (!said) { said = true; fprintf(stderr, "[grlbwt] selftest: seg_sort_lds_max() = %u items, %u bytes of LDS per workgroup\n", mx, prim::rt().lds_bytes); }
+    std::vector<uint32_t> sizes = {2, 3, 63, 64, 65, 255, 256, 257, mx};
+    for (uint32_t p = 2; p <= mx; p <<= 1) { sizes.push_back(p - 1); sizes.push_back(p); if (p < mx) sizes.push_back(p + 1); }
+    std::sort(sizes.begin(), sizes.end());
+    sizes.erase(std::unique(sizes.begin(), sizes.end()), sizes.end());
+    sizes.erase(std::remove_if(sizes.begin(), sizes.end(), [](uint32_t v) { return v < 2; }), sizes.end());
+    const uint32_t tiers[4] = {3, 256, 4096, mx};
+    for (int t = 0; t < 3; t++) {
+        if (tiers[t] >= tiers[t + 1]) continue;
+        if (int rc = test_seg_sort<64>(sizes, tiers[t], tiers[t + 1], seed + t)) return -(300 + rc);
+        if (int rc = test_seg_sort<256>(sizes, tiers[t], tiers[t + 1], seed + 10 + t)) return -(310 + rc);
+    }
+    return 0;
+}
+#endif
+
+// ---- 3: fixed-width records
+struct SelfPackFn {
+    uint64_t salt;
+    GRL_DEV uint64_t operator()(uint64_t i) const { return self_mix(salt ^ (i * 0x9E3779B97F4A7C15ull)); }      // (all 64 bits: the high bytes must be dropped)
+};
+int test_pack() {
+    static const uint64_t ns[5] = {1, 1023, 1024, 1025, 3 * 1024 + 7};
+    static const uint32_t offs[3] = {0, 1, 20};
+    const size_t cap = 64 + 20 + (3 * 1024 + 7) * 8 + 64;
+    grl32::DBuf<uint8_t> d(cap);
+    if ((uintptr_t)d.p & 15) return -401;
+    std::vector<uint8_t> poison(cap, 0xC3), want, got(cap);
+    for (uint32_t rec = 1; rec <= 8; rec++)
+        for (uint64_t n : ns)
+            for (uint32_t off : offs) {
+                const uint64_t salt = rec * 1000003ull + n * 31 + off;
+                const size_t used = 64 + off + n * rec + 64;
+                prim::h2d(d.p, poison.data(), cap);
+                prim::pack_records(n, SelfPackFn{salt}, rec, d.p + 64 + off, "selftest.pack");
+                prim::d2h(got.data(), d.p, cap);
+                want = poison;
+                for (uint64_t i = 0; i < n; i++) {
+                    const uint64_t v = self_mix(salt ^ (i * 0x9E3779B97F4A7C15ull));
+                    for (uint32_t b = 0; b < rec; b++) want[64 + off + i * rec + b] = (uint8_t)(v >> (8 * b));
+                }
+                for (size_t x = 0; x < cap; x++)
+                    if (got[x] != want[x]) {
+                        const long at = (long)x - 64 - (long)off;
+                        fprintf(stderr, "[grlbwt] selftest pack_records: %u-byte records, n = %llu, output %u bytes behind a 16-byte boundary: byte %ld (%s) expected %02x, got %02x\n",
+                                rec, (unsigned long long)n, off, at, at < 0 ? "guard in front" : (x >= used - 64 ? "guard behind" : "record bytes"), want[x], got[x]);
+                        return at < 0 || x >= used - 64 ? -403 : -402;
+                    }
+            }
+    return 0;
+}
+
+// ---- 4: a functor over the set bits
+struct SelfBitFn {
+    uint64_t *out; uint32_t *hits;
+    GRL_DEV void operator()(uint64_t p, uint64_t ord) const { out[ord] = p; prim::atomic_add(&hits[ord], 1u); }
+};
+// span 0: through for_each_set_bit, which picks 4..64 words per wave from the vector's length and the device's size -- 4 for every
+// vector of the bounded sizes here; the longer spans are the kernel itself, launched the way for_each_set_bit does (device library only)
+template <class IDX>
+int test_set_bits_one(uint64_t nbits, int kind, uint64_t seed, uint32_t span = 0) {
+    static const char *kinds[5] = {"empty", "all ones", "one bit in three", "one bit in a thousand", "dense and empty stretches"};
+    const uint64_t nw = (nbits + 63) / 64;
+    std::vector<uint64_t> words(nw, 0), pos;
+    uint64_t s = seed;
+    for (uint64_t p = 0; p < nbits; p++) {
+        bool b = false;
+        if (kind == 1) b = true;
+        else if (kind == 2) b = sm64(s) % 3 == 0;
+        else if (kind == 3) b = sm64(s) % 1000 == 0;
+        else if (kind == 4) b = (p / 4096) % 2 == 0 && p % 4096 != 0;      // 63 bits, then full words: the ring holds 127 entries at every word
+        if (b) { words[p >> 6] |= 1ull << (p & 63); pos.push_back(p); }
+    }
+    std::vector<IDX> base(nw + 1);
+    uint64_t c = 0;
+    for (uint64_t w = 0; w < nw; w++) { base[w] = (IDX)c; c += (uint64_t)__builtin_popcountll(words[w]); }
+    base[nw] = (IDX)c;
+    const uint64_t cnt = pos.size(), cap = cnt + 64;
+    grl32::DBuf<uint64_t> dw, dout(cap);
+    grl32::DBuf<IDX> db;
+    grl32::DBuf<uint32_t> dhits(cap);
+    self_upload(dw, words); self_upload(db, base);
+    prim::dev_memset(dout.p, 0xA5, cap * 8); dhits.zero();
+    if (!span) prim::for_each_set_bit<IDX>(nbits, dw.p, db.p, SelfBitFn{dout.p, dhits.p}, "selftest.set_bits");
+#ifdef GRLBWT_PRIM_HIP
+    else {
+        const uint64_t waves = (nw + span - 1) / span;
+        hipLaunchKernelGGL((prim::k_for_each_set_bit<IDX, SelfBitFn>), dim3((unsigned)((waves + prim::kBlock / 64 - 1) / (prim::kBlock / 64))), dim3(prim::kBlock), 0,
+                           prim::rt().stream, nw, (const uint64_t *)dw.p, (const IDX *)db.p, span, SelfBitFn{dout.p, dhits.p});
+        prim::after_launch("selftest.set_bits");
+    }
+#endif
+    const std::vector<uint64_t> ho = dout.to_host(cap);
+    const std::vector<uint32_t> hh = dhits.to_host(cap);
+    for (uint64_t k = 0; k < cap; k++) {
+        const uint64_t want = k < cnt ? pos[k] : 0xA5A5A5A5A5A5A5A5ull;
+        const uint32_t wh = k < cnt ? 1u : 0u;
+        if (ho[k] != want || hh[k] != wh) {
+            fprintf(stderr, "[grlbwt] selftest for_each_set_bit: %d-byte ranks, %llu bits, %s, span %u: ordinal %llu of %llu expected position %llu (%u calls), got %llu (%u calls)\n",
+                    (int)sizeof(IDX), (unsigned long long)nbits, kinds[kind], span, (unsigned long long)k, (unsigned long long)cnt, (unsigned long long)want, wh, (unsigned long long)ho[k], hh[k]);
+            return k < cnt ? (ho[k] != want ? 1 : 2) : 3;
+        }
+    }
+    return 0;
+}
+int test_set_bits(uint64_t n, uint64_t seed) {
+    const uint64_t sizes[7] = {1, 64, 65, 4095, 4096, 4097, self_size(n)};
+    for (uint64_t nbits : sizes)
+        for (int kind = 0; kind < 5; kind++) {
+            if (int rc = test_set_bits_one<uint32_t>(nbits, kind, seed + kind)) return -(500 + rc);
+            if (int rc = test_set_bits_one<uint64_t>(nbits, kind, seed + 7 + kind)) return -(510 + rc);
+        }
+#ifdef GRLBWT_PRIM_HIP
+    for (uint32_t span = 8; span <= 64; span <<= 1)
+        for (int kind = 2; kind <= 4; kind += 2) {
+            if (int rc = test_set_bits_one<uint32_t>(sizes[6], kind, seed + 20 + kind, span)) return -(520 + rc);
+            if (int rc = test_set_bits_one<uint64_t>(sizes[5], kind, seed + 30 + kind, span)) return -(530 + rc);
+        }
+#endif
+    return 0;
+}
+
 int selftest(uint64_t n, uint64_t seed) {
     if (n < 2) n = 2;
     std::vector<uint32_t> h(n);
@@ -786,6 +1477,13 @@ int selftest(uint64_t n, uint64_t seed) {
     // 7: fused pair scans (8- and 16-byte elements: the 16-byte result stores and the LDS staging of the scan)
     { int r = test_pair_scan<uint32_t, uint32_t>(n, h, d.p); if (r) return -70 - r; }
     { int r = test_pair_scan<uint64_t, uint64_t>(n, h, d.p); if (r) return -80 - r; }
+    // 8-11: what only whole builds reached (sizes taken from n are capped: see self_size)
+    { int r = test_stream_merge(n, seed); if (r) return r; }
+#ifdef GRLBWT_PRIM_HIP
+    { int r = test_seg_sort_all(seed + 40); if (r) return r; }
+#endif
+    { int r = test_pack(); if (r) return r; }
+    { int r = test_set_bits(n, seed + 60); if (r) return r; }
     return 0;
 }
 
@@ -924,7 +1622,7 @@ int grlbwt_alphabet_compact_device(grlbwt_ctx *ctx, const void *dev_cells, uint6
                                    void *dev_values_u64, uint64_t capacity_values, uint64_t *n_distinct) {
     if (!ctx || !dev_cells || !dev_ranks_u32 || !dev_values_u64 || n_cells == 0 || !(cell_bytes == 4 || cell_bytes == 8)) return GRLBWT_EINVAL;
     return guarded(ctx, [&] {
-        const bool big = n_cells >= 0xFFFFFF00ull || (ctx->flags & GRLBWT_FLAG_FORCE_IDX64);
+        const bool big = n_cells >= kIdx32Limit || (ctx->flags & GRLBWT_FLAG_FORCE_IDX64);
         uint64_t k = big ? grl64::Engine::alphabet_compact_device(dev_cells, n_cells, cell_bytes, (uint32_t *)dev_ranks_u32, (uint64_t *)dev_values_u64, capacity_values)
                          : grl32::Engine::alphabet_compact_device(dev_cells, n_cells, cell_bytes, (uint32_t *)dev_ranks_u32, (uint64_t *)dev_values_u64, capacity_values);
         if (n_distinct) *n_distinct = k;
@@ -1073,7 +1771,7 @@ int grlbwt_invert_image_tails(grlbwt_ctx *ctx, const void *dev_image, uint64_t i
     if (!ctx || !dev_image || !dev_out || tail_cells == 0) return GRLBWT_EINVAL;
     return guarded(ctx, [&] {
         const uint64_t total = grl64::Engine::image_total_symbols(dev_image, image_bytes);
-        const bool big = total >= 0xFFFFFF00ull || (ctx->flags & GRLBWT_FLAG_FORCE_IDX64);
+        const bool big = total >= kIdx32Limit || (ctx->flags & GRLBWT_FLAG_FORCE_IDX64);
         uint64_t k = 0;
         const uint64_t n = big ? grl64::Engine::invert_image_tails(dev_image, image_bytes, cell_bytes, tail_cells, dev_out, capacity_cells, &k)
                                : grl32::Engine::invert_image_tails(dev_image, image_bytes, cell_bytes, tail_cells, dev_out, capacity_cells, &k);
@@ -1090,7 +1788,7 @@ int grlbwt_invert_image(grlbwt_ctx *ctx, const void *dev_image, uint64_t image_b
         // a small image can describe >= 2^32 symbols, and a 32-bit scan of its run lengths would wrap
         const uint64_t total = grl64::Engine::image_total_symbols(dev_image, image_bytes);
         if (total > capacity_cells) throw prim::Error(GRLBWT_EINVAL, "inversion: output buffer too small");
-        bool big = total >= 0xFFFFFF00ull || (ctx->flags & GRLBWT_FLAG_FORCE_IDX64);
+        bool big = total >= kIdx32Limit || (ctx->flags & GRLBWT_FLAG_FORCE_IDX64);
         uint64_t n = big ? grl64::Engine::invert_image(dev_image, image_bytes, cell_bytes, dev_text_out, capacity_cells, total)
                          : grl32::Engine::invert_image(dev_image, image_bytes, cell_bytes, dev_text_out, capacity_cells, total);
         if (n_cells_out) *n_cells_out = n;
@@ -1104,7 +1802,7 @@ int grlbwt_image_plain(grlbwt_ctx *ctx, const void *dev_image, uint64_t image_by
     return guarded(ctx, [&] {
         const uint64_t total = grl64::Engine::image_total_symbols(dev_image, image_bytes);
         if (total > capacity) throw prim::Error(GRLBWT_EINVAL, "grl2plain: output buffer too small");
-        bool big = total >= 0xFFFFFF00ull || (ctx->flags & GRLBWT_FLAG_FORCE_IDX64);
+        bool big = total >= kIdx32Limit || (ctx->flags & GRLBWT_FLAG_FORCE_IDX64);
         uint64_t n = big ? grl64::Engine::image_plain(dev_image, image_bytes, (uint8_t *)dev_out_u8, capacity, null_char)
                          : grl32::Engine::image_plain(dev_image, image_bytes, (uint8_t *)dev_out_u8, capacity, null_char);
         if (n_out) *n_out = n;
@@ -1136,7 +1834,7 @@ int grlbwt_image_split_runs(grlbwt_ctx *ctx, const void *dev_image, uint64_t ima
     if (!ctx || !dev_image || !dev_out) return GRLBWT_EINVAL;
     return guarded(ctx, [&] {
         const uint64_t total = grl64::Engine::image_total_symbols(dev_image, image_bytes);
-        bool big = total >= 0xFFFFFF00ull || (ctx->flags & GRLBWT_FLAG_FORCE_IDX64);
+        bool big = total >= kIdx32Limit || (ctx->flags & GRLBWT_FLAG_FORCE_IDX64);
         uint64_t v[6];
         if (big) {
             auto si = grl64::Engine::image_split_runs(dev_image, image_bytes, bits, block_size, (uint8_t *)dev_out, capacity_bytes);

@@ -3468,9 +3468,10 @@ inline u64 *lookback_scratch(size_t words) {
 // run index at a tile's start comes from the look-back.  osym / ostart must hold `out_cap` entries (an upper bound of the runs:
 // segments + runs of T).  Returns false when the walk gave up -- the queue of wide segments overflowed, or a tile waited too long
 // for another one -- and the caller takes stream_merge_count + stream_merge_emit; the plan then holds nothing.
+// `patience`: clock ticks a tile waits for another one (the self-test passes 0: tiles that find a word missing give up at once).
 template <class SEG, class IDX>
 inline bool stream_merge_onepass(u64 G, SEG seg, SmPlan<IDX> &plan, u32 *osym, IDX *ostart, u64 out_cap, u64 queue_cap, const char *name = "stream_merge",
-                                 bool mostly_plain = false) {
+                                 bool mostly_plain = false, u64 patience = sw().dev_lb_patience) {
     plan.release();
     plan = SmPlan<IDX>();
     plan.G = G;
@@ -3496,7 +3497,7 @@ inline bool stream_merge_onepass(u64 G, SEG seg, SmPlan<IDX> &plan, u32 *osym, I
     dev_memset(st, 0, (T + 2) * sizeof(u64));
     SmLb lbk;
     lbk.st_head = st; lbk.res = st + T;
-    lbk.patience = sw().dev_lb_patience;                // two seconds of the 100 MHz clock (development builds: tools/gpu_lookback_giveup.py makes the tiles give up)
+    lbk.patience = patience;                            // two seconds of the 100 MHz clock (development builds: tools/gpu_lookback_giveup.py makes the tiles give up)
     SmWide<IDX> *queue = (SmWide<IDX> *)dev_alloc((queue_cap ? queue_cap : 1) * sizeof(SmWide<IDX>));
     unsigned long long *wide = (unsigned long long *)(dres + 4);      // [1] atoms of the queued segments, [2] queue fill
     (void)out_cap;

@@ -474,7 +474,7 @@ inline void stream_merge_count(u64 G, SEG seg, SmPlan<IDX> &plan, const char * =
 // takes count + emit (GRLBWT_SIM_ONEPASS_GIVES_UP: the tests take that branch)
 static constexpr u32 kSmInline = 8;
 template <class SEG, class IDX>
-inline bool stream_merge_onepass(u64 G, SEG seg, SmPlan<IDX> &plan, u32 *osym, IDX *ostart, u64 out_cap, u64 queue_cap, const char * = "", bool = false) {
+inline bool stream_merge_onepass(u64 G, SEG seg, SmPlan<IDX> &plan, u32 *osym, IDX *ostart, u64 out_cap, u64 queue_cap, const char * = "", bool = false, u64 /*patience*/ = 0) {
     plan = SmPlan<IDX>();
     plan.G = G;
     if (getenv("GRLBWT_SIM_ONEPASS_GIVES_UP")) return false;

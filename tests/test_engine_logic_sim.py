@@ -22,9 +22,10 @@ def sim():
     return simlib.sim_library()
 
 
-def test_primitives_selftest(sim):
+@pytest.mark.parametrize("n", [1, 1025, 2049, 30000])
+def test_primitives_selftest(sim, n):
     with engine.Context(0, 0, sim) as ctx:
-        assert ctx.selftest(30000, 5) == 0
+        assert ctx.selftest(n, 5) == 0
 
 
 def test_golden_table(sim, oracle_mod):
