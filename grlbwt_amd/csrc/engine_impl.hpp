@@ -2916,6 +2916,17 @@ struct UnpackRunsFn {     // (sym: sb bytes LE, len: fb bytes LE) records -> arr
         sym[i] = (u32)s; len[i] = (idx_t)l;
     }
 };
+struct NonEmptyIn {        // 1 for a record that holds symbols
+    const idx_t *len;
+    GRL_DEV idx_t operator()(u64 i) const { return len[i] != 0 ? (idx_t)1 : (idx_t)0; }
+};
+struct KeepRunsFn {        // compacting copy of the non-empty records (dst = scan of NonEmptyIn)
+    const u32 *sym; const idx_t *len; const idx_t *dst; u32 *osym; idx_t *olen;
+    GRL_DEV void operator()(u64 i) const {
+        const idx_t l = len[i];
+        if (l != 0) { const u64 o = dst[i]; osym[o] = sym[i]; olen[o] = l; }
+    }
+};
 struct ImageSymIn {        // run symbol straight from the packed records, all 64 bits of it
     const u8 *img; u32 sb, fb;
     GRL_DEV u64 operator()(u64 i) const {
@@ -2938,13 +2949,18 @@ struct ImageLenIn {        // run length straight from the packed records (64-bi
         return l;
     }
 };
-struct PlainRunsFn {      // scripts/grl2plain.cpp:30-45: one output byte per BWT position, (char)sym, optional null replacement
-    const u32 *rsym; const u64 *rw; const idx_t *rb; int null_char; u8 *out;
+// scripts/grl2plain.cpp:30-45: one output byte per BWT position, (char)sym, optional null replacement.  The replacement is
+// decided per RUN on all 64 bits of the symbol (a symbol of 2^32 is not the null character; its low byte is 0 all the same).
+struct PlainSymFn {
+    ImageSymIn in; int null_char; u32 *rsym;
     GRL_DEV void operator()(u64 i) const {
-        u32 sy = rsym[rank1(rw, rb, i + 1) - 1];
-        if (sy == 0 && null_char >= 0) sy = (u32)null_char;
-        out[i] = (u8)sy;
+        const u64 s = in(i);
+        rsym[i] = (s == 0 && null_char >= 0) ? (u32)null_char : (u32)(u8)s;
     }
+};
+struct PlainRunsFn {
+    const u32 *rsym; const u64 *rw; const idx_t *rb; u8 *out;
+    GRL_DEV void operator()(u64 i) const { out[i] = (u8)rsym[rank1(rw, rb, i + 1) - 1]; }
 };
 struct RleExportFn {      // scripts/grlbwt2rle.cpp:22-30: .syms as uint8, .len as uint32 (the reference's casts)
     const u32 *rsym; const idx_t *rlen; u8 *syms; u32 *lens;
@@ -2956,6 +2972,9 @@ struct RleExportFn {      // scripts/grlbwt2rle.cpp:22-30: .syms as uint8, .len 
 // reference arrives there with acc_block == block_size and emits `push_back(sym, 0)`, :87-90).  Each boundary in (0, n)
 // therefore costs exactly one extra record, so the first record of piece j of run i sits at
 //   (#pieces before it) + (#multiples of B in (0, start of the piece)).
+// An EMPTY input record is one piece and one output record wherever it lies: on a boundary it pays nothing (the next
+// non-empty piece starts there too and pays), so it must not write the extra record -- that slot belongs to its successor,
+// or lies behind the output when nothing follows.
 struct PieceCountFn {     // number of L-pieces of every run
     const idx_t *len; u64 L;
     GRL_DEV idx_t operator()(u64 i) const { u64 l = len[i]; return (idx_t)(l == 0 ? 1 : (l + L - 1) / L); }
@@ -2974,7 +2993,7 @@ struct SplitRunsFn {      // one lane per L-piece
         const u32 sy = rsym[i];
         u64 o = x + ((B && cur > 0) ? (cur - 1) / B : 0);
         if (B) {
-            if (cur > 0 && cur % B == 0) { osym[o] = sy; olen[o] = 0; o++; }
+            if (cur > 0 && cur % B == 0 && end > cur) { osym[o] = sy; olen[o] = 0; o++; }     // (an empty record is its own zero-length record)
             for (u64 nb = (cur / B + 1) * B; nb < end; nb += B) { osym[o] = sy; olen[o] = (idx_t)(nb - cur); o++; cur = nb; }
         }
         osym[o] = sy; olen[o] = (idx_t)(end - cur);
@@ -5637,12 +5656,29 @@ class Engine {
         prim::sync();
         return k;
     }
+    // A record of length zero contributes nothing (the reference's reader, bwt_io.h, just loops over the records; split_runs
+    // writes such records in front of a piece that starts on a block boundary).  The consumers that look a POSITION up find its
+    // run through one bit per run START, which an empty record would share with its successor -- every later position would
+    // read the symbol one record too early.  They drop the empty records first: flag scan + compacting copy, and nothing at
+    // all where the shortest record is not empty (every image the engine builds).  Returns the number of records kept.
+    static u64 drop_empty_runs(DBuf<u32> &rsym, DBuf<idx_t> &rlen, u64 R) {
+        if (R == 0 || prim::reduce_min<u64>(R, IdxIn64{rlen.p}, "image.min_run") != 0) return R;
+        DBuf<idx_t> dst(R + 1);
+        const u64 kept = (u64)prim::exclusive_scan<idx_t>(R, NonEmptyIn{rlen.p}, dst.p, true, "image.nonempty");
+        DBuf<u32> s2(kept);
+        DBuf<idx_t> l2(kept);
+        prim::for_each(R, KeepRunsFn{rsym.p, rlen.p, dst.p, s2.p, l2.p}, "image.drop_empty");
+        rsym = std::move(s2);
+        rlen = std::move(l2);
+        return kept;
+    }
     template <class cell_t>
     static u64 invert_t(const u8 *img, u64 R, u32 sb, u32 fb, cell_t *text_out, u64 capacity, const WideSyms &W) {
         DBuf<u32> rsym(R);
         DBuf<idx_t> rlen(R), rpos(R + 1);
         prim::for_each(R, UnpackRunsFn{img, sb, fb, rsym.p, rlen.p}, "inv.unpack");
         if (W.alpha.p) d2d_copy(rsym.p, W.ranks.p, R);
+        R = drop_empty_runs(rsym, rlen, R);
         u64 n = (u64)prim::exclusive_scan<idx_t>(R, IdxIn<idx_t>{rlen.p}, rpos.p, true, "inv.positions");
         if (n > capacity) throw prim::Error(-22, "inversion: output buffer too small");
         u32 sep = prim::reduce_min<u32>(R, PtrU32In{rsym.p}, "inv.sep");
@@ -5680,6 +5716,7 @@ class Engine {
         DBuf<idx_t> rlen(R), rpos(R + 1);
         prim::for_each(R, UnpackRunsFn{img, sb, fb, rsym.p, rlen.p}, "inv.unpack");
         if (W.alpha.p) d2d_copy(rsym.p, W.ranks.p, R);
+        R = drop_empty_runs(rsym, rlen, R);
         const u64 n = (u64)prim::exclusive_scan<idx_t>(R, IdxIn<idx_t>{rlen.p}, rpos.p, true, "inv.positions");
         if (!tail && n > capacity) throw prim::Error(-22, "inversion: output buffer too small");
         const u32 sep = prim::reduce_min<u32>(R, PtrU32In{rsym.p}, "inv.sep");
@@ -5889,11 +5926,13 @@ class Engine {
         DBuf<u32> rsym(h.R);
         DBuf<idx_t> rlen(h.R), rpos(h.R + 1);
         prim::for_each(h.R, UnpackRunsFn{(const u8 *)dev_image, (u32)h.sb, (u32)h.fb, rsym.p, rlen.p}, "plain.unpack");
-        u64 n = (u64)prim::exclusive_scan<idx_t>(h.R, IdxIn<idx_t>{rlen.p}, rpos.p, true, "plain.positions");
+        prim::for_each(h.R, PlainSymFn{ImageSymIn{(const u8 *)dev_image, (u32)h.sb, (u32)h.fb}, null_char, rsym.p}, "plain.bytes");
+        const u64 R = drop_empty_runs(rsym, rlen, h.R);
+        u64 n = (u64)prim::exclusive_scan<idx_t>(R, IdxIn<idx_t>{rlen.p}, rpos.p, true, "plain.positions");
         if (n > capacity) throw prim::Error(-22, "grl2plain: output buffer too small");
         RankBits rb;
-        build_rankbits(rb, rpos.p, h.R, n + 1, "plain.runbits");
-        prim::for_each(n, PlainRunsFn{rsym.p, rb.words.p, rb.base.p, null_char, dev_out}, "plain.expand");
+        build_rankbits(rb, rpos.p, R, n + 1, "plain.runbits");
+        prim::for_each(n, PlainRunsFn{rsym.p, rb.words.p, rb.base.p, dev_out}, "plain.expand");
         prim::sync();
         return n;
     }

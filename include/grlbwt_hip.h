@@ -223,7 +223,15 @@ int grlbwt_invert_image(grlbwt_ctx *ctx, const void *dev_image, uint64_t image_b
 int grlbwt_invert_image_tails(grlbwt_ctx *ctx, const void *dev_image, uint64_t image_bytes, int cell_bytes, uint64_t tail_cells,
                               void *dev_out, uint64_t capacity_cells, uint64_t *n_strings_out, uint64_t *n_cells_out);
 
-/* The other .rl_bwt consumers of the reference's scripts/ (SURVEY 8f-2), on an image in device memory:
+/* Accepted input of every consumer (grlbwt_invert_image and _tails above included): ANY well-formed image, not only
+ * what grlbwt_build writes -- header widths of 1..8 bytes each, records of length 0 (they contribute nothing, as in the
+ * reference's reader; grlbwt_image_split_runs writes such records itself), neighbouring records with the same symbol, run
+ * lengths and totals of 2^32 and more.  An image without any record (16 bytes) is legal for plain, rle and split_runs
+ * (no output symbols / runs; a 16-byte image); bwt_stats refuses it with GRLBWT_EINVAL.  The inverters need a BWT, i.e.
+ * at least the separators.  Symbols are read as 64 bits: a symbol of 2^32 is not the null character of grl2plain, and
+ * split_runs refuses symbols of 2^32 and more with GRLBWT_EINVAL.
+ *
+ * The other .rl_bwt consumers of the reference's scripts/ (SURVEY 8f-2), on an image in device memory:
  * grl2plain  (scripts/grl2plain.cpp:18-50): plain BWT, one byte per symbol ((char)sym); null_char >= 0 replaces
  *            symbol 0, -1 leaves it.
  * grlbwt2rle (scripts/grlbwt2rle.cpp:17-33): run symbols as uint8 and run lengths as uint32.
@@ -244,8 +252,9 @@ int grlbwt_image_stats_get(grlbwt_ctx *ctx, const void *dev_image, uint64_t imag
 /* split_runs (scripts/split_runs.cpp:44-125; its argv order is `file.rlbwt bits n output_file`): re-encode the image so
  * that no run is longer than 2^bits - 1 and, for block_size > 0, no run crosses a multiple of block_size; the output is
  * an .rl_bwt image with the input's symbol width and ceil(bits/8) length bytes, byte-identical to the reference's output
- * file -- including the zero-length record the reference emits in front of a piece that starts exactly on a block
- * boundary (:87-90).  block_size 0 = no partition (the reference asserts on it).  1 <= bits <= 63.
+ * file -- including the zero-length record the reference emits in front of a non-empty piece that starts exactly on a
+ * block boundary (:87-90); an empty input record stays one empty record wherever it lies.  block_size 0 = no partition
+ * (the reference asserts on it).  1 <= bits <= 63.
  * dev_out needs 16 + runs_after * (sb + ceil(bits/8)) bytes; runs_after = runs + overflow_splits + block_splits. */
 typedef struct grlbwt_split_info {
     uint64_t runs_before, runs_after;     /* "Number of runs before" / "Number of runs now" */
