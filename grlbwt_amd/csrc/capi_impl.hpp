@@ -20,12 +20,20 @@
 #include <vector>
 
 
+// an FM index (grlbwt_fm_create): one of the two index widths; its buffers come from the context's pool
+struct grlbwt_fm {
+    uint32_t flags = 0;
+    std::unique_ptr<grl32::Engine::FmIndex> f32;
+    std::unique_ptr<grl64::Engine::FmIndex> f64;
+};
+
 struct grlbwt_ctx {
     uint32_t flags = 0;
     int device = 0;
     std::unique_ptr<grl32::Engine> e32;
     std::unique_ptr<grl64::Engine> e64;
     std::string err;
+    std::vector<grlbwt_fm *> fms;      // the indexes still alive: released with the context
 };
 
 namespace {
@@ -1554,6 +1562,8 @@ int grlbwt_ctx_create(int device_id, uint32_t flags, grlbwt_ctx **out) {
 void grlbwt_ctx_destroy(grlbwt_ctx *ctx) {
     if (!ctx) return;
     try {
+        for (grlbwt_fm *fm : ctx->fms) delete fm;
+        ctx->fms.clear();
         ctx->e32.reset(); ctx->e64.reset(); prim::sync(); prim::pool_trim();
         if (--prim::rt().live_ctx <= 0) {      // process-wide debug settings and a borrowed stream end with the last context
             prim::rt().live_ctx = 0;
@@ -1795,6 +1805,62 @@ int grlbwt_invert_image(grlbwt_ctx *ctx, const void *dev_image, uint64_t image_b
     });
 }
 
+
+int grlbwt_fm_create(grlbwt_ctx *ctx, const void *dev_image, uint64_t image_bytes, uint32_t fm_flags, grlbwt_fm **out) {
+    if (!ctx || !dev_image || !out || (fm_flags & ~GRLBWT_FM_LOCATE)) return GRLBWT_EINVAL;
+    *out = nullptr;
+    return guarded(ctx, [&] {
+        const uint64_t total = grl64::Engine::image_total_symbols(dev_image, image_bytes);
+        const bool big = total >= kIdx32Limit || (ctx->flags & GRLBWT_FLAG_FORCE_IDX64);
+        const bool locate = fm_flags & GRLBWT_FM_LOCATE;
+        std::unique_ptr<grlbwt_fm> fm(new grlbwt_fm());
+        fm->flags = fm_flags;
+        if (big) {
+            fm->f64.reset(new grl64::Engine::FmIndex());
+            grl64::Engine::fm_create(dev_image, image_bytes, locate, prim::sw().fm_top_bits, *fm->f64);
+        } else {
+            fm->f32.reset(new grl32::Engine::FmIndex());
+            grl32::Engine::fm_create(dev_image, image_bytes, locate, prim::sw().fm_top_bits, *fm->f32);
+        }
+        ctx->fms.push_back(fm.get());
+        *out = fm.release();
+    });
+}
+int grlbwt_fm_destroy(grlbwt_ctx *ctx, grlbwt_fm *fm) {
+    if (!ctx) return GRLBWT_EINVAL;
+    if (!fm) return GRLBWT_OK;
+    auto it = std::find(ctx->fms.begin(), ctx->fms.end(), fm);
+    if (it == ctx->fms.end()) { ctx->err = "fm destroy: not an index of this context"; return GRLBWT_EINVAL; }
+    ctx->fms.erase(it);
+    return guarded(ctx, [&] { prim::sync(); delete fm; });
+}
+int grlbwt_fm_info_get(const grlbwt_fm *fm, grlbwt_fm_info *out) {
+    if (!fm || !out || !(fm->f32 || fm->f64)) return GRLBWT_EINVAL;
+    auto fill = [&](const auto &F, uint64_t idx_bytes) {
+        out->n_syms = F.n; out->n_runs = F.R; out->n_strings = F.k; out->sigma = F.sigma; out->separator = F.sepval;
+        out->idx_bytes = idx_bytes; out->index_bytes = F.bytes(); out->top_entries = F.top_entries; out->flags = fm->flags;
+    };
+    if (fm->f32) fill(*fm->f32, 4); else fill(*fm->f64, 8);
+    return GRLBWT_OK;
+}
+int grlbwt_fm_count(grlbwt_ctx *ctx, const grlbwt_fm *fm, const void *dev_cells, int cell_bytes, const uint64_t *dev_offsets,
+                    uint64_t n_patterns, uint64_t *dev_lo, uint64_t *dev_hi) {
+    if (!ctx || !fm || !(fm->f32 || fm->f64)) return GRLBWT_EINVAL;
+    if (n_patterns && (!dev_offsets || !dev_lo || !dev_hi)) return GRLBWT_EINVAL;
+    return guarded(ctx, [&] {
+        if (fm->f32) grl32::Engine::fm_count(*fm->f32, dev_cells, cell_bytes, dev_offsets, n_patterns, dev_lo, dev_hi);
+        else grl64::Engine::fm_count(*fm->f64, dev_cells, cell_bytes, dev_offsets, n_patterns, dev_lo, dev_hi);
+    });
+}
+int grlbwt_fm_locate(grlbwt_ctx *ctx, const grlbwt_fm *fm, const uint64_t *dev_rows, uint64_t n_rows, uint64_t max_steps,
+                     uint64_t *dev_string, uint64_t *dev_offset) {
+    if (!ctx || !fm || !(fm->f32 || fm->f64)) return GRLBWT_EINVAL;
+    if (n_rows && (!dev_rows || !dev_string || !dev_offset)) return GRLBWT_EINVAL;
+    return guarded(ctx, [&] {
+        if (fm->f32) grl32::Engine::fm_locate(*fm->f32, dev_rows, n_rows, max_steps, dev_string, dev_offset);
+        else grl64::Engine::fm_locate(*fm->f64, dev_rows, n_rows, max_steps, dev_string, dev_offset);
+    });
+}
 
 int grlbwt_image_plain(grlbwt_ctx *ctx, const void *dev_image, uint64_t image_bytes, void *dev_out_u8,
                        uint64_t capacity, int null_char, uint64_t *n_out) {

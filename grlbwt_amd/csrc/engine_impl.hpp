@@ -3124,6 +3124,154 @@ struct RunInvertTailFn {    // the last `tail` cells of string i (separator incl
     }
 };
 
+// ---- counting and locating patterns: one step past scripts/fm_index.h, which stops at lf().  RunRec answers LF for a row's OWN
+// symbol; a backward search needs rank_c(p), the number of c in BWT[0, p), for any c.  The runs in (symbol, position) order --
+// the order the sort above makes -- answer it by binary search: key[j] = (symbol, start) of the j-th run in that order,
+// slf[j] = symbols in the runs before it (slf[R] = n), so slf at the first run of c is C[c], the symbols smaller than c.
+template <int IB> struct FmKeyT;
+template <> struct FmKeyT<4> {                 // symbol << 32 | start: one word while positions have 32 bits
+    u64 v;
+    GRL_DEV static FmKeyT make(u32 sym, u64 start) { return FmKeyT{(u64)sym << 32 | start}; }
+    GRL_DEV u32 sym() const { return (u32)(v >> 32); }
+    GRL_DEV u64 start() const { return v & 0xFFFFFFFFull; }
+    GRL_DEV bool below(u32 c, u64 p) const { return v < ((u64)c << 32 | p); }       // sorts in front of (c, p)
+};
+template <> struct alignas(16) FmKeyT<8> {
+    u64 st, sy;
+    GRL_DEV static FmKeyT make(u32 sym, u64 start) { return FmKeyT{start, (u64)sym}; }
+    GRL_DEV u32 sym() const { return (u32)sy; }
+    GRL_DEV u64 start() const { return st; }
+    GRL_DEV bool below(u32 c, u64 p) const { return sy < (u64)c || (sy == (u64)c && st < p); }
+};
+typedef FmKeyT<sizeof(idx_t)> FmKey;
+struct FmKeyEmitFn {      // RunLfEmitFn that also keeps the sorted order itself (rec may be null: no walk wanted)
+    static constexpr bool kWaveEmit = false;
+    const idx_t *order; const idx_t *rpos; const u32 *rsym; RunRec *rec; FmKey *key; idx_t *slf;
+    GRL_DEV void operator()(u64 j, idx_t ex, idx_t) const {
+        const u64 k = order[j];
+        key[j] = FmKey::make(rsym[k], (u64)rpos[k]);
+        slf[j] = ex;
+        if (rec) {
+            RunRec r;
+            r.delta = (decltype(r.delta))(ex - rpos[k]);
+            r.sym = rsym[k];
+            rec[k] = r;
+        }
+    }
+};
+struct FmHeadIn {         // 1 where a sorted run has another symbol than the run in front of it: their number is sigma
+    const FmKey *key;
+    GRL_DEV u64 operator()(u64 j) const { return j == 0 || key[j].sym() != key[j - 1].sym() ? 1ull : 0ull; }
+};
+struct FmNoTop {          // the search without a top level (the LDS one: prim::LdsTop)
+    GRL_DEV void narrow(u32, u64, u64 &, u64 &) const {}
+};
+// ONE step of the backward search for symbol c: both ends of [lo, hi) go from a row p to C[c] + rank_c(p).  j = the keys below
+// (c, p); the run in front of it, when it is a run of c, is the last run of c that starts before p and holds min(p - start, length)
+// of the symbols counted; otherwise no run of c starts before p and the answer is slf[j] = C[c].  Each lower bound halves
+// [a, b] at most 64 times; hi's starts at lo's (hi >= lo).
+template <class TOP>
+GRL_DEV void fm_step(const FmKey *key, const idx_t *slf, u64 R, const TOP &top, u32 c, u64 &lo, u64 &hi) {
+    u64 from = 0;
+    auto end = [&](u64 p) {
+        u64 a = from, b = R;
+        top.narrow(c, p, a, b);
+        for (int it = 0; it < 64 && a < b; it++) { const u64 mid = (a + b) >> 1; if (key[mid].below(c, p)) a = mid + 1; else b = mid; }
+        const u64 j = from = a;
+        u64 r = (u64)slf[j];
+        if (j > 0) {
+            const FmKey q = key[j - 1];
+            if (q.sym() == c) { const u64 base = (u64)slf[j - 1], len = r - base, in = p - q.start(); r = base + (in < len ? in : len); }
+        }
+        return r;
+    };
+    lo = end(lo);
+    hi = end(hi);
+}
+// pattern i = cells [off[i], off[i + 1]) of w bytes each, read as values; their symbols are the values themselves or, for an
+// image with a compacted alphabet, the ranks among alpha[0, sigma).  A value that is no symbol empties the range.
+struct FmCountFn {
+    typedef FmKey Key;
+    const FmKey *key; const idx_t *slf; u64 R, n;
+    const u64 *alpha; u64 sigma;
+    const void *cells; int w; const u64 *off; u64 *lo, *hi;
+    GRL_HD const FmKey *keys() const { return key; }
+    GRL_HD u64 n_keys() const { return R; }
+    GRL_DEV u64 cell(u64 x) const {
+        switch (w) {
+            case 1: return (u64)((const u8 *)cells)[x];
+            case 2: return (u64)((const u16 *)cells)[x];
+            case 4: return (u64)((const u32 *)cells)[x];
+            default: return ((const u64 *)cells)[x];
+        }
+    }
+    GRL_DEV bool code(u64 v, u32 &c) const {
+        if (!alpha) { c = (u32)v; return (v >> 32) == 0; }
+        u64 a = 0, b = sigma;
+        for (int it = 0; it < 64 && a < b; it++) { const u64 mid = (a + b) >> 1; if (alpha[mid] < v) a = mid + 1; else b = mid; }
+        c = (u32)a;
+        return a < sigma && alpha[a] == v;
+    }
+    template <class TOP>
+    GRL_DEV void operator()(u64 i, const TOP &top) const {
+        u64 a = 0, b = n;
+        const u64 x0 = off[i];
+        for (u64 x = off[i + 1]; x > x0 && a < b; x--) {       // (at most the pattern's cells)
+            u32 c;
+            if (!code(cell(x - 1), c)) { b = a; break; }
+            fm_step(key, slf, R, top, c, a, b);
+        }
+        if (a >= b) a = b = 0;
+        lo[i] = a; hi[i] = b;
+    }
+};
+struct FmCountPlainFn {   // the same through prim::for_each, without a top level
+    FmCountFn f;
+    GRL_DEV void operator()(u64 i) const { f(i, FmNoTop{}); }
+};
+struct FmOffsetsBadIn {
+    const u64 *off;
+    GRL_DEV u64 operator()(u64 i) const { return off[i] > off[i + 1] ? 1ull : 0ull; }
+};
+struct FmSepMisuseIn {    // cell x0 + k: the number of its pattern when it holds the separator and is not the pattern's last cell, else ~0
+    FmCountFn f; u64 sepval, x0, np;
+    GRL_DEV u64 operator()(u64 k) const {
+        const u64 x = x0 + k;
+        if (f.cell(x) != sepval) return ~0ull;
+        const u64 i = upper_bound<u64>(f.off, np + 1, x) - 1;      // off[i] <= x < off[i + 1]: empty patterns are stepped over
+        return x + 1 == f.off[i + 1] ? ~0ull : i;
+    }
+};
+// sid: string i's walk (RunInvertLenFn's) ends at the row r that holds its separator; that separator is the LF(r)-th of the
+// BWT.  The LF map of any image is a permutation, so a walk from one of the first k rows comes back to one of them after at
+// most n steps; the bound is there for an index that is not what it should be.
+struct FmSidFn {
+    const RankCell *rc; const RunRec *rec; u32 sep; u64 n; idx_t *sid; u32 *bad;
+    GRL_DEV void operator()(u64 i) const {
+        idx_t row = (idx_t)i;
+        RunRec r = rec[run_of_row(rc, (u64)row)];
+        for (u64 s = 0; s < n && r.sym != sep; s++) { row = (idx_t)(row + (idx_t)r.delta); r = rec[run_of_row(rc, (u64)row)]; }
+        if (r.sym != sep) { prim::atomic_max(bad, 1u); return; }
+        sid[(u64)(idx_t)(row + (idx_t)r.delta)] = (idx_t)i;
+    }
+};
+struct FmRowBadIn {
+    const u64 *rows; u64 n;
+    GRL_DEV u64 operator()(u64 i) const { return rows[i] >= n ? 1ull : 0ull; }
+};
+struct FmLocateFn {       // row -> (string, offset): LF steps until the row's symbol is the separator, at most `lim` of them
+    const RankCell *rc; const RunRec *rec; const idx_t *sid; u32 sep; u64 lim; const u64 *rows; u64 *str, *ofs;
+    GRL_DEV void operator()(u64 i) const {
+        idx_t row = (idx_t)rows[i];
+        u64 s = 0;
+        RunRec r = rec[run_of_row(rc, (u64)row)];
+        for (; s < lim && r.sym != sep; s++) { row = (idx_t)(row + (idx_t)r.delta); r = rec[run_of_row(rc, (u64)row)]; }
+        const bool found = r.sym == sep;
+        str[i] = found ? (u64)sid[(u64)(idx_t)(row + (idx_t)r.delta)] : ~0ull;
+        ofs[i] = found ? s : ~0ull;
+    }
+};
+
 // =========================================================================
 struct RoundInfo {
     u64 n_in = 0, D = 0, S = 0, M = 0, parse_size = 0, sigma = 0, max_phrase_len = 0, sort_iters = 0, table_retries = 0;
@@ -5710,42 +5858,70 @@ class Engine {
     template <class T>
     static void d2d_copy(T *dst, const T *src, u64 n) { prim::d2d(dst, src, n * sizeof(T)); }
     // the run-indexed form (functor block "the same inversion indexed by RUNS")
-    template <class cell_t>
-    static u64 invert_runs_t(const u8 *img, u64 R, u32 sb, u32 fb, cell_t *text_out, u64 capacity, const WideSyms &W, u64 tail = 0, u64 *n_strings_out = nullptr) {
-        DBuf<u32> rsym(R);
-        DBuf<idx_t> rlen(R), rpos(R + 1);
-        prim::for_each(R, UnpackRunsFn{img, sb, fb, rsym.p, rlen.p}, "inv.unpack");
-        if (W.alpha.p) d2d_copy(rsym.p, W.ranks.p, R);
-        R = drop_empty_runs(rsym, rlen, R);
-        const u64 n = (u64)prim::exclusive_scan<idx_t>(R, IdxIn<idx_t>{rlen.p}, rpos.p, true, "inv.positions");
-        if (!tail && n > capacity) throw prim::Error(-22, "inversion: output buffer too small");
-        const u32 sep = prim::reduce_min<u32>(R, PtrU32In{rsym.p}, "inv.sep");
-        const u32 mx = prim::reduce_max<u32>(R, PtrU32In{rsym.p}, "inv.max");
-        const u64 k = prim::reduce_sum<u64>(R, SepLenIn{rsym.p, rlen.p, sep}, "inv.nstrings");      // strings = separators
-        // run-start bit-vector with the rank of every word beside it
+    // The runs of an image as the inverter and the FM index need them.  run_index_load: the non-empty records as arrays, their
+    // start positions, the separator and the number of strings.  run_index_lf: the runs in (symbol, position) order and the scan
+    // of their lengths in that order -- LF of every run start -- kept in one or both of two forms, after which the arrays go:
+    //   walk    rc + rec: the run-start bit-vector with ranks and (LF(start) - start, symbol) per run: LF of any row of the BWT
+    //   search  key + slf: (symbol, start) and the scan itself in sorted order: the rank of ANY symbol in front of any row
+    struct RunIndex {
+        u64 R = 0, n = 0, k = 0;
+        u32 sep = 0, mx = 0;
+        DBuf<u32> rsym;
+        DBuf<idx_t> rlen, rpos;
         DBuf<RankCell> rc;
-        {
+        DBuf<RunRec> rec;
+        DBuf<FmKey> key;
+        DBuf<idx_t> slf;
+    };
+    static void run_index_load(const u8 *img, u64 R, u32 sb, u32 fb, const WideSyms &W, RunIndex &X) {
+        X.rsym.alloc(R); X.rlen.alloc(R);
+        prim::for_each(R, UnpackRunsFn{img, sb, fb, X.rsym.p, X.rlen.p}, "inv.unpack");
+        if (W.alpha.p) d2d_copy(X.rsym.p, W.ranks.p, R);
+        X.R = R = drop_empty_runs(X.rsym, X.rlen, R);
+        X.rpos.alloc(R + 1);
+        X.n = (u64)prim::exclusive_scan<idx_t>(R, IdxIn<idx_t>{X.rlen.p}, X.rpos.p, true, "inv.positions");
+        X.sep = prim::reduce_min<u32>(R, PtrU32In{X.rsym.p}, "inv.sep");
+        X.mx = prim::reduce_max<u32>(R, PtrU32In{X.rsym.p}, "inv.max");
+        X.k = prim::reduce_sum<u64>(R, SepLenIn{X.rsym.p, X.rlen.p, X.sep}, "inv.nstrings");      // strings = separators
+    }
+    static void run_index_lf(RunIndex &X, bool walk, bool search) {
+        const u64 R = X.R, n = X.n;
+        if (walk) {      // run-start bit-vector with the rank of every word beside it
             RankBits rb;
-            build_rankbits(rb, rpos.p, R, n + 1, "inv.runbits");
+            build_rankbits(rb, X.rpos.p, R, n + 1, "inv.runbits");
             const u64 nw = (n + 1) / 64 + 2;
-            rc.alloc(nw);
-            prim::for_each(nw, RankCellFn{rb.words.p, rb.base.p, rc.p}, "inv.rankcells");
+            X.rc.alloc(nw);
+            prim::for_each(nw, RankCellFn{rb.words.p, rb.base.p, X.rc.p}, "inv.rankcells");
+            X.rec.alloc(R);
         }
-        // LF of every run start: runs in (symbol, position) order, scan of their lengths
-        DBuf<RunRec> rec(R);
+        if (search) { X.key.alloc(R); X.slf.alloc(R + 1); }
         {
             DBuf<u32> k2(R), k3(R);
             DBuf<idx_t> ia(R), ib(R);
-            d2d_copy(k2.p, rsym.p, R);
+            d2d_copy(k2.p, X.rsym.p, R);
             prim::for_each(R, IotaFn{ia.p}, "inv.iota");
-            int bits = (int)bitlen64(mx);
+            int bits = (int)bitlen64(X.mx);
             if (bits < 1) bits = 1;
             const int res = prim::sort_pairs<u32, idx_t>(k2.p, ia.p, k3.p, ib.p, R, 0, bits, "inv.lf_sort");
             const idx_t *order = res ? ib.p : ia.p;
-            const u64 tot = (u64)prim::exclusive_scan_emit<idx_t>(R, RunOrderLenIn{rlen.p, order}, RunLfEmitFn{order, rpos.p, rsym.p, rec.p}, "inv.lf");
+            const u64 tot = search ? (u64)prim::exclusive_scan_emit<idx_t>(R, RunOrderLenIn{X.rlen.p, order}, FmKeyEmitFn{order, X.rpos.p, X.rsym.p, X.rec.p, X.key.p, X.slf.p}, "fm.keys")
+                                   : (u64)prim::exclusive_scan_emit<idx_t>(R, RunOrderLenIn{X.rlen.p, order}, RunLfEmitFn{order, X.rpos.p, X.rsym.p, X.rec.p}, "inv.lf");
             if (tot != n) throw prim::Error(-71, "inversion: run lengths do not add up");
         }
-        rsym.release(); rlen.release(); rpos.release();
+        if (search) { const idx_t total = (idx_t)n; prim::h2d(X.slf.p + R, &total, sizeof(total)); }
+        X.rsym.release(); X.rlen.release(); X.rpos.release();
+    }
+    template <class cell_t>
+    static u64 invert_runs_t(const u8 *img, u64 R, u32 sb, u32 fb, cell_t *text_out, u64 capacity, const WideSyms &W, u64 tail = 0, u64 *n_strings_out = nullptr) {
+        RunIndex X;
+        run_index_load(img, R, sb, fb, W, X);
+        const u64 n = X.n;
+        if (!tail && n > capacity) throw prim::Error(-22, "inversion: output buffer too small");
+        run_index_lf(X, true, false);
+        const u64 k = X.k;
+        const u32 sep = X.sep;
+        DBuf<RankCell> &rc = X.rc;
+        DBuf<RunRec> &rec = X.rec;
         if (tail) {
             // the ends of the strings only (collections whose strings are too long to walk in a test's time -- 100
             // strings of 249 M cells are 249 M dependent steps each): `tail` LF steps per string from its terminator's row
@@ -5819,6 +5995,88 @@ class Engine {
             case 8: return invert_t<u64>(img, R, (u32)sb, (u32)fb, (u64 *)dev_text_out, capacity_cells, W);
             default: throw prim::Error(-22, "bad cell width");
         }
+    }
+
+    // ---- the FM index over the runs of an image (grlbwt_fm_*; functor block "counting and locating patterns") ----------------
+    struct FmIndex {
+        u64 n = 0, R = 0, k = 0, sigma = 0, sepval = 0;
+        u32 sep = 0, top_entries = 0;
+        bool locate = false;
+        DBuf<FmKey> key;
+        DBuf<idx_t> slf;
+        DBuf<u64> alpha;          // the values of a compacted alphabet (null: the symbols are the values)
+        DBuf<RankCell> rc;        // locate: LF of any row (run_of_row + rec) and the string behind every separator
+        DBuf<RunRec> rec;
+        DBuf<idx_t> sid;
+        u64 bytes() const {
+            return key.n * sizeof(FmKey) + slf.n * sizeof(idx_t) + alpha.n * 8 + rc.n * sizeof(RankCell) + rec.n * sizeof(RunRec) + sid.n * sizeof(idx_t);
+        }
+    };
+    // What the locate structures may take while they are made: half of the free device memory (a quarter byte per symbol for the
+    // bit-vector and its ranks, a word per string).  The serial stand-in, which walks the strings one after the other, stops at 256 MB.
+    static u64 fm_locate_budget() { return prim::kIsDevice ? prim::mem_available() / 2 : (u64)1 << 28; }
+    static void fm_create(const void *dev_image, u64 image_bytes, bool locate, int top_bits, FmIndex &F) {
+        const ImageHeader h = image_header(dev_image, image_bytes);
+        if (h.R == 0) throw prim::Error(-22, "fm index: the image has no record");
+        if (top_bits < 0 || top_bits > 12) throw prim::Error(-22, "fm index: the top level takes 0 to 12 bits");
+        const u8 *img = (const u8 *)dev_image;
+        WideSyms W;
+        image_symbols(img, h.R, (u32)h.sb, (u32)h.fb, 8, W);
+        RunIndex X;
+        run_index_load(img, h.R, (u32)h.sb, (u32)h.fb, W, X);
+        W.ranks.release();
+        F.n = X.n; F.R = X.R; F.k = X.k; F.sep = X.sep; F.locate = locate;
+        if (locate) {
+            const u64 words = (X.n + 1) / 64 + 2;
+            const u64 need = words * (sizeof(RankCell) + 8 + sizeof(idx_t)) + X.R * sizeof(RunRec) + X.k * sizeof(idx_t);
+            if (X.n >= ((u64)1 << 62) || need > fm_locate_budget())
+                throw prim::Error(-22, "fm index: the structures for locating (" + std::to_string(need) + " bytes) are more than this device can hold");
+        }
+        run_index_lf(X, locate && X.R, true);
+        F.key = std::move(X.key); F.slf = std::move(X.slf); F.rc = std::move(X.rc); F.rec = std::move(X.rec);
+        F.alpha = std::move(W.alpha);
+        F.sigma = prim::reduce_sum<u64>(F.R, FmHeadIn{F.key.p}, "fm.sigma");
+        if (F.R) F.sepval = F.alpha.p ? F.alpha.get(F.sep) : (u64)F.sep;
+#ifdef GRLBWT_PRIM_HIP
+        F.top_entries = prim::top_search_entries(top_bits, F.R, sizeof(FmKey));
+#endif
+        if (locate && F.R) {
+            DBuf<u32> bad(1);
+            bad.zero();
+            F.sid.alloc(F.k);
+            prim::for_each(F.k, FmSidFn{F.rc.p, F.rec.p, F.sep, F.n, F.sid.p, bad.p}, "fm.sid");
+            if (bad.get(0)) throw prim::Error(-22, "fm index: a string's walk met no separator in n steps: not the BWT of a collection");
+        }
+        prim::sync();
+    }
+    static void fm_count(const FmIndex &F, const void *cells, int w, const u64 *off, u64 np, u64 *lo, u64 *hi) {
+        if (!(w == 1 || w == 2 || w == 4 || w == 8)) throw prim::Error(-22, "fm count: bad cell width");
+        if (np == 0) return;
+        if (prim::reduce_sum<u64>(np, FmOffsetsBadIn{off}, "fm.offsets")) throw prim::Error(-22, "fm count: the pattern offsets decrease");
+        u64 x0, x1;
+        prim::d2h(&x0, off, 8);
+        prim::d2h(&x1, off + np, 8);
+        if (x1 > x0 && !cells) throw prim::Error(-22, "fm count: no pattern cells");
+        const FmCountFn f{F.key.p, F.slf.p, F.R, F.n, F.alpha.p, F.alpha.n, cells, w, off, lo, hi};
+        if (F.R) {
+            // the separator ends a string: a pattern may END with it (the step from [0, n) gives [0, n_strings), the rows of
+            // the strings' ends) but the rows a further step would lead to are no range of a BCR BWT
+            const u64 bad = prim::reduce_min<u64>(x1 - x0, FmSepMisuseIn{f, F.sepval, x0, np}, "fm.separators");
+            if (bad != ~0ull) throw prim::Error(-22, "fm count: pattern " + std::to_string(bad) + " holds the separator in front of its last cell");
+        }
+#ifdef GRLBWT_PRIM_HIP
+        prim::top_search(np, f, F.top_entries, "fm.count");
+#else
+        prim::for_each(np, FmCountPlainFn{f}, "fm.count");
+#endif
+        prim::sync();
+    }
+    static void fm_locate(const FmIndex &F, const u64 *rows, u64 nr, u64 max_steps, u64 *str, u64 *ofs) {
+        if (!F.locate) throw prim::Error(-22, "fm locate: the index was made without the structures for locating");
+        if (nr == 0) return;
+        if (prim::reduce_sum<u64>(nr, FmRowBadIn{rows, F.n}, "fm.rows")) throw prim::Error(-22, "fm locate: a row is not below the number of symbols");
+        prim::for_each(nr, FmLocateFn{F.rc.p, F.rec.p, F.sid.p, F.sep, max_steps < F.n ? max_steps : F.n, rows, str, ofs}, "fm.locate");
+        prim::sync();
     }
 
     // ---- the other .rl_bwt consumers of scripts/ (SURVEY 8f-2), on an image in device memory --------------

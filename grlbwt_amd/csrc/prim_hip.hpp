@@ -3715,4 +3715,73 @@ inline void ac_rank(const cell_t *t, u64 n, AcPlan &P, int key_bits, u64 *values
     }
 }
 
+// ------------------------------------------------------------------ searches under a top level in LDS
+// f(i, top) for every i in [0, n): one lane per item, each item a chain of lower bounds over ONE sorted array of f.n_keys()
+// keys (F::Key, with below(c, p): the key sorts in front of (c, p)).  The first levels of every such search read the same few
+// keys, so each workgroup first copies every stride-th key -- top_n of them, top_n * stride >= n_keys -- into LDS;
+// top.narrow() then cuts a search's interval to one stride with LDS reads and the rest gathers from HBM.  top_n = 0: no copy,
+// narrow() leaves the interval alone.
+//   LDS: 8-byte keys 32 KB, 16-byte keys 64 KB at top_n = 4096; more than 64 KB per workgroup needs the dynamic form (the
+//     static limit is 64 KB) and is checked against rt().lds_bytes.  A CU has 160 KiB: two workgroups at 64 KB.  The
+//     workgroup is therefore 1024 threads (16 waves): two of them fill a CU's 32 wave slots, and at 256 threads the same
+//     LDS would leave it at 8 waves, which is what an HBM gather chain cannot afford.
+//   Banks: the lanes of a wave read unrelated keys after the first few levels (those are one address: a broadcast).
+//     ds_read_b64 is served per 32-lane half over 64 banks, so 32 random 8-byte reads collide about as often as any
+//     gather would; no layout of a sorted array avoids that, and the HBM levels behind it cost a hundred times more.
+//   Loops: a grid-stride loop over the items, the copy loop (top_n / kTopThreads rounds), narrow() at most 13 rounds.
+static constexpr int kTopThreads = 1024;
+static constexpr u32 kTopMaxBits = 12;
+template <class KEY>
+struct LdsTop {
+    const KEY *s; u32 n; u64 stride, n_keys;
+    // the lower bound of (c, p) lies in [a, b] on entry and on return
+    GRL_DEV void narrow(u32 c, u64 p, u64 &a, u64 &b) const {
+        if (n == 0) return;
+        u32 x = 0, y = n;
+        for (u32 it = 0; it <= kTopMaxBits && x < y; it++) { const u32 mid = (x + y) >> 1; if (s[mid].below(c, p)) x = mid + 1; else y = mid; }
+        // x samples are below: key[(x - 1) * stride] is, key[x * stride] is not
+        const u64 a2 = x ? (u64)(x - 1) * stride + 1 : 0, b2 = x < n ? (u64)x * stride : n_keys;
+        if (a2 > a) a = a2;
+        if (b2 < b) b = b2;
+    }
+};
+template <class F>
+__global__ void __launch_bounds__(kTopThreads) k_top_search(u64 n, F f, u32 top_n, u64 stride) {
+    typedef typename F::Key Key;
+    extern __shared__ __attribute__((aligned(16))) u64 s_top[];
+    Key *s = reinterpret_cast<Key *>(s_top);
+    const Key *keys = f.keys();
+    for (u32 t = threadIdx.x; t < top_n; t += kTopThreads) s[t] = keys[(u64)t * stride];
+    __syncthreads();
+    const LdsTop<Key> top{s, top_n, stride, f.n_keys()};
+    const u64 step = (u64)gridDim.x * kTopThreads;
+    for (u64 i = (u64)blockIdx.x * kTopThreads + threadIdx.x; i < n; i += step) f(i, top);
+}
+// top_entries: what top_search_entries() answered for this key array
+template <class F>
+inline void top_search(u64 n, F f, u32 top_entries, const char *name = "top_search") {
+    if (n == 0) return;
+    const u64 R = f.n_keys();
+    const u64 stride = top_entries ? (R + top_entries - 1) / top_entries : 1;
+    const u32 top_n = top_entries ? (u32)((R + stride - 1) / stride) : 0;
+    const size_t lds = (size_t)top_n * sizeof(typename F::Key);
+    if (lds > rt().lds_bytes) throw Error(-71, std::string(name) + ": the top level does not fit the LDS");
+    int occ = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_top_search<F>, kTopThreads, lds) != hipSuccess || occ < 1) { (void)hipGetLastError(); occ = 1; }
+    u64 blocks = (n + kTopThreads - 1) / kTopThreads;
+    const u64 cap = (u64)rt().num_cus * (u64)occ;       // what the CUs hold at once: every workgroup pays for its copy of the top level
+    if (blocks > cap) blocks = cap;
+    prof_begin(name);
+    hipLaunchKernelGGL((k_top_search<F>), dim3((unsigned)blocks), dim3(kTopThreads), lds, rt().stream, n, f, top_n, stride);
+    prof_end();
+    after_launch(name);
+}
+// entries of a top level of 2^bits keys over n_keys keys of key_bytes each (0: none)
+inline u32 top_search_entries(int bits, u64 n_keys, size_t key_bytes) {
+    if (bits <= 0 || n_keys == 0) return 0;
+    u32 b = bits > (int)kTopMaxBits ? kTopMaxBits : (u32)bits;
+    while (b > 0 && ((size_t)key_bytes << b) > rt().lds_bytes) b--;
+    return b ? (u32)1 << b : 0;
+}
+
 }   // namespace prim

@@ -39,6 +39,7 @@
     X(GRLBWT_INVERT, invert, char, 0, "r[uns] | p[ositions]: the form of the inversion (unset: by the memory it needs)")         \
     X(GRLBWT_XS_MAXC, xs_maxc, int, 32, "most cells per item the fused expansion sort takes (lower: the unfused branch)")        \
     X(GRLBWT_ALPHA_TABLE_BITS, alpha_table_bits, int, 20, "log2 of the slots of the alphabet compaction's table, 2..26 (lower: the sorting regime)") \
+    X(GRLBWT_FM_TOP_BITS, fm_top_bits, int, 12, "log2 of the keys of an FM index's search array kept in LDS, 0..12 (0: none; lower: small indexes search HBM)") \
     X(GRLBWT_IO_THREADS, io_threads, int, 0, "reader / writer threads per file chunk, 1..64 (0: from the host's cores)")         \
     X(GRLBWT_QUIET_ENV, quiet_env, bool, false, "no note on stderr about the switches set in the environment")
 

@@ -33,7 +33,16 @@ ABI_SYMBOLS = [
     "grlbwt_image_plain", "grlbwt_image_rle", "grlbwt_image_stats_get", "grlbwt_image_split_runs",
     "grlbwt_level_grammar_size", "grlbwt_level_grammar_download",
     "grlbwt_alphabet_size", "grlbwt_alphabet_download", "grlbwt_alphabet_compact_device",
+    "grlbwt_fm_create", "grlbwt_fm_destroy", "grlbwt_fm_info_get", "grlbwt_fm_count", "grlbwt_fm_locate",
 ]
+
+FM_LOCATE = 1
+UINT64_MAX = 2 ** 64 - 1
+
+
+class FmInfo(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("n_syms", "n_runs", "n_strings", "sigma", "separator", "idx_bytes", "index_bytes",
+                                          "top_entries", "flags")]
 
 
 class ImageStats(C.Structure):
@@ -178,6 +187,11 @@ def load_library(path=None, allow_test_standin=False):
     L.grlbwt_alphabet_size.argtypes = [vp, C.POINTER(u64)]
     L.grlbwt_alphabet_download.argtypes = [vp, vp]
     L.grlbwt_alphabet_compact_device.argtypes = [vp, vp, u64, i32, vp, vp, u64, C.POINTER(u64)]
+    L.grlbwt_fm_create.argtypes = [vp, vp, u64, C.c_uint32, C.POINTER(vp)]
+    L.grlbwt_fm_destroy.argtypes = [vp, vp]
+    L.grlbwt_fm_info_get.argtypes = [vp, C.POINTER(FmInfo)]
+    L.grlbwt_fm_count.argtypes = [vp, vp, vp, i32, vp, u64, vp, vp]
+    L.grlbwt_fm_locate.argtypes = [vp, vp, vp, u64, u64, vp, vp]
     L.grlbwt_profile_enable.argtypes = [vp, i32]
     L.grlbwt_profile_dump.argtypes = [vp, C.c_char_p, u64]
     _libs[path] = L
@@ -452,6 +466,51 @@ class Context:
 
     def selftest(self, n=100000, seed=1):
         return self.L.grlbwt_selftest(self._h, n, seed)
+
+
+class FmIndex:
+    """Count and locate patterns in an .rl_bwt image (grlbwt_fm_*): an index made from an image in device memory, which may
+    be freed afterwards.  All pointers are device pointers; locate=True also builds what locate() needs."""
+
+    def __init__(self, ctx, dev_image_ptr, image_bytes, locate=False):
+        self.ctx = ctx
+        h = C.c_void_p()
+        ctx._ck(ctx.L.grlbwt_fm_create(ctx._h, C.c_void_p(dev_image_ptr), image_bytes, FM_LOCATE if locate else 0, C.byref(h)))
+        self._h = h
+
+    def info(self):
+        out = FmInfo()
+        rc = self.ctx.L.grlbwt_fm_info_get(self._h, C.byref(out))
+        if rc != OK:
+            raise GrlbwtError(rc, self.ctx.L.grlbwt_strerror(rc).decode())
+        return _as_dict(out)
+
+    def count(self, cells_ptr, cell_bytes, offsets_ptr, n, lo_ptr, hi_ptr):
+        """Rows [lo[i], hi[i]) of the BWT whose suffixes start with pattern i = cells [offsets[i], offsets[i + 1])."""
+        self.ctx._ck(self.ctx.L.grlbwt_fm_count(self.ctx._h, self._h, C.c_void_p(cells_ptr), cell_bytes, C.c_void_p(offsets_ptr), n,
+                                                C.c_void_p(lo_ptr), C.c_void_p(hi_ptr)))
+
+    def locate(self, rows_ptr, n_rows, max_steps, string_ptr, offset_ptr):
+        """(string, offset) of every row; UINT64_MAX in both where the offset is above max_steps."""
+        self.ctx._ck(self.ctx.L.grlbwt_fm_locate(self.ctx._h, self._h, C.c_void_p(rows_ptr), n_rows, max_steps,
+                                                 C.c_void_p(string_ptr), C.c_void_p(offset_ptr)))
+
+    def close(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h and getattr(self.ctx, "_h", None):       # (a closed context has released its indexes)
+            self.ctx._ck(self.ctx.L.grlbwt_fm_destroy(self.ctx._h, h))
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def grl_bwt_algo(data, cell_bytes=1, device=0, flags=0, lib=None):

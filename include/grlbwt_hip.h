@@ -265,6 +265,52 @@ typedef struct grlbwt_split_info {
 int grlbwt_image_split_runs(grlbwt_ctx *ctx, const void *dev_image, uint64_t image_bytes, int bits, uint64_t block_size,
                             void *dev_out, uint64_t capacity_bytes, grlbwt_split_info *info);
 
+/* ---- counting and locating patterns in an image: one step past the reference's scripts/fm_index.h, which stops at lf().
+ * grlbwt_fm_create makes an index from ANY well-formed image in device memory (see "Accepted input" above; an image without a
+ * record is refused with GRLBWT_EINVAL).  The index copies what it needs -- the image may be freed when the call returns --
+ * into buffers of the context's pool: two words per non-empty record, (symbol, start position) in (symbol, position) order
+ * and the symbols in front of it in that order (8 + 4 bytes while the image describes fewer than 2^32 - 256 symbols, 16 + 8
+ * from there on or with GRLBWT_FLAG_FORCE_IDX64).  grlbwt_fm_destroy releases it; grlbwt_ctx_destroy releases every index
+ * still alive, whose handles are dead from then on.
+ *
+ * grlbwt_fm_count: n_patterns patterns, pattern i = cells [dev_offsets[i], dev_offsets[i + 1]) of dev_cells (cell_bytes in
+ * {1, 2, 4, 8}, whatever the image's symbol width; n_patterns + 1 non-decreasing offsets).  [dev_lo[i], dev_hi[i]) are the
+ * rows of the BWT whose suffixes start with the pattern -- hi - lo occurrences; lo = hi = 0 when there is none, [0, n_syms)
+ * for a pattern without cells.  A cell that is no symbol of the image (a value too wide for it included) matches nothing.
+ * THE SEPARATOR (the image's smallest symbol) may be a pattern's LAST cell only: there it anchors the match at the end of a
+ * string.  In a BCR BWT the suffix that starts at a separator is that separator alone, ordered by the string's number, so
+ * the rows of "separator, then X" are no range; a pattern with the separator anywhere else fails the WHOLE call with
+ * GRLBWT_EINVAL (the message names the first such pattern; nothing is written).  One lane per pattern, a binary search over
+ * the records per cell and range end; the first GRLBWT_FM_TOP_BITS (environment, 0..12, read by grlbwt_fm_create) levels
+ * of every search are read from a copy in LDS.
+ *
+ * grlbwt_fm_locate (needs GRLBWT_FM_LOCATE): for every row of dev_rows (each < n_syms, else GRLBWT_EINVAL) the string, by
+ * its number in input order, and the offset inside it at which the row's suffix starts.  COST: one dependent LF step per
+ * cell between the occurrence and the START of its string -- the per-string cost model of grlbwt_invert_image_tails: meant
+ * for read-like collections (strings of a few hundred cells), not for a collection of chromosomes.  The walk of a row stops
+ * after min(max_steps, n_syms) steps (UINT64_MAX: no cap of the caller's): an occurrence at offset o is resolved exactly when
+ * o <= max_steps, an unresolved row gets UINT64_MAX in both outputs.
+ * GRLBWT_FM_LOCATE adds to the index the run-start bit-vector with its ranks (a quarter byte per symbol), one LF record
+ * per run and one word per string -- the number of the string behind every separator of the BWT, found by one walk over
+ * every string when the index is made (the separators of a BCR BWT are ordered by the strings' contents, not by their
+ * numbers).  An image whose walks do not end (not the BWT of a collection), or whose structures would take more than half
+ * of the free device memory, is refused with GRLBWT_EINVAL when this flag is given, and accepted without it. */
+typedef struct grlbwt_fm grlbwt_fm;
+#define GRLBWT_FM_LOCATE 1u      /* also build what grlbwt_fm_locate needs (one LF walk over every string, like the inverter's length pass) */
+typedef struct grlbwt_fm_info {
+    uint64_t n_syms, n_runs, n_strings;   /* symbols described, records kept (non-empty), occurrences of the separator */
+    uint64_t sigma, separator;            /* distinct symbols, value of the smallest one */
+    uint64_t idx_bytes, index_bytes;      /* 4 or 8; device bytes the index holds */
+    uint64_t top_entries, flags;          /* entries of the LDS top level (0: none), fm_flags as given */
+} grlbwt_fm_info;
+int grlbwt_fm_create(grlbwt_ctx *ctx, const void *dev_image, uint64_t image_bytes, uint32_t fm_flags, grlbwt_fm **out);
+int grlbwt_fm_destroy(grlbwt_ctx *ctx, grlbwt_fm *fm);
+int grlbwt_fm_info_get(const grlbwt_fm *fm, grlbwt_fm_info *out);
+int grlbwt_fm_count(grlbwt_ctx *ctx, const grlbwt_fm *fm, const void *dev_cells, int cell_bytes, const uint64_t *dev_offsets,
+                    uint64_t n_patterns, uint64_t *dev_lo, uint64_t *dev_hi);
+int grlbwt_fm_locate(grlbwt_ctx *ctx, const grlbwt_fm *fm, const uint64_t *dev_rows, uint64_t n_rows, uint64_t max_steps,
+                     uint64_t *dev_string, uint64_t *dev_offset);
+
 /* ---- inspection (parity tests; need GRLBWT_FLAG_KEEP_LEVELS) --------------- */
 /* text of level >= 1 as (rank<<1 | rep) cells, the reference's on-disk parse format */
 int grlbwt_level_text_size(const grlbwt_ctx *ctx, int level, uint64_t *n_cells);
