@@ -1158,6 +1158,68 @@ int sm_one_walk(const SmScn &sc, const SmRef &R, const SmDevice<IDX> &D, bool mo
     plan.release();
     return rc;
 }
+// count + emit records (device library only): run k as the low 1 + fb bytes of (symbol | length << 8), the symbol as it is or through a
+// table; `out` at 0, 1, 5 and 15 bytes behind a 16-byte boundary, poisoned bytes on both sides.  (A length wider than fb bytes loses
+// its top on both sides of the comparison; the scenario with 2^33-symbol runs takes only the widths that hold them.)
+#ifdef GRLBWT_PRIM_HIP
+struct SelfRecFn {
+    const uint64_t *table;
+    GRL_DEV uint64_t operator()(uint32_t sym, uint64_t len) const { return (table ? table[sym & 3u] : (uint64_t)(sym & 0xFFu)) | (len << 8); }
+};
+template <class IDX>
+int sm_records(const SmScn &sc, const SmRef &R, const SmDevice<IDX> &D, bool mostly_plain) {
+    static const uint32_t kFb[3] = {1, 4, 7}, kOff[4] = {0, 1, 5, 15};
+    static const std::vector<uint64_t> kTable = {0x11, 0x22, 0x33, 0x44};
+    const int spt = mostly_plain ? 4 : 8;
+    const uint64_t heads = R.rsym.size(), guard = 48;
+    prim::SmPlan<IDX> plan;
+    grl32::DBuf<uint32_t> none32;
+    grl32::DBuf<IDX> none;
+    grl32::DBuf<uint64_t> table;
+    grl32::DBuf<uint8_t> buf;
+    self_upload(table, kTable);
+    int rc = 0;
+    try {
+        prim::stream_merge_count<SelfSeg<IDX>, IDX>(D.G, D.seg, plan, "selftest.sm", mostly_plain);
+        rc = sm_compare<IDX>(sc, R, spt, "count + emit records", plan, none32, none, false);
+        for (int f = 0; f < 3 && !rc; f++) {
+            const uint32_t fb = kFb[f], rec = 1 + fb;
+            if (sc.need_wide && fb < 5) continue;
+            for (int tab = 0; tab < 2 && !rc; tab++)
+                for (int o = 0; o < 4 && !rc; o++) {
+                    const uint64_t bytes = heads * rec, cap = 16 + guard + bytes + guard;
+                    buf.alloc(cap);
+                    prim::dev_memset(buf.p, kSmPoison, cap);
+                    const uint64_t at = (16 - ((uintptr_t)buf.p & 15)) % 16 + 16 + kOff[o];      // (>= 16 poisoned bytes in front, >= guard behind)
+                    prim::stream_merge_emit_records<SelfSeg<IDX>, IDX>(D.seg, plan, buf.p + at, rec, SelfRecFn{tab ? table.p : nullptr}, "selftest.sm");
+                    const std::vector<uint8_t> h = buf.to_host(cap);
+                    for (uint64_t k = 0; k < heads && !rc; k++) {
+                        const uint64_t len = (k + 1 < heads ? R.rstart[k + 1] : R.len_total) - R.rstart[k];
+                        const uint64_t v = (tab ? kTable[R.rsym[k] & 3u] : (uint64_t)(R.rsym[k] & 0xFFu)) | (len << 8);
+                        uint64_t got = 0;
+                        for (uint32_t b = 0; b < rec; b++) got |= (uint64_t)h[at + k * rec + b] << (8 * b);
+                        if (got != (rec < 8 ? v & ((1ull << (8 * rec)) - 1ull) : v)) {
+                            fprintf(stderr, "[grlbwt] selftest stream merge: scenario '%s', %d-byte index, %d segments per thread, records of 1 + %u bytes%s at offset %u: "
+                                    "record %llu of %llu expected %llx (symbol %u, length %llu), got %llx\n", sc.name, (int)sizeof(IDX), spt, fb, tab ? " through a table" : "", kOff[o],
+                                    (unsigned long long)k, (unsigned long long)heads, (unsigned long long)v, R.rsym[k], (unsigned long long)len, (unsigned long long)got);
+                            rc = 8;
+                        }
+                    }
+                    for (uint64_t x = 0; x < cap && !rc; x++) {
+                        if ((x < at || x >= at + bytes) && h[x] != kSmPoison) {
+                            fprintf(stderr, "[grlbwt] selftest stream merge: scenario '%s', %d-byte index, %d segments per thread, records of 1 + %u bytes at offset %u: "
+                                    "byte %lld %s the records was written\n", sc.name, (int)sizeof(IDX), spt, fb, kOff[o],
+                                    x < at ? (long long)(at - x) : (long long)(x - (at + bytes)), x < at ? "in front of" : "behind");
+                            rc = 9;
+                        }
+                    }
+                }
+        }
+    } catch (...) { plan.release(); throw; }
+    plan.release();
+    return rc;
+}
+#endif
 template <class IDX>
 int sm_check(const SmScn &sc, const SmRef &R, bool fallbacks) {
     if (sc.idx_only && sc.idx_only != (int)sizeof(IDX)) return 0;
@@ -1170,6 +1232,9 @@ int sm_check(const SmScn &sc, const SmRef &R, bool fallbacks) {
             if (D.queued) if (int rc = sm_one_walk<IDX>(sc, R, D, mp != 0, 1)) return 220 + rc;
             if (int rc = sm_one_walk<IDX>(sc, R, D, mp != 0, 2)) return 230 + rc;
         }
+#ifdef GRLBWT_PRIM_HIP
+        if (int rc = sm_records<IDX>(sc, R, D, mp != 0)) return 240 + rc;
+#endif
     }
     return 0;
 }

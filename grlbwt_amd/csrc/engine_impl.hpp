@@ -2246,6 +2246,10 @@ struct RunRecordFn {      // sym | len << (8 sb): the record of run i as one wor
     const u32 *sym; RunLen len; u32 sb; const u64 *alpha = nullptr;
     GRL_DEV u64 operator()(u64 i) const { return (alpha ? alpha[sym[i]] : (u64)sym[i]) | ((u64)len(i) << (8 * sb)); }
 };
+struct ImageRecFn {       // the same word from a run's symbol and length (prim::stream_merge_emit_records: pass C of level 0 writes the image)
+    u32 sb; const u64 *alpha = nullptr;
+    GRL_DEV u64 operator()(u32 sym, u64 len) const { return (alpha ? alpha[sym] : (u64)sym) | (len << (8 * sb)); }
+};
 struct PackRunsFn {
     const u32 *sym; RunLen len; u32 sb, fb; u8 *out; u32 hdr;      // hdr: bytes in front of the first record (16, or 0 for a part)
     const u64 *alpha = nullptr;
@@ -4964,7 +4968,8 @@ class Engine {
     // what pass C assembles: a contiguous piece of the level's pre-BWT, the metasymbols (buckets) whose HOCC runs lie in it
     // (indices relative to the piece), and the number of symbols the piece describes.  The whole level on one GPU.
     struct AsmIn { const u32 *psym; const idx_t *plen; u64 P; const u32 *u_to_p; const u32 *p_to_u; u64 M; u32 sigma; u64 n_out; };
-    void assemble(const AsmIn &in, LevelInfo &I, const CellView &cells, u64 E, DBuf<u32> &term, int r) {
+    // to_image: the caller runs finish() right behind level 0 (the single-GPU flow), so pass C of level 0 may write the image itself
+    void assemble(const AsmIn &in, LevelInfo &I, const CellView &cells, u64 E, DBuf<u32> &term, int r, bool to_image = false) {
         StageTimer st(&tm.ind_assemble, "ind_assemble");
         DBuf<idx_t> Tpos;
         u64 Tsum;
@@ -4973,7 +4978,7 @@ class Engine {
             Tpos.alloc(bwt.R + 1);
             Tsum = (u64)prim::exclusive_scan<idx_t>(bwt.R, IdxIn<idx_t>{bwt.len.p}, Tpos.p, true, "asm.Tpos");
         }
-        assemble_t(in, I, cells, E, Tpos, Tsum, term, r);
+        assemble_t(in, I, cells, E, Tpos, Tsum, term, r, to_image);
     }
     void release_level(LevelData &L) {           // the level's grammar is no longer needed
         L.g0.release(); L.g1.release(); L.has_hocc.release(); L.u_to_p.release(); L.p_to_u.release(); L.prebwt.sym.release(); L.prebwt.len.release();
@@ -4997,7 +5002,7 @@ class Engine {
             I.Esteps = E - prim::reduce_sum<u64>(R, TakeCountIn{bwt.sym.p, c_gp.p}, "stat.take_cells");
             I.Emerged = prim::reduce_sum<u64>(E, CellHeadIn{cells}, "stat.merged_cells");
         }
-        assemble(AsmIn{L.prebwt.sym.p, L.prebwt.len.p, L.prebwt.R, L.u_to_p.p, L.p_to_u.p, L.M, L.sigma, L.info.n_in}, I, cells, E, term, r);
+        assemble(AsmIn{L.prebwt.sym.p, L.prebwt.len.p, L.prebwt.R, L.u_to_p.p, L.p_to_u.p, L.M, L.sigma, L.info.n_in}, I, cells, E, term, r, r == 0);
         bwt_level = r;
         if (r == 0 && bwt.len.p) bwt.pos.release();      // (no level below wants the prefix -- unless it stands for the lengths)
         I.R = bwt.R;
@@ -5006,7 +5011,7 @@ class Engine {
         release_level(L);
     }
     // pass C (exact_ind_phase.cpp:287-361): BWT_r from the pre-BWT, the induced cells and the rewritten BWT_{r+1}
-    void assemble_t(const AsmIn &L, LevelInfo &I, const CellView &cells, u64 E, DBuf<idx_t> &Tpos, u64 Tsum, DBuf<u32> &term, int r) {
+    void assemble_t(const AsmIn &L, LevelInfo &I, const CellView &cells, u64 E, DBuf<idx_t> &Tpos, u64 Tsum, DBuf<u32> &term, int r, bool to_image) {
         const u32 bwt_code = L.sigma + 1, hocc_code = L.sigma + 2, take_code = bwt_code;
         const u64 R = bwt.R, P = L.P, M = L.M;
         // ---- the maximal runs of the rewritten BWT_{r+1} and their starts over the T axis
@@ -5092,13 +5097,34 @@ class Engine {
             prim::stream_merge_count<AsmSeg, idx_t>(G, seg, plan, "asm", mostly_plain);      // (few pre-BWT runs among the segments: small tiles, see prim_hip.hpp)
             check_totals();
             Ro = plan.heads;
-            out.sym.alloc(Ro); out.pos.alloc(Ro + 1);
-            try { prim::stream_merge_emit<AsmSeg, idx_t>(seg, plan, out.sym.p, out.pos.p, "asm"); } catch (...) { plan.release(); throw; }
+            // Level 0, and nothing but finish() reads its runs: the emit pass writes the .rl_bwt records themselves (a run's length is
+            // the distance to the next head, which the pass has at hand) -- the 12 bytes per run of (symbol, position) are neither
+            // allocated nor written, and finish() has no pack pass left that reads them back.  GRLBWT_ASM_IMAGE=0,
+            // kept levels, records wider than 8 bytes and the serial stand-in take emit + pack.
+            image_fused = false;
+#ifdef GRLBWT_PRIM_HIP
+            const u32 sb = (u32)stats.sb, fb = (u32)stats.fb;
+            if (to_image && r == 0 && !keep_texts && sb + fb <= 8 && fb < 8 && prim::sw().asm_image != 0) {
+                image_bytes = 16 + Ro * (u64)(sb + fb);
+                try {
+                    image.alloc(image_bytes);
+                    image_header(sb, fb);
+                    prim::stream_merge_emit_records<AsmSeg, idx_t>(seg, plan, image.p + 16, sb + fb, ImageRecFn{sb, alpha.p}, "asm");
+                } catch (...) { plan.release(); throw; }
+                image_fused = true;
+            }
+#else
+            (void)to_image;
+#endif
+            if (!image_fused) {
+                out.sym.alloc(Ro); out.pos.alloc(Ro + 1);
+                try { prim::stream_merge_emit<AsmSeg, idx_t>(seg, plan, out.sym.p, out.pos.p, "asm"); } catch (...) { plan.release(); throw; }
+            }
         }
         I.A = plan.atoms;
         plan.release();
         const idx_t total = (idx_t)L.n_out;
-        prim::h2d(out.pos.p + Ro, &total, sizeof(idx_t));
+        if (out.pos.p) prim::h2d(out.pos.p + Ro, &total, sizeof(idx_t));      // (no arrays: the image holds the runs)
         // everything but the runs can go before their lengths are taken (peak memory)
         kinds.release(); nh_sym.release(); nh_len.release(); tstarts.release(); esym.release(); epos.release();
         release_cells();
@@ -5115,21 +5141,28 @@ class Engine {
     }
 
     // ---- a16/a17: .rl_bwt image in HBM --------------------------------------
+    bool image_fused = false;                 // `image` is written already: level 0's pass C emitted records (assemble_t)
+    void image_header(u32 sb, u32 fb) {
+        u8 hdr[16] = {0};
+        for (int i = 0; i < 8; i++) { hdr[i] = (u8)((u64)sb >> (8 * i)); hdr[8 + i] = (u8)((u64)fb >> (8 * i)); }
+        prim::h2d(image.p, hdr, 16);
+    }
     void finish() {
         if (bwt_level != 0) throw prim::Error(-22, "induction not finished");
         prim::rt().tag = -1; prim::rt().phase = 0;
         StageTimer st(&tm.finish, "finish");
         u32 sb = (u32)stats.sb, fb = (u32)stats.fb;
+        if (!image_fused) {
         image_bytes = 16 + bwt.R * (u64)(sb + fb);
         image.alloc(image_bytes);
-        u8 hdr[16] = {0};
-        for (int i = 0; i < 8; i++) { hdr[i] = (u8)((u64)sb >> (8 * i)); hdr[8 + i] = (u8)((u64)fb >> (8 * i)); }
-        prim::h2d(image.p, hdr, 16);
+        image_header(sb, fb);
         // records of up to 8 bytes go through prim::pack_records (tiles assembled in LDS, 16-byte stores); wider ones one lane per run.
         // (Four runs per lane, their 4 x 5 bytes put together in registers, was measured at 15.5 ms against 9 for one lane per run on
         // the 1.66 G runs of the 10 GB image: the loads of a lane's four runs are what is 20 bytes apart then.)
         if (sb + fb <= 8 && fb < 8) prim::pack_records(bwt.R, RunRecordFn{bwt.sym.p, run_len(), sb, alpha.p}, sb + fb, image.p + 16, "pack_rl_bwt");
         else prim::for_each(bwt.R, PackRunsFn{bwt.sym.p, run_len(), sb, fb, image.p, 16u, alpha.p}, "pack_rl_bwt");
+        }                                         // (else: pass C of level 0 wrote header and records, assemble_t)
+        image_fused = false;
         image_runs = bwt.R;
         image_part_off = 0; image_part_bytes = image_bytes;
         // "results are complete when a call returns" (include/grlbwt_hip.h): the image pointer may be handed to another

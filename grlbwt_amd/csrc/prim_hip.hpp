@@ -3092,12 +3092,39 @@ template <class LT, int SPT> struct SmShared {
     u32 w1[4];
     u32 last[kBlock];
 };
+// MODE 3's output: run i as the record of `rec` bytes at out + i * rec, the low bytes of f(symbol, length).  A run's length is
+// the distance to the next head, so a tile cannot finish its last record: it leaves (first head position or none; symbol and
+// position of its last head) per tile, and k_sm_seam writes those records behind the emit pass.
+struct SmNoRec {};
+template <class REC, class IDX>
+struct SmRecOut {
+    u8 *out; u32 rec; REC f;
+    u64 *sfirst;             // [tiles] position of the tile's first head, kSmNoHead: the tile has none
+    u32 *slsym; IDX *slpos;  // [tiles] symbol / position of the tile's last head (tiles with a head)
+};
+static constexpr u64 kSmNoHead = ~0ull;
+GRL_DEV void sm_store_rec(u8 *out, u64 i, u32 rec, u64 v) {
+    u8 *p = out + i * (u64)rec;
+    u32 b = 0;
+    if (rec >= 4) { const u32 lo = (u32)v; __builtin_memcpy(p, &lo, 4); b = 4; }      // (one store at any alignment where the target has them)
+    for (; b < rec; b++) p[b] = (u8)(v >> (8 * b));
+}
 // MODE 0: count pass, 1: emit pass of the two-pass form, 2: ONE WALK (round 6) -- count and emit together; the run index at the tile's
 // start (hb) is not an input but comes from a decoupled look-back over per-tile status words (SmLb), see k_sm_merge
-template <class LT, class SEG, class IDX, int MODE, int SPT>
+// MODE 3: the emit pass of the two-pass form once more, writing records (SmRecOut) instead of (symbol, position):
+//   * a staged tile holds its heads in LDS as before; record k is (symbol k, position k + 1 - position k), stored by lane k % 256
+//     straight from registers -- neighbouring lanes, neighbouring records; only bytes of the tile's own records are touched, whatever
+//     the alignment of `out`.  (Measured against records put together as bytes in LDS and written in 16-byte vectors: DESIGN 7.)
+//     Left out: the places of queued atoms and the tile's last record -- k_sm_wide_rec and k_sm_seam write those.
+//   * a queued segment: k_sm_wide_rec writes its inner atoms but the last (whole runs of T: the next run's start ends them); the
+//     lane stages the last one like any head, and leaves the position of the first in its placeholder slot, where the head in
+//     front of it looks for its end.
+//   * a tile whose heads do not fit LDS: every lane stores its records itself; the one it has begun is ended by its own next
+//     head, or by the first head of a later lane (through LDS, behind the loop).
+template <class LT, class SEG, class IDX, int MODE, int SPT, class RO = SmNoRec>
 GRL_DEV void sm_tile(u64 G, const SEG &seg, const u64 base, const IDX xb, const IDX lb, IDX hb, const u32 prev_tile, const bool plain, const u64 ord0,
                      SmShared<LT, SPT> &S, IDX *tile_heads, IDX *tile_atoms, u32 *tfirst, u32 *tlast, unsigned long long *wide, SmWide<IDX> *queue,
-                     u64 queue_cap, u32 *osym, IDX *ostart, const SmLb &lbk) {
+                     u64 queue_cap, u32 *osym, IDX *ostart, const SmLb &lbk, const RO &ro = RO()) {
     constexpr bool EMIT = MODE != 0;
     constexpr int TILE = kBlock * SPT;
     typedef Pair<LT, LT> P2;
@@ -3271,11 +3298,24 @@ GRL_DEV void sm_tile(u64 G, const SEG &seg, const u64 base, const IDX xb, const 
             __syncthreads();
         }
         u64 r = hl0;
+        // MODE 3, unstaged tile: the record this lane has begun (pend: symbol and position; it is the one in front of the next head),
+        // and the position of the lane's first head, kept in the LDS slot of the lane (seen)
+        [[maybe_unused]] bool pend = false, seen = false;
+        [[maybe_unused]] u32 psym = 0;
+        [[maybe_unused]] LT ppos = 0;
+        [[maybe_unused]] auto next_head = [&](u64 k, u32 s, LT off, bool opens) {      // head k at `off`: ends the record begun, begins record k (opens) or none (atoms the wide kernel writes)
+            if constexpr (MODE == 3) {
+                if (pend) sm_store_rec(ro.out, hbm + k - 1, ro.rec, ro.f(psym, (u64)(LT)(off - ppos)));
+                else if (!seen) S.len[threadIdx.x] = off;
+                seen = true; pend = opens; psym = s; ppos = off;
+            }
+        };
 #pragma unroll
         for (int i = 0; i < SPT; i++) {
             if (g0 + i < G) {
                 if (head[i]) {
                     if (staged) { S.sym[r] = fs[i]; S.len[r] = Ls[i]; }
+                    else if constexpr (MODE == 3) next_head(r, fs[i], Ls[i], true);
                     else { osym[hbm + r] = fs[i]; ostart[hbm + r] = lb + (IDX)Ls[i]; }
                     r++;
                 }
@@ -3284,6 +3324,12 @@ GRL_DEV void sm_tile(u64 G, const SEG &seg, const u64 base, const IDX xb, const 
                     if (in64 > (u64)kSmInline) {
                         const u64 q = (u64)atomicAdd(&wide[2], 1ull);
                         if (q < queue_cap) queue[q] = SmWide<IDX>{(IDX)(qbase_r + r), lb + (IDX)Ls[i], xb + (IDX)xs[i], (IDX)in64, k0[i] + 1, tile1};
+                        if constexpr (MODE == 3) {
+                            const u64 x = (u64)xb + (u64)xs[i];
+                            const LT o0 = Ls[i] + (LT)(seg.epos(k0[i] + 1) - x), o1 = Ls[i] + (LT)(seg.epos(k1m[i]) - x);      // first and last inner atom
+                            if (staged) { S.len[r] = o0; S.sym[r + in64 - 1] = ls[i]; S.len[r + in64 - 1] = o1; }
+                            else { next_head(r, 0, o0, false); next_head(r + in64 - 1, ls[i], o1, true); }
+                        }
                     } else {
                         // (all of a segment's loads in flight first, clamped instead of branched, was tried: no faster -- 18.9 vs 19.4 ms on
                         // level 1 of the 10 GB build -- and 24 more registers)
@@ -3293,6 +3339,7 @@ GRL_DEV void sm_tile(u64 G, const SEG &seg, const u64 base, const IDX xb, const 
                             const u32 sk = seg.esym(k);
                             const u64 off = seg.epos(k) - x;            // (< the segment's length)
                             if (staged) { S.sym[r + a] = sk; S.len[r + a] = Ls[i] + (LT)off; }
+                            else if constexpr (MODE == 3) next_head(r + a, sk, Ls[i] + (LT)off, true);
                             else { osym[hbm + r + a] = sk; ostart[hbm + r + a] = lb + (IDX)Ls[i] + (IDX)off; }
                         }
                     }
@@ -3300,7 +3347,38 @@ GRL_DEV void sm_tile(u64 G, const SEG &seg, const u64 base, const IDX xb, const 
                 }
             }
         }
+        if constexpr (MODE == 3) {
+            if (!staged) {                  // (uniform; the segments' LDS arrays are free: every lane read its own in front of the scans' barriers)
+                S.sym[threadIdx.x] = seen ? 1u : 0u;
+                __syncthreads();
+                if (pend) {                 // (my last head is r - 1)
+                    u32 t = threadIdx.x + 1;
+                    while (t < (u32)kBlock && !S.sym[t]) t++;
+                    if (t < (u32)kBlock) sm_store_rec(ro.out, hbm + r - 1, ro.rec, ro.f(psym, (u64)(LT)(S.len[t] - ppos)));
+                    else { ro.slsym[blockIdx.x] = psym; ro.slpos[blockIdx.x] = lb + (IDX)ppos; }      // the tile's last head
+                }
+                if (threadIdx.x == 0) {     // (htot > TILE: some lane has a head)
+                    u32 t = 0;
+                    while (t + 1 < (u32)kBlock && !S.sym[t]) t++;
+                    ro.sfirst[blockIdx.x] = (u64)lb + (u64)S.len[t];
+                }
+            }
         }
+        }
+        if constexpr (MODE == 3) {
+            if (staged) {
+                __syncthreads();
+                const u32 nh3 = (u32)htot;
+                for (u32 k = threadIdx.x; k + 1 < nh3; k += kBlock) {      // (the last one: k_sm_seam; the places of queued atoms: k_sm_wide_rec)
+                    const u32 sk = S.sym[k];
+                    if (sk != kSmNoSym) sm_store_rec(ro.out, hbm + k, ro.rec, ro.f(sk, (u64)(LT)(S.len[k + 1] - S.len[k])));
+                }
+                if (threadIdx.x == 0) {
+                    ro.sfirst[blockIdx.x] = nh3 ? (u64)lb + (u64)S.len[0] : kSmNoHead;
+                    if (nh3) { ro.slsym[blockIdx.x] = S.sym[nh3 - 1]; ro.slpos[blockIdx.x] = lb + (IDX)S.len[nh3 - 1]; }
+                }
+            }
+        } else
         if (staged) {
             if constexpr (MODE == 2) look_back();            // (its barrier is the one the write-out needs)
             else __syncthreads();
@@ -3313,17 +3391,22 @@ GRL_DEV void sm_tile(u64 G, const SEG &seg, const u64 base, const IDX xb, const 
         }
     }
 }
-template <class SEG, class IDX, int MODE, int SPT>
+template <class SEG, class IDX, int MODE, int SPT, class RO = SmNoRec>
 __global__ void __launch_bounds__(kBlock) k_sm_merge(u64 G, SEG seg, const IDX *xbase, const IDX *lbase, const IDX *hbase, IDX *tile_heads, IDX *tile_atoms,
-                                                     u32 *tfirst, u32 *tlast, unsigned long long *wide, SmWide<IDX> *queue, u64 queue_cap, u32 *osym, IDX *ostart, SmLb lbk) {
+                                                     u32 *tfirst, u32 *tlast, unsigned long long *wide, SmWide<IDX> *queue, u64 queue_cap, u32 *osym, IDX *ostart, SmLb lbk,
+                                                     const RO *rop = nullptr) {
     constexpr int kSmTile = kBlock * SPT;
     __shared__ __attribute__((aligned(16))) unsigned char s_raw[sizeof(SmShared<IDX, SPT>)];
+    // (MODE 3's descriptor is read from device memory where it is used, behind the merge: as a kernel argument its twelve scalar registers
+    // stayed live through the whole tile, the kernel spilled 43 of them, and took 113 vector registers instead of 94 -- four waves per SIMD, not five)
+    const RO none = RO();
+    const RO &ro = MODE == 3 ? *rop : none;
     const u64 base = (u64)blockIdx.x * kSmTile;
     // (loaded first: nothing below has to wait for them)
     const IDX xb = xbase[blockIdx.x], lb = lbase[blockIdx.x], lnext = lbase[blockIdx.x + 1];
     IDX hb = 0;
     u32 prev_tile = kSmNoSym;
-    if constexpr (MODE == 1) { hb = hbase[blockIdx.x]; if (blockIdx.x > 0) prev_tile = tlast[blockIdx.x - 1]; }
+    if constexpr (MODE == 1 || MODE == 3) { hb = hbase[blockIdx.x]; if (blockIdx.x > 0) prev_tile = tlast[blockIdx.x - 1]; }
     if constexpr (MODE == 2) {
         // the last symbol of the segment in front of the tile, by thread 0 itself: its record, and where it is a TAKE -- it ends where my
         // tile's T axis begins -- the run of T in front of xb.  Three dependent loads, issued before everything else: they are back when
@@ -3344,11 +3427,11 @@ __global__ void __launch_bounds__(kBlock) k_sm_merge(u64 G, SEG seg, const IDX *
     const u64 ord0 = seg.pre_before(base), ord1 = seg.pre_before(gend);
     const bool plain = ord0 == ord1;                                   // (uniform) no pre-BWT run among the tile's segments
     if (sizeof(IDX) == 4 || (u64)(lnext - lb) >= 0xFFFFFFFFull)        // (uniform) offsets inside the tile in the index width ...
-        sm_tile<IDX, SEG, IDX, MODE, SPT>(G, seg, base, xb, lb, hb, prev_tile, plain, ord0, *reinterpret_cast<SmShared<IDX, SPT> *>(s_raw), tile_heads, tile_atoms, tfirst, tlast,
-                                     wide, queue, queue_cap, osym, ostart, lbk);
+        sm_tile<IDX, SEG, IDX, MODE, SPT, RO>(G, seg, base, xb, lb, hb, prev_tile, plain, ord0, *reinterpret_cast<SmShared<IDX, SPT> *>(s_raw), tile_heads, tile_atoms, tfirst, tlast,
+                                     wide, queue, queue_cap, osym, ostart, lbk, ro);
     else                                                               // ... or in 32 bits when the tile describes < 2^32 symbols
-        sm_tile<u32, SEG, IDX, MODE, SPT>(G, seg, base, xb, lb, hb, prev_tile, plain, ord0, *reinterpret_cast<SmShared<u32, SPT> *>(s_raw), tile_heads, tile_atoms, tfirst, tlast,
-                                     wide, queue, queue_cap, osym, ostart, lbk);
+        sm_tile<u32, SEG, IDX, MODE, SPT, RO>(G, seg, base, xb, lb, hb, prev_tile, plain, ord0, *reinterpret_cast<SmShared<u32, SPT> *>(s_raw), tile_heads, tile_atoms, tfirst, tlast,
+                                     wide, queue, queue_cap, osym, ostart, lbk, ro);
 }
 // heads of tile t without the provisional head of its first segment where the tile in front ends with the same symbol
 template <class IDX>
@@ -3447,6 +3530,142 @@ inline void stream_merge_emit(SEG seg, SmPlan<IDX> &plan, u32 *osym, IDX *ostart
         dev_free(qbase);
     }
     dev_free(queue); dev_free(wide);
+}
+// ---- the record form of the emit pass (sm_tile MODE 3): what it leaves to the two kernels behind it
+// the inner atoms of the queued segments but the last of each: whole runs of T, (symbol, distance to the next run's start)
+template <class SEG, class IDX, class REC>
+__global__ void __launch_bounds__(kBlock) k_sm_wide_rec(u64 natoms, u64 nq, SEG seg, const SmWide<IDX> *queue, const u64 *qbase, u8 *out, u32 rec, REC f) {
+    const u64 stride = (u64)gridDim.x * kBlock;
+    for (u64 y = (u64)blockIdx.x * kBlock + threadIdx.x; y < natoms; y += stride) {
+        u64 lo = 0, hi = nq;                   // last entry with qbase <= y
+        while (lo + 1 < hi) { const u64 mid = (lo + hi) >> 1; if (qbase[mid] <= y) lo = mid; else hi = mid; }
+        const SmWide<IDX> e = queue[lo];
+        const u64 a = y - qbase[lo], k = e.k + a;
+        if (a + 1 < (u64)e.cnt) sm_store_rec(out, (u64)e.r + a, rec, f(seg.esym(k), seg.epos(k + 1) - seg.epos(k)));
+    }
+}
+// A tile's last record ends at the first head of the next tile that has one -- any number of tiles further on -- or at the end
+// of the symbols.  "The smallest first-head position behind tile t" is a suffix minimum over the tiles (positions grow with the
+// tile index, no head = kSmNoHead): per chunk of kSeamChunk tiles in k_sm_seam_min, over the chunks in k_sm_seam_suffix (one
+// workgroup), inside the chunk in k_sm_seam.  Exclusive suffix minimum of v over the 256 threads of the block; *all = the minimum.
+GRL_DEV u64 block_excl_suffix_min(u64 v, u64 *s_w /*[4]*/, u64 *all) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    for (int off = 1; off < 64; off <<= 1) {
+        const u64 o = __shfl_down(v, off, 64);
+        if (lane + off < 64 && o < v) v = o;
+    }
+    const u64 nxt = __shfl_down(v, 1, 64);
+    __syncthreads();
+    if (lane == 0) s_w[w] = v;
+    __syncthreads();
+    u64 behind = kSmNoHead, tot = kSmNoHead;
+    for (int k = 0; k < 4; k++) {
+        const u64 x = s_w[k];
+        if (k > w && x < behind) behind = x;
+        if (x < tot) tot = x;
+    }
+    *all = tot;
+    return (lane < 63 && nxt < behind) ? nxt : behind;
+}
+static constexpr int kSeamItems = 8;
+static constexpr int kSeamChunk = kBlock * kSeamItems;
+__global__ void __launch_bounds__(kBlock) k_sm_seam_min(u64 tiles, const u64 *sfirst, u64 *cmin) {
+    __shared__ u64 s_w[4];
+    u64 m = kSmNoHead;
+#pragma unroll
+    for (int j = 0; j < kSeamItems; j++) {
+        const u64 t = (u64)blockIdx.x * kSeamChunk + (u32)j * kBlock + threadIdx.x;
+        const u64 v = t < tiles ? sfirst[t] : kSmNoHead;
+        if (v < m) m = v;
+    }
+    u64 all;
+    (void)block_excl_suffix_min(m, s_w, &all);
+    if (threadIdx.x == 0) cmin[blockIdx.x] = all;
+}
+// cmin[c] <- the minimum over the chunks behind c (in place, one workgroup, 256 chunks per step from the back)
+__global__ void __launch_bounds__(kBlock) k_sm_seam_suffix(u64 chunks, u64 *cmin) {
+    __shared__ u64 s_w[4];
+    u64 carry = kSmNoHead;
+    for (u64 hi = chunks; hi > 0; hi = hi > (u64)kBlock ? hi - kBlock : 0) {
+        const u64 lo = hi > (u64)kBlock ? hi - kBlock : 0, c = lo + threadIdx.x;
+        const u64 v = c < hi ? cmin[c] : kSmNoHead;
+        u64 all;
+        const u64 ex = block_excl_suffix_min(v, s_w, &all);
+        if (c < hi) cmin[c] = ex < carry ? ex : carry;
+        if (all < carry) carry = all;
+        __syncthreads();                       // (s_w is written again in the next step)
+    }
+}
+template <class IDX, class REC>
+__global__ void __launch_bounds__(kBlock) k_sm_seam(u64 tiles, const u64 *sfirst, const u64 *cbehind, const IDX *hbase, const u32 *slsym, const IDX *slpos,
+                                                    u64 len_total, u8 *out, u32 rec, REC f) {
+    __shared__ u64 s_w[4];
+    const u64 t0 = (u64)blockIdx.x * kSeamChunk + (u64)threadIdx.x * kSeamItems;
+    u64 first[kSeamItems];
+    u64 m = kSmNoHead;
+#pragma unroll
+    for (int j = 0; j < kSeamItems; j++) {
+        first[j] = t0 + j < tiles ? sfirst[t0 + j] : kSmNoHead;
+        if (first[j] < m) m = first[j];
+    }
+    u64 all;
+    u64 nxt = block_excl_suffix_min(m, s_w, &all);      // the first head behind my tiles: in the chunk ...
+    const u64 cb = cbehind[blockIdx.x];
+    if (cb < nxt) nxt = cb;                              // ... or behind it
+#pragma unroll
+    for (int j = kSeamItems - 1; j >= 0; j--) {
+        const u64 t = t0 + j;
+        if (t < tiles) {
+            const u64 h0 = (u64)hbase[t], h1 = (u64)hbase[t + 1];
+            if (h1 > h0) sm_store_rec(out, h1 - 1, rec, f(slsym[t], (nxt == kSmNoHead ? len_total : nxt) - (u64)slpos[t]));
+            if (first[j] < nxt) nxt = first[j];
+        }
+    }
+}
+// pass 3 as records: run i -> the low `rec` (1..8) bytes of f(symbol i, length i) at out + i * rec; the plan comes from
+// stream_merge_count.  Three launches: the merge (MODE 3), the queued atoms, the tiles' last records.
+template <class SEG, class IDX, class REC>
+inline void stream_merge_emit_records(SEG seg, SmPlan<IDX> &plan, u8 *out, u32 rec, REC f, const char *name = "stream_merge") {
+    if (plan.G == 0) return;
+    if (rec < 1 || rec > 8) throw Error(-22, "stream_merge_emit_records: record width out of range");
+    typedef SmRecOut<REC, IDX> RO;
+    const u64 nq = plan.wide_n, T = plan.tiles, chunks = (T + kSeamChunk - 1) / kSeamChunk;
+    SmWide<IDX> *queue = (SmWide<IDX> *)dev_alloc((nq ? nq : 1) * sizeof(SmWide<IDX>));
+    unsigned long long *wide = (unsigned long long *)dev_alloc(3 * sizeof(unsigned long long));
+    dev_memset(wide, 0, 3 * sizeof(unsigned long long));
+    u64 *sfirst = (u64 *)dev_alloc(T * sizeof(u64)), *cmin = (u64 *)dev_alloc(chunks * sizeof(u64));
+    u32 *slsym = (u32 *)dev_alloc(T * sizeof(u32));
+    IDX *slpos = (IDX *)dev_alloc(T * sizeof(IDX));
+    const RO ro{out, rec, f, sfirst, slsym, slpos};
+    RO *dro = (RO *)dev_alloc(sizeof(RO));              // (read by the kernel from memory, see k_sm_merge)
+    h2d(dro, &ro, sizeof(RO));
+    prof_begin(std::string(name) + ".emit_rec", plan.heads * rec);
+    if (plan.spt == 4)
+        hipLaunchKernelGGL((k_sm_merge<SEG, IDX, 3, 4, RO>), dim3((unsigned)T), dim3(kBlock), 0, rt().stream, plan.G, seg, (const IDX *)plan.xbase,
+                           (const IDX *)plan.lbase, (const IDX *)plan.hbase, (IDX *)nullptr, (IDX *)nullptr, (u32 *)nullptr, plan.tlast, wide, queue, nq, (u32 *)nullptr, (IDX *)nullptr, SmLb(), (const RO *)dro);
+    else
+        hipLaunchKernelGGL((k_sm_merge<SEG, IDX, 3, 8, RO>), dim3((unsigned)T), dim3(kBlock), 0, rt().stream, plan.G, seg, (const IDX *)plan.xbase,
+                           (const IDX *)plan.lbase, (const IDX *)plan.hbase, (IDX *)nullptr, (IDX *)nullptr, (u32 *)nullptr, plan.tlast, wide, queue, nq, (u32 *)nullptr, (IDX *)nullptr, SmLb(), (const RO *)dro);
+    prof_end();
+    after_launch(name);
+    if (nq) {
+        u64 *qbase = (u64 *)dev_alloc((nq + 1) * sizeof(u64));
+        exclusive_scan_async<u64, SmWideCountIn<IDX>>(nq, SmWideCountIn<IDX>{queue}, qbase, (u64 *)nullptr, qbase + nq, name);
+        prof_begin(std::string(name) + ".wide_rec", plan.wide_atoms * rec);
+        hipLaunchKernelGGL((k_sm_wide_rec<SEG, IDX, REC>), dim3(grid_for(plan.wide_atoms, kBlock)), dim3(kBlock), 0, rt().stream, plan.wide_atoms, nq, seg,
+                           (const SmWide<IDX> *)queue, (const u64 *)qbase, out, rec, f);
+        prof_end();
+        after_launch(name);
+        dev_free(qbase);
+    }
+    prof_begin(std::string(name) + ".seam", T * rec);
+    hipLaunchKernelGGL(k_sm_seam_min, dim3((unsigned)chunks), dim3(kBlock), 0, rt().stream, T, (const u64 *)sfirst, cmin);
+    hipLaunchKernelGGL(k_sm_seam_suffix, dim3(1), dim3(kBlock), 0, rt().stream, chunks, cmin);
+    hipLaunchKernelGGL((k_sm_seam<IDX, REC>), dim3((unsigned)chunks), dim3(kBlock), 0, rt().stream, T, (const u64 *)sfirst, (const u64 *)cmin, (const IDX *)plan.hbase,
+                       (const u32 *)slsym, (const IDX *)slpos, plan.len_total, out, rec, f);
+    prof_end();
+    after_launch(name);
+    dev_free(queue); dev_free(wide); dev_free(sfirst); dev_free(cmin); dev_free(slsym); dev_free(slpos); dev_free(dro);
 }
 
 // Status words of the look-back: memory of the runtime's own allocator (hipMalloc), kept between calls -- agent-scope polling

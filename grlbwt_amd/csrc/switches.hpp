@@ -33,6 +33,7 @@
     X(GRLBWT_NO_CELL32, no_cell32, bool, false, "induction cells of one word in 64 bits even where 32 would do")               \
     X(GRLBWT_ASM_TWO_PASS, asm_two_pass, bool, false, "pass C always as count + emit (no one-walk form)")                       \
     X(GRLBWT_ASM_ONE_WALK, asm_one_walk, bool, false, "pass C tries the one-walk form at every level, plain or not")           \
+    X(GRLBWT_ASM_IMAGE, asm_image, int, 1, "level 0's pass C writes the .rl_bwt records itself (0: emit + pack)")             \
     X(GRLBWT_DIST_GATHERED_DICT, dist_gathered_dict, bool, false, "multi-rank: the dictionary gathered on every rank, not sharded") \
     X(GRLBWT_DIST_SHARDED_DICT_MIN, dist_sharded_dict_min, int, 4, "multi-rank: ranks from which the dictionary is sharded")    \
     X(GRLBWT_DIST_SHARDED_DICT_MIN_SYMS, dist_sharded_dict_min_syms, uint64_t, (uint64_t)1 << 27, "multi-rank: dictionary symbols from which it is sharded") \
