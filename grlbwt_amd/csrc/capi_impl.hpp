@@ -1872,20 +1872,26 @@ int grlbwt_invert_image(grlbwt_ctx *ctx, const void *dev_image, uint64_t image_b
 
 
 int grlbwt_fm_create(grlbwt_ctx *ctx, const void *dev_image, uint64_t image_bytes, uint32_t fm_flags, grlbwt_fm **out) {
-    if (!ctx || !dev_image || !out || (fm_flags & ~GRLBWT_FM_LOCATE)) return GRLBWT_EINVAL;
+    if (!ctx || !dev_image || !out) return GRLBWT_EINVAL;
     *out = nullptr;
+    const uint32_t sample_bits = (fm_flags >> 8) & 0xFFu;
+    if ((fm_flags & ~(GRLBWT_FM_LOCATE | GRLBWT_FM_CHECKPOINTS | 0xFF00u)) || sample_bits > 20 ||
+        (!(fm_flags & GRLBWT_FM_CHECKPOINTS) && sample_bits) || ((fm_flags & GRLBWT_FM_CHECKPOINTS) && !(fm_flags & GRLBWT_FM_LOCATE))) {
+        ctx->err = "fm index: bad flags (checkpoints need the locate structures; sample_bits is 0 or 1 to 20 and needs checkpoints)";
+        return GRLBWT_EINVAL;
+    }
     return guarded(ctx, [&] {
         const uint64_t total = grl64::Engine::image_total_symbols(dev_image, image_bytes);
         const bool big = total >= kIdx32Limit || (ctx->flags & GRLBWT_FLAG_FORCE_IDX64);
-        const bool locate = fm_flags & GRLBWT_FM_LOCATE;
+        const bool locate = fm_flags & GRLBWT_FM_LOCATE, cps = fm_flags & GRLBWT_FM_CHECKPOINTS;
         std::unique_ptr<grlbwt_fm> fm(new grlbwt_fm());
         fm->flags = fm_flags;
         if (big) {
             fm->f64.reset(new grl64::Engine::FmIndex());
-            grl64::Engine::fm_create(dev_image, image_bytes, locate, prim::sw().fm_top_bits, *fm->f64);
+            grl64::Engine::fm_create(dev_image, image_bytes, locate, prim::sw().fm_top_bits, *fm->f64, cps, (int)sample_bits);
         } else {
             fm->f32.reset(new grl32::Engine::FmIndex());
-            grl32::Engine::fm_create(dev_image, image_bytes, locate, prim::sw().fm_top_bits, *fm->f32);
+            grl32::Engine::fm_create(dev_image, image_bytes, locate, prim::sw().fm_top_bits, *fm->f32, cps, (int)sample_bits);
         }
         ctx->fms.push_back(fm.get());
         *out = fm.release();
@@ -1907,6 +1913,40 @@ int grlbwt_fm_info_get(const grlbwt_fm *fm, grlbwt_fm_info *out) {
     };
     if (fm->f32) fill(*fm->f32, 4); else fill(*fm->f64, 8);
     return GRLBWT_OK;
+}
+static const auto fill_walk_info = [](const auto &w, grlbwt_walk_info *out) {
+    out->n_strings = w.k; out->n_checkpoints = w.m; out->sample_bits = w.b;
+    out->longest_segment = w.longest_segment; out->longest_chain = w.longest_chain; out->jump_rounds = w.jump_rounds;
+    out->walk_lanes = w.lanes; out->lane_refills = w.refills; out->scratch_bytes = w.scratch_bytes; out->sample_bytes = w.sample_bytes;
+};
+int grlbwt_fm_walk_info_get(const grlbwt_fm *fm, grlbwt_walk_info *out) {
+    if (!fm || !out || !(fm->f32 || fm->f64)) return GRLBWT_EINVAL;
+    if (fm->f32 ? !fm->f32->checkpoints : !fm->f64->checkpoints) return GRLBWT_EINVAL;
+    if (fm->f32) fill_walk_info(fm->f32->walk, out); else fill_walk_info(fm->f64->walk, out);
+    return GRLBWT_OK;
+}
+int grlbwt_invert_image_checkpointed(grlbwt_ctx *ctx, const void *dev_image, uint64_t image_bytes, int cell_bytes, int sample_bits,
+                                     void *dev_text_out, uint64_t capacity_cells, uint64_t *n_cells_out, grlbwt_walk_info *info) {
+    if (!ctx || !dev_image || !dev_text_out) return GRLBWT_EINVAL;
+    return guarded(ctx, [&] {
+        if (sample_bits < 0 || sample_bits > 20) throw prim::Error(GRLBWT_EINVAL, "checkpointed walk: sample_bits is 0 (the default) or 1 to 20");
+        const uint64_t total = grl64::Engine::image_total_symbols(dev_image, image_bytes);
+        if (total > capacity_cells) throw prim::Error(GRLBWT_EINVAL, "inversion: output buffer too small");
+        const bool big = total >= kIdx32Limit || (ctx->flags & GRLBWT_FLAG_FORCE_IDX64);
+        uint64_t n;
+        grlbwt_walk_info wi;
+        if (big) {
+            grl64::Engine::WalkInfo w;
+            n = grl64::Engine::invert_image_checkpointed(dev_image, image_bytes, cell_bytes, sample_bits, dev_text_out, capacity_cells, w);
+            fill_walk_info(w, &wi);
+        } else {
+            grl32::Engine::WalkInfo w;
+            n = grl32::Engine::invert_image_checkpointed(dev_image, image_bytes, cell_bytes, sample_bits, dev_text_out, capacity_cells, w);
+            fill_walk_info(w, &wi);
+        }
+        if (n_cells_out) *n_cells_out = n;
+        if (info) *info = wi;
+    });
 }
 int grlbwt_fm_count(grlbwt_ctx *ctx, const grlbwt_fm *fm, const void *dev_cells, int cell_bytes, const uint64_t *dev_offsets,
                     uint64_t n_patterns, uint64_t *dev_lo, uint64_t *dev_hi) {

@@ -3276,6 +3276,212 @@ struct FmLocateFn {       // row -> (string, offset): LF steps until the row's s
     }
 };
 
+// ---- checkpointed LF walks.  The walks above run one lane per string, one dependent step per cell: their latency
+// is the longest string.  Cut at CHECKPOINT rows they become m = k + ceil(n / s) segments of about s = 2^b steps, which a list
+// ranking over the checkpoints puts back in order.  Rows [0, k) -- where the strings' walks start -- are checkpoints 0 .. k-1;
+// every block of s rows [j s, (j + 1) s) holds one more, checkpoint k + j, at j s + (mix(j) & (s - 1)) (reduced modulo the length
+// of the last, shorter block, so that every pick is a row).  A pick below k is void: that row is a head already.  LF is linear
+// inside a run, so a plain stride would correlate with the walks of a repetitive text: the pick is jittered by a fixed 64-bit
+// mixer.  Whether a row is a checkpoint, and which, is arithmetic: no array, no bit-vector.
+struct Checkpoints {
+    u64 n, k; u32 b;
+    GRL_HD static u64 mix(u64 j) {                         // (splitmix64)
+        u64 z = j + 0x9E3779B97F4A7C15ull;
+        z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+        z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+        return z ^ (z >> 31);
+    }
+    GRL_HD u64 blocks() const { return (n + (1ull << b) - 1) >> b; }
+    GRL_HD u64 count() const { return k + blocks(); }
+    GRL_HD u64 pick(u64 j) const {
+        const u64 s = 1ull << b, base = j << b, len = n - base < s ? n - base : s;
+        u64 off = mix(j) & (s - 1);
+        if (off >= len) off %= len;
+        return base + off;
+    }
+    GRL_HD u64 row_of(u64 c) const { return c < k ? c : pick(c - k); }
+    GRL_HD bool is_void(u64 c) const { return c >= k && pick(c - k) < k; }
+    GRL_HD u64 index_of(u64 row) const {                   // ~0: the row is no checkpoint (a row of [k, n) that is its block's pick is never void)
+        if (row < k) return row;
+        const u64 j = row >> b;
+        return pick(j) == row ? k + j : ~0ull;
+    }
+};
+static constexpr idx_t kCpNone = (idx_t)~(idx_t)0;        // no checkpoint / no string
+static constexpr idx_t kCpEnd = (idx_t)(kCpNone - 1);     // next[]: the segment ends its string
+// Phase A, one ticket per checkpoint c: LF steps from its row until the row reached is a checkpoint (next[c] = its number) or
+// holds the separator (next[c] = kCpEnd, and endcp[slot] = c for the slot FmSidFn computes: that separator's row among [0, k)).
+// seglen[c] = the steps.  A void checkpoint has next = none and no steps.  LF is a permutation and every row a walk starts at is a
+// checkpoint, so a walk is back at a checkpoint after at most n steps: the bound is there for an index that is not what it should be.
+struct CpSegFn {
+    struct State { idx_t row; u64 steps; idx_t to; };
+    const RankCell *rc; const RunRec *rec; u32 sep; Checkpoints cp; idx_t *seglen, *next, *endcp; u32 *bad;
+    GRL_DEV bool begin(u64 c, State &st) const {
+        if (cp.is_void(c)) { seglen[c] = 0; next[c] = kCpNone; return false; }
+        st.row = (idx_t)cp.row_of(c); st.steps = 0; st.to = kCpNone;
+        return true;
+    }
+    GRL_DEV bool step(State &st) const {
+        const RunRec r = rec[run_of_row(rc, (u64)st.row)];
+        if (r.sym == sep) { st.to = kCpEnd; st.row = (idx_t)(st.row + (idx_t)r.delta); return true; }
+        st.row = (idx_t)(st.row + (idx_t)r.delta);
+        st.steps++;
+        const u64 ci = cp.index_of((u64)st.row);
+        if (ci != ~0ull) { st.to = (idx_t)ci; return true; }
+        return st.steps >= cp.n;
+    }
+    GRL_DEV void end(u64 c, const State &st) const {
+        seglen[c] = (idx_t)st.steps;
+        next[c] = st.to;
+        if (st.to == kCpEnd) endcp[(u64)st.row] = (idx_t)c;
+        else if (st.to == kCpNone) prim::atomic_max(bad, 1u);
+    }
+};
+// Phase B, list ranking by pointer jumping over prev.  ptr[c] = the checkpoint in front of c on its chain, acc[c] = the steps
+// between them; a head points at itself with 0 steps, a checkpoint nobody reaches at nothing.
+struct CpInitFn {
+    u64 k; idx_t *ptr, *acc;
+    GRL_DEV void operator()(u64 c) const { ptr[c] = c < k ? (idx_t)c : kCpNone; acc[c] = 0; }
+};
+struct CpPrevFn {         // prev[next[c]] = c: next is one-to-one (LF is a permutation), so every slot has one writer
+    const idx_t *next, *seglen; idx_t *ptr, *acc;
+    GRL_DEV void operator()(u64 c) const {
+        const idx_t d = next[c];
+        if (d == kCpNone || d == kCpEnd) return;
+        ptr[(u64)d] = (idx_t)c; acc[(u64)d] = seglen[c];
+    }
+};
+struct CpJumpFn {         // one round, from generation (p0, a0) to (p1, a1)
+    const idx_t *p0, *a0; idx_t *p1, *a1;
+    GRL_DEV void operator()(u64 c) const {
+        const idx_t p = p0[c];
+        if (p == kCpNone) { p1[c] = p; a1[c] = a0[c]; return; }
+        const idx_t q = p0[(u64)p];
+        p1[c] = q == kCpNone ? p : q;
+        a1[c] = q == kCpNone ? a0[c] : (idx_t)(a0[c] + a0[(u64)p]);
+    }
+};
+struct CpMovedIn {
+    const idx_t *p0, *p1;
+    GRL_DEV u64 operator()(u64 c) const { return p0[c] != p1[c] ? 1ull : 0ull; }
+};
+struct CpHeadFn {         // after the rounds: ptr[c] is c's string where it is a head, none elsewhere (a chain that is a cycle has none)
+    u64 k; idx_t *ptr; u64 *chain;
+    GRL_DEV void operator()(u64 c) const {
+        const idx_t p = ptr[c];
+        if (p != kCpNone && (u64)p >= k) ptr[c] = kCpNone;
+        else if (p != kCpNone) prim::atomic_add(&chain[(u64)p], (u64)1);
+    }
+};
+struct CpLenFn {          // string lengths from the chains' last checkpoints: dist + steps + the separator
+    const idx_t *endcp, *head, *dist, *seglen; idx_t *slen; u32 *bad;
+    GRL_DEV void operator()(u64 slot) const {
+        const u64 e = (u64)endcp[slot];
+        const idx_t h = head[e];
+        if (h == kCpNone) { prim::atomic_max(bad, 1u); return; }
+        slen[(u64)h] = (idx_t)(dist[e] + seglen[e] + 1);
+    }
+};
+// Phase C of the inverter: phase A's walk again, every segment writing its cells backwards from the position its rank gives
+template <class cell_t>
+struct CpWriteFn {
+    struct State { idx_t row; u64 pos, left; };
+    const RankCell *rc; const RunRec *rec; u32 sep; Checkpoints cp; const idx_t *head, *dist, *seglen, *off; cell_t *text; const u64 *alpha;
+    GRL_DEV cell_t val(u32 c) const { return alpha ? (cell_t)alpha[c] : (cell_t)c; }
+    GRL_DEV bool begin(u64 c, State &st) const {
+        const idx_t h = head[c];
+        if (h == kCpNone) return false;
+        st.row = (idx_t)cp.row_of(c);
+        st.pos = (u64)off[(u64)h + 1] - 1 - (u64)dist[c];
+        st.left = (u64)seglen[c];
+        if (c < cp.k) text[st.pos] = val(sep);
+        return st.left != 0;
+    }
+    GRL_DEV bool step(State &st) const {
+        const RunRec r = rec[run_of_row(rc, (u64)st.row)];
+        text[--st.pos] = val(r.sym);
+        st.row = (idx_t)(st.row + (idx_t)r.delta);
+        return --st.left == 0;
+    }
+    GRL_DEV void end(u64, const State &) const {}
+};
+// The store form of the write walk for u8 / u16 cells into an 8-byte aligned text (CpWriteFn otherwise): the cells of one aligned
+// 8-byte word of the text are collected in a register and stored as that word.  A segment's first and last word are shared with its neighbours' segments: what a lane holds of
+// a word it does not own whole goes out cell by cell.  [pos, top) is what the register holds; it never crosses a word.
+template <class cell_t>
+struct CpWritePackedFn {
+    static constexpr u64 kPer = 8 / sizeof(cell_t), kBits = 8 * sizeof(cell_t);
+    struct State { idx_t row; u64 pos, left, top, acc; };
+    CpWriteFn<cell_t> w;
+    GRL_DEV bool begin(u64 c, State &st) const {
+        typename CpWriteFn<cell_t>::State s;
+        const bool go = w.begin(c, s);
+        st.row = s.row; st.pos = s.pos; st.left = s.left; st.top = s.pos; st.acc = 0;
+        return go;
+    }
+    GRL_DEV bool step(State &st) const {
+        const RunRec r = w.rec[run_of_row(w.rc, (u64)st.row)];
+        --st.pos;
+        st.acc |= (u64)w.val(r.sym) << ((st.pos & (kPer - 1)) * kBits);
+        st.row = (idx_t)(st.row + (idx_t)r.delta);
+        --st.left;
+        const bool bottom = (st.pos & (kPer - 1)) == 0;
+        if (bottom || st.left == 0) {
+            if (bottom && st.top - st.pos == kPer) *reinterpret_cast<u64 *>(w.text + st.pos) = st.acc;
+            else for (u64 q = st.pos; q < st.top; q++) w.text[q] = (cell_t)(st.acc >> ((q & (kPer - 1)) * kBits));      // (fewer than kPer cells)
+            st.top = st.pos; st.acc = 0;
+        }
+        return st.left == 0;
+    }
+    GRL_DEV void end(u64, const State &) const {}
+};
+template <class F>
+struct WalkSerialFn {     // the serial form of prim::walk_tickets: one item after the other through prim::for_each
+    F f;
+    GRL_DEV void operator()(u64 c) const {
+        typename F::State st;
+        if (!f.begin(c, st)) return;
+        while (!f.step(st)) {}
+        f.end(c, st);
+    }
+};
+// Phase C of the index: the string behind every separator from the chain ends, and per checkpoint the sample (string, offset of
+// the row's suffix in it)
+struct CpSidFn {
+    const idx_t *endcp, *head; idx_t *sid;
+    GRL_DEV void operator()(u64 slot) const { sid[slot] = head[(u64)endcp[slot]]; }
+};
+struct CpSampleFn {
+    const idx_t *head, *dist, *slen; idx_t *smp;
+    GRL_DEV void operator()(u64 c) const {
+        const idx_t h = head[c];
+        smp[2 * c] = h;
+        smp[2 * c + 1] = h == kCpNone ? kCpNone : (idx_t)(slen[(u64)h] - 1 - dist[c]);
+    }
+};
+// locate over an index with samples: the walk also stops at a checkpoint row; one met after t steps gives (string, offset + t).
+// A checkpoint without a string lies on a cycle of rows that holds no separator: the row has no position, as in FmLocateFn, whose
+// walk runs into its bound.  An offset above `lim` is suppressed: the contract is FmLocateFn's.
+struct FmLocateCpFn {
+    const RankCell *rc; const RunRec *rec; const idx_t *sid, *smp; Checkpoints cp; u32 sep; u64 lim; const u64 *rows; u64 *str, *ofs;
+    GRL_DEV void operator()(u64 i) const {
+        idx_t row = (idx_t)rows[i];
+        u64 rs = ~0ull, ro = ~0ull;
+        for (u64 s = 0; s <= lim; s++) {
+            const u64 ci = cp.index_of((u64)row);
+            if (ci != ~0ull) {
+                const idx_t h = smp[2 * ci];
+                if (h != kCpNone) { const u64 o = (u64)smp[2 * ci + 1] + s; if (o <= lim) { rs = (u64)h; ro = o; } }
+                break;
+            }
+            const RunRec r = rec[run_of_row(rc, (u64)row)];
+            if (r.sym == sep) { rs = (u64)sid[(u64)(idx_t)(row + (idx_t)r.delta)]; ro = s; break; }
+            row = (idx_t)(row + (idx_t)r.delta);
+        }
+        str[i] = rs; ofs[i] = ro;
+    }
+};
+
 // =========================================================================
 struct RoundInfo {
     u64 n_in = 0, D = 0, S = 0, M = 0, parse_size = 0, sigma = 0, max_phrase_len = 0, sort_iters = 0, table_retries = 0;
@@ -5974,6 +6180,103 @@ class Engine {
         return n;
     }
 
+    // ---- checkpointed LF walks (functor block "checkpointed LF walks") -------------------------------------
+    // lf_checkpoints: phases A and B on the rc + rec arrays run_index_lf(X, true, ...) makes.  Scratch: six idx_t arrays of m
+    // (seglen, next, two generations of (ptr, acc)) and two per string.  On return head[c] / dist[c] are c's string and the LF
+    // steps from that string's end row to c, slen[i] is the length of string i (separator included) and endcp[j] the checkpoint
+    // whose segment ends at the j-th separator.
+    //   Loops: the segment walks are bounded by n steps each; the pointer jumping runs a counted number of rounds, at most
+    //   ceil(log2 m), and ends early when a reduce says that no pointer moved; nothing waits for another thread.
+    struct WalkInfo { u64 k = 0, m = 0, b = 0, longest_segment = 0, longest_chain = 0, jump_rounds = 0, lanes = 0, refills = 0, scratch_bytes = 0, sample_bytes = 0; };
+    static constexpr bool kWalkPackedStores(char sw) { return sw != 'c'; }      // the store form of the write walk: words won
+    static constexpr int kDefaultSampleBits = 8;      // what sample_bits = 0 means
+    static int sample_bits_of(int b) {
+        if (b < 0 || b > 20) throw prim::Error(-22, "checkpointed walk: sample_bits is 0 (the default) or 1 to 20");
+        return b ? b : kDefaultSampleBits;
+    }
+    struct CpRank {
+        Checkpoints cp{0, 0, 0};
+        DBuf<idx_t> seglen, next, head, dist, ptr2, acc2, endcp, slen;
+    };
+    template <class F>
+    static void walk(u64 m, F f, WalkInfo &wi, const char *name) {
+#ifdef GRLBWT_PRIM_HIP
+        DBuf<u64> ctr(2);
+        const prim::WalkStats ws = prim::walk_tickets(m, f, ctr.p, name);
+        wi.lanes = ws.lanes; wi.refills = ws.refills;
+#else
+        prim::for_each(m, WalkSerialFn<F>{f}, name);
+        wi.lanes = m; wi.refills = 0;
+#endif
+    }
+    static void lf_checkpoints(const RankCell *rc, const RunRec *rec, u64 n, u64 k, u32 sep, int b, int bad_code, CpRank &C, WalkInfo &wi) {
+        const Checkpoints cp{n, k, (u32)b};
+        const u64 m = cp.count();
+        if (m >= (u64)kCpEnd) throw prim::Error(-75, "checkpointed walk: more checkpoints than positions of this width can number");
+        C.cp = cp;
+        wi.k = k; wi.m = m; wi.b = (u64)b;
+        wi.scratch_bytes = (6 * m + 2 * k + 1) * sizeof(idx_t) + k * 8;
+        C.seglen.alloc(m); C.next.alloc(m); C.head.alloc(m); C.dist.alloc(m); C.ptr2.alloc(m); C.acc2.alloc(m);
+        C.endcp.alloc(k); C.slen.alloc(k + 1);
+        DBuf<u32> bad(1);
+        bad.zero();
+        walk(m, CpSegFn{rc, rec, sep, cp, C.seglen.p, C.next.p, C.endcp.p, bad.p}, wi, "cp.segments");
+        if (bad.get(0)) throw prim::Error(bad_code, "checkpointed walk: a segment met no checkpoint in n steps: not the BWT of a collection");
+        wi.longest_segment = prim::reduce_max<u64>(m, IdxIn64{C.seglen.p}, "cp.longest");
+        prim::for_each(m, CpInitFn{k, C.head.p, C.dist.p}, "cp.init");
+        prim::for_each(m, CpPrevFn{C.next.p, C.seglen.p, C.head.p, C.dist.p}, "cp.prev");
+        const u64 cap = m > 1 ? (u64)bitlen64(m - 1) : 0;       // ceil(log2 m)
+        for (u64 r = 0; r < cap; r++) {
+            prim::for_each(m, CpJumpFn{C.head.p, C.dist.p, C.ptr2.p, C.acc2.p}, "cp.jump");
+            wi.jump_rounds++;
+            const u64 moved = prim::reduce_sum<u64>(m, CpMovedIn{C.head.p, C.ptr2.p}, "cp.moved");
+            std::swap(C.head, C.ptr2);
+            std::swap(C.dist, C.acc2);
+            if (!moved) break;
+        }
+        C.ptr2.release(); C.acc2.release(); C.next.release();
+        DBuf<u64> chain(k);
+        chain.zero();
+        prim::for_each(m, CpHeadFn{k, C.head.p, chain.p}, "cp.heads");
+        wi.longest_chain = prim::reduce_max<u64>(k, CellIn<u64>{chain.p}, "cp.chains");
+        C.slen.zero();
+        prim::for_each(k, CpLenFn{C.endcp.p, C.head.p, C.dist.p, C.seglen.p, C.slen.p, bad.p}, "cp.lengths");
+        if (bad.get(0)) throw prim::Error(bad_code, "checkpointed walk: a string's end lies on no string's chain: not the BWT of a collection");
+    }
+    template <class cell_t>
+    static u64 invert_checkpointed_t(const u8 *img, u64 R, u32 sb, u32 fb, cell_t *text_out, u64 capacity, const WideSyms &W, int b, WalkInfo &wi) {
+        RunIndex X;
+        run_index_load(img, R, sb, fb, W, X);
+        const u64 n = X.n;
+        if (n > capacity) throw prim::Error(-22, "inversion: output buffer too small");
+        run_index_lf(X, true, false);
+        CpRank C;
+        lf_checkpoints(X.rc.p, X.rec.p, n, X.k, X.sep, b, -71, C, wi);
+        const u64 tot = (u64)prim::exclusive_scan<idx_t>(X.k, IdxIn<idx_t>{C.slen.p}, C.slen.p, true, "inv.offsets");
+        if (tot != n) throw prim::Error(-71, "inversion: string lengths do not add up to the BWT length");
+        const CpWriteFn<cell_t> wf{X.rc.p, X.rec.p, X.sep, C.cp, C.head.p, C.dist.p, C.seglen.p, C.slen.p, text_out, W.alpha.p};
+        bool packed = false;
+        if constexpr (sizeof(cell_t) <= 2) packed = kWalkPackedStores(prim::sw().dev_walk_stores) && ((uintptr_t)text_out & 7) == 0;
+        if constexpr (sizeof(cell_t) <= 2) { if (packed) walk(wi.m, CpWritePackedFn<cell_t>{wf}, wi, "cp.write_packed"); }
+        if (!packed) walk(wi.m, wf, wi, "cp.write");
+        prim::sync();
+        return n;
+    }
+    static u64 invert_image_checkpointed(const void *dev_image, u64 image_bytes, int cell_bytes, int sample_bits, void *dev_text_out, u64 capacity_cells, WalkInfo &wi) {
+        const int b = sample_bits_of(sample_bits);
+        const ImageHeader h = image_header(dev_image, image_bytes);
+        const u8 *img = (const u8 *)dev_image;
+        if (!(cell_bytes == 1 || cell_bytes == 2 || cell_bytes == 4 || cell_bytes == 8)) throw prim::Error(-22, "bad cell width");
+        WideSyms W;
+        image_symbols(img, h.R, (u32)h.sb, (u32)h.fb, cell_bytes, W);
+        switch (cell_bytes) {
+            case 1: return invert_checkpointed_t<u8>(img, h.R, (u32)h.sb, (u32)h.fb, (u8 *)dev_text_out, capacity_cells, W, b, wi);
+            case 2: return invert_checkpointed_t<u16>(img, h.R, (u32)h.sb, (u32)h.fb, (u16 *)dev_text_out, capacity_cells, W, b, wi);
+            case 4: return invert_checkpointed_t<u32>(img, h.R, (u32)h.sb, (u32)h.fb, (u32 *)dev_text_out, capacity_cells, W, b, wi);
+            default: return invert_checkpointed_t<u64>(img, h.R, (u32)h.sb, (u32)h.fb, (u64 *)dev_text_out, capacity_cells, W, b, wi);
+        }
+    }
+
     // the last `tail` cells of every string (slot i of `tail` cells holds string i's end, right-aligned); returns the cells written
     static u64 invert_image_tails(const void *dev_image, u64 image_bytes, int cell_bytes, u64 tail, void *dev_out, u64 capacity_cells, u64 *n_strings_out) {
         if (image_bytes < 16 || tail == 0) throw prim::Error(-22, "not an .rl_bwt image, or no tail length");
@@ -6041,14 +6344,20 @@ class Engine {
         DBuf<RankCell> rc;        // locate: LF of any row (run_of_row + rec) and the string behind every separator
         DBuf<RunRec> rec;
         DBuf<idx_t> sid;
+        bool checkpoints = false; // locate with samples: (string, offset) of every checkpoint row, two idx_t each
+        Checkpoints cp{0, 0, 0};
+        DBuf<idx_t> smp;
+        WalkInfo walk;
         u64 bytes() const {
-            return key.n * sizeof(FmKey) + slf.n * sizeof(idx_t) + alpha.n * 8 + rc.n * sizeof(RankCell) + rec.n * sizeof(RunRec) + sid.n * sizeof(idx_t);
+            return key.n * sizeof(FmKey) + slf.n * sizeof(idx_t) + alpha.n * 8 + rc.n * sizeof(RankCell) + rec.n * sizeof(RunRec) + sid.n * sizeof(idx_t) +
+                   smp.n * sizeof(idx_t);
         }
     };
     // What the locate structures may take while they are made: half of the free device memory (a quarter byte per symbol for the
     // bit-vector and its ranks, a word per string).  The serial stand-in, which walks the strings one after the other, stops at 256 MB.
     static u64 fm_locate_budget() { return prim::kIsDevice ? prim::mem_available() / 2 : (u64)1 << 28; }
-    static void fm_create(const void *dev_image, u64 image_bytes, bool locate, int top_bits, FmIndex &F) {
+    static void fm_create(const void *dev_image, u64 image_bytes, bool locate, int top_bits, FmIndex &F, bool checkpoints = false, int sample_bits = 0) {
+        const int b = checkpoints ? sample_bits_of(sample_bits) : 0;
         const ImageHeader h = image_header(dev_image, image_bytes);
         if (h.R == 0) throw prim::Error(-22, "fm index: the image has no record");
         if (top_bits < 0 || top_bits > 12) throw prim::Error(-22, "fm index: the top level takes 0 to 12 bits");
@@ -6061,7 +6370,8 @@ class Engine {
         F.n = X.n; F.R = X.R; F.k = X.k; F.sep = X.sep; F.locate = locate;
         if (locate) {
             const u64 words = (X.n + 1) / 64 + 2;
-            const u64 need = words * (sizeof(RankCell) + 8 + sizeof(idx_t)) + X.R * sizeof(RunRec) + X.k * sizeof(idx_t);
+            u64 need = words * (sizeof(RankCell) + 8 + sizeof(idx_t)) + X.R * sizeof(RunRec) + X.k * sizeof(idx_t);
+            if (checkpoints) need += (Checkpoints{X.n, X.k, (u32)b}.count() * 8 + 2 * X.k + 1) * sizeof(idx_t) + X.k * 8;       // the ranking's scratch and the samples
             if (X.n >= ((u64)1 << 62) || need > fm_locate_budget())
                 throw prim::Error(-22, "fm index: the structures for locating (" + std::to_string(need) + " bytes) are more than this device can hold");
         }
@@ -6073,7 +6383,19 @@ class Engine {
 #ifdef GRLBWT_PRIM_HIP
         F.top_entries = prim::top_search_entries(top_bits, F.R, sizeof(FmKey));
 #endif
-        if (locate && F.R) {
+        if (locate && F.R && checkpoints) {
+            // sid from the chain ends (FmSidFn is not run) and the samples.  An image with rows on no string's chain (cycles of LF
+            // without a separator) is accepted as without checkpoints: such rows have no position, their samples say so.
+            CpRank C;
+            lf_checkpoints(F.rc.p, F.rec.p, F.n, F.k, F.sep, b, -22, C, F.walk);
+            F.checkpoints = true;
+            F.cp = C.cp;
+            F.sid.alloc(F.k);
+            prim::for_each(F.k, CpSidFn{C.endcp.p, C.head.p, F.sid.p}, "fm.sid_chains");
+            F.smp.alloc(2 * F.walk.m);
+            prim::for_each(F.walk.m, CpSampleFn{C.head.p, C.dist.p, C.slen.p, F.smp.p}, "fm.samples");
+            F.walk.sample_bytes = F.smp.n * sizeof(idx_t);
+        } else if (locate && F.R) {
             DBuf<u32> bad(1);
             bad.zero();
             F.sid.alloc(F.k);
@@ -6108,7 +6430,9 @@ class Engine {
         if (!F.locate) throw prim::Error(-22, "fm locate: the index was made without the structures for locating");
         if (nr == 0) return;
         if (prim::reduce_sum<u64>(nr, FmRowBadIn{rows, F.n}, "fm.rows")) throw prim::Error(-22, "fm locate: a row is not below the number of symbols");
-        prim::for_each(nr, FmLocateFn{F.rc.p, F.rec.p, F.sid.p, F.sep, max_steps < F.n ? max_steps : F.n, rows, str, ofs}, "fm.locate");
+        const u64 lim = max_steps < F.n ? max_steps : F.n;
+        if (F.checkpoints) prim::for_each(nr, FmLocateCpFn{F.rc.p, F.rec.p, F.sid.p, F.smp.p, F.cp, F.sep, lim, rows, str, ofs}, "fm.locate_cp");
+        else prim::for_each(nr, FmLocateFn{F.rc.p, F.rec.p, F.sid.p, F.sep, lim, rows, str, ofs}, "fm.locate");
         prim::sync();
     }
 

@@ -4003,4 +4003,100 @@ inline u32 top_search_entries(int bits, u64 n_keys, size_t key_bytes) {
     return b ? (u32)1 << b : 0;
 }
 
+// ------------------------------------------------------------------ walks of uneven length: lanes that take tickets
+// m work items ("tickets"), each a chain of dependent steps whose number is known only when it ends (the segments of a
+// checkpointed LF walk: near-geometric lengths).  One item per lane through k_for_each makes a wave last as long as the longest
+// of its 64 items, about ln 64 = 4 times the mean, with most lanes idle most of the time.  Here a lane that finishes an item takes
+// the next ticket.  The functor:
+//     typename F::State
+//     bool begin(u64 ticket, State &)    false: nothing to walk (the item is complete)
+//     bool step(State &)                 one step; true: that was the item's last one
+//     void end(u64 ticket, State &)
+//   Launch: 256-thread workgroups, as many as the CUs hold at once (occupancy query, as top_search); GRLBWT_WALK_LANES sets
+//     another number of lanes, rounded up to a wave; never more than m rounded up to a wave.  Waves past the last lane leave at once.
+//   Tickets: lane g starts with ticket g.  Tickets from `lanes` on come from ONE word in device memory (zeroed before the launch),
+//     64 at a time per WAVE: the wave keeps [r_next, r_end) in scalar registers and hands them to its idle lanes by their rank
+//     in the ballot; only an empty reserve costs an atomic.  The rate, ESTIMATED, not measured: 8192 resident waves (the functors here take fewer than 64
+//     vector registers) whose lanes each end an item every 2^b steps of ~2 us end 64 / 2^b items per step and wave -- at b = 8
+//     that would be ~1000 returning atomics per us on one word, against the ~88 per us one word is documented to take; a reserve
+//     of 64 divides the rate by 64, so one word is enough and there is no per-XCD head.  (Where m is below the resident lanes --
+//     b >= 8 on 32 M cells -- no ticket is drawn at all.)
+//   The main loop is WAVE-UNIFORM: every lane of the wave stays in it until the wave leaves, the ballot, the broadcast and the
+//     atomic's branch are reached under full EXEC, and only begin / step / end run predicated per lane.
+//   Loops: the main loop runs once per step of the wave's longest-running lane plus once per refill, and every item's steps are
+//     bounded by its functor; the reserve is refilled at most (m - lanes) / 64 + 1 times over all waves; nothing waits for another
+//     thread.
+//   Counters (ctr[1]): tickets taken from the word by a lane that had finished an item ("refills"), summed per wave on leaving.
+static constexpr int kWalkThreads = 256;
+static constexpr u64 kWalkReserve = 64;
+struct WalkStats { u64 lanes = 0, refills = 0; };
+template <class F>
+__global__ void __launch_bounds__(kWalkThreads) k_walk_tickets(u64 m, u64 lanes, F f, u64 *ctr) {
+    const u64 gid = (u64)blockIdx.x * kWalkThreads + threadIdx.x;
+    if (gid >= lanes) return;                                   // (lanes is a multiple of 64: whole waves)
+    const u32 lane = threadIdx.x & 63u;
+    typename F::State st;
+    u64 ticket = gid;
+    bool active = gid < m && f.begin(ticket, st);
+    u64 r_next = 0, r_end = 0;                                  // the wave's reserve of tickets
+    bool more = lanes < m;                                      // the word may still hold tickets
+    u32 taken = 0;
+    for (;;) {
+        const u64 idle = __ballot(!active);
+        if (idle && r_next >= r_end && more) {
+            const u32 first = (u32)__builtin_ctzll(idle);
+            u64 base = 0;
+            if (lane == first) base = atomic_add(&ctr[0], kWalkReserve);
+            base = __shfl(base, (int)first);
+            const u32 lo = __builtin_amdgcn_readfirstlane((u32)base), hi = __builtin_amdgcn_readfirstlane((u32)(base >> 32));
+            r_next = lanes + ((u64)hi << 32 | lo);
+            r_end = r_next + kWalkReserve < m ? r_next + kWalkReserve : m;
+            more = r_next + kWalkReserve < m;
+            if (r_next > r_end) r_next = r_end;
+        }
+        if (idle && r_next < r_end) {
+            const u64 have = r_end - r_next;
+            const u32 rank = (u32)__builtin_popcountll(idle & ((1ull << lane) - 1ull));
+            if (!active && rank < have) {
+                ticket = r_next + rank;
+                taken++;
+                active = f.begin(ticket, st);
+            }
+            const u64 n_idle = (u64)__builtin_popcountll(idle);
+            r_next += n_idle < have ? n_idle : have;
+        }
+        if (!__any(active)) {
+            if (r_next >= r_end && !more) break;
+            continue;
+        }
+        if (active && f.step(st)) { f.end(ticket, st); active = false; }
+    }
+    u32 sum = taken;
+    for (int d = 32; d > 0; d >>= 1) sum += __shfl_xor(sum, d);
+    if (lane == 0 && sum) atomic_add(&ctr[1], (u64)sum);
+}
+// ctr: two words of device memory, the caller's; they are zeroed here
+template <class F>
+inline WalkStats walk_tickets(u64 m, F f, u64 *ctr, const char *name = "walk_tickets") {
+    WalkStats ws;
+    if (m == 0) return ws;
+    int occ = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_walk_tickets<F>, kWalkThreads, 0) != hipSuccess || occ < 1) { (void)hipGetLastError(); occ = 1; }
+    const u64 m_up = (m + 63) / 64 * 64;
+    u64 lanes = sw().walk_lanes ? (sw().walk_lanes + 63) / 64 * 64 : (u64)rt().num_cus * (u64)occ * kWalkThreads;
+    if (lanes > m_up) lanes = m_up;
+    const u64 blocks = (lanes + kWalkThreads - 1) / kWalkThreads;
+    if (blocks > 0x7FFFFFFFull) throw Error(-75, std::string(name) + ": too many workgroups");
+    dev_memset(ctr, 0, 16);
+    prof_begin(name);
+    hipLaunchKernelGGL((k_walk_tickets<F>), dim3((unsigned)blocks), dim3(kWalkThreads), 0, rt().stream, m, lanes, f, ctr);
+    prof_end();
+    after_launch(name);
+    u64 h[2];
+    d2h(h, ctr, 16);
+    ws.lanes = lanes;
+    ws.refills = h[1];
+    return ws;
+}
+
 }   // namespace prim

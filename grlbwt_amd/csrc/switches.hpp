@@ -41,6 +41,7 @@
     X(GRLBWT_XS_MAXC, xs_maxc, int, 32, "most cells per item the fused expansion sort takes (lower: the unfused branch)")        \
     X(GRLBWT_ALPHA_TABLE_BITS, alpha_table_bits, int, 20, "log2 of the slots of the alphabet compaction's table, 2..26 (lower: the sorting regime)") \
     X(GRLBWT_FM_TOP_BITS, fm_top_bits, int, 12, "log2 of the keys of an FM index's search array kept in LDS, 0..12 (0: none; lower: small indexes search HBM)") \
+    X(GRLBWT_WALK_LANES, walk_lanes, uint64_t, 0, "most lanes of a checkpointed walk launch, rounded up to a wave (0: from occupancy; lower: small inputs refill their lanes)") \
     X(GRLBWT_IO_THREADS, io_threads, int, 0, "reader / writer threads per file chunk, 1..64 (0: from the host's cores)")         \
     X(GRLBWT_QUIET_ENV, quiet_env, bool, false, "no note on stderr about the switches set in the environment")
 
@@ -85,6 +86,7 @@
     X(GRLBWT_RS_THREADS_XS, rs_threads_xs, int, 0, "the same for the sorts behind the fused expansion")                      \
     X(GRLBWT_SM_SPT, sm_spt, int, 0, "segments per thread of the segment merge, 4 or 8 (0: by the level)")                  \
     X(GRLBWT_DEV_SM1_SPT, dev_sm1_spt, int, 0, "segments per thread of the one-walk pass C, 4 or 8 (0: by the level)")      \
+    X(GRLBWT_DEV_WALK_STORES, dev_walk_stores, char, 0, "c[ells]: the checkpointed write walk stores u8/u16 cells one by one, not collected as aligned 8-byte words") \
     X(GRLBWT_DEV_LB_PATIENCE, dev_lb_patience, uint64_t, 200000000, "clock ticks a look-back tile waits before it gives up")
 
 namespace prim {

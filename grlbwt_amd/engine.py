@@ -34,15 +34,22 @@ ABI_SYMBOLS = [
     "grlbwt_level_grammar_size", "grlbwt_level_grammar_download",
     "grlbwt_alphabet_size", "grlbwt_alphabet_download", "grlbwt_alphabet_compact_device",
     "grlbwt_fm_create", "grlbwt_fm_destroy", "grlbwt_fm_info_get", "grlbwt_fm_count", "grlbwt_fm_locate",
+    "grlbwt_invert_image_checkpointed", "grlbwt_fm_walk_info_get",
 ]
 
 FM_LOCATE = 1
+FM_CHECKPOINTS = 2
 UINT64_MAX = 2 ** 64 - 1
 
 
 class FmInfo(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in ("n_syms", "n_runs", "n_strings", "sigma", "separator", "idx_bytes", "index_bytes",
                                           "top_entries", "flags")]
+
+
+class WalkInfo(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("n_strings", "n_checkpoints", "sample_bits", "longest_segment", "longest_chain",
+                                          "jump_rounds", "walk_lanes", "lane_refills", "scratch_bytes", "sample_bytes")]
 
 
 class ImageStats(C.Structure):
@@ -179,6 +186,8 @@ def load_library(path=None, allow_test_standin=False):
     L.grlbwt_selftest.argtypes = [vp, u64, u64]
     L.grlbwt_memory_usage.argtypes = [vp, C.POINTER(u64), C.POINTER(u64)]
     L.grlbwt_invert_image.argtypes = [vp, vp, u64, i32, vp, u64, C.POINTER(u64)]
+    L.grlbwt_invert_image_checkpointed.argtypes = [vp, vp, u64, i32, i32, vp, u64, C.POINTER(u64), C.POINTER(WalkInfo)]
+    L.grlbwt_fm_walk_info_get.argtypes = [vp, C.POINTER(WalkInfo)]
     L.grlbwt_invert_image_tails.argtypes = [vp, vp, u64, i32, u64, vp, u64, C.POINTER(u64), C.POINTER(u64)]
     L.grlbwt_image_plain.argtypes = [vp, vp, u64, vp, u64, i32, C.POINTER(u64)]
     L.grlbwt_image_rle.argtypes = [vp, vp, u64, vp, vp, u64, C.POINTER(u64)]
@@ -408,6 +417,14 @@ class Context:
                                             C.c_void_p(dev_out_ptr), capacity_cells, C.byref(n)))
         return n.value
 
+    def invert_image_checkpointed(self, dev_image_ptr, image_bytes, cell_bytes, dev_out_ptr, capacity_cells, sample_bits=0):
+        """invert_image for collections of long strings: the LF walks cut at checkpoint rows, one in 2^sample_bits (0: the
+        default); returns (#cells, the walk's counters)."""
+        n, info = C.c_uint64(), WalkInfo()
+        self._ck(self.L.grlbwt_invert_image_checkpointed(self._h, C.c_void_p(dev_image_ptr), image_bytes, cell_bytes, sample_bits,
+                                                         C.c_void_p(dev_out_ptr), capacity_cells, C.byref(n), C.byref(info)))
+        return n.value, _as_dict(info)
+
     def invert_image_tails(self, dev_image_ptr, image_bytes, cell_bytes, tail_cells, dev_out_ptr, capacity_cells):
         """The last `tail_cells` cells of every string (slot i of the output: string i's end, right-aligned); returns
         (strings, cells written)."""
@@ -470,13 +487,25 @@ class Context:
 
 class FmIndex:
     """Count and locate patterns in an .rl_bwt image (grlbwt_fm_*): an index made from an image in device memory, which may
-    be freed afterwards.  All pointers are device pointers; locate=True also builds what locate() needs."""
+    be freed afterwards.  All pointers are device pointers; locate=True also builds what locate() needs, checkpoints=True
+    (with locate) the samples that bound a locate walk by 2^sample_bits steps (0: the default) whatever the strings' lengths."""
 
-    def __init__(self, ctx, dev_image_ptr, image_bytes, locate=False):
+    def __init__(self, ctx, dev_image_ptr, image_bytes, locate=False, checkpoints=False, sample_bits=0):
         self.ctx = ctx
         h = C.c_void_p()
-        ctx._ck(ctx.L.grlbwt_fm_create(ctx._h, C.c_void_p(dev_image_ptr), image_bytes, FM_LOCATE if locate else 0, C.byref(h)))
+        if not 0 <= sample_bits <= 255:
+            raise GrlbwtError(-22, "sample_bits is 0 or 1 to 20")
+        flags = (FM_LOCATE if locate else 0) | (FM_CHECKPOINTS if checkpoints else 0) | (sample_bits << 8)
+        ctx._ck(ctx.L.grlbwt_fm_create(ctx._h, C.c_void_p(dev_image_ptr), image_bytes, flags, C.byref(h)))
         self._h = h
+
+    def walk_info(self):
+        """The counters of the checkpointed walks that made this index (an index without checkpoints: GrlbwtError)."""
+        out = WalkInfo()
+        rc = self.ctx.L.grlbwt_fm_walk_info_get(self._h, C.byref(out))
+        if rc != OK:
+            raise GrlbwtError(rc, self.ctx.L.grlbwt_strerror(rc).decode())
+        return _as_dict(out)
 
     def info(self):
         out = FmInfo()

@@ -217,13 +217,34 @@ int grlbwt_invert_image(grlbwt_ctx *ctx, const void *dev_image, uint64_t image_b
 
 /* The same LF walk (scripts/reverse_bwt.cpp:36-52), stopped after tail_cells steps per string: slot i of dev_out (tail_cells cells wide)
  * receives the LAST min(length, tail_cells) cells of string i, separator included, right-aligned; the cells in front of them are
- * left as they were.  *n_strings_out = strings, *n_cells_out = cells written.  For collections whose strings are too long to walk
- * end to end in a test's time (100 strings of 249 M cells: 249 M dependent steps each): the ends of all strings check the ORDER of
- * the BWT, which a symbol-count comparison does not.  capacity_cells >= strings * tail_cells. */
+ * left as they were.  *n_strings_out = strings, *n_cells_out = cells written.  COST: one lane per string, tail_cells dependent
+ * steps each.  It was made for collections whose strings grlbwt_invert_image cannot walk end to end in a test's time (100 strings
+ * of 249 M cells: 249 M dependent steps each): the ends of all strings check the ORDER of the BWT, which a symbol-count comparison
+ * does not.  The whole of such a collection comes back through grlbwt_invert_image_checkpointed below, whose walks are cut into
+ * segments.  capacity_cells >= strings * tail_cells. */
 int grlbwt_invert_image_tails(grlbwt_ctx *ctx, const void *dev_image, uint64_t image_bytes, int cell_bytes, uint64_t tail_cells,
                               void *dev_out, uint64_t capacity_cells, uint64_t *n_strings_out, uint64_t *n_cells_out);
 
-/* Accepted input of every consumer (grlbwt_invert_image and _tails above included): ANY well-formed image, not only
+/* ---- checkpointed LF walks: the inversion and the locate index for collections of LONG strings.  The walks above run one lane per
+ * string, one dependent step per cell.  Here they are cut at checkpoint rows: rows [0, n_strings) and one row, picked by a fixed
+ * mixer, in every block of 2^sample_bits rows -- n_checkpoints = n_strings + ceil(n_syms / 2^sample_bits) segments of about
+ * 2^sample_bits steps each, walked by lanes that take the next segment when they finish one, and put back in order by a list
+ * ranking over the checkpoints.  sample_bits: 1..20, 0 = the default (8); anything else is GRLBWT_EINVAL.
+ * grlbwt_invert_image_checkpointed writes byte for byte what grlbwt_invert_image writes, accepts the same images and refuses the
+ * same ones with the same codes (in 32-bit positions also GRLBWT_ERANGE for 2^32 - 2 checkpoints or more).  It always takes the
+ * run-indexed form; its scratch -- six words of the position width per checkpoint, three per string -- is released before it returns. */
+typedef struct grlbwt_walk_info {
+    uint64_t n_strings, n_checkpoints, sample_bits;   /* m = n_strings + ceil(n_syms / 2^sample_bits) */
+    uint64_t longest_segment, longest_chain;          /* LF steps; checkpoints on one string's chain */
+    uint64_t jump_rounds;                             /* pointer-jumping rounds run */
+    uint64_t walk_lanes, lane_refills;                /* of the last walk launch */
+    uint64_t scratch_bytes, sample_bytes;             /* peak scratch; bytes kept in an index (0 for the inverter) */
+} grlbwt_walk_info;
+int grlbwt_invert_image_checkpointed(grlbwt_ctx *ctx, const void *dev_image, uint64_t image_bytes, int cell_bytes,
+                                     int sample_bits, void *dev_text_out, uint64_t capacity_cells,
+                                     uint64_t *n_cells_out, grlbwt_walk_info *info /* may be NULL */);
+
+/* Accepted input of every consumer (grlbwt_invert_image, _tails and _checkpointed above included): ANY well-formed image, not only
  * what grlbwt_build writes -- header widths of 1..8 bytes each, records of length 0 (they contribute nothing, as in the
  * reference's reader; grlbwt_image_split_runs writes such records itself), neighbouring records with the same symbol, run
  * lengths and totals of 2^32 and more.  An image without any record (16 bytes) is legal for plain, rle and split_runs
@@ -286,15 +307,24 @@ int grlbwt_image_split_runs(grlbwt_ctx *ctx, const void *dev_image, uint64_t ima
  *
  * grlbwt_fm_locate (needs GRLBWT_FM_LOCATE): for every row of dev_rows (each < n_syms, else GRLBWT_EINVAL) the string, by
  * its number in input order, and the offset inside it at which the row's suffix starts.  COST: one dependent LF step per
- * cell between the occurrence and the START of its string -- the per-string cost model of grlbwt_invert_image_tails: meant
- * for read-like collections (strings of a few hundred cells), not for a collection of chromosomes.  The walk of a row stops
+ * cell between the occurrence and the START of its string -- the per-string cost model of grlbwt_invert_image_tails: fine
+ * for read-like collections (strings of a few hundred cells).  For a collection of chromosomes make the index with
+ * GRLBWT_FM_LOCATE | GRLBWT_FM_CHECKPOINTS: its walks end at the next checkpoint row, within about 2^sample_bits steps, and
+ * making it walks segments instead of whole strings.  The walk of a row stops
  * after min(max_steps, n_syms) steps (UINT64_MAX: no cap of the caller's): an occurrence at offset o is resolved exactly when
  * o <= max_steps, an unresolved row gets UINT64_MAX in both outputs.
  * GRLBWT_FM_LOCATE adds to the index the run-start bit-vector with its ranks (a quarter byte per symbol), one LF record
  * per run and one word per string -- the number of the string behind every separator of the BWT, found by one walk over
  * every string when the index is made (the separators of a BCR BWT are ordered by the strings' contents, not by their
  * numbers).  An image whose walks do not end (not the BWT of a collection), or whose structures would take more than half
- * of the free device memory, is refused with GRLBWT_EINVAL when this flag is given, and accepted without it. */
+ * of the free device memory, is refused with GRLBWT_EINVAL when this flag is given, and accepted without it.
+ *
+ * GRLBWT_FM_CHECKPOINTS (with GRLBWT_FM_LOCATE; alone: GRLBWT_EINVAL) keeps, per checkpoint row of the walks above, the (string,
+ * offset) of that row's suffix -- two words of the position width each, counted in index_bytes and in the budget -- and finds
+ * the strings behind the separators from the ranked segments instead of by a walk over every string.  GRLBWT_FM_SAMPLE_BITS(b)
+ * in fm_flags sets sample_bits (0 or 1..20; a value without GRLBWT_FM_CHECKPOINTS, or above 20: GRLBWT_EINVAL, *out = NULL).  grlbwt_fm_locate on such an index stops at a checkpoint row as well as at a separator; its
+ * contract and its outputs are those of the index without checkpoints for every row and every max_steps (an answer found through
+ * a sample whose offset is above max_steps is suppressed).  grlbwt_fm_walk_info_get: GRLBWT_EINVAL for an index without checkpoints. */
 typedef struct grlbwt_fm grlbwt_fm;
 #define GRLBWT_FM_LOCATE 1u      /* also build what grlbwt_fm_locate needs (one LF walk over every string, like the inverter's length pass) */
 typedef struct grlbwt_fm_info {
@@ -303,9 +333,12 @@ typedef struct grlbwt_fm_info {
     uint64_t idx_bytes, index_bytes;      /* 4 or 8; device bytes the index holds */
     uint64_t top_entries, flags;          /* entries of the LDS top level (0: none), fm_flags as given */
 } grlbwt_fm_info;
+#define GRLBWT_FM_CHECKPOINTS 2u                        /* with GRLBWT_FM_LOCATE; alone: GRLBWT_EINVAL */
+#define GRLBWT_FM_SAMPLE_BITS(b) ((uint32_t)(b) << 8)   /* in fm_flags; 0 = default */
 int grlbwt_fm_create(grlbwt_ctx *ctx, const void *dev_image, uint64_t image_bytes, uint32_t fm_flags, grlbwt_fm **out);
 int grlbwt_fm_destroy(grlbwt_ctx *ctx, grlbwt_fm *fm);
 int grlbwt_fm_info_get(const grlbwt_fm *fm, grlbwt_fm_info *out);
+int grlbwt_fm_walk_info_get(const grlbwt_fm *fm, grlbwt_walk_info *out);
 int grlbwt_fm_count(grlbwt_ctx *ctx, const grlbwt_fm *fm, const void *dev_cells, int cell_bytes, const uint64_t *dev_offsets,
                     uint64_t n_patterns, uint64_t *dev_lo, uint64_t *dev_hi);
 int grlbwt_fm_locate(grlbwt_ctx *ctx, const grlbwt_fm *fm, const uint64_t *dev_rows, uint64_t n_rows, uint64_t max_steps,
