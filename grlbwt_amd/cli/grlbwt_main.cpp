@@ -39,12 +39,15 @@ struct arguments {
     bool rev_comp = false;                  // -R (main.cpp:17,75): also the DNA reverse complements, FASTA/Q inputs
     bool fastx = false;                     // --fastx: TEXT holds FASTA/Q records (the reference's own conversion, main.cpp:117-136, is switched off upstream)
     int gpus = 1;                           // --gpus N: one process per GPU, record shards, RCCL (collection-level mode)
+    bool merge = false;                     // --merge A B: no TEXT; the images of two collections -> the image of "A's strings, then B's"
+    std::string merge_a, merge_b;
     std::string version = "v1.0.1 alpha";   // main.cpp:20 (reference version string)
 };
 
 static void usage(const char *prog) {
     std::cout << "Repetition-aware BWT construction (MI355X / HIP engine)\n"
-              << "Usage: " << prog << " [OPTIONS] TEXT\n\n"
+              << "Usage: " << prog << " [OPTIONS] TEXT\n"
+              << "       " << prog << " --merge A.rl_bwt B.rl_bwt -o OUT [-a N] [-g DEV]\n\n"
               << "Positionals:\n"
               << "  TEXT                   Input file in one-string-per-line format\n\n"
               << "Options:\n"
@@ -59,6 +62,9 @@ static void usage(const char *prog) {
               << "  --fastx                TEXT is a FASTA/Q file (optionally gzip): its records become the strings.  Without this\n"
               << "                         flag TEXT is always taken as one-string-per-line cells, as the reference does\n"
               << "  -R,--rev-comp          Also consider the DNA reverse complements of the strings in TEXT (implies --fastx)\n"
+              << "  --merge A B            Merge the images of two collections into the image of \"A's strings, then B's\" (no TEXT;\n"
+              << "                         needs -o; -a as the images were built; at most 256 distinct symbols in both together;\n"
+              << "                         about read length + 1 passes over the merged rows: for read-like collections)\n"
               << "  -g,--gpu               HIP device ordinal (def. 0; with --gpus: the first of N consecutive devices)\n"
               << "  --gpus                 Number of GPUs: the collection is sharded by record, one process per GPU,\n"
               << "                         exchanges over RCCL; the output does not depend on it (def. 1)\n";
@@ -308,6 +314,51 @@ static int run_multi_gpu(const arguments &args) {
     return worst;
 }
 
+// ---- --merge A B: two images -> the image of the joined collection (grlbwt_merge_files) --------------------------------
+static int run_merge(arguments &args, bool have_text) {
+    if (have_text) fail(105, "--merge: takes two images and no TEXT (got " + args.input_file + ")");
+    if (args.output_file.empty()) fail(105, "--merge: --output-file is required");
+    if (args.gpus > 1) fail(105, "--merge: runs on one GPU (--gpus " + std::to_string(args.gpus) + ")");
+    if (args.fastx || args.rev_comp) fail(105, "--merge: takes images, not FASTA/Q records (--fastx / -R)");
+    if (!is_file(args.merge_a)) fail(105, "--merge: File does not exist: " + args.merge_a);
+    if (!is_file(args.merge_b)) fail(105, "--merge: File does not exist: " + args.merge_b);
+    if (args.ver) { std::cout << args.version << std::endl; return 0; }
+    args.output_file = std::filesystem::path(args.output_file).replace_extension(".rl_bwt");
+    std::cout << "Input images:     " << args.merge_a << ", " << args.merge_b << std::endl;
+    std::cout << (args.alph_bytes > 1 ? "Alphabet type:    integer" : "Alphabet type:    byte") << std::endl;
+    const auto t_start = std::chrono::steady_clock::now();
+    grlbwt_ctx *ctx = nullptr;
+    int rc = grlbwt_ctx_create(args.device, 0, &ctx);
+    if (rc != GRLBWT_OK) {
+        std::cerr << "grlbwt: no usable HIP device (" << grlbwt_strerror(rc) << "); this build has no CPU path" << std::endl;
+        return 3;
+    }
+    std::cout << "Merging the BWTs" << std::endl;
+    grlbwt_merge_info mi;
+    rc = grlbwt_merge_files(ctx, args.merge_a.c_str(), args.merge_b.c_str(), args.alph_bytes, 0, args.output_file.c_str(), &mi);
+    if (rc != GRLBWT_OK) {
+        std::cerr << "grlbwt: " << grlbwt_last_error(ctx) << " (" << grlbwt_strerror(rc) << ")" << std::endl;
+        grlbwt_ctx_destroy(ctx);
+        return 2;
+    }
+    std::cout << "Stats: " << std::endl;
+    std::cout << "  Smallest symbol               : " << mi.separator << std::endl;
+    std::cout << "  Number of distinct symbols    : " << mi.sigma << std::endl;
+    std::cout << "  Number of symbols (A + B)     : " << mi.n_syms_a << " + " << mi.n_syms_b << std::endl;
+    std::cout << "  Number of strings (A + B)     : " << mi.n_strings_a << " + " << mi.n_strings_b << std::endl;
+    std::cout << "  Refinement rounds             : " << mi.rounds << std::endl;
+    std::cout << "  Rows changed over the rounds  : " << mi.rows_changed << std::endl;
+    std::cout << "  BWT size (n)                  : " << mi.n_syms_a + mi.n_syms_b << std::endl;
+    std::cout << "  Number of runs (r)            : " << mi.n_runs << std::endl;
+    std::cout << "  Bytes per run symbol          : " << mi.sb << std::endl;
+    std::cout << "  Bytes per run length          : " << mi.fb << std::endl;
+    report_time(t_start, std::chrono::steady_clock::now(), 2);
+    std::cout << "The resulting BCR BWT was stored in " << args.output_file << std::endl;
+    std::cout << std::flush;
+    grlbwt_ctx_destroy(ctx);
+    return 0;
+}
+
 int main(int argc, char **argv) {
     arguments args;
     bool have_text = false;
@@ -339,6 +390,7 @@ int main(int argc, char **argv) {
         else if (a == "-R" || a == "--rev-comp") { args.rev_comp = true; args.fastx = true; }
         else if (a == "--fastx") args.fastx = true;
         else if (a == "--plain") args.fastx = false;                              // (the default: kept so that scripts can say it)
+        else if (a == "--merge") { args.merge = true; args.merge_a = need("--merge"); args.merge_b = need("--merge"); }
         else if (a == "--gpus") {
             args.gpus = std::atoi(need("--gpus").c_str());
             if (args.gpus < 1 || args.gpus > 64) fail(105, "--gpus: Value not in range 1 to 64");
@@ -347,6 +399,7 @@ int main(int argc, char **argv) {
         else if (!have_text) { args.input_file = a; have_text = true; }
         else fail(109, "The following argument was not expected: " + a);
     }
+    if (args.merge) return run_merge(args, have_text);
     if (!have_text) fail(106, "TEXT is required");                                  // main.cpp:53 ->required()
     if (!is_file(args.input_file)) fail(105, "TEXT: File does not exist: " + args.input_file);
     if (args.ver) { std::cout << args.version << std::endl; return 0; }              // main.cpp:106-109

@@ -27,6 +27,12 @@ struct grlbwt_fm {
     std::unique_ptr<grl64::Engine::FmIndex> f64;
 };
 
+// a merge of two images (grlbwt_merge_create): the converged interleave, the two rank sequences and the alphabet
+struct grlbwt_merge {
+    std::unique_ptr<grl32::Engine::ImageMerge> m32;
+    std::unique_ptr<grl64::Engine::ImageMerge> m64;
+};
+
 struct grlbwt_ctx {
     uint32_t flags = 0;
     int device = 0;
@@ -34,6 +40,7 @@ struct grlbwt_ctx {
     std::unique_ptr<grl64::Engine> e64;
     std::string err;
     std::vector<grlbwt_fm *> fms;      // the indexes still alive: released with the context
+    std::vector<grlbwt_merge *> merges;      // and the merges
 };
 
 namespace {
@@ -124,6 +131,7 @@ void grammar_download(const E &e, int level, uint64_t *g0, uint64_t *g1, uint8_t
 #define ENG(ctx, expr) ((ctx)->e32 ? (ctx)->e32->expr : (ctx)->e64->expr)
 #define HAS_ENG(ctx) ((ctx) && ((ctx)->e32 || (ctx)->e64))
 
+static constexpr uint64_t kMergeRowLimit = 1ull << 40;      // grlbwt_merge_create: merged rows, as the build's limit on cells
 static constexpr uint64_t kIdx32Limit = 0xFFFFFF00ull;      // texts of this many cells or more take the 64-bit index build
 void load(grlbwt_ctx *ctx, const void *cells, uint64_t n, int w, bool host) {
     ctx->e32.reset();
@@ -439,6 +447,14 @@ void read_fastx_raw(const char *path, RawText &R) {
         cleanup();
         throw;
     }
+}
+// an .rl_bwt file in device memory (grlbwt_merge_files): the plain-file branch of the reader above -- an image starts with its
+// symbol width, 1 to 8, never with the gzip magic
+void read_image_file(const char *path, RawText &R) {
+    unsigned char mg[2] = {0, 0};
+    if (!file_magic(path, mg)) throw prim::Error(GRLBWT_EINVAL, std::string("cannot open ") + path);
+    if (mg[0] == 0x1F && mg[1] == 0x8B) throw prim::Error(GRLBWT_EINVAL, std::string(path) + " is a gzip file, not an .rl_bwt image");
+    read_fastx_raw(path, R);
 }
 void load_fastx(grlbwt_ctx *ctx, const char *path, uint32_t fx_flags, uint64_t *n_strings) {
     ctx->e32.reset();
@@ -1473,6 +1489,64 @@ int test_set_bits(uint64_t n, uint64_t seed) {
     return 0;
 }
 
+// 12: one refinement round of the image merge (Engine::MergeRound: the three round kernels on the device) against a host loop: flags
+// in runs of up to 9000 rows and in coin flips (tiles fed from one image alone, slices that start at any byte), rank bytes below sigma
+template <class E>
+int test_merge_round_one(uint64_t n, uint64_t seed, uint32_t sigma, int ib) {
+    std::vector<uint8_t> z(n), prev(n);
+    uint64_t s = seed, na = 0, exp_changed = 0;
+    for (uint64_t i = 0; i < n;) {
+        const uint64_t kind = sm64(s) % 3;
+        uint64_t len = kind == 0 ? 1 + sm64(s) % 9000 : 1 + sm64(s) % 300;
+        const uint8_t bit = (uint8_t)(sm64(s) & 1);
+        for (; len && i < n; len--, i++) z[i] = kind == 2 ? (uint8_t)(sm64(s) & 1) : bit;
+    }
+    for (uint64_t i = 0; i < n; i++) {
+        na += z[i] == 0;
+        prev[i] = sm64(s) % 11 == 0 ? (uint8_t)(z[i] ^ 1) : z[i];
+        exp_changed += prev[i] != z[i];
+    }
+    const uint64_t nb = n - na;
+    std::vector<uint8_t> ra(na), rb(nb), want(n);
+    for (auto &v : ra) v = (uint8_t)(sm64(s) % sigma);
+    for (auto &v : rb) v = (uint8_t)(sm64(s) % sigma);
+    {   // the definition: a stable sort of the flags by the symbol each reads from its own image
+        std::vector<uint8_t> key(n);
+        std::vector<uint64_t> at(257, 0);
+        uint64_t i = 0, j = 0;
+        for (uint64_t p = 0; p < n; p++) { key[p] = z[p] ? rb[j++] : ra[i++]; at[key[p] + 1]++; }
+        for (int c = 0; c < 256; c++) at[c + 1] += at[c];
+        for (uint64_t p = 0; p < n; p++) want[at[key[p]]++] = z[p];
+    }
+    grl32::DBuf<uint8_t> dra(na + 16), drb(nb + 16), dz(n + 16), dp(n + 16), dout(n + 64);
+    prim::h2d(dra.p, ra.data(), na); prim::h2d(drb.p, rb.data(), nb); prim::h2d(dz.p, z.data(), n); prim::h2d(dp.p, prev.data(), n);
+    prim::dev_memset(dout.p, 0xA5, n + 64);
+    typename E::MergeRound W;
+    W.alloc(n);
+    if (W.changed(dz.p, dp.p, na) != exp_changed) return 1;
+    if (W.changed(dz.p, nullptr, na) != 0) return 2;
+    W.step(dra.p, drb.p, dz.p, dout.p);
+    prim::sync();
+    const std::vector<uint8_t> got = dout.to_host(n + 64);
+    for (uint64_t p = 0; p < n; p++)
+        if (got[p] != want[p]) {
+            fprintf(stderr, "[grlbwt] selftest merge round: %d-byte index, %llu rows (%llu of A), %u symbols: row %llu expected flag %u, got %u\n", ib,
+                    (unsigned long long)n, (unsigned long long)na, sigma, (unsigned long long)p, want[p], got[p]);
+            return 3;
+        }
+    for (uint64_t p = n; p < n + 64; p++) if (got[p] != 0xA5) return 4;
+    return 0;
+}
+int test_merge_round(uint64_t n, uint64_t seed) {
+    const uint64_t m = self_size(n);
+    const uint32_t sigmas[3] = {2, 5, 256};
+    for (int k = 0; k < 3; k++) {
+        if (int rc = test_merge_round_one<grl32::Engine>(m, seed + k, sigmas[k], 4)) return -(600 + rc);
+        if (int rc = test_merge_round_one<grl64::Engine>(m + 1 + k, seed + 10 + k, sigmas[k], 8)) return -(610 + rc);
+    }
+    return 0;
+}
+
 int selftest(uint64_t n, uint64_t seed) {
     if (n < 2) n = 2;
     std::vector<uint32_t> h(n);
@@ -1557,6 +1631,7 @@ int selftest(uint64_t n, uint64_t seed) {
 #endif
     { int r = test_pack(); if (r) return r; }
     { int r = test_set_bits(n, seed + 60); if (r) return r; }
+    { int r = test_merge_round(n, seed + 80); if (r) return r; }
     return 0;
 }
 
@@ -1629,6 +1704,8 @@ void grlbwt_ctx_destroy(grlbwt_ctx *ctx) {
     try {
         for (grlbwt_fm *fm : ctx->fms) delete fm;
         ctx->fms.clear();
+        for (grlbwt_merge *mg : ctx->merges) delete mg;
+        ctx->merges.clear();
         ctx->e32.reset(); ctx->e64.reset(); prim::sync(); prim::pool_trim();
         if (--prim::rt().live_ctx <= 0) {      // process-wide debug settings and a borrowed stream end with the last context
             prim::rt().live_ctx = 0;
@@ -1965,6 +2042,86 @@ int grlbwt_fm_locate(grlbwt_ctx *ctx, const grlbwt_fm *fm, const uint64_t *dev_r
         if (fm->f32) grl32::Engine::fm_locate(*fm->f32, dev_rows, n_rows, max_steps, dev_string, dev_offset);
         else grl64::Engine::fm_locate(*fm->f64, dev_rows, n_rows, max_steps, dev_string, dev_offset);
     });
+}
+
+int grlbwt_merge_create(grlbwt_ctx *ctx, const void *dev_image_a, uint64_t bytes_a, const void *dev_image_b, uint64_t bytes_b, int cell_bytes,
+                        uint64_t max_rounds, grlbwt_merge **out) {
+    if (out) *out = nullptr;
+    if (!ctx || !dev_image_a || !dev_image_b || !out) return GRLBWT_EINVAL;
+    return guarded(ctx, [&] {
+        const uint64_t ta = grl64::Engine::image_total_symbols(dev_image_a, bytes_a), tb = grl64::Engine::image_total_symbols(dev_image_b, bytes_b);
+        if (ta >= kMergeRowLimit || tb >= kMergeRowLimit || ta + tb >= kMergeRowLimit) throw prim::Error(GRLBWT_ERANGE, "merge: 2^40 merged rows or more");
+        const bool big = ta + tb >= kIdx32Limit || (ctx->flags & GRLBWT_FLAG_FORCE_IDX64);
+        std::unique_ptr<grlbwt_merge> mg(new grlbwt_merge());
+        if (big) {
+            mg->m64.reset(new grl64::Engine::ImageMerge());
+            grl64::Engine::merge_create(dev_image_a, bytes_a, dev_image_b, bytes_b, cell_bytes, max_rounds, *mg->m64);
+        } else {
+            mg->m32.reset(new grl32::Engine::ImageMerge());
+            grl32::Engine::merge_create(dev_image_a, bytes_a, dev_image_b, bytes_b, cell_bytes, max_rounds, *mg->m32);
+        }
+        ctx->merges.push_back(mg.get());
+        *out = mg.release();
+    });
+}
+int grlbwt_merge_destroy(grlbwt_ctx *ctx, grlbwt_merge *mg) {
+    if (!ctx) return GRLBWT_EINVAL;
+    if (!mg) return GRLBWT_OK;
+    auto it = std::find(ctx->merges.begin(), ctx->merges.end(), mg);
+    if (it == ctx->merges.end()) { ctx->err = "merge destroy: not a merge of this context"; return GRLBWT_EINVAL; }
+    ctx->merges.erase(it);
+    return guarded(ctx, [&] { prim::sync(); delete mg; });
+}
+int grlbwt_merge_info_get(const grlbwt_merge *mg, grlbwt_merge_info *out) {
+    if (!mg || !out || !(mg->m32 || mg->m64)) return GRLBWT_EINVAL;
+    auto fill = [&](const auto &M, uint64_t idx_bytes, uint64_t tile_rows) {
+        out->n_syms_a = M.na; out->n_syms_b = M.nb; out->n_strings_a = M.ka; out->n_strings_b = M.kb;
+        out->sigma = M.sigma; out->separator = M.sepval; out->rounds = M.rounds; out->rows_changed = M.rows_changed;
+        out->n_runs = M.n_runs; out->out_bytes = M.out_bytes; out->sb = M.sb; out->fb = M.fb;
+        out->idx_bytes = idx_bytes; out->tile_rows = tile_rows; out->scratch_bytes = M.scratch_bytes; out->held_bytes = M.held_bytes();
+    };
+    if (mg->m32) fill(*mg->m32, 4, grl32::Engine::kMergeTile); else fill(*mg->m64, 8, grl64::Engine::kMergeTile);
+    return GRLBWT_OK;
+}
+int grlbwt_merge_emit(grlbwt_ctx *ctx, const grlbwt_merge *mg, void *dev_out, uint64_t capacity_bytes) {
+    if (!ctx || !mg || !dev_out || !(mg->m32 || mg->m64)) return GRLBWT_EINVAL;
+    return guarded(ctx, [&] {
+        if (mg->m32) grl32::Engine::merge_emit(*mg->m32, (uint8_t *)dev_out, capacity_bytes);
+        else grl64::Engine::merge_emit(*mg->m64, (uint8_t *)dev_out, capacity_bytes);
+    });
+}
+int grlbwt_merge_interleave(grlbwt_ctx *ctx, const grlbwt_merge *mg, uint64_t *dev_bits) {
+    if (!ctx || !mg || !dev_bits || !(mg->m32 || mg->m64)) return GRLBWT_EINVAL;
+    return guarded(ctx, [&] {
+        if (mg->m32) grl32::Engine::merge_interleave(*mg->m32, dev_bits);
+        else grl64::Engine::merge_interleave(*mg->m64, dev_bits);
+    });
+}
+int grlbwt_merge_files(grlbwt_ctx *ctx, const char *path_a, const char *path_b, int cell_bytes, uint64_t max_rounds, const char *path_out,
+                       grlbwt_merge_info *info) {
+    if (!ctx || !path_a || !path_b || !path_out) return GRLBWT_EINVAL;
+    grlbwt_merge *mg = nullptr;
+    int rc = guarded(ctx, [&] {
+        RawText a, b;
+        read_image_file(path_a, a);
+        read_image_file(path_b, b);
+        const int r = grlbwt_merge_create(ctx, a.buf.p, a.n, b.buf.p, b.n, cell_bytes, max_rounds, &mg);
+        if (r != GRLBWT_OK) throw prim::Error(r, ctx->err);
+    });
+    if (rc != GRLBWT_OK) return rc;
+    rc = guarded(ctx, [&] {
+        grlbwt_merge_info mi;
+        grlbwt_merge_info_get(mg, &mi);
+        grl64::DBuf<uint8_t> out(mi.out_bytes);
+        const int r = grlbwt_merge_emit(ctx, mg, out.p, mi.out_bytes);
+        if (r != GRLBWT_OK) throw prim::Error(r, ctx->err);
+        write_image(out.p, mi.out_bytes, path_out);
+        if (info) *info = mi;
+    });
+    const std::string err = ctx->err;
+    grlbwt_merge_destroy(ctx, mg);
+    if (rc != GRLBWT_OK) ctx->err = err;
+    return rc;
 }
 
 int grlbwt_image_plain(grlbwt_ctx *ctx, const void *dev_image, uint64_t image_bytes, void *dev_out_u8,

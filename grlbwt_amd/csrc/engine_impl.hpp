@@ -3128,6 +3128,62 @@ struct RunInvertTailFn {    // the last `tail` cells of string i (separator incl
     }
 };
 
+// ---- merging two images (grlbwt_merge_*): the interleave z holds one flag byte per merged row, 0 = the row is the
+// next unread row of A, 1 = of B; ra / rb hold one rank byte per row of A / B (the rank of the row's symbol among the distinct
+// values of both images).
+struct MgUnpackFn {        // records -> (symbol: all 64 bits, length)
+    const u8 *img; u32 sb, fb; u64 *val; idx_t *len;
+    GRL_DEV void operator()(u64 i) const {
+        const u8 *p = img + 16 + i * (u64)(sb + fb);
+        u64 s = 0, l = 0;
+        for (u32 b = 0; b < sb; b++) s |= (u64)p[b] << (8 * b);
+        for (u32 b = 0; b < fb; b++) l |= (u64)p[sb + b] << (8 * b);
+        val[i] = s; len[i] = (idx_t)l;
+    }
+};
+struct MgKeepFn {          // compacting copy of the non-empty records (dst = scan of NonEmptyIn)
+    const u64 *val; const idx_t *len; const idx_t *dst; u64 *oval; idx_t *olen;
+    GRL_DEV void operator()(u64 i) const {
+        const idx_t l = len[i];
+        if (l != 0) { const u64 o = dst[i]; oval[o] = val[i]; olen[o] = l; }
+    }
+};
+struct MgExpandFn {        // one rank byte per row, through the run-start bitmap
+    const u32 *rrank; const u64 *rw; const idx_t *rb; u8 *out;
+    GRL_DEV void operator()(u64 i) const { out[i] = (u8)rrank[rank1(rw, rb, i + 1) - 1]; }
+};
+struct MgSplitFn {         // z[p] = p >= na: 0^na 1^(n - na) -- the first interleave, and the separator bucket of every round
+    u8 *z; u64 na;
+    GRL_DEV void operator()(u64 p) const { z[p] = p >= na ? (u8)1 : (u8)0; }
+};
+struct MgFlagPred {
+    const u8 *z;
+    GRL_DEV bool operator()(u64 p) const { return z[p] != 0; }
+};
+struct MgDiffIn {
+    const u8 *a, *b;
+    GRL_DEV u64 operator()(u64 p) const { return a[p] != b[p] ? 1ull : 0ull; }
+};
+struct MgSym {             // the merged symbol (a rank) of row p through the interleave as a bit-vector with ranks
+    const u8 *ra, *rb; const u64 *zw; const idx_t *zb;
+    GRL_DEV u32 operator()(u64 p) const {
+        const u64 b = rank1(zw, zb, p);                  // B-rows in front of p
+        return ((zw[p >> 6] >> (p & 63)) & 1ull) ? (u32)rb[b] : (u32)ra[p - b];
+    }
+};
+struct MgKeyFn {           // the serial form of a round: the merged symbols gathered as sort keys
+    MgSym s; u8 *key;
+    GRL_DEV void operator()(u64 p) const { key[p] = (u8)s(p); }
+};
+struct MgHeadPred {
+    MgSym s;
+    GRL_DEV bool operator()(u64 p) const { return p == 0 || s(p) != s(p - 1); }
+};
+struct MgHeadFn {          // for_each_set_bit over the run heads: run `ord` starts at row p
+    MgSym s; u32 *sym; idx_t *start;
+    GRL_DEV void operator()(u64 p, u64 ord) const { sym[ord] = s(p); start[ord] = (idx_t)p; }
+};
+
 // ---- counting and locating patterns: one step past scripts/fm_index.h, which stops at lf().  RunRec answers LF for a row's OWN
 // symbol; a backward search needs rank_c(p), the number of c in BWT[0, p), for any c.  The runs in (symbol, position) order --
 // the order the sort above makes -- answer it by binary search: key[j] = (symbol, start) of the j-th run in that order,
@@ -6433,6 +6489,224 @@ class Engine {
         const u64 lim = max_steps < F.n ? max_steps : F.n;
         if (F.checkpoints) prim::for_each(nr, FmLocateCpFn{F.rc.p, F.rec.p, F.sid.p, F.smp.p, F.cp, F.sep, lim, rows, str, ofs}, "fm.locate_cp");
         else prim::for_each(nr, FmLocateFn{F.rc.p, F.rec.p, F.sid.p, F.sep, lim, rows, str, ofs}, "fm.locate");
+        prim::sync();
+    }
+
+    // ---- merging two images into the image of "A's strings, then B's" (grlbwt_merge_*; functor block "merging two images";
+    // DESIGN.md 4c).  The interleave refinement of Holt and McMillan: z starts as 0^nA 1^nB; a round writes every row's flag where
+    // a stable sort of the rows by their symbol puts it and resets the separator's bucket to 0^kA 1^kB (the terminators are
+    // ordered by the strings' numbers); the rounds end with the one that changes nothing.
+    struct ImageMerge {
+        u64 na = 0, nb = 0, ka = 0, kb = 0, sigma = 0, sepval = 0;
+        u64 rounds = 0, rows_changed = 0, n_runs = 0, out_bytes = 0, sb = 0, fb = 0, scratch_bytes = 0;
+        DBuf<u8> ra, rb, z;       // rank byte per row of A and of B (16 bytes of padding behind each), the converged interleave
+        DBuf<u64> alpha;          // rank -> symbol value
+        u64 held_bytes() const { return ra.n + rb.n + z.n + alpha.n * 8; }
+    };
+#ifdef GRLBWT_PRIM_HIP
+    static constexpr u64 kMergeTile = prim::kMgTile;
+#else
+    static constexpr u64 kMergeTile = 4096;      // (the serial form has no tiles: the figure the device library reports)
+#endif
+    static constexpr u64 kMergeSigmaMax = 256;
+    // the non-empty records of an image: their symbols as 64-bit values and their lengths
+    static u64 merge_load_runs(const void *dev_image, u64 image_bytes, const char *which, DBuf<u64> &val, DBuf<idx_t> &len) {
+        const ImageHeader h = image_header(dev_image, image_bytes);
+        if (h.R == 0) throw prim::Error(-22, std::string("merge: image ") + which + " has no record");
+        val.alloc(h.R); len.alloc(h.R);
+        prim::for_each(h.R, MgUnpackFn{(const u8 *)dev_image, (u32)h.sb, (u32)h.fb, val.p, len.p}, "merge.unpack");
+        u64 R = h.R;
+        if (prim::reduce_min<u64>(R, IdxIn64{len.p}, "merge.min_run") == 0) {
+            DBuf<idx_t> dst(R + 1);
+            const u64 kept = (u64)prim::exclusive_scan<idx_t>(R, NonEmptyIn{len.p}, dst.p, true, "merge.nonempty");
+            DBuf<u64> v2(kept);
+            DBuf<idx_t> l2(kept);
+            prim::for_each(R, MgKeepFn{val.p, len.p, dst.p, v2.p, l2.p}, "merge.drop_empty");
+            val = std::move(v2); len = std::move(l2);
+            R = kept;
+        }
+        if (R == 0) throw prim::Error(-22, std::string("merge: image ") + which + " describes no symbol");
+        return R;
+    }
+    // rank byte per row of one image: out[0, n) (allocated with the padding the round kernels read over); returns n
+    static u64 merge_expand(const u32 *rrank, const idx_t *rlen, u64 R, DBuf<u8> &out) {
+        DBuf<idx_t> rpos(R + 1);
+        const u64 n = (u64)prim::exclusive_scan<idx_t>(R, IdxIn<idx_t>{rlen}, rpos.p, true, "merge.positions");
+        RankBits rb;
+        build_rankbits(rb, rpos.p, R, n + 1, "merge.runbits");
+        out.alloc(n + 16);
+        prim::for_each(n, MgExpandFn{rrank, rb.words.p, rb.base.p, out.p}, "merge.expand");
+        return n;
+    }
+    // the interleave as a bit-vector with ranks, and the run heads of the merged sequence read through it
+    struct MergeHeads { RankBits zb; DBuf<u64> hw; DBuf<idx_t> hb; u64 R = 0; };
+    static u64 merge_heads_bytes(u64 n) { return (n / 64 + 3) * 2 * (8 + sizeof(idx_t)); }
+    static void merge_bits(const u8 *z, u64 n, RankBits &zb) {
+        const u64 nw = n / 64 + 2;
+        zb.words.alloc(nw); zb.base.alloc(nw + 1);
+        zb.words.zero();
+        prim::bitvector_from_pred(n, MgFlagPred{z}, zb.words.p, "merge.bits");
+        prim::exclusive_scan_nosync<idx_t>(nw, PopcIn{zb.words.p}, zb.base.p, true, "merge.bit_ranks");
+    }
+    static MgSym merge_sym(const ImageMerge &M, const RankBits &zb) { return MgSym{M.ra.p, M.rb.p, zb.words.p, zb.base.p}; }
+    static void merge_heads(const ImageMerge &M, MergeHeads &H) {
+        const u64 n = M.na + M.nb, nw = n / 64 + 2;
+        merge_bits(M.z.p, n, H.zb);
+        H.hw.alloc(nw); H.hb.alloc(nw + 1);
+        H.hw.zero();
+        prim::bitvector_from_pred(n, MgHeadPred{merge_sym(M, H.zb)}, H.hw.p, "merge.heads");
+        H.R = (u64)prim::exclusive_scan<idx_t>(nw, PopcIn{H.hw.p}, H.hb.p, true, "merge.head_ranks");
+    }
+    // One refinement round without the separator rule, and the test that ends the rounds.  changed(): the rows at which the
+    // interleave `cur` differs from `prev`, the one before it (null: 0) -- the device form takes the A-rows per tile of `cur` in
+    // the same pass, so it comes first; step(): oth = the flags of cur where a stable sort of the rows by their symbol puts them.
+    // The device form is prim::MgRound (three kernels, the symbols read from two contiguous slices per tile); the serial form
+    // goes through the generic primitives: the merged symbols gathered as keys, a stable sort of (key, flag).
+    struct MergeRound {
+        u64 n = 0;
+        bool by_sort = !prim::kIsDevice;
+        static u64 sort_scratch_bytes(u64 n_) { return 3 * n_ + (n_ / 64 + 3) * (8 + sizeof(idx_t)) + (n_ / 4096 + 1) * 256 * 12; }
+        u64 changed_by_sum(const u8 *cur, const u8 *prev) { return prev ? prim::reduce_sum<u64>(n, MgDiffIn{cur, prev}, "merge.changed") : 0; }
+        void step_by_sort(const u8 *ra, const u8 *rb, const u8 *cur, u8 *oth) {
+            RankBits zb;
+            merge_bits(cur, n, zb);
+            DBuf<u8> ka(n), kb(n), v2(n);
+            prim::for_each(n, MgKeyFn{MgSym{ra, rb, zb.words.p, zb.base.p}, ka.p}, "merge.keys");
+            d2d_copy(oth, cur, n);
+            const int res = prim::sort_pairs<u8, u8>(ka.p, oth, kb.p, v2.p, n, 0, 8, "merge.sort");
+            if (res) d2d_copy(oth, v2.p, n);
+        }
+#ifdef GRLBWT_PRIM_HIP
+        // (GRLBWT_MERGE_ROUND=sort: the generic form on the device too -- the baseline the fused kernels are measured against)
+        prim::MgRound<idx_t> W;
+        static u64 scratch_bytes(u64 n_) { return prim::sw().merge_round == 's' ? sort_scratch_bytes(n_) : prim::MgRound<idx_t>::scratch_bytes(n_); }
+        void alloc(u64 n_) { n = n_; by_sort = prim::sw().merge_round == 's'; if (!by_sort) W.alloc(n_); }
+        void release() { W.release(); }
+        u64 changed(const u8 *cur, const u8 *prev, u64 na) {
+            if (by_sort) return changed_by_sum(cur, prev);
+            u64 a_rows = 0;
+            const u64 c = W.count(cur, prev, &a_rows);
+            if (a_rows != na) throw prim::Error(-71, "merge: a round lost rows of A");
+            return c;
+        }
+        void step(const u8 *ra, const u8 *rb, const u8 *cur, u8 *oth) { if (by_sort) step_by_sort(ra, rb, cur, oth); else W.scatter(cur, ra, rb, oth); }
+#else
+        static u64 scratch_bytes(u64 n_) { return sort_scratch_bytes(n_); }
+        void alloc(u64 n_) { n = n_; }
+        void release() {}
+        u64 changed(const u8 *cur, const u8 *prev, u64) { return changed_by_sum(cur, prev); }
+        void step(const u8 *ra, const u8 *rb, const u8 *cur, u8 *oth) { step_by_sort(ra, rb, cur, oth); }
+#endif
+    };
+    // device milliseconds the profile table holds under a kernel name (0 while the profile is off)
+    static double merge_prof_ms(const char *name) {
+        auto it = prim::rt().prof.find(name);
+        return it == prim::rt().prof.end() ? 0.0 : (double)it->second.ms;
+    }
+    static void merge_create(const void *img_a, u64 bytes_a, const void *img_b, u64 bytes_b, int cell_bytes, u64 max_rounds, ImageMerge &M) {
+        if (!(cell_bytes == 1 || cell_bytes == 2 || cell_bytes == 4 || cell_bytes == 8)) throw prim::Error(-22, "merge: bad cell width");
+        // ---- load: the records of both images, the union of their symbol values, one rank byte per row
+        DBuf<u64> va, vb;
+        DBuf<idx_t> la, lb;
+        const u64 Ra = merge_load_runs(img_a, bytes_a, "A", va, la), Rb = merge_load_runs(img_b, bytes_b, "B", vb, lb);
+        DBuf<u64> cat(Ra + Rb);
+        d2d_copy(cat.p, va.p, Ra);
+        d2d_copy(cat.p + Ra, vb.p, Rb);
+        va.release(); vb.release();
+        const u64 mx = prim::reduce_max<u64>(Ra + Rb, CellIn<u64>{cat.p}, "merge.max_sym");
+        if (cell_bytes < 8 && (mx >> (8 * cell_bytes))) throw prim::Error(-22, "merge: the largest symbol (" + std::to_string(mx) + ") does not fit the cell width");
+        DBuf<u32> ranks(Ra + Rb);
+        M.sigma = alphabet_compact<u64>(cat.p, Ra + Rb, mx, ranks.p, M.alpha);
+        cat.release();
+        if (M.sigma > kMergeSigmaMax)
+            throw prim::Error(-75, "merge: the two images hold " + std::to_string(M.sigma) + " distinct symbols together, more than the 256 a round sorts by");
+        const std::vector<u64> alpha = M.alpha.to_host(M.sigma);
+        const u32 sep_a = prim::reduce_min<u32>(Ra, PtrU32In{ranks.p}, "merge.sep_a"), sep_b = prim::reduce_min<u32>(Rb, PtrU32In{ranks.p + Ra}, "merge.sep_b");
+        if (sep_a != sep_b)
+            throw prim::Error(-22, "merge: the smallest symbols of the two images differ (" + std::to_string(alpha[sep_a]) + " in A, " + std::to_string(alpha[sep_b]) +
+                                       " in B): they are not collections with one separator");
+        M.sepval = alpha[0];
+        M.na = merge_expand(ranks.p, la.p, Ra, M.ra);
+        M.nb = merge_expand(ranks.p + Ra, lb.p, Rb, M.rb);
+        ranks.release(); la.release(); lb.release();
+        const u64 n = M.na + M.nb;
+        u64 ha[256], hb[256];
+        prim::byte_histogram(M.ra.p, M.na, ha);
+        prim::byte_histogram(M.rb.p, M.nb, hb);
+        M.ka = ha[0]; M.kb = hb[0];
+        u64 F = n;
+        if (cell_bytes == 1) { F = 0; for (int i = 0; i < 256; i++) if (ha[i] + hb[i] > F) F = ha[i] + hb[i]; }
+        M.sb = (bitlen64(mx + 4) + 7) / 8;
+        M.fb = (bitlen64(F) + 7) / 8;
+        // ---- the rounds.  Scratch: the second interleave buffer, the tile tables, and what the run heads take afterwards
+        const u64 round_scratch = MergeRound::scratch_bytes(n);
+        M.scratch_bytes = (n + 16) + std::max(round_scratch, merge_heads_bytes(n));
+        if (M.scratch_bytes + (n + 16) > prim::mem_available())
+            throw prim::Error(-12, "merge: the rounds need " + std::to_string(M.scratch_bytes + n + 16) + " bytes of device memory, more than is free");
+        DBuf<u8> z0(n + 16), z1(n + 16);
+        u8 *cur = z0.p, *oth = z1.p;
+        prim::for_each(n, MgSplitFn{cur, M.na}, "merge.first");
+        const u64 cap = max_rounds ? max_rounds : n + 2, k = M.ka + M.kb;
+        bool converged = false;
+        MergeRound W;
+        W.alloc(n);
+        prim::rt().tag = -1; prim::rt().phase = 0;
+        const char *kinds[6] = {"merge.counts", "merge.hist", "merge.scatter", "merge.changed", "merge.keys", "merge.sort.scatter"};
+        double seen[6] = {0, 0, 0, 0, 0, 0};
+        for (;;) {
+            const u64 changed = W.changed(cur, M.rounds ? oth : nullptr, M.na);
+            if (prim::rt().profile) {
+                // the per-round log (grlbwt_profile_enable): the kernels of the round just done and the pass that found what it changed
+                double ms[6];
+                for (int i = 0; i < 6; i++) { const double t = merge_prof_ms(kinds[i]); ms[i] = t - seen[i]; seen[i] = t; }
+                if (M.rounds)
+                    fprintf(stderr, "[grlbwt] merge round %llu: rows changed %llu; ms: counts %.3f hist %.3f scatter %.3f (sort form: changed %.3f keys %.3f sort scatter %.3f)\n",
+                            (unsigned long long)M.rounds, (unsigned long long)changed, ms[0], ms[1], ms[2], ms[3], ms[4], ms[5]);
+            }
+            if (M.rounds) {
+                M.rows_changed += changed;
+                if (changed == 0) { converged = true; break; }
+            }
+            if (M.rounds == cap) break;
+            W.step(M.ra.p, M.rb.p, cur, oth);
+            prim::for_each(k, MgSplitFn{oth, M.ka}, "merge.separators");
+            std::swap(cur, oth);
+            M.rounds++;
+        }
+        if (!converged)
+            throw prim::Error(-22, "merge: not converged after " + std::to_string(M.rounds) + " rounds (max_rounds); the rounds needed are about the longest prefix a suffix of A "
+                                   "shares with a suffix of B -- the per-string cost model of grlbwt_fm_locate without checkpoints: fine for reads, hopeless for chromosomes");
+        W.release();
+        if (cur == z0.p) { M.z = std::move(z0); z1.release(); } else { M.z = std::move(z1); z0.release(); }
+        MergeHeads H;
+        merge_heads(M, H);
+        M.n_runs = H.R;
+        M.out_bytes = 16 + H.R * (M.sb + M.fb);
+        prim::sync();
+    }
+    static void merge_emit(const ImageMerge &M, u8 *out, u64 capacity) {
+        if (capacity < M.out_bytes) throw prim::Error(-22, "merge: output buffer too small (" + std::to_string(M.out_bytes) + " bytes needed)");
+        const u64 n = M.na + M.nb;
+        MergeHeads H;
+        merge_heads(M, H);
+        if (H.R != M.n_runs) throw prim::Error(-71, "merge: the run heads changed since the merge was made");
+        const u64 R = H.R;
+        DBuf<u32> sym(R);
+        DBuf<idx_t> start(R + 1);
+        prim::for_each_set_bit<idx_t>(n, H.hw.p, H.hb.p, MgHeadFn{merge_sym(M, H.zb), sym.p, start.p}, "merge.runs");
+        const idx_t total = (idx_t)n;
+        prim::h2d(start.p + R, &total, sizeof(total));
+        const u32 sb = (u32)M.sb, fb = (u32)M.fb;
+        u8 hdr[16] = {0};
+        hdr[0] = (u8)sb; hdr[8] = (u8)fb;
+        prim::h2d(out, hdr, 16);
+        const RunLen len{nullptr, start.p};
+        if (sb + fb <= 8 && fb < 8) prim::pack_records(R, RunRecordFn{sym.p, len, sb, M.alpha.p}, sb + fb, out + 16, "merge.pack");
+        else prim::for_each(R, PackRunsFn{sym.p, len, sb, fb, out, 16u, M.alpha.p}, "merge.pack");
+        prim::sync();
+    }
+    static void merge_interleave(const ImageMerge &M, u64 *dev_bits) {
+        prim::bitvector_from_pred(M.na + M.nb, MgFlagPred{M.z.p}, dev_bits, "merge.interleave");
         prim::sync();
     }
 

@@ -2055,6 +2055,253 @@ __global__ void __launch_bounds__(TB)
     }
 }
 
+// ------------------------------------------------------------------ interleave refinement (grlbwt_merge_*)
+// One round of the Holt-McMillan merge of two BWTs: z = one flag byte per merged row (0: the row is A's next unread row, 1: B's);
+// the round writes every row's flag where a STABLE sort of the rows by their symbol puts it.  The symbols are never gathered into
+// an array of their own: a tile of kMgTile merged rows reads A's rows [i0, i0 + ca) and B's [j0, j0 + cb) -- two contiguous
+// slices of the rank-byte arrays ra / rb, i0 = A-rows in front of the tile (apre[tile]), j0 = tile base - i0.
+//   k_mg_counts   per tile: its A-rows (acount[tile]; their scan is apre) and, against the interleave of the round before, the rows
+//                 that changed (tchanged[tile], summed by a reduce: the convergence test.  One atomic per tile on ONE device word
+//                 was measured first: 2.4 M tiles of the 10 GB merge took 27 ms at the ~88 atomics per us a word takes, against
+//                 3 ms for the pass in a round that changes nothing)
+//   k_mg_hist     per tile: the 256 bin counts of its two slices.  The bins of a tile are the bins of the slices whatever the
+//                 order of the flags inside the tile, so this pass reads no flags.  -> rs_offsets<256>
+//   k_mg_scatter  per tile: the flags' prefix sum gives every row its place in its slice, the symbol comes from the slice in LDS,
+//                 the in-tile stable rank per symbol is wave_rank's (as in k_rs_scatter), the flags are permuted in LDS and
+//                 written out in runs per symbol.
+// The slices start at any byte: a slice is loaded as the 16-byte vectors that cover it, from the vector-aligned address below its
+// start -- up to 15 bytes in front of and behind the slice are read and not used.  ra and rb therefore start 16-byte aligned and
+// have 16 bytes of padding behind their last row (the engine allocates them so).
+// LDS per workgroup: 4 KB (hist), 22.6 KB (scatter, 93 vector registers: five waves per SIMD): the registers, not the LDS, set
+// how many workgroups a CU holds.
+static constexpr int kMgTile = kRsTile;      // 4096 merged rows per workgroup of 256 threads, 16 per lane
+__global__ void __launch_bounds__(kBlock) k_mg_counts(const u8 *z, const u8 *zprev, u64 n, u32 *acount, u32 *tchanged) {
+    __shared__ u32 s_one[kBlock / 64], s_dif[kBlock / 64];
+    const u64 base = (u64)blockIdx.x * kMgTile;
+    const u64 left = n - base;
+    const u32 tile_n = left < (u64)kMgTile ? (u32)left : (u32)kMgTile;
+    const u32 t = threadIdx.x * 16u;
+    u32 ones = 0, dif = 0;
+    if (t + 16u <= tile_n) {                 // (z and zprev are 16-byte aligned, the tile base is a multiple of 4096)
+        const uint4 a = *reinterpret_cast<const uint4 *>(z + base + t);
+        ones = (u32)__popc(a.x) + (u32)__popc(a.y) + (u32)__popc(a.z) + (u32)__popc(a.w);      // the flags are 0 or 1
+        if (zprev) {
+            const uint4 b = *reinterpret_cast<const uint4 *>(zprev + base + t);
+            dif = (u32)__popc(a.x ^ b.x) + (u32)__popc(a.y ^ b.y) + (u32)__popc(a.z ^ b.z) + (u32)__popc(a.w ^ b.w);
+        }
+    } else {
+        for (u32 i = t; i < tile_n; i++) {
+            const u8 a = z[base + i];
+            ones += a;
+            if (zprev) dif += (u32)(a != zprev[base + i]);
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) { ones += (u32)__shfl_xor((int)ones, off); dif += (u32)__shfl_xor((int)dif, off); }
+    if ((threadIdx.x & 63) == 0) { s_one[threadIdx.x >> 6] = ones; s_dif[threadIdx.x >> 6] = dif; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        u32 o = 0, d = 0;
+#pragma unroll
+        for (int k = 0; k < kBlock / 64; k++) { o += s_one[k]; d += s_dif[k]; }
+        acount[blockIdx.x] = tile_n - o;
+        tchanged[blockIdx.x] = d;
+    }
+}
+// the bins of len rank bytes at p, added to the wave's table h (every lane of the workgroup calls this: the loop is workgroup-uniform)
+GRL_DEV void mg_count_slice(const u8 *p, u32 len, u32 *h) {
+    if (len == 0) return;
+    const u32 off = (u32)((uintptr_t)p & 15);
+    const uint4 *pa = reinterpret_cast<const uint4 *>(p - off);
+    const u32 nvec = (off + len + 15u) >> 4;
+    for (u32 v0 = 0; v0 < nvec; v0 += kBlock) {
+        if (v0 + (threadIdx.x & ~63u) >= nvec) continue;          // (wave-uniform: nothing of this wave's 64 vectors lies in the slice)
+        const u32 v = v0 + threadIdx.x;
+        const bool in = v < nvec;
+        uint4 x = make_uint4(0, 0, 0, 0);
+        if (in) x = pa[v];
+        const u32 w[4] = {x.x, x.y, x.z, x.w};
+#pragma unroll
+        for (int e = 0; e < 16; e++) {
+            const u32 d = (w[e >> 2] >> (8 * (e & 3))) & 0xFFu;
+            const u32 at = v * 16u + (u32)e;                         // byte `at` of the vectors is byte at - off of the slice
+            const bool valid = in && at >= off && at - off < len;
+            u32 below, count;
+            wave_match<8, true>(d, valid, below, count);
+            if (valid && below == 0u) (void)__hip_atomic_fetch_add(&h[d], count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+        }
+    }
+}
+template <class IDX>
+__global__ void __launch_bounds__(kBlock) k_mg_hist(const u8 *ra, const u8 *rb, u64 n, const IDX *apre, u32 *counts) {
+    constexpr int NB = 256;
+    __shared__ u32 s_h[kBlock / 64][NB];
+    for (int i = threadIdx.x; i < (kBlock / 64) * NB; i += kBlock) (&s_h[0][0])[i] = 0;
+    const u64 base = (u64)blockIdx.x * kMgTile;
+    const u64 left = n - base;
+    const u32 tile_n = left < (u64)kMgTile ? (u32)left : (u32)kMgTile;
+    const u64 i0 = (u64)apre[blockIdx.x];
+    const u32 ca = (u32)((u64)apre[blockIdx.x + 1] - i0), cb = tile_n - ca;
+    __syncthreads();
+    mg_count_slice(ra + i0, ca, s_h[threadIdx.x >> 6]);
+    mg_count_slice(rb + (base - i0), cb, s_h[threadIdx.x >> 6]);
+    __syncthreads();
+    for (int d = threadIdx.x; d < NB; d += kBlock) {
+        u32 tot = 0;
+#pragma unroll
+        for (int q = 0; q < kBlock / 64; q++) tot += s_h[q][d];
+        counts[(u64)blockIdx.x * NB + d] = tot;
+    }
+}
+// the vectors that cover len bytes at p -> dst (16-byte aligned LDS): byte i of the slice lands at dst[(p & 15) + i]
+GRL_DEV void mg_load_slice(const u8 *p, u32 len, u8 *dst) {
+    if (len == 0) return;
+    const u32 off = (u32)((uintptr_t)p & 15);
+    const uint4 *pa = reinterpret_cast<const uint4 *>(p - off);
+    const u32 nvec = (off + len + 15u) >> 4;                         // <= (15 + kMgTile + 15) / 16 = kMgTile / 16 + 1
+    for (u32 v = threadIdx.x; v < nvec; v += kBlock) reinterpret_cast<uint4 *>(dst)[v] = pa[v];
+}
+template <class IDX>
+__global__ void __launch_bounds__(kBlock) k_mg_scatter(const u8 *z, const u8 *ra, const u8 *rb, u64 n, const IDX *apre,
+                                                       const u64 *offsets /*[tiles][256] exclusive*/, u8 *zout) {
+    constexpr int NB = 256, NW = kBlock / 64, ROWS = kMgTile / kBlock;
+    __shared__ __attribute__((aligned(16))) u8 s_a[kMgTile + 32], s_b[kMgTile + 32];      // the two slices, at their alignment in HBM
+    __shared__ __attribute__((aligned(16))) u8 s_flag[kMgTile];                           // the tile's flags; then the flags in sorted order
+    __shared__ u8 s_dig[kMgTile];                                                         // the symbol of every sorted place
+    __shared__ u32 s_cnt[NW][NB];
+    __shared__ u64 s_gbase[NB];
+    __shared__ u32 s_wsum[NW], s_wones[NW];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    for (int i = threadIdx.x; i < NW * NB; i += kBlock) (&s_cnt[0][0])[i] = 0;
+    const u64 base = (u64)blockIdx.x * kMgTile;
+    const u64 left = n - base;
+    const u32 tile_n = left < (u64)kMgTile ? (u32)left : (u32)kMgTile;
+    const u64 i0 = (u64)apre[blockIdx.x], j0 = base - i0;
+    const u32 ca = (u32)((u64)apre[blockIdx.x + 1] - i0), cb = tile_n - ca;
+    const u32 offa = (u32)((uintptr_t)(ra + i0) & 15), offb = (u32)((uintptr_t)(rb + j0) & 15);
+    mg_load_slice(ra + i0, ca, s_a);
+    mg_load_slice(rb + j0, cb, s_b);
+    {
+        const u32 t = threadIdx.x * 16u;
+        if (t + 16u <= tile_n) *reinterpret_cast<uint4 *>(s_flag + t) = *reinterpret_cast<const uint4 *>(z + base + t);
+        else for (u32 i = t; i < tile_n; i++) s_flag[i] = z[base + i];
+    }
+    __syncthreads();
+    // wave w owns rows [w * 1024, (w + 1) * 1024) of the tile, lane l the rows wbase + 64 q + l: the order of (q, l) is the tile's
+    const u32 wbase = (u32)w * (64u * ROWS);
+    u32 fmask = 0, ob[ROWS], runb = 0;
+#pragma unroll
+    for (int q = 0; q < ROWS; q++) {
+        const u32 t = wbase + (u32)q * 64u + (u32)lane;
+        const bool f = t < tile_n && s_flag[t] != 0;
+        const unsigned long long m = __ballot(f);
+        ob[q] = runb + __builtin_amdgcn_mbcnt_hi((u32)(m >> 32), __builtin_amdgcn_mbcnt_lo((u32)m, 0u));      // B-rows of this wave in front of the row
+        runb += (u32)__popcll(m);
+        fmask |= (f ? 1u : 0u) << q;
+    }
+    if (lane == 0) s_wones[w] = runb;
+    __syncthreads();
+    u32 wb = 0;
+    for (int k = 0; k < w; k++) wb += s_wones[k];
+    u32 dig[ROWS], idx[ROWS];
+#pragma unroll
+    for (int q = 0; q < ROWS; q++) {
+        const u32 t = wbase + (u32)q * 64u + (u32)lane;
+        dig[q] = 0;
+        if (t < tile_n) {
+            const u32 pb = wb + ob[q];                               // B-rows of the tile in front of row t; t - pb A-rows
+            dig[q] = (fmask >> q) & 1u ? (u32)s_b[offb + pb] : (u32)s_a[offa + (t - pb)];
+        }
+    }
+    wave_rank<8, ROWS, true, u32>([&](int q) { return dig[q]; }, wbase + (u32)lane, tile_n, (u32)ROWS, &s_cnt[w][0], idx);
+    __syncthreads();
+    {   // thread d, bin d: wave bases, the bin's start in the tile, its global base (k_rs_scatter's offset phase, one bin per thread)
+        u32 cw[NW], tt = 0;
+#pragma unroll
+        for (int k = 0; k < NW; k++) { cw[k] = s_cnt[k][threadIdx.x]; tt += cw[k]; }
+        u32 incl = tt;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const u32 o = (u32)__shfl_up((int)incl, off);
+            if (lane >= off) incl += o;
+        }
+        if (lane == 63) s_wsum[w] = incl;
+        __syncthreads();
+        u32 start = incl - tt;
+        for (int k = 0; k < w; k++) start += s_wsum[k];
+        u32 run = start;
+#pragma unroll
+        for (int k = 0; k < NW; k++) { s_cnt[k][threadIdx.x] = run; run += cw[k]; }
+        s_gbase[threadIdx.x] = offsets[(u64)blockIdx.x * NB + threadIdx.x] - (u64)start;
+    }
+    __syncthreads();                                                 // (every read of s_flag lies in front of this barrier)
+#pragma unroll
+    for (int q = 0; q < ROWS; q++) {
+        const u32 t = wbase + (u32)q * 64u + (u32)lane;
+        if (t < tile_n) {
+            const u32 at = idx[q] + s_cnt[w][dig[q]];
+            s_flag[at] = (u8)((fmask >> q) & 1u);
+            s_dig[at] = (u8)dig[q];
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < ROWS; j++) {
+        const u32 t = (u32)j * kBlock + threadIdx.x;
+        if (t < tile_n) zout[s_gbase[s_dig[t]] + t] = s_flag[t];
+    }
+}
+// The scratch of the rounds and their launches.  One MgRound serves every round of a merge.
+template <class IDX>
+struct MgRound {
+    u64 n = 0;
+    u32 tiles = 0, chunks = 0;
+    u32 *acount = nullptr, *tchanged = nullptr, *counts = nullptr, *chunk_sums = nullptr;
+    IDX *apre = nullptr;
+    u64 *chunk_off = nullptr, *offsets = nullptr;
+    static u64 tiles_of(u64 n_) { return (n_ + kMgTile - 1) / kMgTile; }
+    static u64 scratch_bytes(u64 n_) {
+        const u64 t = tiles_of(n_), c = (t + kRsChunk - 1) / kRsChunk;
+        return t * (8 + sizeof(IDX) + 256 * 12) + sizeof(IDX) + c * 256 * 12;
+    }
+    void alloc(u64 n_) {
+        n = n_; tiles = (u32)tiles_of(n_); chunks = (tiles + kRsChunk - 1) / kRsChunk;
+        acount = (u32 *)dev_alloc((u64)tiles * 4);
+        tchanged = (u32 *)dev_alloc((u64)tiles * 4);
+        apre = (IDX *)dev_alloc(((u64)tiles + 1) * sizeof(IDX));
+        counts = (u32 *)dev_alloc((u64)tiles * 256 * 4);
+        offsets = (u64 *)dev_alloc((u64)tiles * 256 * 8);
+        chunk_sums = (u32 *)dev_alloc((u64)chunks * 256 * 4);
+        chunk_off = (u64 *)dev_alloc((u64)chunks * 256 * 8);
+    }
+    void release() {
+        dev_free(acount); dev_free(tchanged); dev_free(apre); dev_free(counts); dev_free(offsets); dev_free(chunk_sums); dev_free(chunk_off);
+        acount = tchanged = counts = chunk_sums = nullptr; apre = nullptr; chunk_off = offsets = nullptr;
+    }
+    ~MgRound() { release(); }
+    // A-rows per tile of z and their scan; *n_a = A-rows of all tiles; returns the rows at which z differs from zprev (null: 0)
+    u64 count(const u8 *z, const u8 *zprev, u64 *n_a) {
+        prof_begin("merge.counts", n * (zprev ? 2 : 1));
+        hipLaunchKernelGGL(k_mg_counts, dim3(tiles), dim3(kBlock), 0, rt().stream, z, zprev, n, acount, tchanged);
+        prof_end();
+        after_launch("merge.counts");
+        *n_a = (u64)exclusive_scan<IDX>((u64)tiles, PtrIn<u32>{acount}, apre, true, "merge.tile_scan");
+        return zprev ? reduce_sum<u64>((u64)tiles, PtrIn<u32>{tchanged}, "merge.changed_sum") : 0;
+    }
+    // z -> zout by the symbols behind the flags (count() ran on this z)
+    void scatter(const u8 *z, const u8 *ra, const u8 *rb, u8 *zout) {
+        prof_begin("merge.hist", n);
+        hipLaunchKernelGGL((k_mg_hist<IDX>), dim3(tiles), dim3(kBlock), 0, rt().stream, ra, rb, n, apre, counts);
+        prof_end();
+        after_launch("merge.hist");
+        rs_offsets<256>(counts, tiles, chunk_sums, chunk_off, offsets, nullptr, "merge.offsets");
+        prof_begin("merge.scatter", n * 3);
+        hipLaunchKernelGGL((k_mg_scatter<IDX>), dim3(tiles), dim3(kBlock), 0, rt().stream, z, ra, rb, n, apre, offsets, zout);
+        prof_end();
+        after_launch("merge.scatter");
+    }
+};
+
 // Digit plan of an LSD sort over `bits` key bits: the fewest passes with digits of at most rs_max_digit() bits, widths as equal
 // as possible (at 9: 51 bits = 9,9,9,8,8,8; 54 = 6 x 9; 18 = 9,9).  GRLBWT_SORT_DIGIT=8|9|10 sets the widest digit; the default
 // stays 8: measured on the 10 GB build (profiles/r03), 9- and 10-bit digits save a pass over the 51-56-bit suffix keys and the

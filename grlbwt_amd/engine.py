@@ -35,6 +35,8 @@ ABI_SYMBOLS = [
     "grlbwt_alphabet_size", "grlbwt_alphabet_download", "grlbwt_alphabet_compact_device",
     "grlbwt_fm_create", "grlbwt_fm_destroy", "grlbwt_fm_info_get", "grlbwt_fm_count", "grlbwt_fm_locate",
     "grlbwt_invert_image_checkpointed", "grlbwt_fm_walk_info_get",
+    "grlbwt_merge_create", "grlbwt_merge_info_get", "grlbwt_merge_emit", "grlbwt_merge_interleave", "grlbwt_merge_destroy",
+    "grlbwt_merge_files",
 ]
 
 FM_LOCATE = 1
@@ -45,6 +47,12 @@ UINT64_MAX = 2 ** 64 - 1
 class FmInfo(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in ("n_syms", "n_runs", "n_strings", "sigma", "separator", "idx_bytes", "index_bytes",
                                           "top_entries", "flags")]
+
+
+class MergeInfo(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("n_syms_a", "n_syms_b", "n_strings_a", "n_strings_b", "sigma", "separator", "rounds",
+                                          "rows_changed", "n_runs", "out_bytes", "sb", "fb", "idx_bytes", "tile_rows",
+                                          "scratch_bytes", "held_bytes")]
 
 
 class WalkInfo(C.Structure):
@@ -201,6 +209,12 @@ def load_library(path=None, allow_test_standin=False):
     L.grlbwt_fm_info_get.argtypes = [vp, C.POINTER(FmInfo)]
     L.grlbwt_fm_count.argtypes = [vp, vp, vp, i32, vp, u64, vp, vp]
     L.grlbwt_fm_locate.argtypes = [vp, vp, vp, u64, u64, vp, vp]
+    L.grlbwt_merge_create.argtypes = [vp, vp, u64, vp, u64, i32, u64, C.POINTER(vp)]
+    L.grlbwt_merge_info_get.argtypes = [vp, C.POINTER(MergeInfo)]
+    L.grlbwt_merge_emit.argtypes = [vp, vp, vp, u64]
+    L.grlbwt_merge_interleave.argtypes = [vp, vp, vp]
+    L.grlbwt_merge_destroy.argtypes = [vp, vp]
+    L.grlbwt_merge_files.argtypes = [vp, C.c_char_p, C.c_char_p, i32, u64, C.c_char_p, C.POINTER(MergeInfo)]
     L.grlbwt_profile_enable.argtypes = [vp, i32]
     L.grlbwt_profile_dump.argtypes = [vp, C.c_char_p, u64]
     _libs[path] = L
@@ -463,6 +477,14 @@ class Context:
                                                 C.c_void_p(dev_out_ptr), capacity_bytes, C.byref(si)))
         return _as_dict(si)
 
+    def merge_files(self, path_a, path_b, path_out, cell_bytes=1, max_rounds=0):
+        """The images in two files merged into the image of "A's strings, then B's", written to path_out; returns the merge's
+        counters (ImageMerge.info)."""
+        mi = MergeInfo()
+        self._ck(self.L.grlbwt_merge_files(self._h, os.fsencode(path_a), os.fsencode(path_b), cell_bytes, max_rounds,
+                                           os.fsencode(path_out), C.byref(mi)))
+        return _as_dict(mi)
+
     def memory_usage(self):
         a, b = C.c_uint64(), C.c_uint64()
         self._ck(self.L.grlbwt_memory_usage(self._h, C.byref(a), C.byref(b)))
@@ -528,6 +550,52 @@ class FmIndex:
         h, self._h = getattr(self, "_h", None), None
         if h and getattr(self.ctx, "_h", None):       # (a closed context has released its indexes)
             self.ctx._ck(self.ctx.L.grlbwt_fm_destroy(self.ctx._h, h))
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class ImageMerge:
+    """The images of collections A and B merged into the image of "A's strings, then B's" (grlbwt_merge_*), without the texts.
+    All pointers are device pointers; both images may be freed once the object exists (all rounds have run by then).  Both
+    images together may hold at most 256 distinct symbols; the number of rounds is about the longest prefix a suffix of A
+    shares with a suffix of B (max_rounds bounds it, 0: no bound of the caller's)."""
+
+    def __init__(self, ctx, a_ptr, a_bytes, b_ptr, b_bytes, cell_bytes, max_rounds=0):
+        self.ctx = ctx
+        h = C.c_void_p()
+        ctx._ck(ctx.L.grlbwt_merge_create(ctx._h, C.c_void_p(a_ptr), a_bytes, C.c_void_p(b_ptr), b_bytes, cell_bytes, max_rounds,
+                                          C.byref(h)))
+        self._h = h
+
+    def info(self):
+        out = MergeInfo()
+        rc = self.ctx.L.grlbwt_merge_info_get(self._h, C.byref(out))
+        if rc != OK:
+            raise GrlbwtError(rc, self.ctx.L.grlbwt_strerror(rc).decode())
+        return _as_dict(out)
+
+    def emit(self, out_ptr, capacity_bytes):
+        """The merged image into out_ptr (info()["out_bytes"] bytes)."""
+        self.ctx._ck(self.ctx.L.grlbwt_merge_emit(self.ctx._h, self._h, C.c_void_p(out_ptr), capacity_bytes))
+
+    def interleave(self, bits_ptr):
+        """ceil(n / 64) words: bit p of word p // 64 is set when row p of the merged BWT comes from B."""
+        self.ctx._ck(self.ctx.L.grlbwt_merge_interleave(self.ctx._h, self._h, C.c_void_p(bits_ptr)))
+
+    def close(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h and getattr(self.ctx, "_h", None):       # (a closed context has released its merges)
+            self.ctx._ck(self.ctx.L.grlbwt_merge_destroy(self.ctx._h, h))
 
     def __enter__(self):
         return self

@@ -344,6 +344,53 @@ int grlbwt_fm_count(grlbwt_ctx *ctx, const grlbwt_fm *fm, const void *dev_cells,
 int grlbwt_fm_locate(grlbwt_ctx *ctx, const grlbwt_fm *fm, const uint64_t *dev_rows, uint64_t n_rows, uint64_t max_steps,
                      uint64_t *dev_string, uint64_t *dev_offset);
 
+/* ---- merging two images: the image of the collection "strings of A, then strings of B" from the images of A and B, without the
+ * texts -- a collection larger than one build is built in batches and folded together, a batch of new strings is added to an
+ * existing image.  String i of B becomes string n_strings_a + i.  When A and B were built by this engine with cells of cell_bytes,
+ * the output is byte for byte what grlbwt_build writes for the concatenated text, header included: sb from the largest symbol of
+ * both images + 4, fb from the largest total of one symbol in the merged BWT (cell_bytes 1) or from the merged length (2, 4, 8) --
+ * which is why the call takes cell_bytes, as grlbwt_invert_image does.  Any well-formed image is accepted ("Accepted input"
+ * above); the output always has maximal runs, no empty record and those widths.
+ *
+ * The algorithm is the interleave refinement of Holt and McMillan (2014) with the separator rule of the BCR order: one flag per
+ * merged row (0: the row comes from A), 0^nA 1^nB to begin with; a round writes every row's flag where a stable sort of the rows
+ * by their symbol puts it, then sets the separator's bucket -- the first n_strings_a + n_strings_b rows -- to 0^kA 1^kB (the
+ * terminators are ordered by the strings' numbers); the rounds end with the one that changes nothing.  COST: about (the longest
+ * prefix a suffix of A shares with a suffix of B) + 2 rounds, each a streaming pass over the merged rows -- the per-string cost
+ * model of grlbwt_fm_locate without checkpoints: fine for read-like collections (read length + 1 rounds), hopeless for
+ * chromosomes.  max_rounds bounds them (0: n + 2); a merge that has not converged by then fails with GRLBWT_EINVAL.
+ * SCOPE: both images together hold at most 256 distinct symbols (a round sorts by one byte); more: GRLBWT_ERANGE.
+ * Device memory: one byte per row of A and of B and one per merged row are kept in the handle (held_bytes); the rounds take a
+ * second byte per merged row and tile tables on top (scratch_bytes), checked against the free memory before the first round
+ * (GRLBWT_ENOMEM).  64-bit positions from 2^32 - 256 merged rows on or with GRLBWT_FLAG_FORCE_IDX64; 2^40 rows or more:
+ * GRLBWT_ERANGE.  GRLBWT_EINVAL: an image without a record or with a bad header, cell_bytes not in {1, 2, 4, 8}, a symbol that
+ * does not fit cell_bytes, images whose smallest symbols differ (the message names both), capacity_bytes < out_bytes.  On failure
+ * *out = NULL and nothing is written.
+ * grlbwt_merge_create copies what it needs -- both images may be freed when it returns -- and runs all rounds; grlbwt_merge_emit
+ * writes the merged image (out_bytes of the info); grlbwt_merge_interleave the converged interleave as ceil(n / 64) words, bit p
+ * of word p / 64 set when row p comes from B; grlbwt_ctx_destroy releases the handles still alive.  grlbwt_merge_files: both
+ * images from files, the merged image to a file (pinned reader and writer of the other file calls).
+ * (GRLBWT_MERGE_ROUND=sort in the environment runs a round as gathered keys and a stable radix sort instead of the fused
+ * kernels: the same merge, the form the kernels are measured against.) */
+typedef struct grlbwt_merge grlbwt_merge;
+typedef struct grlbwt_merge_info {
+    uint64_t n_syms_a, n_syms_b, n_strings_a, n_strings_b;
+    uint64_t sigma, separator;          /* distinct symbols of both images together; the common smallest one */
+    uint64_t rounds;                    /* refinement rounds run, the one that changed nothing included */
+    uint64_t rows_changed;              /* summed over the rounds: what a work-skipping form would have to touch */
+    uint64_t n_runs, out_bytes, sb, fb; /* of the merged image */
+    uint64_t idx_bytes, tile_rows;      /* 4 or 8; merged rows per workgroup tile of the round kernels */
+    uint64_t scratch_bytes, held_bytes; /* peak scratch while merging; bytes the handle keeps */
+} grlbwt_merge_info;
+int grlbwt_merge_create(grlbwt_ctx *ctx, const void *dev_image_a, uint64_t bytes_a, const void *dev_image_b, uint64_t bytes_b,
+                        int cell_bytes, uint64_t max_rounds /* 0: n + 2 */, grlbwt_merge **out);
+int grlbwt_merge_info_get(const grlbwt_merge *mg, grlbwt_merge_info *out);
+int grlbwt_merge_emit(grlbwt_ctx *ctx, const grlbwt_merge *mg, void *dev_out, uint64_t capacity_bytes);
+int grlbwt_merge_interleave(grlbwt_ctx *ctx, const grlbwt_merge *mg, uint64_t *dev_bits);
+int grlbwt_merge_destroy(grlbwt_ctx *ctx, grlbwt_merge *mg);
+int grlbwt_merge_files(grlbwt_ctx *ctx, const char *path_a, const char *path_b, int cell_bytes, uint64_t max_rounds,
+                       const char *path_out, grlbwt_merge_info *info /* may be NULL */);
+
 /* ---- inspection (parity tests; need GRLBWT_FLAG_KEEP_LEVELS) --------------- */
 /* text of level >= 1 as (rank<<1 | rep) cells, the reference's on-disk parse format */
 int grlbwt_level_text_size(const grlbwt_ctx *ctx, int level, uint64_t *n_cells);
