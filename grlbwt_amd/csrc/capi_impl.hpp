@@ -1952,23 +1952,23 @@ int grlbwt_fm_create(grlbwt_ctx *ctx, const void *dev_image, uint64_t image_byte
     if (!ctx || !dev_image || !out) return GRLBWT_EINVAL;
     *out = nullptr;
     const uint32_t sample_bits = (fm_flags >> 8) & 0xFFu;
-    if ((fm_flags & ~(GRLBWT_FM_LOCATE | GRLBWT_FM_CHECKPOINTS | 0xFF00u)) || sample_bits > 20 ||
-        (!(fm_flags & GRLBWT_FM_CHECKPOINTS) && sample_bits) || ((fm_flags & GRLBWT_FM_CHECKPOINTS) && !(fm_flags & GRLBWT_FM_LOCATE))) {
-        ctx->err = "fm index: bad flags (checkpoints need the locate structures; sample_bits is 0 or 1 to 20 and needs checkpoints)";
+    if ((fm_flags & ~(GRLBWT_FM_LOCATE | GRLBWT_FM_CHECKPOINTS | GRLBWT_FM_EXTRACT | 0xFF00u)) || sample_bits > 20 ||
+        (!(fm_flags & GRLBWT_FM_CHECKPOINTS) && sample_bits) || ((fm_flags & (GRLBWT_FM_CHECKPOINTS | GRLBWT_FM_EXTRACT)) && !(fm_flags & GRLBWT_FM_LOCATE))) {
+        ctx->err = "fm index: bad flags (checkpoints and extracting need the locate structures; sample_bits is 0 or 1 to 20 and needs checkpoints)";
         return GRLBWT_EINVAL;
     }
     return guarded(ctx, [&] {
         const uint64_t total = grl64::Engine::image_total_symbols(dev_image, image_bytes);
         const bool big = total >= kIdx32Limit || (ctx->flags & GRLBWT_FLAG_FORCE_IDX64);
-        const bool locate = fm_flags & GRLBWT_FM_LOCATE, cps = fm_flags & GRLBWT_FM_CHECKPOINTS;
+        const bool locate = fm_flags & GRLBWT_FM_LOCATE, cps = fm_flags & GRLBWT_FM_CHECKPOINTS, ext = fm_flags & GRLBWT_FM_EXTRACT;
         std::unique_ptr<grlbwt_fm> fm(new grlbwt_fm());
         fm->flags = fm_flags;
         if (big) {
             fm->f64.reset(new grl64::Engine::FmIndex());
-            grl64::Engine::fm_create(dev_image, image_bytes, locate, prim::sw().fm_top_bits, *fm->f64, cps, (int)sample_bits);
+            grl64::Engine::fm_create(dev_image, image_bytes, locate, prim::sw().fm_top_bits, *fm->f64, cps, (int)sample_bits, ext);
         } else {
             fm->f32.reset(new grl32::Engine::FmIndex());
-            grl32::Engine::fm_create(dev_image, image_bytes, locate, prim::sw().fm_top_bits, *fm->f32, cps, (int)sample_bits);
+            grl32::Engine::fm_create(dev_image, image_bytes, locate, prim::sw().fm_top_bits, *fm->f32, cps, (int)sample_bits, ext);
         }
         ctx->fms.push_back(fm.get());
         *out = fm.release();
@@ -2042,6 +2042,34 @@ int grlbwt_fm_locate(grlbwt_ctx *ctx, const grlbwt_fm *fm, const uint64_t *dev_r
         if (fm->f32) grl32::Engine::fm_locate(*fm->f32, dev_rows, n_rows, max_steps, dev_string, dev_offset);
         else grl64::Engine::fm_locate(*fm->f64, dev_rows, n_rows, max_steps, dev_string, dev_offset);
     });
+}
+int grlbwt_fm_string_lengths(grlbwt_ctx *ctx, const grlbwt_fm *fm, uint64_t *dev_len) {
+    if (!ctx || !fm || !dev_len || !(fm->f32 || fm->f64)) return GRLBWT_EINVAL;
+    return guarded(ctx, [&] {
+        if (fm->f32) grl32::Engine::fm_string_lengths(*fm->f32, dev_len);
+        else grl64::Engine::fm_string_lengths(*fm->f64, dev_len);
+    });
+}
+int grlbwt_fm_extract(grlbwt_ctx *ctx, const grlbwt_fm *fm, const uint64_t *dev_string, const uint64_t *dev_begin, const uint64_t *dev_end,
+                      uint64_t n_ranges, int cell_bytes, void *dev_out, uint64_t capacity_cells, uint64_t *dev_out_offsets, uint64_t *n_cells_out) {
+    if (!ctx || !fm || !dev_out_offsets || !(fm->f32 || fm->f64)) return GRLBWT_EINVAL;
+    if (n_ranges && (!dev_string || !dev_begin || !dev_end || (!dev_out && capacity_cells))) return GRLBWT_EINVAL;
+    return guarded(ctx, [&] {
+        const uint64_t n = fm->f32 ? grl32::Engine::fm_extract(*fm->f32, dev_string, dev_begin, dev_end, n_ranges, cell_bytes, dev_out, capacity_cells, dev_out_offsets)
+                                   : grl64::Engine::fm_extract(*fm->f64, dev_string, dev_begin, dev_end, n_ranges, cell_bytes, dev_out, capacity_cells, dev_out_offsets);
+        if (n_cells_out) *n_cells_out = n;
+    });
+}
+int grlbwt_fm_extract_info_get(const grlbwt_fm *fm, grlbwt_fm_extract_info *out) {
+    if (!fm || !out || !(fm->f32 || fm->f64)) return GRLBWT_EINVAL;
+    if (fm->f32 ? !fm->f32->extract : !fm->f64->extract) return GRLBWT_EINVAL;
+    auto fill = [&](const auto &F) {
+        const auto &x = F.xinfo;
+        out->n_ranges = x.ranges; out->n_pieces = x.pieces; out->n_cells = x.cells; out->walk_steps = x.steps;
+        out->walk_lanes = x.lanes; out->lane_refills = x.refills; out->n_samples = F.xq.n; out->extract_bytes = F.extract_bytes();
+    };
+    if (fm->f32) fill(*fm->f32); else fill(*fm->f64);
+    return GRLBWT_OK;
 }
 
 int grlbwt_merge_create(grlbwt_ctx *ctx, const void *dev_image_a, uint64_t bytes_a, const void *dev_image_b, uint64_t bytes_b, int cell_bytes,

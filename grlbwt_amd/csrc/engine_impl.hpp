@@ -3538,6 +3538,121 @@ struct FmLocateCpFn {
     }
 };
 
+// ---- extracting text ranges (grlbwt_fm_extract).  T[s] = the cells in front of string s, so (s, o) is the absolute
+// position T[s] + o.  The index keeps the INVERSE of its samples: xq = the absolute positions of the sampled rows, ascending, and
+// xc = the checkpoint of each (its row is cp.row_of).  The head of string s is a sample at T[s + 1] - 1, its separator's position,
+// so every cell of a string lies below a sample of that string, and one LF step from the row of position x reads cell x - 1.
+struct FmSidLenFn {       // FmSidFn for an index that extracts: the steps of string i's walk + the separator are its length
+    const RankCell *rc; const RunRec *rec; u32 sep; u64 n; idx_t *sid, *slen; u32 *bad;
+    GRL_DEV void operator()(u64 i) const {
+        idx_t row = (idx_t)i;
+        u64 s = 0;
+        RunRec r = rec[run_of_row(rc, (u64)row)];
+        for (; s < n && r.sym != sep; s++) { row = (idx_t)(row + (idx_t)r.delta); r = rec[run_of_row(rc, (u64)row)]; }
+        if (r.sym != sep) { prim::atomic_max(bad, 1u); return; }
+        sid[(u64)(idx_t)(row + (idx_t)r.delta)] = (idx_t)i;
+        slen[i] = (idx_t)(s + 1);
+    }
+};
+struct FmHeadSampleFn {   // without checkpoints the samples are the k heads: sorted as they come
+    const idx_t *T; idx_t *xq, *xc;
+    GRL_DEV void operator()(u64 s) const { xq[s] = (idx_t)(T[s + 1] - 1); xc[s] = (idx_t)s; }
+};
+struct FmCpSampleKeyFn {  // checkpoint c -> (absolute position, c); n, above every position, for a void checkpoint or one on no string's chain
+    Checkpoints cp; const idx_t *head, *dist, *T; idx_t *key, *val;
+    GRL_DEV void operator()(u64 c) const {
+        const idx_t h = head[c];
+        const bool has = h != kCpNone && !cp.is_void(c);
+        key[c] = has ? (idx_t)(T[(u64)h + 1] - 1 - dist[c]) : (idx_t)cp.n;
+        val[c] = (idx_t)c;
+    }
+};
+struct FmSampleValidIn {
+    const idx_t *key; u64 n;
+    GRL_DEV u64 operator()(u64 c) const { return (u64)key[c] != n ? 1ull : 0ull; }
+};
+struct FmLenOutFn {
+    const idx_t *T; u64 *len;
+    GRL_DEV void operator()(u64 s) const { len[s] = (u64)T[s + 1] - (u64)T[s]; }
+};
+struct FmExtractBadIn {   // the number of a range whose string is none, else ~0
+    const u64 *str; u64 k;
+    GRL_DEV u64 operator()(u64 i) const { return str[i] >= k ? i : ~0ull; }
+};
+// Range i of string s = str[i]: cells [b, e) with e clamped to the string's length, [B, E) in absolute positions.  The separator's
+// cell (E = T[s + 1]) is stored directly, the cells [B, E') in front of it are walked: E' = E - 1 there, E elsewhere.
+struct FmRange {
+    u64 B, E, Ew;         // Ew = E': (B < Ew: there is something to walk)
+    bool sep;
+};
+struct FmExtractPlan {
+    const idx_t *T, *xq; u64 ns; const u64 *str, *beg, *end;
+    GRL_DEV FmRange range(u64 i) const {
+        const u64 s = str[i], t0 = (u64)T[s], t1 = (u64)T[s + 1], len = t1 - t0;
+        const u64 e = end[i] < len ? end[i] : len, b = beg[i] < e ? beg[i] : e;      // (b >= e: empty)
+        FmRange r;
+        r.B = t0 + b; r.E = t0 + e;
+        r.sep = b < e && r.E == t1;
+        r.Ew = r.sep ? r.E - 1 : r.E;
+        return r;
+    }
+    GRL_DEV u64 first_above(u64 B) const { return upper_bound<idx_t>(xq, ns, (idx_t)B); }       // the first sample q > B
+};
+// The pieces of a range are the samples q with B < q <= q_top, q_top = the smallest sample >= E' (it exists, in the same string:
+// the head); cells = its length; steps = the cells walked + the steps q_top - E' its top piece takes before it writes.
+struct FmExtractPlanFn {
+    FmExtractPlan p; u64 *npiece, *ncell, *nstep;
+    GRL_DEV void operator()(u64 i) const {
+        const FmRange r = p.range(i);
+        u64 pieces = 0, steps = 0;
+        if (r.B < r.Ew) {
+            const u64 top = lower_bound<idx_t>(p.xq, p.ns, (idx_t)r.Ew);
+            pieces = top - p.first_above(r.B) + 1;
+            steps = (u64)p.xq[top] - r.B;
+        }
+        npiece[i] = pieces; ncell[i] = r.E - r.B; nstep[i] = steps;
+    }
+};
+template <class cell_t>
+struct FmExtractSepFn {   // the separator of every range that reaches its string's end
+    FmExtractPlan p; const u64 *ooff; cell_t *out; cell_t sepval;
+    GRL_DEV void operator()(u64 i) const {
+        const FmRange r = p.range(i);
+        if (r.sep) out[ooff[i] + (r.E - r.B) - 1] = sepval;
+    }
+};
+// One ticket per piece.  Piece j of range i (pscan[i] <= ticket < pscan[i + 1]) belongs to sample first_above(B) + j, at position
+// q; it writes the cells [lo, top), lo = B for j = 0 and the sample below q otherwise, top = min(q, E'), walking backwards from
+// q's row: q - top steps that store nothing (the top piece alone has any), then one store per step.
+//   Bounds, known before the launch: the steps of a piece are q - lo <= the gap between neighbouring samples <= n, and lo >= T[s]:
+//   the walk never steps from its string's first row.  A cell x of range i goes to ooff[i] + (x - B) < ooff[i + 1] <= n_cells, which
+//   the caller has checked against the capacity.
+template <class cell_t>
+struct FmExtractFn {
+    struct State { idx_t row; u64 skip, left, o; };
+    const RankCell *rc; const RunRec *rec; Checkpoints cp; const idx_t *xc; FmExtractPlan p; u64 nr; const u64 *pscan, *ooff; cell_t *out; const u64 *alpha;
+    GRL_DEV cell_t val(u32 c) const { return alpha ? (cell_t)alpha[c] : (cell_t)c; }
+    GRL_DEV bool begin(u64 t, State &st) const {
+        const u64 i = upper_bound<u64>(pscan, nr + 1, t) - 1;       // (ranges without a piece are stepped over)
+        const u64 j = t - pscan[i];
+        const FmRange r = p.range(i);
+        const u64 x = p.first_above(r.B) + j;
+        const u64 q = (u64)p.xq[x], lo = j ? (u64)p.xq[x - 1] : r.B, top = q < r.Ew ? q : r.Ew;
+        st.row = (idx_t)cp.row_of((u64)xc[x]);
+        st.skip = q - top; st.left = top - lo;
+        st.o = ooff[i] + (top - r.B);
+        return true;                                                // (left >= 1: lo < top by the choice of the samples)
+    }
+    GRL_DEV bool step(State &st) const {
+        const RunRec r = rec[run_of_row(rc, (u64)st.row)];
+        st.row = (idx_t)(st.row + (idx_t)r.delta);
+        if (st.skip) { st.skip--; return false; }
+        out[--st.o] = val(r.sym);
+        return --st.left == 0;
+    }
+    GRL_DEV void end(u64, const State &) const {}
+};
+
 // =========================================================================
 struct RoundInfo {
     u64 n_in = 0, D = 0, S = 0, M = 0, parse_size = 0, sigma = 0, max_phrase_len = 0, sort_iters = 0, table_retries = 0;
@@ -6390,6 +6505,7 @@ class Engine {
     }
 
     // ---- the FM index over the runs of an image (grlbwt_fm_*; functor block "counting and locating patterns") ----------------
+    struct ExtractInfo { u64 ranges = 0, pieces = 0, cells = 0, steps = 0, lanes = 0, refills = 0; };      // of the last fm_extract
     struct FmIndex {
         u64 n = 0, R = 0, k = 0, sigma = 0, sepval = 0;
         u32 sep = 0, top_entries = 0;
@@ -6404,15 +6520,22 @@ class Engine {
         Checkpoints cp{0, 0, 0};
         DBuf<idx_t> smp;
         WalkInfo walk;
+        bool extract = false;     // extract: the strings' start positions T (k + 1) and the inverse of the samples, (position, checkpoint) by position
+        u64 maxval = 0;           // (the largest symbol's value)
+        DBuf<idx_t> T, xq, xc;
+        mutable ExtractInfo xinfo;
+        u64 extract_bytes() const { return (T.n + xq.n + xc.n) * sizeof(idx_t); }
         u64 bytes() const {
             return key.n * sizeof(FmKey) + slf.n * sizeof(idx_t) + alpha.n * 8 + rc.n * sizeof(RankCell) + rec.n * sizeof(RunRec) + sid.n * sizeof(idx_t) +
-                   smp.n * sizeof(idx_t);
+                   smp.n * sizeof(idx_t) + extract_bytes();
         }
     };
     // What the locate structures may take while they are made: half of the free device memory (a quarter byte per symbol for the
     // bit-vector and its ranks, a word per string).  The serial stand-in, which walks the strings one after the other, stops at 256 MB.
     static u64 fm_locate_budget() { return prim::kIsDevice ? prim::mem_available() / 2 : (u64)1 << 28; }
-    static void fm_create(const void *dev_image, u64 image_bytes, bool locate, int top_bits, FmIndex &F, bool checkpoints = false, int sample_bits = 0) {
+    static void fm_create(const void *dev_image, u64 image_bytes, bool locate, int top_bits, FmIndex &F, bool checkpoints = false, int sample_bits = 0,
+                          bool extract = false) {
+        if (extract && !locate) throw prim::Error(-22, "fm index: extracting needs the structures for locating");
         const int b = checkpoints ? sample_bits_of(sample_bits) : 0;
         const ImageHeader h = image_header(dev_image, image_bytes);
         if (h.R == 0) throw prim::Error(-22, "fm index: the image has no record");
@@ -6428,6 +6551,8 @@ class Engine {
             const u64 words = (X.n + 1) / 64 + 2;
             u64 need = words * (sizeof(RankCell) + 8 + sizeof(idx_t)) + X.R * sizeof(RunRec) + X.k * sizeof(idx_t);
             if (checkpoints) need += (Checkpoints{X.n, X.k, (u32)b}.count() * 8 + 2 * X.k + 1) * sizeof(idx_t) + X.k * 8;       // the ranking's scratch and the samples
+            // the inverse table (a pair per sample, at most one per checkpoint) beside the second half of its sort, and T
+            if (extract) need += (4 * (checkpoints ? Checkpoints{X.n, X.k, (u32)b}.count() : X.k) + X.k + 1) * sizeof(idx_t);
             if (X.n >= ((u64)1 << 62) || need > fm_locate_budget())
                 throw prim::Error(-22, "fm index: the structures for locating (" + std::to_string(need) + " bytes) are more than this device can hold");
         }
@@ -6451,6 +6576,33 @@ class Engine {
             F.smp.alloc(2 * F.walk.m);
             prim::for_each(F.walk.m, CpSampleFn{C.head.p, C.dist.p, C.slen.p, F.smp.p}, "fm.samples");
             F.walk.sample_bytes = F.smp.n * sizeof(idx_t);
+            if (extract) {
+                const u64 m = F.walk.m;
+                C.seglen.release(); C.endcp.release();
+                F.T.alloc(F.k + 1);
+                prim::exclusive_scan<idx_t>(F.k, IdxIn<idx_t>{C.slen.p}, F.T.p, true, "fm.extract_starts");
+                DBuf<idx_t> ka(m), va(m), kb(m), vb(m);
+                prim::for_each(m, FmCpSampleKeyFn{C.cp, C.head.p, C.dist.p, F.T.p, ka.p, va.p}, "fm.extract_keys");
+                C.head.release(); C.dist.release();
+                const u64 ns = prim::reduce_sum<u64>(m, FmSampleValidIn{ka.p, F.n}, "fm.extract_samples");
+                const int res = prim::sort_pairs<idx_t, idx_t>(ka.p, va.p, kb.p, vb.p, m, 0, std::max((int)bitlen64(F.n), 1), "fm.extract_sort");
+                F.xq.alloc(ns); F.xc.alloc(ns);      // (the ns samples come first: the others carry n)
+                d2d_copy(F.xq.p, res ? kb.p : ka.p, ns);
+                d2d_copy(F.xc.p, res ? vb.p : va.p, ns);
+            }
+        } else if (locate && F.R && extract) {
+            DBuf<u32> bad(1);
+            bad.zero();
+            F.sid.alloc(F.k);
+            DBuf<idx_t> slen(F.k + 1);
+            slen.zero();
+            prim::for_each(F.k, FmSidLenFn{F.rc.p, F.rec.p, F.sep, F.n, F.sid.p, slen.p, bad.p}, "fm.sid_len");
+            if (bad.get(0)) throw prim::Error(-22, "fm index: a string's walk met no separator in n steps: not the BWT of a collection");
+            F.cp = Checkpoints{F.n, F.k, 0};         // (row_of(c) = c below k: the heads' rows)
+            F.T.alloc(F.k + 1);
+            prim::exclusive_scan<idx_t>(F.k, IdxIn<idx_t>{slen.p}, F.T.p, true, "fm.extract_starts");
+            F.xq.alloc(F.k); F.xc.alloc(F.k);
+            prim::for_each(F.k, FmHeadSampleFn{F.T.p, F.xq.p, F.xc.p}, "fm.extract_heads");
         } else if (locate && F.R) {
             DBuf<u32> bad(1);
             bad.zero();
@@ -6458,6 +6610,7 @@ class Engine {
             prim::for_each(F.k, FmSidFn{F.rc.p, F.rec.p, F.sep, F.n, F.sid.p, bad.p}, "fm.sid");
             if (bad.get(0)) throw prim::Error(-22, "fm index: a string's walk met no separator in n steps: not the BWT of a collection");
         }
+        if (extract) { F.extract = true; F.maxval = F.alpha.p ? F.alpha.get(F.alpha.n - 1) : (u64)X.mx; }
         prim::sync();
     }
     static void fm_count(const FmIndex &F, const void *cells, int w, const u64 *off, u64 np, u64 *lo, u64 *hi) {
@@ -6490,6 +6643,55 @@ class Engine {
         if (F.checkpoints) prim::for_each(nr, FmLocateCpFn{F.rc.p, F.rec.p, F.sid.p, F.smp.p, F.cp, F.sep, lim, rows, str, ofs}, "fm.locate_cp");
         else prim::for_each(nr, FmLocateFn{F.rc.p, F.rec.p, F.sid.p, F.sep, lim, rows, str, ofs}, "fm.locate");
         prim::sync();
+    }
+    // ---- extract (functor block "extracting text ranges").  Everything that can refuse the call runs before the first
+    // store into `out` or `out_off`: the ranges' strings, then the plan -- pieces, cells and steps per range, scanned in scratch --
+    // and the capacity.  Then the separators (one lane per range) and the walk, one ticket per piece.
+    //   Loops: the binary searches run over the table and the scanned counts; a piece's steps are planned (FmExtractFn); nothing
+    //   waits for another thread, and the only atomics are the ticket word's.
+    static void fm_string_lengths(const FmIndex &F, u64 *len) {
+        if (!F.extract) throw prim::Error(-22, "fm string lengths: the index was made without the structures for extracting");
+        prim::for_each(F.k, FmLenOutFn{F.T.p, len}, "fm.string_lengths");
+        prim::sync();
+    }
+    template <class cell_t>
+    static void fm_extract_t(const FmIndex &F, const FmExtractPlan &P, u64 nr, const u64 *pscan, const u64 *ooff, u64 pieces, cell_t *out, ExtractInfo &xi) {
+        prim::for_each(nr, FmExtractSepFn<cell_t>{P, ooff, out, (cell_t)F.sepval}, "fm.extract_sep");
+        WalkInfo wi;
+        walk(pieces, FmExtractFn<cell_t>{F.rc.p, F.rec.p, F.cp, F.xc.p, P, nr, pscan, ooff, out, F.alpha.p}, wi, "fm.extract");
+        xi.lanes = wi.lanes; xi.refills = wi.refills;
+    }
+    static u64 fm_extract(const FmIndex &F, const u64 *str, const u64 *beg, const u64 *end, u64 nr, int w, void *out, u64 capacity, u64 *out_off) {
+        if (!F.extract) throw prim::Error(-22, "fm extract: the index was made without the structures for extracting");
+        if (!(w == 1 || w == 2 || w == 4 || w == 8)) throw prim::Error(-22, "fm extract: bad cell width");
+        if (w < 8 && (F.maxval >> (8 * w))) throw prim::Error(-22, "fm extract: the image's largest symbol does not fit the cell width");
+        ExtractInfo xi;
+        xi.ranges = nr;
+        if (nr == 0) {
+            prim::dev_memset(out_off, 0, 8);
+            prim::sync();
+            F.xinfo = xi;
+            return 0;
+        }
+        const u64 bad = prim::reduce_min<u64>(nr, FmExtractBadIn{str, F.k}, "fm.extract_strings");
+        if (bad != ~0ull) throw prim::Error(-22, "fm extract: range " + std::to_string(bad) + " names a string that is not below the number of strings");
+        const FmExtractPlan P{F.T.p, F.xq.p, F.xq.n, str, beg, end};
+        DBuf<u64> npiece(nr + 1), ncell(nr + 1), nstep(nr);
+        prim::for_each(nr, FmExtractPlanFn{P, npiece.p, ncell.p, nstep.p}, "fm.extract_plan");
+        xi.steps = prim::reduce_sum<u64>(nr, CellIn<u64>{nstep.p}, "fm.extract_steps");
+        xi.pieces = prim::exclusive_scan<u64>(nr, CellIn<u64>{npiece.p}, npiece.p, true, "fm.extract_pieces");
+        xi.cells = prim::exclusive_scan<u64>(nr, CellIn<u64>{ncell.p}, ncell.p, true, "fm.extract_cells");
+        if (xi.cells > capacity) throw prim::Error(-22, "fm extract: the ranges hold " + std::to_string(xi.cells) + " cells, more than the output buffer");
+        prim::d2d(out_off, ncell.p, (nr + 1) * 8);
+        switch (w) {
+            case 1: fm_extract_t<u8>(F, P, nr, npiece.p, ncell.p, xi.pieces, (u8 *)out, xi); break;
+            case 2: fm_extract_t<u16>(F, P, nr, npiece.p, ncell.p, xi.pieces, (u16 *)out, xi); break;
+            case 4: fm_extract_t<u32>(F, P, nr, npiece.p, ncell.p, xi.pieces, (u32 *)out, xi); break;
+            default: fm_extract_t<u64>(F, P, nr, npiece.p, ncell.p, xi.pieces, (u64 *)out, xi); break;
+        }
+        prim::sync();
+        F.xinfo = xi;
+        return xi.cells;
     }
 
     // ---- merging two images into the image of "A's strings, then B's" (grlbwt_merge_*; functor block "merging two images";

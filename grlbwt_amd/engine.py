@@ -35,12 +35,14 @@ ABI_SYMBOLS = [
     "grlbwt_alphabet_size", "grlbwt_alphabet_download", "grlbwt_alphabet_compact_device",
     "grlbwt_fm_create", "grlbwt_fm_destroy", "grlbwt_fm_info_get", "grlbwt_fm_count", "grlbwt_fm_locate",
     "grlbwt_invert_image_checkpointed", "grlbwt_fm_walk_info_get",
+    "grlbwt_fm_string_lengths", "grlbwt_fm_extract", "grlbwt_fm_extract_info_get",
     "grlbwt_merge_create", "grlbwt_merge_info_get", "grlbwt_merge_emit", "grlbwt_merge_interleave", "grlbwt_merge_destroy",
     "grlbwt_merge_files",
 ]
 
 FM_LOCATE = 1
 FM_CHECKPOINTS = 2
+FM_EXTRACT = 4
 UINT64_MAX = 2 ** 64 - 1
 
 
@@ -58,6 +60,11 @@ class MergeInfo(C.Structure):
 class WalkInfo(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in ("n_strings", "n_checkpoints", "sample_bits", "longest_segment", "longest_chain",
                                           "jump_rounds", "walk_lanes", "lane_refills", "scratch_bytes", "sample_bytes")]
+
+
+class ExtractInfo(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("n_ranges", "n_pieces", "n_cells", "walk_steps", "walk_lanes", "lane_refills",
+                                          "n_samples", "extract_bytes")]
 
 
 class ImageStats(C.Structure):
@@ -209,6 +216,9 @@ def load_library(path=None, allow_test_standin=False):
     L.grlbwt_fm_info_get.argtypes = [vp, C.POINTER(FmInfo)]
     L.grlbwt_fm_count.argtypes = [vp, vp, vp, i32, vp, u64, vp, vp]
     L.grlbwt_fm_locate.argtypes = [vp, vp, vp, u64, u64, vp, vp]
+    L.grlbwt_fm_string_lengths.argtypes = [vp, vp, vp]
+    L.grlbwt_fm_extract.argtypes = [vp, vp, vp, vp, vp, u64, i32, vp, u64, vp, C.POINTER(u64)]
+    L.grlbwt_fm_extract_info_get.argtypes = [vp, C.POINTER(ExtractInfo)]
     L.grlbwt_merge_create.argtypes = [vp, vp, u64, vp, u64, i32, u64, C.POINTER(vp)]
     L.grlbwt_merge_info_get.argtypes = [vp, C.POINTER(MergeInfo)]
     L.grlbwt_merge_emit.argtypes = [vp, vp, vp, u64]
@@ -510,14 +520,15 @@ class Context:
 class FmIndex:
     """Count and locate patterns in an .rl_bwt image (grlbwt_fm_*): an index made from an image in device memory, which may
     be freed afterwards.  All pointers are device pointers; locate=True also builds what locate() needs, checkpoints=True
-    (with locate) the samples that bound a locate walk by 2^sample_bits steps (0: the default) whatever the strings' lengths."""
+    (with locate) the samples that bound a locate walk by 2^sample_bits steps (0: the default) whatever the strings' lengths,
+    extract=True (with locate) what extract() and string_lengths() need: the index then stands in for the text."""
 
-    def __init__(self, ctx, dev_image_ptr, image_bytes, locate=False, checkpoints=False, sample_bits=0):
+    def __init__(self, ctx, dev_image_ptr, image_bytes, locate=False, checkpoints=False, sample_bits=0, extract=False):
         self.ctx = ctx
         h = C.c_void_p()
         if not 0 <= sample_bits <= 255:
             raise GrlbwtError(-22, "sample_bits is 0 or 1 to 20")
-        flags = (FM_LOCATE if locate else 0) | (FM_CHECKPOINTS if checkpoints else 0) | (sample_bits << 8)
+        flags = (FM_LOCATE if locate else 0) | (FM_CHECKPOINTS if checkpoints else 0) | (FM_EXTRACT if extract else 0) | (sample_bits << 8)
         ctx._ck(ctx.L.grlbwt_fm_create(ctx._h, C.c_void_p(dev_image_ptr), image_bytes, flags, C.byref(h)))
         self._h = h
 
@@ -545,6 +556,26 @@ class FmIndex:
         """(string, offset) of every row; UINT64_MAX in both where the offset is above max_steps."""
         self.ctx._ck(self.ctx.L.grlbwt_fm_locate(self.ctx._h, self._h, C.c_void_p(rows_ptr), n_rows, max_steps,
                                                  C.c_void_p(string_ptr), C.c_void_p(offset_ptr)))
+
+    def string_lengths(self, len_ptr):
+        """The length of every string, its separator included (n_strings uint64 words)."""
+        self.ctx._ck(self.ctx.L.grlbwt_fm_string_lengths(self.ctx._h, self._h, C.c_void_p(len_ptr)))
+
+    def extract(self, string_ptr, begin_ptr, end_ptr, n, cell_bytes, out_ptr, capacity_cells, offsets_ptr):
+        """Cells [begin[i], min(end[i], length)) of string[i] for n ranges, back to back in out; offsets[i] = the first cell of
+        range i, offsets[n] = the number of cells, which is returned.  UINT64_MAX as an end: to the end of the string."""
+        got = C.c_uint64()
+        self.ctx._ck(self.ctx.L.grlbwt_fm_extract(self.ctx._h, self._h, C.c_void_p(string_ptr), C.c_void_p(begin_ptr), C.c_void_p(end_ptr),
+                                                  n, cell_bytes, C.c_void_p(out_ptr), capacity_cells, C.c_void_p(offsets_ptr), C.byref(got)))
+        return got.value
+
+    def extract_info(self):
+        """The counters of the last extract() on this index (an index made without extract=True: GrlbwtError)."""
+        out = ExtractInfo()
+        rc = self.ctx.L.grlbwt_fm_extract_info_get(self._h, C.byref(out))
+        if rc != OK:
+            raise GrlbwtError(rc, self.ctx.L.grlbwt_strerror(rc).decode())
+        return _as_dict(out)
 
     def close(self):
         h, self._h = getattr(self, "_h", None), None

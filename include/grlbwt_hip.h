@@ -324,7 +324,31 @@ int grlbwt_image_split_runs(grlbwt_ctx *ctx, const void *dev_image, uint64_t ima
  * the strings behind the separators from the ranked segments instead of by a walk over every string.  GRLBWT_FM_SAMPLE_BITS(b)
  * in fm_flags sets sample_bits (0 or 1..20; a value without GRLBWT_FM_CHECKPOINTS, or above 20: GRLBWT_EINVAL, *out = NULL).  grlbwt_fm_locate on such an index stops at a checkpoint row as well as at a separator; its
  * contract and its outputs are those of the index without checkpoints for every row and every max_steps (an answer found through
- * a sample whose offset is above max_steps is suppressed).  grlbwt_fm_walk_info_get: GRLBWT_EINVAL for an index without checkpoints. */
+ * a sample whose offset is above max_steps is suppressed).  grlbwt_fm_walk_info_get: GRLBWT_EINVAL for an index without checkpoints.
+ *
+ * GRLBWT_FM_EXTRACT (with GRLBWT_FM_LOCATE; alone: GRLBWT_EINVAL, *out = NULL; with or without GRLBWT_FM_CHECKPOINTS) makes the index
+ * a self-index: grlbwt_fm_extract returns cells of the text, which need not be kept.  COORDINATES, those of grlbwt_fm_locate:
+ * string s has slen[s] cells, its separator included as the last one (offset slen[s] - 1; grlbwt_fm_string_lengths writes the
+ * n_strings values of slen).  The index keeps T, the k + 1 scanned lengths, and the INVERSE of its samples: the absolute position
+ * T[string] + offset of every sample, ascending, with its checkpoint beside it -- two words of the position width per sample
+ * (n_samples: with checkpoints every checkpoint that lies on a string, at most n_checkpoints; without, the n_strings separators'
+ * rows).  extract_bytes = (2 n_samples + n_strings + 1) position words; it is counted in index_bytes and in the budget of
+ * GRLBWT_FM_LOCATE.  An index made without the bit holds what it held before, byte for byte.
+ *
+ * grlbwt_fm_extract: range i is cells [dev_begin[i], min(dev_end[i], slen)) of string dev_string[i] -- Python's slice rules: an
+ * end of UINT64_MAX means "to the end of the string", the separator is included when the range reaches it, begin at or behind the
+ * clamped end is an empty range.  The ranges go out back to back in input order as cells of cell_bytes (wide symbols as their
+ * values): dev_out_offsets[i] is the first cell of range i in dev_out, dev_out_offsets[n_ranges] = *n_cells_out.  n_ranges = 0
+ * is legal and writes dev_out_offsets[0] = 0.  The results are complete when the call returns.  The WHOLE call fails with
+ * GRLBWT_EINVAL, and neither output buffer is written, when a dev_string[i] >= n_strings (the message names the first such
+ * range), the ranges hold more than capacity_cells cells, cell_bytes is not in {1, 2, 4, 8}, the index's largest symbol does not
+ * fit cell_bytes, or the index was made without GRLBWT_FM_EXTRACT.
+ * COST: a range is cut at the samples inside it into pieces that are walked in parallel, each backwards from its sample's row, at
+ * most the gap between neighbouring samples (with checkpoints about 2^sample_bits, at most longest_segment) dependent LF steps;
+ * only the topmost piece first steps down from the sample above the range's end without writing.  Without checkpoints the only
+ * samples are the strings' ends: a range costs the steps from its string's END to its begin, one lane per range -- fine for
+ * read-like collections.  grlbwt_fm_extract_info_get: the counters of the last grlbwt_fm_extract on the index (GRLBWT_EINVAL for
+ * an index without the bit). */
 typedef struct grlbwt_fm grlbwt_fm;
 #define GRLBWT_FM_LOCATE 1u      /* also build what grlbwt_fm_locate needs (one LF walk over every string, like the inverter's length pass) */
 typedef struct grlbwt_fm_info {
@@ -343,6 +367,18 @@ int grlbwt_fm_count(grlbwt_ctx *ctx, const grlbwt_fm *fm, const void *dev_cells,
                     uint64_t n_patterns, uint64_t *dev_lo, uint64_t *dev_hi);
 int grlbwt_fm_locate(grlbwt_ctx *ctx, const grlbwt_fm *fm, const uint64_t *dev_rows, uint64_t n_rows, uint64_t max_steps,
                      uint64_t *dev_string, uint64_t *dev_offset);
+#define GRLBWT_FM_EXTRACT 4u    /* with GRLBWT_FM_LOCATE; alone: GRLBWT_EINVAL. With or without GRLBWT_FM_CHECKPOINTS */
+typedef struct grlbwt_fm_extract_info {
+    uint64_t n_ranges, n_pieces, n_cells;   /* of the last grlbwt_fm_extract on this index */
+    uint64_t walk_steps;                     /* LF steps planned: skipped + written */
+    uint64_t walk_lanes, lane_refills;       /* of the walk launch, as in grlbwt_walk_info */
+    uint64_t n_samples, extract_bytes;       /* entries of the inverse table; bytes GRLBWT_FM_EXTRACT added to the index */
+} grlbwt_fm_extract_info;
+int grlbwt_fm_string_lengths(grlbwt_ctx *ctx, const grlbwt_fm *fm, uint64_t *dev_len /* n_strings words, separator included */);
+int grlbwt_fm_extract(grlbwt_ctx *ctx, const grlbwt_fm *fm, const uint64_t *dev_string, const uint64_t *dev_begin, const uint64_t *dev_end,
+                      uint64_t n_ranges, int cell_bytes, void *dev_out, uint64_t capacity_cells,
+                      uint64_t *dev_out_offsets /* n_ranges + 1 words, written */, uint64_t *n_cells_out);
+int grlbwt_fm_extract_info_get(const grlbwt_fm *fm, grlbwt_fm_extract_info *out);
 
 /* ---- merging two images: the image of the collection "strings of A, then strings of B" from the images of A and B, without the
  * texts -- a collection larger than one build is built in batches and folded together, a batch of new strings is added to an
