@@ -41,13 +41,17 @@ struct arguments {
     int gpus = 1;                           // --gpus N: one process per GPU, record shards, RCCL (collection-level mode)
     bool merge = false;                     // --merge A B: no TEXT; the images of two collections -> the image of "A's strings, then B's"
     std::string merge_a, merge_b;
+    bool select = false;                    // --select IMAGE (--drop IDS | --keep IDS): no TEXT; the image without the listed strings, or of them alone
+    std::string select_image, drop_ids, keep_ids;
+    int sample_bits = -1;                   // --sample-bits B: the checkpointed form of the marking walk (0: the default spacing)
     std::string version = "v1.0.1 alpha";   // main.cpp:20 (reference version string)
 };
 
 static void usage(const char *prog) {
     std::cout << "Repetition-aware BWT construction (MI355X / HIP engine)\n"
               << "Usage: " << prog << " [OPTIONS] TEXT\n"
-              << "       " << prog << " --merge A.rl_bwt B.rl_bwt -o OUT [-a N] [-g DEV]\n\n"
+              << "       " << prog << " --merge A.rl_bwt B.rl_bwt -o OUT [-a N] [-g DEV]\n"
+              << "       " << prog << " --select IMAGE.rl_bwt (--drop IDS | --keep IDS) -o OUT [-a N] [--sample-bits B] [-g DEV]\n\n"
               << "Positionals:\n"
               << "  TEXT                   Input file in one-string-per-line format\n\n"
               << "Options:\n"
@@ -65,6 +69,13 @@ static void usage(const char *prog) {
               << "  --merge A B            Merge the images of two collections into the image of \"A's strings, then B's\" (no TEXT;\n"
               << "                         needs -o; -a as the images were built; at most 256 distinct symbols in both together;\n"
               << "                         about read length + 1 passes over the merged rows: for read-like collections)\n"
+              << "  --select IMAGE         Remove strings from the image of a collection, or keep only some (no TEXT; needs -o and\n"
+              << "                         one of --drop / --keep; -a as the image was built); the strings keep their order\n"
+              << "  --drop IDS             With --select: IDS is a text file of decimal string numbers (input order, from 0) separated\n"
+              << "                         by white space; those strings are removed\n"
+              << "  --keep IDS             With --select: only the strings IDS lists remain\n"
+              << "  --sample-bits B        With --select: mark through checkpoints, one in 2^B rows (0: the default spacing, 1..20);\n"
+              << "                         the form for collections of long strings (chromosomes)\n"
               << "  -g,--gpu               HIP device ordinal (def. 0; with --gpus: the first of N consecutive devices)\n"
               << "  --gpus                 Number of GPUs: the collection is sharded by record, one process per GPU,\n"
               << "                         exchanges over RCCL; the output does not depend on it (def. 1)\n";
@@ -359,6 +370,70 @@ static int run_merge(arguments &args, bool have_text) {
     return 0;
 }
 
+// ---- --select IMAGE (--drop IDS | --keep IDS): an image -> the image without / of the listed strings (grlbwt_select_files) ----
+static int run_select(arguments &args, bool have_text) {
+    if (have_text) fail(105, "--select: takes an image and no TEXT (got " + args.input_file + ")");
+    if (args.output_file.empty()) fail(105, "--select: --output-file is required");
+    if (args.drop_ids.empty() == args.keep_ids.empty()) fail(105, "--select: exactly one of --drop IDS and --keep IDS is required");
+    if (args.merge) fail(105, "--select: cannot be combined with --merge");
+    if (args.gpus > 1) fail(105, "--select: runs on one GPU (--gpus " + std::to_string(args.gpus) + ")");
+    if (args.fastx || args.rev_comp) fail(105, "--select: takes an image, not FASTA/Q records (--fastx / -R)");
+    if (!is_file(args.select_image)) fail(105, "--select: File does not exist: " + args.select_image);
+    const bool keep = !args.keep_ids.empty();
+    const std::string ids_path = keep ? args.keep_ids : args.drop_ids, opt = keep ? "--keep" : "--drop";
+    if (!is_file(ids_path)) fail(105, opt + ": File does not exist: " + ids_path);
+    std::vector<uint64_t> ids;
+    {
+        std::ifstream in(ids_path);
+        std::string tok;
+        while (in >> tok) {
+            errno = 0;
+            char *end = nullptr;
+            const unsigned long long v = std::strtoull(tok.c_str(), &end, 10);
+            if (tok[0] < '0' || tok[0] > '9' || *end != 0 || errno == ERANGE) fail(105, opt + ": not a string number: " + tok);
+            ids.push_back((uint64_t)v);
+        }
+    }
+    if (args.ver) { std::cout << args.version << std::endl; return 0; }
+    args.output_file = std::filesystem::path(args.output_file).replace_extension(".rl_bwt");
+    std::cout << "Input image:      " << args.select_image << std::endl;
+    std::cout << (args.alph_bytes > 1 ? "Alphabet type:    integer" : "Alphabet type:    byte") << std::endl;
+    const auto t_start = std::chrono::steady_clock::now();
+    grlbwt_ctx *ctx = nullptr;
+    int rc = grlbwt_ctx_create(args.device, 0, &ctx);
+    if (rc != GRLBWT_OK) {
+        std::cerr << "grlbwt: no usable HIP device (" << grlbwt_strerror(rc) << "); this build has no CPU path" << std::endl;
+        return 3;
+    }
+    std::cout << (keep ? "Keeping the listed strings" : "Removing the listed strings") << std::endl;
+    uint32_t flags = keep ? GRLBWT_SELECT_KEEP : 0u;
+    if (args.sample_bits >= 0) flags |= GRLBWT_SELECT_CHECKPOINTS | GRLBWT_SELECT_SAMPLE_BITS(args.sample_bits);
+    grlbwt_select_info si;
+    rc = grlbwt_select_files(ctx, args.select_image.c_str(), ids.data(), ids.size(), args.alph_bytes, flags, args.output_file.c_str(), &si);
+    if (rc != GRLBWT_OK) {
+        std::cerr << "grlbwt: " << grlbwt_last_error(ctx) << " (" << grlbwt_strerror(rc) << ")" << std::endl;
+        grlbwt_ctx_destroy(ctx);
+        return 2;
+    }
+    std::cout << "Stats: " << std::endl;
+    std::cout << "  Smallest symbol               : " << si.separator << std::endl;
+    std::cout << "  Number of strings (in -> out) : " << si.n_strings_in << " -> " << si.n_strings_out << std::endl;
+    std::cout << "  Number of symbols (in -> out) : " << si.n_syms_in << " -> " << si.n_syms_out << std::endl;
+    std::cout << "  Strings listed                : " << si.n_listed << std::endl;
+    std::cout << "  Rows removed                  : " << si.n_syms_in - si.n_syms_out << std::endl;
+    std::cout << "  Longest marking walk          : " << si.longest_walk << std::endl;
+    if (si.n_checkpoints) std::cout << "  Checkpoints                   : " << si.n_checkpoints << " (one in 2^" << si.sample_bits << " rows)" << std::endl;
+    std::cout << "  BWT size (n)                  : " << si.n_syms_out << std::endl;
+    std::cout << "  Number of runs (in -> out)    : " << si.n_runs_in << " -> " << si.n_runs_out << std::endl;
+    std::cout << "  Bytes per run symbol          : " << si.sb << std::endl;
+    std::cout << "  Bytes per run length          : " << si.fb << std::endl;
+    report_time(t_start, std::chrono::steady_clock::now(), 2);
+    std::cout << "The resulting BCR BWT was stored in " << args.output_file << std::endl;
+    std::cout << std::flush;
+    grlbwt_ctx_destroy(ctx);
+    return 0;
+}
+
 int main(int argc, char **argv) {
     arguments args;
     bool have_text = false;
@@ -391,6 +466,16 @@ int main(int argc, char **argv) {
         else if (a == "--fastx") args.fastx = true;
         else if (a == "--plain") args.fastx = false;                              // (the default: kept so that scripts can say it)
         else if (a == "--merge") { args.merge = true; args.merge_a = need("--merge"); args.merge_b = need("--merge"); }
+        else if (a == "--select") { args.select = true; args.select_image = need("--select"); }
+        else if (a == "--drop") args.drop_ids = need("--drop");
+        else if (a == "--keep") args.keep_ids = need("--keep");
+        else if (a == "--sample-bits") {
+            const std::string v = need("--sample-bits");
+            char *end = nullptr;
+            const long bits = std::strtol(v.c_str(), &end, 10);
+            if (v.empty() || *end != 0 || bits < 0 || bits > 20) fail(105, "--sample-bits: Value not in range 0 to 20");
+            args.sample_bits = (int)bits;
+        }
         else if (a == "--gpus") {
             args.gpus = std::atoi(need("--gpus").c_str());
             if (args.gpus < 1 || args.gpus > 64) fail(105, "--gpus: Value not in range 1 to 64");
@@ -399,6 +484,8 @@ int main(int argc, char **argv) {
         else if (!have_text) { args.input_file = a; have_text = true; }
         else fail(109, "The following argument was not expected: " + a);
     }
+    if (args.select) return run_select(args, have_text);
+    if (!args.drop_ids.empty() || !args.keep_ids.empty() || args.sample_bits >= 0) fail(105, "--drop / --keep / --sample-bits: only with --select");
     if (args.merge) return run_merge(args, have_text);
     if (!have_text) fail(106, "TEXT is required");                                  // main.cpp:53 ->required()
     if (!is_file(args.input_file)) fail(105, "TEXT: File does not exist: " + args.input_file);

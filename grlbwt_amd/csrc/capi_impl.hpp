@@ -33,6 +33,12 @@ struct grlbwt_merge {
     std::unique_ptr<grl64::Engine::ImageMerge> m64;
 };
 
+// a selection of strings (grlbwt_select_create): the rewritten runs, the alphabet and the marked rows
+struct grlbwt_select {
+    std::unique_ptr<grl32::Engine::ImageSelect> s32;
+    std::unique_ptr<grl64::Engine::ImageSelect> s64;
+};
+
 struct grlbwt_ctx {
     uint32_t flags = 0;
     int device = 0;
@@ -41,6 +47,7 @@ struct grlbwt_ctx {
     std::string err;
     std::vector<grlbwt_fm *> fms;      // the indexes still alive: released with the context
     std::vector<grlbwt_merge *> merges;      // and the merges
+    std::vector<grlbwt_select *> selects;    // and the selections
 };
 
 namespace {
@@ -1706,6 +1713,8 @@ void grlbwt_ctx_destroy(grlbwt_ctx *ctx) {
         ctx->fms.clear();
         for (grlbwt_merge *mg : ctx->merges) delete mg;
         ctx->merges.clear();
+        for (grlbwt_select *sel : ctx->selects) delete sel;
+        ctx->selects.clear();
         ctx->e32.reset(); ctx->e64.reset(); prim::sync(); prim::pool_trim();
         if (--prim::rt().live_ctx <= 0) {      // process-wide debug settings and a borrowed stream end with the last context
             prim::rt().live_ctx = 0;
@@ -2148,6 +2157,98 @@ int grlbwt_merge_files(grlbwt_ctx *ctx, const char *path_a, const char *path_b, 
     });
     const std::string err = ctx->err;
     grlbwt_merge_destroy(ctx, mg);
+    if (rc != GRLBWT_OK) ctx->err = err;
+    return rc;
+}
+
+int grlbwt_select_create(grlbwt_ctx *ctx, const void *dev_image, uint64_t image_bytes, int cell_bytes, const uint64_t *dev_ids, uint64_t n_ids,
+                         uint32_t select_flags, grlbwt_select **out) {
+    if (out) *out = nullptr;
+    if (!ctx || !dev_image || !out || (n_ids && !dev_ids)) return GRLBWT_EINVAL;
+    const uint32_t sample_bits = (select_flags >> 8) & 0xFFu;
+    const bool keep = select_flags & GRLBWT_SELECT_KEEP, cps = select_flags & GRLBWT_SELECT_CHECKPOINTS;
+    if ((select_flags & ~(GRLBWT_SELECT_KEEP | GRLBWT_SELECT_CHECKPOINTS | 0xFF00u)) || sample_bits > 20 || (!cps && sample_bits)) {
+        ctx->err = "select: bad flags (the keep flag, the checkpoint flag and sample_bits are all there is; sample_bits is 0 or 1 to 20 and needs the checkpoint flag)";
+        return GRLBWT_EINVAL;
+    }
+    return guarded(ctx, [&] {
+        const uint64_t total = grl64::Engine::image_total_symbols(dev_image, image_bytes);
+        if (total >= kMergeRowLimit) throw prim::Error(GRLBWT_ERANGE, "select: 2^40 rows or more");
+        const bool big = total >= kIdx32Limit || (ctx->flags & GRLBWT_FLAG_FORCE_IDX64);
+        std::unique_ptr<grlbwt_select> sel(new grlbwt_select());
+        if (big) {
+            sel->s64.reset(new grl64::Engine::ImageSelect());
+            sel->s64->flags = select_flags;
+            grl64::Engine::select_create(dev_image, image_bytes, cell_bytes, dev_ids, n_ids, keep, cps, (int)sample_bits, *sel->s64);
+        } else {
+            sel->s32.reset(new grl32::Engine::ImageSelect());
+            sel->s32->flags = select_flags;
+            grl32::Engine::select_create(dev_image, image_bytes, cell_bytes, dev_ids, n_ids, keep, cps, (int)sample_bits, *sel->s32);
+        }
+        ctx->selects.push_back(sel.get());
+        *out = sel.release();
+    });
+}
+int grlbwt_select_destroy(grlbwt_ctx *ctx, grlbwt_select *sel) {
+    if (!ctx) return GRLBWT_EINVAL;
+    if (!sel) return GRLBWT_OK;
+    auto it = std::find(ctx->selects.begin(), ctx->selects.end(), sel);
+    if (it == ctx->selects.end()) { ctx->err = "select destroy: not a selection of this context"; return GRLBWT_EINVAL; }
+    ctx->selects.erase(it);
+    return guarded(ctx, [&] { prim::sync(); delete sel; });
+}
+int grlbwt_select_info_get(const grlbwt_select *sel, grlbwt_select_info *out) {
+    if (!sel || !out || !(sel->s32 || sel->s64)) return GRLBWT_EINVAL;
+    auto fill = [&](const auto &S, uint64_t idx_bytes) {
+        out->n_syms_in = S.n_in; out->n_strings_in = S.k_in; out->n_runs_in = S.R_in; out->n_listed = S.n_listed;
+        out->rows_marked = S.rows_marked; out->longest_walk = S.longest_walk;
+        out->n_syms_out = S.n_out; out->n_strings_out = S.k_out; out->n_runs_out = S.R_out; out->out_bytes = S.out_bytes; out->sb = S.sb; out->fb = S.fb;
+        out->separator = S.sepval; out->idx_bytes = idx_bytes; out->flags = S.flags;
+        out->walk_lanes = S.lanes; out->lane_refills = S.refills;
+        out->sample_bits = S.sample_bits; out->n_checkpoints = S.n_checkpoints; out->jump_rounds = S.jump_rounds;
+        out->scratch_bytes = S.scratch_bytes; out->held_bytes = S.held_bytes();
+    };
+    if (sel->s32) fill(*sel->s32, 4); else fill(*sel->s64, 8);
+    return GRLBWT_OK;
+}
+int grlbwt_select_emit(grlbwt_ctx *ctx, const grlbwt_select *sel, void *dev_out, uint64_t capacity_bytes) {
+    if (!ctx || !sel || !dev_out || !(sel->s32 || sel->s64)) return GRLBWT_EINVAL;
+    return guarded(ctx, [&] {
+        if (sel->s32) grl32::Engine::select_emit(*sel->s32, (uint8_t *)dev_out, capacity_bytes);
+        else grl64::Engine::select_emit(*sel->s64, (uint8_t *)dev_out, capacity_bytes);
+    });
+}
+int grlbwt_select_rows(grlbwt_ctx *ctx, const grlbwt_select *sel, uint64_t *dev_bits) {
+    if (!ctx || !sel || !dev_bits || !(sel->s32 || sel->s64)) return GRLBWT_EINVAL;
+    return guarded(ctx, [&] {
+        if (sel->s32) grl32::Engine::select_rows(*sel->s32, dev_bits);
+        else grl64::Engine::select_rows(*sel->s64, dev_bits);
+    });
+}
+int grlbwt_select_files(grlbwt_ctx *ctx, const char *path_in, const uint64_t *host_ids, uint64_t n_ids, int cell_bytes, uint32_t select_flags,
+                        const char *path_out, grlbwt_select_info *info) {
+    if (!ctx || !path_in || !path_out || (n_ids && !host_ids)) return GRLBWT_EINVAL;
+    grlbwt_select *sel = nullptr;
+    int rc = guarded(ctx, [&] {
+        RawText a;
+        read_image_file(path_in, a);
+        grl64::DBuf<uint64_t> ids(n_ids);
+        prim::h2d(ids.p, host_ids, n_ids * 8);
+        const int r = grlbwt_select_create(ctx, a.buf.p, a.n, cell_bytes, ids.p, n_ids, select_flags, &sel);
+        if (r != GRLBWT_OK) throw prim::Error(r, ctx->err);
+    });
+    if (rc != GRLBWT_OK) return rc;
+    rc = guarded(ctx, [&] {
+        grlbwt_select_info si;
+        grlbwt_select_info_get(sel, &si);
+        grl64::DBuf<uint8_t> out(si.out_bytes);
+        const int r = grlbwt_select_emit(ctx, sel, out.p, si.out_bytes);
+        if (r != GRLBWT_OK) throw prim::Error(r, ctx->err);
+        write_image(out.p, si.out_bytes, path_out);
+        if (info) *info = si;
+    });
+    const std::string err = ctx->err;
+    grlbwt_select_destroy(ctx, sel);
     if (rc != GRLBWT_OK) ctx->err = err;
     return rc;
 }

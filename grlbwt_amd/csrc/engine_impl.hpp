@@ -3538,6 +3538,86 @@ struct FmLocateCpFn {
     }
 };
 
+// ---- removing or keeping chosen strings (grlbwt_select_*).  The suffixes of string i are the rows on the LF chain
+// from row i to the row whose symbol is the separator; the chains of distinct strings are disjoint.  The walks set one bit per
+// chain row of the LISTED strings; the rows a run loses (or keeps) are then a difference of two ranks over those bits.
+struct SelListFn {        // the list as a set: bit s of a k-bit vector for every entry s
+    const u64 *ids; u64 *bits;
+    GRL_DEV void operator()(u64 i) const { const u64 s = ids[i]; prim::atomic_or(&bits[s >> 6], 1ull << (s & 63)); }
+};
+struct SelTicketFn {      // prim::for_each_set_bit over that vector: the distinct entries in ascending order
+    idx_t *tick;
+    GRL_DEV void operator()(u64 p, u64 ord) const { tick[ord] = (idx_t)p; }
+};
+GRL_DEV bool sel_listed(const u64 *bits, u64 s) { return (bits[s >> 6] >> (s & 63)) & 1ull; }
+// (several lanes share a word, hence the atomic; a row lies on one chain, so no bit is set twice, and nothing reads the result)
+GRL_DEV void sel_mark(u64 *mark, u64 row) { prim::atomic_or(&mark[row >> 6], 1ull << (row & 63)); }
+// Marking per string, one ticket per listed string: row = its number, then LF steps up to and including the row whose symbol is
+// the separator.  As in FmSidFn a walk from one of the first k rows meets that row after at most n steps whatever the image is;
+// the bound is there all the same.  steps[t] = the rows marked = the string's length, separator included.
+struct SelMarkFn {
+    struct State { idx_t row; u64 steps; bool found; };
+    const RankCell *rc; const RunRec *rec; u32 sep; u64 n; const idx_t *tick; u64 *mark; idx_t *steps; u32 *bad;
+    GRL_DEV bool begin(u64 t, State &st) const { st.row = tick[t]; st.steps = 0; st.found = false; return true; }
+    GRL_DEV bool step(State &st) const {
+        sel_mark(mark, (u64)st.row);
+        const RunRec r = rec[run_of_row(rc, (u64)st.row)];
+        st.steps++;
+        if (r.sym == sep) { st.found = true; return true; }
+        st.row = (idx_t)(st.row + (idx_t)r.delta);
+        return st.steps >= n;
+    }
+    GRL_DEV void end(u64 t, const State &st) const {
+        steps[t] = (idx_t)st.steps;
+        if (!st.found) prim::atomic_max(bad, 1u);
+    }
+};
+// Marking through checkpointed segments, one ticket per checkpoint (CpWriteFn's shape): the segments of listed strings mark
+// their seglen rows.  The row a segment ends at is either the next checkpoint's (that segment marks it) or the row whose symbol
+// is the separator, which CpSegFn does not count: the last step looks at that row and marks it where it holds the separator.  (A
+// checkpoint row that holds the separator is marked from both sides, by segments of the same string.)
+struct SelMarkCpFn {
+    struct State { idx_t row; u64 left; };
+    const RankCell *rc; const RunRec *rec; u32 sep; Checkpoints cp; const idx_t *head, *seglen; const u64 *list; u64 *mark;
+    GRL_DEV bool begin(u64 c, State &st) const {
+        const idx_t h = head[c];
+        if (h == kCpNone || !sel_listed(list, (u64)h)) return false;
+        st.row = (idx_t)cp.row_of(c);
+        st.left = (u64)seglen[c];
+        return true;
+    }
+    GRL_DEV bool step(State &st) const {
+        const RunRec r = rec[run_of_row(rc, (u64)st.row)];
+        if (st.left == 0) {
+            if (r.sym == sep) sel_mark(mark, (u64)st.row);
+            return true;
+        }
+        sel_mark(mark, (u64)st.row);
+        st.row = (idx_t)(st.row + (idx_t)r.delta);
+        st.left--;
+        return false;
+    }
+    GRL_DEV void end(u64, const State &) const {}
+};
+struct SelListedLenIn {   // the length of the t-th listed string (CpLenFn's slen)
+    const idx_t *tick, *slen;
+    GRL_DEV u64 operator()(u64 t) const { return (u64)slen[(u64)tick[t]]; }
+};
+struct SelSegStepsIn {    // the steps of checkpoint c's marking walk (0: not walked)
+    const idx_t *head, *seglen; const u64 *list;
+    GRL_DEV u64 operator()(u64 c) const {
+        const idx_t h = head[c];
+        return h != kCpNone && sel_listed(list, (u64)h) ? (u64)seglen[c] : 0ull;
+    }
+};
+struct SelRunLenFn {      // the rewrite: a run's length less the marked rows in it -- or those alone, to keep the listed strings
+    const idx_t *rpos; const u64 *mark; const idx_t *mbase; bool keep; idx_t *len;
+    GRL_DEV void operator()(u64 r) const {
+        const u64 a = (u64)rpos[r], b = (u64)rpos[r + 1], cnt = rank1(mark, mbase, b) - rank1(mark, mbase, a);
+        len[r] = (idx_t)(keep ? cnt : (b - a) - cnt);
+    }
+};
+
 // ---- extracting text ranges (grlbwt_fm_extract).  T[s] = the cells in front of string s, so (s, o) is the absolute
 // position T[s] + o.  The index keeps the INVERSE of its samples: xq = the absolute positions of the sampled rows, ascending, and
 // xc = the checkpoint of each (its row is cp.row_of).  The head of string s is a sample at T[s + 1] - 1, its separator's position,
@@ -6194,10 +6274,10 @@ class Engine {
     // The run symbols of an image are read as 64 bits.  Where the largest is 2^30 or more they are compacted like a wide text
     // (R values, not n): the LF walk runs on ranks and the write functors put alpha[rank] into the text.
     struct WideSyms { DBuf<u32> ranks; DBuf<u64> alpha; };
-    static void image_symbols(const u8 *img, u64 R, u32 sb, u32 fb, int cell_bytes, WideSyms &W) {
+    static void image_symbols(const u8 *img, u64 R, u32 sb, u32 fb, int cell_bytes, WideSyms &W, const char *who = "inversion") {
         const ImageSymIn in{img, sb, fb};
         const u64 mx = prim::reduce_max<u64>(R, in, "inv.max_sym");
-        if (cell_bytes < 8 && (mx >> (8 * cell_bytes))) throw prim::Error(-22, "inversion: the image's largest symbol does not fit the cell width");
+        if (cell_bytes < 8 && (mx >> (8 * cell_bytes))) throw prim::Error(-22, std::string(who) + ": the image's largest symbol does not fit the cell width");
         if (mx < (1ull << 30)) return;
         DBuf<u64> s64(R);
         prim::for_each(R, UnpackSymFn{in, s64.p}, "inv.unpack_syms");
@@ -6294,7 +6374,7 @@ class Engine {
         X.mx = prim::reduce_max<u32>(R, PtrU32In{X.rsym.p}, "inv.max");
         X.k = prim::reduce_sum<u64>(R, SepLenIn{X.rsym.p, X.rlen.p, X.sep}, "inv.nstrings");      // strings = separators
     }
-    static void run_index_lf(RunIndex &X, bool walk, bool search) {
+    static void run_index_lf(RunIndex &X, bool walk, bool search, bool keep_runs = false) {
         const u64 R = X.R, n = X.n;
         if (walk) {      // run-start bit-vector with the rank of every word beside it
             RankBits rb;
@@ -6319,7 +6399,7 @@ class Engine {
             if (tot != n) throw prim::Error(-71, "inversion: run lengths do not add up");
         }
         if (search) { const idx_t total = (idx_t)n; prim::h2d(X.slf.p + R, &total, sizeof(total)); }
-        X.rsym.release(); X.rlen.release(); X.rpos.release();
+        if (!keep_runs) { X.rsym.release(); X.rlen.release(); X.rpos.release(); }
     }
     template <class cell_t>
     static u64 invert_runs_t(const u8 *img, u64 R, u32 sb, u32 fb, cell_t *text_out, u64 capacity, const WideSyms &W, u64 tail = 0, u64 *n_strings_out = nullptr) {
@@ -6805,6 +6885,19 @@ class Engine {
         auto it = prim::rt().prof.find(name);
         return it == prim::rt().prof.end() ? 0.0 : (double)it->second.ms;
     }
+    // The header rule of an image and its records, shared by what writes an image from runs (merge, select).  sb comes from the
+    // largest symbol + 4, fb from `longest`: the largest total of one symbol (cells of one byte) or the number of symbols.
+    static void image_widths(u64 max_sym, u64 longest, u64 &sb, u64 &fb) {
+        sb = (bitlen64(max_sym + 4) + 7) / 8;
+        fb = (bitlen64(longest) + 7) / 8;
+    }
+    static void emit_records(const u32 *sym, RunLen len, u64 R, u32 sb, u32 fb, const u64 *alpha, u8 *out, const char *name) {
+        u8 hdr[16] = {0};
+        hdr[0] = (u8)sb; hdr[8] = (u8)fb;
+        prim::h2d(out, hdr, 16);
+        if (sb + fb <= 8 && fb < 8) prim::pack_records(R, RunRecordFn{sym, len, sb, alpha}, sb + fb, out + 16, name);
+        else prim::for_each(R, PackRunsFn{sym, len, sb, fb, out, 16u, alpha}, name);
+    }
     static void merge_create(const void *img_a, u64 bytes_a, const void *img_b, u64 bytes_b, int cell_bytes, u64 max_rounds, ImageMerge &M) {
         if (!(cell_bytes == 1 || cell_bytes == 2 || cell_bytes == 4 || cell_bytes == 8)) throw prim::Error(-22, "merge: bad cell width");
         // ---- load: the records of both images, the union of their symbol values, one rank byte per row
@@ -6838,8 +6931,7 @@ class Engine {
         M.ka = ha[0]; M.kb = hb[0];
         u64 F = n;
         if (cell_bytes == 1) { F = 0; for (int i = 0; i < 256; i++) if (ha[i] + hb[i] > F) F = ha[i] + hb[i]; }
-        M.sb = (bitlen64(mx + 4) + 7) / 8;
-        M.fb = (bitlen64(F) + 7) / 8;
+        image_widths(mx, F, M.sb, M.fb);
         // ---- the rounds.  Scratch: the second interleave buffer, the tile tables, and what the run heads take afterwards
         const u64 round_scratch = MergeRound::scratch_bytes(n);
         M.scratch_bytes = (n + 16) + std::max(round_scratch, merge_heads_bytes(n));
@@ -6898,17 +6990,146 @@ class Engine {
         prim::for_each_set_bit<idx_t>(n, H.hw.p, H.hb.p, MgHeadFn{merge_sym(M, H.zb), sym.p, start.p}, "merge.runs");
         const idx_t total = (idx_t)n;
         prim::h2d(start.p + R, &total, sizeof(total));
-        const u32 sb = (u32)M.sb, fb = (u32)M.fb;
-        u8 hdr[16] = {0};
-        hdr[0] = (u8)sb; hdr[8] = (u8)fb;
-        prim::h2d(out, hdr, 16);
-        const RunLen len{nullptr, start.p};
-        if (sb + fb <= 8 && fb < 8) prim::pack_records(R, RunRecordFn{sym.p, len, sb, M.alpha.p}, sb + fb, out + 16, "merge.pack");
-        else prim::for_each(R, PackRunsFn{sym.p, len, sb, fb, out, 16u, M.alpha.p}, "merge.pack");
+        emit_records(sym.p, RunLen{nullptr, start.p}, R, (u32)M.sb, (u32)M.fb, M.alpha.p, out, "merge.pack");
         prim::sync();
     }
     static void merge_interleave(const ImageMerge &M, u64 *dev_bits) {
         prim::bitvector_from_pred(M.na + M.nb, MgFlagPred{M.z.p}, dev_bits, "merge.interleave");
+        prim::sync();
+    }
+
+    // ---- removing or keeping chosen strings of an image (grlbwt_select_*; functor block "removing or keeping chosen strings";
+    // DESIGN.md 4e).  The list becomes a k-bit set; the chains of the listed strings are marked in an n-bit vector, per string or
+    // through checkpointed segments; a rank over the marked bits gives every run its new length; empty runs go, equal neighbours
+    // are joined.  The handle keeps the new runs, the values of a compacted alphabet and the marked bits.
+    //   Loops: a string's walk is bounded by n steps, a segment's by seglen[c] + 1, the pointer jumping by ceil(log2 m) rounds;
+    //   nothing waits for another thread; the atomics are the ticket word's and the ORs into the two bit-vectors.
+    struct ImageSelect {
+        u64 n_in = 0, k_in = 0, R_in = 0, n_listed = 0, rows_marked = 0, longest_walk = 0;
+        u64 n_out = 0, k_out = 0, R_out = 0, out_bytes = 0, sb = 0, fb = 0, sepval = 0, flags = 0;
+        u64 lanes = 0, refills = 0, sample_bits = 0, n_checkpoints = 0, jump_rounds = 0, scratch_bytes = 0;
+        DBuf<u32> sym;            // the runs of the output: symbols (ranks where alpha is set) and lengths
+        DBuf<idx_t> len;
+        DBuf<u64> alpha;          // rank -> symbol value (null: the symbols are the values)
+        DBuf<u64> marked;         // bit p: row p of the input lies on a listed string's chain
+        u64 held_bytes() const { return sym.n * 4 + len.n * sizeof(idx_t) + alpha.n * 8 + marked.n * 8; }
+    };
+    static void select_create(const void *dev_image, u64 image_bytes, int cell_bytes, const u64 *ids, u64 n_ids, bool keep, bool checkpoints, int sample_bits,
+                              ImageSelect &S) {
+        if (!(cell_bytes == 1 || cell_bytes == 2 || cell_bytes == 4 || cell_bytes == 8)) throw prim::Error(-22, "select: bad cell width");
+        if (!checkpoints && sample_bits) throw prim::Error(-22, "select: sample_bits needs the checkpoint flag");
+        const int b = checkpoints ? sample_bits_of(sample_bits) : 0;
+        const ImageHeader h = image_header(dev_image, image_bytes);
+        if (h.R == 0) throw prim::Error(-22, "select: the image has no record");
+        const u8 *img = (const u8 *)dev_image;
+        WideSyms W;
+        image_symbols(img, h.R, (u32)h.sb, (u32)h.fb, cell_bytes, W, "select");
+        RunIndex X;
+        run_index_load(img, h.R, (u32)h.sb, (u32)h.fb, W, X);
+        W.ranks.release();
+        const u64 R = X.R, n = X.n, k = X.k;
+        if (R == 0) throw prim::Error(-22, "select: the image describes no symbol");
+        const u32 sep = X.sep;
+        S.n_in = n; S.k_in = k; S.R_in = R;
+        S.sepval = W.alpha.p ? W.alpha.get(sep) : (u64)sep;
+        // ---- the list as a set, its distinct entries in ascending order as the tickets
+        if (n_ids) {
+            const u64 bad = prim::reduce_min<u64>(n_ids, FmExtractBadIn{ids, k}, "select.list_check");
+            if (bad != ~0ull) {
+                u64 v = 0;
+                prim::d2h(&v, ids + bad, 8);
+                throw prim::Error(-22, "select: entry " + std::to_string(bad) + " of the list (" + std::to_string(v) + ") is not below the number of strings (" +
+                                           std::to_string(k) + ")");
+            }
+        }
+        const u64 lw = k / 64 + 2;
+        DBuf<u64> list(lw);
+        DBuf<idx_t> lbase(lw + 1);
+        list.zero();
+        prim::for_each(n_ids, SelListFn{ids, list.p}, "select.list");
+        const u64 nl = (u64)prim::exclusive_scan<idx_t>(lw, PopcIn{list.p}, lbase.p, true, "select.list_ranks");
+        S.n_listed = nl;
+        S.k_out = keep ? nl : k - nl;
+        if (S.k_out == 0)
+            throw prim::Error(-22, keep ? "select: the keep flag with an empty list leaves no string" : "select: every string is listed, the result would hold no string");
+        // ---- memory, before the first walk: the run index and its sort, the two bit-vectors with their ranks, the tickets, the
+        // checkpoint ranking's arrays, the rewrite's scan
+        const u64 words = (n + 1) / 64 + 2, mw = n / 64 + 2;
+        const u64 m = checkpoints ? Checkpoints{n, k, (u32)b}.count() : 0;
+        u64 need = words * (sizeof(RankCell) + 8 + sizeof(idx_t)) + R * (sizeof(RunRec) + 3 * (4 + sizeof(idx_t))) + lw * (8 + sizeof(idx_t)) +
+                   mw * (8 + sizeof(idx_t)) + 2 * nl * sizeof(idx_t);
+        if (checkpoints) need += (6 * m + 2 * k + 1) * sizeof(idx_t) + k * 8;
+        S.scratch_bytes = need;
+        if (need > prim::mem_available())
+            throw prim::Error(-12, "select: the structures need " + std::to_string(need) + " bytes of device memory, more than is free");
+        DBuf<idx_t> tick(nl);
+        prim::for_each_set_bit<idx_t>(k, list.p, lbase.p, SelTicketFn{tick.p}, "select.tickets");
+        lbase.release();
+        run_index_lf(X, true, false, true);
+        // ---- marking
+        S.marked.alloc(mw);
+        S.marked.zero();
+        u64 listed_len = 0;
+        WalkInfo wi;
+        if (!checkpoints) {
+            DBuf<idx_t> steps(nl);
+            DBuf<u32> bad(1);
+            bad.zero();
+            walk(nl, SelMarkFn{X.rc.p, X.rec.p, sep, n, tick.p, S.marked.p, steps.p, bad.p}, wi, "select.mark");
+            if (nl && bad.get(0)) throw prim::Error(-22, "select: a string's walk met no separator in n steps: not the BWT of a collection");
+            listed_len = prim::reduce_sum<u64>(nl, IdxIn64{steps.p}, "select.steps");
+            S.longest_walk = prim::reduce_max<u64>(nl, IdxIn64{steps.p}, "select.longest");
+        } else {
+            CpRank C;
+            lf_checkpoints(X.rc.p, X.rec.p, n, k, sep, b, -22, C, wi);
+            walk(m, SelMarkCpFn{X.rc.p, X.rec.p, sep, C.cp, C.head.p, C.seglen.p, list.p, S.marked.p}, wi, "select.mark_cp");
+            listed_len = prim::reduce_sum<u64>(nl, SelListedLenIn{tick.p, C.slen.p}, "select.steps");
+            S.longest_walk = prim::reduce_max<u64>(m, SelSegStepsIn{C.head.p, C.seglen.p, list.p}, "select.longest");
+            S.sample_bits = (u64)b; S.n_checkpoints = m; S.jump_rounds = wi.jump_rounds;
+        }
+        S.lanes = wi.lanes; S.refills = wi.refills;
+        X.rc.release(); X.rec.release(); tick.release(); list.release();
+        // ---- the rewrite: ranks over the marked words, the new length of every run, maximal runs
+        {
+            DBuf<idx_t> mbase(mw + 1);
+            S.rows_marked = (u64)prim::exclusive_scan<idx_t>(mw, PopcIn{S.marked.p}, mbase.p, true, "select.ranks");
+            if (S.rows_marked != listed_len) throw prim::Error(-71, "select: the rows marked do not add up to the lengths of the listed strings");
+            prim::for_each(R, SelRunLenFn{X.rpos.p, S.marked.p, mbase.p, keep, X.rlen.p}, "select.run_lengths");
+        }
+        X.rpos.release();
+        const u64 R2 = drop_empty_runs(X.rsym, X.rlen, R);
+        Runs out = merge_runs(X.rsym.p, X.rlen.p, R2);
+        X.rsym.release(); X.rlen.release(); out.pos.release();
+        S.R_out = out.R; S.n_out = out.n;
+        if (S.n_out != (keep ? S.rows_marked : n - S.rows_marked)) throw prim::Error(-71, "select: the rewritten runs do not add up");
+        if (prim::reduce_sum<u64>(out.R, SepLenIn{out.sym.p, out.len.p, sep}, "select.separators") != S.k_out)
+            throw prim::Error(-71, "select: the rewritten runs do not hold one separator per remaining string");
+        // ---- the header: the largest remaining symbol; the largest total of one symbol (cells of one byte) or the length
+        const u32 mxr = prim::reduce_max<u32>(out.R, PtrU32In{out.sym.p}, "select.max_sym");
+        const u64 mx = W.alpha.p ? W.alpha.get(mxr) : (u64)mxr;
+        u64 F = S.n_out;
+        if (cell_bytes == 1) {
+            DBuf<u64> bins(256);
+            bins.zero();
+            prim::for_each_agg(out.R, RunSymFn{out.sym.p}, BinAddFn{bins.p}, true, "select.runs_per_symbol");
+            const std::vector<u64> hb = bins.to_host(256);
+            F = 0;
+            for (u32 c = 0; c < 256; c++)
+                if (hb[c]) F = std::max(F, prim::reduce_sum<u64>(out.R, SepLenIn{out.sym.p, out.len.p, c}, "select.symbol_total"));
+        }
+        image_widths(mx, F, S.sb, S.fb);
+        S.out_bytes = 16 + S.R_out * (S.sb + S.fb);
+        S.sym = std::move(out.sym); S.len = std::move(out.len);
+        S.alpha = std::move(W.alpha);
+        prim::sync();
+    }
+    static void select_emit(const ImageSelect &S, u8 *out, u64 capacity) {
+        if (capacity < S.out_bytes) throw prim::Error(-22, "select: output buffer too small (" + std::to_string(S.out_bytes) + " bytes needed)");
+        emit_records(S.sym.p, RunLen{S.len.p, nullptr}, S.R_out, (u32)S.sb, (u32)S.fb, S.alpha.p, out, "select.pack");
+        prim::sync();
+    }
+    static void select_rows(const ImageSelect &S, u64 *dev_bits) {
+        prim::d2d(dev_bits, S.marked.p, (S.n_in + 63) / 64 * 8);
         prim::sync();
     }
 

@@ -38,12 +38,16 @@ ABI_SYMBOLS = [
     "grlbwt_fm_string_lengths", "grlbwt_fm_extract", "grlbwt_fm_extract_info_get",
     "grlbwt_merge_create", "grlbwt_merge_info_get", "grlbwt_merge_emit", "grlbwt_merge_interleave", "grlbwt_merge_destroy",
     "grlbwt_merge_files",
+    "grlbwt_select_create", "grlbwt_select_info_get", "grlbwt_select_emit", "grlbwt_select_rows", "grlbwt_select_destroy",
+    "grlbwt_select_files",
 ]
 
 FM_LOCATE = 1
 FM_CHECKPOINTS = 2
 FM_EXTRACT = 4
 UINT64_MAX = 2 ** 64 - 1
+SELECT_KEEP = 1
+SELECT_CHECKPOINTS = 2
 
 
 class FmInfo(C.Structure):
@@ -55,6 +59,13 @@ class MergeInfo(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in ("n_syms_a", "n_syms_b", "n_strings_a", "n_strings_b", "sigma", "separator", "rounds",
                                           "rows_changed", "n_runs", "out_bytes", "sb", "fb", "idx_bytes", "tile_rows",
                                           "scratch_bytes", "held_bytes")]
+
+
+class SelectInfo(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("n_syms_in", "n_strings_in", "n_runs_in", "n_listed", "rows_marked", "longest_walk",
+                                          "n_syms_out", "n_strings_out", "n_runs_out", "out_bytes", "sb", "fb", "separator",
+                                          "idx_bytes", "flags", "walk_lanes", "lane_refills", "sample_bits", "n_checkpoints",
+                                          "jump_rounds", "scratch_bytes", "held_bytes")]
 
 
 class WalkInfo(C.Structure):
@@ -225,6 +236,12 @@ def load_library(path=None, allow_test_standin=False):
     L.grlbwt_merge_interleave.argtypes = [vp, vp, vp]
     L.grlbwt_merge_destroy.argtypes = [vp, vp]
     L.grlbwt_merge_files.argtypes = [vp, C.c_char_p, C.c_char_p, i32, u64, C.c_char_p, C.POINTER(MergeInfo)]
+    L.grlbwt_select_create.argtypes = [vp, vp, u64, i32, vp, u64, C.c_uint32, C.POINTER(vp)]
+    L.grlbwt_select_info_get.argtypes = [vp, C.POINTER(SelectInfo)]
+    L.grlbwt_select_emit.argtypes = [vp, vp, vp, u64]
+    L.grlbwt_select_rows.argtypes = [vp, vp, vp]
+    L.grlbwt_select_destroy.argtypes = [vp, vp]
+    L.grlbwt_select_files.argtypes = [vp, C.c_char_p, vp, u64, i32, C.c_uint32, C.c_char_p, C.POINTER(SelectInfo)]
     L.grlbwt_profile_enable.argtypes = [vp, i32]
     L.grlbwt_profile_dump.argtypes = [vp, C.c_char_p, u64]
     _libs[path] = L
@@ -495,6 +512,16 @@ class Context:
                                            os.fsencode(path_out), C.byref(mi)))
         return _as_dict(mi)
 
+    def select_files(self, path_in, ids, path_out, cell_bytes=1, keep=False, checkpoints=False, sample_bits=0):
+        """The image in a file without the strings whose numbers `ids` lists -- or with those alone (keep=True) -- written to
+        path_out; returns the selection's counters (ImageSelect.info)."""
+        import numpy as np
+        ids = np.ascontiguousarray(np.asarray(ids, dtype=np.uint64).reshape(-1))
+        si = SelectInfo()
+        self._ck(self.L.grlbwt_select_files(self._h, os.fsencode(path_in), ids.ctypes.data_as(C.c_void_p), len(ids), cell_bytes,
+                                            select_flags(keep, checkpoints, sample_bits), os.fsencode(path_out), C.byref(si)))
+        return _as_dict(si)
+
     def memory_usage(self):
         a, b = C.c_uint64(), C.c_uint64()
         self._ck(self.L.grlbwt_memory_usage(self._h, C.byref(a), C.byref(b)))
@@ -627,6 +654,59 @@ class ImageMerge:
         h, self._h = getattr(self, "_h", None), None
         if h and getattr(self.ctx, "_h", None):       # (a closed context has released its merges)
             self.ctx._ck(self.ctx.L.grlbwt_merge_destroy(self.ctx._h, h))
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def select_flags(keep=False, checkpoints=False, sample_bits=0):
+    if not 0 <= sample_bits <= 255:
+        raise GrlbwtError(-22, "sample_bits is 0 or 1 to 20")
+    return (SELECT_KEEP if keep else 0) | (SELECT_CHECKPOINTS if checkpoints else 0) | (sample_bits << 8)
+
+
+class ImageSelect:
+    """The image of a collection without the strings `ids` lists -- or, with keep=True, of those strings alone -- from its image,
+    without the text (grlbwt_select_*).  All pointers are device pointers; the ids are uint64 string numbers in input order, in any
+    order, repeats allowed; the image and the list may be freed once the object exists (the walks have run by then).
+    checkpoints=True marks through checkpointed segments, one checkpoint in 2^sample_bits rows (0: the default): the form for
+    collections of long strings."""
+
+    def __init__(self, ctx, dev_image_ptr, image_bytes, cell_bytes, dev_ids_ptr, n_ids, keep=False, checkpoints=False, sample_bits=0):
+        self.ctx = ctx
+        h = C.c_void_p()
+        ctx._ck(ctx.L.grlbwt_select_create(ctx._h, C.c_void_p(dev_image_ptr), image_bytes, cell_bytes, C.c_void_p(dev_ids_ptr), n_ids,
+                                           select_flags(keep, checkpoints, sample_bits), C.byref(h)))
+        self._h = h
+
+    def info(self):
+        out = SelectInfo()
+        rc = self.ctx.L.grlbwt_select_info_get(self._h, C.byref(out))
+        if rc != OK:
+            raise GrlbwtError(rc, self.ctx.L.grlbwt_strerror(rc).decode())
+        return _as_dict(out)
+
+    def emit(self, out_ptr, capacity_bytes):
+        """The image of the remaining strings into out_ptr (info()["out_bytes"] bytes)."""
+        self.ctx._ck(self.ctx.L.grlbwt_select_emit(self.ctx._h, self._h, C.c_void_p(out_ptr), capacity_bytes))
+
+    def rows(self, bits_ptr):
+        """ceil(n_syms_in / 64) words: bit p of word p // 64 is set when row p of the input BWT lies on a listed string's chain."""
+        self.ctx._ck(self.ctx.L.grlbwt_select_rows(self.ctx._h, self._h, C.c_void_p(bits_ptr)))
+
+    def close(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h and getattr(self.ctx, "_h", None):       # (a closed context has released its selections)
+            self.ctx._ck(self.ctx.L.grlbwt_select_destroy(self.ctx._h, h))
 
     def __enter__(self):
         return self

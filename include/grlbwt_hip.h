@@ -427,6 +427,60 @@ int grlbwt_merge_destroy(grlbwt_ctx *ctx, grlbwt_merge *mg);
 int grlbwt_merge_files(grlbwt_ctx *ctx, const char *path_a, const char *path_b, int cell_bytes, uint64_t max_rounds,
                        const char *path_out, grlbwt_merge_info *info /* may be NULL */);
 
+/* ---- removing or keeping chosen strings: the image of a collection without the listed strings -- or of the listed strings
+ * alone (GRLBWT_SELECT_KEEP) -- from its image, without the text.  With the merge this makes an image a collection that can be
+ * maintained: add with merge, retire with select.  The suffixes of string i are the rows on the LF chain from row i (rows
+ * [0, n_strings) are the terminators, in string order) to the row whose symbol is the separator; two remaining suffixes compare
+ * as before, so deleting the chain rows of the listed strings leaves the BWT of the others, and the deleted rows, in order, are
+ * the BWT of the listed strings.
+ * INPUT: any well-formed image ("Accepted input" above), taken to be a BCR BWT as the inverters take it.  dev_ids: string numbers
+ * in input order, as grlbwt_fm_locate reports them, in any order, repeats allowed -- the list is a set; n_ids = 0 is legal.  An
+ * entry >= n_strings_in fails the whole call with GRLBWT_EINVAL; the message names the first such entry.
+ * OUTPUT: the image of the remaining strings in their old relative order (the m-th remaining string in ascending old number
+ * becomes string m).  When the input was built by this engine with cells of cell_bytes, the output is byte for byte what
+ * grlbwt_build writes for the text of the remaining strings, header included: sb from the largest REMAINING symbol + 4, fb from
+ * the largest total of one symbol (cell_bytes 1) or from the remaining length (2, 4, 8) -- the merge's rule.  The output always
+ * has maximal runs and no empty record; removing nothing gives the canonical re-encoding of the input.
+ * COST: one LF walk over the listed strings (always the LISTED ones: keeping 10 strings of a million costs 10 walks) and one pass
+ * over the runs -- the per-string cost model of grlbwt_fm_locate.  GRLBWT_SELECT_CHECKPOINTS marks through the checkpointed
+ * segments of grlbwt_invert_image_checkpointed instead (one checkpoint in 2^sample_bits rows, 0: the default): a segment walk
+ * over the whole collection whatever the list holds, and the only form that ends for collections of long strings.  The marking
+ * walk obeys GRLBWT_WALK_LANES.
+ * GRLBWT_EINVAL: a result without any string (everything removed, or keeping an empty list), an image without a record or with
+ * a bad header, cell_bytes not in {1, 2, 4, 8}, a symbol that does not fit cell_bytes, sample_bits without the checkpoint flag or
+ * above 20, unknown flag bits, a marking walk that meets no separator (or checkpoint) in n steps (not the BWT of a collection),
+ * capacity_bytes < out_bytes (nothing is written).  GRLBWT_ERANGE: 2^40 rows or more.  GRLBWT_ENOMEM: the structures do not fit
+ * the free device memory (checked before the first walk; scratch_bytes).  64-bit positions from 2^32 - 256 rows on or with
+ * GRLBWT_FLAG_FORCE_IDX64.  On every refusal *out = NULL and nothing is held.
+ * grlbwt_select_create copies what it needs -- the image and the list may be freed when it returns -- and runs the walks and the
+ * rewrite; the handle keeps the new runs, the values of a compacted alphabet and the marked rows (held_bytes).
+ * grlbwt_select_emit writes the image (out_bytes of the info); grlbwt_select_rows the marked rows as ceil(n_syms_in / 64) words,
+ * bit p of word p / 64 set when row p of the input BWT lies on a LISTED string's chain (the keep flag does not change the
+ * bits); grlbwt_ctx_destroy releases the handles still alive.  grlbwt_select_files: the image from a file, the list from host
+ * memory, the result to a file. */
+typedef struct grlbwt_select grlbwt_select;
+#define GRLBWT_SELECT_KEEP 1u              /* only the listed strings stay; without it the listed strings are removed */
+#define GRLBWT_SELECT_CHECKPOINTS 2u       /* mark through checkpointed segments: collections of long strings */
+#define GRLBWT_SELECT_SAMPLE_BITS(b) ((uint32_t)(b) << 8)   /* with CHECKPOINTS; 0 = the default, 1..20 */
+typedef struct grlbwt_select_info {
+    uint64_t n_syms_in, n_strings_in, n_runs_in;     /* rows, separators, non-empty records of the input */
+    uint64_t n_listed;                               /* DISTINCT ids listed */
+    uint64_t rows_marked, longest_walk;              /* rows on the listed strings' chains; LF steps of the longest marking walk (string or segment) */
+    uint64_t n_syms_out, n_strings_out, n_runs_out, out_bytes, sb, fb;
+    uint64_t separator, idx_bytes, flags;
+    uint64_t walk_lanes, lane_refills;               /* of the marking walk, as in grlbwt_walk_info */
+    uint64_t sample_bits, n_checkpoints, jump_rounds;/* 0 without CHECKPOINTS */
+    uint64_t scratch_bytes, held_bytes;
+} grlbwt_select_info;
+int grlbwt_select_create(grlbwt_ctx *ctx, const void *dev_image, uint64_t image_bytes, int cell_bytes, const uint64_t *dev_ids,
+                         uint64_t n_ids, uint32_t select_flags, grlbwt_select **out);
+int grlbwt_select_info_get(const grlbwt_select *sel, grlbwt_select_info *out);
+int grlbwt_select_emit(grlbwt_ctx *ctx, const grlbwt_select *sel, void *dev_out, uint64_t capacity_bytes);
+int grlbwt_select_rows(grlbwt_ctx *ctx, const grlbwt_select *sel, uint64_t *dev_bits /* ceil(n_syms_in / 64) words */);
+int grlbwt_select_destroy(grlbwt_ctx *ctx, grlbwt_select *sel);
+int grlbwt_select_files(grlbwt_ctx *ctx, const char *path_in, const uint64_t *host_ids, uint64_t n_ids, int cell_bytes,
+                        uint32_t select_flags, const char *path_out, grlbwt_select_info *info /* may be NULL */);
+
 /* ---- inspection (parity tests; need GRLBWT_FLAG_KEEP_LEVELS) --------------- */
 /* text of level >= 1 as (rank<<1 | rep) cells, the reference's on-disk parse format */
 int grlbwt_level_text_size(const grlbwt_ctx *ctx, int level, uint64_t *n_cells);
