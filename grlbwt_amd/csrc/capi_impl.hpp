@@ -2043,6 +2043,41 @@ int grlbwt_fm_count(grlbwt_ctx *ctx, const grlbwt_fm *fm, const void *dev_cells,
         else grl64::Engine::fm_count(*fm->f64, dev_cells, cell_bytes, dev_offsets, n_patterns, dev_lo, dev_hi);
     });
 }
+int grlbwt_fm_match(grlbwt_ctx *ctx, const grlbwt_fm *fm, const void *dev_cells, int cell_bytes, const uint64_t *dev_offsets,
+                    uint64_t n_patterns, uint64_t max_len, uint64_t *dev_len, uint64_t *dev_lo, uint64_t *dev_hi) {
+    if (!ctx || !fm || !(fm->f32 || fm->f64)) return GRLBWT_EINVAL;
+    if (n_patterns && !dev_offsets) return GRLBWT_EINVAL;
+    return guarded(ctx, [&] {
+        if (fm->f32) grl32::Engine::fm_match(*fm->f32, dev_cells, cell_bytes, dev_offsets, n_patterns, max_len, dev_len, dev_lo, dev_hi);
+        else grl64::Engine::fm_match(*fm->f64, dev_cells, cell_bytes, dev_offsets, n_patterns, max_len, dev_len, dev_lo, dev_hi);
+    });
+}
+int grlbwt_fm_mems(grlbwt_ctx *ctx, const grlbwt_fm *fm, const void *dev_cells, int cell_bytes, const uint64_t *dev_offsets,
+                   uint64_t n_patterns, uint64_t min_len, uint64_t max_len, uint64_t *dev_pattern, uint64_t *dev_begin, uint64_t *dev_mlen,
+                   uint64_t *dev_lo, uint64_t *dev_hi, uint64_t capacity, uint64_t *n_mems_out) {
+    if (n_mems_out) *n_mems_out = 0;
+    if (!ctx || !fm || !(fm->f32 || fm->f64)) return GRLBWT_EINVAL;
+    if (n_patterns && !dev_offsets) return GRLBWT_EINVAL;
+    uint64_t n = 0;
+    const int rc = guarded(ctx, [&] {
+        if (fm->f32) grl32::Engine::fm_mems(*fm->f32, dev_cells, cell_bytes, dev_offsets, n_patterns, min_len, max_len, dev_pattern, dev_begin, dev_mlen,
+                                            dev_lo, dev_hi, capacity, n);
+        else grl64::Engine::fm_mems(*fm->f64, dev_cells, cell_bytes, dev_offsets, n_patterns, min_len, max_len, dev_pattern, dev_begin, dev_mlen,
+                                    dev_lo, dev_hi, capacity, n);
+    });
+    if (n_mems_out) *n_mems_out = n;
+    return rc;
+}
+int grlbwt_fm_match_info_get(const grlbwt_fm *fm, grlbwt_fm_match_info *out) {
+    if (!fm || !out || !(fm->f32 || fm->f64)) return GRLBWT_EINVAL;
+    auto fill = [&](const auto &F) {
+        const auto &m = F.minfo;
+        out->n_patterns = m.patterns; out->n_cells = m.cells; out->matched_cells = m.matched; out->longest = m.longest;
+        out->n_capped = m.capped; out->n_mems = m.mems; out->walk_lanes = m.lanes; out->lane_refills = m.refills;
+    };
+    if (fm->f32) fill(*fm->f32); else fill(*fm->f64);
+    return GRLBWT_OK;
+}
 int grlbwt_fm_locate(grlbwt_ctx *ctx, const grlbwt_fm *fm, const uint64_t *dev_rows, uint64_t n_rows, uint64_t max_steps,
                      uint64_t *dev_string, uint64_t *dev_offset) {
     if (!ctx || !fm || !(fm->f32 || fm->f64)) return GRLBWT_EINVAL;

@@ -3302,6 +3302,78 @@ struct FmSepMisuseIn {    // cell x0 + k: the number of its pattern when it hold
         return x + 1 == f.off[i + 1] ? ~0ull : i;
     }
 };
+// ---- longest matches and maximal exact matches (grlbwt_fm_match / grlbwt_fm_mems).  Ticket t is the query cell
+// x = x0 + t, at offset e inside its pattern: the greedy backward search from [0, n) over cells x, x - 1, ... keeps the last
+// non-empty range, so len is the largest L <= min(e + 1, max_len) such that the L cells ending at x occur in the collection
+// (occurring is monotone in L).  A cell that is no symbol, or the separator, ends the item: no match holds or crosses one.
+//   Loops: an item takes at most min(e + 1, max_len) steps, each one fm_step; begin's upper_bound halves n_patterns + 1 offsets.
+struct FmMatchFn {
+    typedef FmKey Key;
+    struct State { u64 x, lo, hi, len, cap; };
+    FmCountFn f; u64 sepval, x0, np, max_len; u64 *len, *lo, *hi;       // (lo and hi both null: the lengths alone)
+    GRL_HD const FmKey *keys() const { return f.key; }
+    GRL_HD u64 n_keys() const { return f.R; }
+    GRL_DEV bool begin(u64 t, State &st) const {
+        st.x = x0 + t;
+        const u64 i = upper_bound<u64>(f.off, np + 1, st.x) - 1;      // off[i] <= x < off[i + 1]: empty patterns are stepped over
+        st.cap = st.x - f.off[i] + 1;
+        if (max_len && max_len < st.cap) st.cap = max_len;
+        st.lo = 0; st.hi = f.n; st.len = 0;
+        return true;
+    }
+    template <class TOP>
+    GRL_DEV bool step(State &st, const TOP &top) const {
+        const u64 v = f.cell(st.x - st.len);
+        u32 c;
+        if (st.lo >= st.hi || v == sepval || !f.code(v, c)) return true;       // (an index of no symbol: nothing matches)
+        u64 a = st.lo, b = st.hi;
+        fm_step(f.key, f.slf, f.R, top, c, a, b);
+        if (a >= b) return true;
+        st.lo = a; st.hi = b; st.len++;
+        return st.len >= st.cap;
+    }
+    GRL_DEV bool step(State &st) const { return step(st, FmNoTop{}); }
+    GRL_DEV void end(u64 t, const State &st) const {
+        len[t] = st.len;
+        if (lo) { lo[t] = st.len ? st.lo : 0; hi[t] = st.len ? st.hi : 0; }
+    }
+};
+struct FmMatchLaneFn {    // the same, one lane per cell through prim::top_search (GRLBWT_FM_MATCH=l)
+    typedef FmKey Key;
+    FmMatchFn f;
+    GRL_HD const FmKey *keys() const { return f.keys(); }
+    GRL_HD u64 n_keys() const { return f.n_keys(); }
+    template <class TOP>
+    GRL_DEV void operator()(u64 t, const TOP &top) const {
+        FmMatchFn::State st;
+        f.begin(t, st);
+        while (!f.step(st, top)) {}
+        f.end(t, st);
+    }
+};
+struct FmLenCappedIn {
+    const u64 *len; u64 cap;
+    GRL_DEV u64 operator()(u64 t) const { return len[t] == cap ? 1ull : 0ull; }
+};
+// end e of a pattern closes a maximal match when its length is at least the floor and the next end's match is no longer:
+// L[e + 1] <= L[e] + 1 always (drop the last cell of that match), with equality exactly when this one extends to the right
+struct FmMemFlagIn {
+    const u64 *len, *off; u64 x0, np, floor;
+    GRL_DEV bool operator()(u64 t) const {
+        const u64 L = len[t];
+        if (L < floor) return false;
+        const u64 x = x0 + t, i = upper_bound<u64>(off, np + 1, x) - 1;
+        return x + 1 == off[i + 1] || len[t + 1] <= L;
+    }
+};
+struct FmMemEmitFn {      // prim::for_each_set_bit over those flags: entry `ord` is the match that ends at cell x0 + t
+    const u64 *len, *slo, *shi, *off; u64 x0, np; u64 *pat, *beg, *mlen, *lo, *hi;
+    GRL_DEV void operator()(u64 t, u64 ord) const {
+        const u64 x = x0 + t, i = upper_bound<u64>(off, np + 1, x) - 1, L = len[t];
+        pat[ord] = i; beg[ord] = x - off[i] + 1 - L; mlen[ord] = L;
+        if (lo) { lo[ord] = slo[t]; hi[ord] = shi[t]; }
+    }
+};
 // sid: string i's walk (RunInvertLenFn's) ends at the row r that holds its separator; that separator is the LF(r)-th of the
 // BWT.  The LF map of any image is a permutation, so a walk from one of the first k rows comes back to one of them after at
 // most n steps; the bound is there for an index that is not what it should be.
@@ -6586,6 +6658,7 @@ class Engine {
 
     // ---- the FM index over the runs of an image (grlbwt_fm_*; functor block "counting and locating patterns") ----------------
     struct ExtractInfo { u64 ranges = 0, pieces = 0, cells = 0, steps = 0, lanes = 0, refills = 0; };      // of the last fm_extract
+    struct MatchInfo { u64 patterns = 0, cells = 0, matched = 0, longest = 0, capped = 0, mems = 0, lanes = 0, refills = 0; };
     struct FmIndex {
         u64 n = 0, R = 0, k = 0, sigma = 0, sepval = 0;
         u32 sep = 0, top_entries = 0;
@@ -6604,6 +6677,7 @@ class Engine {
         u64 maxval = 0;           // (the largest symbol's value)
         DBuf<idx_t> T, xq, xc;
         mutable ExtractInfo xinfo;
+        mutable MatchInfo minfo;  // of the last fm_match / fm_mems
         u64 extract_bytes() const { return (T.n + xq.n + xc.n) * sizeof(idx_t); }
         u64 bytes() const {
             return key.n * sizeof(FmKey) + slf.n * sizeof(idx_t) + alpha.n * 8 + rc.n * sizeof(RankCell) + rec.n * sizeof(RunRec) + sid.n * sizeof(idx_t) +
@@ -6714,6 +6788,84 @@ class Engine {
         prim::for_each(np, FmCountPlainFn{f}, "fm.count");
 #endif
         prim::sync();
+    }
+    // ---- longest matches and MEMs (functor block "longest matches and maximal exact matches").  Everything that
+    // can refuse a call runs before the first store into an output.  One ticket per query cell; the device form is
+    // prim::top_tickets (lanes that take the next cell when their match ends, under the LDS top level of fm_count), or with
+    // GRLBWT_FM_MATCH=l one lane per cell through prim::top_search; the stand-in runs the same functor serially.
+    //   The compiler's report for gfx950 (tools/kernel_resources.py): prim::k_top_tickets<FmMatchFn> takes 46 vector registers in
+    //   both index widths (k_top_search<FmMatchLaneFn> 32, k_top_search<FmCountFn> 26), no scratch, no static LDS -- the dynamic
+    //   LDS is the top level, at most 32 KB of 8-byte keys or 64 KB of 16-byte keys; 8 waves per SIMD fit either way.
+    // fm_match_cells: the checks both calls share; the number of cells, x0 in `x0`
+    static u64 fm_match_cells(const void *cells, int w, const u64 *off, u64 np, u64 &x0, const char *who) {
+        if (!(w == 1 || w == 2 || w == 4 || w == 8)) throw prim::Error(-22, std::string(who) + ": bad cell width");
+        x0 = 0;
+        if (np == 0) return 0;
+        if (prim::reduce_sum<u64>(np, FmOffsetsBadIn{off}, "fm.offsets")) throw prim::Error(-22, std::string(who) + ": the pattern offsets decrease");
+        u64 x1;
+        prim::d2h(&x0, off, 8);
+        prim::d2h(&x1, off + np, 8);
+        if (x1 > x0 && !cells) throw prim::Error(-22, std::string(who) + ": no pattern cells");
+        return x1 - x0;
+    }
+    static void fm_match_run(const FmIndex &F, const FmMatchFn &f, u64 nc, u64 np, MatchInfo &mi) {
+        mi = MatchInfo();
+        mi.patterns = np; mi.cells = nc;
+        if (nc == 0) return;
+#ifdef GRLBWT_PRIM_HIP
+        if (prim::sw().fm_match == 'l') {
+            prim::top_search(nc, FmMatchLaneFn{f}, F.top_entries, "fm.match_lanes");
+            mi.lanes = nc;
+        } else {
+            DBuf<u64> ctr(2);
+            const prim::WalkStats ws = prim::top_tickets(nc, f, ctr.p, F.top_entries, "fm.match");
+            mi.lanes = ws.lanes; mi.refills = ws.refills;
+        }
+#else
+        prim::for_each(nc, WalkSerialFn<FmMatchFn>{f}, "fm.match");
+        mi.lanes = nc;
+#endif
+        mi.matched = prim::reduce_sum<u64>(nc, CellIn<u64>{f.len}, "fm.match_sum");
+        mi.longest = prim::reduce_max<u64>(nc, CellIn<u64>{f.len}, "fm.match_max");
+        if (f.max_len) mi.capped = prim::reduce_sum<u64>(nc, FmLenCappedIn{f.len, f.max_len}, "fm.match_capped");
+    }
+    static FmMatchFn fm_match_fn(const FmIndex &F, const void *cells, int w, const u64 *off, u64 np, u64 x0, u64 max_len, u64 *len, u64 *lo, u64 *hi) {
+        return FmMatchFn{FmCountFn{F.key.p, F.slf.p, F.R, F.n, F.alpha.p, F.alpha.n, cells, w, off, nullptr, nullptr}, F.sepval, x0, np, max_len, len, lo, hi};
+    }
+    static void fm_match(const FmIndex &F, const void *cells, int w, const u64 *off, u64 np, u64 max_len, u64 *len, u64 *lo, u64 *hi) {
+        if ((lo == nullptr) != (hi == nullptr)) throw prim::Error(-22, "fm match: the range outputs are both given or both null");
+        u64 x0;
+        const u64 nc = fm_match_cells(cells, w, off, np, x0, "fm match");
+        if (nc && !len) throw prim::Error(-22, "fm match: no output for the lengths");
+        MatchInfo mi;
+        fm_match_run(F, fm_match_fn(F, cells, w, off, np, x0, max_len, len, lo, hi), nc, np, mi);
+        prim::sync();
+        F.minfo = mi;
+    }
+    // n_mems is set whenever the count was reached, also when the capacity then refuses the call
+    static void fm_mems(const FmIndex &F, const void *cells, int w, const u64 *off, u64 np, u64 min_len, u64 max_len, u64 *pat, u64 *beg, u64 *mlen,
+                        u64 *lo, u64 *hi, u64 capacity, u64 &n_mems) {
+        n_mems = 0;
+        if ((lo == nullptr) != (hi == nullptr)) throw prim::Error(-22, "fm mems: the range outputs are both given or both null");
+        u64 x0;
+        const u64 nc = fm_match_cells(cells, w, off, np, x0, "fm mems");
+        MatchInfo mi;
+        mi.patterns = np;
+        if (nc == 0) { prim::sync(); F.minfo = mi; return; }
+        const u64 nw = nc / 64 + 2;
+        const u64 need = nc * 8 * (lo ? 3 : 1) + nw * 16 + 24;
+        if (need > prim::mem_available()) throw prim::Error(-12, "fm mems: the scratch needs " + std::to_string(need) + " bytes of device memory, more than is free");
+        DBuf<u64> L(nc), slo(lo ? nc : 0), shi(lo ? nc : 0), words(nw), base(nw + 1);
+        fm_match_run(F, fm_match_fn(F, cells, w, off, np, x0, max_len, L.p, lo ? slo.p : nullptr, lo ? shi.p : nullptr), nc, np, mi);
+        words.zero();
+        prim::bitvector_from_pred(nc, FmMemFlagIn{L.p, off, x0, np, min_len ? min_len : 1}, words.p, "fm.mem_flags");
+        mi.mems = n_mems = prim::exclusive_scan<u64>(nw, PopcIn{words.p}, base.p, true, "fm.mem_ranks");
+        if (n_mems > capacity)
+            throw prim::Error(-22, "fm mems: " + std::to_string(n_mems) + " matches, more than the output arrays hold");
+        if (n_mems && (!pat || !beg || !mlen)) throw prim::Error(-22, "fm mems: no output arrays");
+        prim::for_each_set_bit<u64>(nc, words.p, base.p, FmMemEmitFn{L.p, slo.p, shi.p, off, x0, np, pat, beg, mlen, lo, hi}, "fm.mems");
+        prim::sync();
+        F.minfo = mi;
     }
     static void fm_locate(const FmIndex &F, const u64 *rows, u64 nr, u64 max_steps, u64 *str, u64 *ofs) {
         if (!F.locate) throw prim::Error(-22, "fm locate: the index was made without the structures for locating");

@@ -4277,10 +4277,10 @@ inline u32 top_search_entries(int bits, u64 n_keys, size_t key_bytes) {
 static constexpr int kWalkThreads = 256;
 static constexpr u64 kWalkReserve = 64;
 struct WalkStats { u64 lanes = 0, refills = 0; };
-template <class F>
-__global__ void __launch_bounds__(kWalkThreads) k_walk_tickets(u64 m, u64 lanes, F f, u64 *ctr) {
-    const u64 gid = (u64)blockIdx.x * kWalkThreads + threadIdx.x;
-    if (gid >= lanes) return;                                   // (lanes is a multiple of 64: whole waves)
+// the ticket loop of one lane, shared by k_walk_tickets and k_top_tickets (which passes the step under its LDS top level);
+// every lane of the wave enters it together
+template <class F, class STEP>
+__device__ __forceinline__ void ticket_loop(u64 m, u64 lanes, u64 gid, const F &f, u64 *ctr, STEP step) {
     const u32 lane = threadIdx.x & 63u;
     typename F::State st;
     u64 ticket = gid;
@@ -4316,11 +4316,17 @@ __global__ void __launch_bounds__(kWalkThreads) k_walk_tickets(u64 m, u64 lanes,
             if (r_next >= r_end && !more) break;
             continue;
         }
-        if (active && f.step(st)) { f.end(ticket, st); active = false; }
+        if (active && step(st)) { f.end(ticket, st); active = false; }
     }
     u32 sum = taken;
     for (int d = 32; d > 0; d >>= 1) sum += __shfl_xor(sum, d);
     if (lane == 0 && sum) atomic_add(&ctr[1], (u64)sum);
+}
+template <class F>
+__global__ void __launch_bounds__(kWalkThreads) k_walk_tickets(u64 m, u64 lanes, F f, u64 *ctr) {
+    const u64 gid = (u64)blockIdx.x * kWalkThreads + threadIdx.x;
+    if (gid >= lanes) return;                                   // (lanes is a multiple of 64: whole waves)
+    ticket_loop(m, lanes, gid, f, ctr, [&](typename F::State &st) { return f.step(st); });
 }
 // ctr: two words of device memory, the caller's; they are zeroed here
 template <class F>
@@ -4337,6 +4343,63 @@ inline WalkStats walk_tickets(u64 m, F f, u64 *ctr, const char *name = "walk_tic
     dev_memset(ctr, 0, 16);
     prof_begin(name);
     hipLaunchKernelGGL((k_walk_tickets<F>), dim3((unsigned)blocks), dim3(kWalkThreads), 0, rt().stream, m, lanes, f, ctr);
+    prof_end();
+    after_launch(name);
+    u64 h[2];
+    d2h(h, ctr, 16);
+    ws.lanes = lanes;
+    ws.refills = h[1];
+    return ws;
+}
+
+// ------------------------------------------------------------------ ticketed searches under the LDS top level
+// k_top_search and k_walk_tickets joined: m items, each a chain of searches over f.keys() whose number is known only when it
+// ends (the longest match that ends at a query cell: a changed cell ends it after a dozen steps, its neighbour runs to the cap).
+// The functor is walk_tickets' with F::Key, keys(), n_keys() of top_search and
+//     bool step(State &, const TOP &)    one step under the top level; true: that was the item's last one
+//   Launch: kTopThreads-thread workgroups for the reason given there, as many as the CUs hold at once with this much LDS
+//     (occupancy query); GRLBWT_WALK_LANES sets another number of lanes as in walk_tickets, never more than m rounded up to a
+//     wave.  Lane g starts with ticket g: neighbouring lanes read neighbouring cells.
+//   LDS per workgroup: top_n keys, as k_top_search -- at most 32 KB of 8-byte keys, 64 KB of 16-byte keys; checked against
+//     rt().lds_bytes.
+//   Loops: the copy loop (top_n / kTopThreads rounds), then ticket_loop -- once per step of the wave's longest-running lane plus
+//     once per refill, at most (m - lanes) / 64 + 1 refills over all waves; narrow() at most 13 rounds per search; an item's steps
+//     are bounded by its functor.  The ONE barrier stands behind the copy, in front of the first exit: every thread of the
+//     workgroup reaches it, the waves past the last lane leave behind it.  Nothing waits for another thread.
+//   Registers on gfx950 (tools/kernel_resources.py): k_top_tickets<FmMatchFn> 46 VGPRs in both index widths, no scratch.
+template <class F>
+__global__ void __launch_bounds__(kTopThreads) k_top_tickets(u64 m, u64 lanes, F f, u64 *ctr, u32 top_n, u64 stride) {
+    typedef typename F::Key Key;
+    extern __shared__ __attribute__((aligned(16))) u64 s_top[];
+    Key *s = reinterpret_cast<Key *>(s_top);
+    const Key *keys = f.keys();
+    for (u32 t = threadIdx.x; t < top_n; t += kTopThreads) s[t] = keys[(u64)t * stride];
+    __syncthreads();
+    const u64 gid = (u64)blockIdx.x * kTopThreads + threadIdx.x;
+    if (gid >= lanes) return;                                   // (lanes is a multiple of 64: whole waves)
+    const LdsTop<Key> top{s, top_n, stride, f.n_keys()};
+    ticket_loop(m, lanes, gid, f, ctr, [&](typename F::State &st) { return f.step(st, top); });
+}
+// ctr: two words of device memory, the caller's; they are zeroed here.  top_entries: as top_search
+template <class F>
+inline WalkStats top_tickets(u64 m, F f, u64 *ctr, u32 top_entries, const char *name = "top_tickets") {
+    WalkStats ws;
+    if (m == 0) return ws;
+    const u64 R = f.n_keys();
+    const u64 stride = top_entries ? (R + top_entries - 1) / top_entries : 1;
+    const u32 top_n = top_entries ? (u32)((R + stride - 1) / stride) : 0;
+    const size_t lds = (size_t)top_n * sizeof(typename F::Key);
+    if (lds > rt().lds_bytes) throw Error(-71, std::string(name) + ": the top level does not fit the LDS");
+    int occ = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_top_tickets<F>, kTopThreads, lds) != hipSuccess || occ < 1) { (void)hipGetLastError(); occ = 1; }
+    const u64 m_up = (m + 63) / 64 * 64;
+    u64 lanes = sw().walk_lanes ? (sw().walk_lanes + 63) / 64 * 64 : (u64)rt().num_cus * (u64)occ * kTopThreads;
+    if (lanes > m_up) lanes = m_up;
+    const u64 blocks = (lanes + kTopThreads - 1) / kTopThreads;
+    if (blocks > 0x7FFFFFFFull) throw Error(-75, std::string(name) + ": too many workgroups");
+    dev_memset(ctr, 0, 16);
+    prof_begin(name);
+    hipLaunchKernelGGL((k_top_tickets<F>), dim3((unsigned)blocks), dim3(kTopThreads), lds, rt().stream, m, lanes, f, ctr, top_n, stride);
     prof_end();
     after_launch(name);
     u64 h[2];

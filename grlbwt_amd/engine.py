@@ -36,6 +36,7 @@ ABI_SYMBOLS = [
     "grlbwt_fm_create", "grlbwt_fm_destroy", "grlbwt_fm_info_get", "grlbwt_fm_count", "grlbwt_fm_locate",
     "grlbwt_invert_image_checkpointed", "grlbwt_fm_walk_info_get",
     "grlbwt_fm_string_lengths", "grlbwt_fm_extract", "grlbwt_fm_extract_info_get",
+    "grlbwt_fm_match", "grlbwt_fm_mems", "grlbwt_fm_match_info_get",
     "grlbwt_merge_create", "grlbwt_merge_info_get", "grlbwt_merge_emit", "grlbwt_merge_interleave", "grlbwt_merge_destroy",
     "grlbwt_merge_files",
     "grlbwt_select_create", "grlbwt_select_info_get", "grlbwt_select_emit", "grlbwt_select_rows", "grlbwt_select_destroy",
@@ -76,6 +77,11 @@ class WalkInfo(C.Structure):
 class ExtractInfo(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in ("n_ranges", "n_pieces", "n_cells", "walk_steps", "walk_lanes", "lane_refills",
                                           "n_samples", "extract_bytes")]
+
+
+class MatchInfo(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("n_patterns", "n_cells", "matched_cells", "longest", "n_capped", "n_mems", "walk_lanes",
+                                          "lane_refills")]
 
 
 class ImageStats(C.Structure):
@@ -230,6 +236,9 @@ def load_library(path=None, allow_test_standin=False):
     L.grlbwt_fm_string_lengths.argtypes = [vp, vp, vp]
     L.grlbwt_fm_extract.argtypes = [vp, vp, vp, vp, vp, u64, i32, vp, u64, vp, C.POINTER(u64)]
     L.grlbwt_fm_extract_info_get.argtypes = [vp, C.POINTER(ExtractInfo)]
+    L.grlbwt_fm_match.argtypes = [vp, vp, vp, i32, vp, u64, u64, vp, vp, vp]
+    L.grlbwt_fm_mems.argtypes = [vp, vp, vp, i32, vp, u64, u64, u64, vp, vp, vp, vp, vp, u64, C.POINTER(u64)]
+    L.grlbwt_fm_match_info_get.argtypes = [vp, C.POINTER(MatchInfo)]
     L.grlbwt_merge_create.argtypes = [vp, vp, u64, vp, u64, i32, u64, C.POINTER(vp)]
     L.grlbwt_merge_info_get.argtypes = [vp, C.POINTER(MergeInfo)]
     L.grlbwt_merge_emit.argtypes = [vp, vp, vp, u64]
@@ -600,6 +609,36 @@ class FmIndex:
         """The counters of the last extract() on this index (an index made without extract=True: GrlbwtError)."""
         out = ExtractInfo()
         rc = self.ctx.L.grlbwt_fm_extract_info_get(self._h, C.byref(out))
+        if rc != OK:
+            raise GrlbwtError(rc, self.ctx.L.grlbwt_strerror(rc).decode())
+        return _as_dict(out)
+
+    def match(self, cells_ptr, cell_bytes, offsets_ptr, n, max_len, len_ptr, lo_ptr=None, hi_ptr=None):
+        """For every cell of the n patterns (given as to count()) the length of the longest piece ending there that occurs
+        inside one string, at most max_len (0: no cap); lo / hi, both or neither, receive the rows of that piece.  A cell that
+        is no symbol, or the separator, gets 0."""
+        self.ctx._ck(self.ctx.L.grlbwt_fm_match(self.ctx._h, self._h, C.c_void_p(cells_ptr), cell_bytes, C.c_void_p(offsets_ptr), n, max_len,
+                                                C.c_void_p(len_ptr), C.c_void_p(lo_ptr), C.c_void_p(hi_ptr)))
+
+    def mems(self, cells_ptr, cell_bytes, offsets_ptr, n, min_len, max_len, pattern_ptr, begin_ptr, mlen_ptr, capacity, lo_ptr=None,
+             hi_ptr=None):
+        """The maximal exact matches of at least min_len cells (lengths capped by max_len, 0: no cap) as (pattern, begin, length
+        [, lo, hi]) in ascending (pattern, end) order; their number is returned.  More than `capacity`: GrlbwtError whose
+        n_mems attribute is that number, and nothing is written."""
+        got = C.c_uint64()
+        try:
+            self.ctx._ck(self.ctx.L.grlbwt_fm_mems(self.ctx._h, self._h, C.c_void_p(cells_ptr), cell_bytes, C.c_void_p(offsets_ptr), n, min_len,
+                                                   max_len, C.c_void_p(pattern_ptr), C.c_void_p(begin_ptr), C.c_void_p(mlen_ptr),
+                                                   C.c_void_p(lo_ptr), C.c_void_p(hi_ptr), capacity, C.byref(got)))
+        except GrlbwtError as e:
+            e.n_mems = got.value
+            raise
+        return got.value
+
+    def match_info(self):
+        """The counters of the last match() or mems() on this index."""
+        out = MatchInfo()
+        rc = self.ctx.L.grlbwt_fm_match_info_get(self._h, C.byref(out))
         if rc != OK:
             raise GrlbwtError(rc, self.ctx.L.grlbwt_strerror(rc).decode())
         return _as_dict(out)

@@ -380,6 +380,53 @@ int grlbwt_fm_extract(grlbwt_ctx *ctx, const grlbwt_fm *fm, const uint64_t *dev_
                       uint64_t *dev_out_offsets /* n_ranges + 1 words, written */, uint64_t *n_cells_out);
 int grlbwt_fm_extract_info_get(const grlbwt_fm *fm, grlbwt_fm_extract_info *out);
 
+/* ---- longest matches and maximal exact matches of query batches: what grlbwt_fm_count cannot say about a query that does not
+ * occur whole (a read with one error, a read across two source strings, a query with an unknown base).  Both calls work on any
+ * index of grlbwt_fm_create, with or without GRLBWT_FM_LOCATE, and take their patterns exactly as grlbwt_fm_count does: pattern
+ * i = cells [dev_offsets[i], dev_offsets[i + 1]) of dev_cells, cell_bytes in {1, 2, 4, 8}, n_patterns + 1 non-decreasing offsets.
+ * x0 = dev_offsets[0], x1 = dev_offsets[n_patterns], n_cells = x1 - x0; n_patterns = 0 and n_cells = 0 are legal and write nothing.
+ *
+ * grlbwt_fm_match: for cell x at offset e inside its pattern q, dev_len[x - x0] is the largest L <= e + 1 (and <= max_len when
+ * max_len is not 0) such that q[e + 1 - L .. e + 1) occurs inside one string of the collection -- the backward matching
+ * statistics.  A cell that is no symbol of the image gets L = 0, and so does a cell equal to THE SEPARATOR: no match holds or
+ * crosses one.  Unlike grlbwt_fm_count, the separator does not anchor a match at a string's end here, and it does not fail the
+ * call.  dev_lo and dev_hi are both given or both NULL (one without the other: GRLBWT_EINVAL); for L > 0 they receive the rows
+ * grlbwt_fm_count returns for that substring, for L = 0 they receive 0, 0.
+ *
+ * grlbwt_fm_mems: the same lengths, capped by max_len in the same way.  End e of pattern i is reported when L[e] >= max(min_len, 1)
+ * and e is the pattern's last cell or L[e + 1] <= L[e].  (L[e + 1] <= L[e] + 1 always, with equality exactly when the match
+ * extends to the right; every length is left-maximal by definition, so without a cap the entries are exactly the maximal exact
+ * matches.)  Entry j is (dev_pattern[j], dev_begin[j] = e + 1 - L, dev_mlen[j] = L, dev_lo[j], dev_hi[j]), in ascending
+ * (pattern, end) order.  WITH A CAP a match of max_len cells may extend further to the left, and it is reported at every end
+ * that reaches the cap.  *n_mems_out is always set; when there are more entries than `capacity`, the call fails with
+ * GRLBWT_EINVAL and writes none of the output arrays (the sizing idiom of grlbwt_alphabet_compact_device: call with capacity 0).
+ *
+ * Both refuse with GRLBWT_EINVAL, before the first store into any output: a cell_bytes not in {1, 2, 4, 8}, decreasing offsets,
+ * dev_cells missing while n_cells > 0, a null index.  GRLBWT_ENOMEM when the scratch does not fit: none for grlbwt_fm_match;
+ * for grlbwt_fm_mems one word per cell for the lengths, two more when the rows are asked for, and a quarter byte per cell for
+ * the flags and their ranks.
+ * COST: one backward step (grlbwt_fm_count's: two binary searches over the records, the first GRLBWT_FM_TOP_BITS levels in LDS)
+ * per matched cell and one more per cell, matched_cells + n_cells steps in all.  A query that lies in the collection whole costs,
+ * uncapped, a number of steps quadratic in its length: max_len is what bounds it.  Fine for reads, hopeless for uncapped
+ * chromosome-length queries.  One ticket per cell: lanes whose match has ended take the next cell (GRLBWT_WALK_LANES as for the
+ * checkpointed walks); GRLBWT_FM_MATCH=l runs one lane per cell without refilling, with the same outputs.
+ * grlbwt_fm_match_info_get: the counters of the last of the two calls that succeeded on the index. */
+typedef struct grlbwt_fm_match_info {
+    uint64_t n_patterns, n_cells;          /* of the last grlbwt_fm_match / grlbwt_fm_mems on this index */
+    uint64_t matched_cells, longest;       /* sum and maximum of the lengths written */
+    uint64_t n_capped;                     /* ends whose length is max_len (0 without a cap) */
+    uint64_t n_mems;                       /* 0 after grlbwt_fm_match */
+    uint64_t walk_lanes, lane_refills;     /* of the search launch, as in grlbwt_walk_info */
+} grlbwt_fm_match_info;
+int grlbwt_fm_match(grlbwt_ctx *ctx, const grlbwt_fm *fm, const void *dev_cells, int cell_bytes, const uint64_t *dev_offsets,
+                    uint64_t n_patterns, uint64_t max_len /* 0: no cap */, uint64_t *dev_len /* n_cells words */,
+                    uint64_t *dev_lo /* may be NULL */, uint64_t *dev_hi /* may be NULL */);
+int grlbwt_fm_mems(grlbwt_ctx *ctx, const grlbwt_fm *fm, const void *dev_cells, int cell_bytes, const uint64_t *dev_offsets,
+                   uint64_t n_patterns, uint64_t min_len, uint64_t max_len /* 0: no cap */, uint64_t *dev_pattern, uint64_t *dev_begin,
+                   uint64_t *dev_mlen, uint64_t *dev_lo /* may be NULL */, uint64_t *dev_hi /* may be NULL */, uint64_t capacity,
+                   uint64_t *n_mems_out);
+int grlbwt_fm_match_info_get(const grlbwt_fm *fm, grlbwt_fm_match_info *out);
+
 /* ---- merging two images: the image of the collection "strings of A, then strings of B" from the images of A and B, without the
  * texts -- a collection larger than one build is built in batches and folded together, a batch of new strings is added to an
  * existing image.  String i of B becomes string n_strings_a + i.  When A and B were built by this engine with cells of cell_bytes,
