@@ -23,20 +23,20 @@
 // an FM index (grlbwt_fm_create): one of the two index widths; its buffers come from the context's pool
 struct grlbwt_fm {
     uint32_t flags = 0;
-    std::unique_ptr<grl32::Engine::FmIndex> f32;
-    std::unique_ptr<grl64::Engine::FmIndex> f64;
+    std::unique_ptr<grl32::Image::FmIndex> f32;
+    std::unique_ptr<grl64::Image::FmIndex> f64;
 };
 
 // a merge of two images (grlbwt_merge_create): the converged interleave, the two rank sequences and the alphabet
 struct grlbwt_merge {
-    std::unique_ptr<grl32::Engine::ImageMerge> m32;
-    std::unique_ptr<grl64::Engine::ImageMerge> m64;
+    std::unique_ptr<grl32::Image::ImageMerge> m32;
+    std::unique_ptr<grl64::Image::ImageMerge> m64;
 };
 
 // a selection of strings (grlbwt_select_create): the rewritten runs, the alphabet and the marked rows
 struct grlbwt_select {
-    std::unique_ptr<grl32::Engine::ImageSelect> s32;
-    std::unique_ptr<grl64::Engine::ImageSelect> s64;
+    std::unique_ptr<grl32::Image::ImageSelect> s32;
+    std::unique_ptr<grl64::Image::ImageSelect> s64;
 };
 
 struct grlbwt_ctx {
@@ -140,10 +140,12 @@ void grammar_download(const E &e, int level, uint64_t *g0, uint64_t *g1, uint8_t
 
 static constexpr uint64_t kMergeRowLimit = 1ull << 40;      // grlbwt_merge_create: merged rows, as the build's limit on cells
 static constexpr uint64_t kIdx32Limit = 0xFFFFFF00ull;      // texts of this many cells or more take the 64-bit index build
+// the index width of a call over n cells, rows or symbols: the 64-bit engine from the limit on, or when the context forces it
+static bool idx64_for(const grlbwt_ctx *ctx, uint64_t n) { return n >= kIdx32Limit || (ctx->flags & GRLBWT_FLAG_FORCE_IDX64); }
 void load(grlbwt_ctx *ctx, const void *cells, uint64_t n, int w, bool host) {
     ctx->e32.reset();
     ctx->e64.reset();
-    bool big = (n >= kIdx32Limit) || (ctx->flags & GRLBWT_FLAG_FORCE_IDX64);
+    bool big = idx64_for(ctx, n);
     bool keep = ctx->flags & GRLBWT_FLAG_KEEP_LEVELS;
     if (big) {
         std::unique_ptr<grl64::Engine> e(new grl64::Engine());
@@ -319,7 +321,7 @@ void load_file(grlbwt_ctx *ctx, const char *path, int w, uint64_t base = 0, uint
             bytes = range_bytes;
         } else base = 0;
         const uint64_t n = bytes / (uint64_t)w;
-        bool big = (n >= kIdx32Limit) || (ctx->flags & GRLBWT_FLAG_FORCE_IDX64);
+        bool big = idx64_for(ctx, n);
         bool keep = ctx->flags & GRLBWT_FLAG_KEEP_LEVELS;
         if (big) {
             std::unique_ptr<grl64::Engine> e(new grl64::Engine());
@@ -476,7 +478,7 @@ void load_fastx(grlbwt_ctx *ctx, const char *path, uint32_t fx_flags, uint64_t *
     if (n_strings) *n_strings = info.n_strings;
     if (info.n_out == 0) throw prim::Error(GRLBWT_EILLFORMED, "Error: the file is ill formed");      // no record at all
     const uint64_t n = info.n_out;
-    bool big = (n >= kIdx32Limit) || (ctx->flags & GRLBWT_FLAG_FORCE_IDX64);
+    bool big = idx64_for(ctx, n);
     bool keep = ctx->flags & GRLBWT_FLAG_KEEP_LEVELS;
     if (big) {
         std::unique_ptr<grl64::Engine> e(new grl64::Engine());
@@ -1496,7 +1498,7 @@ int test_set_bits(uint64_t n, uint64_t seed) {
     return 0;
 }
 
-// 12: one refinement round of the image merge (Engine::MergeRound: the three round kernels on the device) against a host loop: flags
+// 12: one refinement round of the image merge (Image::MergeRound: the three round kernels on the device) against a host loop: flags
 // in runs of up to 9000 rows and in coin flips (tiles fed from one image alone, slices that start at any byte), rank bytes below sigma
 template <class E>
 int test_merge_round_one(uint64_t n, uint64_t seed, uint32_t sigma, int ib) {
@@ -1548,8 +1550,8 @@ int test_merge_round(uint64_t n, uint64_t seed) {
     const uint64_t m = self_size(n);
     const uint32_t sigmas[3] = {2, 5, 256};
     for (int k = 0; k < 3; k++) {
-        if (int rc = test_merge_round_one<grl32::Engine>(m, seed + k, sigmas[k], 4)) return -(600 + rc);
-        if (int rc = test_merge_round_one<grl64::Engine>(m + 1 + k, seed + 10 + k, sigmas[k], 8)) return -(610 + rc);
+        if (int rc = test_merge_round_one<grl32::Image>(m, seed + k, sigmas[k], 4)) return -(600 + rc);
+        if (int rc = test_merge_round_one<grl64::Image>(m + 1 + k, seed + 10 + k, sigmas[k], 8)) return -(610 + rc);
     }
     return 0;
 }
@@ -1783,7 +1785,7 @@ int grlbwt_alphabet_compact_device(grlbwt_ctx *ctx, const void *dev_cells, uint6
                                    void *dev_values_u64, uint64_t capacity_values, uint64_t *n_distinct) {
     if (!ctx || !dev_cells || !dev_ranks_u32 || !dev_values_u64 || n_cells == 0 || !(cell_bytes == 4 || cell_bytes == 8)) return GRLBWT_EINVAL;
     return guarded(ctx, [&] {
-        const bool big = n_cells >= kIdx32Limit || (ctx->flags & GRLBWT_FLAG_FORCE_IDX64);
+        const bool big = idx64_for(ctx, n_cells);
         uint64_t k = big ? grl64::Engine::alphabet_compact_device(dev_cells, n_cells, cell_bytes, (uint32_t *)dev_ranks_u32, (uint64_t *)dev_values_u64, capacity_values)
                          : grl32::Engine::alphabet_compact_device(dev_cells, n_cells, cell_bytes, (uint32_t *)dev_ranks_u32, (uint64_t *)dev_values_u64, capacity_values);
         if (n_distinct) *n_distinct = k;
@@ -1931,11 +1933,11 @@ int grlbwt_invert_image_tails(grlbwt_ctx *ctx, const void *dev_image, uint64_t i
                               void *dev_out, uint64_t capacity_cells, uint64_t *n_strings_out, uint64_t *n_cells_out) {
     if (!ctx || !dev_image || !dev_out || tail_cells == 0) return GRLBWT_EINVAL;
     return guarded(ctx, [&] {
-        const uint64_t total = grl64::Engine::image_total_symbols(dev_image, image_bytes);
-        const bool big = total >= kIdx32Limit || (ctx->flags & GRLBWT_FLAG_FORCE_IDX64);
+        const uint64_t total = grl64::Image::image_total_symbols(dev_image, image_bytes);
+        const bool big = idx64_for(ctx, total);
         uint64_t k = 0;
-        const uint64_t n = big ? grl64::Engine::invert_image_tails(dev_image, image_bytes, cell_bytes, tail_cells, dev_out, capacity_cells, &k)
-                               : grl32::Engine::invert_image_tails(dev_image, image_bytes, cell_bytes, tail_cells, dev_out, capacity_cells, &k);
+        const uint64_t n = big ? grl64::Image::invert_image_tails(dev_image, image_bytes, cell_bytes, tail_cells, dev_out, capacity_cells, &k)
+                               : grl32::Image::invert_image_tails(dev_image, image_bytes, cell_bytes, tail_cells, dev_out, capacity_cells, &k);
         if (n_strings_out) *n_strings_out = k;
         if (n_cells_out) *n_cells_out = n;
     });
@@ -1947,11 +1949,11 @@ int grlbwt_invert_image(grlbwt_ctx *ctx, const void *dev_image, uint64_t image_b
     return guarded(ctx, [&] {
         // the index width follows the number of symbols the image DESCRIBES (summed in 64 bits), not the buffer sizes:
         // a small image can describe >= 2^32 symbols, and a 32-bit scan of its run lengths would wrap
-        const uint64_t total = grl64::Engine::image_total_symbols(dev_image, image_bytes);
+        const uint64_t total = grl64::Image::image_total_symbols(dev_image, image_bytes);
         if (total > capacity_cells) throw prim::Error(GRLBWT_EINVAL, "inversion: output buffer too small");
-        bool big = total >= kIdx32Limit || (ctx->flags & GRLBWT_FLAG_FORCE_IDX64);
-        uint64_t n = big ? grl64::Engine::invert_image(dev_image, image_bytes, cell_bytes, dev_text_out, capacity_cells, total)
-                         : grl32::Engine::invert_image(dev_image, image_bytes, cell_bytes, dev_text_out, capacity_cells, total);
+        bool big = idx64_for(ctx, total);
+        uint64_t n = big ? grl64::Image::invert_image(dev_image, image_bytes, cell_bytes, dev_text_out, capacity_cells, total)
+                         : grl32::Image::invert_image(dev_image, image_bytes, cell_bytes, dev_text_out, capacity_cells, total);
         if (n_cells_out) *n_cells_out = n;
     });
 }
@@ -1967,17 +1969,17 @@ int grlbwt_fm_create(grlbwt_ctx *ctx, const void *dev_image, uint64_t image_byte
         return GRLBWT_EINVAL;
     }
     return guarded(ctx, [&] {
-        const uint64_t total = grl64::Engine::image_total_symbols(dev_image, image_bytes);
-        const bool big = total >= kIdx32Limit || (ctx->flags & GRLBWT_FLAG_FORCE_IDX64);
+        const uint64_t total = grl64::Image::image_total_symbols(dev_image, image_bytes);
+        const bool big = idx64_for(ctx, total);
         const bool locate = fm_flags & GRLBWT_FM_LOCATE, cps = fm_flags & GRLBWT_FM_CHECKPOINTS, ext = fm_flags & GRLBWT_FM_EXTRACT;
         std::unique_ptr<grlbwt_fm> fm(new grlbwt_fm());
         fm->flags = fm_flags;
         if (big) {
-            fm->f64.reset(new grl64::Engine::FmIndex());
-            grl64::Engine::fm_create(dev_image, image_bytes, locate, prim::sw().fm_top_bits, *fm->f64, cps, (int)sample_bits, ext);
+            fm->f64.reset(new grl64::Image::FmIndex());
+            grl64::Image::fm_create(dev_image, image_bytes, locate, prim::sw().fm_top_bits, *fm->f64, cps, (int)sample_bits, ext);
         } else {
-            fm->f32.reset(new grl32::Engine::FmIndex());
-            grl32::Engine::fm_create(dev_image, image_bytes, locate, prim::sw().fm_top_bits, *fm->f32, cps, (int)sample_bits, ext);
+            fm->f32.reset(new grl32::Image::FmIndex());
+            grl32::Image::fm_create(dev_image, image_bytes, locate, prim::sw().fm_top_bits, *fm->f32, cps, (int)sample_bits, ext);
         }
         ctx->fms.push_back(fm.get());
         *out = fm.release();
@@ -2016,18 +2018,18 @@ int grlbwt_invert_image_checkpointed(grlbwt_ctx *ctx, const void *dev_image, uin
     if (!ctx || !dev_image || !dev_text_out) return GRLBWT_EINVAL;
     return guarded(ctx, [&] {
         if (sample_bits < 0 || sample_bits > 20) throw prim::Error(GRLBWT_EINVAL, "checkpointed walk: sample_bits is 0 (the default) or 1 to 20");
-        const uint64_t total = grl64::Engine::image_total_symbols(dev_image, image_bytes);
+        const uint64_t total = grl64::Image::image_total_symbols(dev_image, image_bytes);
         if (total > capacity_cells) throw prim::Error(GRLBWT_EINVAL, "inversion: output buffer too small");
-        const bool big = total >= kIdx32Limit || (ctx->flags & GRLBWT_FLAG_FORCE_IDX64);
+        const bool big = idx64_for(ctx, total);
         uint64_t n;
         grlbwt_walk_info wi;
         if (big) {
-            grl64::Engine::WalkInfo w;
-            n = grl64::Engine::invert_image_checkpointed(dev_image, image_bytes, cell_bytes, sample_bits, dev_text_out, capacity_cells, w);
+            grl64::Image::WalkInfo w;
+            n = grl64::Image::invert_image_checkpointed(dev_image, image_bytes, cell_bytes, sample_bits, dev_text_out, capacity_cells, w);
             fill_walk_info(w, &wi);
         } else {
-            grl32::Engine::WalkInfo w;
-            n = grl32::Engine::invert_image_checkpointed(dev_image, image_bytes, cell_bytes, sample_bits, dev_text_out, capacity_cells, w);
+            grl32::Image::WalkInfo w;
+            n = grl32::Image::invert_image_checkpointed(dev_image, image_bytes, cell_bytes, sample_bits, dev_text_out, capacity_cells, w);
             fill_walk_info(w, &wi);
         }
         if (n_cells_out) *n_cells_out = n;
@@ -2039,8 +2041,8 @@ int grlbwt_fm_count(grlbwt_ctx *ctx, const grlbwt_fm *fm, const void *dev_cells,
     if (!ctx || !fm || !(fm->f32 || fm->f64)) return GRLBWT_EINVAL;
     if (n_patterns && (!dev_offsets || !dev_lo || !dev_hi)) return GRLBWT_EINVAL;
     return guarded(ctx, [&] {
-        if (fm->f32) grl32::Engine::fm_count(*fm->f32, dev_cells, cell_bytes, dev_offsets, n_patterns, dev_lo, dev_hi);
-        else grl64::Engine::fm_count(*fm->f64, dev_cells, cell_bytes, dev_offsets, n_patterns, dev_lo, dev_hi);
+        if (fm->f32) grl32::Image::fm_count(*fm->f32, dev_cells, cell_bytes, dev_offsets, n_patterns, dev_lo, dev_hi);
+        else grl64::Image::fm_count(*fm->f64, dev_cells, cell_bytes, dev_offsets, n_patterns, dev_lo, dev_hi);
     });
 }
 int grlbwt_fm_match(grlbwt_ctx *ctx, const grlbwt_fm *fm, const void *dev_cells, int cell_bytes, const uint64_t *dev_offsets,
@@ -2048,8 +2050,8 @@ int grlbwt_fm_match(grlbwt_ctx *ctx, const grlbwt_fm *fm, const void *dev_cells,
     if (!ctx || !fm || !(fm->f32 || fm->f64)) return GRLBWT_EINVAL;
     if (n_patterns && !dev_offsets) return GRLBWT_EINVAL;
     return guarded(ctx, [&] {
-        if (fm->f32) grl32::Engine::fm_match(*fm->f32, dev_cells, cell_bytes, dev_offsets, n_patterns, max_len, dev_len, dev_lo, dev_hi);
-        else grl64::Engine::fm_match(*fm->f64, dev_cells, cell_bytes, dev_offsets, n_patterns, max_len, dev_len, dev_lo, dev_hi);
+        if (fm->f32) grl32::Image::fm_match(*fm->f32, dev_cells, cell_bytes, dev_offsets, n_patterns, max_len, dev_len, dev_lo, dev_hi);
+        else grl64::Image::fm_match(*fm->f64, dev_cells, cell_bytes, dev_offsets, n_patterns, max_len, dev_len, dev_lo, dev_hi);
     });
 }
 int grlbwt_fm_mems(grlbwt_ctx *ctx, const grlbwt_fm *fm, const void *dev_cells, int cell_bytes, const uint64_t *dev_offsets,
@@ -2060,9 +2062,9 @@ int grlbwt_fm_mems(grlbwt_ctx *ctx, const grlbwt_fm *fm, const void *dev_cells, 
     if (n_patterns && !dev_offsets) return GRLBWT_EINVAL;
     uint64_t n = 0;
     const int rc = guarded(ctx, [&] {
-        if (fm->f32) grl32::Engine::fm_mems(*fm->f32, dev_cells, cell_bytes, dev_offsets, n_patterns, min_len, max_len, dev_pattern, dev_begin, dev_mlen,
+        if (fm->f32) grl32::Image::fm_mems(*fm->f32, dev_cells, cell_bytes, dev_offsets, n_patterns, min_len, max_len, dev_pattern, dev_begin, dev_mlen,
                                             dev_lo, dev_hi, capacity, n);
-        else grl64::Engine::fm_mems(*fm->f64, dev_cells, cell_bytes, dev_offsets, n_patterns, min_len, max_len, dev_pattern, dev_begin, dev_mlen,
+        else grl64::Image::fm_mems(*fm->f64, dev_cells, cell_bytes, dev_offsets, n_patterns, min_len, max_len, dev_pattern, dev_begin, dev_mlen,
                                     dev_lo, dev_hi, capacity, n);
     });
     if (n_mems_out) *n_mems_out = n;
@@ -2083,15 +2085,15 @@ int grlbwt_fm_locate(grlbwt_ctx *ctx, const grlbwt_fm *fm, const uint64_t *dev_r
     if (!ctx || !fm || !(fm->f32 || fm->f64)) return GRLBWT_EINVAL;
     if (n_rows && (!dev_rows || !dev_string || !dev_offset)) return GRLBWT_EINVAL;
     return guarded(ctx, [&] {
-        if (fm->f32) grl32::Engine::fm_locate(*fm->f32, dev_rows, n_rows, max_steps, dev_string, dev_offset);
-        else grl64::Engine::fm_locate(*fm->f64, dev_rows, n_rows, max_steps, dev_string, dev_offset);
+        if (fm->f32) grl32::Image::fm_locate(*fm->f32, dev_rows, n_rows, max_steps, dev_string, dev_offset);
+        else grl64::Image::fm_locate(*fm->f64, dev_rows, n_rows, max_steps, dev_string, dev_offset);
     });
 }
 int grlbwt_fm_string_lengths(grlbwt_ctx *ctx, const grlbwt_fm *fm, uint64_t *dev_len) {
     if (!ctx || !fm || !dev_len || !(fm->f32 || fm->f64)) return GRLBWT_EINVAL;
     return guarded(ctx, [&] {
-        if (fm->f32) grl32::Engine::fm_string_lengths(*fm->f32, dev_len);
-        else grl64::Engine::fm_string_lengths(*fm->f64, dev_len);
+        if (fm->f32) grl32::Image::fm_string_lengths(*fm->f32, dev_len);
+        else grl64::Image::fm_string_lengths(*fm->f64, dev_len);
     });
 }
 int grlbwt_fm_extract(grlbwt_ctx *ctx, const grlbwt_fm *fm, const uint64_t *dev_string, const uint64_t *dev_begin, const uint64_t *dev_end,
@@ -2099,8 +2101,8 @@ int grlbwt_fm_extract(grlbwt_ctx *ctx, const grlbwt_fm *fm, const uint64_t *dev_
     if (!ctx || !fm || !dev_out_offsets || !(fm->f32 || fm->f64)) return GRLBWT_EINVAL;
     if (n_ranges && (!dev_string || !dev_begin || !dev_end || (!dev_out && capacity_cells))) return GRLBWT_EINVAL;
     return guarded(ctx, [&] {
-        const uint64_t n = fm->f32 ? grl32::Engine::fm_extract(*fm->f32, dev_string, dev_begin, dev_end, n_ranges, cell_bytes, dev_out, capacity_cells, dev_out_offsets)
-                                   : grl64::Engine::fm_extract(*fm->f64, dev_string, dev_begin, dev_end, n_ranges, cell_bytes, dev_out, capacity_cells, dev_out_offsets);
+        const uint64_t n = fm->f32 ? grl32::Image::fm_extract(*fm->f32, dev_string, dev_begin, dev_end, n_ranges, cell_bytes, dev_out, capacity_cells, dev_out_offsets)
+                                   : grl64::Image::fm_extract(*fm->f64, dev_string, dev_begin, dev_end, n_ranges, cell_bytes, dev_out, capacity_cells, dev_out_offsets);
         if (n_cells_out) *n_cells_out = n;
     });
 }
@@ -2121,16 +2123,16 @@ int grlbwt_merge_create(grlbwt_ctx *ctx, const void *dev_image_a, uint64_t bytes
     if (out) *out = nullptr;
     if (!ctx || !dev_image_a || !dev_image_b || !out) return GRLBWT_EINVAL;
     return guarded(ctx, [&] {
-        const uint64_t ta = grl64::Engine::image_total_symbols(dev_image_a, bytes_a), tb = grl64::Engine::image_total_symbols(dev_image_b, bytes_b);
+        const uint64_t ta = grl64::Image::image_total_symbols(dev_image_a, bytes_a), tb = grl64::Image::image_total_symbols(dev_image_b, bytes_b);
         if (ta >= kMergeRowLimit || tb >= kMergeRowLimit || ta + tb >= kMergeRowLimit) throw prim::Error(GRLBWT_ERANGE, "merge: 2^40 merged rows or more");
-        const bool big = ta + tb >= kIdx32Limit || (ctx->flags & GRLBWT_FLAG_FORCE_IDX64);
+        const bool big = idx64_for(ctx, ta + tb);
         std::unique_ptr<grlbwt_merge> mg(new grlbwt_merge());
         if (big) {
-            mg->m64.reset(new grl64::Engine::ImageMerge());
-            grl64::Engine::merge_create(dev_image_a, bytes_a, dev_image_b, bytes_b, cell_bytes, max_rounds, *mg->m64);
+            mg->m64.reset(new grl64::Image::ImageMerge());
+            grl64::Image::merge_create(dev_image_a, bytes_a, dev_image_b, bytes_b, cell_bytes, max_rounds, *mg->m64);
         } else {
-            mg->m32.reset(new grl32::Engine::ImageMerge());
-            grl32::Engine::merge_create(dev_image_a, bytes_a, dev_image_b, bytes_b, cell_bytes, max_rounds, *mg->m32);
+            mg->m32.reset(new grl32::Image::ImageMerge());
+            grl32::Image::merge_create(dev_image_a, bytes_a, dev_image_b, bytes_b, cell_bytes, max_rounds, *mg->m32);
         }
         ctx->merges.push_back(mg.get());
         *out = mg.release();
@@ -2152,21 +2154,21 @@ int grlbwt_merge_info_get(const grlbwt_merge *mg, grlbwt_merge_info *out) {
         out->n_runs = M.n_runs; out->out_bytes = M.out_bytes; out->sb = M.sb; out->fb = M.fb;
         out->idx_bytes = idx_bytes; out->tile_rows = tile_rows; out->scratch_bytes = M.scratch_bytes; out->held_bytes = M.held_bytes();
     };
-    if (mg->m32) fill(*mg->m32, 4, grl32::Engine::kMergeTile); else fill(*mg->m64, 8, grl64::Engine::kMergeTile);
+    if (mg->m32) fill(*mg->m32, 4, grl32::Image::kMergeTile); else fill(*mg->m64, 8, grl64::Image::kMergeTile);
     return GRLBWT_OK;
 }
 int grlbwt_merge_emit(grlbwt_ctx *ctx, const grlbwt_merge *mg, void *dev_out, uint64_t capacity_bytes) {
     if (!ctx || !mg || !dev_out || !(mg->m32 || mg->m64)) return GRLBWT_EINVAL;
     return guarded(ctx, [&] {
-        if (mg->m32) grl32::Engine::merge_emit(*mg->m32, (uint8_t *)dev_out, capacity_bytes);
-        else grl64::Engine::merge_emit(*mg->m64, (uint8_t *)dev_out, capacity_bytes);
+        if (mg->m32) grl32::Image::merge_emit(*mg->m32, (uint8_t *)dev_out, capacity_bytes);
+        else grl64::Image::merge_emit(*mg->m64, (uint8_t *)dev_out, capacity_bytes);
     });
 }
 int grlbwt_merge_interleave(grlbwt_ctx *ctx, const grlbwt_merge *mg, uint64_t *dev_bits) {
     if (!ctx || !mg || !dev_bits || !(mg->m32 || mg->m64)) return GRLBWT_EINVAL;
     return guarded(ctx, [&] {
-        if (mg->m32) grl32::Engine::merge_interleave(*mg->m32, dev_bits);
-        else grl64::Engine::merge_interleave(*mg->m64, dev_bits);
+        if (mg->m32) grl32::Image::merge_interleave(*mg->m32, dev_bits);
+        else grl64::Image::merge_interleave(*mg->m64, dev_bits);
     });
 }
 int grlbwt_merge_files(grlbwt_ctx *ctx, const char *path_a, const char *path_b, int cell_bytes, uint64_t max_rounds, const char *path_out,
@@ -2207,18 +2209,18 @@ int grlbwt_select_create(grlbwt_ctx *ctx, const void *dev_image, uint64_t image_
         return GRLBWT_EINVAL;
     }
     return guarded(ctx, [&] {
-        const uint64_t total = grl64::Engine::image_total_symbols(dev_image, image_bytes);
+        const uint64_t total = grl64::Image::image_total_symbols(dev_image, image_bytes);
         if (total >= kMergeRowLimit) throw prim::Error(GRLBWT_ERANGE, "select: 2^40 rows or more");
-        const bool big = total >= kIdx32Limit || (ctx->flags & GRLBWT_FLAG_FORCE_IDX64);
+        const bool big = idx64_for(ctx, total);
         std::unique_ptr<grlbwt_select> sel(new grlbwt_select());
         if (big) {
-            sel->s64.reset(new grl64::Engine::ImageSelect());
+            sel->s64.reset(new grl64::Image::ImageSelect());
             sel->s64->flags = select_flags;
-            grl64::Engine::select_create(dev_image, image_bytes, cell_bytes, dev_ids, n_ids, keep, cps, (int)sample_bits, *sel->s64);
+            grl64::Image::select_create(dev_image, image_bytes, cell_bytes, dev_ids, n_ids, keep, cps, (int)sample_bits, *sel->s64);
         } else {
-            sel->s32.reset(new grl32::Engine::ImageSelect());
+            sel->s32.reset(new grl32::Image::ImageSelect());
             sel->s32->flags = select_flags;
-            grl32::Engine::select_create(dev_image, image_bytes, cell_bytes, dev_ids, n_ids, keep, cps, (int)sample_bits, *sel->s32);
+            grl32::Image::select_create(dev_image, image_bytes, cell_bytes, dev_ids, n_ids, keep, cps, (int)sample_bits, *sel->s32);
         }
         ctx->selects.push_back(sel.get());
         *out = sel.release();
@@ -2249,15 +2251,15 @@ int grlbwt_select_info_get(const grlbwt_select *sel, grlbwt_select_info *out) {
 int grlbwt_select_emit(grlbwt_ctx *ctx, const grlbwt_select *sel, void *dev_out, uint64_t capacity_bytes) {
     if (!ctx || !sel || !dev_out || !(sel->s32 || sel->s64)) return GRLBWT_EINVAL;
     return guarded(ctx, [&] {
-        if (sel->s32) grl32::Engine::select_emit(*sel->s32, (uint8_t *)dev_out, capacity_bytes);
-        else grl64::Engine::select_emit(*sel->s64, (uint8_t *)dev_out, capacity_bytes);
+        if (sel->s32) grl32::Image::select_emit(*sel->s32, (uint8_t *)dev_out, capacity_bytes);
+        else grl64::Image::select_emit(*sel->s64, (uint8_t *)dev_out, capacity_bytes);
     });
 }
 int grlbwt_select_rows(grlbwt_ctx *ctx, const grlbwt_select *sel, uint64_t *dev_bits) {
     if (!ctx || !sel || !dev_bits || !(sel->s32 || sel->s64)) return GRLBWT_EINVAL;
     return guarded(ctx, [&] {
-        if (sel->s32) grl32::Engine::select_rows(*sel->s32, dev_bits);
-        else grl64::Engine::select_rows(*sel->s64, dev_bits);
+        if (sel->s32) grl32::Image::select_rows(*sel->s32, dev_bits);
+        else grl64::Image::select_rows(*sel->s64, dev_bits);
     });
 }
 int grlbwt_select_files(grlbwt_ctx *ctx, const char *path_in, const uint64_t *host_ids, uint64_t n_ids, int cell_bytes, uint32_t select_flags,
@@ -2292,11 +2294,11 @@ int grlbwt_image_plain(grlbwt_ctx *ctx, const void *dev_image, uint64_t image_by
                        uint64_t capacity, int null_char, uint64_t *n_out) {
     if (!ctx || !dev_image || !dev_out_u8 || null_char > 255) return GRLBWT_EINVAL;
     return guarded(ctx, [&] {
-        const uint64_t total = grl64::Engine::image_total_symbols(dev_image, image_bytes);
+        const uint64_t total = grl64::Image::image_total_symbols(dev_image, image_bytes);
         if (total > capacity) throw prim::Error(GRLBWT_EINVAL, "grl2plain: output buffer too small");
-        bool big = total >= kIdx32Limit || (ctx->flags & GRLBWT_FLAG_FORCE_IDX64);
-        uint64_t n = big ? grl64::Engine::image_plain(dev_image, image_bytes, (uint8_t *)dev_out_u8, capacity, null_char)
-                         : grl32::Engine::image_plain(dev_image, image_bytes, (uint8_t *)dev_out_u8, capacity, null_char);
+        bool big = idx64_for(ctx, total);
+        uint64_t n = big ? grl64::Image::image_plain(dev_image, image_bytes, (uint8_t *)dev_out_u8, capacity, null_char)
+                         : grl32::Image::image_plain(dev_image, image_bytes, (uint8_t *)dev_out_u8, capacity, null_char);
         if (n_out) *n_out = n;
     });
 }
@@ -2304,15 +2306,15 @@ int grlbwt_image_rle(grlbwt_ctx *ctx, const void *dev_image, uint64_t image_byte
                      uint64_t capacity_runs, uint64_t *n_runs_out) {
     if (!ctx || !dev_image || !dev_syms_u8 || !dev_lens_u32) return GRLBWT_EINVAL;
     return guarded(ctx, [&] {
-        uint64_t r = grl64::Engine::image_rle(dev_image, image_bytes, (uint8_t *)dev_syms_u8, (uint32_t *)dev_lens_u32, capacity_runs);
+        uint64_t r = grl64::Image::image_rle(dev_image, image_bytes, (uint8_t *)dev_syms_u8, (uint32_t *)dev_lens_u32, capacity_runs);
         if (n_runs_out) *n_runs_out = r;
     });
 }
 int grlbwt_image_stats_get(grlbwt_ctx *ctx, const void *dev_image, uint64_t image_bytes, grlbwt_image_stats *out) {
     if (!ctx || !dev_image || !out) return GRLBWT_EINVAL;
     return guarded(ctx, [&] {
-        grl64::Engine::ImageStats st;
-        grl64::Engine::image_stats(dev_image, image_bytes, st);
+        grl64::Image::ImageStats st;
+        grl64::Image::image_stats(dev_image, image_bytes, st);
         out->n_runs = st.n_runs; out->sigma = st.sigma; out->text_size = st.text_size; out->min_run = st.min_run; out->max_run = st.max_run;
         out->fit1 = st.fit1; out->fit2 = st.fit2; out->fit3 = st.fit3;
         for (int c = 0; c < 256; c++) { out->runs_of[c] = st.runs_of[c]; out->freq_of[c] = st.freq_of[c]; }
@@ -2325,14 +2327,14 @@ int grlbwt_image_split_runs(grlbwt_ctx *ctx, const void *dev_image, uint64_t ima
                             void *dev_out, uint64_t capacity_bytes, grlbwt_split_info *info) {
     if (!ctx || !dev_image || !dev_out) return GRLBWT_EINVAL;
     return guarded(ctx, [&] {
-        const uint64_t total = grl64::Engine::image_total_symbols(dev_image, image_bytes);
-        bool big = total >= kIdx32Limit || (ctx->flags & GRLBWT_FLAG_FORCE_IDX64);
+        const uint64_t total = grl64::Image::image_total_symbols(dev_image, image_bytes);
+        bool big = idx64_for(ctx, total);
         uint64_t v[6];
         if (big) {
-            auto si = grl64::Engine::image_split_runs(dev_image, image_bytes, bits, block_size, (uint8_t *)dev_out, capacity_bytes);
+            auto si = grl64::Image::image_split_runs(dev_image, image_bytes, bits, block_size, (uint8_t *)dev_out, capacity_bytes);
             v[0] = si.runs_before; v[1] = si.runs_after; v[2] = si.overflow_splits; v[3] = si.block_splits; v[4] = si.n_syms; v[5] = si.out_bytes;
         } else {
-            auto si = grl32::Engine::image_split_runs(dev_image, image_bytes, bits, block_size, (uint8_t *)dev_out, capacity_bytes);
+            auto si = grl32::Image::image_split_runs(dev_image, image_bytes, bits, block_size, (uint8_t *)dev_out, capacity_bytes);
             v[0] = si.runs_before; v[1] = si.runs_after; v[2] = si.overflow_splits; v[3] = si.block_splits; v[4] = si.n_syms; v[5] = si.out_bytes;
         }
         if (info) {

@@ -1,6 +1,7 @@
 // engine_hip.hip -- the one translation unit of libgrlbwt_hip.so (gfx950 only).
 // prim_hip.hpp: hand-written device primitives; engine_impl.hpp: the engine,
-// instantiated for 32-bit and 64-bit positions/lengths; capi_impl.hpp: C-ABI.
+// image_impl.hpp: the consumers of a finished image, both instantiated for
+// 32-bit and 64-bit positions/lengths; capi_impl.hpp: C-ABI.
 #include <time.h>
 #include <cmath>
 #include <type_traits>
@@ -15,6 +16,7 @@
 #define GRL_IDX_T uint32_t
 #define GRL_IDX_BYTES 4
 #include "engine_impl.hpp"
+#include "image_impl.hpp"
 #undef GRL_NS
 #undef GRL_IDX_T
 #undef GRL_IDX_BYTES
@@ -23,6 +25,7 @@
 #define GRL_IDX_T uint64_t
 #define GRL_IDX_BYTES 8
 #include "engine_impl.hpp"
+#include "image_impl.hpp"
 #undef GRL_NS
 #undef GRL_IDX_T
 #undef GRL_IDX_BYTES

@@ -1,0 +1,1941 @@
+// image_impl.hpp -- the consumers of a finished .rl_bwt image: what reads, inverts, searches, merges or rewrites
+// an image in device memory.  Nothing here builds a BWT and the builder (engine_impl.hpp) calls nothing of it.
+//
+// Included once per index width right after engine_impl.hpp, inside the same GRL_NS / GRL_IDX_T window: engine_hip.hip and
+// tests/hostsim/engine_sim.cpp do so.  engine_impl.hpp also ends with this include, so that a translation unit that names
+// engine_impl.hpp alone still gets what capi_impl.hpp calls; the guard below makes the second inclusion of a width empty.
+//
+// What it holds: the device functors (in the order of the sections below) and, as static members of the stateless
+// `struct Image`, the host functions behind the C-ABI's grlbwt_image_*, grlbwt_invert_*, grlbwt_fm_*, grlbwt_merge_* and
+// grlbwt_select_* calls (reference: scripts/*.cpp of ddiazdom/grlBWT):
+//   records and the scripts/ consumers   ImageRecs, plain / rle / stats / split_runs
+//   inversion                            per position (invert_t) and per run (RunIndex, invert_runs_t)
+//   FM index                             count, locate, match / MEMs, extract
+//   checkpointed LF walks                lf_checkpoints and the walks cut at checkpoints
+//   merge, select                        ImageMerge, ImageSelect
+// The pieces every consumer shares, one copy each: ImageRecs (the record layout), image_header / check_cell_bytes /
+// with_cell (opening an image), drop_empty_runs, run_index_load / run_index_lf, LfRows (one LF step), SymOut (rank -> cell).
+//
+// What it takes from engine_impl.hpp, all at namespace level: DBuf, RankBits / build_rankbits / rank1 / RankCell, Runs /
+// merge_runs, alphabet_compact, the record writers PackRunsFn / RunRecordFn / RunLen, the input functors IdxIn / IdxIn64 /
+// CellIn / PopcIn / PtrU32In / SymHeadIn64, upper_bound / lower_bound and bitlen64.
+
+#if (GRL_IDX_BYTES == 4 && !defined(GRL_IMAGE_IMPL_32)) || (GRL_IDX_BYTES == 8 && !defined(GRL_IMAGE_IMPL_64))
+#if GRL_IDX_BYTES == 4
+#define GRL_IMAGE_IMPL_32
+#else
+#define GRL_IMAGE_IMPL_64
+#endif
+
+namespace GRL_NS {
+
+// ---- .rl_bwt consumers (scripts/grl2plain.cpp, scripts/reverse_bwt.cpp + fm_index.h:79-83) ------
+struct SepLenIn {         // total length of the runs of one symbol
+    const u32 *sym; const idx_t *len; u32 code;
+    GRL_DEV u64 operator()(u64 i) const { return sym[i] == code ? (u64)len[i] : 0ull; }
+};
+// The packed records of an image, behind its 16 header bytes: (symbol: sb bytes, length: fb bytes), both little-endian.  The
+// one place that knows the layout on the reading side (PackRunsFn and RunRecordFn of engine_impl.hpp write it).
+struct ImageRecs {
+    const u8 *img; u32 sb, fb;
+    GRL_DEV static u64 le(const u8 *p, u32 w) {
+        u64 v = 0;
+        for (u32 b = 0; b < w; b++) v |= (u64)p[b] << (8 * b);
+        return v;
+    }
+    GRL_DEV const u8 *at(u64 i) const { return img + 16 + i * (u64)(sb + fb); }
+    GRL_DEV u64 sym(u64 i) const { return le(at(i), sb); }       // all 64 bits of it
+    GRL_DEV u64 len(u64 i) const { return le(at(i) + sb, fb); }
+};
+template <class sym_t>
+struct UnpackRunsFn {     // records -> arrays (sym_t = u32: the symbol's low half; u64: all of it)
+    ImageRecs in; sym_t *sym; idx_t *len;
+    GRL_DEV void operator()(u64 i) const { sym[i] = (sym_t)in.sym(i); len[i] = (idx_t)in.len(i); }
+};
+struct NonEmptyIn {        // 1 for a record that holds symbols
+    const idx_t *len;
+    GRL_DEV idx_t operator()(u64 i) const { return len[i] != 0 ? (idx_t)1 : (idx_t)0; }
+};
+template <class sym_t>
+struct KeepRunsFn {        // compacting copy of the non-empty records (dst = scan of NonEmptyIn)
+    const sym_t *sym; const idx_t *len; const idx_t *dst; sym_t *osym; idx_t *olen;
+    GRL_DEV void operator()(u64 i) const {
+        const idx_t l = len[i];
+        if (l != 0) { const u64 o = dst[i]; osym[o] = sym[i]; olen[o] = l; }
+    }
+};
+struct ImageSymIn {        // run symbol straight from the packed records
+    ImageRecs in;
+    GRL_DEV u64 operator()(u64 i) const { return in.sym(i); }
+};
+struct UnpackSymFn {
+    ImageRecs in; u64 *sym;
+    GRL_DEV void operator()(u64 i) const { sym[i] = in.sym(i); }
+};
+struct ImageLenIn {        // run length straight from the packed records (64-bit sum: decides the index width of a consumer)
+    ImageRecs in;
+    GRL_DEV u64 operator()(u64 i) const { return in.len(i); }
+};
+// scripts/grl2plain.cpp:30-45: one output byte per BWT position, (char)sym, optional null replacement.  The replacement is
+// decided per RUN on all 64 bits of the symbol (a symbol of 2^32 is not the null character; its low byte is 0 all the same).
+struct PlainSymFn {
+    ImageRecs in; int null_char; u32 *rsym;
+    GRL_DEV void operator()(u64 i) const {
+        const u64 s = in.sym(i);
+        rsym[i] = (s == 0 && null_char >= 0) ? (u32)null_char : (u32)(u8)s;
+    }
+};
+struct PlainRunsFn {
+    const u32 *rsym; const u64 *rw; const idx_t *rb; u8 *out;
+    GRL_DEV void operator()(u64 i) const { out[i] = (u8)rsym[rank1(rw, rb, i + 1) - 1]; }
+};
+struct RleExportFn {      // scripts/grlbwt2rle.cpp:22-30: .syms as uint8, .len as uint32 (the reference's casts)
+    const u32 *rsym; const idx_t *rlen; u8 *syms; u32 *lens;
+    GRL_DEV void operator()(u64 i) const { syms[i] = (u8)rsym[i]; lens[i] = (u32)rlen[i]; }
+};
+// split_runs (scripts/split_runs.cpp:44-109).  A run is first cut into pieces of at most L = 2^bits - 1 symbols
+// (`while(len>max_length)`), every piece then at the multiples of the block size B that fall strictly inside it; a piece
+// that STARTS on a block boundary (other than position 0) is preceded by a zero-length record of its own symbol (the
+// reference arrives there with acc_block == block_size and emits `push_back(sym, 0)`, :87-90).  Each boundary in (0, n)
+// therefore costs exactly one extra record, so the first record of piece j of run i sits at
+//   (#pieces before it) + (#multiples of B in (0, start of the piece)).
+// An EMPTY input record is one piece and one output record wherever it lies: on a boundary it pays nothing (the next
+// non-empty piece starts there too and pays), so it must not write the extra record -- that slot belongs to its successor,
+// or lies behind the output when nothing follows.
+struct PieceCountFn {     // number of L-pieces of every run
+    const idx_t *len; u64 L;
+    GRL_DEV idx_t operator()(u64 i) const { u64 l = len[i]; return (idx_t)(l == 0 ? 1 : (l + L - 1) / L); }
+};
+struct SplitRunsFn {      // one lane per L-piece
+    const u32 *rsym; const idx_t *rlen; const idx_t *rpos; const idx_t *jbase; const u64 *jw; const idx_t *jb;
+    u64 L, B;
+    u32 *osym; idx_t *olen;
+    GRL_DEV void operator()(u64 x) const {
+        const u64 i = rank1(jw, jb, x + 1) - 1;          // run owning piece x
+        const u64 j = x - (u64)jbase[i];
+        const u64 l = rlen[i];
+        const u64 k = l == 0 ? 0 : (l + L - 1) / L - 1;  // full pieces peeled off in front of the remainder
+        u64 cur = (u64)rpos[i] + j * L;
+        const u64 end = cur + (j < k ? L : l - k * L);
+        const u32 sy = rsym[i];
+        u64 o = x + ((B && cur > 0) ? (cur - 1) / B : 0);
+        if (B) {
+            if (cur > 0 && cur % B == 0 && end > cur) { osym[o] = sy; olen[o] = 0; o++; }     // (an empty record is its own zero-length record)
+            for (u64 nb = (cur / B + 1) * B; nb < end; nb += B) { osym[o] = sy; olen[o] = (idx_t)(nb - cur); o++; cur = nb; }
+        }
+        osym[o] = sy; olen[o] = (idx_t)(end - cur);
+    }
+};
+struct RunSymFn {         // for_each_agg protocol: every run is a work item, its bucket is its symbol
+    static constexpr int kBatch = 1;
+    static constexpr bool kClaims = false;
+    GRL_DEV u64 claim_pos(u64 i) const { return i; }
+    const u32 *rsym;
+    GRL_DEV bool is_start(u64) const { return true; }
+    GRL_DEV u32 process(u64 i) const { return rsym[i]; }
+    GRL_DEV u32 operator()(u64 i) const { return rsym[i]; }
+};
+struct BinAddFn {
+    u64 *bins;
+    GRL_DEV void operator()(u32 b, u32 c) const { prim::atomic_add(&bins[b & 255u], (u64)c); }
+};
+struct LenFitIn {         // 1 if the run length needs exactly `cls` bytes class (1: <=255, 2: <=65535, 3: more)
+    const idx_t *len; int cls;
+    GRL_DEV u64 operator()(u64 i) const {
+        u64 l = len[i];
+        int c = l <= 255 ? 1 : (l <= 65535 ? 2 : 3);
+        return c == cls ? 1ull : 0ull;
+    }
+};
+struct LenKeyFn {
+    const idx_t *len; u32 *key; u32 *val;
+    GRL_DEV void operator()(u64 i) const { key[i] = (u32)len[i]; val[i] = (u32)i; }
+};
+struct ExpandRunsFn {     // grl2plain: symbol of every BWT position through the run-start bitmap
+    const u32 *rsym; const u64 *rw; const idx_t *rb; u32 *out; idx_t *idx;
+    GRL_DEV void operator()(u64 i) const { out[i] = rsym[rank1(rw, rb, i + 1) - 1]; idx[i] = (idx_t)i; }
+};
+struct LfScatterFn {      // LF[order[j]] = j  (order = stable sort of positions by symbol)
+    const idx_t *order; idx_t *lf;
+    GRL_DEV void operator()(u64 j) const { lf[order[j]] = (idx_t)j; }
+};
+struct InvertLenFn {      // string i: backward LF walk from row i until its own terminator comes back
+    const u32 *bwt; const idx_t *lf; u32 sep; idx_t *slen;
+    GRL_DEV void operator()(u64 i) const {
+        u64 row = i, l = 1;
+        for (u32 c = bwt[row]; c != sep; c = bwt[row]) { l++; row = lf[row]; }
+        slen[i] = (idx_t)l;
+    }
+};
+template <class cell_t>
+struct SymOut {             // the cell a walk writes for symbol c (alpha: the values of a compacted alphabet, the walk runs on their ranks; null: the symbols themselves)
+    const u64 *alpha;
+    GRL_DEV cell_t operator()(u32 c) const { return alpha ? (cell_t)alpha[c] : (cell_t)c; }
+};
+template <class cell_t>
+struct InvertWriteFn {
+    const u32 *bwt; const idx_t *lf; const idx_t *off; u32 sep; cell_t *text; SymOut<cell_t> val;
+    GRL_DEV void operator()(u64 i) const {
+        u64 end = off[i + 1] - 1, row = i;
+        text[end] = val(sep);
+        for (u32 c = bwt[row]; c != sep; c = bwt[row]) { text[--end] = val(c); row = lf[row]; }
+    }
+};
+
+// ---- the same inversion indexed by RUNS (scripts/fm_index.h:79-83 computes LF from the symbol's rank; over the run-length
+// BWT the rank of a run's first symbol is a prefix sum over the RUNS of that symbol).  A stable sort of the runs by symbol and
+// a scan of their lengths in that order give LF of every run start; LF inside a run is linear, so one record per run --
+// (LF(start) - start, symbol) -- and the run-start bit-vector replace the per-position arrays: 28-36 bytes per RUN instead
+// of 20-36 per symbol, which is what lets the 10 GB headline image (1.66 G runs, 10^10 symbols) round-trip on one device.
+template <int IB> struct RunRecT;
+template <> struct alignas(8) RunRecT<4> { u32 delta; u32 sym; };
+template <> struct alignas(16) RunRecT<8> { u64 delta; u32 sym; u32 pad; };
+typedef RunRecT<sizeof(idx_t)> RunRec;
+struct RankCellFn {
+    const u64 *words; const idx_t *base; RankCell *rc;
+    GRL_DEV void operator()(u64 i) const { rc[i] = RankCell{words[i], (u64)base[i]}; }
+};
+struct IotaFn {
+    idx_t *v;
+    GRL_DEV void operator()(u64 i) const { v[i] = (idx_t)i; }
+};
+struct RunOrderLenIn {    // length of the j-th run in (symbol, position) order
+    const idx_t *rlen; const idx_t *order;
+    GRL_DEV idx_t operator()(u64 j) const { return rlen[order[j]]; }
+};
+struct RunLfEmitFn {      // emit side of that scan: ex = LF of the run's first position
+    static constexpr bool kWaveEmit = false;
+    const idx_t *order; const idx_t *rpos; const u32 *rsym; RunRec *rec;
+    GRL_DEV void operator()(u64 j, idx_t ex, idx_t) const {
+        const u64 k = order[j];
+        RunRec r;
+        r.delta = (decltype(r.delta))(ex - rpos[k]);      // (wraps below zero: row + delta is taken modulo 2^bits)
+        r.sym = rsym[k];
+        rec[k] = r;
+    }
+};
+GRL_DEV u64 run_of_row(const RankCell *rc, u64 row) {      // index of the run holding BWT position row
+    const RankCell c = rc[(row + 1) >> 6];
+    return c.b + (u64)__builtin_popcountll(c.w & ((1ull << ((row + 1) & 63)) - 1ull)) - 1;
+}
+// LF of any row, for the row's OWN symbol: the run-start bit-vector with the rank of every word, and one record per run.
+struct LfRows {
+    const RankCell *rc; const RunRec *rec;
+    GRL_DEV RunRec at(idx_t row) const { return rec[run_of_row(rc, (u64)row)]; }
+    GRL_DEV static idx_t next(idx_t row, const RunRec &r) { return (idx_t)(row + (idx_t)r.delta); }      // (modulo 2^bits: RunLfEmitFn)
+};
+struct RunInvertLenFn {
+    LfRows lf; u32 sep; idx_t *slen;
+    GRL_DEV void operator()(u64 i) const {
+        idx_t row = (idx_t)i;
+        u64 l = 1;
+        RunRec r = lf.at(row);
+        while (r.sym != sep) { l++; row = LfRows::next(row, r); r = lf.at(row); }
+        slen[i] = (idx_t)l;
+    }
+};
+template <class cell_t>
+struct RunInvertWriteFn {
+    LfRows lf; const idx_t *off; u32 sep; cell_t *text; SymOut<cell_t> val;
+    GRL_DEV void operator()(u64 i) const {
+        u64 end = off[i + 1] - 1;
+        idx_t row = (idx_t)i;
+        text[end] = val(sep);
+        RunRec r = lf.at(row);
+        while (r.sym != sep) { text[--end] = val(r.sym); row = LfRows::next(row, r); r = lf.at(row); }
+    }
+};
+
+template <class cell_t>
+struct RunInvertTailFn {    // the last `tail` cells of string i (separator included), right-aligned in slot i of `tail` cells; the rest of the slot stays as it was
+    LfRows lf; u32 sep; u64 tail; cell_t *out; idx_t *got; SymOut<cell_t> val;
+    GRL_DEV void operator()(u64 i) const {
+        u64 end = (i + 1) * tail - 1, l = 1;
+        idx_t row = (idx_t)i;
+        out[end] = val(sep);
+        RunRec r = lf.at(row);
+        while (r.sym != sep && l < tail) { out[--end] = val(r.sym); l++; row = LfRows::next(row, r); r = lf.at(row); }
+        got[i] = (idx_t)l;
+    }
+};
+
+// ---- merging two images (grlbwt_merge_*): the interleave z holds one flag byte per merged row, 0 = the row is the
+// next unread row of A, 1 = of B; ra / rb hold one rank byte per row of A / B (the rank of the row's symbol among the distinct
+// values of both images).
+struct MgExpandFn {        // one rank byte per row, through the run-start bitmap
+    const u32 *rrank; const u64 *rw; const idx_t *rb; u8 *out;
+    GRL_DEV void operator()(u64 i) const { out[i] = (u8)rrank[rank1(rw, rb, i + 1) - 1]; }
+};
+struct MgSplitFn {         // z[p] = p >= na: 0^na 1^(n - na) -- the first interleave, and the separator bucket of every round
+    u8 *z; u64 na;
+    GRL_DEV void operator()(u64 p) const { z[p] = p >= na ? (u8)1 : (u8)0; }
+};
+struct MgFlagPred {
+    const u8 *z;
+    GRL_DEV bool operator()(u64 p) const { return z[p] != 0; }
+};
+struct MgDiffIn {
+    const u8 *a, *b;
+    GRL_DEV u64 operator()(u64 p) const { return a[p] != b[p] ? 1ull : 0ull; }
+};
+struct MgSym {             // the merged symbol (a rank) of row p through the interleave as a bit-vector with ranks
+    const u8 *ra, *rb; const u64 *zw; const idx_t *zb;
+    GRL_DEV u32 operator()(u64 p) const {
+        const u64 b = rank1(zw, zb, p);                  // B-rows in front of p
+        return ((zw[p >> 6] >> (p & 63)) & 1ull) ? (u32)rb[b] : (u32)ra[p - b];
+    }
+};
+struct MgKeyFn {           // the serial form of a round: the merged symbols gathered as sort keys
+    MgSym s; u8 *key;
+    GRL_DEV void operator()(u64 p) const { key[p] = (u8)s(p); }
+};
+struct MgHeadPred {
+    MgSym s;
+    GRL_DEV bool operator()(u64 p) const { return p == 0 || s(p) != s(p - 1); }
+};
+struct MgHeadFn {          // for_each_set_bit over the run heads: run `ord` starts at row p
+    MgSym s; u32 *sym; idx_t *start;
+    GRL_DEV void operator()(u64 p, u64 ord) const { sym[ord] = s(p); start[ord] = (idx_t)p; }
+};
+
+// ---- counting and locating patterns: one step past scripts/fm_index.h, which stops at lf().  RunRec answers LF for a row's OWN
+// symbol; a backward search needs rank_c(p), the number of c in BWT[0, p), for any c.  The runs in (symbol, position) order --
+// the order the sort above makes -- answer it by binary search: key[j] = (symbol, start) of the j-th run in that order,
+// slf[j] = symbols in the runs before it (slf[R] = n), so slf at the first run of c is C[c], the symbols smaller than c.
+template <int IB> struct FmKeyT;
+template <> struct FmKeyT<4> {                 // symbol << 32 | start: one word while positions have 32 bits
+    u64 v;
+    GRL_DEV static FmKeyT make(u32 sym, u64 start) { return FmKeyT{(u64)sym << 32 | start}; }
+    GRL_DEV u32 sym() const { return (u32)(v >> 32); }
+    GRL_DEV u64 start() const { return v & 0xFFFFFFFFull; }
+    GRL_DEV bool below(u32 c, u64 p) const { return v < ((u64)c << 32 | p); }       // sorts in front of (c, p)
+};
+template <> struct alignas(16) FmKeyT<8> {
+    u64 st, sy;
+    GRL_DEV static FmKeyT make(u32 sym, u64 start) { return FmKeyT{start, (u64)sym}; }
+    GRL_DEV u32 sym() const { return (u32)sy; }
+    GRL_DEV u64 start() const { return st; }
+    GRL_DEV bool below(u32 c, u64 p) const { return sy < (u64)c || (sy == (u64)c && st < p); }
+};
+typedef FmKeyT<sizeof(idx_t)> FmKey;
+struct FmKeyEmitFn {      // RunLfEmitFn that also keeps the sorted order itself (rec may be null: no walk wanted)
+    static constexpr bool kWaveEmit = false;
+    const idx_t *order; const idx_t *rpos; const u32 *rsym; RunRec *rec; FmKey *key; idx_t *slf;
+    GRL_DEV void operator()(u64 j, idx_t ex, idx_t) const {
+        const u64 k = order[j];
+        key[j] = FmKey::make(rsym[k], (u64)rpos[k]);
+        slf[j] = ex;
+        if (rec) {
+            RunRec r;
+            r.delta = (decltype(r.delta))(ex - rpos[k]);
+            r.sym = rsym[k];
+            rec[k] = r;
+        }
+    }
+};
+struct FmHeadIn {         // 1 where a sorted run has another symbol than the run in front of it: their number is sigma
+    const FmKey *key;
+    GRL_DEV u64 operator()(u64 j) const { return j == 0 || key[j].sym() != key[j - 1].sym() ? 1ull : 0ull; }
+};
+struct FmNoTop {          // the search without a top level (the LDS one: prim::LdsTop)
+    GRL_DEV void narrow(u32, u64, u64 &, u64 &) const {}
+};
+// ONE step of the backward search for symbol c: both ends of [lo, hi) go from a row p to C[c] + rank_c(p).  j = the keys below
+// (c, p); the run in front of it, when it is a run of c, is the last run of c that starts before p and holds min(p - start, length)
+// of the symbols counted; otherwise no run of c starts before p and the answer is slf[j] = C[c].  Each lower bound halves
+// [a, b] at most 64 times; hi's starts at lo's (hi >= lo).
+template <class TOP>
+GRL_DEV void fm_step(const FmKey *key, const idx_t *slf, u64 R, const TOP &top, u32 c, u64 &lo, u64 &hi) {
+    u64 from = 0;
+    auto end = [&](u64 p) {
+        u64 a = from, b = R;
+        top.narrow(c, p, a, b);
+        for (int it = 0; it < 64 && a < b; it++) { const u64 mid = (a + b) >> 1; if (key[mid].below(c, p)) a = mid + 1; else b = mid; }
+        const u64 j = from = a;
+        u64 r = (u64)slf[j];
+        if (j > 0) {
+            const FmKey q = key[j - 1];
+            if (q.sym() == c) { const u64 base = (u64)slf[j - 1], len = r - base, in = p - q.start(); r = base + (in < len ? in : len); }
+        }
+        return r;
+    };
+    lo = end(lo);
+    hi = end(hi);
+}
+// pattern i = cells [off[i], off[i + 1]) of w bytes each, read as values; their symbols are the values themselves or, for an
+// image with a compacted alphabet, the ranks among alpha[0, sigma).  A value that is no symbol empties the range.
+struct FmCountFn {
+    typedef FmKey Key;
+    const FmKey *key; const idx_t *slf; u64 R, n;
+    const u64 *alpha; u64 sigma;
+    const void *cells; int w; const u64 *off; u64 *lo, *hi;
+    GRL_HD const FmKey *keys() const { return key; }
+    GRL_HD u64 n_keys() const { return R; }
+    GRL_DEV u64 cell(u64 x) const {
+        switch (w) {
+            case 1: return (u64)((const u8 *)cells)[x];
+            case 2: return (u64)((const u16 *)cells)[x];
+            case 4: return (u64)((const u32 *)cells)[x];
+            default: return ((const u64 *)cells)[x];
+        }
+    }
+    GRL_DEV bool code(u64 v, u32 &c) const {
+        if (!alpha) { c = (u32)v; return (v >> 32) == 0; }
+        u64 a = 0, b = sigma;
+        for (int it = 0; it < 64 && a < b; it++) { const u64 mid = (a + b) >> 1; if (alpha[mid] < v) a = mid + 1; else b = mid; }
+        c = (u32)a;
+        return a < sigma && alpha[a] == v;
+    }
+    template <class TOP>
+    GRL_DEV void operator()(u64 i, const TOP &top) const {
+        u64 a = 0, b = n;
+        const u64 x0 = off[i];
+        for (u64 x = off[i + 1]; x > x0 && a < b; x--) {       // (at most the pattern's cells)
+            u32 c;
+            if (!code(cell(x - 1), c)) { b = a; break; }
+            fm_step(key, slf, R, top, c, a, b);
+        }
+        if (a >= b) a = b = 0;
+        lo[i] = a; hi[i] = b;
+    }
+};
+struct FmCountPlainFn {   // the same through prim::for_each, without a top level
+    FmCountFn f;
+    GRL_DEV void operator()(u64 i) const { f(i, FmNoTop{}); }
+};
+struct FmOffsetsBadIn {
+    const u64 *off;
+    GRL_DEV u64 operator()(u64 i) const { return off[i] > off[i + 1] ? 1ull : 0ull; }
+};
+struct FmSepMisuseIn {    // cell x0 + k: the number of its pattern when it holds the separator and is not the pattern's last cell, else ~0
+    FmCountFn f; u64 sepval, x0, np;
+    GRL_DEV u64 operator()(u64 k) const {
+        const u64 x = x0 + k;
+        if (f.cell(x) != sepval) return ~0ull;
+        const u64 i = upper_bound<u64>(f.off, np + 1, x) - 1;      // off[i] <= x < off[i + 1]: empty patterns are stepped over
+        return x + 1 == f.off[i + 1] ? ~0ull : i;
+    }
+};
+// ---- longest matches and maximal exact matches (grlbwt_fm_match / grlbwt_fm_mems).  Ticket t is the query cell
+// x = x0 + t, at offset e inside its pattern: the greedy backward search from [0, n) over cells x, x - 1, ... keeps the last
+// non-empty range, so len is the largest L <= min(e + 1, max_len) such that the L cells ending at x occur in the collection
+// (occurring is monotone in L).  A cell that is no symbol, or the separator, ends the item: no match holds or crosses one.
+//   Loops: an item takes at most min(e + 1, max_len) steps, each one fm_step; begin's upper_bound halves n_patterns + 1 offsets.
+struct FmMatchFn {
+    typedef FmKey Key;
+    struct State { u64 x, lo, hi, len, cap; };
+    FmCountFn f; u64 sepval, x0, np, max_len; u64 *len, *lo, *hi;       // (lo and hi both null: the lengths alone)
+    GRL_HD const FmKey *keys() const { return f.key; }
+    GRL_HD u64 n_keys() const { return f.R; }
+    GRL_DEV bool begin(u64 t, State &st) const {
+        st.x = x0 + t;
+        const u64 i = upper_bound<u64>(f.off, np + 1, st.x) - 1;      // off[i] <= x < off[i + 1]: empty patterns are stepped over
+        st.cap = st.x - f.off[i] + 1;
+        if (max_len && max_len < st.cap) st.cap = max_len;
+        st.lo = 0; st.hi = f.n; st.len = 0;
+        return true;
+    }
+    template <class TOP>
+    GRL_DEV bool step(State &st, const TOP &top) const {
+        const u64 v = f.cell(st.x - st.len);
+        u32 c;
+        if (st.lo >= st.hi || v == sepval || !f.code(v, c)) return true;       // (an index of no symbol: nothing matches)
+        u64 a = st.lo, b = st.hi;
+        fm_step(f.key, f.slf, f.R, top, c, a, b);
+        if (a >= b) return true;
+        st.lo = a; st.hi = b; st.len++;
+        return st.len >= st.cap;
+    }
+    GRL_DEV bool step(State &st) const { return step(st, FmNoTop{}); }
+    GRL_DEV void end(u64 t, const State &st) const {
+        len[t] = st.len;
+        if (lo) { lo[t] = st.len ? st.lo : 0; hi[t] = st.len ? st.hi : 0; }
+    }
+};
+struct FmMatchLaneFn {    // the same, one lane per cell through prim::top_search (GRLBWT_FM_MATCH=l)
+    typedef FmKey Key;
+    FmMatchFn f;
+    GRL_HD const FmKey *keys() const { return f.keys(); }
+    GRL_HD u64 n_keys() const { return f.n_keys(); }
+    template <class TOP>
+    GRL_DEV void operator()(u64 t, const TOP &top) const {
+        FmMatchFn::State st;
+        f.begin(t, st);
+        while (!f.step(st, top)) {}
+        f.end(t, st);
+    }
+};
+struct FmLenCappedIn {
+    const u64 *len; u64 cap;
+    GRL_DEV u64 operator()(u64 t) const { return len[t] == cap ? 1ull : 0ull; }
+};
+// end e of a pattern closes a maximal match when its length is at least the floor and the next end's match is no longer:
+// L[e + 1] <= L[e] + 1 always (drop the last cell of that match), with equality exactly when this one extends to the right
+struct FmMemFlagIn {
+    const u64 *len, *off; u64 x0, np, floor;
+    GRL_DEV bool operator()(u64 t) const {
+        const u64 L = len[t];
+        if (L < floor) return false;
+        const u64 x = x0 + t, i = upper_bound<u64>(off, np + 1, x) - 1;
+        return x + 1 == off[i + 1] || len[t + 1] <= L;
+    }
+};
+struct FmMemEmitFn {      // prim::for_each_set_bit over those flags: entry `ord` is the match that ends at cell x0 + t
+    const u64 *len, *slo, *shi, *off; u64 x0, np; u64 *pat, *beg, *mlen, *lo, *hi;
+    GRL_DEV void operator()(u64 t, u64 ord) const {
+        const u64 x = x0 + t, i = upper_bound<u64>(off, np + 1, x) - 1, L = len[t];
+        pat[ord] = i; beg[ord] = x - off[i] + 1 - L; mlen[ord] = L;
+        if (lo) { lo[ord] = slo[t]; hi[ord] = shi[t]; }
+    }
+};
+// sid: string i's walk (RunInvertLenFn's) ends at the row r that holds its separator; that separator is the LF(r)-th of the
+// BWT.  The LF map of any image is a permutation, so a walk from one of the first k rows comes back to one of them after at
+// most n steps; the bound is there for an index that is not what it should be.
+struct FmSidLenFn {       // (slen, where an index extracts: the steps of string i's walk + the separator are its length; null: not wanted)
+    LfRows lf; u32 sep; u64 n; idx_t *sid, *slen; u32 *bad;
+    GRL_DEV void operator()(u64 i) const {
+        idx_t row = (idx_t)i;
+        u64 s = 0;
+        RunRec r = lf.at(row);
+        for (; s < n && r.sym != sep; s++) { row = LfRows::next(row, r); r = lf.at(row); }
+        if (r.sym != sep) { prim::atomic_max(bad, 1u); return; }
+        sid[(u64)LfRows::next(row, r)] = (idx_t)i;
+        if (slen) slen[i] = (idx_t)(s + 1);
+    }
+};
+struct FmRowBadIn {
+    const u64 *rows; u64 n;
+    GRL_DEV u64 operator()(u64 i) const { return rows[i] >= n ? 1ull : 0ull; }
+};
+struct FmLocateFn {       // row -> (string, offset): LF steps until the row's symbol is the separator, at most `lim` of them
+    LfRows lf; const idx_t *sid; u32 sep; u64 lim; const u64 *rows; u64 *str, *ofs;
+    GRL_DEV void operator()(u64 i) const {
+        idx_t row = (idx_t)rows[i];
+        u64 s = 0;
+        RunRec r = lf.at(row);
+        for (; s < lim && r.sym != sep; s++) { row = LfRows::next(row, r); r = lf.at(row); }
+        const bool found = r.sym == sep;
+        str[i] = found ? (u64)sid[(u64)LfRows::next(row, r)] : ~0ull;
+        ofs[i] = found ? s : ~0ull;
+    }
+};
+
+// ---- checkpointed LF walks.  The walks above run one lane per string, one dependent step per cell: their latency
+// is the longest string.  Cut at CHECKPOINT rows they become m = k + ceil(n / s) segments of about s = 2^b steps, which a list
+// ranking over the checkpoints puts back in order.  Rows [0, k) -- where the strings' walks start -- are checkpoints 0 .. k-1;
+// every block of s rows [j s, (j + 1) s) holds one more, checkpoint k + j, at j s + (mix(j) & (s - 1)) (reduced modulo the length
+// of the last, shorter block, so that every pick is a row).  A pick below k is void: that row is a head already.  LF is linear
+// inside a run, so a plain stride would correlate with the walks of a repetitive text: the pick is jittered by a fixed 64-bit
+// mixer.  Whether a row is a checkpoint, and which, is arithmetic: no array, no bit-vector.
+struct Checkpoints {
+    u64 n, k; u32 b;
+    GRL_HD static u64 mix(u64 j) {                         // (splitmix64)
+        u64 z = j + 0x9E3779B97F4A7C15ull;
+        z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+        z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+        return z ^ (z >> 31);
+    }
+    GRL_HD u64 blocks() const { return (n + (1ull << b) - 1) >> b; }
+    GRL_HD u64 count() const { return k + blocks(); }
+    GRL_HD u64 pick(u64 j) const {
+        const u64 s = 1ull << b, base = j << b, len = n - base < s ? n - base : s;
+        u64 off = mix(j) & (s - 1);
+        if (off >= len) off %= len;
+        return base + off;
+    }
+    GRL_HD u64 row_of(u64 c) const { return c < k ? c : pick(c - k); }
+    GRL_HD bool is_void(u64 c) const { return c >= k && pick(c - k) < k; }
+    GRL_HD u64 index_of(u64 row) const {                   // ~0: the row is no checkpoint (a row of [k, n) that is its block's pick is never void)
+        if (row < k) return row;
+        const u64 j = row >> b;
+        return pick(j) == row ? k + j : ~0ull;
+    }
+};
+static constexpr idx_t kCpNone = (idx_t)~(idx_t)0;        // no checkpoint / no string
+static constexpr idx_t kCpEnd = (idx_t)(kCpNone - 1);     // next[]: the segment ends its string
+// Phase A, one ticket per checkpoint c: LF steps from its row until the row reached is a checkpoint (next[c] = its number) or
+// holds the separator (next[c] = kCpEnd, and endcp[slot] = c for the slot FmSidLenFn computes: that separator's row among [0, k)).
+// seglen[c] = the steps.  A void checkpoint has next = none and no steps.  LF is a permutation and every row a walk starts at is a
+// checkpoint, so a walk is back at a checkpoint after at most n steps: the bound is there for an index that is not what it should be.
+struct CpSegFn {
+    struct State { idx_t row; u64 steps; idx_t to; };
+    LfRows lf; u32 sep; Checkpoints cp; idx_t *seglen, *next, *endcp; u32 *bad;
+    GRL_DEV bool begin(u64 c, State &st) const {
+        if (cp.is_void(c)) { seglen[c] = 0; next[c] = kCpNone; return false; }
+        st.row = (idx_t)cp.row_of(c); st.steps = 0; st.to = kCpNone;
+        return true;
+    }
+    GRL_DEV bool step(State &st) const {
+        const RunRec r = lf.at(st.row);
+        if (r.sym == sep) { st.to = kCpEnd; st.row = LfRows::next(st.row, r); return true; }
+        st.row = LfRows::next(st.row, r);
+        st.steps++;
+        const u64 ci = cp.index_of((u64)st.row);
+        if (ci != ~0ull) { st.to = (idx_t)ci; return true; }
+        return st.steps >= cp.n;
+    }
+    GRL_DEV void end(u64 c, const State &st) const {
+        seglen[c] = (idx_t)st.steps;
+        next[c] = st.to;
+        if (st.to == kCpEnd) endcp[(u64)st.row] = (idx_t)c;
+        else if (st.to == kCpNone) prim::atomic_max(bad, 1u);
+    }
+};
+// Phase B, list ranking by pointer jumping over prev.  ptr[c] = the checkpoint in front of c on its chain, acc[c] = the steps
+// between them; a head points at itself with 0 steps, a checkpoint nobody reaches at nothing.
+struct CpInitFn {
+    u64 k; idx_t *ptr, *acc;
+    GRL_DEV void operator()(u64 c) const { ptr[c] = c < k ? (idx_t)c : kCpNone; acc[c] = 0; }
+};
+struct CpPrevFn {         // prev[next[c]] = c: next is one-to-one (LF is a permutation), so every slot has one writer
+    const idx_t *next, *seglen; idx_t *ptr, *acc;
+    GRL_DEV void operator()(u64 c) const {
+        const idx_t d = next[c];
+        if (d == kCpNone || d == kCpEnd) return;
+        ptr[(u64)d] = (idx_t)c; acc[(u64)d] = seglen[c];
+    }
+};
+struct CpJumpFn {         // one round, from generation (p0, a0) to (p1, a1)
+    const idx_t *p0, *a0; idx_t *p1, *a1;
+    GRL_DEV void operator()(u64 c) const {
+        const idx_t p = p0[c];
+        if (p == kCpNone) { p1[c] = p; a1[c] = a0[c]; return; }
+        const idx_t q = p0[(u64)p];
+        p1[c] = q == kCpNone ? p : q;
+        a1[c] = q == kCpNone ? a0[c] : (idx_t)(a0[c] + a0[(u64)p]);
+    }
+};
+struct CpMovedIn {
+    const idx_t *p0, *p1;
+    GRL_DEV u64 operator()(u64 c) const { return p0[c] != p1[c] ? 1ull : 0ull; }
+};
+struct CpHeadFn {         // after the rounds: ptr[c] is c's string where it is a head, none elsewhere (a chain that is a cycle has none)
+    u64 k; idx_t *ptr; u64 *chain;
+    GRL_DEV void operator()(u64 c) const {
+        const idx_t p = ptr[c];
+        if (p != kCpNone && (u64)p >= k) ptr[c] = kCpNone;
+        else if (p != kCpNone) prim::atomic_add(&chain[(u64)p], (u64)1);
+    }
+};
+struct CpLenFn {          // string lengths from the chains' last checkpoints: dist + steps + the separator
+    const idx_t *endcp, *head, *dist, *seglen; idx_t *slen; u32 *bad;
+    GRL_DEV void operator()(u64 slot) const {
+        const u64 e = (u64)endcp[slot];
+        const idx_t h = head[e];
+        if (h == kCpNone) { prim::atomic_max(bad, 1u); return; }
+        slen[(u64)h] = (idx_t)(dist[e] + seglen[e] + 1);
+    }
+};
+// Phase C of the inverter: phase A's walk again, every segment writing its cells backwards from the position its rank gives
+template <class cell_t>
+struct CpWriteFn {
+    struct State { idx_t row; u64 pos, left; };
+    LfRows lf; u32 sep; Checkpoints cp; const idx_t *head, *dist, *seglen, *off; cell_t *text; SymOut<cell_t> val;
+    GRL_DEV bool begin(u64 c, State &st) const {
+        const idx_t h = head[c];
+        if (h == kCpNone) return false;
+        st.row = (idx_t)cp.row_of(c);
+        st.pos = (u64)off[(u64)h + 1] - 1 - (u64)dist[c];
+        st.left = (u64)seglen[c];
+        if (c < cp.k) text[st.pos] = val(sep);
+        return st.left != 0;
+    }
+    GRL_DEV bool step(State &st) const {
+        const RunRec r = lf.at(st.row);
+        text[--st.pos] = val(r.sym);
+        st.row = LfRows::next(st.row, r);
+        return --st.left == 0;
+    }
+    GRL_DEV void end(u64, const State &) const {}
+};
+// The store form of the write walk for u8 / u16 cells into an 8-byte aligned text (CpWriteFn otherwise): the cells of one aligned
+// 8-byte word of the text are collected in a register and stored as that word.  A segment's first and last word are shared with its neighbours' segments: what a lane holds of
+// a word it does not own whole goes out cell by cell.  [pos, top) is what the register holds; it never crosses a word.
+template <class cell_t>
+struct CpWritePackedFn {
+    static constexpr u64 kPer = 8 / sizeof(cell_t), kBits = 8 * sizeof(cell_t);
+    struct State { idx_t row; u64 pos, left, top, acc; };
+    CpWriteFn<cell_t> w;
+    GRL_DEV bool begin(u64 c, State &st) const {
+        typename CpWriteFn<cell_t>::State s;
+        const bool go = w.begin(c, s);
+        st.row = s.row; st.pos = s.pos; st.left = s.left; st.top = s.pos; st.acc = 0;
+        return go;
+    }
+    GRL_DEV bool step(State &st) const {
+        const RunRec r = w.lf.at(st.row);
+        --st.pos;
+        st.acc |= (u64)w.val(r.sym) << ((st.pos & (kPer - 1)) * kBits);
+        st.row = LfRows::next(st.row, r);
+        --st.left;
+        const bool bottom = (st.pos & (kPer - 1)) == 0;
+        if (bottom || st.left == 0) {
+            if (bottom && st.top - st.pos == kPer) *reinterpret_cast<u64 *>(w.text + st.pos) = st.acc;
+            else for (u64 q = st.pos; q < st.top; q++) w.text[q] = (cell_t)(st.acc >> ((q & (kPer - 1)) * kBits));      // (fewer than kPer cells)
+            st.top = st.pos; st.acc = 0;
+        }
+        return st.left == 0;
+    }
+    GRL_DEV void end(u64, const State &) const {}
+};
+template <class F>
+struct WalkSerialFn {     // the serial form of prim::walk_tickets: one item after the other through prim::for_each
+    F f;
+    GRL_DEV void operator()(u64 c) const {
+        typename F::State st;
+        if (!f.begin(c, st)) return;
+        while (!f.step(st)) {}
+        f.end(c, st);
+    }
+};
+// Phase C of the index: the string behind every separator from the chain ends, and per checkpoint the sample (string, offset of
+// the row's suffix in it)
+struct CpSidFn {
+    const idx_t *endcp, *head; idx_t *sid;
+    GRL_DEV void operator()(u64 slot) const { sid[slot] = head[(u64)endcp[slot]]; }
+};
+struct CpSampleFn {
+    const idx_t *head, *dist, *slen; idx_t *smp;
+    GRL_DEV void operator()(u64 c) const {
+        const idx_t h = head[c];
+        smp[2 * c] = h;
+        smp[2 * c + 1] = h == kCpNone ? kCpNone : (idx_t)(slen[(u64)h] - 1 - dist[c]);
+    }
+};
+// locate over an index with samples: the walk also stops at a checkpoint row; one met after t steps gives (string, offset + t).
+// A checkpoint without a string lies on a cycle of rows that holds no separator: the row has no position, as in FmLocateFn, whose
+// walk runs into its bound.  An offset above `lim` is suppressed: the contract is FmLocateFn's.
+struct FmLocateCpFn {
+    LfRows lf; const idx_t *sid, *smp; Checkpoints cp; u32 sep; u64 lim; const u64 *rows; u64 *str, *ofs;
+    GRL_DEV void operator()(u64 i) const {
+        idx_t row = (idx_t)rows[i];
+        u64 rs = ~0ull, ro = ~0ull;
+        for (u64 s = 0; s <= lim; s++) {
+            const u64 ci = cp.index_of((u64)row);
+            if (ci != ~0ull) {
+                const idx_t h = smp[2 * ci];
+                if (h != kCpNone) { const u64 o = (u64)smp[2 * ci + 1] + s; if (o <= lim) { rs = (u64)h; ro = o; } }
+                break;
+            }
+            const RunRec r = lf.at(row);
+            if (r.sym == sep) { rs = (u64)sid[(u64)LfRows::next(row, r)]; ro = s; break; }
+            row = LfRows::next(row, r);
+        }
+        str[i] = rs; ofs[i] = ro;
+    }
+};
+
+// ---- removing or keeping chosen strings (grlbwt_select_*).  The suffixes of string i are the rows on the LF chain
+// from row i to the row whose symbol is the separator; the chains of distinct strings are disjoint.  The walks set one bit per
+// chain row of the LISTED strings; the rows a run loses (or keeps) are then a difference of two ranks over those bits.
+struct SelListFn {        // the list as a set: bit s of a k-bit vector for every entry s
+    const u64 *ids; u64 *bits;
+    GRL_DEV void operator()(u64 i) const { const u64 s = ids[i]; prim::atomic_or(&bits[s >> 6], 1ull << (s & 63)); }
+};
+struct SelTicketFn {      // prim::for_each_set_bit over that vector: the distinct entries in ascending order
+    idx_t *tick;
+    GRL_DEV void operator()(u64 p, u64 ord) const { tick[ord] = (idx_t)p; }
+};
+GRL_DEV bool sel_listed(const u64 *bits, u64 s) { return (bits[s >> 6] >> (s & 63)) & 1ull; }
+// (several lanes share a word, hence the atomic; a row lies on one chain, so no bit is set twice, and nothing reads the result)
+GRL_DEV void sel_mark(u64 *mark, u64 row) { prim::atomic_or(&mark[row >> 6], 1ull << (row & 63)); }
+// Marking per string, one ticket per listed string: row = its number, then LF steps up to and including the row whose symbol is
+// the separator.  As in FmSidLenFn a walk from one of the first k rows meets that row after at most n steps whatever the image is;
+// the bound is there all the same.  steps[t] = the rows marked = the string's length, separator included.
+struct SelMarkFn {
+    struct State { idx_t row; u64 steps; bool found; };
+    LfRows lf; u32 sep; u64 n; const idx_t *tick; u64 *mark; idx_t *steps; u32 *bad;
+    GRL_DEV bool begin(u64 t, State &st) const { st.row = tick[t]; st.steps = 0; st.found = false; return true; }
+    GRL_DEV bool step(State &st) const {
+        sel_mark(mark, (u64)st.row);
+        const RunRec r = lf.at(st.row);
+        st.steps++;
+        if (r.sym == sep) { st.found = true; return true; }
+        st.row = LfRows::next(st.row, r);
+        return st.steps >= n;
+    }
+    GRL_DEV void end(u64 t, const State &st) const {
+        steps[t] = (idx_t)st.steps;
+        if (!st.found) prim::atomic_max(bad, 1u);
+    }
+};
+// Marking through checkpointed segments, one ticket per checkpoint (CpWriteFn's shape): the segments of listed strings mark
+// their seglen rows.  The row a segment ends at is either the next checkpoint's (that segment marks it) or the row whose symbol
+// is the separator, which CpSegFn does not count: the last step looks at that row and marks it where it holds the separator.  (A
+// checkpoint row that holds the separator is marked from both sides, by segments of the same string.)
+struct SelMarkCpFn {
+    struct State { idx_t row; u64 left; };
+    LfRows lf; u32 sep; Checkpoints cp; const idx_t *head, *seglen; const u64 *list; u64 *mark;
+    GRL_DEV bool begin(u64 c, State &st) const {
+        const idx_t h = head[c];
+        if (h == kCpNone || !sel_listed(list, (u64)h)) return false;
+        st.row = (idx_t)cp.row_of(c);
+        st.left = (u64)seglen[c];
+        return true;
+    }
+    GRL_DEV bool step(State &st) const {
+        const RunRec r = lf.at(st.row);
+        if (st.left == 0) {
+            if (r.sym == sep) sel_mark(mark, (u64)st.row);
+            return true;
+        }
+        sel_mark(mark, (u64)st.row);
+        st.row = LfRows::next(st.row, r);
+        st.left--;
+        return false;
+    }
+    GRL_DEV void end(u64, const State &) const {}
+};
+struct SelListedLenIn {   // the length of the t-th listed string (CpLenFn's slen)
+    const idx_t *tick, *slen;
+    GRL_DEV u64 operator()(u64 t) const { return (u64)slen[(u64)tick[t]]; }
+};
+struct SelSegStepsIn {    // the steps of checkpoint c's marking walk (0: not walked)
+    const idx_t *head, *seglen; const u64 *list;
+    GRL_DEV u64 operator()(u64 c) const {
+        const idx_t h = head[c];
+        return h != kCpNone && sel_listed(list, (u64)h) ? (u64)seglen[c] : 0ull;
+    }
+};
+struct SelRunLenFn {      // the rewrite: a run's length less the marked rows in it -- or those alone, to keep the listed strings
+    const idx_t *rpos; const u64 *mark; const idx_t *mbase; bool keep; idx_t *len;
+    GRL_DEV void operator()(u64 r) const {
+        const u64 a = (u64)rpos[r], b = (u64)rpos[r + 1], cnt = rank1(mark, mbase, b) - rank1(mark, mbase, a);
+        len[r] = (idx_t)(keep ? cnt : (b - a) - cnt);
+    }
+};
+
+// ---- extracting text ranges (grlbwt_fm_extract).  T[s] = the cells in front of string s, so (s, o) is the absolute
+// position T[s] + o.  The index keeps the INVERSE of its samples: xq = the absolute positions of the sampled rows, ascending, and
+// xc = the checkpoint of each (its row is cp.row_of).  The head of string s is a sample at T[s + 1] - 1, its separator's position,
+// so every cell of a string lies below a sample of that string, and one LF step from the row of position x reads cell x - 1.
+struct FmHeadSampleFn {   // without checkpoints the samples are the k heads: sorted as they come
+    const idx_t *T; idx_t *xq, *xc;
+    GRL_DEV void operator()(u64 s) const { xq[s] = (idx_t)(T[s + 1] - 1); xc[s] = (idx_t)s; }
+};
+struct FmCpSampleKeyFn {  // checkpoint c -> (absolute position, c); n, above every position, for a void checkpoint or one on no string's chain
+    Checkpoints cp; const idx_t *head, *dist, *T; idx_t *key, *val;
+    GRL_DEV void operator()(u64 c) const {
+        const idx_t h = head[c];
+        const bool has = h != kCpNone && !cp.is_void(c);
+        key[c] = has ? (idx_t)(T[(u64)h + 1] - 1 - dist[c]) : (idx_t)cp.n;
+        val[c] = (idx_t)c;
+    }
+};
+struct FmSampleValidIn {
+    const idx_t *key; u64 n;
+    GRL_DEV u64 operator()(u64 c) const { return (u64)key[c] != n ? 1ull : 0ull; }
+};
+struct FmLenOutFn {
+    const idx_t *T; u64 *len;
+    GRL_DEV void operator()(u64 s) const { len[s] = (u64)T[s + 1] - (u64)T[s]; }
+};
+struct FmExtractBadIn {   // the number of a range whose string is none, else ~0
+    const u64 *str; u64 k;
+    GRL_DEV u64 operator()(u64 i) const { return str[i] >= k ? i : ~0ull; }
+};
+// Range i of string s = str[i]: cells [b, e) with e clamped to the string's length, [B, E) in absolute positions.  The separator's
+// cell (E = T[s + 1]) is stored directly, the cells [B, E') in front of it are walked: E' = E - 1 there, E elsewhere.
+struct FmRange {
+    u64 B, E, Ew;         // Ew = E': (B < Ew: there is something to walk)
+    bool sep;
+};
+struct FmExtractPlan {
+    const idx_t *T, *xq; u64 ns; const u64 *str, *beg, *end;
+    GRL_DEV FmRange range(u64 i) const {
+        const u64 s = str[i], t0 = (u64)T[s], t1 = (u64)T[s + 1], len = t1 - t0;
+        const u64 e = end[i] < len ? end[i] : len, b = beg[i] < e ? beg[i] : e;      // (b >= e: empty)
+        FmRange r;
+        r.B = t0 + b; r.E = t0 + e;
+        r.sep = b < e && r.E == t1;
+        r.Ew = r.sep ? r.E - 1 : r.E;
+        return r;
+    }
+    GRL_DEV u64 first_above(u64 B) const { return upper_bound<idx_t>(xq, ns, (idx_t)B); }       // the first sample q > B
+};
+// The pieces of a range are the samples q with B < q <= q_top, q_top = the smallest sample >= E' (it exists, in the same string:
+// the head); cells = its length; steps = the cells walked + the steps q_top - E' its top piece takes before it writes.
+struct FmExtractPlanFn {
+    FmExtractPlan p; u64 *npiece, *ncell, *nstep;
+    GRL_DEV void operator()(u64 i) const {
+        const FmRange r = p.range(i);
+        u64 pieces = 0, steps = 0;
+        if (r.B < r.Ew) {
+            const u64 top = lower_bound<idx_t>(p.xq, p.ns, (idx_t)r.Ew);
+            pieces = top - p.first_above(r.B) + 1;
+            steps = (u64)p.xq[top] - r.B;
+        }
+        npiece[i] = pieces; ncell[i] = r.E - r.B; nstep[i] = steps;
+    }
+};
+template <class cell_t>
+struct FmExtractSepFn {   // the separator of every range that reaches its string's end
+    FmExtractPlan p; const u64 *ooff; cell_t *out; cell_t sepval;
+    GRL_DEV void operator()(u64 i) const {
+        const FmRange r = p.range(i);
+        if (r.sep) out[ooff[i] + (r.E - r.B) - 1] = sepval;
+    }
+};
+// One ticket per piece.  Piece j of range i (pscan[i] <= ticket < pscan[i + 1]) belongs to sample first_above(B) + j, at position
+// q; it writes the cells [lo, top), lo = B for j = 0 and the sample below q otherwise, top = min(q, E'), walking backwards from
+// q's row: q - top steps that store nothing (the top piece alone has any), then one store per step.
+//   Bounds, known before the launch: the steps of a piece are q - lo <= the gap between neighbouring samples <= n, and lo >= T[s]:
+//   the walk never steps from its string's first row.  A cell x of range i goes to ooff[i] + (x - B) < ooff[i + 1] <= n_cells, which
+//   the caller has checked against the capacity.
+template <class cell_t>
+struct FmExtractFn {
+    struct State { idx_t row; u64 skip, left, o; };
+    LfRows lf; Checkpoints cp; const idx_t *xc; FmExtractPlan p; u64 nr; const u64 *pscan, *ooff; cell_t *out; SymOut<cell_t> val;
+    GRL_DEV bool begin(u64 t, State &st) const {
+        const u64 i = upper_bound<u64>(pscan, nr + 1, t) - 1;       // (ranges without a piece are stepped over)
+        const u64 j = t - pscan[i];
+        const FmRange r = p.range(i);
+        const u64 x = p.first_above(r.B) + j;
+        const u64 q = (u64)p.xq[x], lo = j ? (u64)p.xq[x - 1] : r.B, top = q < r.Ew ? q : r.Ew;
+        st.row = (idx_t)cp.row_of((u64)xc[x]);
+        st.skip = q - top; st.left = top - lo;
+        st.o = ooff[i] + (top - r.B);
+        return true;                                                // (left >= 1: lo < top by the choice of the samples)
+    }
+    GRL_DEV bool step(State &st) const {
+        const RunRec r = lf.at(st.row);
+        st.row = LfRows::next(st.row, r);
+        if (st.skip) { st.skip--; return false; }
+        out[--st.o] = val(r.sym);
+        return --st.left == 0;
+    }
+    GRL_DEV void end(u64, const State &) const {}
+};
+
+struct Image {
+    // ---- opening an image: the one parse of the 16 header bytes, the one test of a cell width, the one dispatch on it -------
+    struct ImageHeader {
+        u64 sb, fb, R;
+        ImageRecs recs(const void *dev_image) const { return ImageRecs{(const u8 *)dev_image, (u32)sb, (u32)fb}; }
+    };
+    static ImageHeader image_header(const void *dev_image, u64 image_bytes) {
+        if (image_bytes < 16) throw prim::Error(-22, "not an .rl_bwt image");
+        u64 hdr[2];
+        prim::d2h(hdr, dev_image, 16);
+        if (hdr[0] == 0 || hdr[0] > 8 || hdr[1] == 0 || hdr[1] > 8 || (image_bytes - 16) % (hdr[0] + hdr[1]))
+            throw prim::Error(-22, "bad .rl_bwt header");
+        return ImageHeader{hdr[0], hdr[1], (image_bytes - 16) / (hdr[0] + hdr[1])};
+    }
+    static void check_cell_bytes(int w, const char *who = nullptr) {      // (who: the prefix of the caller's messages, if it has one)
+        if (!(w == 1 || w == 2 || w == 4 || w == 8)) throw prim::Error(-22, who ? std::string(who) + ": bad cell width" : std::string("bad cell width"));
+    }
+    // f(cell_t()) for the cell type of a checked width: `[&](auto c) { typedef decltype(c) cell_t; ... }`
+    template <class F>
+    static auto with_cell(int cell_bytes, F f) {
+        switch (cell_bytes) {
+            case 1: return f(u8());
+            case 2: return f(u16());
+            case 4: return f(u32());
+            default: return f(u64());
+        }
+    }
+    // ---- consumers of the .rl_bwt image (validation): grl2plain + reverse_bwt on the device ----------
+    // Rebuilds the collection (strings in input order) from an image in device memory.
+    // The run symbols of an image are read as 64 bits.  Where the largest is 2^30 or more they are compacted like a wide text
+    // (R values, not n): the LF walk runs on ranks and the write functors put alpha[rank] into the text.
+    struct WideSyms { DBuf<u32> ranks; DBuf<u64> alpha; };
+    static void image_symbols(const ImageRecs &in, u64 R, int cell_bytes, WideSyms &W, const char *who = "inversion") {
+        const u64 mx = prim::reduce_max<u64>(R, ImageSymIn{in}, "inv.max_sym");
+        if (cell_bytes < 8 && (mx >> (8 * cell_bytes))) throw prim::Error(-22, std::string(who) + ": the image's largest symbol does not fit the cell width");
+        if (mx < (1ull << 30)) return;
+        DBuf<u64> s64(R);
+        prim::for_each(R, UnpackSymFn{in, s64.p}, "inv.unpack_syms");
+        W.ranks.alloc(R);
+        alphabet_compact<u64>(s64.p, R, mx, W.ranks.p, W.alpha);
+    }
+    // A record of length zero contributes nothing (the reference's reader, bwt_io.h, just loops over the records; split_runs
+    // writes such records in front of a piece that starts on a block boundary).  The consumers that look a POSITION up find its
+    // run through one bit per run START, which an empty record would share with its successor -- every later position would
+    // read the symbol one record too early.  They drop the empty records first: flag scan + compacting copy, and nothing at
+    // all where the shortest record is not empty (every image the engine builds).  Returns the number of records kept.
+    // `who` prefixes the labels of the three kernels ("image" or "merge").
+    template <class sym_t>
+    static u64 drop_empty_runs(DBuf<sym_t> &rsym, DBuf<idx_t> &rlen, u64 R, const char *who = "image") {
+        const std::string w(who);
+        if (R == 0 || prim::reduce_min<u64>(R, IdxIn64{rlen.p}, (w + ".min_run").c_str()) != 0) return R;
+        DBuf<idx_t> dst(R + 1);
+        const u64 kept = (u64)prim::exclusive_scan<idx_t>(R, NonEmptyIn{rlen.p}, dst.p, true, (w + ".nonempty").c_str());
+        DBuf<sym_t> s2(kept);
+        DBuf<idx_t> l2(kept);
+        prim::for_each(R, KeepRunsFn<sym_t>{rsym.p, rlen.p, dst.p, s2.p, l2.p}, (w + ".drop_empty").c_str());
+        rsym = std::move(s2);
+        rlen = std::move(l2);
+        return kept;
+    }
+    template <class T>
+    static void d2d_copy(T *dst, const T *src, u64 n) { prim::d2d(dst, src, n * sizeof(T)); }
+    // the run-indexed form (functor block "the same inversion indexed by RUNS")
+    // The runs of an image as the inverter and the FM index need them.  run_index_load: the non-empty records as arrays, their
+    // start positions, the separator and the number of strings.  run_index_lf: the runs in (symbol, position) order and the scan
+    // of their lengths in that order -- LF of every run start -- kept in one or both of two forms, after which the arrays go:
+    //   walk    rc + rec: the run-start bit-vector with ranks and (LF(start) - start, symbol) per run: LF of any row of the BWT
+    //   search  key + slf: (symbol, start) and the scan itself in sorted order: the rank of ANY symbol in front of any row
+    struct RunIndex {
+        u64 R = 0, n = 0, k = 0;
+        u32 sep = 0, mx = 0;
+        DBuf<u32> rsym;
+        DBuf<idx_t> rlen, rpos;
+        DBuf<RankCell> rc;
+        DBuf<RunRec> rec;
+        DBuf<FmKey> key;
+        DBuf<idx_t> slf;
+        LfRows lf() const { return LfRows{rc.p, rec.p}; }
+    };
+    static void run_index_load(const ImageRecs &in, u64 R, const WideSyms &W, RunIndex &X) {
+        X.rsym.alloc(R); X.rlen.alloc(R);
+        prim::for_each(R, UnpackRunsFn<u32>{in, X.rsym.p, X.rlen.p}, "inv.unpack");
+        if (W.alpha.p) d2d_copy(X.rsym.p, W.ranks.p, R);
+        X.R = R = drop_empty_runs(X.rsym, X.rlen, R);
+        X.rpos.alloc(R + 1);
+        X.n = (u64)prim::exclusive_scan<idx_t>(R, IdxIn<idx_t>{X.rlen.p}, X.rpos.p, true, "inv.positions");
+        X.sep = prim::reduce_min<u32>(R, PtrU32In{X.rsym.p}, "inv.sep");
+        X.mx = prim::reduce_max<u32>(R, PtrU32In{X.rsym.p}, "inv.max");
+        X.k = prim::reduce_sum<u64>(R, SepLenIn{X.rsym.p, X.rlen.p, X.sep}, "inv.nstrings");      // strings = separators
+    }
+    static void run_index_lf(RunIndex &X, bool walk, bool search, bool keep_runs = false) {
+        const u64 R = X.R, n = X.n;
+        if (walk) {      // run-start bit-vector with the rank of every word beside it
+            RankBits rb;
+            build_rankbits(rb, X.rpos.p, R, n + 1, "inv.runbits");
+            const u64 nw = (n + 1) / 64 + 2;
+            X.rc.alloc(nw);
+            prim::for_each(nw, RankCellFn{rb.words.p, rb.base.p, X.rc.p}, "inv.rankcells");
+            X.rec.alloc(R);
+        }
+        if (search) { X.key.alloc(R); X.slf.alloc(R + 1); }
+        {
+            DBuf<u32> k2(R), k3(R);
+            DBuf<idx_t> ia(R), ib(R);
+            d2d_copy(k2.p, X.rsym.p, R);
+            prim::for_each(R, IotaFn{ia.p}, "inv.iota");
+            int bits = (int)bitlen64(X.mx);
+            if (bits < 1) bits = 1;
+            const int res = prim::sort_pairs<u32, idx_t>(k2.p, ia.p, k3.p, ib.p, R, 0, bits, "inv.lf_sort");
+            const idx_t *order = res ? ib.p : ia.p;
+            const u64 tot = search ? (u64)prim::exclusive_scan_emit<idx_t>(R, RunOrderLenIn{X.rlen.p, order}, FmKeyEmitFn{order, X.rpos.p, X.rsym.p, X.rec.p, X.key.p, X.slf.p}, "fm.keys")
+                                   : (u64)prim::exclusive_scan_emit<idx_t>(R, RunOrderLenIn{X.rlen.p, order}, RunLfEmitFn{order, X.rpos.p, X.rsym.p, X.rec.p}, "inv.lf");
+            if (tot != n) throw prim::Error(-71, "inversion: run lengths do not add up");
+        }
+        if (search) { const idx_t total = (idx_t)n; prim::h2d(X.slf.p + R, &total, sizeof(total)); }
+        if (!keep_runs) { X.rsym.release(); X.rlen.release(); X.rpos.release(); }
+    }
+    // the position-indexed form: the BWT expanded to one symbol per position, LF as an array over them
+    template <class cell_t>
+    static u64 invert_t(const ImageRecs &in, u64 R, cell_t *text_out, u64 capacity, const WideSyms &W) {
+        RunIndex X;
+        run_index_load(in, R, W, X);
+        const u64 n = X.n, k = X.k;
+        const u32 sep = X.sep;
+        if (n > capacity) throw prim::Error(-22, "inversion: output buffer too small");
+        RankBits rb;
+        build_rankbits(rb, X.rpos.p, X.R, n + 1, "inv.runbits");
+        DBuf<u32> bwt(n), k2(n);
+        DBuf<idx_t> ia(n), ib(n), lf(n);
+        prim::for_each(n, ExpandRunsFn{X.rsym.p, rb.words.p, rb.base.p, bwt.p, ia.p}, "inv.expand");          // grl2plain
+        d2d_copy(k2.p, bwt.p, n);
+        DBuf<u32> k3(n);
+        const int res = prim::sort_pairs<u32, idx_t>(k2.p, ia.p, k3.p, ib.p, n, 0, std::max((int)bitlen64(X.mx), 1), "inv.lf_sort");
+        prim::for_each(n, LfScatterFn{res ? ib.p : ia.p, lf.p}, "inv.lf");
+        k2.release(); k3.release();
+        DBuf<idx_t> slen(k + 1);
+        prim::for_each(k, InvertLenFn{bwt.p, lf.p, sep, slen.p}, "inv.lengths");
+        const u64 tot = (u64)prim::exclusive_scan<idx_t>(k, IdxIn<idx_t>{slen.p}, slen.p, true, "inv.offsets");
+        if (tot != n) throw prim::Error(-71, "inversion: string lengths do not add up to the BWT length");
+        prim::for_each(k, InvertWriteFn<cell_t>{bwt.p, lf.p, slen.p, sep, text_out, {W.alpha.p}}, "inv.write");
+        prim::sync();
+        return n;
+    }
+    template <class cell_t>
+    static u64 invert_runs_t(const ImageRecs &in, u64 R, cell_t *text_out, u64 capacity, const WideSyms &W, u64 tail = 0, u64 *n_strings_out = nullptr) {
+        RunIndex X;
+        run_index_load(in, R, W, X);
+        const u64 n = X.n;
+        if (!tail && n > capacity) throw prim::Error(-22, "inversion: output buffer too small");
+        run_index_lf(X, true, false);
+        const u64 k = X.k;
+        const u32 sep = X.sep;
+        const LfRows lf = X.lf();
+        if (tail) {
+            // the ends of the strings only (collections whose strings are too long to walk in a test's time -- 100
+            // strings of 249 M cells are 249 M dependent steps each): `tail` LF steps per string from its terminator's row
+            if (k * tail > capacity) throw prim::Error(-22, "inversion: output buffer too small");
+            DBuf<idx_t> got(k);
+            prim::for_each(k, RunInvertTailFn<cell_t>{lf, sep, tail, text_out, got.p, {W.alpha.p}}, "inv.tails");
+            prim::sync();
+            if (n_strings_out) *n_strings_out = k;
+            return (u64)prim::reduce_sum<u64>(k, IdxIn<idx_t>{got.p}, "inv.tails");
+        }
+        DBuf<idx_t> slen(k + 1);
+        prim::for_each(k, RunInvertLenFn{lf, sep, slen.p}, "inv.lengths");
+        const u64 tot = (u64)prim::exclusive_scan<idx_t>(k, IdxIn<idx_t>{slen.p}, slen.p, true, "inv.offsets");
+        if (tot != n) throw prim::Error(-71, "inversion: string lengths do not add up to the BWT length");
+        prim::for_each(k, RunInvertWriteFn<cell_t>{lf, slen.p, sep, text_out, {W.alpha.p}}, "inv.write");
+        prim::sync();
+        return n;
+    }
+
+    // ---- checkpointed LF walks (functor block "checkpointed LF walks") -------------------------------------
+    // lf_checkpoints: phases A and B on the rc + rec arrays run_index_lf(X, true, ...) makes.  Scratch: six idx_t arrays of m
+    // (seglen, next, two generations of (ptr, acc)) and two per string.  On return head[c] / dist[c] are c's string and the LF
+    // steps from that string's end row to c, slen[i] is the length of string i (separator included) and endcp[j] the checkpoint
+    // whose segment ends at the j-th separator.
+    //   Loops: the segment walks are bounded by n steps each; the pointer jumping runs a counted number of rounds, at most
+    //   ceil(log2 m), and ends early when a reduce says that no pointer moved; nothing waits for another thread.
+    struct WalkInfo { u64 k = 0, m = 0, b = 0, longest_segment = 0, longest_chain = 0, jump_rounds = 0, lanes = 0, refills = 0, scratch_bytes = 0, sample_bytes = 0; };
+    static constexpr bool kWalkPackedStores(char sw) { return sw != 'c'; }      // the store form of the write walk: words won
+    static constexpr int kDefaultSampleBits = 8;      // what sample_bits = 0 means
+    static int sample_bits_of(int b) {
+        if (b < 0 || b > 20) throw prim::Error(-22, "checkpointed walk: sample_bits is 0 (the default) or 1 to 20");
+        return b ? b : kDefaultSampleBits;
+    }
+    struct CpRank {
+        Checkpoints cp{0, 0, 0};
+        DBuf<idx_t> seglen, next, head, dist, ptr2, acc2, endcp, slen;
+    };
+    template <class F>
+    static void walk(u64 m, F f, WalkInfo &wi, const char *name) {
+#ifdef GRLBWT_PRIM_HIP
+        DBuf<u64> ctr(2);
+        const prim::WalkStats ws = prim::walk_tickets(m, f, ctr.p, name);
+        wi.lanes = ws.lanes; wi.refills = ws.refills;
+#else
+        prim::for_each(m, WalkSerialFn<F>{f}, name);
+        wi.lanes = m; wi.refills = 0;
+#endif
+    }
+    static void lf_checkpoints(const LfRows &lf, u64 n, u64 k, u32 sep, int b, int bad_code, CpRank &C, WalkInfo &wi) {
+        const Checkpoints cp{n, k, (u32)b};
+        const u64 m = cp.count();
+        if (m >= (u64)kCpEnd) throw prim::Error(-75, "checkpointed walk: more checkpoints than positions of this width can number");
+        C.cp = cp;
+        wi.k = k; wi.m = m; wi.b = (u64)b;
+        wi.scratch_bytes = (6 * m + 2 * k + 1) * sizeof(idx_t) + k * 8;
+        C.seglen.alloc(m); C.next.alloc(m); C.head.alloc(m); C.dist.alloc(m); C.ptr2.alloc(m); C.acc2.alloc(m);
+        C.endcp.alloc(k); C.slen.alloc(k + 1);
+        DBuf<u32> bad(1);
+        bad.zero();
+        walk(m, CpSegFn{lf, sep, cp, C.seglen.p, C.next.p, C.endcp.p, bad.p}, wi, "cp.segments");
+        if (bad.get(0)) throw prim::Error(bad_code, "checkpointed walk: a segment met no checkpoint in n steps: not the BWT of a collection");
+        wi.longest_segment = prim::reduce_max<u64>(m, IdxIn64{C.seglen.p}, "cp.longest");
+        prim::for_each(m, CpInitFn{k, C.head.p, C.dist.p}, "cp.init");
+        prim::for_each(m, CpPrevFn{C.next.p, C.seglen.p, C.head.p, C.dist.p}, "cp.prev");
+        const u64 cap = m > 1 ? (u64)bitlen64(m - 1) : 0;       // ceil(log2 m)
+        for (u64 r = 0; r < cap; r++) {
+            prim::for_each(m, CpJumpFn{C.head.p, C.dist.p, C.ptr2.p, C.acc2.p}, "cp.jump");
+            wi.jump_rounds++;
+            const u64 moved = prim::reduce_sum<u64>(m, CpMovedIn{C.head.p, C.ptr2.p}, "cp.moved");
+            std::swap(C.head, C.ptr2);
+            std::swap(C.dist, C.acc2);
+            if (!moved) break;
+        }
+        C.ptr2.release(); C.acc2.release(); C.next.release();
+        DBuf<u64> chain(k);
+        chain.zero();
+        prim::for_each(m, CpHeadFn{k, C.head.p, chain.p}, "cp.heads");
+        wi.longest_chain = prim::reduce_max<u64>(k, CellIn<u64>{chain.p}, "cp.chains");
+        C.slen.zero();
+        prim::for_each(k, CpLenFn{C.endcp.p, C.head.p, C.dist.p, C.seglen.p, C.slen.p, bad.p}, "cp.lengths");
+        if (bad.get(0)) throw prim::Error(bad_code, "checkpointed walk: a string's end lies on no string's chain: not the BWT of a collection");
+    }
+    template <class cell_t>
+    static u64 invert_checkpointed_t(const ImageRecs &in, u64 R, cell_t *text_out, u64 capacity, const WideSyms &W, int b, WalkInfo &wi) {
+        RunIndex X;
+        run_index_load(in, R, W, X);
+        const u64 n = X.n;
+        if (n > capacity) throw prim::Error(-22, "inversion: output buffer too small");
+        run_index_lf(X, true, false);
+        CpRank C;
+        lf_checkpoints(X.lf(), n, X.k, X.sep, b, -71, C, wi);
+        const u64 tot = (u64)prim::exclusive_scan<idx_t>(X.k, IdxIn<idx_t>{C.slen.p}, C.slen.p, true, "inv.offsets");
+        if (tot != n) throw prim::Error(-71, "inversion: string lengths do not add up to the BWT length");
+        const CpWriteFn<cell_t> wf{X.lf(), X.sep, C.cp, C.head.p, C.dist.p, C.seglen.p, C.slen.p, text_out, {W.alpha.p}};
+        bool packed = false;
+        if constexpr (sizeof(cell_t) <= 2) packed = kWalkPackedStores(prim::sw().dev_walk_stores) && ((uintptr_t)text_out & 7) == 0;
+        if constexpr (sizeof(cell_t) <= 2) { if (packed) walk(wi.m, CpWritePackedFn<cell_t>{wf}, wi, "cp.write_packed"); }
+        if (!packed) walk(wi.m, wf, wi, "cp.write");
+        prim::sync();
+        return n;
+    }
+    static u64 invert_image_checkpointed(const void *dev_image, u64 image_bytes, int cell_bytes, int sample_bits, void *dev_text_out, u64 capacity_cells, WalkInfo &wi) {
+        const int b = sample_bits_of(sample_bits);
+        const ImageHeader h = image_header(dev_image, image_bytes);
+        const ImageRecs in = h.recs(dev_image);
+        check_cell_bytes(cell_bytes);
+        WideSyms W;
+        image_symbols(in, h.R, cell_bytes, W);
+        return with_cell(cell_bytes, [&](auto c) {
+            typedef decltype(c) cell_t;
+            return invert_checkpointed_t<cell_t>(in, h.R, (cell_t *)dev_text_out, capacity_cells, W, b, wi);
+        });
+    }
+
+    // the last `tail` cells of every string (slot i of `tail` cells holds string i's end, right-aligned); returns the cells written
+    static u64 invert_image_tails(const void *dev_image, u64 image_bytes, int cell_bytes, u64 tail, void *dev_out, u64 capacity_cells, u64 *n_strings_out) {
+        if (image_bytes < 16 || tail == 0) throw prim::Error(-22, "not an .rl_bwt image, or no tail length");
+        const ImageHeader h = image_header(dev_image, image_bytes);
+        const ImageRecs in = h.recs(dev_image);
+        check_cell_bytes(cell_bytes);
+        WideSyms W;
+        image_symbols(in, h.R, cell_bytes, W);
+        return with_cell(cell_bytes, [&](auto c) {
+            typedef decltype(c) cell_t;
+            return invert_runs_t<cell_t>(in, h.R, (cell_t *)dev_out, capacity_cells, W, tail, n_strings_out);
+        });
+    }
+
+    static u64 invert_image(const void *dev_image, u64 image_bytes, int cell_bytes, void *dev_text_out, u64 capacity_cells, u64 n_total_hint = 0) {
+        const ImageHeader h = image_header(dev_image, image_bytes);
+        const ImageRecs in = h.recs(dev_image);
+        check_cell_bytes(cell_bytes);
+        WideSyms W;
+        image_symbols(in, h.R, cell_bytes, W);
+        // Two index forms.  Per POSITION (LF array: one gather per symbol of a string, (12 + 3 * sizeof(idx_t)) bytes per symbol
+        // while it is built) when that fits the device comfortably; per RUN (two dependent gathers per symbol, 30-50 bytes per
+        // run) otherwise -- the 10 GB headline image needs 360 GB in the first form and ~100 GB in the second.
+        // GRLBWT_INVERT=runs|positions forces one (the tests take both on small inputs).
+        bool by_runs = (n_total_hint ? n_total_hint : capacity_cells) * (12 + 3 * (u64)sizeof(idx_t)) > prim::mem_available() / 2;
+        if (prim::sw().invert) by_runs = prim::sw().invert == 'r';
+        return with_cell(cell_bytes, [&](auto c) {
+            typedef decltype(c) cell_t;
+            return by_runs ? invert_runs_t<cell_t>(in, h.R, (cell_t *)dev_text_out, capacity_cells, W) : invert_t<cell_t>(in, h.R, (cell_t *)dev_text_out, capacity_cells, W);
+        });
+    }
+
+    // ---- the FM index over the runs of an image (grlbwt_fm_*; functor block "counting and locating patterns") ----------------
+    struct ExtractInfo { u64 ranges = 0, pieces = 0, cells = 0, steps = 0, lanes = 0, refills = 0; };      // of the last fm_extract
+    struct MatchInfo { u64 patterns = 0, cells = 0, matched = 0, longest = 0, capped = 0, mems = 0, lanes = 0, refills = 0; };
+    struct FmIndex {
+        u64 n = 0, R = 0, k = 0, sigma = 0, sepval = 0;
+        u32 sep = 0, top_entries = 0;
+        bool locate = false;
+        DBuf<FmKey> key;
+        DBuf<idx_t> slf;
+        DBuf<u64> alpha;          // the values of a compacted alphabet (null: the symbols are the values)
+        DBuf<RankCell> rc;        // locate: LF of any row (LfRows) and the string behind every separator
+        DBuf<RunRec> rec;
+        DBuf<idx_t> sid;
+        LfRows lf() const { return LfRows{rc.p, rec.p}; }
+        bool checkpoints = false; // locate with samples: (string, offset) of every checkpoint row, two idx_t each
+        Checkpoints cp{0, 0, 0};
+        DBuf<idx_t> smp;
+        WalkInfo walk;
+        bool extract = false;     // extract: the strings' start positions T (k + 1) and the inverse of the samples, (position, checkpoint) by position
+        u64 maxval = 0;           // (the largest symbol's value)
+        DBuf<idx_t> T, xq, xc;
+        mutable ExtractInfo xinfo;
+        mutable MatchInfo minfo;  // of the last fm_match / fm_mems
+        u64 extract_bytes() const { return (T.n + xq.n + xc.n) * sizeof(idx_t); }
+        u64 bytes() const {
+            return key.n * sizeof(FmKey) + slf.n * sizeof(idx_t) + alpha.n * 8 + rc.n * sizeof(RankCell) + rec.n * sizeof(RunRec) + sid.n * sizeof(idx_t) +
+                   smp.n * sizeof(idx_t) + extract_bytes();
+        }
+    };
+    // What the locate structures may take while they are made: half of the free device memory (a quarter byte per symbol for the
+    // bit-vector and its ranks, a word per string).  The serial stand-in, which walks the strings one after the other, stops at 256 MB.
+    static u64 fm_locate_budget() { return prim::kIsDevice ? prim::mem_available() / 2 : (u64)1 << 28; }
+    static void fm_create(const void *dev_image, u64 image_bytes, bool locate, int top_bits, FmIndex &F, bool checkpoints = false, int sample_bits = 0,
+                          bool extract = false) {
+        if (extract && !locate) throw prim::Error(-22, "fm index: extracting needs the structures for locating");
+        const int b = checkpoints ? sample_bits_of(sample_bits) : 0;
+        const ImageHeader h = image_header(dev_image, image_bytes);
+        if (h.R == 0) throw prim::Error(-22, "fm index: the image has no record");
+        if (top_bits < 0 || top_bits > 12) throw prim::Error(-22, "fm index: the top level takes 0 to 12 bits");
+        WideSyms W;
+        image_symbols(h.recs(dev_image), h.R, 8, W);
+        RunIndex X;
+        run_index_load(h.recs(dev_image), h.R, W, X);
+        W.ranks.release();
+        F.n = X.n; F.R = X.R; F.k = X.k; F.sep = X.sep; F.locate = locate;
+        if (locate) {
+            const u64 words = (X.n + 1) / 64 + 2;
+            u64 need = words * (sizeof(RankCell) + 8 + sizeof(idx_t)) + X.R * sizeof(RunRec) + X.k * sizeof(idx_t);
+            if (checkpoints) need += (Checkpoints{X.n, X.k, (u32)b}.count() * 8 + 2 * X.k + 1) * sizeof(idx_t) + X.k * 8;       // the ranking's scratch and the samples
+            // the inverse table (a pair per sample, at most one per checkpoint) beside the second half of its sort, and T
+            if (extract) need += (4 * (checkpoints ? Checkpoints{X.n, X.k, (u32)b}.count() : X.k) + X.k + 1) * sizeof(idx_t);
+            if (X.n >= ((u64)1 << 62) || need > fm_locate_budget())
+                throw prim::Error(-22, "fm index: the structures for locating (" + std::to_string(need) + " bytes) are more than this device can hold");
+        }
+        run_index_lf(X, locate && X.R, true);
+        F.key = std::move(X.key); F.slf = std::move(X.slf); F.rc = std::move(X.rc); F.rec = std::move(X.rec);
+        F.alpha = std::move(W.alpha);
+        F.sigma = prim::reduce_sum<u64>(F.R, FmHeadIn{F.key.p}, "fm.sigma");
+        if (F.R) F.sepval = F.alpha.p ? F.alpha.get(F.sep) : (u64)F.sep;
+#ifdef GRLBWT_PRIM_HIP
+        F.top_entries = prim::top_search_entries(top_bits, F.R, sizeof(FmKey));
+#endif
+        if (locate && F.R && checkpoints) {
+            // sid from the chain ends (FmSidLenFn is not run) and the samples.  An image with rows on no string's chain (cycles of LF
+            // without a separator) is accepted as without checkpoints: such rows have no position, their samples say so.
+            CpRank C;
+            lf_checkpoints(F.lf(), F.n, F.k, F.sep, b, -22, C, F.walk);
+            F.checkpoints = true;
+            F.cp = C.cp;
+            F.sid.alloc(F.k);
+            prim::for_each(F.k, CpSidFn{C.endcp.p, C.head.p, F.sid.p}, "fm.sid_chains");
+            F.smp.alloc(2 * F.walk.m);
+            prim::for_each(F.walk.m, CpSampleFn{C.head.p, C.dist.p, C.slen.p, F.smp.p}, "fm.samples");
+            F.walk.sample_bytes = F.smp.n * sizeof(idx_t);
+            if (extract) {
+                const u64 m = F.walk.m;
+                C.seglen.release(); C.endcp.release();
+                F.T.alloc(F.k + 1);
+                prim::exclusive_scan<idx_t>(F.k, IdxIn<idx_t>{C.slen.p}, F.T.p, true, "fm.extract_starts");
+                DBuf<idx_t> ka(m), va(m), kb(m), vb(m);
+                prim::for_each(m, FmCpSampleKeyFn{C.cp, C.head.p, C.dist.p, F.T.p, ka.p, va.p}, "fm.extract_keys");
+                C.head.release(); C.dist.release();
+                const u64 ns = prim::reduce_sum<u64>(m, FmSampleValidIn{ka.p, F.n}, "fm.extract_samples");
+                const int res = prim::sort_pairs<idx_t, idx_t>(ka.p, va.p, kb.p, vb.p, m, 0, std::max((int)bitlen64(F.n), 1), "fm.extract_sort");
+                F.xq.alloc(ns); F.xc.alloc(ns);      // (the ns samples come first: the others carry n)
+                d2d_copy(F.xq.p, res ? kb.p : ka.p, ns);
+                d2d_copy(F.xc.p, res ? vb.p : va.p, ns);
+            }
+        } else if (locate && F.R && extract) {
+            DBuf<u32> bad(1);
+            bad.zero();
+            F.sid.alloc(F.k);
+            DBuf<idx_t> slen(F.k + 1);
+            slen.zero();
+            prim::for_each(F.k, FmSidLenFn{F.lf(), F.sep, F.n, F.sid.p, slen.p, bad.p}, "fm.sid_len");
+            if (bad.get(0)) throw prim::Error(-22, "fm index: a string's walk met no separator in n steps: not the BWT of a collection");
+            F.cp = Checkpoints{F.n, F.k, 0};         // (row_of(c) = c below k: the heads' rows)
+            F.T.alloc(F.k + 1);
+            prim::exclusive_scan<idx_t>(F.k, IdxIn<idx_t>{slen.p}, F.T.p, true, "fm.extract_starts");
+            F.xq.alloc(F.k); F.xc.alloc(F.k);
+            prim::for_each(F.k, FmHeadSampleFn{F.T.p, F.xq.p, F.xc.p}, "fm.extract_heads");
+        } else if (locate && F.R) {
+            DBuf<u32> bad(1);
+            bad.zero();
+            F.sid.alloc(F.k);
+            prim::for_each(F.k, FmSidLenFn{F.lf(), F.sep, F.n, F.sid.p, nullptr, bad.p}, "fm.sid");
+            if (bad.get(0)) throw prim::Error(-22, "fm index: a string's walk met no separator in n steps: not the BWT of a collection");
+        }
+        if (extract) { F.extract = true; F.maxval = F.alpha.p ? F.alpha.get(F.alpha.n - 1) : (u64)X.mx; }
+        prim::sync();
+    }
+    // the checks every call that takes patterns shares; returns the number of their cells, the first one's index in `x0`
+    static u64 fm_match_cells(const void *cells, int w, const u64 *off, u64 np, u64 &x0, const char *who) {
+        check_cell_bytes(w, who);
+        x0 = 0;
+        if (np == 0) return 0;
+        if (prim::reduce_sum<u64>(np, FmOffsetsBadIn{off}, "fm.offsets")) throw prim::Error(-22, std::string(who) + ": the pattern offsets decrease");
+        u64 x1;
+        prim::d2h(&x0, off, 8);
+        prim::d2h(&x1, off + np, 8);
+        if (x1 > x0 && !cells) throw prim::Error(-22, std::string(who) + ": no pattern cells");
+        return x1 - x0;
+    }
+    static FmCountFn fm_count_fn(const FmIndex &F, const void *cells, int w, const u64 *off, u64 *lo, u64 *hi) {
+        return FmCountFn{F.key.p, F.slf.p, F.R, F.n, F.alpha.p, F.alpha.n, cells, w, off, lo, hi};
+    }
+    static void fm_count(const FmIndex &F, const void *cells, int w, const u64 *off, u64 np, u64 *lo, u64 *hi) {
+        u64 x0;
+        const u64 nc = fm_match_cells(cells, w, off, np, x0, "fm count");
+        if (np == 0) return;
+        const FmCountFn f = fm_count_fn(F, cells, w, off, lo, hi);
+        if (F.R) {
+            // the separator ends a string: a pattern may END with it (the step from [0, n) gives [0, n_strings), the rows of
+            // the strings' ends) but the rows a further step would lead to are no range of a BCR BWT
+            const u64 bad = prim::reduce_min<u64>(nc, FmSepMisuseIn{f, F.sepval, x0, np}, "fm.separators");
+            if (bad != ~0ull) throw prim::Error(-22, "fm count: pattern " + std::to_string(bad) + " holds the separator in front of its last cell");
+        }
+#ifdef GRLBWT_PRIM_HIP
+        prim::top_search(np, f, F.top_entries, "fm.count");
+#else
+        prim::for_each(np, FmCountPlainFn{f}, "fm.count");
+#endif
+        prim::sync();
+    }
+    // ---- longest matches and MEMs (functor block "longest matches and maximal exact matches").  Everything that
+    // can refuse a call runs before the first store into an output.  One ticket per query cell; the device form is
+    // prim::top_tickets (lanes that take the next cell when their match ends, under the LDS top level of fm_count), or with
+    // GRLBWT_FM_MATCH=l one lane per cell through prim::top_search; the stand-in runs the same functor serially.
+    //   The compiler's report for gfx950 (tools/kernel_resources.py): prim::k_top_tickets<FmMatchFn> takes 46 vector registers in
+    //   both index widths (k_top_search<FmMatchLaneFn> 32, k_top_search<FmCountFn> 26), no scratch, no static LDS -- the dynamic
+    //   LDS is the top level, at most 32 KB of 8-byte keys or 64 KB of 16-byte keys; 8 waves per SIMD fit either way.
+    static void fm_match_run(const FmIndex &F, const FmMatchFn &f, u64 nc, u64 np, MatchInfo &mi) {
+        mi = MatchInfo();
+        mi.patterns = np; mi.cells = nc;
+        if (nc == 0) return;
+#ifdef GRLBWT_PRIM_HIP
+        if (prim::sw().fm_match == 'l') {
+            prim::top_search(nc, FmMatchLaneFn{f}, F.top_entries, "fm.match_lanes");
+            mi.lanes = nc;
+        } else {
+            DBuf<u64> ctr(2);
+            const prim::WalkStats ws = prim::top_tickets(nc, f, ctr.p, F.top_entries, "fm.match");
+            mi.lanes = ws.lanes; mi.refills = ws.refills;
+        }
+#else
+        prim::for_each(nc, WalkSerialFn<FmMatchFn>{f}, "fm.match");
+        mi.lanes = nc;
+#endif
+        mi.matched = prim::reduce_sum<u64>(nc, CellIn<u64>{f.len}, "fm.match_sum");
+        mi.longest = prim::reduce_max<u64>(nc, CellIn<u64>{f.len}, "fm.match_max");
+        if (f.max_len) mi.capped = prim::reduce_sum<u64>(nc, FmLenCappedIn{f.len, f.max_len}, "fm.match_capped");
+    }
+    static FmMatchFn fm_match_fn(const FmIndex &F, const void *cells, int w, const u64 *off, u64 np, u64 x0, u64 max_len, u64 *len, u64 *lo, u64 *hi) {
+        return FmMatchFn{fm_count_fn(F, cells, w, off, nullptr, nullptr), F.sepval, x0, np, max_len, len, lo, hi};
+    }
+    static void fm_match(const FmIndex &F, const void *cells, int w, const u64 *off, u64 np, u64 max_len, u64 *len, u64 *lo, u64 *hi) {
+        if ((lo == nullptr) != (hi == nullptr)) throw prim::Error(-22, "fm match: the range outputs are both given or both null");
+        u64 x0;
+        const u64 nc = fm_match_cells(cells, w, off, np, x0, "fm match");
+        if (nc && !len) throw prim::Error(-22, "fm match: no output for the lengths");
+        MatchInfo mi;
+        fm_match_run(F, fm_match_fn(F, cells, w, off, np, x0, max_len, len, lo, hi), nc, np, mi);
+        prim::sync();
+        F.minfo = mi;
+    }
+    // n_mems is set whenever the count was reached, also when the capacity then refuses the call
+    static void fm_mems(const FmIndex &F, const void *cells, int w, const u64 *off, u64 np, u64 min_len, u64 max_len, u64 *pat, u64 *beg, u64 *mlen,
+                        u64 *lo, u64 *hi, u64 capacity, u64 &n_mems) {
+        n_mems = 0;
+        if ((lo == nullptr) != (hi == nullptr)) throw prim::Error(-22, "fm mems: the range outputs are both given or both null");
+        u64 x0;
+        const u64 nc = fm_match_cells(cells, w, off, np, x0, "fm mems");
+        MatchInfo mi;
+        mi.patterns = np;
+        if (nc == 0) { prim::sync(); F.minfo = mi; return; }
+        const u64 nw = nc / 64 + 2;
+        const u64 need = nc * 8 * (lo ? 3 : 1) + nw * 16 + 24;
+        if (need > prim::mem_available()) throw prim::Error(-12, "fm mems: the scratch needs " + std::to_string(need) + " bytes of device memory, more than is free");
+        DBuf<u64> L(nc), slo(lo ? nc : 0), shi(lo ? nc : 0), words(nw), base(nw + 1);
+        fm_match_run(F, fm_match_fn(F, cells, w, off, np, x0, max_len, L.p, lo ? slo.p : nullptr, lo ? shi.p : nullptr), nc, np, mi);
+        words.zero();
+        prim::bitvector_from_pred(nc, FmMemFlagIn{L.p, off, x0, np, min_len ? min_len : 1}, words.p, "fm.mem_flags");
+        mi.mems = n_mems = prim::exclusive_scan<u64>(nw, PopcIn{words.p}, base.p, true, "fm.mem_ranks");
+        if (n_mems > capacity)
+            throw prim::Error(-22, "fm mems: " + std::to_string(n_mems) + " matches, more than the output arrays hold");
+        if (n_mems && (!pat || !beg || !mlen)) throw prim::Error(-22, "fm mems: no output arrays");
+        prim::for_each_set_bit<u64>(nc, words.p, base.p, FmMemEmitFn{L.p, slo.p, shi.p, off, x0, np, pat, beg, mlen, lo, hi}, "fm.mems");
+        prim::sync();
+        F.minfo = mi;
+    }
+    static void fm_locate(const FmIndex &F, const u64 *rows, u64 nr, u64 max_steps, u64 *str, u64 *ofs) {
+        if (!F.locate) throw prim::Error(-22, "fm locate: the index was made without the structures for locating");
+        if (nr == 0) return;
+        if (prim::reduce_sum<u64>(nr, FmRowBadIn{rows, F.n}, "fm.rows")) throw prim::Error(-22, "fm locate: a row is not below the number of symbols");
+        const u64 lim = max_steps < F.n ? max_steps : F.n;
+        if (F.checkpoints) prim::for_each(nr, FmLocateCpFn{F.lf(), F.sid.p, F.smp.p, F.cp, F.sep, lim, rows, str, ofs}, "fm.locate_cp");
+        else prim::for_each(nr, FmLocateFn{F.lf(), F.sid.p, F.sep, lim, rows, str, ofs}, "fm.locate");
+        prim::sync();
+    }
+    // ---- extract (functor block "extracting text ranges").  Everything that can refuse the call runs before the first
+    // store into `out` or `out_off`: the ranges' strings, then the plan -- pieces, cells and steps per range, scanned in scratch --
+    // and the capacity.  Then the separators (one lane per range) and the walk, one ticket per piece.
+    //   Loops: the binary searches run over the table and the scanned counts; a piece's steps are planned (FmExtractFn); nothing
+    //   waits for another thread, and the only atomics are the ticket word's.
+    static void fm_string_lengths(const FmIndex &F, u64 *len) {
+        if (!F.extract) throw prim::Error(-22, "fm string lengths: the index was made without the structures for extracting");
+        prim::for_each(F.k, FmLenOutFn{F.T.p, len}, "fm.string_lengths");
+        prim::sync();
+    }
+    template <class cell_t>
+    static void fm_extract_t(const FmIndex &F, const FmExtractPlan &P, u64 nr, const u64 *pscan, const u64 *ooff, u64 pieces, cell_t *out, ExtractInfo &xi) {
+        prim::for_each(nr, FmExtractSepFn<cell_t>{P, ooff, out, (cell_t)F.sepval}, "fm.extract_sep");
+        WalkInfo wi;
+        walk(pieces, FmExtractFn<cell_t>{F.lf(), F.cp, F.xc.p, P, nr, pscan, ooff, out, {F.alpha.p}}, wi, "fm.extract");
+        xi.lanes = wi.lanes; xi.refills = wi.refills;
+    }
+    static u64 fm_extract(const FmIndex &F, const u64 *str, const u64 *beg, const u64 *end, u64 nr, int w, void *out, u64 capacity, u64 *out_off) {
+        if (!F.extract) throw prim::Error(-22, "fm extract: the index was made without the structures for extracting");
+        check_cell_bytes(w, "fm extract");
+        if (w < 8 && (F.maxval >> (8 * w))) throw prim::Error(-22, "fm extract: the image's largest symbol does not fit the cell width");
+        ExtractInfo xi;
+        xi.ranges = nr;
+        if (nr == 0) {
+            prim::dev_memset(out_off, 0, 8);
+            prim::sync();
+            F.xinfo = xi;
+            return 0;
+        }
+        const u64 bad = prim::reduce_min<u64>(nr, FmExtractBadIn{str, F.k}, "fm.extract_strings");
+        if (bad != ~0ull) throw prim::Error(-22, "fm extract: range " + std::to_string(bad) + " names a string that is not below the number of strings");
+        const FmExtractPlan P{F.T.p, F.xq.p, F.xq.n, str, beg, end};
+        DBuf<u64> npiece(nr + 1), ncell(nr + 1), nstep(nr);
+        prim::for_each(nr, FmExtractPlanFn{P, npiece.p, ncell.p, nstep.p}, "fm.extract_plan");
+        xi.steps = prim::reduce_sum<u64>(nr, CellIn<u64>{nstep.p}, "fm.extract_steps");
+        xi.pieces = prim::exclusive_scan<u64>(nr, CellIn<u64>{npiece.p}, npiece.p, true, "fm.extract_pieces");
+        xi.cells = prim::exclusive_scan<u64>(nr, CellIn<u64>{ncell.p}, ncell.p, true, "fm.extract_cells");
+        if (xi.cells > capacity) throw prim::Error(-22, "fm extract: the ranges hold " + std::to_string(xi.cells) + " cells, more than the output buffer");
+        prim::d2d(out_off, ncell.p, (nr + 1) * 8);
+        with_cell(w, [&](auto c) {
+            typedef decltype(c) cell_t;
+            fm_extract_t<cell_t>(F, P, nr, npiece.p, ncell.p, xi.pieces, (cell_t *)out, xi);
+        });
+        prim::sync();
+        F.xinfo = xi;
+        return xi.cells;
+    }
+
+    // ---- merging two images into the image of "A's strings, then B's" (grlbwt_merge_*; functor block "merging two images";
+    // DESIGN.md 4c).  The interleave refinement of Holt and McMillan: z starts as 0^nA 1^nB; a round writes every row's flag where
+    // a stable sort of the rows by their symbol puts it and resets the separator's bucket to 0^kA 1^kB (the terminators are
+    // ordered by the strings' numbers); the rounds end with the one that changes nothing.
+    struct ImageMerge {
+        u64 na = 0, nb = 0, ka = 0, kb = 0, sigma = 0, sepval = 0;
+        u64 rounds = 0, rows_changed = 0, n_runs = 0, out_bytes = 0, sb = 0, fb = 0, scratch_bytes = 0;
+        DBuf<u8> ra, rb, z;       // rank byte per row of A and of B (16 bytes of padding behind each), the converged interleave
+        DBuf<u64> alpha;          // rank -> symbol value
+        u64 held_bytes() const { return ra.n + rb.n + z.n + alpha.n * 8; }
+    };
+#ifdef GRLBWT_PRIM_HIP
+    static constexpr u64 kMergeTile = prim::kMgTile;
+#else
+    static constexpr u64 kMergeTile = 4096;      // (the serial form has no tiles: the figure the device library reports)
+#endif
+    static constexpr u64 kMergeSigmaMax = 256;
+    // the non-empty records of an image: their symbols as 64-bit values and their lengths
+    static u64 merge_load_runs(const void *dev_image, u64 image_bytes, const char *which, DBuf<u64> &val, DBuf<idx_t> &len) {
+        const ImageHeader h = image_header(dev_image, image_bytes);
+        if (h.R == 0) throw prim::Error(-22, std::string("merge: image ") + which + " has no record");
+        val.alloc(h.R); len.alloc(h.R);
+        prim::for_each(h.R, UnpackRunsFn<u64>{h.recs(dev_image), val.p, len.p}, "merge.unpack");
+        const u64 R = drop_empty_runs(val, len, h.R, "merge");
+        if (R == 0) throw prim::Error(-22, std::string("merge: image ") + which + " describes no symbol");
+        return R;
+    }
+    // rank byte per row of one image: out[0, n) (allocated with the padding the round kernels read over); returns n
+    static u64 merge_expand(const u32 *rrank, const idx_t *rlen, u64 R, DBuf<u8> &out) {
+        DBuf<idx_t> rpos(R + 1);
+        const u64 n = (u64)prim::exclusive_scan<idx_t>(R, IdxIn<idx_t>{rlen}, rpos.p, true, "merge.positions");
+        RankBits rb;
+        build_rankbits(rb, rpos.p, R, n + 1, "merge.runbits");
+        out.alloc(n + 16);
+        prim::for_each(n, MgExpandFn{rrank, rb.words.p, rb.base.p, out.p}, "merge.expand");
+        return n;
+    }
+    // the interleave as a bit-vector with ranks, and the run heads of the merged sequence read through it
+    struct MergeHeads { RankBits zb; DBuf<u64> hw; DBuf<idx_t> hb; u64 R = 0; };
+    static u64 merge_heads_bytes(u64 n) { return (n / 64 + 3) * 2 * (8 + sizeof(idx_t)); }
+    static void merge_bits(const u8 *z, u64 n, RankBits &zb) {
+        const u64 nw = n / 64 + 2;
+        zb.words.alloc(nw); zb.base.alloc(nw + 1);
+        zb.words.zero();
+        prim::bitvector_from_pred(n, MgFlagPred{z}, zb.words.p, "merge.bits");
+        prim::exclusive_scan_nosync<idx_t>(nw, PopcIn{zb.words.p}, zb.base.p, true, "merge.bit_ranks");
+    }
+    static MgSym merge_sym(const ImageMerge &M, const RankBits &zb) { return MgSym{M.ra.p, M.rb.p, zb.words.p, zb.base.p}; }
+    static void merge_heads(const ImageMerge &M, MergeHeads &H) {
+        const u64 n = M.na + M.nb, nw = n / 64 + 2;
+        merge_bits(M.z.p, n, H.zb);
+        H.hw.alloc(nw); H.hb.alloc(nw + 1);
+        H.hw.zero();
+        prim::bitvector_from_pred(n, MgHeadPred{merge_sym(M, H.zb)}, H.hw.p, "merge.heads");
+        H.R = (u64)prim::exclusive_scan<idx_t>(nw, PopcIn{H.hw.p}, H.hb.p, true, "merge.head_ranks");
+    }
+    // One refinement round without the separator rule, and the test that ends the rounds.  changed(): the rows at which the
+    // interleave `cur` differs from `prev`, the one before it (null: 0) -- the device form takes the A-rows per tile of `cur` in
+    // the same pass, so it comes first; step(): oth = the flags of cur where a stable sort of the rows by their symbol puts them.
+    // The device form is prim::MgRound (three kernels, the symbols read from two contiguous slices per tile); the serial form
+    // goes through the generic primitives: the merged symbols gathered as keys, a stable sort of (key, flag).
+    struct MergeRound {
+        u64 n = 0;
+        bool by_sort = !prim::kIsDevice;
+        static u64 sort_scratch_bytes(u64 n_) { return 3 * n_ + (n_ / 64 + 3) * (8 + sizeof(idx_t)) + (n_ / 4096 + 1) * 256 * 12; }
+        u64 changed_by_sum(const u8 *cur, const u8 *prev) { return prev ? prim::reduce_sum<u64>(n, MgDiffIn{cur, prev}, "merge.changed") : 0; }
+        void step_by_sort(const u8 *ra, const u8 *rb, const u8 *cur, u8 *oth) {
+            RankBits zb;
+            merge_bits(cur, n, zb);
+            DBuf<u8> ka(n), kb(n), v2(n);
+            prim::for_each(n, MgKeyFn{MgSym{ra, rb, zb.words.p, zb.base.p}, ka.p}, "merge.keys");
+            d2d_copy(oth, cur, n);
+            const int res = prim::sort_pairs<u8, u8>(ka.p, oth, kb.p, v2.p, n, 0, 8, "merge.sort");
+            if (res) d2d_copy(oth, v2.p, n);
+        }
+#ifdef GRLBWT_PRIM_HIP
+        // (GRLBWT_MERGE_ROUND=sort: the generic form on the device too -- the baseline the fused kernels are measured against)
+        prim::MgRound<idx_t> W;
+        static u64 scratch_bytes(u64 n_) { return prim::sw().merge_round == 's' ? sort_scratch_bytes(n_) : prim::MgRound<idx_t>::scratch_bytes(n_); }
+        void alloc(u64 n_) { n = n_; by_sort = prim::sw().merge_round == 's'; if (!by_sort) W.alloc(n_); }
+        void release() { W.release(); }
+        u64 changed(const u8 *cur, const u8 *prev, u64 na) {
+            if (by_sort) return changed_by_sum(cur, prev);
+            u64 a_rows = 0;
+            const u64 c = W.count(cur, prev, &a_rows);
+            if (a_rows != na) throw prim::Error(-71, "merge: a round lost rows of A");
+            return c;
+        }
+        void step(const u8 *ra, const u8 *rb, const u8 *cur, u8 *oth) { if (by_sort) step_by_sort(ra, rb, cur, oth); else W.scatter(cur, ra, rb, oth); }
+#else
+        static u64 scratch_bytes(u64 n_) { return sort_scratch_bytes(n_); }
+        void alloc(u64 n_) { n = n_; }
+        void release() {}
+        u64 changed(const u8 *cur, const u8 *prev, u64) { return changed_by_sum(cur, prev); }
+        void step(const u8 *ra, const u8 *rb, const u8 *cur, u8 *oth) { step_by_sort(ra, rb, cur, oth); }
+#endif
+    };
+    // device milliseconds the profile table holds under a kernel name (0 while the profile is off)
+    static double merge_prof_ms(const char *name) {
+        auto it = prim::rt().prof.find(name);
+        return it == prim::rt().prof.end() ? 0.0 : (double)it->second.ms;
+    }
+    // The header rule of an image and its records, shared by what writes an image from runs (merge, select).  sb comes from the
+    // largest symbol + 4, fb from `longest`: the largest total of one symbol (cells of one byte) or the number of symbols.
+    static void image_widths(u64 max_sym, u64 longest, u64 &sb, u64 &fb) {
+        sb = (bitlen64(max_sym + 4) + 7) / 8;
+        fb = (bitlen64(longest) + 7) / 8;
+    }
+    static void emit_records(const u32 *sym, RunLen len, u64 R, u32 sb, u32 fb, const u64 *alpha, u8 *out, const char *name) {
+        u8 hdr[16] = {0};
+        hdr[0] = (u8)sb; hdr[8] = (u8)fb;
+        prim::h2d(out, hdr, 16);
+        if (sb + fb <= 8 && fb < 8) prim::pack_records(R, RunRecordFn{sym, len, sb, alpha}, sb + fb, out + 16, name);
+        else prim::for_each(R, PackRunsFn{sym, len, sb, fb, out, 16u, alpha}, name);
+    }
+    static void merge_create(const void *img_a, u64 bytes_a, const void *img_b, u64 bytes_b, int cell_bytes, u64 max_rounds, ImageMerge &M) {
+        check_cell_bytes(cell_bytes, "merge");
+        // ---- load: the records of both images, the union of their symbol values, one rank byte per row
+        DBuf<u64> va, vb;
+        DBuf<idx_t> la, lb;
+        const u64 Ra = merge_load_runs(img_a, bytes_a, "A", va, la), Rb = merge_load_runs(img_b, bytes_b, "B", vb, lb);
+        DBuf<u64> cat(Ra + Rb);
+        d2d_copy(cat.p, va.p, Ra);
+        d2d_copy(cat.p + Ra, vb.p, Rb);
+        va.release(); vb.release();
+        const u64 mx = prim::reduce_max<u64>(Ra + Rb, CellIn<u64>{cat.p}, "merge.max_sym");
+        if (cell_bytes < 8 && (mx >> (8 * cell_bytes))) throw prim::Error(-22, "merge: the largest symbol (" + std::to_string(mx) + ") does not fit the cell width");
+        DBuf<u32> ranks(Ra + Rb);
+        M.sigma = alphabet_compact<u64>(cat.p, Ra + Rb, mx, ranks.p, M.alpha);
+        cat.release();
+        if (M.sigma > kMergeSigmaMax)
+            throw prim::Error(-75, "merge: the two images hold " + std::to_string(M.sigma) + " distinct symbols together, more than the 256 a round sorts by");
+        const std::vector<u64> alpha = M.alpha.to_host(M.sigma);
+        const u32 sep_a = prim::reduce_min<u32>(Ra, PtrU32In{ranks.p}, "merge.sep_a"), sep_b = prim::reduce_min<u32>(Rb, PtrU32In{ranks.p + Ra}, "merge.sep_b");
+        if (sep_a != sep_b)
+            throw prim::Error(-22, "merge: the smallest symbols of the two images differ (" + std::to_string(alpha[sep_a]) + " in A, " + std::to_string(alpha[sep_b]) +
+                                       " in B): they are not collections with one separator");
+        M.sepval = alpha[0];
+        M.na = merge_expand(ranks.p, la.p, Ra, M.ra);
+        M.nb = merge_expand(ranks.p + Ra, lb.p, Rb, M.rb);
+        ranks.release(); la.release(); lb.release();
+        const u64 n = M.na + M.nb;
+        u64 ha[256], hb[256];
+        prim::byte_histogram(M.ra.p, M.na, ha);
+        prim::byte_histogram(M.rb.p, M.nb, hb);
+        M.ka = ha[0]; M.kb = hb[0];
+        u64 F = n;
+        if (cell_bytes == 1) { F = 0; for (int i = 0; i < 256; i++) if (ha[i] + hb[i] > F) F = ha[i] + hb[i]; }
+        image_widths(mx, F, M.sb, M.fb);
+        // ---- the rounds.  Scratch: the second interleave buffer, the tile tables, and what the run heads take afterwards
+        const u64 round_scratch = MergeRound::scratch_bytes(n);
+        M.scratch_bytes = (n + 16) + std::max(round_scratch, merge_heads_bytes(n));
+        if (M.scratch_bytes + (n + 16) > prim::mem_available())
+            throw prim::Error(-12, "merge: the rounds need " + std::to_string(M.scratch_bytes + n + 16) + " bytes of device memory, more than is free");
+        DBuf<u8> z0(n + 16), z1(n + 16);
+        u8 *cur = z0.p, *oth = z1.p;
+        prim::for_each(n, MgSplitFn{cur, M.na}, "merge.first");
+        const u64 cap = max_rounds ? max_rounds : n + 2, k = M.ka + M.kb;
+        bool converged = false;
+        MergeRound W;
+        W.alloc(n);
+        prim::rt().tag = -1; prim::rt().phase = 0;
+        const char *kinds[6] = {"merge.counts", "merge.hist", "merge.scatter", "merge.changed", "merge.keys", "merge.sort.scatter"};
+        double seen[6] = {0, 0, 0, 0, 0, 0};
+        for (;;) {
+            const u64 changed = W.changed(cur, M.rounds ? oth : nullptr, M.na);
+            if (prim::rt().profile) {
+                // the per-round log (grlbwt_profile_enable): the kernels of the round just done and the pass that found what it changed
+                double ms[6];
+                for (int i = 0; i < 6; i++) { const double t = merge_prof_ms(kinds[i]); ms[i] = t - seen[i]; seen[i] = t; }
+                if (M.rounds)
+                    fprintf(stderr, "[grlbwt] merge round %llu: rows changed %llu; ms: counts %.3f hist %.3f scatter %.3f (sort form: changed %.3f keys %.3f sort scatter %.3f)\n",
+                            (unsigned long long)M.rounds, (unsigned long long)changed, ms[0], ms[1], ms[2], ms[3], ms[4], ms[5]);
+            }
+            if (M.rounds) {
+                M.rows_changed += changed;
+                if (changed == 0) { converged = true; break; }
+            }
+            if (M.rounds == cap) break;
+            W.step(M.ra.p, M.rb.p, cur, oth);
+            prim::for_each(k, MgSplitFn{oth, M.ka}, "merge.separators");
+            std::swap(cur, oth);
+            M.rounds++;
+        }
+        if (!converged)
+            throw prim::Error(-22, "merge: not converged after " + std::to_string(M.rounds) + " rounds (max_rounds); the rounds needed are about the longest prefix a suffix of A "
+                                   "shares with a suffix of B -- the per-string cost model of grlbwt_fm_locate without checkpoints: fine for reads, hopeless for chromosomes");
+        W.release();
+        if (cur == z0.p) { M.z = std::move(z0); z1.release(); } else { M.z = std::move(z1); z0.release(); }
+        MergeHeads H;
+        merge_heads(M, H);
+        M.n_runs = H.R;
+        M.out_bytes = 16 + H.R * (M.sb + M.fb);
+        prim::sync();
+    }
+    static void merge_emit(const ImageMerge &M, u8 *out, u64 capacity) {
+        if (capacity < M.out_bytes) throw prim::Error(-22, "merge: output buffer too small (" + std::to_string(M.out_bytes) + " bytes needed)");
+        const u64 n = M.na + M.nb;
+        MergeHeads H;
+        merge_heads(M, H);
+        if (H.R != M.n_runs) throw prim::Error(-71, "merge: the run heads changed since the merge was made");
+        const u64 R = H.R;
+        DBuf<u32> sym(R);
+        DBuf<idx_t> start(R + 1);
+        prim::for_each_set_bit<idx_t>(n, H.hw.p, H.hb.p, MgHeadFn{merge_sym(M, H.zb), sym.p, start.p}, "merge.runs");
+        const idx_t total = (idx_t)n;
+        prim::h2d(start.p + R, &total, sizeof(total));
+        emit_records(sym.p, RunLen{nullptr, start.p}, R, (u32)M.sb, (u32)M.fb, M.alpha.p, out, "merge.pack");
+        prim::sync();
+    }
+    static void merge_interleave(const ImageMerge &M, u64 *dev_bits) {
+        prim::bitvector_from_pred(M.na + M.nb, MgFlagPred{M.z.p}, dev_bits, "merge.interleave");
+        prim::sync();
+    }
+
+    // ---- removing or keeping chosen strings of an image (grlbwt_select_*; functor block "removing or keeping chosen strings";
+    // DESIGN.md 4e).  The list becomes a k-bit set; the chains of the listed strings are marked in an n-bit vector, per string or
+    // through checkpointed segments; a rank over the marked bits gives every run its new length; empty runs go, equal neighbours
+    // are joined.  The handle keeps the new runs, the values of a compacted alphabet and the marked bits.
+    //   Loops: a string's walk is bounded by n steps, a segment's by seglen[c] + 1, the pointer jumping by ceil(log2 m) rounds;
+    //   nothing waits for another thread; the atomics are the ticket word's and the ORs into the two bit-vectors.
+    struct ImageSelect {
+        u64 n_in = 0, k_in = 0, R_in = 0, n_listed = 0, rows_marked = 0, longest_walk = 0;
+        u64 n_out = 0, k_out = 0, R_out = 0, out_bytes = 0, sb = 0, fb = 0, sepval = 0, flags = 0;
+        u64 lanes = 0, refills = 0, sample_bits = 0, n_checkpoints = 0, jump_rounds = 0, scratch_bytes = 0;
+        DBuf<u32> sym;            // the runs of the output: symbols (ranks where alpha is set) and lengths
+        DBuf<idx_t> len;
+        DBuf<u64> alpha;          // rank -> symbol value (null: the symbols are the values)
+        DBuf<u64> marked;         // bit p: row p of the input lies on a listed string's chain
+        u64 held_bytes() const { return sym.n * 4 + len.n * sizeof(idx_t) + alpha.n * 8 + marked.n * 8; }
+    };
+    static void select_create(const void *dev_image, u64 image_bytes, int cell_bytes, const u64 *ids, u64 n_ids, bool keep, bool checkpoints, int sample_bits,
+                              ImageSelect &S) {
+        check_cell_bytes(cell_bytes, "select");
+        if (!checkpoints && sample_bits) throw prim::Error(-22, "select: sample_bits needs the checkpoint flag");
+        const int b = checkpoints ? sample_bits_of(sample_bits) : 0;
+        const ImageHeader h = image_header(dev_image, image_bytes);
+        if (h.R == 0) throw prim::Error(-22, "select: the image has no record");
+        WideSyms W;
+        image_symbols(h.recs(dev_image), h.R, cell_bytes, W, "select");
+        RunIndex X;
+        run_index_load(h.recs(dev_image), h.R, W, X);
+        W.ranks.release();
+        const u64 R = X.R, n = X.n, k = X.k;
+        if (R == 0) throw prim::Error(-22, "select: the image describes no symbol");
+        const u32 sep = X.sep;
+        S.n_in = n; S.k_in = k; S.R_in = R;
+        S.sepval = W.alpha.p ? W.alpha.get(sep) : (u64)sep;
+        // ---- the list as a set, its distinct entries in ascending order as the tickets
+        if (n_ids) {
+            const u64 bad = prim::reduce_min<u64>(n_ids, FmExtractBadIn{ids, k}, "select.list_check");
+            if (bad != ~0ull) {
+                u64 v = 0;
+                prim::d2h(&v, ids + bad, 8);
+                throw prim::Error(-22, "select: entry " + std::to_string(bad) + " of the list (" + std::to_string(v) + ") is not below the number of strings (" +
+                                           std::to_string(k) + ")");
+            }
+        }
+        const u64 lw = k / 64 + 2;
+        DBuf<u64> list(lw);
+        DBuf<idx_t> lbase(lw + 1);
+        list.zero();
+        prim::for_each(n_ids, SelListFn{ids, list.p}, "select.list");
+        const u64 nl = (u64)prim::exclusive_scan<idx_t>(lw, PopcIn{list.p}, lbase.p, true, "select.list_ranks");
+        S.n_listed = nl;
+        S.k_out = keep ? nl : k - nl;
+        if (S.k_out == 0)
+            throw prim::Error(-22, keep ? "select: the keep flag with an empty list leaves no string" : "select: every string is listed, the result would hold no string");
+        // ---- memory, before the first walk: the run index and its sort, the two bit-vectors with their ranks, the tickets, the
+        // checkpoint ranking's arrays, the rewrite's scan
+        const u64 words = (n + 1) / 64 + 2, mw = n / 64 + 2;
+        const u64 m = checkpoints ? Checkpoints{n, k, (u32)b}.count() : 0;
+        u64 need = words * (sizeof(RankCell) + 8 + sizeof(idx_t)) + R * (sizeof(RunRec) + 3 * (4 + sizeof(idx_t))) + lw * (8 + sizeof(idx_t)) +
+                   mw * (8 + sizeof(idx_t)) + 2 * nl * sizeof(idx_t);
+        if (checkpoints) need += (6 * m + 2 * k + 1) * sizeof(idx_t) + k * 8;
+        S.scratch_bytes = need;
+        if (need > prim::mem_available())
+            throw prim::Error(-12, "select: the structures need " + std::to_string(need) + " bytes of device memory, more than is free");
+        DBuf<idx_t> tick(nl);
+        prim::for_each_set_bit<idx_t>(k, list.p, lbase.p, SelTicketFn{tick.p}, "select.tickets");
+        lbase.release();
+        run_index_lf(X, true, false, true);
+        // ---- marking
+        S.marked.alloc(mw);
+        S.marked.zero();
+        u64 listed_len = 0;
+        WalkInfo wi;
+        if (!checkpoints) {
+            DBuf<idx_t> steps(nl);
+            DBuf<u32> bad(1);
+            bad.zero();
+            walk(nl, SelMarkFn{X.lf(), sep, n, tick.p, S.marked.p, steps.p, bad.p}, wi, "select.mark");
+            if (nl && bad.get(0)) throw prim::Error(-22, "select: a string's walk met no separator in n steps: not the BWT of a collection");
+            listed_len = prim::reduce_sum<u64>(nl, IdxIn64{steps.p}, "select.steps");
+            S.longest_walk = prim::reduce_max<u64>(nl, IdxIn64{steps.p}, "select.longest");
+        } else {
+            CpRank C;
+            lf_checkpoints(X.lf(), n, k, sep, b, -22, C, wi);
+            walk(m, SelMarkCpFn{X.lf(), sep, C.cp, C.head.p, C.seglen.p, list.p, S.marked.p}, wi, "select.mark_cp");
+            listed_len = prim::reduce_sum<u64>(nl, SelListedLenIn{tick.p, C.slen.p}, "select.steps");
+            S.longest_walk = prim::reduce_max<u64>(m, SelSegStepsIn{C.head.p, C.seglen.p, list.p}, "select.longest");
+            S.sample_bits = (u64)b; S.n_checkpoints = m; S.jump_rounds = wi.jump_rounds;
+        }
+        S.lanes = wi.lanes; S.refills = wi.refills;
+        X.rc.release(); X.rec.release(); tick.release(); list.release();
+        // ---- the rewrite: ranks over the marked words, the new length of every run, maximal runs
+        {
+            DBuf<idx_t> mbase(mw + 1);
+            S.rows_marked = (u64)prim::exclusive_scan<idx_t>(mw, PopcIn{S.marked.p}, mbase.p, true, "select.ranks");
+            if (S.rows_marked != listed_len) throw prim::Error(-71, "select: the rows marked do not add up to the lengths of the listed strings");
+            prim::for_each(R, SelRunLenFn{X.rpos.p, S.marked.p, mbase.p, keep, X.rlen.p}, "select.run_lengths");
+        }
+        X.rpos.release();
+        const u64 R2 = drop_empty_runs(X.rsym, X.rlen, R);
+        Runs out = merge_runs(X.rsym.p, X.rlen.p, R2);
+        X.rsym.release(); X.rlen.release(); out.pos.release();
+        S.R_out = out.R; S.n_out = out.n;
+        if (S.n_out != (keep ? S.rows_marked : n - S.rows_marked)) throw prim::Error(-71, "select: the rewritten runs do not add up");
+        if (prim::reduce_sum<u64>(out.R, SepLenIn{out.sym.p, out.len.p, sep}, "select.separators") != S.k_out)
+            throw prim::Error(-71, "select: the rewritten runs do not hold one separator per remaining string");
+        // ---- the header: the largest remaining symbol; the largest total of one symbol (cells of one byte) or the length
+        const u32 mxr = prim::reduce_max<u32>(out.R, PtrU32In{out.sym.p}, "select.max_sym");
+        const u64 mx = W.alpha.p ? W.alpha.get(mxr) : (u64)mxr;
+        u64 F = S.n_out;
+        if (cell_bytes == 1) {
+            DBuf<u64> bins(256);
+            bins.zero();
+            prim::for_each_agg(out.R, RunSymFn{out.sym.p}, BinAddFn{bins.p}, true, "select.runs_per_symbol");
+            const std::vector<u64> hb = bins.to_host(256);
+            F = 0;
+            for (u32 c = 0; c < 256; c++)
+                if (hb[c]) F = std::max(F, prim::reduce_sum<u64>(out.R, SepLenIn{out.sym.p, out.len.p, c}, "select.symbol_total"));
+        }
+        image_widths(mx, F, S.sb, S.fb);
+        S.out_bytes = 16 + S.R_out * (S.sb + S.fb);
+        S.sym = std::move(out.sym); S.len = std::move(out.len);
+        S.alpha = std::move(W.alpha);
+        prim::sync();
+    }
+    static void select_emit(const ImageSelect &S, u8 *out, u64 capacity) {
+        if (capacity < S.out_bytes) throw prim::Error(-22, "select: output buffer too small (" + std::to_string(S.out_bytes) + " bytes needed)");
+        emit_records(S.sym.p, RunLen{S.len.p, nullptr}, S.R_out, (u32)S.sb, (u32)S.fb, S.alpha.p, out, "select.pack");
+        prim::sync();
+    }
+    static void select_rows(const ImageSelect &S, u64 *dev_bits) {
+        prim::d2d(dev_bits, S.marked.p, (S.n_in + 63) / 64 * 8);
+        prim::sync();
+    }
+
+    // number of symbols an image describes, summed in 64 bits whatever the index width of the caller
+    static u64 image_total_symbols(const void *dev_image, u64 image_bytes) {
+        ImageHeader h = image_header(dev_image, image_bytes);
+        return prim::reduce_sum<u64>(h.R, ImageLenIn{h.recs(dev_image)}, "image.total");
+    }
+    // grl2plain (scripts/grl2plain.cpp): the plain BWT, one byte per symbol; null_char >= 0 replaces symbol 0
+    static u64 image_plain(const void *dev_image, u64 image_bytes, u8 *dev_out, u64 capacity, int null_char) {
+        ImageHeader h = image_header(dev_image, image_bytes);
+        DBuf<u32> rsym(h.R);
+        DBuf<idx_t> rlen(h.R), rpos(h.R + 1);
+        prim::for_each(h.R, UnpackRunsFn<u32>{h.recs(dev_image), rsym.p, rlen.p}, "plain.unpack");
+        prim::for_each(h.R, PlainSymFn{h.recs(dev_image), null_char, rsym.p}, "plain.bytes");
+        const u64 R = drop_empty_runs(rsym, rlen, h.R);
+        u64 n = (u64)prim::exclusive_scan<idx_t>(R, IdxIn<idx_t>{rlen.p}, rpos.p, true, "plain.positions");
+        if (n > capacity) throw prim::Error(-22, "grl2plain: output buffer too small");
+        RankBits rb;
+        build_rankbits(rb, rpos.p, R, n + 1, "plain.runbits");
+        prim::for_each(n, PlainRunsFn{rsym.p, rb.words.p, rb.base.p, dev_out}, "plain.expand");
+        prim::sync();
+        return n;
+    }
+    // grlbwt2rle (scripts/grlbwt2rle.cpp): the two RLE arrays
+    static u64 image_rle(const void *dev_image, u64 image_bytes, u8 *dev_syms, u32 *dev_lens, u64 capacity_runs) {
+        ImageHeader h = image_header(dev_image, image_bytes);
+        if (h.R > capacity_runs) throw prim::Error(-22, "grlbwt2rle: output buffers too small");
+        DBuf<u32> rsym(h.R);
+        DBuf<idx_t> rlen(h.R);
+        prim::for_each(h.R, UnpackRunsFn<u32>{h.recs(dev_image), rsym.p, rlen.p}, "rle.unpack");
+        prim::for_each(h.R, RleExportFn{rsym.p, rlen.p, dev_syms, dev_lens}, "rle.export");
+        prim::sync();
+        return h.R;
+    }
+    // bwt_stats (scripts/bwt_stats.cpp:18-98), byte alphabets (the reference indexes 256-entry tables by the symbol)
+    struct ImageStats {
+        u64 n_runs, sigma, text_size, min_run, max_run, fit1, fit2, fit3;
+        u64 runs_of[256], freq_of[256];
+        u64 deciles[9];
+        u64 non_maximal;
+    };
+    static void image_stats(const void *dev_image, u64 image_bytes, ImageStats &st) {
+        ImageHeader h = image_header(dev_image, image_bytes);
+        if (h.sb != 1) throw prim::Error(-22, "bwt_stats: byte alphabets only (sb == 1)");
+        if (h.R == 0) throw prim::Error(-22, "bwt_stats: empty BWT");
+        const u64 R = h.R;
+        DBuf<u32> rsym(R);
+        DBuf<idx_t> rlen(R);
+        prim::for_each(R, UnpackRunsFn<u32>{h.recs(dev_image), rsym.p, rlen.p}, "stats.unpack");
+        st.n_runs = R;
+        st.min_run = prim::reduce_min<u64>(R, IdxIn64{rlen.p}, "stats.min_run");
+        st.max_run = prim::reduce_max<u64>(R, IdxIn64{rlen.p}, "stats.max_run");
+        st.text_size = prim::reduce_sum<u64>(R, IdxIn64{rlen.p}, "stats.text_size");
+        st.fit1 = prim::reduce_sum<u64>(R, LenFitIn{rlen.p, 1}, "stats.fit1");
+        st.fit2 = prim::reduce_sum<u64>(R, LenFitIn{rlen.p, 2}, "stats.fit2");
+        st.fit3 = R - st.fit1 - st.fit2;
+        st.non_maximal = R - prim::reduce_sum<u64>(R, SymHeadIn64{rsym.p}, "stats.maximal");
+        DBuf<u64> bins(256);
+        bins.zero();
+        prim::for_each_agg(R, RunSymFn{rsym.p}, BinAddFn{bins.p}, true, "stats.runs_per_symbol");
+        std::vector<u64> hb = bins.to_host(256);
+        st.sigma = 0;
+        for (int c = 0; c < 256; c++) {
+            st.runs_of[c] = hb[c];
+            st.freq_of[c] = hb[c] ? prim::reduce_sum<u64>(R, SepLenIn{rsym.p, rlen.p, (u32)c}, "stats.freq") : 0;
+            if ((hb[c] & 0xFFu) != 0) st.sigma++;       // the reference iterates the table as unsigned char (:57-62)
+        }
+        // deciles of the sorted run lengths (uint32 like the reference's vector), index ceil(R * k/10) with the
+        // reference's accumulated double (:83-89); an index past the end (R < 10) is clamped to the last run
+        DBuf<u32> ka(R), kb(R), va(R), vb(R);
+        prim::for_each(R, LenKeyFn{rlen.p, ka.p, va.p}, "stats.len_keys");
+        int res = prim::sort_pairs<u32, u32>(ka.p, va.p, kb.p, vb.p, R, 0, 32, "stats.sort");
+        const DBuf<u32> &sorted = res ? kb : ka;
+        double l = (double)R, prop = 0.1;
+        for (int i = 0; i < 9; i++) {
+            u64 q = (u64)std::ceil(l * prop);
+            if (q >= R) q = R - 1;
+            st.deciles[i] = sorted.get(q);
+            prop += 0.1;
+        }
+    }
+
+    // split_runs (scripts/split_runs.cpp): re-encode an image with run lengths of at most 2^bits - 1 and, for
+    // block_size > 0, no run crossing a multiple of block_size; run-length field of ceil(bits/8) bytes.  block_size 0
+    // = no partition (what the reference's usage text promises; its own code asserts there).
+    struct SplitInfo { u64 runs_before, runs_after, overflow_splits, block_splits, n_syms, out_bytes; };
+    static SplitInfo image_split_runs(const void *dev_image, u64 image_bytes, int bits, u64 block_size, u8 *dev_out, u64 capacity_bytes) {
+        ImageHeader h = image_header(dev_image, image_bytes);
+        if (bits < 1 || bits > 63) throw prim::Error(-22, "split_runs: bits must be in [1, 63]");
+        const u64 L = (1ull << bits) - 1, B = block_size, R = h.R;
+        const u32 fb2 = (u32)((bits + 7) / 8);
+        // (the pieces carry their symbol in 32 bits: a wider one is refused, not cut)
+        if (h.sb > 4 && prim::reduce_max<u64>(R, ImageSymIn{h.recs(dev_image)}, "split.max_sym") >> 32)
+            throw prim::Error(-22, "split_runs: symbols >= 2^32 are not supported");
+        DBuf<u32> rsym(R);
+        DBuf<idx_t> rlen(R), rpos(R + 1), jbase(R + 1);
+        prim::for_each(R, UnpackRunsFn<u32>{h.recs(dev_image), rsym.p, rlen.p}, "split.unpack");
+        const u64 n = (u64)prim::exclusive_scan<idx_t>(R, IdxIn<idx_t>{rlen.p}, rpos.p, true, "split.positions");
+        const u64 J = (u64)prim::exclusive_scan<idx_t>(R, PieceCountFn{rlen.p, L}, jbase.p, true, "split.pieces");
+        const u64 cuts = (B && n > 0) ? (n - 1) / B : 0;
+        SplitInfo si{R, J + cuts, J - R, cuts, n, 16 + (J + cuts) * (u64)(h.sb + fb2)};
+        if (si.out_bytes > capacity_bytes) throw prim::Error(-22, "split_runs: output buffer too small");
+        RankBits jb;
+        build_rankbits(jb, jbase.p, R, J + 1, "split.piecebits");
+        DBuf<u32> osym(si.runs_after);
+        DBuf<idx_t> olen(si.runs_after);
+        prim::for_each(J, SplitRunsFn{rsym.p, rlen.p, rpos.p, jbase.p, jb.words.p, jb.base.p, L, B, osym.p, olen.p}, "split.emit");
+        u8 hdr[16] = {0};
+        for (int i = 0; i < 8; i++) { hdr[i] = (u8)(h.sb >> (8 * i)); hdr[8 + i] = (u8)((u64)fb2 >> (8 * i)); }
+        prim::h2d(dev_out, hdr, 16);
+        prim::for_each(si.runs_after, PackRunsFn{osym.p, RunLen{olen.p, nullptr}, (u32)h.sb, fb2, dev_out, 16u}, "split.pack");
+        prim::sync();
+        return si;
+    }
+};
+
+}   // namespace GRL_NS
+
+#endif   // once per index width

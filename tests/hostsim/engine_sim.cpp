@@ -17,6 +17,7 @@
 #define GRL_IDX_T uint32_t
 #define GRL_IDX_BYTES 4
 #include "../../grlbwt_amd/csrc/engine_impl.hpp"
+#include "../../grlbwt_amd/csrc/image_impl.hpp"
 #undef GRL_NS
 #undef GRL_IDX_T
 #undef GRL_IDX_BYTES
@@ -25,6 +26,7 @@
 #define GRL_IDX_T uint64_t
 #define GRL_IDX_BYTES 8
 #include "../../grlbwt_amd/csrc/engine_impl.hpp"
+#include "../../grlbwt_amd/csrc/image_impl.hpp"
 #undef GRL_NS
 #undef GRL_IDX_T
 #undef GRL_IDX_BYTES

@@ -119,6 +119,6 @@ def test_environment_switches_of_the_product_are_few(hip_lib):
     assert len(names) <= 35, sorted(names)
     assert names == product, (sorted(names - product), sorted(product - names))
     # the switches are read in switches.hpp alone
-    for f in ("engine_impl.hpp", "prim_hip.hpp", "capi_impl.hpp"):
+    for f in ("engine_impl.hpp", "image_impl.hpp", "prim_hip.hpp", "capi_impl.hpp"):
         src = open(os.path.join(ROOT, "grlbwt_amd", "csrc", f)).read()
         assert not re.findall(r"\b(?:getenv|test_env|dev_env)\(", src), f
