@@ -2080,6 +2080,35 @@ int grlbwt_fm_match_info_get(const grlbwt_fm *fm, grlbwt_fm_match_info *out) {
     if (fm->f32) fill(*fm->f32); else fill(*fm->f64);
     return GRLBWT_OK;
 }
+int grlbwt_fm_approx(grlbwt_ctx *ctx, const grlbwt_fm *fm, const void *dev_cells, int cell_bytes, const uint64_t *dev_offsets,
+                     uint64_t n_patterns, uint32_t max_mismatches, uint64_t max_hits, uint64_t *dev_hit_offsets, uint64_t *dev_mism,
+                     uint64_t *dev_lo, uint64_t *dev_hi, uint64_t *dev_sub_pos, uint64_t *dev_sub_val, uint64_t capacity, uint64_t *n_hits_out) {
+    if (n_hits_out) *n_hits_out = 0;
+    if (!ctx || !fm || !(fm->f32 || fm->f64)) return GRLBWT_EINVAL;
+    if (n_patterns && !dev_offsets) return GRLBWT_EINVAL;
+    uint64_t n = 0;
+    const int rc = guarded(ctx, [&] {
+        if (fm->f32) grl32::Image::fm_approx(*fm->f32, dev_cells, cell_bytes, dev_offsets, n_patterns, max_mismatches, max_hits, dev_hit_offsets, dev_mism,
+                                              dev_lo, dev_hi, dev_sub_pos, dev_sub_val, capacity, n);
+        else grl64::Image::fm_approx(*fm->f64, dev_cells, cell_bytes, dev_offsets, n_patterns, max_mismatches, max_hits, dev_hit_offsets, dev_mism,
+                                      dev_lo, dev_hi, dev_sub_pos, dev_sub_val, capacity, n);
+    });
+    if (n_hits_out) *n_hits_out = n;
+    return rc;
+}
+int grlbwt_fm_approx_info_get(const grlbwt_fm *fm, grlbwt_fm_approx_info *out) {
+    if (!fm || !out || !(fm->f32 || fm->f64)) return GRLBWT_EINVAL;
+    auto fill = [&](const auto &F) {
+        const auto &a = F.ainfo;
+        out->n_patterns = a.patterns; out->n_cells = a.cells; out->max_mismatches = a.k; out->max_hits = a.max_hits;
+        out->n_hits = a.hits;
+        for (int d = 0; d < 4; d++) out->hits_by_mismatches[d] = a.by[d];
+        out->n_truncated = a.cut; out->steps = a.steps; out->walk_lanes = a.lanes; out->lane_refills = a.refills;
+        out->table_bytes = 0;
+    };
+    if (fm->f32) fill(*fm->f32); else fill(*fm->f64);
+    return GRLBWT_OK;
+}
 int grlbwt_fm_locate(grlbwt_ctx *ctx, const grlbwt_fm *fm, const uint64_t *dev_rows, uint64_t n_rows, uint64_t max_steps,
                      uint64_t *dev_string, uint64_t *dev_offset) {
     if (!ctx || !fm || !(fm->f32 || fm->f64)) return GRLBWT_EINVAL;

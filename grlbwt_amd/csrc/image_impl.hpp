@@ -488,6 +488,155 @@ struct FmMemEmitFn {      // prim::for_each_set_bit over those flags: entry `ord
         if (lo) { lo[ord] = slo[t]; hi[ord] = shi[t]; }
     }
 };
+// ---- patterns with up to k substituted cells (grlbwt_fm_approx).  Ticket i is pattern i, of m cells.  The search
+// runs from the pattern's last cell to its first; at a cell, with range r and d substitutions made, it first tries, while d < k,
+// every symbol of the image above the separator other than the pattern's own cell in ascending order -- each one that leaves a
+// non-empty range is followed with d + 1 -- and then the pattern's own cell with d.  The own cell comes last, so nothing has to
+// be kept for it: the whole state is the current (x, lo, hi) and one Frame per substitution made, at most k = 3 of them, held in
+// NAMED members among whose VALUES the depth chooses (an array indexed by it goes to scratch).  A cell that is no symbol, or
+// the separator, has no own step: only a substitution passes it.  x = 0 is a hit: entry (d, [lo, hi), the frames' offsets and
+// symbols).  The symbols present come from the keys: the next one above c is the symbol of the key at the lower bound of
+// (c + 1, 0), one more search under the top level; no table is kept.
+//   Two passes of this one search: cnt[i] = hits | cut << 63 while `mism` is null; then, with hoff = the scanned counts, the
+//   entries, cnt[i] = the pass's backward steps, and `bad` where a pattern found another number of hits than it had counted.
+//   The emit pass never stores past hoff[i + 1].  With max_hits the search ends at the first hit beyond it: that is what says
+//   the list was longer.
+//   Loops: step() holds none but the binary searches; over an item, steps per frame <= sigma, frames <= k, cells <= m.
+struct FmApproxFn {
+    typedef FmKey Key;
+    struct Frame { u64 x, lo, hi; u32 cur; };      // the node where a substitution was made (x cells were left), and the substitute
+    struct State {
+        u64 x0, x, lo, hi, cnt, base, room, steps;
+        u32 d, cur;                // substitutions made; the last substitute tried at this node (the separator: none yet)
+        bool sub, cut;             // substitutes are still to be tried here; the list was cut at max_hits
+        u64 x_0, x_1, x_2, lo_0, lo_1, lo_2, hi_0, hi_1, hi_2;      // the frames, member by member: every access names its member,
+        u32 c_0, c_1, c_2;                                          // so that the state stays in registers
+    };
+    FmCountFn f; u32 sep; u64 sepval; u32 k; u64 max_hits;
+    u64 *cnt; const u64 *hoff; u64 *mism, *lo, *hi, *spos, *sval; u32 *bad;
+    GRL_HD const FmKey *keys() const { return f.key; }
+    GRL_HD u64 n_keys() const { return f.R; }
+    // Every member is read and written where it stands and the depth only chooses among VALUES: a store under a switch on the
+    // depth is merged by the compiler into one store through a chosen address, and the frames are back in scratch.
+    template <class T>
+    GRL_DEV static T pick(u32 d, T a0, T a1, T a2) { return d == 0 ? a0 : d == 1 ? a1 : a2; }
+    template <class T>
+    GRL_DEV static void put(u32 d, T v, T &a0, T &a1, T &a2) {
+        const T b0 = a0, b1 = a1, b2 = a2;
+        a0 = d == 0 ? v : b0; a1 = d == 1 ? v : b1; a2 = d >= 2 ? v : b2;
+    }
+    GRL_DEV static void save(State &st, u32 d, const Frame &fr) {
+        put(d, fr.x, st.x_0, st.x_1, st.x_2); put(d, fr.lo, st.lo_0, st.lo_1, st.lo_2);
+        put(d, fr.hi, st.hi_0, st.hi_1, st.hi_2); put(d, fr.cur, st.c_0, st.c_1, st.c_2);
+    }
+    GRL_DEV static Frame load(const State &st, u32 d) {
+        return Frame{pick(d, st.x_0, st.x_1, st.x_2), pick(d, st.lo_0, st.lo_1, st.lo_2), pick(d, st.hi_0, st.hi_1, st.hi_2),
+                     pick(d, st.c_0, st.c_1, st.c_2)};
+    }
+    template <class TOP>
+    GRL_DEV bool next_sym(u32 c, const TOP &top, u32 &out) const {      // the smallest symbol of the image above c
+        if (c == ~0u) return false;
+        u64 a = 0, b = f.R;
+        top.narrow(c + 1, 0, a, b);
+        for (int it = 0; it < 64 && a < b; it++) { const u64 mid = (a + b) >> 1; if (f.key[mid].below(c + 1, 0)) a = mid + 1; else b = mid; }
+        if (a >= f.R) return false;
+        out = f.key[a].sym();
+        return true;
+    }
+    GRL_DEV void hit(State &st) const {
+        if (max_hits && st.cnt == max_hits) { st.cut = true; return; }
+        if (mism && st.cnt < st.room) {
+            const u64 j = st.base + st.cnt;
+            mism[j] = (u64)st.d; lo[j] = st.lo; hi[j] = st.hi;
+            if (spos) {
+#pragma unroll
+                for (u32 s = 0; s < 3; s++) {                            // (k <= 3; unrolled: every load names its frame)
+                    if (s >= k) break;
+                    const Frame fr = load(st, s);
+                    spos[j * k + s] = s < st.d ? fr.x - 1 : ~0ull;
+                    sval[j * k + s] = s < st.d ? (f.alpha ? f.alpha[fr.cur] : (u64)fr.cur) : ~0ull;
+                }
+            }
+        }
+        st.cnt++;
+    }
+    // back to the node of the last substitution; true: there is none, the search is over
+    GRL_DEV bool pop(State &st) const {
+        if (st.d == 0) return true;
+        st.d--;
+        const Frame fr = load(st, st.d);
+        st.x = fr.x; st.lo = fr.lo; st.hi = fr.hi; st.cur = fr.cur; st.sub = true;
+        return false;
+    }
+    GRL_DEV bool enter(State &st) const {                                // a node was reached with a non-empty range
+        if (st.x == 0) { hit(st); return st.cut || pop(st); }
+        st.sub = st.d < k; st.cur = sep;
+        return false;
+    }
+    GRL_DEV bool begin(u64 i, State &st) const {
+        st.x0 = f.off[i]; st.x = f.off[i + 1] - st.x0;
+        st.lo = 0; st.hi = f.n; st.cnt = 0; st.steps = 0; st.d = 0; st.cur = sep; st.sub = false; st.cut = false;
+        st.base = mism ? hoff[i] : 0; st.room = mism ? hoff[i + 1] - st.base : 0;
+        st.x_0 = st.x_1 = st.x_2 = st.lo_0 = st.lo_1 = st.lo_2 = st.hi_0 = st.hi_1 = st.hi_2 = 0; st.c_0 = st.c_1 = st.c_2 = 0;
+        if ((st.x && st.lo >= st.hi) || enter(st)) { end(i, st); return false; }      // (an index of no symbol; a pattern of no cell)
+        return true;
+    }
+    template <class TOP>
+    GRL_DEV bool step(State &st, const TOP &top) const {                // at most ONE fm_step
+        const u64 v = f.cell(st.x0 + st.x - 1);
+        u32 qc = 0, c = 0;
+        const bool own = f.code(v, qc) && v != sepval;
+        bool have = false;
+        if (st.sub) {
+            have = next_sym(st.cur, top, c);
+            if (have && own && c == qc) have = next_sym(qc, top, c);
+            st.sub = have;
+        }
+        if (!have) {
+            if (!own) return pop(st);
+            c = qc;
+        }
+        u64 a = st.lo, b = st.hi;
+        fm_step(f.key, f.slf, f.R, top, c, a, b);
+        st.steps++;
+        if (have) st.cur = c;
+        if (a >= b) return have ? false : pop(st);
+        if (have) { save(st, st.d, Frame{st.x, st.lo, st.hi, c}); st.d++; }
+        st.x--; st.lo = a; st.hi = b;
+        return enter(st);
+    }
+    GRL_DEV bool step(State &st) const { return step(st, FmNoTop{}); }
+    GRL_DEV void end(u64 i, const State &st) const {
+        if (!mism) { cnt[i] = st.cnt | (u64)st.cut << 63; return; }
+        if (st.cnt != st.room) prim::atomic_max(bad, 1u);
+        cnt[i] = st.steps;
+    }
+};
+struct FmApproxLaneFn {   // the same, one lane per pattern through prim::top_search (GRLBWT_FM_MATCH=l)
+    typedef FmKey Key;
+    FmApproxFn f;
+    GRL_HD const FmKey *keys() const { return f.keys(); }
+    GRL_HD u64 n_keys() const { return f.n_keys(); }
+    template <class TOP>
+    GRL_DEV void operator()(u64 i, const TOP &top) const {
+        FmApproxFn::State st;
+        if (!f.begin(i, st)) return;
+        while (!f.step(st, top)) {}                                      // (bounded as said above)
+        f.end(i, st);
+    }
+};
+struct FmApproxHitsIn {   // the count pass's word without its flag; the flag
+    const u64 *cnt;
+    GRL_DEV u64 operator()(u64 i) const { return cnt[i] & ~(1ull << 63); }
+};
+struct FmApproxCutIn {
+    const u64 *cnt;
+    GRL_DEV u64 operator()(u64 i) const { return cnt[i] >> 63; }
+};
+struct FmApproxMismIn {
+    const u64 *mism; u64 d;
+    GRL_DEV u64 operator()(u64 j) const { return mism[j] == d ? 1ull : 0ull; }
+};
 // sid: string i's walk (RunInvertLenFn's) ends at the row r that holds its separator; that separator is the LF(r)-th of the
 // BWT.  The LF map of any image is a permutation, so a walk from one of the first k rows comes back to one of them after at
 // most n steps; the bound is there for an index that is not what it should be.
@@ -1209,6 +1358,7 @@ struct Image {
     // ---- the FM index over the runs of an image (grlbwt_fm_*; functor block "counting and locating patterns") ----------------
     struct ExtractInfo { u64 ranges = 0, pieces = 0, cells = 0, steps = 0, lanes = 0, refills = 0; };      // of the last fm_extract
     struct MatchInfo { u64 patterns = 0, cells = 0, matched = 0, longest = 0, capped = 0, mems = 0, lanes = 0, refills = 0; };
+    struct ApproxInfo { u64 patterns = 0, cells = 0, k = 0, max_hits = 0, hits = 0, by[4] = {0, 0, 0, 0}, cut = 0, steps = 0, lanes = 0, refills = 0; };
     struct FmIndex {
         u64 n = 0, R = 0, k = 0, sigma = 0, sepval = 0;
         u32 sep = 0, top_entries = 0;
@@ -1229,6 +1379,7 @@ struct Image {
         DBuf<idx_t> T, xq, xc;
         mutable ExtractInfo xinfo;
         mutable MatchInfo minfo;  // of the last fm_match / fm_mems
+        mutable ApproxInfo ainfo; // of the last fm_approx
         u64 extract_bytes() const { return (T.n + xq.n + xc.n) * sizeof(idx_t); }
         u64 bytes() const {
             return key.n * sizeof(FmKey) + slf.n * sizeof(idx_t) + alpha.n * 8 + rc.n * sizeof(RankCell) + rec.n * sizeof(RunRec) + sid.n * sizeof(idx_t) +
@@ -1415,6 +1566,67 @@ struct Image {
         prim::for_each_set_bit<u64>(nc, words.p, base.p, FmMemEmitFn{L.p, slo.p, shi.p, off, x0, np, pat, beg, mlen, lo, hi}, "fm.mems");
         prim::sync();
         F.minfo = mi;
+    }
+    // ---- patterns with up to k substituted cells (functor block "patterns with up to k substituted cells").
+    // Everything that can refuse the call runs before the first store into an output: the count pass writes scratch only (one word
+    // per pattern), its sum is held against the capacity, then the scan writes dev_hit_offsets and the emit pass the entries.  One
+    // ticket per pattern through prim::top_tickets -- neighbouring patterns differ by orders of magnitude in cost, a lane whose
+    // search has ended takes the next pattern -- or with GRLBWT_FM_MATCH=l one lane per pattern through prim::top_search; the
+    // stand-in runs the same functor serially.
+    //   The compiler's report for gfx950 (tools/kernel_resources.py; profiles/fm_approx/kernel_resources.txt):
+    //   k_top_tickets<FmApproxFn> 95 VGPRs, 5 waves per SIMD; k_top_search<FmApproxLaneFn> 67 / 66 (32- / 64-bit positions), 7 waves; no scratch in either.
+    static void fm_approx_run(const FmIndex &F, const FmApproxFn &f, u64 np, ApproxInfo &ai) {
+#ifdef GRLBWT_PRIM_HIP
+        if (prim::sw().fm_match == 'l') {
+            prim::top_search(np, FmApproxLaneFn{f}, F.top_entries, "fm.approx_lanes");
+            ai.lanes = np; ai.refills = 0;
+        } else {
+            DBuf<u64> ctr(2);
+            const prim::WalkStats ws = prim::top_tickets(np, f, ctr.p, F.top_entries, "fm.approx");
+            ai.lanes = ws.lanes; ai.refills = ws.refills;
+        }
+#else
+        prim::for_each(np, WalkSerialFn<FmApproxFn>{f}, "fm.approx");
+        ai.lanes = np; ai.refills = 0;
+#endif
+    }
+    static constexpr u32 kApproxMaxK = 3;
+    // n_hits is set whenever the count was reached, also when the capacity then refuses the call
+    static void fm_approx(const FmIndex &F, const void *cells, int w, const u64 *off, u64 np, u32 k, u64 max_hits, u64 *hoff, u64 *mism, u64 *lo, u64 *hi,
+                          u64 *spos, u64 *sval, u64 capacity, u64 &n_hits) {
+        n_hits = 0;
+        if (k > kApproxMaxK) throw prim::Error(-22, "fm approx: at most 3 substitutions");
+        if ((spos == nullptr) != (sval == nullptr)) throw prim::Error(-22, "fm approx: the substitution outputs are both given or both null");
+        u64 x0;
+        const u64 nc = fm_match_cells(cells, w, off, np, x0, "fm approx");
+        ApproxInfo ai;
+        ai.patterns = np; ai.cells = nc; ai.k = k; ai.max_hits = max_hits;
+        if (np == 0) {
+            if (hoff) prim::dev_memset(hoff, 0, 8);
+            prim::sync();
+            F.ainfo = ai;
+            return;
+        }
+        if (np >= (~0ull >> 4) || (np + 1) * 8 + 64 > prim::mem_available())
+            throw prim::Error(-12, "fm approx: the counts need " + std::to_string((np + 1) * 8) + " bytes of device memory, more than is free");
+        DBuf<u64> cnt(np + 1);
+        DBuf<u32> bad(1);
+        bad.zero();
+        FmApproxFn f{fm_count_fn(F, cells, w, off, nullptr, nullptr), F.sep, F.sepval, k, max_hits, cnt.p, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, bad.p};
+        fm_approx_run(F, f, np, ai);
+        ai.hits = n_hits = prim::reduce_sum<u64>(np, FmApproxHitsIn{cnt.p}, "fm.approx_hits");
+        ai.cut = prim::reduce_sum<u64>(np, FmApproxCutIn{cnt.p}, "fm.approx_cut");
+        if (n_hits > capacity) throw prim::Error(-22, "fm approx: " + std::to_string(n_hits) + " hits, more than the output arrays hold");
+        if (!hoff || (n_hits && (!mism || !lo || !hi))) throw prim::Error(-22, "fm approx: no output arrays");      // (the sizing call takes none)
+        prim::exclusive_scan<u64>(np, FmApproxHitsIn{cnt.p}, hoff, true, "fm.approx_offsets");
+        // (without a hit the arrays may be missing: the pass then stores no entry, and the spare scratch word marks it as the emit pass)
+        f.hoff = hoff; f.mism = mism ? mism : cnt.p + np; f.lo = lo; f.hi = hi; f.spos = k ? spos : nullptr; f.sval = k ? sval : nullptr;
+        fm_approx_run(F, f, np, ai);
+        if (bad.get(0)) throw prim::Error(-71, "fm approx: a pattern's second pass found another number of hits than its first");
+        ai.steps = prim::reduce_sum<u64>(np, CellIn<u64>{cnt.p}, "fm.approx_steps");
+        for (u32 d = 0; d <= k && n_hits; d++) ai.by[d] = prim::reduce_sum<u64>(n_hits, FmApproxMismIn{mism, (u64)d}, "fm.approx_strata");
+        prim::sync();
+        F.ainfo = ai;
     }
     static void fm_locate(const FmIndex &F, const u64 *rows, u64 nr, u64 max_steps, u64 *str, u64 *ofs) {
         if (!F.locate) throw prim::Error(-22, "fm locate: the index was made without the structures for locating");

@@ -41,7 +41,7 @@
     X(GRLBWT_XS_MAXC, xs_maxc, int, 32, "most cells per item the fused expansion sort takes (lower: the unfused branch)")        \
     X(GRLBWT_ALPHA_TABLE_BITS, alpha_table_bits, int, 20, "log2 of the slots of the alphabet compaction's table, 2..26 (lower: the sorting regime)") \
     X(GRLBWT_FM_TOP_BITS, fm_top_bits, int, 12, "log2 of the keys of an FM index's search array kept in LDS, 0..12 (0: none; lower: small indexes search HBM)") \
-    X(GRLBWT_FM_MATCH, fm_match, char, 0, "l[anes]: grlbwt_fm_match / grlbwt_fm_mems with one lane per query cell and no refilling, not lanes that take tickets") \
+    X(GRLBWT_FM_MATCH, fm_match, char, 0, "l[anes]: grlbwt_fm_match / grlbwt_fm_mems with one lane per query cell, grlbwt_fm_approx with one lane per pattern, and no refilling, not lanes that take tickets") \
     X(GRLBWT_WALK_LANES, walk_lanes, uint64_t, 0, "most lanes of a checkpointed walk launch, rounded up to a wave (0: from occupancy; lower: small inputs refill their lanes)") \
     X(GRLBWT_MERGE_ROUND, merge_round, char, 0, "s[ort]: a round of the image merge as gathered keys and a stable sort, not the fused kernels") \
     X(GRLBWT_IO_THREADS, io_threads, int, 0, "reader / writer threads per file chunk, 1..64 (0: from the host's cores)")         \

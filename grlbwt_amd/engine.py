@@ -37,6 +37,7 @@ ABI_SYMBOLS = [
     "grlbwt_invert_image_checkpointed", "grlbwt_fm_walk_info_get",
     "grlbwt_fm_string_lengths", "grlbwt_fm_extract", "grlbwt_fm_extract_info_get",
     "grlbwt_fm_match", "grlbwt_fm_mems", "grlbwt_fm_match_info_get",
+    "grlbwt_fm_approx", "grlbwt_fm_approx_info_get",
     "grlbwt_merge_create", "grlbwt_merge_info_get", "grlbwt_merge_emit", "grlbwt_merge_interleave", "grlbwt_merge_destroy",
     "grlbwt_merge_files",
     "grlbwt_select_create", "grlbwt_select_info_get", "grlbwt_select_emit", "grlbwt_select_rows", "grlbwt_select_destroy",
@@ -82,6 +83,12 @@ class ExtractInfo(C.Structure):
 class MatchInfo(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in ("n_patterns", "n_cells", "matched_cells", "longest", "n_capped", "n_mems", "walk_lanes",
                                           "lane_refills")]
+
+
+class ApproxInfo(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("n_patterns", "n_cells", "max_mismatches", "max_hits", "n_hits")] + \
+               [("hits_by_mismatches", C.c_uint64 * 4)] + \
+               [(k, C.c_uint64) for k in ("n_truncated", "steps", "walk_lanes", "lane_refills", "table_bytes")]
 
 
 class ImageStats(C.Structure):
@@ -239,6 +246,8 @@ def load_library(path=None, allow_test_standin=False):
     L.grlbwt_fm_match.argtypes = [vp, vp, vp, i32, vp, u64, u64, vp, vp, vp]
     L.grlbwt_fm_mems.argtypes = [vp, vp, vp, i32, vp, u64, u64, u64, vp, vp, vp, vp, vp, u64, C.POINTER(u64)]
     L.grlbwt_fm_match_info_get.argtypes = [vp, C.POINTER(MatchInfo)]
+    L.grlbwt_fm_approx.argtypes = [vp, vp, vp, i32, vp, u64, C.c_uint32, u64, vp, vp, vp, vp, vp, vp, u64, C.POINTER(u64)]
+    L.grlbwt_fm_approx_info_get.argtypes = [vp, C.POINTER(ApproxInfo)]
     L.grlbwt_merge_create.argtypes = [vp, vp, u64, vp, u64, i32, u64, C.POINTER(vp)]
     L.grlbwt_merge_info_get.argtypes = [vp, C.POINTER(MergeInfo)]
     L.grlbwt_merge_emit.argtypes = [vp, vp, vp, u64]
@@ -642,6 +651,35 @@ class FmIndex:
         if rc != OK:
             raise GrlbwtError(rc, self.ctx.L.grlbwt_strerror(rc).decode())
         return _as_dict(out)
+
+    def approx(self, cells_ptr, cell_bytes, offsets_ptr, n, max_mismatches, max_hits, hit_offsets_ptr, mism_ptr, lo_ptr, hi_ptr,
+               capacity, sub_pos_ptr=None, sub_val_ptr=None):
+        """Every occurrence of the n patterns (given as to count()) with at most max_mismatches (0 to 3) substituted cells: the
+        hits of pattern i are entries [hit_offsets[i], hit_offsets[i + 1]) of (mism, lo, hi), in the order of the search (at a
+        cell, from the last one on: the other symbols ascending, then the pattern's own); max_hits cuts each list (0: no cap).
+        sub_pos / sub_val, both or neither, receive max_mismatches words per entry: the substituted offsets in descending order
+        and the substitutes, UINT64_MAX in unused slots.  The number of hits is returned.  More than `capacity`: GrlbwtError
+        whose n_hits attribute is that number, and nothing is written."""
+        got = C.c_uint64()
+        try:
+            self.ctx._ck(self.ctx.L.grlbwt_fm_approx(self.ctx._h, self._h, C.c_void_p(cells_ptr), cell_bytes, C.c_void_p(offsets_ptr), n,
+                                                     max_mismatches, max_hits, C.c_void_p(hit_offsets_ptr), C.c_void_p(mism_ptr),
+                                                     C.c_void_p(lo_ptr), C.c_void_p(hi_ptr), C.c_void_p(sub_pos_ptr), C.c_void_p(sub_val_ptr),
+                                                     capacity, C.byref(got)))
+        except GrlbwtError as e:
+            e.n_hits = got.value
+            raise
+        return got.value
+
+    def approx_info(self):
+        """The counters of the last approx() on this index; hits_by_mismatches as a list of four."""
+        out = ApproxInfo()
+        rc = self.ctx.L.grlbwt_fm_approx_info_get(self._h, C.byref(out))
+        if rc != OK:
+            raise GrlbwtError(rc, self.ctx.L.grlbwt_strerror(rc).decode())
+        d = _as_dict(out)
+        d["hits_by_mismatches"] = [int(v) for v in out.hits_by_mismatches]
+        return d
 
     def close(self):
         h, self._h = getattr(self, "_h", None), None

@@ -427,6 +427,60 @@ int grlbwt_fm_mems(grlbwt_ctx *ctx, const grlbwt_fm *fm, const void *dev_cells, 
                    uint64_t *n_mems_out);
 int grlbwt_fm_match_info_get(const grlbwt_fm *fm, grlbwt_fm_match_info *out);
 
+/* ---- patterns with up to three substituted cells: every occurrence within Hamming distance k = max_mismatches of a pattern, as
+ * row ranges that feed grlbwt_fm_locate -- the backtracking search of the short-read aligners, for a read with a sequencing error
+ * or a query with an unknown base.  The call works on any index, with or without GRLBWT_FM_LOCATE, and takes its patterns exactly
+ * as grlbwt_fm_count and grlbwt_fm_match do (cell_bytes in {1, 2, 4, 8} whatever the image's width, n_patterns + 1 non-decreasing
+ * offsets, dev_offsets[0] may be above 0, compacted alphabets are searched on their ranks).
+ *
+ * A HIT of pattern q (m cells) is a string v of m cells that holds no separator, differs from q at no more than k offsets and
+ * occurs in the collection.  A cell of q that is no symbol of the image (a value too wide for it included), or that equals the
+ * separator, can only be matched by a substitution and costs one unit of the budget; a substitute is any symbol of the image
+ * except the separator and the pattern's own cell.  Different hits of one pattern have disjoint row ranges (LF is a permutation),
+ * so a hit is (number of substitutions, [lo, hi), where and what was substituted); its rows are what grlbwt_fm_count answers
+ * for v.  A pattern without cells has one hit, 0 substitutions and [0, n_syms); a pattern whose forced substitutions exceed k has
+ * none.  Unlike grlbwt_fm_count, and like grlbwt_fm_match, the separator never anchors a match and never fails the call.
+ *
+ * ORDER, part of the contract: the search runs from the last cell to the first; at a cell it first tries, while budget is left,
+ * every other non-separator symbol in ascending order and then the pattern's own cell.  For two hits u != v of one pattern, with
+ * x the largest offset where they differ: if one of them equals q[x] there, the other one comes first; otherwise the one with the
+ * smaller symbol at x.  max_hits (0: no cap) cuts each pattern's list after its first max_hits hits in this order; the
+ * pattern's search ends at the next hit it meets, which is what tells a cut list (n_truncated) from one of exactly max_hits.
+ * OUT OF SCOPE: choosing the best stratum only (all hits with up to k substitutions are reported, not just those with the
+ * fewest), and insertions or deletions.
+ *
+ * OUTPUT: the hits of pattern i are entries [dev_hit_offsets[i], dev_hit_offsets[i + 1]), back to back in pattern order;
+ * dev_hit_offsets[n_patterns] = *n_hits_out.  Entry j is (dev_mism[j], dev_lo[j], dev_hi[j]).  dev_sub_pos and dev_sub_val are
+ * given both or neither (one alone: GRLBWT_EINVAL); when given, entry j owns max_mismatches words of each, [j * k, (j + 1) * k):
+ * the substituted offsets inside the pattern in descending order and the substitute's value there (wide symbols as their
+ * values); unused slots hold UINT64_MAX.  *n_hits_out is always set once the count is known; with more hits than `capacity` the
+ * call fails with GRLBWT_EINVAL and writes no output array, dev_hit_offsets included (the sizing idiom of grlbwt_fm_mems: call
+ * with capacity 0 and no arrays).  GRLBWT_EINVAL before the first store: max_mismatches > 3, a cell_bytes not in {1, 2, 4, 8},
+ * decreasing offsets, dev_cells missing while there are cells, dev_hit_offsets missing while n_patterns > 0, hits without
+ * dev_mism / dev_lo / dev_hi, a null index.  GRLBWT_ENOMEM when the scratch, one word per pattern for the counts, does not fit.
+ * COST: the search runs twice, to count and to emit.  A backward step is grlbwt_fm_count's.  A cell at which a substitution
+ * is open costs sigma - 2 steps, each with one more search for the next symbol present (no table of the symbols is kept, the
+ * index holds what it held); the worst case grows like (m * sigma)^k / k!, pruned wherever a range empties.  Fine for DNA-like
+ * alphabets and reads; slow for large alphabets at k >= 2.  max_hits bounds the output, not the pruned tree.  One ticket per
+ * pattern: lanes whose search has ended take the next pattern (GRLBWT_WALK_LANES as for grlbwt_fm_match); GRLBWT_FM_MATCH=l runs
+ * one lane per pattern without refilling, with the same outputs; GRLBWT_FM_TOP_BITS as for grlbwt_fm_count.
+ * grlbwt_fm_approx_info_get: the counters of the last grlbwt_fm_approx that succeeded on the index. */
+#define GRLBWT_FM_APPROX_MAX_K 3
+typedef struct grlbwt_fm_approx_info {
+    uint64_t n_patterns, n_cells, max_mismatches, max_hits;   /* of the last grlbwt_fm_approx on this index */
+    uint64_t n_hits, hits_by_mismatches[4];
+    uint64_t n_truncated;              /* patterns cut at max_hits */
+    uint64_t steps;                    /* backward steps of the emitting pass */
+    uint64_t walk_lanes, lane_refills; /* of the emitting launch, as in grlbwt_walk_info */
+    uint64_t table_bytes;              /* 0 when no symbol table is kept: always, in this form */
+} grlbwt_fm_approx_info;
+int grlbwt_fm_approx(grlbwt_ctx *ctx, const grlbwt_fm *fm, const void *dev_cells, int cell_bytes, const uint64_t *dev_offsets,
+                     uint64_t n_patterns, uint32_t max_mismatches, uint64_t max_hits /* per pattern; 0: no cap */,
+                     uint64_t *dev_hit_offsets /* n_patterns + 1 words */, uint64_t *dev_mism, uint64_t *dev_lo, uint64_t *dev_hi,
+                     uint64_t *dev_sub_pos /* may be NULL */, uint64_t *dev_sub_val /* may be NULL */, uint64_t capacity,
+                     uint64_t *n_hits_out);
+int grlbwt_fm_approx_info_get(const grlbwt_fm *fm, grlbwt_fm_approx_info *out);
+
 /* ---- merging two images: the image of the collection "strings of A, then strings of B" from the images of A and B, without the
  * texts -- a collection larger than one build is built in batches and folded together, a batch of new strings is added to an
  * existing image.  String i of B becomes string n_strings_a + i.  When A and B were built by this engine with cells of cell_bytes,
