@@ -1556,6 +1556,52 @@ int test_merge_round(uint64_t n, uint64_t seed) {
     return 0;
 }
 
+// 13: the scan in two phases (SplitScan: total first, consumer second) against exclusive_scan + for_each, at the edges of a scan
+// tile and of the second level of tile sums, whatever n the caller gave; no flag set, every flag set, coin flips
+struct SelfSplitRefFn {
+    const uint8_t *f; const uint32_t *ex; uint32_t *pos;
+    GRL_DEV void operator()(uint64_t i) const { if (f[i]) pos[ex[i]] = (uint32_t)i; }
+};
+struct SelfSplitEmitFn {
+    static constexpr bool kWaveEmit = false;
+    uint32_t *pre; uint32_t *pos;
+    GRL_DEV void operator()(uint64_t i, uint32_t ex, uint32_t v) const { pre[i] = ex; if (v) pos[ex] = (uint32_t)i; }
+};
+int test_split_scan(uint64_t seed) {
+    const uint64_t tile = 2048, sizes[7] = {1, tile - 1, tile, tile + 1, tile * tile - 1, tile * tile, tile * tile + 1};
+    for (int si = 0; si < 7; si++)
+        for (int density = 0; density < 3; density++) {
+            const uint64_t n = sizes[si];
+            std::vector<uint8_t> f(n);
+            uint64_t s = seed + 3 * si + density, want = 0;
+            for (uint64_t i = 0; i < n; i++) { f[i] = density == 0 ? 0 : density == 1 ? 1 : (uint8_t)(sm64(s) % 3 == 0); want += f[i]; }
+            grl32::DBuf<uint8_t> df(n);
+            prim::h2d(df.p, f.data(), n);
+            grl32::DBuf<uint32_t> ex(n + 1), ref(want + 1), pre(n), pos(want + 1);
+            prim::dev_memset(ref.p, 0xA5, (want + 1) * 4); prim::dev_memset(pos.p, 0xA5, (want + 1) * 4);
+            const uint32_t tot = prim::exclusive_scan<uint32_t>(n, grl32::ByteIn{df.p}, ex.p, false, "selftest.split_ref");
+            prim::for_each(n, SelfSplitRefFn{df.p, ex.p, ref.p}, "selftest.split_ref");
+            grl32::SplitScan<uint32_t, grl32::ByteIn> sc(n, grl32::ByteIn{df.p}, "selftest.split_scan");
+            if (sc.total != want || tot != want) {
+                fprintf(stderr, "[grlbwt] selftest split scan: n = %llu, density %d: total %llu, exclusive_scan %llu, expected %llu\n", (unsigned long long)n, density,
+                        (unsigned long long)sc.total, (unsigned long long)tot, (unsigned long long)want);
+                return 1;
+            }
+            sc.emit(SelfSplitEmitFn{pre.p, pos.p}, "selftest.split_scan");
+            prim::sync();
+            const std::vector<uint32_t> hex = ex.to_host(n), hpre = pre.to_host(n), href = ref.to_host(want + 1), hpos = pos.to_host(want + 1);
+            for (uint64_t i = 0; i < n; i++)
+                if (hpre[i] != hex[i]) {
+                    fprintf(stderr, "[grlbwt] selftest split scan: n = %llu, density %d: element %llu got prefix %u, exclusive_scan gave %u\n", (unsigned long long)n,
+                            density, (unsigned long long)i, hpre[i], hex[i]);
+                    return 2;
+                }
+            for (uint64_t k = 0; k <= want; k++) if (hpos[k] != href[k]) return 3;
+            if (hpos[want] != 0xA5A5A5A5u) return 4;
+        }
+    return 0;
+}
+
 int selftest(uint64_t n, uint64_t seed) {
     if (n < 2) n = 2;
     std::vector<uint32_t> h(n);
@@ -1641,6 +1687,7 @@ int selftest(uint64_t n, uint64_t seed) {
     { int r = test_pack(); if (r) return r; }
     { int r = test_set_bits(n, seed + 60); if (r) return r; }
     { int r = test_merge_round(n, seed + 80); if (r) return r; }
+    { int r = test_split_scan(seed + 90); if (r) return -(700 + r); }
     return 0;
 }
 

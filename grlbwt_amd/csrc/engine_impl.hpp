@@ -1118,6 +1118,22 @@ struct ByteIn {
     const u8 *f;
     GRL_DEV u32 operator()(u64 i) const { return f[i]; }
 };
+// A scan whose consumer's outputs are sized by its total, in two phases (prim::scan_prepare / prim::scan_emit): the constructor
+// gives the total, the caller allocates, emit(e) calls e(i, sum_{j<i} in(j), in(i)) for every i.  No prefix array is stored.
+template <class T, class F>
+struct SplitScan {
+    T total;
+#ifdef GRLBWT_PRIM_HIP
+    prim::ScanPlan<T> plan; F in;
+    SplitScan(u64 n, F f, const char *name) : plan(prim::scan_prepare<T, F>(n, f, name)), in(f) { total = plan.total; }
+    template <class E> void emit(E e, const char *name) { prim::scan_emit<T, F, E>(plan, in, e, name); }
+#else
+    // (the serial stand-in: a sum, then the fused scan)
+    u64 n; F in;
+    SplitScan(u64 n_, F f, const char *name) : total(prim::reduce_sum<T>(n_, f, name)), n(n_), in(f) {}
+    template <class E> void emit(E e, const char *name) { (void)prim::exclusive_scan_emit<T, F, E>(n, in, e, name); }
+#endif
+};
 // (the same without an exchange, for few ranks: every rank looks at ALL positions and keeps the records of its own key range)
 struct OwnKeyFlagFn {     // flag[q] = 1 for the kept suffixes whose key lies in the range of rank `me`
     SufKeep keep; const u32 *dict_sym; int K, b; const u64 *spl; int N, me; u8 *flag; RunKeys rk;
@@ -1168,72 +1184,91 @@ struct HeadFlagFn {       // after the first sort: hflag[t] = 1 where the sorted
 static constexpr u32 kSegCap = 64;
 static_assert(prim::Switches{}.seg_cap == (int)kSegCap, "GRLBWT_SEG_CAP defaults to kSegCap");
 static constexpr u32 kSegLdsShort = 512;       // LDS tier: groups up to here take a workgroup of one wave, the others one of four
-struct GroupStartsFn {    // gstart[dense group id] = head slot ; gstart[G] = S
-    const u8 *hflag; const u32 *ex; u64 S; u32 *gstart;
-    GRL_DEV void operator()(u64 t) const {
-        if (hflag[t]) gstart[ex[t]] = (u32)t;
-        if (t == S - 1) gstart[ex[t] + hflag[t]] = (u32)S;
+struct DenseGidFn {       // final dense group id of every slot (ex: heads in front of the slot)
+    u32 *gid;
+    GRL_DEV void operator()(u64 t, u32 ex, u32 head) const { gid[t] = ex + head - 1; }
+};
+struct GroupStartsFn {    // consumer of the scan over hflag[]: gstart[dense group id] = head slot ; gstart[G] = S ; and the slot's group id
+    static constexpr bool kWaveEmit = false;
+    u64 S; u32 *gstart; DenseGidFn dense;
+    GRL_DEV void operator()(u64 t, u32 ex, u32 head) const {
+        if (head) gstart[ex] = (u32)t;
+        if (t == S - 1) gstart[ex + head] = (u32)S;
+        dense(t, ex, head);
     }
 };
-struct ExtKeyFn {         // compact the unresolved slots; key = the next K symbols of each (sentinel behind the phrase end)
+struct UnresolvedItem {   // the i-th active slot becomes item o of the round: slot, position, head of its group so far; returns the position
+    const u32 *act; const u32 *perm; const u8 *hflag; u32 *uslot; u32 *uq; u8 *uhead;
+    GRL_DEV u64 compact(u64 i, u32 o) const {
+        const u64 t = act ? (u64)act[i] : i;
+        const u32 q = perm[t];
+        uslot[o] = (u32)t; uq[o] = q; uhead[o] = hflag[t];
+        return q;
+    }
+};
+struct ExtKeyFn {         // consumer of the scan over uflag[]: compact the unresolved slots; key = the next K symbols of each (sentinel
+                          // behind the phrase end)
     // Where the phrase ends comes from the phrase-start bit-vector of the dictionary (S/8 bytes: it stays in the caches),
     // not from a per-position length array: an unresolved suffix has not ended within its first Lres symbols, so it ends
     // at the first phrase start in [q + Lres, q + Lres + K].
-    const u32 *act; const u8 *uflag; const u32 *uex; const u32 *perm; const u8 *hflag; const u32 *dict_sym; const u64 *pw; u64 S;
+    static constexpr bool kWaveEmit = false;
+    UnresolvedItem c; const u32 *dict_sym; const u64 *pw; u64 S;
     u64 Lres; int K, b;
-    u32 *uslot; u32 *uq; u64 *ukey; u8 *uhead;
+    u64 *ukey;
     RunKeys rk;
-    GRL_DEV void operator()(u64 i) const {
-        if (uflag[i]) {
-            const u64 t = act ? (u64)act[i] : i;
-            const u64 q = perm[t], x = q + Lres + (rk.rb ? (u64)rk.skip[q] : 0ull);
-            // bits x .. x+K-1 of the start vector (K <= 16; the vector has a spare word behind position S)
-            u64 w = 0;
-            if (x < S) {
-                w = pw[x >> 6] >> (x & 63);
-                if ((x & 63) + (u64)K > 64) w |= pw[(x >> 6) + 1] << (64 - (x & 63));
-            }
-            u32 valid = x >= S ? 0u : (u32)K;                      // symbols of the key that lie inside the phrase
-            const u32 starts = (u32)(w & ((1ull << K) - 1ull));
-            if (x < S && starts) valid = (u32)__builtin_ctz(starts);
-            if (x < S && x + valid > S) valid = (u32)(S - x);
-            const u64 sent = (1ull << b) - 1;
-            u64 key = 0;
-            for (int j = 0; j < K; j++) key = (key << b) | (((u32)j < valid) ? (u64)dict_sym[x + (u64)j] : sent);
-            if (rk.rb) {                           // (the run field of suffix_key0, with the phrase end taken from the start bits)
-                u64 low = 0;
-                if (valid == (u32)K) {
-                    const u32 r = rk.rem[x];
-                    if (r >= (u32)K) {
-                        const u32 a = dict_sym[x];
-                        const u64 xe = x + (u64)r;
-                        const bool up = xe >= S || bit_at(pw, xe) || dict_sym[xe] > a;
-                        const int R = rk.rb - 1;
-                        low = up ? ((1ull << R) | (((1ull << R) - 1ull) - (u64)r)) : (u64)r;
-                        rk.skip[q] += r - (u32)K;
-                    }
-                }
-                key = (key << rk.rb) | low;
-            }
-            const u32 o = uex[i];
-            uslot[o] = (u32)t; uq[o] = (u32)q; ukey[o] = key; uhead[o] = hflag[t];
+    GRL_DEV void operator()(u64 i, u32 o, u32 v) const { if (v) ukey[o] = key_of(c.compact(i, o)); }
+    GRL_DEV u64 key_of(const u64 q) const {
+        const u64 x = q + Lres + (rk.rb ? (u64)rk.skip[q] : 0ull);
+        // bits x .. x+K-1 of the start vector (K <= 16; the vector has a spare word behind position S)
+        u64 w = 0;
+        if (x < S) {
+            w = pw[x >> 6] >> (x & 63);
+            if ((x & 63) + (u64)K > 64) w |= pw[(x >> 6) + 1] << (64 - (x & 63));
         }
+        u32 valid = x >= S ? 0u : (u32)K;                      // symbols of the key that lie inside the phrase
+        const u32 starts = (u32)(w & ((1ull << K) - 1ull));
+        if (x < S && starts) valid = (u32)__builtin_ctz(starts);
+        if (x < S && x + valid > S) valid = (u32)(S - x);
+        const u64 sent = (1ull << b) - 1;
+        u64 key = 0;
+        for (int j = 0; j < K; j++) key = (key << b) | (((u32)j < valid) ? (u64)dict_sym[x + (u64)j] : sent);
+        if (rk.rb) {                           // (the run field of suffix_key0, with the phrase end taken from the start bits)
+            u64 low = 0;
+            if (valid == (u32)K) {
+                const u32 r = rk.rem[x];
+                if (r >= (u32)K) {
+                    const u32 a = dict_sym[x];
+                    const u64 xe = x + (u64)r;
+                    const bool up = xe >= S || bit_at(pw, xe) || dict_sym[xe] > a;
+                    const int R = rk.rb - 1;
+                    low = up ? ((1ull << R) | (((1ull << R) - 1ull) - (u64)r)) : (u64)r;
+                    rk.skip[q] += r - (u32)K;
+                }
+            }
+            key = (key << rk.rb) | low;
+        }
+        return key;
     }
 };
-struct SegStartFn {       // seg_start[k] = item of the k-th group head among the unresolved items ; seg_start[nseg] = U
-    const u8 *uhead; const u32 *hex; u64 U; u32 *seg_start;
-    GRL_DEV void operator()(u64 j) const {
-        if (uhead[j]) seg_start[hex[j]] = (u32)j;
-        if (j == U - 1) seg_start[hex[j] + uhead[j]] = (u32)U;
+struct SegStartFn {       // consumer of the scan over uhead[]: hex[j] = heads in front of item j ; seg_start[k] = item of the k-th group
+                          // head among the unresolved items ; seg_start[nseg] = U
+    static constexpr bool kWaveEmit = false;
+    u32 *hex; u64 U; u32 *seg_start;
+    GRL_DEV void operator()(u64 j, u32 ex, u32 head) const {
+        hex[j] = ex;
+        if (head) seg_start[ex] = (u32)j;
+        if (j == U - 1) seg_start[ex + head] = (u32)U;
     }
 };
 struct SegSortSmallFn {   // one lane per item of a group of at most kSegCap items: stable rank among the group's keys
     const u8 *uhead; const u32 *hex; const u32 *seg_start; const u32 *uslot; const u32 *uq; const u64 *ukey; u64 sent; u32 cap;
     u32 *perm; u8 *hflag; u8 *unext;       // unext[position] = the item now at that position is still unresolved
+    u32 *any_big;                          // set by the head of every group above cap: the round needs the tiers behind this one
     GRL_DEV void operator()(u64 j) const {
         const u32 s = hex[j] + uhead[j] - 1;
         const u32 a = seg_start[s], e = seg_start[s + 1];
-        if (e - a <= cap) {
+        if (e - a > cap) { if (uhead[j]) *any_big = 1u; }
+        else {
             const u64 k = ukey[j];
             u32 less = 0, eq_before = 0, eq_total = 0;
             for (u32 x = a; x < e; x++) {
@@ -1327,26 +1362,23 @@ struct UresInitFn {       // the unresolved flags of the active list, by slot
     GRL_DEV void operator()(u64 i) const { if (uflag[i]) ures[act ? (u64)act[i] : i] = 1; }
 };
 struct DoubleKeyFn {
-    const u32 *act; const u8 *uflag; const u32 *uex; const u32 *perm; const u8 *hflag;
+    static constexpr bool kWaveEmit = false;
+    UnresolvedItem c; const u8 *hflag;
     const u32 *dict_phr; const u32 *ph_off; const u32 *slot_of; const u32 *rank_ex; const u8 *ures; const u32 *skip;
     u64 Ld, Sg;
-    u32 *uslot; u32 *uq; u64 *ukey; u8 *uhead; u32 *nskip;
-    GRL_DEV void operator()(u64 i) const {
-        if (uflag[i]) {
-            const u64 t = act ? (u64)act[i] : i;
-            const u64 q = perm[t];
-            const u64 sk = skip[q], x = q + Ld + sk, end = ph_off[dict_phr[q] + 1];
-            u64 key = (Sg << 1) | 1ull;                     // the suffix has ended: behind every real group, resolved
-            u64 ns = sk;
-            if (x < end) {
-                const u32 st = slot_of[x];
-                const bool tu = ures[st] != 0;
-                key = ((u64)(rank_ex[st] + hflag[st] - 1) << 1) | (tu ? 0ull : 1ull);
-                if (tu) ns = sk + Ld + (u64)skip[x];
-            }
-            const u32 o = uex[i];
-            uslot[o] = (u32)t; uq[o] = (u32)q; ukey[o] = key; uhead[o] = hflag[t]; nskip[o] = (u32)ns;
+    u64 *ukey; u32 *nskip;
+    GRL_DEV void operator()(u64 i, u32 o, u32 v) const { if (v) key_of(c.compact(i, o), o); }
+    GRL_DEV void key_of(const u64 q, const u32 o) const {
+        const u64 sk = skip[q], x = q + Ld + sk, end = ph_off[dict_phr[q] + 1];
+        u64 key = (Sg << 1) | 1ull;                     // the suffix has ended: behind every real group, resolved
+        u64 ns = sk;
+        if (x < end) {
+            const u32 st = slot_of[x];
+            const bool tu = ures[st] != 0;
+            key = ((u64)(rank_ex[st] + hflag[st] - 1) << 1) | (tu ? 0ull : 1ull);
+            if (tu) ns = sk + Ld + (u64)skip[x];
         }
+        ukey[o] = key; nskip[o] = (u32)ns;
     }
 };
 struct AfterDoubleFn {    // item j: its position's new depth; place j: which position sits there now and whether it is still unresolved
@@ -1357,10 +1389,6 @@ struct AfterDoubleFn {    // item j: its position's new depth; place j: which po
         slot_of[perm[sl]] = sl;
         ures[sl] = unext[j];
     }
-};
-struct DenseGidFn {       // final dense group id of every slot
-    const u8 *hflag; const u32 *ex; u32 *gid;
-    GRL_DEV void operator()(u64 t) const { gid[t] = ex[t] + hflag[t] - 1; }
 };
 
 // -------------------------------------------- a7: groups -> pre-BWT + ranks
@@ -3658,17 +3686,28 @@ class Engine {
     // (GRLBWT_SEG_CAP and GRLBWT_SEG_LDS_CAP, product tier: the tests lower the limits so that ordinary inputs take every tier)
     static void order_segments(u64 U, const u8 *uhead, u32 *hex, const u64 *ukey, const u32 *uslot, const u32 *uq, u64 sent_r, int kbits_r, u32 cap,
                         u32 *perm, u8 *hflag, u8 *unext) {
-        const u64 nseg = prim::exclusive_scan<u32>(U, ByteIn{uhead}, hex, false, "suffix_heads");
+        SplitScan<u32, ByteIn> heads(U, ByteIn{uhead}, "suffix_heads");
+        const u64 nseg = heads.total;
         u32 lds_cap = (u32)std::max(prim::sw().seg_lds_cap, 0);
 #ifdef GRLBWT_PRIM_HIP
         lds_cap = std::min(lds_cap, prim::seg_sort_lds_max());
 #endif
         const u32 big_cap = std::max(cap, lds_cap);
+        DBuf<u32> seg_start(nseg + 1), any_big(1);
+        any_big.zero();
+        heads.emit(SegStartFn{hex, U, seg_start.p}, "suffix_heads");
+        prim::for_each(U, SegSortSmallFn{uhead, hex, seg_start.p, uslot, uq, ukey, sent_r, cap, perm, hflag, unext, any_big.p}, "suffix_sort.small");
+        // Only a round with a group above cap goes on (one host synchronisation either way: for the word the heads of such groups
+        // set, or for the totals of the scan below).
+        if (any_big.to_host(1)[0] == 0) {
+            if (prim::sw().table_trace)
+                fprintf(stderr, "[grlbwt] level %d refinement round: %llu items in %llu groups; counting all of them\n", prim::rt().tag, (unsigned long long)U,
+                        (unsigned long long)nseg);
+            return;
+        }
         const u64 nmid = U / ((u64)cap + 1) + 1;     // (no more groups above cap than this)
-        DBuf<u32> seg_start(nseg + 1), bex(U + 1), mid(nmid);
-        prim::for_each(U, SegStartFn{uhead, hex, U, seg_start.p}, "suffix_gstart");
-        prim::for_each(U, SegSortSmallFn{uhead, hex, seg_start.p, uslot, uq, ukey, sent_r, cap, perm, hflag, unext}, "suffix_sort.small");
-        // the large items counted and the LDS tier's groups listed by one scan (one host synchronisation)
+        DBuf<u32> bex(U + 1), mid(nmid);
+        // the large items counted and the LDS tier's groups listed by one scan
         const SegTiers tot = prim::exclusive_scan_emit<SegTiers>(U, SegBigIn{uhead, hex, seg_start.p, cap, lds_cap},
                                                                  SegBigEmitFn{hex, bex.p, mid.p, nmid}, "suffix_sort.big_scan");
         const u64 NB = tot.a & 0xffffffffull, n_short = tot.b & 0xffffffffull, n_long = tot.b >> 32;
@@ -3715,11 +3754,8 @@ class Engine {
 #endif
     }
     // The sorted slots are cut into groups of equal suffixes at the heads: gstart[], gid[]; returns the number of groups.
-    static u64 close_groups(const u8 *hflag, u32 *ex, u64 Sg, u32 *gstart, u32 *gid) {
-        const u64 G = prim::exclusive_scan<u32>(Sg, ByteIn{hflag}, ex, false, "suffix_heads");
-        prim::for_each(Sg, GroupStartsFn{hflag, ex, Sg, gstart}, "suffix_gstart");
-        prim::for_each(Sg, DenseGidFn{hflag, ex, gid}, "suffix_gid");
-        return G;
+    static u64 close_groups(const u8 *hflag, u64 Sg, u32 *gstart, u32 *gid) {
+        return prim::exclusive_scan_emit<u32>(Sg, ByteIn{hflag}, GroupStartsFn{Sg, gstart, DenseGidFn{gid}}, "suffix_heads");
     }
     // (very long phrases only: the grammar walks jump to their stops; empty otherwise)
     static DBuf<u64> grammar_stop_bits(const u64 *dm, u64 n, u32 maxlen) {
@@ -3902,7 +3938,6 @@ class Engine {
             }
             gid.alloc(Sg); gstart.alloc(Sg + 1);
             DBuf<u8> hflag(Sg), uflag(Sg);
-            DBuf<u32> ex(Sg + 1);
             first_sort_and_flags(ka, perm, Sg, ks, rk, hflag.p, uflag.p);
             ka.release();
             u64 Lres = (u64)K, iters = 1;        // Lres symbols (incl. a possible sentinel) resolved so far
@@ -3913,8 +3948,8 @@ class Engine {
             DBuf<u32> slot_of, rank_ex, nskip;
             DBuf<u8> ures;
             for (;;) {
-                DBuf<u32> uex(A + 1);
-                const u64 U = prim::exclusive_scan<u32>(A, ByteIn{uflag.p}, uex.p, false, "suffix_unresolved_scan");
+                SplitScan<u32, ByteIn> unres(A, ByteIn{uflag.p}, "suffix_unresolved_scan");
+                const u64 U = unres.total;
                 if (U == 0) break;
                 if (Lres > (u64)maxlen + (u64)K || dbl_rounds > 80) throw prim::Error(-71, "suffix refinement does not terminate");
                 if (!doubling && longmode && iters > dbl_after) {
@@ -3930,15 +3965,18 @@ class Engine {
                 DBuf<u32> uslot(U), uq(U), hex(U + 1);
                 DBuf<u64> ukey(U);
                 DBuf<u8> uhead(U), unext(U);
+                // The key functor is the consumer of the scan: it compacts the unresolved slots and makes their keys; no prefix array.
+                const UnresolvedItem compact{refined ? act.p : nullptr, perm.p, hflag.p, uslot.p, uq.p, uhead.p};
                 if (doubling) {
                     prim::exclusive_scan_nosync<u32>(Sg, ByteIn{hflag.p}, rank_ex.p, false, "suffix_doubling");      // group numbers of all slots
                     nskip.alloc(U);
-                    prim::for_each(A, DoubleKeyFn{refined ? act.p : nullptr, uflag.p, uex.p, perm.p, hflag.p, dict_phr.p, I.ph_off, slot_of.p, rank_ex.p,
-                                                  ures.p, rk.skip, Ld, Sg, uslot.p, uq.p, ukey.p, uhead.p, nskip.p}, "suffix_doubling");
+                    const DoubleKeyFn keys{compact, hflag.p, dict_phr.p, I.ph_off, slot_of.p, rank_ex.p, ures.p, rk.skip, Ld, Sg, ukey.p, nskip.p};
+                    unres.emit(keys, "suffix_doubling");
                     dbl_rounds++;
-                } else
-                prim::for_each(A, ExtKeyFn{refined ? act.p : nullptr, uflag.p, uex.p, perm.p, hflag.p, dict_sym.p, pbits.words.p, S, Lres, K, b,
-                                           uslot.p, uq.p, ukey.p, uhead.p, rk}, "suffix_keys");
+                } else {
+                    const ExtKeyFn keys{compact, dict_sym.p, pbits.words.p, S, Lres, K, b, ukey.p, rk};
+                    unres.emit(keys, "suffix_keys");
+                }
                 // ("still unresolved" bit(s) of a key and its sort bits: the doubling rounds' keys are group numbers)
                 order_segments(U, uhead.p, hex.p, ukey.p, uslot.p, uq.p, doubling ? 1ull : ks.sent, doubling ? (int)bitlen64((Sg << 1) | 1ull) : ks.kbits, cap,
                                perm.p, hflag.p, unext.p);
@@ -3949,7 +3987,7 @@ class Engine {
                 iters++;
             }
             pbits.base.release();
-            G = close_groups(hflag.p, ex.p, Sg, gstart.p, gid.p);
+            G = close_groups(hflag.p, Sg, gstart.p, gid.p);
             L.info.sort_iters = iters;
         }
         // The same with the dictionary sharded by owner.  Every rank runs the same sequence of collectives (the refinement goes on
@@ -4008,9 +4046,9 @@ class Engine {
             if (carry) C->named("sort.sample_rec").alltoall(sr.p, scnt, rec_arr.p, rcnt, 8, cn.maxb);
             sk.release(); sp.release(); sr.release();
             if (carry) C->local([&] { prim::for_each(Sg, IotaU32Fn{perm.p}, "suffix_keys0"); });      // the values of the sort: arrival indices
-            DBuf<u8> hflag, uflag; DBuf<u32> ex;
+            DBuf<u8> hflag, uflag;
             C->local([&] {
-                gid.alloc(Sg); gstart.alloc(Sg + 1); hflag.alloc(Sg); uflag.alloc(Sg); ex.alloc(Sg + 1);
+                gid.alloc(Sg); gstart.alloc(Sg + 1); hflag.alloc(Sg); uflag.alloc(Sg);
                 first_sort_and_flags(ka, perm, Sg, ks, RunKeys(), hflag.p, uflag.p);
             });
             ka.release();
@@ -4051,7 +4089,7 @@ class Engine {
             }
             pbits.base.release();
             C->local([&] {
-                G = close_groups(hflag.p, ex.p, Sg, gstart.p, gid.p);
+                G = close_groups(hflag.p, Sg, gstart.p, gid.p);
                 if (carry) {                     // from here on perm[] holds positions (offsets, owner in pown[]) again; the arrival indices stay for the fold's records
                     DBuf<u32> pp(Sg);
                     pown.alloc(Sg);

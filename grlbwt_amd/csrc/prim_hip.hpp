@@ -1537,6 +1537,58 @@ inline void exclusive_scan_emit_async(u64 n, F in, E emit, T *tot, const char *n
     }
 }
 
+// The fused scan in two phases, for a consumer whose outputs are sized by the grand total: scan_prepare runs the tile sums and
+// their scan and returns the total (host value, one sync -- the one exclusive_scan pays); the caller allocates; scan_emit runs
+// the per-tile scan with the consumer against the tile offsets the plan kept, and releases them.  The prefix array is never
+// stored.  `in` must give the same values in both phases.  (A plan that is never emitted releases its offsets when it goes.)
+template <class T>
+struct ScanPlan {
+    u64 n = 0, tiles = 0;
+    T total = T(0);
+    T *offsets = nullptr;                 // exclusive prefix of the tile sums (more than one tile only)
+    ScanPlan() = default;
+    ScanPlan(const ScanPlan &) = delete;
+    ScanPlan &operator=(const ScanPlan &) = delete;
+    ScanPlan(ScanPlan &&o) noexcept : n(o.n), tiles(o.tiles), total(o.total), offsets(o.offsets) { o.offsets = nullptr; }
+    void release() { if (offsets) { dev_free(offsets); offsets = nullptr; } }
+    ~ScanPlan() { release(); }
+};
+template <class T, class F>
+inline ScanPlan<T> scan_prepare(u64 n, F in, const char *name = "scan") {
+    ScanPlan<T> plan;
+    plan.n = n;
+    if (n == 0) return plan;
+    plan.tiles = (n + kScanTile - 1) / kScanTile;
+    T *tot = (T *)result_page();
+    if (plan.tiles == 1) {                      // the one tile's sum is the total: straight to the host page
+        prof_begin(name);
+        hipLaunchKernelGGL((k_scan_tile_sums<T, F>), dim3(1), dim3(kBlock), 0, rt().stream, n, in, tot);
+        prof_end();
+        after_launch(name);
+    } else {
+        plan.offsets = (T *)dev_alloc(sizeof(T) * (plan.tiles + 1));
+        prof_begin(name);
+        hipLaunchKernelGGL((k_scan_tile_sums<T, F>), dim3((unsigned)plan.tiles), dim3(kBlock), 0, rt().stream, n, in, plan.offsets);
+        prof_end();
+        after_launch(name);
+        exclusive_scan_async<T, PtrIn<T>>(plan.tiles, PtrIn<T>{plan.offsets}, plan.offsets, tot, nullptr, name);
+    }
+    sync();
+    std::memcpy(&plan.total, tot, sizeof(T));
+    return plan;
+}
+template <class T, class F, class E>
+inline void scan_emit(ScanPlan<T> &plan, F in, E emit, const char *name = "scan") {
+    if (plan.n == 0) return;
+    if (plan.tiles > 1 && !plan.offsets) throw Error(-71, "scan_emit: the plan was emitted or released before");
+    prof_begin(name);
+    hipLaunchKernelGGL((k_scan_tiles<T, F, E>), dim3((unsigned)plan.tiles), dim3(kBlock), 0, rt().stream, plan.n, in, (const T *)plan.offsets, (T *)nullptr,
+                       (T *)nullptr, (T *)nullptr, emit);
+    prof_end();
+    after_launch(name);
+    plan.release();      // stream-ordered reuse (pool)
+}
+
 // out[i] = sum_{j<i} in(j) for i in [0,n); returns the grand total (host value, one sync).
 // If store_total_at_n, also stores the total at out[n].
 template <class T, class F>
