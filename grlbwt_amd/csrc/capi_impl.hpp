@@ -2156,6 +2156,29 @@ int grlbwt_fm_approx_info_get(const grlbwt_fm *fm, grlbwt_fm_approx_info *out) {
     if (fm->f32) fill(*fm->f32); else fill(*fm->f64);
     return GRLBWT_OK;
 }
+int grlbwt_fm_lcp(grlbwt_ctx *ctx, const grlbwt_fm *fm, uint64_t max_lcp, int lcp_bytes, void *dev_lcp, uint64_t *host_rows_at,
+                  uint64_t *host_suffixes_of, uint64_t hist_capacity, uint64_t *n_levels_out) {
+    if (n_levels_out) *n_levels_out = 0;
+    if (!ctx || !fm || !(fm->f32 || fm->f64)) return GRLBWT_EINVAL;
+    uint64_t n = 0;
+    const int rc = guarded(ctx, [&] {
+        if (fm->f32) grl32::Image::fm_lcp(*fm->f32, max_lcp, lcp_bytes, dev_lcp, host_rows_at, host_suffixes_of, hist_capacity, n);
+        else grl64::Image::fm_lcp(*fm->f64, max_lcp, lcp_bytes, dev_lcp, host_rows_at, host_suffixes_of, hist_capacity, n);
+    });
+    if (n_levels_out) *n_levels_out = n;
+    return rc;
+}
+int grlbwt_fm_lcp_info_get(const grlbwt_fm *fm, grlbwt_fm_lcp_info *out) {
+    if (!fm || !out || !(fm->f32 || fm->f64)) return GRLBWT_EINVAL;
+    auto fill = [&](const auto &F) {
+        const auto &l = F.linfo;
+        out->n_rows = l.n; out->n_strings = l.k; out->lcp_bytes = l.lcp_bytes; out->cap = l.cap;
+        out->passes = l.passes; out->n_levels = l.n_levels; out->max_lcp = l.max_lcp; out->n_capped = l.n_capped;
+        out->tile_rows = l.tile_rows; out->scratch_bytes = l.scratch_bytes;
+    };
+    if (fm->f32) fill(*fm->f32); else fill(*fm->f64);
+    return GRLBWT_OK;
+}
 int grlbwt_fm_locate(grlbwt_ctx *ctx, const grlbwt_fm *fm, const uint64_t *dev_rows, uint64_t n_rows, uint64_t max_steps,
                      uint64_t *dev_string, uint64_t *dev_offset) {
     if (!ctx || !fm || !(fm->f32 || fm->f64)) return GRLBWT_EINVAL;

@@ -7,10 +7,10 @@
 //
 // What it holds: the device functors (in the order of the sections below) and, as static members of the stateless
 // `struct Image`, the host functions behind the C-ABI's grlbwt_image_*, grlbwt_invert_*, grlbwt_fm_*, grlbwt_merge_* and
-// grlbwt_select_* calls (reference: scripts/*.cpp of ddiazdom/grlBWT, SURVEY.md 8f-2; DESIGN.md 4b-4f):
+// grlbwt_select_* calls (reference: scripts/*.cpp of ddiazdom/grlBWT, SURVEY.md 8f-2; DESIGN.md 4b-4h):
 //   records and the scripts/ consumers   ImageRecs, plain / rle / stats / split_runs
 //   inversion                            per position (invert_t) and per run (RunIndex, invert_runs_t)
-//   FM index                             count, locate, match / MEMs, extract
+//   FM index                             count, locate, match / MEMs, extract, the LCP array (FmLcp)
 //   checkpointed LF walks                lf_checkpoints and the walks cut at checkpoints
 //   merge, select                        ImageMerge, ImageSelect
 // The pieces every consumer shares, one copy each: ImageRecs (the record layout), image_header / check_cell_bytes /
@@ -1056,6 +1056,99 @@ struct FmExtractFn {
     GRL_DEV void end(u64, const State &) const {}
 };
 
+// ---- the LCP array of the collection (grlbwt_fm_lcp).  B holds one bit per row: set once the row's suffix is
+// known to differ from the suffix of the row above within the first l cells.  A pass reads the rows in F-order: row q >= k lies
+// in the sorted run j with slf[j] <= q < slf[j + 1] (one bit per slf[j], with ranks: frc) and is LF of row p = key[j].start() +
+// (q - slf[j]); row q - 1 is LF of the occurrence of the same symbol in front of p, so the two suffixes differ within l + 1 cells
+// when any row between the two occurrences (the later one included) differs from its predecessor within l.  Inside a run that
+// is B[p] alone; at a run's first row it is a rank difference over B, from the end of the run in front.  S holds the rows whose
+// suffix has exactly l cells: S'[q] = S[p].
+//   Bounds: q < n gives j < R (frc has a bit at slf[0] = 0) and p inside run j, so p < n; q >= k gives j >= 1, since the runs of
+//   the separator, the smallest symbol, cover rows [0, k); pe = the end of run j - 1 <= p when both hold one symbol, since the
+//   sorted order of one symbol's runs is their order in the BWT.  rank1 reads word (p + 1) / 64 <= n / 64 of n / 64 + 2.
+GRL_DEV bool lcp_bit(const u64 *w, u64 p) { return ((w[p >> 6] >> (p & 63)) & 1ull) != 0; }
+struct LcpRowFn {
+    const RankCell *frc; const FmKey *key; const idx_t *slf; u64 k;
+    const u64 *B; const idx_t *brank; const u64 *S;
+    GRL_DEV u64 run(u64 q) const { return run_of_row(frc, q); }
+    // (single exit everywhere: the rows of a wave take different branches)
+    GRL_DEV bool head(u64 q) const {          // before the first pass: the first row of a symbol, and every terminator
+        bool h = true;
+        if (q >= k) {
+            const u64 j = run(q);
+            h = q == (u64)slf[j] && (j == 0 || key[j].sym() != key[j - 1].sym());
+        }
+        return h;
+    }
+    // the row's bit of B' (bq: its bit of B) and of S'
+    GRL_DEV bool operator()(u64 q, bool bq, bool &s) const {
+        bool b = true;
+        s = false;
+        if (q >= k) {
+            const u64 j = run(q);
+            const FmKey kj = key[j];
+            const u64 f = (u64)slf[j], p = kj.start() + (q - f);
+            s = lcp_bit(S, p);
+            b = bq;
+            if (!b) {
+                if (q > f) {
+                    b = lcp_bit(B, p);
+                } else if (j == 0) {
+                    b = true;
+                } else {
+                    const FmKey kp = key[j - 1];
+                    const u64 pe = kp.start() + (f - (u64)slf[j - 1]);
+                    b = kp.sym() != kj.sym() || rank1(B, brank, p + 1) != rank1(B, brank, pe);
+                }
+            }
+        }
+        return b;
+    }
+    GRL_DEV bool len(u64 q) const {
+        bool s = false;
+        if (q >= k) {
+            const u64 j = run(q);
+            s = lcp_bit(S, key[j].start() + (q - (u64)slf[j]));
+        }
+        return s;
+    }
+};
+struct LcpHeadPred {
+    LcpRowFn f;
+    GRL_DEV bool operator()(u64 q) const { return f.head(q); }
+};
+struct LcpBelowPred {       // S_0: the terminator-only suffixes
+    u64 k;
+    GRL_DEV bool operator()(u64 q) const { return q < k; }
+};
+struct LcpPassPred {        // the generic form of a pass: B' ...
+    LcpRowFn f;
+    GRL_DEV bool operator()(u64 q) const { bool s; return f(q, lcp_bit(f.B, q), s); }
+};
+struct LcpLenPred {         // ... and S'
+    LcpRowFn f;
+    GRL_DEV bool operator()(u64 q) const { return f.len(q); }
+};
+struct LcpNewFn {           // old := the bits of cur that old lacks
+    const u64 *cur; u64 *old;
+    GRL_DEV void operator()(u64 i) const { old[i] = cur[i] & ~old[i]; }
+};
+struct LcpUnsetPred {
+    const u64 *B;
+    GRL_DEV bool operator()(u64 q) const { return !lcp_bit(B, q); }
+};
+struct LcpStoreFn {         // prim::for_each_set_bit: the value v, in the output's width, at every set row
+    void *out; int w; u64 v;
+    GRL_DEV void operator()(u64 p, u64) const {
+        switch (w) {
+            case 1: ((u8 *)out)[p] = (u8)v; break;
+            case 2: ((u16 *)out)[p] = (u16)v; break;
+            case 4: ((u32 *)out)[p] = (u32)v; break;
+            default: ((u64 *)out)[p] = v; break;
+        }
+    }
+};
+
 struct Image {
     // ---- opening an image: the one parse of the 16 header bytes, the one test of a cell width, the one dispatch on it -------
     struct ImageHeader {
@@ -1359,6 +1452,7 @@ struct Image {
     struct ExtractInfo { u64 ranges = 0, pieces = 0, cells = 0, steps = 0, lanes = 0, refills = 0; };      // of the last fm_extract
     struct MatchInfo { u64 patterns = 0, cells = 0, matched = 0, longest = 0, capped = 0, mems = 0, lanes = 0, refills = 0; };
     struct ApproxInfo { u64 patterns = 0, cells = 0, k = 0, max_hits = 0, hits = 0, by[4] = {0, 0, 0, 0}, cut = 0, steps = 0, lanes = 0, refills = 0; };
+    struct LcpInfo { u64 n = 0, k = 0, lcp_bytes = 0, cap = 0, passes = 0, n_levels = 0, max_lcp = 0, n_capped = 0, tile_rows = 0, scratch_bytes = 0; };      // of the last fm_lcp
     struct FmIndex {
         u64 n = 0, R = 0, k = 0, sigma = 0, sepval = 0;
         u32 sep = 0, top_entries = 0;
@@ -1380,6 +1474,7 @@ struct Image {
         mutable ExtractInfo xinfo;
         mutable MatchInfo minfo;  // of the last fm_match / fm_mems
         mutable ApproxInfo ainfo; // of the last fm_approx
+        mutable LcpInfo linfo;    // of the last fm_lcp
         u64 extract_bytes() const { return (T.n + xq.n + xc.n) * sizeof(idx_t); }
         u64 bytes() const {
             return key.n * sizeof(FmKey) + slf.n * sizeof(idx_t) + alpha.n * 8 + rc.n * sizeof(RankCell) + rec.n * sizeof(RunRec) + sid.n * sizeof(idx_t) +
@@ -1627,6 +1722,131 @@ struct Image {
         for (u32 d = 0; d <= k && n_hits; d++) ai.by[d] = prim::reduce_sum<u64>(n_hits, FmApproxMismIn{mism, (u64)d}, "fm.approx_strata");
         prim::sync();
         F.ainfo = ai;
+    }
+    // ---- the LCP array and the suffix-length counts (functor block "the LCP array of the collection").  Everything
+    // that can refuse the call for its arguments or for memory runs before the first store into an output; histograms that may
+    // not fit their capacity are sized by a run that stores nothing.  Scratch, about 0.9 byte per row: two generations of B and
+    // of S, the ranks of B, the F-order run-start bit-vector with its RankCells (and a word per tile of the fused pass).
+    //   A pass in its generic form goes through the primitives alone (the serial stand-in's form, and with GRLBWT_LCP_ROUND=p the
+    //   device's): ranks of B (scan), B' and S' (bitvector_from_pred), B' & ~B and its ranks, the values (for_each_set_bit), |S'|
+    //   (reduce_sum).  The device form is prim::LcpRound: one kernel that writes B', S' and the values and counts per tile.
+    //   Loops: at most cap - 1 passes, each of which sets a bit or ends the call; nothing waits for another thread, and a pass has no atomics.
+#ifdef GRLBWT_PRIM_HIP
+    static constexpr u64 kLcpTile = prim::kLcpTile;
+#else
+    static constexpr u64 kLcpTile = 4096;        // (the serial form has no tiles: the figure the device library reports)
+#endif
+    struct FmLcp {
+        u64 n = 0, nw = 0;
+        bool plain = !prim::kIsDevice;
+        DBuf<RankCell> frc;
+        DBuf<u64> b0, b1, s0, s1;
+        DBuf<idx_t> brank;
+        static u64 words_of(u64 n_) { return n_ / 64 + 2; }
+        static u64 tiles_of(u64 n_) { return (n_ + kLcpTile - 1) / kLcpTile; }
+        static u64 scratch_bytes(u64 n_) {
+            return 4 * words_of(n_) * 8 + (words_of(n_) + 1) * sizeof(idx_t) + ((n_ + 1) / 64 + 2) * sizeof(RankCell) + tiles_of(n_) * 8;
+        }
+#ifdef GRLBWT_PRIM_HIP
+        prim::LcpRound W;
+#endif
+        void alloc(const FmIndex &F) {
+            n = F.n; nw = words_of(n);
+#ifdef GRLBWT_PRIM_HIP
+            plain = prim::sw().lcp_round == 'p';
+            if (!plain) W.alloc(n);
+#endif
+            {   // one bit per slf[j]: the first row of every sorted run
+                RankBits rb;
+                build_rankbits(rb, F.slf.p, F.R, n + 1, "lcp.runbits");
+                const u64 nc = (n + 1) / 64 + 2;
+                frc.alloc(nc);
+                prim::for_each(nc, RankCellFn{rb.words.p, rb.base.p, frc.p}, "lcp.rankcells");
+            }
+            b0.alloc(nw); b1.alloc(nw); s0.alloc(nw); s1.alloc(nw); brank.alloc(nw + 1);
+        }
+        LcpRowFn rows(const FmIndex &F, const u64 *B, const u64 *S) const { return LcpRowFn{frc.p, F.key.p, F.slf.p, F.k, B, brank.p, S}; }
+        // B (with its ranks in brank) and S -> Bn and Sn; v at the newly set rows of out (null: no store).  B is used up.
+        void pass_plain(const LcpRowFn &f, u64 *B, u64 *Bn, u64 *Sn, void *out, int w, u64 v, u64 &n_new, u64 &n_suf) {
+            prim::bitvector_from_pred(n, LcpPassPred{f}, Bn, "lcp.bits");
+            prim::bitvector_from_pred(n, LcpLenPred{f}, Sn, "lcp.lengths");
+            prim::for_each((n + 63) / 64, LcpNewFn{Bn, B}, "lcp.new");
+            n_new = (u64)prim::exclusive_scan<idx_t>(nw, PopcIn{B}, brank.p, true, "lcp.new_ranks");
+            if (out && n_new) prim::for_each_set_bit<idx_t>(n, B, brank.p, LcpStoreFn{out, w, v}, "lcp.values");
+            n_suf = prim::reduce_sum<u64>((n + 63) / 64, PopcIn{Sn}, "lcp.suffixes");
+        }
+        void run(const FmIndex &F, u64 cap, void *out, int w, LcpInfo &li, std::vector<u64> &rows_at, std::vector<u64> &suf) {
+            rows_at.clear(); suf.clear();
+            b0.zero(); b1.zero(); s0.zero(); s1.zero();
+            u64 *B = b0.p, *Bn = b1.p, *S = s0.p, *Sn = s1.p;
+            prim::bitvector_from_pred(n, LcpHeadPred{rows(F, nullptr, nullptr)}, B, "lcp.heads");
+            prim::bitvector_from_pred(n, LcpBelowPred{F.k}, S, "lcp.terminators");
+            if (out) prim::dev_memset(out, 0, n * (u64)w);
+            u64 set = prim::reduce_sum<u64>((n + 63) / 64, PopcIn{B}, "lcp.heads_sum");
+            rows_at.push_back(set); suf.push_back(F.k);
+            u64 passes = 0;
+            while (set < n && passes + 1 < cap) {
+                const u64 v = passes + 1;
+                u64 n_new = 0, n_suf = 0;
+                const LcpRowFn f = rows(F, B, S);
+#ifdef GRLBWT_PRIM_HIP
+                if (!plain) {
+                    prim::exclusive_scan_nosync<idx_t>(nw, PopcIn{B}, brank.p, true, "lcp.ranks");
+                    W.pass(f, B, Bn, Sn, out, w, v, &n_new, &n_suf);
+                } else
+#endif
+                {
+                    (void)prim::exclusive_scan<idx_t>(nw, PopcIn{B}, brank.p, true, "lcp.ranks");
+                    pass_plain(f, B, Bn, Sn, out, w, v, n_new, n_suf);
+                }
+                if (n_new == 0)
+                    throw prim::Error(-22, "fm lcp: pass " + std::to_string(v) + " set no row while " + std::to_string(n - set) +
+                                               " rows are open: not the BWT of a collection");
+                rows_at.push_back(n_new); suf.push_back(n_suf);
+                set += n_new; passes++;
+                std::swap(B, Bn); std::swap(S, Sn);
+            }
+            li.passes = passes; li.n_levels = passes + 1; li.n_capped = n - set;
+            li.max_lcp = li.n_capped ? cap : passes;
+            if (out && li.n_capped) {     // the rows still open: their LCP is cap or more
+                prim::bitvector_from_pred(n, LcpUnsetPred{B}, Bn, "lcp.open");
+                (void)prim::exclusive_scan<idx_t>(nw, PopcIn{Bn}, brank.p, true, "lcp.open_ranks");
+                prim::for_each_set_bit<idx_t>(n, Bn, brank.p, LcpStoreFn{out, w, cap}, "lcp.capped");
+            }
+        }
+    };
+    // n_levels is set whenever the passes were run, also when the capacity then refuses the call
+    static void fm_lcp(const FmIndex &F, u64 max_lcp, int w, void *out, u64 *rows_at, u64 *suffixes_of, u64 hist_capacity, u64 &n_levels) {
+        n_levels = 0;
+        if (!(w == 1 || w == 2 || w == 4 || w == 8)) throw prim::Error(-22, "fm lcp: the values take 1, 2, 4 or 8 bytes");
+        if (!out && !rows_at && !suffixes_of) throw prim::Error(-22, "fm lcp: no output");
+        const u64 lim = w == 8 ? ~0ull : (1ull << (8 * w)) - 1;
+        const u64 cap = max_lcp && max_lcp < lim ? max_lcp : lim;
+        const bool hist = rows_at || suffixes_of;
+        LcpInfo li;
+        li.n = F.n; li.k = F.k; li.lcp_bytes = (u64)w; li.cap = cap; li.tile_rows = kLcpTile;
+        std::vector<u64> ra(1, 0), su(1, 0);
+        if (F.n) {
+            li.scratch_bytes = FmLcp::scratch_bytes(F.n);
+            if (F.n >= ((u64)1 << 62) || li.scratch_bytes > prim::mem_available())
+                throw prim::Error(-12, "fm lcp: the passes need " + std::to_string(li.scratch_bytes) + " bytes of device memory, more than is free");
+            FmLcp L;
+            L.alloc(F);
+            // at most cap levels, and a pass sets a row: where the histograms may not hold them, a run without stores sizes them
+            const u64 bound = cap < F.n + 1 ? cap : F.n + 1;
+            const bool sizing = out && hist && hist_capacity < bound;
+            if (sizing) L.run(F, cap, nullptr, w, li, ra, su);
+            if (!sizing || li.n_levels <= hist_capacity) L.run(F, cap, out, w, li, ra, su);
+        } else {
+            li.n_levels = 1;
+        }
+        prim::sync();
+        F.linfo = li;
+        n_levels = li.n_levels;
+        if (hist && n_levels > hist_capacity)
+            throw prim::Error(-22, "fm lcp: " + std::to_string(n_levels) + " levels, more than the histograms hold");
+        if (rows_at) std::memcpy(rows_at, ra.data(), n_levels * 8);
+        if (suffixes_of) std::memcpy(suffixes_of, su.data(), n_levels * 8);
     }
     static void fm_locate(const FmIndex &F, const u64 *rows, u64 nr, u64 max_steps, u64 *str, u64 *ofs) {
         if (!F.locate) throw prim::Error(-22, "fm locate: the index was made without the structures for locating");

@@ -2354,6 +2354,83 @@ struct MgRound {
     }
 };
 
+// ------------------------------------------------------------------ LCP passes (grlbwt_fm_lcp)
+// One pass over the rows of a BWT in F-order: B' (the rows known to differ from the row above) and S' (the rows whose suffix has
+// exactly the pass's number of cells) from B and S, the pass's number stored at the rows B' adds, and the two counts the host
+// reads.  The row functor F (image_impl.hpp: LcpRowFn) says what a row reads: f(q, its bit of B, s) -> its bit of B', s = its bit
+// of S'.  One lane per row, the two ballots of a wave are the words of B' and S'; a workgroup takes a tile of kLcpTile rows, 16
+// consecutive words per wave.  Neighbouring lanes lie in the same or neighbouring runs, so the key and slf entries of a wave are
+// a few cache lines, and inside a run the bits a wave reads of B and S are consecutive: a word or two.  Only a run's first lane
+// takes the two ranks of the range test.  The mask of new rows is in row order, so the values' store is dense within the word.
+//   Counts: per wave in registers, per tile through 8 words of LDS into tnew[tile] / tsuf[tile] (at most kLcpTile each), summed
+//   by two reduces -- no device word that every tile adds to (k_mg_counts above: what that cost the merge).
+//   Bounds: a wave's loop ends in front of the first word x >= ceil(n / 64) (wave-uniform; the workgroup's only barrier comes after it); a lane
+//   with q >= n evaluates nothing and its ballot bits are 0, so Bn / Sn keep zero bits behind row n and out[q] is stored only
+//   for q < n.  No loop but the 16 words of a wave; no workgroup waits for another.
+static constexpr int kLcpTile = 4096;
+template <class F>
+__global__ void __launch_bounds__(kBlock) k_lcp_round(u64 n, F f, const u64 *B, u64 *Bn, u64 *Sn, void *out, int w, u64 v, u32 *tnew, u32 *tsuf) {
+    constexpr int NW = kBlock / 64, WPW = kLcpTile / 64 / NW;
+    __shared__ u32 s_new[NW], s_suf[NW];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const u64 nwords = (n + 63) >> 6;
+    const u64 x0 = (u64)blockIdx.x * (kLcpTile / 64) + (u64)wave * WPW;
+    u32 cn = 0, cs = 0;
+    for (int i = 0; i < WPW && x0 + (u64)i < nwords; i++) {
+        const u64 x = x0 + (u64)i;
+        const u64 q = x * 64 + (u64)lane;
+        const u64 old = B[x];
+        bool s = false, b = false;
+        if (q < n) b = f(q, ((old >> lane) & 1ull) != 0, s);
+        const u64 mb = __ballot(b), ms = __ballot(s);
+        const u64 fresh = mb & ~old;
+        if (lane == 0) { Bn[x] = mb; Sn[x] = ms; }
+        if (out && ((fresh >> lane) & 1ull)) {
+            switch (w) {
+                case 1: ((u8 *)out)[q] = (u8)v; break;
+                case 2: ((u16 *)out)[q] = (u16)v; break;
+                case 4: ((u32 *)out)[q] = (u32)v; break;
+                default: ((u64 *)out)[q] = v; break;
+            }
+        }
+        cn += (u32)__popcll(fresh);
+        cs += (u32)__popcll(ms);
+    }
+    if (lane == 0) { s_new[wave] = cn; s_suf[wave] = cs; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        u32 a = 0, c = 0;
+#pragma unroll
+        for (int k = 0; k < NW; k++) { a += s_new[k]; c += s_suf[k]; }
+        tnew[blockIdx.x] = a;
+        tsuf[blockIdx.x] = c;
+    }
+}
+// The per-tile words of the passes and their launch.  One LcpRound serves every pass of a call.
+struct LcpRound {
+    u64 n = 0, tiles = 0;
+    u32 *tnew = nullptr, *tsuf = nullptr;
+    static u64 tiles_of(u64 n_) { return (n_ + kLcpTile - 1) / kLcpTile; }
+    void alloc(u64 n_) {
+        n = n_; tiles = tiles_of(n_);
+        if (tiles > 0x7FFFFFFFull) throw Error(-75, "lcp: more rows than one launch takes");
+        tnew = (u32 *)dev_alloc(tiles * 4);
+        tsuf = (u32 *)dev_alloc(tiles * 4);
+    }
+    void release() { dev_free(tnew); dev_free(tsuf); tnew = tsuf = nullptr; }
+    ~LcpRound() { release(); }
+    // B (its ranks where f reads them) and S -> Bn and Sn; v, as w bytes, at the rows of out that Bn adds (out null: no store)
+    template <class F>
+    void pass(const F &f, const u64 *B, u64 *Bn, u64 *Sn, void *out, int w, u64 v, u64 *n_new, u64 *n_suf) {
+        prof_begin("lcp.round", n / 2);
+        hipLaunchKernelGGL((k_lcp_round<F>), dim3((unsigned)tiles), dim3(kBlock), 0, rt().stream, n, f, B, Bn, Sn, out, w, v, tnew, tsuf);
+        prof_end();
+        after_launch("lcp.round");
+        *n_new = reduce_sum<u64>(tiles, PtrIn<u32>{tnew}, "lcp.new_sum");
+        *n_suf = reduce_sum<u64>(tiles, PtrIn<u32>{tsuf}, "lcp.suffix_sum");
+    }
+};
+
 // Digit plan of an LSD sort over `bits` key bits: the fewest passes with digits of at most rs_max_digit() bits, widths as equal
 // as possible (at 9: 51 bits = 9,9,9,8,8,8; 54 = 6 x 9; 18 = 9,9).  GRLBWT_SORT_DIGIT=8|9|10 sets the widest digit; the default
 // stays 8: measured on the 10 GB build (profiles/r03), 9- and 10-bit digits save a pass over the 51-56-bit suffix keys and the

@@ -44,6 +44,7 @@
     X(GRLBWT_FM_MATCH, fm_match, char, 0, "l[anes]: grlbwt_fm_match / grlbwt_fm_mems with one lane per query cell, grlbwt_fm_approx with one lane per pattern, and no refilling, not lanes that take tickets") \
     X(GRLBWT_WALK_LANES, walk_lanes, uint64_t, 0, "most lanes of a checkpointed walk launch, rounded up to a wave (0: from occupancy; lower: small inputs refill their lanes)") \
     X(GRLBWT_MERGE_ROUND, merge_round, char, 0, "s[ort]: a round of the image merge as gathered keys and a stable sort, not the fused kernels") \
+    X(GRLBWT_LCP_ROUND, lcp_round, char, 0, "p[lain]: a pass of grlbwt_fm_lcp through the generic primitives, not the fused kernel")  \
     X(GRLBWT_IO_THREADS, io_threads, int, 0, "reader / writer threads per file chunk, 1..64 (0: from the host's cores)")         \
     X(GRLBWT_QUIET_ENV, quiet_env, bool, false, "no note on stderr about the switches set in the environment")
 

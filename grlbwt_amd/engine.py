@@ -38,6 +38,7 @@ ABI_SYMBOLS = [
     "grlbwt_fm_string_lengths", "grlbwt_fm_extract", "grlbwt_fm_extract_info_get",
     "grlbwt_fm_match", "grlbwt_fm_mems", "grlbwt_fm_match_info_get",
     "grlbwt_fm_approx", "grlbwt_fm_approx_info_get",
+    "grlbwt_fm_lcp", "grlbwt_fm_lcp_info_get",
     "grlbwt_merge_create", "grlbwt_merge_info_get", "grlbwt_merge_emit", "grlbwt_merge_interleave", "grlbwt_merge_destroy",
     "grlbwt_merge_files",
     "grlbwt_select_create", "grlbwt_select_info_get", "grlbwt_select_emit", "grlbwt_select_rows", "grlbwt_select_destroy",
@@ -89,6 +90,11 @@ class ApproxInfo(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in ("n_patterns", "n_cells", "max_mismatches", "max_hits", "n_hits")] + \
                [("hits_by_mismatches", C.c_uint64 * 4)] + \
                [(k, C.c_uint64) for k in ("n_truncated", "steps", "walk_lanes", "lane_refills", "table_bytes")]
+
+
+class LcpInfo(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("n_rows", "n_strings", "lcp_bytes", "cap", "passes", "n_levels", "max_lcp", "n_capped",
+                                          "tile_rows", "scratch_bytes")]
 
 
 class ImageStats(C.Structure):
@@ -248,6 +254,8 @@ def load_library(path=None, allow_test_standin=False):
     L.grlbwt_fm_match_info_get.argtypes = [vp, C.POINTER(MatchInfo)]
     L.grlbwt_fm_approx.argtypes = [vp, vp, vp, i32, vp, u64, C.c_uint32, u64, vp, vp, vp, vp, vp, vp, u64, C.POINTER(u64)]
     L.grlbwt_fm_approx_info_get.argtypes = [vp, C.POINTER(ApproxInfo)]
+    L.grlbwt_fm_lcp.argtypes = [vp, vp, u64, i32, vp, vp, vp, u64, C.POINTER(u64)]
+    L.grlbwt_fm_lcp_info_get.argtypes = [vp, C.POINTER(LcpInfo)]
     L.grlbwt_merge_create.argtypes = [vp, vp, u64, vp, u64, i32, u64, C.POINTER(vp)]
     L.grlbwt_merge_info_get.argtypes = [vp, C.POINTER(MergeInfo)]
     L.grlbwt_merge_emit.argtypes = [vp, vp, vp, u64]
@@ -680,6 +688,56 @@ class FmIndex:
         d = _as_dict(out)
         d["hits_by_mismatches"] = [int(v) for v in out.hits_by_mismatches]
         return d
+
+    LCP_HIST_FIRST = 1 << 20      # levels the histograms of lcp() are first sized for, where the cap and the rows allow more
+
+    def lcp(self, max_lcp=0, lcp_bytes=4, lcp_ptr=None, want_hist=True):
+        """The LCP array of the collection: n_syms values of lcp_bytes bytes (1, 2, 4, 8) into lcp_ptr (None: no array), each
+        min(LCP, cap) with cap = min(max_lcp if not 0, 2^(8 * lcp_bytes) - 1).  With want_hist returns (rows_at, suffixes_of),
+        numpy uint64 arrays of n_levels entries: rows_at[l] = the rows whose value is exactly l, suffixes_of[l] = the suffixes
+        of exactly l cells (distinct_kmers() takes both); without it (None, None).  The histograms are sized for the most levels the
+        cap and the number of rows allow, which the call accepts at once; above LCP_HIST_FIRST by the idiom of mems(): that
+        capacity first, then the number of levels the refusal reports."""
+        import numpy as np
+        L, got = self.ctx.L, C.c_uint64()
+        if not want_hist:
+            self.ctx._ck(L.grlbwt_fm_lcp(self.ctx._h, self._h, max_lcp, lcp_bytes, C.c_void_p(lcp_ptr), None, None, 0, C.byref(got)))
+            return None, None
+        lim = 2 ** (8 * lcp_bytes) - 1 if lcp_bytes in (1, 2, 4) else UINT64_MAX
+        cap = max(1, min(min(max_lcp, lim) if max_lcp else lim, self.info()["n_syms"] + 1, self.LCP_HIST_FIRST))
+        while True:
+            rows_at, suffixes_of = np.zeros(cap, dtype=np.uint64), np.zeros(cap, dtype=np.uint64)
+            rc = L.grlbwt_fm_lcp(self.ctx._h, self._h, max_lcp, lcp_bytes, C.c_void_p(lcp_ptr), rows_at.ctypes.data_as(C.c_void_p),
+                                 suffixes_of.ctypes.data_as(C.c_void_p), cap, C.byref(got))
+            if rc != OK and got.value > cap:
+                cap = got.value
+                continue
+            self.ctx._ck(rc)
+            return rows_at[:got.value].copy(), suffixes_of[:got.value].copy()
+
+    def lcp_info(self):
+        """The counters of the last lcp() on this index."""
+        out = LcpInfo()
+        rc = self.ctx.L.grlbwt_fm_lcp_info_get(self._h, C.byref(out))
+        if rc != OK:
+            raise GrlbwtError(rc, self.ctx.L.grlbwt_strerror(rc).decode())
+        return _as_dict(out)
+
+    @staticmethod
+    def distinct_kmers(rows_at, suffixes_of, k=None):
+        """The number of distinct k-mers (windows of k cells that hold no separator) from the histograms of lcp(): the rows with
+        an LCP below k less the suffixes of fewer than k cells.  k None: the list c with c[k] for 1 <= k <= n_levels (c[0] is
+        0); beyond n_levels the passes did not get that far: ValueError."""
+        import numpy as np
+        n_levels = len(rows_at)
+        if len(suffixes_of) != n_levels:
+            raise ValueError("the two histograms differ in length")
+        c = np.concatenate([[0], np.cumsum(np.asarray(rows_at, dtype=np.int64)) - np.cumsum(np.asarray(suffixes_of, dtype=np.int64))])
+        if k is None:
+            return [int(v) for v in c]
+        if not 1 <= k <= n_levels:
+            raise ValueError("k = %d is outside 1 .. n_levels = %d: the passes did not get that far" % (k, n_levels))
+        return int(c[k])
 
     def close(self):
         h, self._h = getattr(self, "_h", None), None

@@ -481,6 +481,54 @@ int grlbwt_fm_approx(grlbwt_ctx *ctx, const grlbwt_fm *fm, const void *dev_cells
                      uint64_t *n_hits_out);
 int grlbwt_fm_approx_info_get(const grlbwt_fm *fm, grlbwt_fm_approx_info *out);
 
+/* ---- the LCP array of the collection and its suffix-length counts: the other half of the enhanced suffix array, what BCR-style
+ * tools write beside the BWT.  With it the distinct k-mer counts for every k, the nodes and edges of a de Bruijn graph,
+ * suffix / prefix overlaps and the repeat structure of a read set are one pass over an array.  The call works on any index of
+ * grlbwt_fm_create, with or without GRLBWT_FM_LOCATE, in both position widths and on compacted alphabets (only equality of
+ * symbols matters); it makes no handle and leaves the index, its index_bytes and every later answer as they were.
+ *
+ * DEFINITION, part of the contract.  Rows are the rows of the BWT the image describes, in grlbwt_fm_count's coordinates: n_rows
+ * of them for n_strings strings.  The suffix of row p is a run of cells followed by its string's terminator, and every
+ * terminator is a symbol of its own: it equals nothing, not even another terminator.  LCP[0] = 0; for p >= 1 LCP[p] is the
+ * number of leading cells the suffixes of rows p - 1 and p share.  Rows [0, n_strings) are the terminator-only suffixes and get
+ * 0; two identical strings reach their full length, never more.
+ *
+ * VALUES: dev_lcp (may be NULL) receives n_rows values of lcp_bytes bytes, lcp_bytes in {1, 2, 4, 8}.  The effective cap is
+ * min(max_lcp if it is not 0, 2^(8 * lcp_bytes) - 1); 8 bytes without max_lcp have none.  The value written is min(LCP, cap).
+ * HISTOGRAMS, host arrays, each may be NULL: host_rows_at[l] = the rows whose value is exactly l (a capped row is in none),
+ * host_suffixes_of[l] = the suffixes of exactly l cells = the strings of at least l cells, for l in [0, n_levels), n_levels =
+ * passes + 1.  *n_levels_out is always set once the passes have run; with a histogram given and hist_capacity < n_levels the
+ * call fails with GRLBWT_EINVAL and writes no output, dev_lcp included (the sizing idiom of grlbwt_fm_mems; a call whose
+ * capacity may not suffice first runs its passes without storing).  Since a suffix of fewer than k cells has an LCP below k,
+ * the number of distinct k-mers -- windows of k cells that hold no separator -- is the sum of host_rows_at[0, k) less the sum of
+ * host_suffixes_of[0, k), for every k <= n_levels.
+ *
+ * ALGORITHM: B holds one bit per row, set once the row is known to differ from the row above within l cells; it starts as the
+ * terminator rows and the first row of every symbol (LCP 0).  Pass l reads the rows in F-order through the runs in (symbol,
+ * position) order: a row inside a run copies the bit of the row it is LF of, a run's first row tests whether B has any bit
+ * between the end of the run in front and that row (a rank difference); the rows a pass adds get LCP l.  A second bit-vector,
+ * the suffixes of exactly l cells, rides the same pass as a pure copy.  COST: (the largest LCP) passes, or cap - 1 if that is
+ * less, each a streaming pass over the rows -- the cost model of grlbwt_merge_create: fine for read-like collections, for
+ * chromosomes usable only with a cap, and a capped LCP is all that k-mer work needs.  A pass that sets no row while rows are
+ * open means the image is not the BWT of a collection (the images GRLBWT_FM_LOCATE refuses for walks that do not end; e.g. the
+ * records ($,1)(A,2)): GRLBWT_EINVAL.  Every well-formed image is accepted.
+ * GRLBWT_EINVAL before any store: an lcp_bytes not in {1, 2, 4, 8}, a null index, all three outputs NULL.  GRLBWT_ENOMEM, before
+ * the first pass, when the scratch does not fit the free memory: about 0.9 byte per row (two generations of each bit-vector, the
+ * ranks of B, the F-order run-start bit-vector with its ranks).  GRLBWT_LCP_ROUND=p[lain] runs a pass through the generic
+ * primitives instead of the fused kernel, with the same outputs.  OUT OF SCOPE: skipping rows that are already final, a
+ * command-line flag, a multi-GPU form.
+ * grlbwt_fm_lcp_info_get: the counters of the last grlbwt_fm_lcp whose passes ran on the index. */
+typedef struct grlbwt_fm_lcp_info {
+    uint64_t n_rows, n_strings, lcp_bytes, cap;   /* cap: the effective one (UINT64_MAX: none) */
+    uint64_t passes, n_levels;                    /* n_levels = passes + 1 */
+    uint64_t max_lcp, n_capped;                   /* largest value written; rows whose true LCP is >= cap */
+    uint64_t tile_rows, scratch_bytes;            /* rows per workgroup of the pass kernel; peak scratch */
+} grlbwt_fm_lcp_info;
+int grlbwt_fm_lcp(grlbwt_ctx *ctx, const grlbwt_fm *fm, uint64_t max_lcp /* 0: none */, int lcp_bytes,
+                  void *dev_lcp /* n_rows values, may be NULL */, uint64_t *host_rows_at /* may be NULL */,
+                  uint64_t *host_suffixes_of /* may be NULL */, uint64_t hist_capacity, uint64_t *n_levels_out);
+int grlbwt_fm_lcp_info_get(const grlbwt_fm *fm, grlbwt_fm_lcp_info *out);
+
 /* ---- merging two images: the image of the collection "strings of A, then strings of B" from the images of A and B, without the
  * texts -- a collection larger than one build is built in batches and folded together, a batch of new strings is added to an
  * existing image.  String i of B becomes string n_strings_a + i.  When A and B were built by this engine with cells of cell_bytes,
