@@ -2015,6 +2015,41 @@ struct CellSymFn {
     const u32 *t; u32 *sym; idx_t *len;
     GRL_DEV void operator()(u64 i) const { sym[i] = t[i] >> 2; len[i] = 1; }
 };
+// ------------------------------------ the base case: BWT_r of a level of short strings by sorting its suffixes (Engine::base_bwt)
+// The level's text read as a dictionary in which every string is a phrase: one scan over the terminator flags gives every cell
+// its string, every string its start, and the ranks as the dictionary's symbols.
+struct TermIn {
+    const u32 *t;
+    GRL_DEV u32 operator()(u64 q) const { return t[q] & 1u; }
+};
+struct BaseTextFn {       // consumer of that scan (ex: strings that end in front of q)
+    static constexpr bool kWaveEmit = false;
+    const u32 *t; u64 n; u32 *sym; u32 *str; u32 *off; u64 cap;      // (off[] has cap + 1 entries: a text with more flagged cells is refused by the caller)
+    GRL_DEV void operator()(u64 q, u32 ex, u32 v) const {
+        sym[q] = t[q] >> 2; str[q] = ex;
+        if ((q == 0 || (t[q - 1] & 1u)) && ex <= cap) off[ex] = (u32)q;
+        if (q == n - 1 && (u64)ex + v <= cap) off[ex + v] = (u32)n;
+    }
+};
+struct OffLenIn {         // length of string k from the starts
+    const u32 *off;
+    GRL_DEV u32 operator()(u64 k) const { return off[k + 1] - off[k]; }
+};
+// The rows in sorted order.  A suffix that starts inside its string carries the cell in front of it; the m-th WHOLE string in
+// sorted order carries the last cell of string m in text order (parse2bwt is the case of one cell per string): the scan over
+// "slot t holds a string start" numbers them.
+struct StartSlotIn {
+    const u32 *perm; const u64 *starts;
+    GRL_DEV u32 operator()(u64 t) const { return bit_at(starts, perm[t]) ? 1u : 0u; }
+};
+struct BaseRowFn {
+    static constexpr bool kWaveEmit = false;
+    const u32 *perm; const u32 *sym; const u32 *off; u32 *osym; idx_t *olen;
+    GRL_DEV void operator()(u64 t, u32 m, u32 whole) const {
+        osym[t] = whole ? sym[off[m + 1] - 1u] : sym[perm[t] - 1u];
+        olen[t] = 1;
+    }
+};
 
 template <class F>
 struct StoreFn {          // out[i] = f(i): materialise an expensive scan input once
@@ -3688,6 +3723,8 @@ class Engine {
                         u32 *perm, u8 *hflag, u8 *unext) {
         SplitScan<u32, ByteIn> heads(U, ByteIn{uhead}, "suffix_heads");
         const u64 nseg = heads.total;
+        // (the trace tells the rounds of the base case, which sorts inside an induction phase, from the dictionary stage's)
+        const char *round_name = prim::rt().phase == 'i' ? "base case sort round" : "refinement round";
         u32 lds_cap = (u32)std::max(prim::sw().seg_lds_cap, 0);
 #ifdef GRLBWT_PRIM_HIP
         lds_cap = std::min(lds_cap, prim::seg_sort_lds_max());
@@ -3701,7 +3738,7 @@ class Engine {
         // set, or for the totals of the scan below).
         if (any_big.to_host(1)[0] == 0) {
             if (prim::sw().table_trace)
-                fprintf(stderr, "[grlbwt] level %d refinement round: %llu items in %llu groups; counting all of them\n", prim::rt().tag, (unsigned long long)U,
+                fprintf(stderr, "[grlbwt] level %d %s: %llu items in %llu groups; counting all of them\n", prim::rt().tag, round_name, (unsigned long long)U,
                         (unsigned long long)nseg);
             return;
         }
@@ -3712,8 +3749,8 @@ class Engine {
                                                                  SegBigEmitFn{hex, bex.p, mid.p, nmid}, "suffix_sort.big_scan");
         const u64 NB = tot.a & 0xffffffffull, n_short = tot.b & 0xffffffffull, n_long = tot.b >> 32;
         if (prim::sw().table_trace)
-            fprintf(stderr, "[grlbwt] level %d refinement round: %llu items in %llu groups; counting %llu, LDS %llu (%llu short + %llu long groups), radix %llu\n",
-                    prim::rt().tag, (unsigned long long)U, (unsigned long long)nseg, (unsigned long long)(U - NB - (tot.a >> 32)), (unsigned long long)(tot.a >> 32),
+            fprintf(stderr, "[grlbwt] level %d %s: %llu items in %llu groups; counting %llu, LDS %llu (%llu short + %llu long groups), radix %llu\n",
+                    prim::rt().tag, round_name, (unsigned long long)U, (unsigned long long)nseg, (unsigned long long)(U - NB - (tot.a >> 32)), (unsigned long long)(tot.a >> 32),
                     (unsigned long long)n_short, (unsigned long long)n_long, (unsigned long long)NB);
         order_segments_lds(n_short, SegBigLdsFn{mid.p, seg_start.p, ukey, uslot, uq, sent_r, perm, hflag, unext}, false, std::min(lds_cap, kSegLdsShort));
         order_segments_lds(n_long, SegBigLdsFn{mid.p + (nmid - n_long), seg_start.p, ukey, uslot, uq, sent_r, perm, hflag, unext}, true, lds_cap);
@@ -4465,6 +4502,83 @@ class Engine {
         linfo[bwt_level].R = bwt.R;
         linfo[bwt_level].n = cur_n;
         if (keep_texts) { kept_bwts.clear(); kept_bwts.resize(levels.size() + 1); keep_bwt(bwt_level); }
+    }
+    // ---- a11/a12 without the last rounds: the base case ----------------------------------------------------------------------
+    // The reference parses until every string is one cell (exact_par_phase.cpp:496) and reads BWT_r off that text.  Once the
+    // strings are a cell or two long a round compresses nothing -- nearly every cell is a distinct symbol -- but still runs the
+    // whole dictionary stage, and the induction level above it the whole expansion.  BWT_r of such a level is written down
+    // directly.  Its rows are the suffixes c_j .. c_k of every string c_1 .. c_k (c_k the terminator-flagged cell), ordered by
+    // their ranks, equal ones by text position; no suffix is a proper prefix of another (flagged symbols occur at string ends
+    // only).  The row of a suffix with j > 1 carries the rank of c_(j-1); the m-th whole-string row in sorted order carries the
+    // last cell of string m in text order, which is what keeps the separators of the final BWT in string order (first_bwt is
+    // the case k = 1 everywhere).  Runs are merged as there.
+    // The sort is the dictionary stage's (DictStage::suffix_sort_local) over a dictionary in which every string is a phrase and
+    // no suffix is left out; it keeps equal suffixes in position order through every tier (tests/base_case_cases.py).
+    struct BaseText {                        // the level's text as that dictionary
+        DBuf<u32> sym, str, off;             // rank and string of every cell; the strings' starts (+ the cell count)
+        u64 D = 0; u32 maxlen = 0;
+    };
+    BaseText base_text() {
+        prim::rt().tag = (int)levels.size();
+        prim::rt().phase = 'i';
+        StageTimer st(&tm.ind_assemble, "ind_assemble");
+        BaseText B;
+        B.sym.alloc(cur_n); B.str.alloc(cur_n); B.off.alloc(stats.n_strings + 2);
+        B.D = prim::exclusive_scan_emit<u32>(cur_n, TermIn{cur_text.p}, BaseTextFn{cur_text.p, cur_n, B.sym.p, B.str.p, B.off.p, stats.n_strings + 1}, "base_text");
+        if (B.D != stats.n_strings || !(cur_text.get(cur_n - 1) & 1u)) throw prim::Error(-71, "base case: the level's text does not hold one flagged cell per string");
+        B.maxlen = prim::reduce_max<u32>(B.D, OffLenIn{B.off.p}, "base_maxlen");
+        return B;
+    }
+    // (GRLBWT_BASE_CASE_RATIO, product tier: cells per string from which on a level is a base case; 0 = never)
+    // The stepwise calls and the collection-level flow keep the reference's rounds; so does a build that keeps every level's text.
+    bool base_case_candidate() const {
+        const u64 ratio = prim::sw().base_case_ratio;
+        if (ratio == 0 || keep_texts || parse_done || levels.size() < 2) return false;
+        if (cur_n >= 0xFFFFFFF0ull || stats.n_strings >= 0xFFFFFFF0ull) return false;      // (32-bit dictionary positions and phrases)
+        return cur_n / ratio < stats.n_strings || (cur_n / ratio == stats.n_strings && cur_n % ratio == 0);      // cur_n <= ratio * n_strings
+    }
+    void base_bwt(BaseText &B) {
+        prim::rt().tag = (int)levels.size();
+        prim::rt().phase = 'i';
+        const u64 n = cur_n, D = B.D;
+        DBuf<u8> all_last(D);
+        all_last.fill_ff();                  // (every string ends with its terminator: no suffix is left out of the sort)
+        DictIn<u32, false> I;
+        I.D = D; I.S = n; I.maxlen = B.maxlen; I.sigma = cur_sigma;
+        I.ph_off = B.off.p; I.ph_lastT = all_last.p;
+        LevelData scratch;                   // (the stage's counters of a round: nobody asks for them at this level)
+        DictStage<u32, false> Z(*this, I, scratch);
+        Z.dict_sym = std::move(B.sym); Z.dict_phr = std::move(B.str);
+        {
+            StageTimer st(&tm.ind_assemble, "ind_assemble");
+            build_rankbits32(Z.pbits, I.ph_off, D, n + 1, "base_text");
+        }
+        Z.suffix_sort_local();
+        if (Z.Sg != n) throw prim::Error(-71, "base case: the sort left suffixes out");
+        StageTimer st(&tm.ind_assemble, "ind_assemble");
+        Z.gid.release(); Z.gstart.release();
+        DBuf<u32> s(n);
+        DBuf<idx_t> l(n);
+        const u64 whole = prim::exclusive_scan_emit<u32>(n, StartSlotIn{Z.perm.p, Z.pbits.words.p}, BaseRowFn{Z.perm.p, Z.dict_sym.p, I.ph_off, s.p, l.p}, "base_rows");
+        if (whole != D) throw prim::Error(-71, "base case: whole-string rows do not match the string count");
+        bwt = merge_runs(s.p, l.p, n);
+        bwt_level = (int)levels.size();
+        cur_text.release();
+        parse_done = true;
+        linfo.assign(levels.size() + 1, LevelInfo());
+        linfo[bwt_level].R = bwt.R;
+        linfo[bwt_level].n = n;
+    }
+    // The parsing phase of a whole build: the reference's rounds, cut short at the first level that is a base case.
+    void parse_phase_or_base() {
+        while (!parse_done) {
+            if (base_case_candidate()) {
+                BaseText B = base_text();
+                // (no run-aware keys and no doubling rounds at the base level: such a level goes on parsing)
+                if ((u64)B.maxlen < prim::sw().run_keys_min) { base_bwt(B); return; }
+            }
+            parse_round();
+        }
     }
     RunLen run_len() const { return RunLen{bwt.len.p, bwt.pos.p}; }      // (one of the two is there)
     void need_len() {                          // the lengths as an array (inspection, the collection-level mode's edges)
@@ -5574,8 +5688,9 @@ class Engine {
     }
 
     void run_all() {
-        parse_phase();
-        induce_phase();
+        parse_phase_or_base();
+        if (bwt_level < 0) first_bwt();
+        while (bwt_level > 0) induce_level();
         finish();
     }
 };

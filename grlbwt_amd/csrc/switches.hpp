@@ -27,6 +27,7 @@
     X(GRLBWT_A2A_SELF_VIA_COMM, a2a_self_via_comm, bool, false, "a rank's own all-to-all block goes through the callback too")    \
     X(GRLBWT_RUN_KEYS_MIN, run_keys_min, uint64_t, 512, "phrase length from which the suffix sort takes run-aware keys")         \
     X(GRLBWT_DOUBLING_AFTER, doubling_after, uint64_t, 24, "refinement rounds of a long-phrase level before doubling rounds")     \
+    X(GRLBWT_BASE_CASE_RATIO, base_case_ratio, uint64_t, 5, "a whole build stops parsing at a level of at most this many cells per string and sorts its suffixes (0: never)") \
     X(GRLBWT_SEG_CAP, seg_cap, int, 64, "largest suffix group ordered by counting (kSegCap); larger ones in LDS or by two radix sorts") \
     X(GRLBWT_SEG_LDS_CAP, seg_lds_cap, int, 4096, "largest suffix group ordered in LDS (above: two radix sorts; 0: no LDS tier)") \
     X(GRLBWT_CELL_LAYOUT, cell_layout, char, 0, "p[acked] | s[eparate]: a wider induction cell layout than the input needs")     \
@@ -52,7 +53,6 @@
     X(GRLBWT_TRACE, trace, char, 0, "1: print every launch and synchronise after it")                                          \
     X(GRLBWT_SYNC_SITES, sync_sites, bool, false, "profile: count behind which launch site the host waited")                  \
     X(GRLBWT_MEM_TRACE, mem_trace, bool, false, "per-stage peak device memory on stderr")                                      \
-    X(GRLBWT_NOPOOL, nopool, bool, false, "no slab allocator: hipMalloc / hipFree for every buffer")                           \
     X(GRLBWT_POOL_CLASSIC, pool_classic, bool, false, "hipMalloc slabs only, no reserved arena")                              \
     X(GRLBWT_POOL_TRACE, pool_trace, bool, false, "what backing the arena cost the process, on stderr at exit")               \
     X(GRLBWT_IO_TRACE, io_trace, bool, false, "where the file loader and the image writer spend their time, on stderr")
@@ -77,6 +77,7 @@
     X(GRLBWT_TEST_FAIL_RANK_INDUCE, test_fail_rank_induce, int, -1, "this rank fails in the induction")
 
 #define GRLBWT_SWITCHES_DEV(X)                                                                                                      \
+    X(GRLBWT_NOPOOL, nopool, bool, false, "no slab allocator: hipMalloc / hipFree for every buffer")                           \
     X(GRLBWT_NO_PART, no_part, bool, false, "no partitioned naming (single GPU)")                                              \
     X(GRLBWT_DIST_NO_PART, dist_no_part, bool, false, "no partitioned naming (multi-rank)")                                   \
     X(GRLBWT_NO_NAME_STREAM, no_name_stream, bool, false, "the direct index without the name_stream kernel")                  \
