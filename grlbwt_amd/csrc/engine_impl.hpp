@@ -21,7 +21,7 @@
 //   a12 parse2bwt                   exact_ind_phase.cpp:603-672             -> Engine::first_bwt
 //   a13 compute_hocc_size           exact_ind_phase.cpp:42-109              -> Engine::expand_split: ChainGen through prim::expand_count
 //   a14 infer_lvl_bwt pass B        exact_ind_phase.cpp:143-258             -> ... and prim::expand_sort (expansion fused with the first split pass)
-//   a15 infer_lvl_bwt pass C        exact_ind_phase.cpp:287-361             -> Engine::assemble_t: TermHeadEmitFn, PrePlaceFn, AsmSeg through
+//   a15 infer_lvl_bwt pass C        exact_ind_phase.cpp:287-361             -> Engine::assemble (AsmStage): TermHeadEmitFn, PrePlaceFn, AsmSeg through
 //                                                                               prim::stream_merge_count / stream_merge_emit
 //   8e  collection-level mode       parsing_strategies.h:200-386 (thread ranges) -> Engine::dist_build (dist_round_t, dist_induce_level, dist_finish)
 //   8f2 .rl_bwt consumers           scripts/*.cpp                            -> image_impl.hpp (struct Image: image_plain / image_rle / image_stats / image_split_runs / invert_image)
@@ -4595,145 +4595,160 @@ class Engine {
     }
 
     // ---- a13-a15: BWT_r from BWT_{r+1} -------------------------------------
-    // passes A+B (exact_ind_phase.cpp:42-109,143-258) over the runs this engine holds of BWT_{r+1}: chain walks through
-    // the level's grammar, cells split by bucket (stable).  The cells stay in c_* (bucket-major), term[i] = rewritten symbol
-    // of run i.  `maxrun` = longest run of BWT_{r+1} (of ALL shards in the collection-level mode: it fixes the cell layout).
-    u64 expand_split(LevelData &L, DBuf<u32> &term, u64 maxrun, int &kb, int &lb) {
-        const u32 sigma3 = L.sigma + 3, bwt_code = L.sigma + 1, take_code = bwt_code;
-        const u64 R = bwt.R, M = L.M;
-        DBuf<idx_t> eoff;
-        DBuf<u32> ssym; DBuf<idx_t> slen;
-        DBuf<u64> gp;                           // packed grammar cells (chain walks)
-        u64 E = 0;
-        DBuf<u32> skey;                         // bucket of every induced cell, bucket-major order
-        DBuf<u64> spack;                        // (sym<<32 | len) of every induced cell, same order (packed path)
-        DBuf<u64> sfused;                       // sym | len | bucket in one word per cell (fused path)
-        DBuf<u32> sfused32;                     // the same word in 32 bits when the three fields fit (kb + lb + sbits <= 32 < 2^32: kb < 32)
-        kb = (int)bitlen64(L.M > 0 ? L.M - 1 : 0);
-        if (kb < 1) kb = 1;
-        {
-            const int bits = kb;
-            {
-                StageTimer st(&tm.ind_expand, "ind_expand");
-                gp.alloc(M);
-                prim::for_each(M, PackGrammarFn{L.g0.p, L.g1.p, L.has_hocc.p, gp.p}, "induce_pack_grammar");
-            }
-            const int sbits = (int)bitlen64((u64)sigma3);
-            prim::XsPlan plan;
-            lb = (int)bitlen64(maxrun);
-            if (lb < 1) lb = 1;
-            // Whenever bucket, run length and symbol fit 64 bits together (always at DNA scales), the cell IS the sort
-            // key: the split moves 8 bytes per cell and pass instead of 12, and holds 16 instead of 24 bytes per cell.
-            // (GRLBWT_CELL_LAYOUT=packed|separate: the tests take the wider layouts on inputs that would never need them)
-            const char force = prim::sw().cell_layout;
-            const bool fused = kb + lb + sbits <= 64 && !force;
-            const bool cell32 = fused && kb + lb + sbits <= 32 && kb < 32 && !prim::sw().no_cell32;
-            if (prim::sw().table_trace) fprintf(stderr, "[grlbwt] induction level %d: %llu runs, longest %llu, cell bits: bucket %d + length %d + symbol %d\n",
-                                                      prim::rt().tag, (unsigned long long)R, (unsigned long long)maxrun, kb, lb, sbits);
-            // otherwise the payload (sym, len) rides through the split as one u64 whenever every run length fits 32 bits
-            const bool packed = !fused && maxrun < 0xFFFFFFFFull && force != 's';
-            bool done = false;
-            if (fused) {
-                // chain expansion fused with the first pass of the bucket split (prim::expand_*): the cells are never
-                // written in run order, there is no offset array and no scan over the runs
-                const ChainGen gen{bwt.sym.p, run_len(), gp.p, sigma3, take_code, term.p, kb, lb};
-                {
-                    StageTimer st(&tm.ind_expand, "ind_expand");
-                    E = prim::expand_count(R, gen, bits, plan, "induce");
-                }
-                // 4-byte cells when everything fits (level 0 of the 10 GB DNA build: 17 + 8 + 7 bits): every pass of the split, pass C
-                // and -- in the collection-level mode -- the cell exchange move half the bytes.  (A function of the layout alone:
-                // the ranks of a collection-level build agree on it.)
-                if (plan.ok && cell32) {
-                    DBuf<u32> ef(E), ef2(E);
-                    StageTimer st(&tm.ind_sort, "ind_sort");
-                    int res = prim::expand_sort<ChainGen, u32>(gen, plan, ef.p, ef2.p, "induce");
-                    sfused32 = std::move(res ? ef2 : ef);
-                    done = true;
-                } else if (plan.ok) {
-                    DBuf<u64> ef(E), ef2(E);
-                    StageTimer st(&tm.ind_sort, "ind_sort");
-                    int res = prim::expand_sort(gen, plan, ef.p, ef2.p, "induce");
-                    sfused = std::move(res ? ef2 : ef);
-                    done = true;
-                }
-            }
-            plan.release();
-            if (!done) {     // offsets of every run's cells (an item with more than 32 cells, or cells that do not fit one word)
-                StageTimer st(&tm.ind_expand, "ind_expand");
-                eoff.alloc(R + 1);
-                prim::for_each(R, StoreFn<ChainCountFn>{ChainCountFn{bwt.sym.p, gp.p, sigma3}, eoff.p}, "induce_count");
-                E = (u64)prim::exclusive_scan<idx_t>(R, IdxIn<idx_t>{eoff.p}, eoff.p, true, "induce_count_scan");
-            }
-            if (done) {
-            } else if (fused) {
-                DBuf<u64> ef(E), ef2(E);
-                {
-                    StageTimer st(&tm.ind_expand, "ind_expand");
-                    prim::for_each(R, ChainExpandFn<CELLS_FUSED>{bwt.sym.p, run_len(), gp.p, eoff.p, sigma3, take_code,
-                                                                 nullptr, nullptr, nullptr, nullptr, ef.p, term.p, kb, lb}, "induce_expand");
-                }
-                StageTimer st(&tm.ind_sort, "ind_sort");
-                int res = prim::sort_keys<u64, 1>(ef.p, ef2.p, E, 0, bits, "induce_split");
-                if (cell32) {                    // (the same form as the fused kernel's: the layout decides, not the path taken)
-                    sfused32.alloc(E);
-                    prim::for_each(E, NarrowCellFn{res ? ef2.p : ef.p, sfused32.p}, "induce_split");
-                } else sfused = std::move(res ? ef2 : ef);
-                prim::sync();
-            } else if (packed) {
-                DBuf<u32> ekey(E), ekey2(E);
-                DBuf<u64> ep(E), ep2(E);
-                {
-                    StageTimer st(&tm.ind_expand, "ind_expand");
-                    prim::for_each(R, ChainExpandFn<CELLS_PACKED>{bwt.sym.p, run_len(), gp.p, eoff.p, sigma3, take_code,
-                                                                  ekey.p, nullptr, nullptr, nullptr, ep.p, term.p, 0, 0}, "induce_expand");
-                }
-                StageTimer st(&tm.ind_sort, "ind_sort");
-                int res = prim::sort_pairs<u32, u64>(ekey.p, ep.p, ekey2.p, ep2.p, E, 0, bits, "induce_split");
-                skey = std::move(res ? ekey2 : ekey);
-                spack = std::move(res ? ep2 : ep);
-                prim::sync();
-            } else {
-                DBuf<u32> ekey(E), ekey2(E);
-                DBuf<u32> esym(E);
-                DBuf<idx_t> eidx(E), eidx2(E), elen(E);
-                {
-                    StageTimer st(&tm.ind_expand, "ind_expand");
-                    prim::for_each(R, ChainExpandFn<CELLS_SEPARATE>{bwt.sym.p, run_len(), gp.p, eoff.p, sigma3, take_code,
-                                                                    ekey.p, eidx.p, esym.p, elen.p, nullptr, term.p, 0, 0}, "induce_expand");
-                }
-                StageTimer st(&tm.ind_sort, "ind_sort");
-                ssym.alloc(E); slen.alloc(E);
-                int res = prim::sort_pairs<u32, idx_t>(ekey.p, eidx.p, ekey2.p, eidx2.p, E, 0, bits, "induce_split");
-                prim::for_each(E, GatherCellFn{res ? eidx2.p : eidx.p, esym.p, elen.p, ssym.p, slen.p}, "induce_gather");
-                skey = std::move(res ? ekey2 : ekey);
-                prim::sync();
-            }
-        }
-        // the cells move to the engine: pass C drops them before its run merge (peak memory)
-        c_skey = std::move(skey); c_ssym = std::move(ssym); c_slen = std::move(slen); c_spack = std::move(spack);
-        c_sfused = std::move(sfused); c_sfused32 = std::move(sfused32); c_gp = std::move(gp);
-        return E;
+    // the marker symbols of a level with sigma symbols, in the pre-BWT and in the cells
+    struct LevelCodes { u32 bwt, hocc, take, sigma3; explicit LevelCodes(u32 sigma) : bwt(sigma + 1), hocc(sigma + 2), take(sigma + 1), sigma3(sigma + 3) {} };
+    // The form of a level's induced cells (host arithmetic, no device call), from the bits of a bucket, a run length and a symbol; len32:
+    // maxrun < 2^32 - 1.  A function of these and the switches alone: the ranks of a collection-level build agree on it.
+    // Whenever bucket, run length and symbol fit 64 bits together (always at DNA scales), the cell IS the sort key: the split moves
+    // 8 bytes per cell and pass instead of 12, and holds 16 instead of 24 bytes per cell.  4-byte cells when everything fits 32 bits
+    // (level 0 of the 10 GB DNA build: 17 + 8 + 7 bits; kb < 32): every pass of the split, pass C and -- in the collection-level mode --
+    // the cell exchange move half the bytes.  Otherwise the payload (sym, len) rides through the split as one u64 whenever every run
+    // length fits 32 bits, and as two arrays behind an index when not.
+    // (GRLBWT_CELL_LAYOUT=packed|separate, GRLBWT_NO_CELL32: the tests take the wider layouts on inputs that would never need them)
+    enum class CellLayout { Word32, Word64, Packed, Separate };
+    static CellLayout choose_layout(int kb, int lb, int sbits, bool len32) {
+        const char force = prim::sw().cell_layout;
+        if (kb + lb + sbits <= 64 && !force) return (kb + lb + sbits <= 32 && kb < 32 && !prim::sw().no_cell32) ? CellLayout::Word32 : CellLayout::Word64;
+        return (len32 && force != 's') ? CellLayout::Packed : CellLayout::Separate;
     }
-    // the received blocks (rcnt[g] cells from rank g, back to back in `in`) merged by bucket; buckets [u0, u0 + M)
-    template <class K>
-    void merge_cell_blocks(DBuf<K> &in, const std::vector<u64> &rcnt, int kb, int lb, u32 u0, u64 M, u64 Er) {
+    // The induced cells of the level being assembled, bucket-major, and the packed grammar cells the chain walks read.  Owned by the
+    // engine (`cells`) so that pass C can drop them before its run merge (peak memory).
+    struct Cells {
+        CellLayout layout = CellLayout::Word64;
+        int kb = 1, lb = 1; u64 E = 0;          // bits of a bucket and of a run length; cells
+        DBuf<u32> w32; DBuf<u64> w64;           // Word32 | Word64: sym | len | bucket in one word per cell
+        DBuf<u32> key;                          // Packed, Separate: the bucket of every cell
+        DBuf<u64> pack;                         // Packed: sym << 32 | len
+        DBuf<u32> sym; DBuf<idx_t> len;         // Separate
+        DBuf<u64> gp;
+        template <class W> DBuf<W> &word() { if constexpr (sizeof(W) == 4) return w32; else return w64; }
+        template <class T> static const T *from(const DBuf<T> &b, u64 first) { return b.p ? b.p + first : nullptr; }
+        // the cells from `first` on, buckets counted from u0
+        CellView view(u32 u0 = 0, u64 first = 0) const {
+            return CellView{from(w64, first), kb, lb, from(key, first), from(pack, first), from(sym, first), from(len, first), u0, from(w32, first)};
+        }
+        void release() { key.release(); sym.release(); len.release(); pack.release(); w64.release(); w32.release(); gp.release(); }
+    };
+    Cells cells;
+    // Stable sort of (bucket, index) pairs on the bucket bits, then the payload gathered through the permutation into c.sym / c.len:
+    // the Separate layout's split, after the expansion and again after the cell exchange.  `key` holds the sorted buckets afterwards.
+    void sort_gather_cells(Cells &c, u64 E, DBuf<u32> &key, DBuf<u32> &key2, DBuf<idx_t> &ix, DBuf<idx_t> &ix2, const u32 *sym, const idx_t *len,
+                           const char *sort_site, const char *gather_site) {
+        c.sym.alloc(E); c.len.alloc(E);
+        const int res = prim::sort_pairs<u32, idx_t>(key.p, ix.p, key2.p, ix2.p, E, 0, c.kb, sort_site);
+        prim::for_each(E, GatherCellFn{res ? ix2.p : ix.p, sym, len, c.sym.p, c.len.p}, gather_site);
+        if (res) key = std::move(key2);
+    }
+    // passes A+B (exact_ind_phase.cpp:42-109,143-258) over the runs this engine holds of BWT_{r+1}: chain walks through the level's
+    // grammar, cells split by bucket (stable), term[i] = rewritten symbol of run i.  As steps; expand_split runs them.
+    struct ExpandStage {
+        Engine &eng; LevelData &L; DBuf<u32> &term; const LevelCodes code; const u64 R;
+        Cells c; DBuf<idx_t> eoff;              // (eoff: the offset fallback, where every run's cells start)
+        ExpandStage(Engine &e, LevelData &l, DBuf<u32> &t) : eng(e), L(l), term(t), code(l.sigma), R(e.bwt.R) {}
+        void pack_grammar() {
+            StageTimer st(&eng.tm.ind_expand, "ind_expand");
+            c.gp.alloc(L.M);
+            prim::for_each(L.M, PackGrammarFn{L.g0.p, L.g1.p, L.has_hocc.p, c.gp.p}, "induce_pack_grammar");
+        }
+        void choose_layout(u64 maxrun) {
+            c.kb = std::max((int)bitlen64(L.M > 0 ? L.M - 1 : 0), 1);
+            c.lb = std::max((int)bitlen64(maxrun), 1);
+            const int sbits = (int)bitlen64((u64)code.sigma3);
+            c.layout = Engine::choose_layout(c.kb, c.lb, sbits, maxrun < 0xFFFFFFFFull);
+            if (prim::sw().table_trace) fprintf(stderr, "[grlbwt] induction level %d: %llu runs, longest %llu, cell bits: bucket %d + length %d + symbol %d\n",
+                                                      prim::rt().tag, (unsigned long long)R, (unsigned long long)maxrun, c.kb, c.lb, sbits);
+        }
+        bool one_word() const { return c.layout == CellLayout::Word32 || c.layout == CellLayout::Word64; }
+        // chain expansion fused with the first pass of the bucket split (prim::expand_*): the cells are never written in run order, there
+        // is no offset array and no scan over the runs.  false: an item with more than 32 cells -- c.E is valid, the cells are not there.
+        bool expand_fused() {
+            const ChainGen gen{eng.bwt.sym.p, eng.run_len(), c.gp.p, code.sigma3, code.take, term.p, c.kb, c.lb};
+            prim::XsPlan plan;
+            { StageTimer st(&eng.tm.ind_expand, "ind_expand"); c.E = prim::expand_count(R, gen, c.kb, plan, "induce"); }
+            const bool ok = plan.ok;
+            if (ok) { if (c.layout == CellLayout::Word32) fused_sort<u32>(gen, plan); else fused_sort<u64>(gen, plan); }
+            plan.release();
+            return ok;
+        }
+        template <class W> void fused_sort(const ChainGen &gen, prim::XsPlan &plan) {
+            DBuf<W> ef(c.E), ef2(c.E);
+            StageTimer st(&eng.tm.ind_sort, "ind_sort");
+            const int res = prim::expand_sort<ChainGen, W>(gen, plan, ef.p, ef2.p, "induce");
+            c.word<W>() = std::move(res ? ef2 : ef);
+        }
+        // the offset fallback: the offsets of every run's cells, then expansion in run order and a split of its own
+        void count_offsets() {
+            StageTimer st(&eng.tm.ind_expand, "ind_expand");
+            eoff.alloc(R + 1);
+            prim::for_each(R, StoreFn<ChainCountFn>{ChainCountFn{eng.bwt.sym.p, c.gp.p, code.sigma3}, eoff.p}, "induce_count");
+            c.E = (u64)prim::exclusive_scan<idx_t>(R, IdxIn<idx_t>{eoff.p}, eoff.p, true, "induce_count_scan");
+        }
+        template <int FORM> void expand_at_offsets(u32 *key, idx_t *idx, u32 *sym, idx_t *len, u64 *word) {
+            StageTimer st(&eng.tm.ind_expand, "ind_expand");
+            const bool w = FORM == CELLS_FUSED;
+            prim::for_each(R, ChainExpandFn<FORM>{eng.bwt.sym.p, eng.run_len(), c.gp.p, eoff.p, code.sigma3, code.take,
+                                                  key, idx, sym, len, word, term.p, w ? c.kb : 0, w ? c.lb : 0}, "induce_expand");
+        }
+        void split_words() {
+            DBuf<u64> ef(c.E), ef2(c.E);
+            expand_at_offsets<CELLS_FUSED>(nullptr, nullptr, nullptr, nullptr, ef.p);
+            StageTimer st(&eng.tm.ind_sort, "ind_sort");
+            const int res = prim::sort_keys<u64, 1>(ef.p, ef2.p, c.E, 0, c.kb, "induce_split");
+            if (c.layout == CellLayout::Word32) {       // (the same form as the fused kernel's: the layout decides, not the path taken)
+                c.w32.alloc(c.E);
+                prim::for_each(c.E, NarrowCellFn{res ? ef2.p : ef.p, c.w32.p}, "induce_split");
+            } else c.w64 = std::move(res ? ef2 : ef);
+            prim::sync();
+        }
+        void split_packed() {
+            DBuf<u32> ekey(c.E), ekey2(c.E);
+            DBuf<u64> ep(c.E), ep2(c.E);
+            expand_at_offsets<CELLS_PACKED>(ekey.p, nullptr, nullptr, nullptr, ep.p);
+            StageTimer st(&eng.tm.ind_sort, "ind_sort");
+            const int res = prim::sort_pairs<u32, u64>(ekey.p, ep.p, ekey2.p, ep2.p, c.E, 0, c.kb, "induce_split");
+            c.key = std::move(res ? ekey2 : ekey);
+            c.pack = std::move(res ? ep2 : ep);
+            prim::sync();
+        }
+        void split_separate() {
+            DBuf<u32> ekey(c.E), ekey2(c.E);
+            DBuf<u32> esym(c.E);
+            DBuf<idx_t> eidx(c.E), eidx2(c.E), elen(c.E);
+            expand_at_offsets<CELLS_SEPARATE>(ekey.p, eidx.p, esym.p, elen.p, nullptr);
+            StageTimer st(&eng.tm.ind_sort, "ind_sort");
+            eng.sort_gather_cells(c, c.E, ekey, ekey2, eidx, eidx2, esym.p, elen.p, "induce_split", "induce_gather");
+            c.key = std::move(ekey);
+            prim::sync();
+        }
+    };
+    // `maxrun` = longest run of BWT_{r+1} (of ALL shards in the collection-level mode: it fixes the cell layout)
+    Cells expand_split(LevelData &L, DBuf<u32> &term, u64 maxrun) {
+        ExpandStage Z(*this, L, term);
+        Z.pack_grammar();
+        Z.choose_layout(maxrun);
+        if (!(Z.one_word() && Z.expand_fused())) {
+            Z.count_offsets();
+            if (Z.one_word()) Z.split_words();
+            else if (Z.c.layout == CellLayout::Packed) Z.split_packed();
+            else Z.split_separate();
+        }
+        return std::move(Z.c);
+    }
+    // the received blocks (rcnt[g] cells from rank g, back to back in the cells' word array) merged by bucket; buckets [u0, u0 + M)
+    template <class K> void merge_cell_blocks(Cells &c, const std::vector<u64> &rcnt, u32 u0, u64 M, u64 Er) {
+        DBuf<K> &in = c.word<K>();
         const int N = (int)rcnt.size();
         DBuf<idx_t> bstart1((u64)N * M), bend((u64)N * M), base(M + 1), off((u64)N * M);
         bstart1.zero(); bend.zero();
         u64 ro = 0;
         for (int g = 0; g < N; g++) {
-            if (rcnt[g]) {
-                const K *blk = in.p + ro;
-                CellView cv{sizeof(K) == 8 ? (const u64 *)blk : nullptr, kb, lb, nullptr, nullptr, nullptr, nullptr, u0, sizeof(K) == 4 ? (const u32 *)blk : nullptr};
-                prim::for_each(rcnt[g], BucketEdgesFn{cv, rcnt[g], bstart1.p + (u64)g * M, bend.p + (u64)g * M}, "dist.merge_cells");
-            }
+            if (rcnt[g]) prim::for_each(rcnt[g], BucketEdgesFn{c.view(u0, ro), rcnt[g], bstart1.p + (u64)g * M, bend.p + (u64)g * M}, "dist.merge_cells");
             ro += rcnt[g];
         }
         prim::exclusive_scan_nosync<idx_t>(M, BlockTotalIn{bstart1.p, bend.p, N, M}, base.p, true, "dist.merge_cells");
         prim::for_each(M, BlockOffsetsFn{bstart1.p, bend.p, base.p, N, M, off.p}, "dist.merge_cells");
         DBuf<K> out(Er);
-        const K kmask = (K)((kb >= (int)(8 * sizeof(K))) ? ~K(0) : ((K(1) << kb) - 1));
+        const K kmask = (K)((c.kb >= (int)(8 * sizeof(K))) ? ~K(0) : ((K(1) << c.kb) - 1));
         ro = 0;
         for (int g = 0; g < N; g++) {
             if (rcnt[g]) prim::for_each(rcnt[g], BlockPlaceFn<K>{in.p + ro, kmask, u0, off.p + (u64)g * M, out.p}, "dist.merge_cells.scatter");
@@ -4741,110 +4756,103 @@ class Engine {
         }
         in = std::move(out);
     }
-    CellView cell_view(int kb, int lb, u32 u0 = 0) const { return CellView{c_sfused.p, kb, lb, c_skey.p, c_spack.p, c_ssym.p, c_slen.p, u0, c_sfused32.p}; }
     u64 level_maxrun() {
         StageTimer st(&tm.ind_expand, "ind_expand");
         return prim::reduce_max<u64>(bwt.R, RunLenIn64{run_len()}, "induce_maxrun");
     }
-    // what pass C assembles: a contiguous piece of the level's pre-BWT, the metasymbols (buckets) whose HOCC runs lie in it
-    // (indices relative to the piece), and the number of symbols the piece describes.  The whole level on one GPU.
-    struct AsmIn { const u32 *psym; const idx_t *plen; u64 P; const u32 *u_to_p; const u32 *p_to_u; u64 M; u32 sigma; u64 n_out; };
-    // to_image: the caller runs finish() right behind level 0 (the single-GPU flow), so pass C of level 0 may write the image itself
-    void assemble(const AsmIn &in, LevelInfo &I, const CellView &cells, u64 E, DBuf<u32> &term, int r, bool to_image = false) {
-        StageTimer st(&tm.ind_assemble, "ind_assemble");
-        DBuf<idx_t> Tpos;
-        u64 Tsum;
-        if (bwt.pos.p) { Tpos = std::move(bwt.pos); Tsum = bwt.n; }       // the run merge that produced BWT_{r+1} left its prefix behind
-        else {
-            Tpos.alloc(bwt.R + 1);
-            Tsum = (u64)prim::exclusive_scan<idx_t>(bwt.R, IdxIn<idx_t>{bwt.len.p}, Tpos.p, true, "asm.Tpos");
-        }
-        assemble_t(in, I, cells, E, Tpos, Tsum, term, r, to_image);
+    // The starts of the runs of BWT_{r+1} over its symbols (R + 1 entries) into Tpos, and the number of symbols: the prefix that the
+    // run merge which produced BWT_{r+1} left behind, else a scan of the lengths.
+    u64 take_tpos(DBuf<idx_t> &Tpos, const char *site) {
+        if (bwt.pos.p) { Tpos = std::move(bwt.pos); return bwt.n; }
+        Tpos.alloc(bwt.R + 1);
+        return (u64)prim::exclusive_scan<idx_t>(bwt.R, IdxIn<idx_t>{bwt.len.p}, Tpos.p, true, site);
     }
     void release_level(LevelData &L) {           // the level's grammar is no longer needed
         L.g0.release(); L.g1.release(); L.has_hocc.release(); L.u_to_p.release(); L.p_to_u.release(); L.prebwt.sym.release(); L.prebwt.len.release();
     }
-
     void induce_level() {
         if (bwt_level <= 0) throw prim::Error(-22, "no level left to induce");
         const int r = bwt_level - 1;
-        prim::rt().tag = r;
-        prim::rt().phase = 'i';
+        prim::rt().tag = r; prim::rt().phase = 'i';
         LevelData &L = levels[r];
         const u64 R = bwt.R;
         LevelInfo &I = linfo[r];
         I.R_next = R; I.P = L.prebwt.R;
         DBuf<u32> term(R);
-        int kb, lb;
-        const u64 E = expand_split(L, term, level_maxrun(), kb, lb);
-        I.E = E;
-        const CellView cells = cell_view(kb, lb);
+        cells = expand_split(L, term, level_maxrun());
+        I.E = cells.E;
         if (prim::rt().profile) {              // SURVEY 8d's E'_r and E_r for the roofline accounting (bench.py)
-            I.Esteps = E - prim::reduce_sum<u64>(R, TakeCountIn{bwt.sym.p, c_gp.p}, "stat.take_cells");
-            I.Emerged = prim::reduce_sum<u64>(E, CellHeadIn{cells}, "stat.merged_cells");
+            I.Esteps = cells.E - prim::reduce_sum<u64>(R, TakeCountIn{bwt.sym.p, cells.gp.p}, "stat.take_cells");
+            I.Emerged = prim::reduce_sum<u64>(cells.E, CellHeadIn{cells.view()}, "stat.merged_cells");
         }
-        assemble(AsmIn{L.prebwt.sym.p, L.prebwt.len.p, L.prebwt.R, L.u_to_p.p, L.p_to_u.p, L.M, L.sigma, L.info.n_in}, I, cells, E, term, r, r == 0);
+        assemble(AsmIn{L.prebwt.sym.p, L.prebwt.len.p, L.prebwt.R, L.u_to_p.p, L.p_to_u.p, L.M, L.sigma, L.info.n_in}, I, 0, term, r, r == 0);
         bwt_level = r;
         if (r == 0 && bwt.len.p) bwt.pos.release();      // (no level below wants the prefix -- unless it stands for the lengths)
-        I.R = bwt.R;
-        I.n = L.info.n_in;
+        I.R = bwt.R; I.n = L.info.n_in;
         if (keep_texts) keep_bwt(r);
         release_level(L);
     }
-    // pass C (exact_ind_phase.cpp:287-361): BWT_r from the pre-BWT, the induced cells and the rewritten BWT_{r+1}
-    void assemble_t(const AsmIn &L, LevelInfo &I, const CellView &cells, u64 E, DBuf<idx_t> &Tpos, u64 Tsum, DBuf<u32> &term, int r, bool to_image) {
-        const u32 bwt_code = L.sigma + 1, hocc_code = L.sigma + 2, take_code = bwt_code;
-        const u64 R = bwt.R, P = L.P, M = L.M;
+    // what pass C assembles: a contiguous piece of the level's pre-BWT, the metasymbols (buckets) whose HOCC runs lie in it
+    // (indices relative to the piece), and the number of symbols the piece describes.  The whole level on one GPU.
+    struct AsmIn { const u32 *psym; const idx_t *plen; u64 P; const u32 *u_to_p; const u32 *p_to_u; u64 M; u32 sigma; u64 n_out; };
+    // pass C (exact_ind_phase.cpp:287-361): BWT_r from the pre-BWT, the induced cells and the rewritten BWT_{r+1}.  As steps; assemble
+    // runs them.  Buckets are counted from u0 (a piece of the collection-level mode).
+    // to_image: the caller runs finish() right behind level 0 (the single-GPU flow), so pass C of level 0 may write the image itself
+    struct AsmStage {
+        Engine &eng; const AsmIn &L; LevelInfo &I; const CellView cells; const u64 E, Tsum; const int r; const bool to_image; const LevelCodes code; const u64 R;
+        DBuf<u32> esym; DBuf<idx_t> epos; u64 Re = 0;      // the maximal runs of the rewritten BWT_{r+1}: symbols, starts over the T axis
+        DBuf<RankCell> tstarts;                 // ... and the starts as a bit-vector with ranks
+        u64 NH = 0, G = 0;                      // non-HOCC pre-BWT runs, segments (those and the cells)
+        DBuf<idx_t> nh_len; DBuf<u32> nh_sym; DBuf<RankCell> kinds;
+        Runs out; u64 Ro = 0;
+        AsmStage(Engine &e, const AsmIn &l, LevelInfo &i, u32 u0, u64 tsum, int r_, bool img) : eng(e), L(l), I(i), cells(e.cells.view(u0)), E(e.cells.E), Tsum(tsum),
+            r(r_), to_image(img), code(l.sigma), R(e.bwt.R) {}
         // ---- the maximal runs of the rewritten BWT_{r+1} and their starts over the T axis
-        DBuf<u32> esym(R ? R : 1);
-        DBuf<idx_t> epos(R + 1);
-        const u64 Re = R ? (u64)prim::exclusive_scan_emit<idx_t>(R, TermHeadIn{term.p}, TermHeadEmitFn{term.p, Tpos.p, esym.p, epos.p}, "asm.truns") : 0;
-        Tpos.release(); term.release();
-        bwt.sym.release(); bwt.len.release();
-        const u64 nwT = Tsum / 64 + 2;
-        DBuf<RankCell> tstarts(nwT);
-        tstarts.zero();
-        if (Re) prim::for_each((Re + 15) / 16, BuildBitsFn{epos.p, Re, reinterpret_cast<u64 *>(tstarts.p), 2}, "asm.tbits");
-        prim::exclusive_scan_emit_nosync<u64>(nwT, RankCellPopcIn{tstarts.p}, RankCellBaseEmitFn{tstarts.p}, "asm.tbits");
-        // ---- the non-HOCC pre-BWT runs, compacted, and where they sit among the segments
-        DBuf<idx_t> nhb(P + 1);
-        const u64 NH = (u64)prim::exclusive_scan<idx_t>(P, NotCodeIn{L.psym, hocc_code}, nhb.p, true, "asm.nhb");
-        const u64 G = NH + E;
-        I.G = G;
-        DBuf<idx_t> seg_pos(NH ? NH : 1), nh_len(NH ? NH : 1);
-        DBuf<u32> nh_sym(NH ? NH : 1);
-        {
-            // where the cells of the buckets in front of a pre-BWT run end: a table over the metasymbols when the runs are
-            // many (one pass over the cells), a binary search per run when they are few (level 0: 45 k runs, 2.6 G cells)
-            DBuf<idx_t> first_cell;
-            if (P * 32 > E && L.p_to_u) {
-                first_cell.alloc(M + 1);
-                DBuf<idx_t> bstart1(M), bend(M);
-                bstart1.zero(); bend.zero();
-                prim::for_each(E, BucketEdgesFn{cells, E, bstart1.p, bend.p}, "asm.first_cell");
-                prim::exclusive_scan_nosync<idx_t>(M, BucketSizeIn{bstart1.p, bend.p}, first_cell.p, true, "asm.first_cell");
-            }
-            prim::for_each(P, PrePlaceFn{L.psym, L.plen, nhb.p, L.u_to_p, M, cells, E, L.p_to_u, first_cell.p, hocc_code,
-                                         seg_pos.p, nh_sym.p, nh_len.p}, "asm.pre_place");
+        void truns(DBuf<idx_t> &Tpos, DBuf<u32> &term) {
+            esym.alloc(R ? R : 1); epos.alloc(R + 1);
+            Re = R ? (u64)prim::exclusive_scan_emit<idx_t>(R, TermHeadIn{term.p}, TermHeadEmitFn{term.p, Tpos.p, esym.p, epos.p}, "asm.truns") : 0;
+            Tpos.release(); term.release(); eng.bwt.sym.release(); eng.bwt.len.release();
+            const u64 nwT = Tsum / 64 + 2;
+            tstarts.alloc(nwT); tstarts.zero();
+            if (Re) prim::for_each((Re + 15) / 16, BuildBitsFn{epos.p, Re, reinterpret_cast<u64 *>(tstarts.p), 2}, "asm.tbits");
+            prim::exclusive_scan_emit_nosync<u64>(nwT, RankCellPopcIn{tstarts.p}, RankCellBaseEmitFn{tstarts.p}, "asm.tbits");
         }
-        nhb.release();
-        const u64 nwG = G / 64 + 2;
-        DBuf<RankCell> kinds(nwG);
-        kinds.zero();
-        if (NH) prim::for_each((NH + 15) / 16, BuildBitsFn{seg_pos.p, NH, reinterpret_cast<u64 *>(kinds.p), 2}, "asm.kinds");
-        prim::exclusive_scan_emit_nosync<u64>(nwG, RankCellPopcIn{kinds.p}, RankCellBaseEmitFn{kinds.p}, "asm.kinds");
-        seg_pos.release();
-        // ---- the stream merge: count (T positions, run heads), then emit
-        const AsmSeg seg{kinds.p, nh_sym.p, nh_len.p, cells, take_code, tstarts.p, esym.p, epos.p};
-        prim::SmPlan<idx_t> plan;
-        auto check_totals = [&] {
-            if (plan.take_total != Tsum) { plan.release(); throw prim::Error(-71, "induction: BWT_{r+1} consumption mismatch (level " + std::to_string(r) + ": " +
-                                                                                           std::to_string(plan.take_total) + " vs " + std::to_string(Tsum) + ")"); }
-            if (plan.len_total != L.n_out) { plan.release(); throw prim::Error(-71, "induction: BWT of level " + std::to_string(r) + " describes " + std::to_string(plan.len_total) +
-                                                                                           " symbols, the level has " + std::to_string(L.n_out)); }
-        };
-        Runs out;
-        u64 Ro = 0;
+        // ---- the non-HOCC pre-BWT runs, compacted, and where they sit among the segments
+        void place_prebwt() {
+            const u64 P = L.P, M = L.M;
+            DBuf<idx_t> nhb(P + 1);
+            NH = (u64)prim::exclusive_scan<idx_t>(P, NotCodeIn{L.psym, code.hocc}, nhb.p, true, "asm.nhb");
+            I.G = G = NH + E;
+            DBuf<idx_t> seg_pos(NH ? NH : 1);
+            nh_len.alloc(NH ? NH : 1); nh_sym.alloc(NH ? NH : 1);
+            {
+                // where the cells of the buckets in front of a pre-BWT run end: a table over the metasymbols when the runs are
+                // many (one pass over the cells), a binary search per run when they are few (level 0: 45 k runs, 2.6 G cells)
+                DBuf<idx_t> first_cell;
+                if (P * 32 > E && L.p_to_u) {
+                    first_cell.alloc(M + 1);
+                    DBuf<idx_t> bstart1(M), bend(M);
+                    bstart1.zero(); bend.zero();
+                    prim::for_each(E, BucketEdgesFn{cells, E, bstart1.p, bend.p}, "asm.first_cell");
+                    prim::exclusive_scan_nosync<idx_t>(M, BucketSizeIn{bstart1.p, bend.p}, first_cell.p, true, "asm.first_cell");
+                }
+                prim::for_each(P, PrePlaceFn{L.psym, L.plen, nhb.p, L.u_to_p, M, cells, E, L.p_to_u, first_cell.p, code.hocc,
+                                             seg_pos.p, nh_sym.p, nh_len.p}, "asm.pre_place");
+            }
+            nhb.release();
+            const u64 nwG = G / 64 + 2;
+            kinds.alloc(nwG); kinds.zero();
+            if (NH) prim::for_each((NH + 15) / 16, BuildBitsFn{seg_pos.p, NH, reinterpret_cast<u64 *>(kinds.p), 2}, "asm.kinds");
+            prim::exclusive_scan_emit_nosync<u64>(nwG, RankCellPopcIn{kinds.p}, RankCellBaseEmitFn{kinds.p}, "asm.kinds");
+        }
+        typedef prim::SmPlan<idx_t> Plan;
+        struct PlanGuard { Plan &p; ~PlanGuard() { p.release(); } };      // (the plan's device arrays go with the scope, thrown out of or not)
+        void check_totals(const Plan &plan) const {
+            if (plan.take_total != Tsum) throw prim::Error(-71, "induction: BWT_{r+1} consumption mismatch (level " + std::to_string(r) + ": " +
+                                                                    std::to_string(plan.take_total) + " vs " + std::to_string(Tsum) + ")");
+            if (plan.len_total != L.n_out) throw prim::Error(-71, "induction: BWT of level " + std::to_string(r) + " describes " + std::to_string(plan.len_total) +
+                                                                      " symbols, the level has " + std::to_string(L.n_out));
+        }
         // ONE WALK (round 6): the run heads are found and written by one pass over the segments, the run index at every tile's start
         // comes from a look-back across the tiles (prim::stream_merge_onepass) -- the count pass (28 of 125 ms of pass C at 10 GB)
         // re-derived exactly what the emit pass derives.  The runs are written into arrays sized for an upper bound (every segment
@@ -4855,66 +4863,77 @@ class Engine {
         // with tiles of 2048 (GRLBWT_DEV_SM1_SPT=8) -- and needs 12 bytes per SEGMENT of upper-bound arrays (32 GB at level 0 of the
         // 10 GB build, where the runs take 20): the two-pass form stays.
         // (GRLBWT_ASM_ONE_WALK=1: the tests take the one-walk form at every level, plain or not)
-        const bool two_pass = prim::sw().asm_two_pass;
-        const bool plain_too = prim::sw().asm_one_walk;
-        const bool mostly_plain = NH * 64 < G;
-        bool done = false;
-        if (!two_pass && (!mostly_plain || plain_too)) {
+        bool one_walk(const AsmSeg &seg, Plan &plan, bool mostly_plain) {
+            if (prim::sw().asm_two_pass || (mostly_plain && !prim::sw().asm_one_walk)) return false;
             const u64 cap = G + Re + 1;
             // queued segments: a TAKE that spans more than kSmInline further runs of T -- at most Re / kSmInline of them
             const u64 qcap = Re / prim::kSmInline + 1;
             out.sym.alloc(cap); out.pos.alloc(cap + 1);
-            try { done = prim::stream_merge_onepass<AsmSeg, idx_t>(G, seg, plan, out.sym.p, out.pos.p, cap, qcap, "asm", mostly_plain); } catch (...) { plan.release(); throw; }
-            if (done) {
-                check_totals();
-                Ro = plan.heads;
+            if (prim::stream_merge_onepass<AsmSeg, idx_t>(G, seg, plan, out.sym.p, out.pos.p, cap, qcap, "asm", mostly_plain)) {
+                check_totals(plan); Ro = plan.heads;
                 out.sym.shrink(Ro); out.pos.shrink(Ro + 1);
-            } else {
-                out.sym.release(); out.pos.release();
-                if (prim::sw().table_trace) fprintf(stderr, "[grlbwt] level %d: the one-walk form of pass C gave up, taking count + emit\n", r);
+                return true;
             }
+            out.sym.release(); out.pos.release();
+            if (prim::sw().table_trace) fprintf(stderr, "[grlbwt] level %d: the one-walk form of pass C gave up, taking count + emit\n", r);
+            return false;
         }
-        if (!done) {
-            prim::stream_merge_count<AsmSeg, idx_t>(G, seg, plan, "asm", mostly_plain);      // (few pre-BWT runs among the segments: small tiles, see prim_hip.hpp)
-            check_totals();
-            Ro = plan.heads;
-            // Level 0, and nothing but finish() reads its runs: the emit pass writes the .rl_bwt records themselves (a run's length is
-            // the distance to the next head, which the pass has at hand) -- the 12 bytes per run of (symbol, position) are neither
-            // allocated nor written, and finish() has no pack pass left that reads them back.  GRLBWT_ASM_IMAGE=0,
-            // kept levels, records wider than 8 bytes and the serial stand-in take emit + pack.
-            image_fused = false;
+        // Level 0, and nothing but finish() reads its runs: the emit pass writes the .rl_bwt records themselves (a run's length is
+        // the distance to the next head, which the pass has at hand) -- the 12 bytes per run of (symbol, position) are neither
+        // allocated nor written, and finish() has no pack pass left that reads them back.  GRLBWT_ASM_IMAGE=0,
+        // kept levels, records wider than 8 bytes and the serial stand-in take emit + pack.
 #ifdef GRLBWT_PRIM_HIP
-            const u32 sb = (u32)stats.sb, fb = (u32)stats.fb;
-            if (to_image && r == 0 && !keep_texts && sb + fb <= 8 && fb < 8 && prim::sw().asm_image != 0) {
-                image_bytes = 16 + Ro * (u64)(sb + fb);
-                try {
-                    image.alloc(image_bytes);
-                    image_header(sb, fb);
-                    prim::stream_merge_emit_records<AsmSeg, idx_t>(seg, plan, image.p + 16, sb + fb, ImageRecFn{sb, alpha.p}, "asm");
-                } catch (...) { plan.release(); throw; }
-                image_fused = true;
-            }
-#else
-            (void)to_image;
-#endif
-            if (!image_fused) {
-                out.sym.alloc(Ro); out.pos.alloc(Ro + 1);
-                try { prim::stream_merge_emit<AsmSeg, idx_t>(seg, plan, out.sym.p, out.pos.p, "asm"); } catch (...) { plan.release(); throw; }
-            }
+        bool can_emit_records() const {
+            const u32 sb = (u32)eng.stats.sb, fb = (u32)eng.stats.fb;
+            return to_image && r == 0 && !eng.keep_texts && sb + fb <= 8 && fb < 8 && prim::sw().asm_image != 0;
         }
-        I.A = plan.atoms;
-        plan.release();
-        const idx_t total = (idx_t)L.n_out;
-        if (out.pos.p) prim::h2d(out.pos.p + Ro, &total, sizeof(idx_t));      // (no arrays: the image holds the runs)
-        // everything but the runs can go before their lengths are taken (peak memory)
-        kinds.release(); nh_sym.release(); nh_len.release(); tstarts.release(); esym.release(); epos.release();
-        release_cells();
-        out.R = Ro; out.n = L.n_out;            // (no length array: RunLen reads the prefix)
-        bwt = std::move(out);
+        void emit_records(const AsmSeg &seg, Plan &plan) {
+            const u32 sb = (u32)eng.stats.sb, fb = (u32)eng.stats.fb;
+            eng.image.alloc(eng.image_bytes = 16 + Ro * (u64)(sb + fb));
+            image_header(eng.image.p, sb, fb);
+            prim::stream_merge_emit_records<AsmSeg, idx_t>(seg, plan, eng.image.p + 16, sb + fb, ImageRecFn{sb, eng.alpha.p}, "asm");
+            eng.image_fused = true;
+        }
+#else
+        bool can_emit_records() const { return false; }
+        void emit_records(const AsmSeg &, Plan &) {}
+#endif
+        void count_emit(const AsmSeg &seg, Plan &plan, bool mostly_plain) {
+            prim::stream_merge_count<AsmSeg, idx_t>(G, seg, plan, "asm", mostly_plain);      // (few pre-BWT runs among the segments: small tiles, see prim_hip.hpp)
+            check_totals(plan); Ro = plan.heads;
+            eng.image_fused = false;
+            if (can_emit_records()) { emit_records(seg, plan); return; }
+            out.sym.alloc(Ro); out.pos.alloc(Ro + 1);
+            prim::stream_merge_emit<AsmSeg, idx_t>(seg, plan, out.sym.p, out.pos.p, "asm");
+        }
+        // ---- the stream merge: one walk, or count (T positions, run heads), then emit
+        void stream_merge() {
+            const AsmSeg seg{kinds.p, nh_sym.p, nh_len.p, cells, code.take, tstarts.p, esym.p, epos.p};
+            Plan plan; PlanGuard guard{plan};
+            const bool mostly_plain = NH * 64 < G;
+            if (!one_walk(seg, plan, mostly_plain)) count_emit(seg, plan, mostly_plain);
+            I.A = plan.atoms;
+        }
+        void tail() {
+            const idx_t total = (idx_t)L.n_out;
+            if (out.pos.p) prim::h2d(out.pos.p + Ro, &total, sizeof(idx_t));      // (no arrays: the image holds the runs)
+            // everything but the runs can go before their lengths are taken (peak memory)
+            kinds.release(); nh_sym.release(); nh_len.release(); tstarts.release(); esym.release(); epos.release();
+            eng.cells.release();
+            out.R = Ro; out.n = L.n_out;            // (no length array: RunLen reads the prefix)
+            eng.bwt = std::move(out);
+        }
+    };
+    void assemble(const AsmIn &in, LevelInfo &I, u32 u0, DBuf<u32> &term, int r, bool to_image = false) {
+        StageTimer st(&tm.ind_assemble, "ind_assemble");
+        DBuf<idx_t> Tpos;
+        const u64 Tsum = take_tpos(Tpos, "asm.Tpos");
+        AsmStage Z(*this, in, I, u0, Tsum, r, to_image);
+        Z.truns(Tpos, term);
+        Z.place_prebwt();
+        Z.stream_merge();
+        Z.tail();
     }
-    // the induced cells of the level being assembled (owned here so that pass C can drop them before the run merge)
-    DBuf<u32> c_skey, c_ssym, c_sfused32; DBuf<idx_t> c_slen; DBuf<u64> c_spack, c_sfused, c_gp;
-    void release_cells() { c_skey.release(); c_ssym.release(); c_slen.release(); c_spack.release(); c_sfused.release(); c_sfused32.release(); c_gp.release(); }
 
     void induce_phase() {                                        // exact_ind_phase.cpp:674-697
         first_bwt();
@@ -4922,11 +4941,11 @@ class Engine {
     }
 
     // ---- a16/a17: .rl_bwt image in HBM --------------------------------------
-    bool image_fused = false;                 // `image` is written already: level 0's pass C emitted records (assemble_t)
-    void image_header(u32 sb, u32 fb) {
+    bool image_fused = false;                 // `image` is written already: level 0's pass C emitted records (AsmStage::emit_records)
+    static void image_header(u8 *dst, u32 sb, u32 fb) {          // the image's 16 header bytes, to device memory
         u8 hdr[16] = {0};
         for (int i = 0; i < 8; i++) { hdr[i] = (u8)((u64)sb >> (8 * i)); hdr[8 + i] = (u8)((u64)fb >> (8 * i)); }
-        prim::h2d(image.p, hdr, 16);
+        prim::h2d(dst, hdr, 16);
     }
     void finish() {
         if (bwt_level != 0) throw prim::Error(-22, "induction not finished");
@@ -4936,13 +4955,13 @@ class Engine {
         if (!image_fused) {
         image_bytes = 16 + bwt.R * (u64)(sb + fb);
         image.alloc(image_bytes);
-        image_header(sb, fb);
+        image_header(image.p, sb, fb);
         // records of up to 8 bytes go through prim::pack_records (tiles assembled in LDS, 16-byte stores); wider ones one lane per run.
         // (Four runs per lane, their 4 x 5 bytes put together in registers, was measured at 15.5 ms against 9 for one lane per run on
         // the 1.66 G runs of the 10 GB image: the loads of a lane's four runs are what is 20 bytes apart then.)
         if (sb + fb <= 8 && fb < 8) prim::pack_records(bwt.R, RunRecordFn{bwt.sym.p, run_len(), sb, alpha.p}, sb + fb, image.p + 16, "pack_rl_bwt");
         else prim::for_each(bwt.R, PackRunsFn{bwt.sym.p, run_len(), sb, fb, image.p, 16u, alpha.p}, "pack_rl_bwt");
-        }                                         // (else: pass C of level 0 wrote header and records, assemble_t)
+        }                                         // (else: pass C of level 0 wrote header and records, AsmStage::emit_records)
         image_fused = false;
         image_runs = bwt.R;
         image_part_off = 0; image_part_bytes = image_bytes;
@@ -5236,272 +5255,254 @@ class Engine {
     // go to the owners of their buckets (8 bytes per cell in the usual layout) and are merged by one stable split on the
     // bucket bits (rank order inside a bucket = slice order); (5) every rank runs the single-GPU pass C on its piece and
     // ends up holding its slice of BWT_r.  Nothing is replicated and no symbol crosses the fabric more than once per level.
+    // (local failures -- out of memory, an internal check -- are recorded by Comm::local and travel with the next counter exchange,
+    // where every rank raises: nobody is left waiting for a rank that gave up)
+    void set_empty_bwt() { bwt = Runs(); bwt.sym.alloc(0); bwt.len.alloc(0); }
     void dist_first_bwt(const Comm &C) {
-        try { first_bwt(); }     // local: my strings' final symbols, in collection order
-        catch (const prim::Error &e) {            // (raised by every rank at the first counter exchange of the level below)
-            C.fail(e);
-            bwt = Runs();
-            bwt.sym.alloc(0); bwt.len.alloc(0);
-            bwt_level = (int)levels.size();
-            linfo.assign(levels.size() + 1, LevelInfo());
-        }
+        C.local([&] { first_bwt(); });           // local: my strings' final symbols, in collection order
+        // (a failure is raised by every rank at the first counter exchange of the level below)
+        if (C.pending) { set_empty_bwt(); bwt_level = (int)levels.size(); linfo.assign(levels.size() + 1, LevelInfo()); }
     }
-
-    void dist_induce_level(const Comm &C) {
-        if (bwt_level <= 0) throw prim::Error(-22, "no level left to induce");
-        const int r = bwt_level - 1;
-        prim::rt().tag = r;
-        prim::rt().phase = 'i';
-        LevelData &L = levels[r];
-        const u32 bwt_code = L.sigma + 1, hocc_code = L.sigma + 2, take_code = bwt_code;
-        const u64 P = L.prebwt.R, M = L.M, R = bwt.R;
-        const int N = C.size, me = C.rank;
-        LevelInfo &I = linfo[r];
-        I.R_next = R; I.P = P;
-        // (1) one cell layout for all shards, then passes A+B over my slice (the single-GPU kernels)
-        // (local failures -- out of memory, an internal check -- are recorded with C.fail and travel with the next counter
-        // exchange, where every rank raises: nobody is left waiting for a rank that gave up)
-        DBuf<idx_t> Tpos;
-        u64 Tlocal = 0, maxrun = 0, Toff = 0, Ttotal = 0;
-        std::vector<u64> piece;                  // (pre_local) per rank boundary: -, first metasymbol, symbols and BWT-marker symbols in front
-        {
-            u64 mr = 0;
-            try {
-                StageTimer st(&tm.ind_expand, "ind_expand");
-                need_len();                      // (pass C leaves the prefix only; the passes below read lengths after the prefix has moved on)
-                if (bwt.pos.p) { Tpos = std::move(bwt.pos); Tlocal = bwt.n; }      // pass C of the level above left my slice's prefix behind
-                else {
-                    Tpos.alloc(R + 1);
-                    Tlocal = (u64)prim::exclusive_scan<idx_t>(R, IdxIn<idx_t>{bwt.len.p}, Tpos.p, true, "dist.Tpos");
-                }
-                mr = level_maxrun();
-            } catch (const prim::Error &e) { C.fail(e); Tlocal = 0; mr = 0; }
-            // (pre-BWT kept by key range: my piece's symbols, BWT-marker symbols, metasymbols and runs travel with this exchange)
-            u64 pn = 0, pb = 0;
-            if (L.pre_local) {
-                try {
-                    pn = prim::reduce_sum<u64>(P, IdxIn<idx_t>{L.prebwt.len.p}, "dist.piece_sums");
-                    pb = prim::reduce_sum<u64>(P, PreBwtLenIn{L.prebwt.sym.p, L.prebwt.len.p, bwt_code}, "dist.piece_sums");
-                } catch (const prim::Error &e) { C.fail(e); }
-            }
-            std::vector<u64> g1 = C.allgather_u64({mr, Tlocal, pn, pb, (u64)L.Ml, P});
+    // One level as steps over what they decide; dist_induce_level runs them in order.
+    struct DistInduce {
+        // the columns of the two gathered tables: a shard's row of agree_layout's all-gather, and a piece boundary (a row of OwnerSplitFn's):
+        // the owner's first pre-BWT run and first metasymbol, the symbols and the BWT-marker symbols in front of its piece
+        enum { S_MAXRUN, S_T, S_SYMS, S_BWT_SYMS, S_METAS, S_RUNS, S_COLS };
+        enum { B_RUN, B_META, B_SYMS, B_BWT_SYMS, B_COLS };
+        static u64 &at(std::vector<u64> &rows, int d, int col) { return rows[(u64)B_COLS * d + col]; }
+        Engine &eng; const Comm &C; const int r; LevelData &L; LevelInfo &I; const LevelCodes code;
+        const u64 P, M, R; const int N, me;
+        DBuf<idx_t> Tpos;                        // my slice of BWT_{r+1}: run starts, symbols, symbols of the slices in front, of all slices
+        u64 Tlocal = 0, Toff = 0, Ttotal = 0, maxrun = 0;
+        std::vector<u64> piece;                  // (pre_local) the boundaries of the ranks' own parts of the pre-BWT
+        DBuf<u32> term; DBuf<u64> split;         // the rewritten symbols of my runs; the piece boundaries on the device
+        std::vector<u64> sp, v, mat, Tc;         // the boundaries; my cells and TAKE symbols per owner, everybody's, and the symbols of the
+        u64 n_r = 0;                             // rewritten BWT_{r+1} consumed in front of every piece; the level's symbols
+        DBuf<u32> wsym; DBuf<idx_t> wlen; u64 Rw = 0;      // my piece's window of the rewritten BWT_{r+1}
+        DistInduce(Engine &e, const Comm &c, int r_) : eng(e), C(c), r(r_), L(e.levels[r_]), I(e.linfo[r_]), code(L.sigma), P(L.prebwt.R), M(L.M), R(e.bwt.R),
+            N(c.size), me(c.rank), sp(B_COLS * ((u64)c.size + 1), 0), v(2 * (u64)c.size, 0) { I.R_next = R; I.P = P; }
+        // (1) one cell layout for all shards: the longest run of all slices.  (Pre-BWT kept by key range: my piece's symbols, BWT-marker
+        // symbols, metasymbols and runs travel with this exchange.)
+        void agree_layout() {
+            u64 mr = 0, pn = 0, pb = 0;
+            C.local([&] {
+                StageTimer st(&eng.tm.ind_expand, "ind_expand");
+                eng.need_len();                  // (pass C leaves the prefix only; the passes below read lengths after the prefix has moved on)
+                Tlocal = eng.take_tpos(Tpos, "dist.Tpos");
+                mr = eng.level_maxrun();
+            });
+            if (C.pending) { Tlocal = 0; mr = 0; }
+            if (L.pre_local) C.local([&] {
+                pn = prim::reduce_sum<u64>(P, IdxIn<idx_t>{L.prebwt.len.p}, "dist.piece_sums");
+                pb = prim::reduce_sum<u64>(P, PreBwtLenIn{L.prebwt.sym.p, L.prebwt.len.p, code.bwt}, "dist.piece_sums");
+            });
+            const std::vector<u64> g1 = C.allgather_u64({mr, Tlocal, pn, pb, (u64)L.Ml, P});
+            if (L.pre_local) piece.assign(B_COLS * ((u64)N + 1), 0);
+            u64 Psum = 0;
             for (int g = 0; g < N; g++) {
-                if (g1[6 * g] > maxrun) maxrun = g1[6 * g];
-                if (g < me) Toff += g1[6 * g + 1];
-                Ttotal += g1[6 * g + 1];
+                const u64 *row = &g1[(u64)S_COLS * g];
+                maxrun = std::max(maxrun, row[S_MAXRUN]);
+                Toff += g < me ? row[S_T] : 0; Ttotal += row[S_T];
+                if (!L.pre_local) continue;
+                at(piece, g + 1, B_META) = at(piece, g, B_META) + row[S_METAS];
+                at(piece, g + 1, B_SYMS) = at(piece, g, B_SYMS) + row[S_SYMS];
+                at(piece, g + 1, B_BWT_SYMS) = at(piece, g, B_BWT_SYMS) + row[S_BWT_SYMS];
+                Psum += row[S_RUNS];
             }
-            if (L.pre_local) {
-                piece.assign(4 * ((u64)N + 1), 0);
-                u64 Psum = 0;
-                for (int g = 0; g < N; g++) {
-                    piece[4 * (g + 1) + 1] = piece[4 * g + 1] + g1[6 * g + 4];
-                    piece[4 * (g + 1) + 2] = piece[4 * g + 2] + g1[6 * g + 2];
-                    piece[4 * (g + 1) + 3] = piece[4 * g + 3] + g1[6 * g + 3];
-                    Psum += g1[6 * g + 5];
-                }
-                if (piece[4 * (u64)N + 1] != M) throw prim::Error(-71, "dist induction: the pieces' metasymbols do not add up (level " + std::to_string(r) + ")");
-                I.P = Psum;
-            }
+            if (!L.pre_local) return;
+            if (at(piece, N, B_META) != M) throw prim::Error(-71, "dist induction: the pieces' metasymbols do not add up (level " + std::to_string(r) + ")");
+            I.P = Psum;
         }
-        DBuf<u32> term;
-        int kb = 1, lb = 1;
-        u64 E = 0;
-        u32 p0, p1, u0, u1;
-        u64 n_out, n_r = 0;
-        std::vector<u64> sp(4 * ((u64)N + 1), 0), cbh, v(2 * (u64)N, 0);
-        DBuf<u64> split;
-        try {
+        // passes A+B over my slice (the single-GPU kernels)
+        void expand() {
             term.alloc(R);
-            split.alloc(4 * ((u64)N + 1));
+            split.alloc(B_COLS * ((u64)N + 1));
             // (GRLBWT_TEST_FAIL_RANK_INDUCE=<rank>: the tests make one rank fail here)
             if (test_fail_rank(prim::sw().test_fail_rank_induce, me)) throw prim::Error(-12, "out of device memory (injected by the test)");
-            E = expand_split(L, term, maxrun, kb, lb);
-            I.E = E;
-            StageTimer st(&tm.ind_assemble, "ind_assemble");
-            // (2) owners of the output: pre-BWT run ranges of about n_r / size symbols, and the buckets inside them
+            eng.cells = eng.expand_split(L, term, maxrun);
+            I.E = eng.cells.E;
+        }
+        // (2) owners of the output: pre-BWT run ranges of about n_r / size symbols, and the buckets inside them
+        void owners() {
+            const std::string not_the_level = "dist induction: the pre-BWT of level " + std::to_string(r) + " does not describe the level";
             if (L.pre_local) {                   // the pieces are the ranks' own parts of the pre-BWT: nothing to look up
-                sp = piece;
-                sp[4 * (u64)me] = 0; sp[4 * ((u64)me + 1)] = P;          // (run indices are relative to my part)
-                n_r = piece[4 * (u64)N + 2];
-                if (n_r != L.info.n_in) throw prim::Error(-71, "dist induction: the pre-BWT of level " + std::to_string(r) + " does not describe the level");
-                prim::h2d(split.p, sp.data(), 4 * ((u64)N + 1) * 8);
-            } else {
-                DBuf<idx_t> Ppos(P + 1);
-                DBuf<HoccBwt> PHB(P + 1);
-                n_r = (u64)prim::exclusive_scan<idx_t>(P, IdxIn<idx_t>{L.prebwt.len.p}, Ppos.p, true, "dist.Ppos");
-                prim::exclusive_scan_nosync<HoccBwt>(P, PreScanIn{L.prebwt.sym.p, L.prebwt.len.p, hocc_code, bwt_code}, PHB.p, true, "dist.pre_scan");
-                if (n_r != L.info.n_in) throw prim::Error(-71, "dist induction: the pre-BWT of level " + std::to_string(r) + " does not describe the level");
-                prim::for_each((u64)N + 1, OwnerSplitFn{Ppos.p, PHB.p, L.u_to_p.p, P, M, n_r, N, split.p}, "dist.owners");
-                sp = split.to_host(4 * ((u64)N + 1));
+                sp = piece; at(sp, me, B_RUN) = 0; at(sp, me + 1, B_RUN) = P;        // (run indices are relative to my part)
+                n_r = at(piece, N, B_SYMS);
+                if (n_r != L.info.n_in) throw prim::Error(-71, not_the_level);
+                prim::h2d(split.p, sp.data(), sp.size() * 8);
+                return;
             }
-            // my cells and my TAKE symbols per owner
-            {
-                const CellView mine = cell_view(kb, lb);
-                DBuf<u64> cb((u64)N + 1);
-                prim::for_each((u64)N + 1, CellBoundsFn{mine, E, split.p, cb.p}, "dist.cell_bounds");
-                cbh = cb.to_host((u64)N + 1);
-                for (int d = 0; d < N; d++) {
-                    const u64 cnt = cbh[d + 1] - cbh[d];
-                    v[d] = cnt;
-                    v[N + d] = cnt ? prim::reduce_sum<u64>(cnt, CellTakeOffIn{mine, take_code, cbh[d]}, "dist.take_sums") : 0;
-                }
+            DBuf<idx_t> Ppos(P + 1); DBuf<HoccBwt> PHB(P + 1);
+            n_r = (u64)prim::exclusive_scan<idx_t>(P, IdxIn<idx_t>{L.prebwt.len.p}, Ppos.p, true, "dist.Ppos");
+            prim::exclusive_scan_nosync<HoccBwt>(P, PreScanIn{L.prebwt.sym.p, L.prebwt.len.p, code.hocc, code.bwt}, PHB.p, true, "dist.pre_scan");
+            if (n_r != L.info.n_in) throw prim::Error(-71, not_the_level);
+            prim::for_each((u64)N + 1, OwnerSplitFn{Ppos.p, PHB.p, L.u_to_p.p, P, M, n_r, N, split.p}, "dist.owners");
+            sp = split.to_host(B_COLS * ((u64)N + 1));
+        }
+        // my cells and my TAKE symbols per owner
+        void count_cells() {
+            const CellView mine = eng.cells.view();
+            DBuf<u64> cb((u64)N + 1);
+            prim::for_each((u64)N + 1, CellBoundsFn{mine, eng.cells.E, split.p, cb.p}, "dist.cell_bounds");
+            const std::vector<u64> cbh = cb.to_host((u64)N + 1);
+            for (int d = 0; d < N; d++) {
+                const u64 cnt = v[d] = cbh[d + 1] - cbh[d];
+                v[N + d] = cnt ? prim::reduce_sum<u64>(cnt, CellTakeOffIn{mine, code.take, cbh[d]}, "dist.take_sums") : 0;
             }
-        } catch (const prim::Error &e) { C.fail(e); std::fill(v.begin(), v.end(), 0); }
-        {
-            StageTimer st(&tm.ind_assemble, "ind_assemble");
-            std::vector<u64> mat = C.allgather_u64(v);           // mat[s*2N + d] cells, mat[s*2N + N + d] TAKE symbols of rank s for owner d
-            // symbols of the rewritten BWT_{r+1} consumed in front of every owner's piece (output order = consumption order)
-            std::vector<u64> Tc((u64)N + 1);
-            {
-                u64 acc = 0;
-                for (int d = 0; d <= N; d++) {
-                    Tc[d] = sp[4 * d + 3] + acc;
-                    if (d < N) for (int g = 0; g < N; g++) acc += mat[(u64)g * 2 * N + N + d];
-                }
+        }
+        // everybody's counts (row s of mat: [d] cells, [N + d] TAKE symbols of rank s for owner d), and from them the symbols of the
+        // rewritten BWT_{r+1} consumed in front of every owner's piece (output order = consumption order)
+        void gather_counts() {
+            if (C.pending) std::fill(v.begin(), v.end(), 0);
+            mat = C.allgather_u64(v);
+            Tc.assign((u64)N + 1, 0);
+            u64 acc = 0;
+            for (int d = 0; d <= N; d++) {
+                Tc[d] = at(sp, d, B_BWT_SYMS) + acc;
+                if (d < N) for (int g = 0; g < N; g++) acc += mat[(u64)g * 2 * N + N + d];
             }
             if (Tc[N] != Ttotal) throw prim::Error(-71, "dist induction: BWT_{r+1} consumption mismatch (level " + std::to_string(r) + ": " +
                                                             std::to_string(Tc[N]) + " vs " + std::to_string(Ttotal) + ")");
-            // (3) every owner's window of the rewritten BWT_{r+1}: I send the part of it that lies in my slice
-            DBuf<u32> wsym; DBuf<idx_t> wlen;
-            u64 Rw = 0;
-            {
-                std::vector<u64> ab(2 * (u64)N), scnt(N), soff((u64)N + 1, 0), rcnt(N);
-                for (int d = 0; d < N; d++) {
-                    const u64 lo = Tc[d] > Toff ? Tc[d] - Toff : 0, hi = Tc[d + 1] > Toff ? Tc[d + 1] - Toff : 0;
-                    ab[2 * d] = lo < Tlocal ? lo : Tlocal;
-                    ab[2 * d + 1] = hi < Tlocal ? hi : Tlocal;
-                }
-                DBuf<u64> abd(2 * (u64)N), kc(2 * (u64)N), sod((u64)N + 1);
-                try {
-                    prim::h2d(abd.p, ab.data(), 2 * (u64)N * 8);
-                    prim::for_each((u64)N, WindowRunsFn{Tpos.p, R, abd.p, kc.p}, "dist.window_runs");
-                    std::vector<u64> kch = kc.to_host(2 * (u64)N);
-                    for (int d = 0; d < N; d++) { scnt[d] = kch[2 * d + 1]; soff[d + 1] = soff[d] + scnt[d]; }
-                } catch (const prim::Error &e) { C.fail(e); std::fill(scnt.begin(), scnt.end(), 0); std::fill(soff.begin(), soff.end(), 0); }
-                const auto cn = C.counts(scnt);
-                rcnt = cn.rcnt; Rw = cn.total;
-                const u64 maxw = cn.maxb;
-                // (the lengths travel as u32 whenever the level's longest run fits -- the ranks agreed on `maxrun` for the cell layout)
-                const bool narrow = sizeof(idx_t) == 8 && maxrun < 0xFFFFFFFFull;
-                DBuf<u32> ssym, slen32, wlen32; DBuf<idx_t> slen;
-                try {
-                    ssym.alloc(soff[N]);
-                    prim::h2d(sod.p, soff.data(), ((u64)N + 1) * 8);
-                    if (narrow) {
-                        slen32.alloc(soff[N]); wlen32.alloc(Rw);
-                        prim::for_each(soff[N], WindowSendFn<u32>{Tpos.p, term.p, abd.p, kc.p, sod.p, N, ssym.p, slen32.p}, "dist.window_send");
-                    } else {
-                        slen.alloc(soff[N]);
-                        prim::for_each(soff[N], WindowSendFn<idx_t>{Tpos.p, term.p, abd.p, kc.p, sod.p, N, ssym.p, slen.p}, "dist.window_send");
-                    }
-                    wsym.alloc(Rw); wlen.alloc(Rw);
-                } catch (const prim::Error &e) { C.fail(e); }
-                C.allgather_u64({});                             // (nothing but the failure flag: the bulk exchanges below have no way back)
-                C.named("induce.window_sym").alltoall(ssym.p, scnt, wsym.p, rcnt, sizeof(u32), maxw);
+        }
+        // (3) every owner's window of the rewritten BWT_{r+1}: I send the part of it that lies in my slice
+        void exchange_window() {
+            std::vector<u64> ab(2 * (u64)N), scnt(N), soff((u64)N + 1, 0);
+            for (int d = 0; d < N; d++) {
+                const u64 lo = Tc[d] > Toff ? Tc[d] - Toff : 0, hi = Tc[d + 1] > Toff ? Tc[d + 1] - Toff : 0;
+                ab[2 * d] = lo < Tlocal ? lo : Tlocal;
+                ab[2 * d + 1] = hi < Tlocal ? hi : Tlocal;
+            }
+            DBuf<u64> abd(2 * (u64)N), kc(2 * (u64)N), sod((u64)N + 1);
+            C.local([&] {
+                prim::h2d(abd.p, ab.data(), 2 * (u64)N * 8);
+                prim::for_each((u64)N, WindowRunsFn{Tpos.p, R, abd.p, kc.p}, "dist.window_runs");
+                const std::vector<u64> kch = kc.to_host(2 * (u64)N);
+                for (int d = 0; d < N; d++) { scnt[d] = kch[2 * d + 1]; soff[d + 1] = soff[d] + scnt[d]; }
+            });
+            if (C.pending) { std::fill(scnt.begin(), scnt.end(), 0); std::fill(soff.begin(), soff.end(), 0); }
+            const auto cn = C.counts(scnt);
+            const std::vector<u64> &rcnt = cn.rcnt;
+            const u64 maxw = cn.maxb; Rw = cn.total;
+            // (the lengths travel as u32 whenever the level's longest run fits -- the ranks agreed on `maxrun` for the cell layout)
+            const bool narrow = sizeof(idx_t) == 8 && maxrun < 0xFFFFFFFFull;
+            DBuf<u32> ssym, slen32, wlen32; DBuf<idx_t> slen;
+            C.local([&] {
+                ssym.alloc(soff[N]);
+                prim::h2d(sod.p, soff.data(), ((u64)N + 1) * 8);
                 if (narrow) {
-                    C.named("induce.window_len").alltoall(slen32.p, scnt, wlen32.p, rcnt, sizeof(u32), maxw);
-                    prim::for_each(Rw, WidenLenFn{wlen32.p, wlen.p}, "dist.window_send");
-                } else C.named("induce.window_len").alltoall(slen.p, scnt, wlen.p, rcnt, sizeof(idx_t), maxw);
-            }
-            Tpos.release(); term.release();
-            bwt.sym.release(); bwt.len.release(); bwt.pos.release();
-            // (4) the cells of my buckets, from every rank; rank order inside a bucket = order of the slices
-            {
-                const std::vector<u64> scnt(v.begin(), v.begin() + N);
-                const auto cn = C.unpack(mat, 2 * (u64)N, 0);
-                const std::vector<u64> &rcnt = cn.rcnt;
-                const u64 Er = cn.total, maxc = cn.maxb;
-                const int bits = kb;
-                // (the received blocks are bucket-sorted: merged by block offsets; GRLBWT_MERGE_CELLS=sort keeps the stable radix sort)
-                const bool merge_by_blocks = prim::sw().merge_cells != 's';
-                const u32 mu0 = (u32)sp[4 * me + 1], mu1 = (u32)sp[4 * (me + 1) + 1];
-                if (c_sfused32.p) {
-                    DBuf<u32> rf(Er);
-                    C.named("induce.cells").alltoall(c_sfused32.p, scnt, rf.p, rcnt, 4, maxc);
-                    c_sfused32 = std::move(rf);
-                    if (N > 1 && Er) {
-                        if (merge_by_blocks) merge_cell_blocks<u32>(c_sfused32, rcnt, kb, lb, mu0, (u64)(mu1 - mu0), Er);
-                        else {
-                            DBuf<u32> tmp(Er);
-                            if (prim::sort_keys<u32, 1>(c_sfused32.p, tmp.p, Er, 0, bits, "dist.merge_cells")) c_sfused32 = std::move(tmp);
-                        }
-                    }
-                } else if (c_sfused.p) {
-                    DBuf<u64> rf(Er);
-                    C.named("induce.cells").alltoall(c_sfused.p, scnt, rf.p, rcnt, 8, maxc);
-                    c_sfused = std::move(rf);
-                    if (N > 1 && Er) {
-                        if (merge_by_blocks) merge_cell_blocks<u64>(c_sfused, rcnt, kb, lb, mu0, (u64)(mu1 - mu0), Er);
-                        else {
-                            DBuf<u64> tmp(Er);
-                            if (prim::sort_keys<u64, 1>(c_sfused.p, tmp.p, Er, 0, bits, "dist.merge_cells")) c_sfused = std::move(tmp);
-                        }
-                    }
-                } else if (c_spack.p) {
-                    DBuf<u32> rk(Er); DBuf<u64> rp(Er);
-                    C.named("induce.cells_key").alltoall(c_skey.p, scnt, rk.p, rcnt, 4, maxc);
-                    C.named("induce.cells_pack").alltoall(c_spack.p, scnt, rp.p, rcnt, 8, maxc);
-                    c_skey = std::move(rk); c_spack = std::move(rp);
-                    if (N > 1 && Er) {
-                        DBuf<u32> k2(Er); DBuf<u64> p2(Er);
-                        if (prim::sort_pairs<u32, u64>(c_skey.p, c_spack.p, k2.p, p2.p, Er, 0, bits, "dist.merge_cells")) { c_skey = std::move(k2); c_spack = std::move(p2); }
-                    }
+                    slen32.alloc(soff[N]); wlen32.alloc(Rw);
+                    prim::for_each(soff[N], WindowSendFn<u32>{Tpos.p, term.p, abd.p, kc.p, sod.p, N, ssym.p, slen32.p}, "dist.window_send");
                 } else {
-                    DBuf<u32> rk(Er), rs(Er); DBuf<idx_t> rl(Er);
-                    C.named("induce.cells_key").alltoall(c_skey.p, scnt, rk.p, rcnt, 4, maxc);
-                    C.named("induce.cells_sym").alltoall(c_ssym.p, scnt, rs.p, rcnt, 4, maxc);
-                    C.named("induce.cells_len").alltoall(c_slen.p, scnt, rl.p, rcnt, sizeof(idx_t), maxc);
-                    c_skey = std::move(rk);
-                    if (N > 1 && Er) {
-                        DBuf<u32> k2(Er); DBuf<idx_t> ix(Er), ix2(Er);
-                        prim::for_each(Er, IotaIdxFn{ix.p}, "dist.merge_cells");
-                        int res = prim::sort_pairs<u32, idx_t>(c_skey.p, ix.p, k2.p, ix2.p, Er, 0, bits, "dist.merge_cells");
-                        c_ssym.alloc(Er); c_slen.alloc(Er);
-                        prim::for_each(Er, GatherCellFn{res ? ix2.p : ix.p, rs.p, rl.p, c_ssym.p, c_slen.p}, "dist.merge_cells");
-                        if (res) c_skey = std::move(k2);
-                    } else { c_ssym = std::move(rs); c_slen = std::move(rl); }
+                    slen.alloc(soff[N]);
+                    prim::for_each(soff[N], WindowSendFn<idx_t>{Tpos.p, term.p, abd.p, kc.p, sod.p, N, ssym.p, slen.p}, "dist.window_send");
                 }
-                E = Er;
+                wsym.alloc(Rw); wlen.alloc(Rw);
+            });
+            C.allgather_u64({});                             // (nothing but the failure flag: the bulk exchanges below have no way back)
+            C.named("induce.window_sym").alltoall(ssym.p, scnt, wsym.p, rcnt, sizeof(u32), maxw);
+            if (narrow) {
+                C.named("induce.window_len").alltoall(slen32.p, scnt, wlen32.p, rcnt, sizeof(u32), maxw);
+                prim::for_each(Rw, WidenLenFn{wlen32.p, wlen.p}, "dist.window_send");
+            } else C.named("induce.window_len").alltoall(slen.p, scnt, wlen.p, rcnt, sizeof(idx_t), maxw);
+            Tpos.release(); term.release();          // (my slice of BWT_{r+1} has been sent)
+            eng.bwt.sym.release(); eng.bwt.len.release(); eng.bwt.pos.release();
+        }
+        // (4) the cells of my buckets, from every rank; rank order inside a bucket = order of the slices
+        // (the received blocks are bucket-sorted: merged by block offsets; GRLBWT_MERGE_CELLS=sort keeps the stable radix sort)
+        template <class W> void exchange_words(const std::vector<u64> &scnt, const Comm::Counts &cn) {
+            Cells &c = eng.cells;
+            DBuf<W> &w = c.word<W>();
+            const u64 Er = cn.total;
+            DBuf<W> rf(Er);
+            C.named("induce.cells").alltoall(w.p, scnt, rf.p, cn.rcnt, sizeof(W), cn.maxb);
+            w = std::move(rf);
+            if (!(N > 1 && Er)) return;
+            if (prim::sw().merge_cells != 's') eng.merge_cell_blocks<W>(c, cn.rcnt, (u32)at(sp, me, B_META), at(sp, me + 1, B_META) - at(sp, me, B_META), Er);
+            else {
+                DBuf<W> tmp(Er);
+                if (prim::sort_keys<W, 1>(w.p, tmp.p, Er, 0, c.kb, "dist.merge_cells")) w = std::move(tmp);
             }
-            p0 = (u32)sp[4 * me]; p1 = (u32)sp[4 * (me + 1)];
-            u0 = (u32)sp[4 * me + 1]; u1 = (u32)sp[4 * (me + 1) + 1];
-            n_out = sp[4 * (me + 1) + 2] - sp[4 * me + 2];
+        }
+        void exchange_cells() {
+            Cells &c = eng.cells;
+            const std::vector<u64> scnt(v.begin(), v.begin() + N);
+            const auto cn = C.unpack(mat, 2 * (u64)N, 0);
+            const std::vector<u64> &rcnt = cn.rcnt; const u64 Er = cn.total, maxc = cn.maxb;
+            switch (c.layout) {
+            case CellLayout::Word32: exchange_words<u32>(scnt, cn); break;
+            case CellLayout::Word64: exchange_words<u64>(scnt, cn); break;
+            case CellLayout::Packed: {
+                DBuf<u32> rk(Er); DBuf<u64> rp(Er);
+                C.named("induce.cells_key").alltoall(c.key.p, scnt, rk.p, rcnt, 4, maxc);
+                C.named("induce.cells_pack").alltoall(c.pack.p, scnt, rp.p, rcnt, 8, maxc);
+                c.key = std::move(rk); c.pack = std::move(rp);
+                if (N > 1 && Er) {
+                    DBuf<u32> k2(Er); DBuf<u64> p2(Er);
+                    if (prim::sort_pairs<u32, u64>(c.key.p, c.pack.p, k2.p, p2.p, Er, 0, c.kb, "dist.merge_cells")) { c.key = std::move(k2); c.pack = std::move(p2); }
+                }
+            } break;
+            case CellLayout::Separate: {
+                DBuf<u32> rk(Er), rs(Er); DBuf<idx_t> rl(Er);
+                C.named("induce.cells_key").alltoall(c.key.p, scnt, rk.p, rcnt, 4, maxc);
+                C.named("induce.cells_sym").alltoall(c.sym.p, scnt, rs.p, rcnt, 4, maxc);
+                C.named("induce.cells_len").alltoall(c.len.p, scnt, rl.p, rcnt, sizeof(idx_t), maxc);
+                c.key = std::move(rk);
+                if (N > 1 && Er) {
+                    DBuf<u32> k2(Er); DBuf<idx_t> ix(Er), ix2(Er);
+                    prim::for_each(Er, IotaIdxFn{ix.p}, "dist.merge_cells");
+                    eng.sort_gather_cells(c, Er, c.key, k2, ix, ix2, rs.p, rl.p, "dist.merge_cells", "dist.merge_cells");
+                } else { c.sym = std::move(rs); c.len = std::move(rl); }
+            } break;
+            }
+            c.E = Er;
             // my window becomes "the BWT_{r+1}" of my piece
-            bwt.sym.alloc(0);
-            bwt.len = std::move(wlen);
-            bwt.R = Rw;
-            bwt.n = Tc[me + 1] - Tc[me];
+            eng.bwt.sym.alloc(0); eng.bwt.len = std::move(wlen); eng.bwt.R = Rw; eng.bwt.n = Tc[me + 1] - Tc[me];
             term = std::move(wsym);
         }
         // (5) pass C on my piece (the single-GPU kernels)
-        try {
-            if (n_out == 0) {
-                if (E || bwt.R) throw prim::Error(-71, "dist induction: cells or BWT_{r+1} symbols for an empty piece (level " + std::to_string(r) + ")");
-                release_cells();
-                bwt = Runs();
-                bwt.sym.alloc(0); bwt.len.alloc(0);
-            } else {
-                const u64 Pm = p1 - p0, Mm = u1 - u0;
-                if (L.pre_local) {               // my part's maps are relative to it already
+        void assemble_piece() {
+            const u32 p0 = (u32)at(sp, me, B_RUN), p1 = (u32)at(sp, me + 1, B_RUN), u0 = (u32)at(sp, me, B_META), u1 = (u32)at(sp, me + 1, B_META);
+            const u64 n_out = at(sp, me + 1, B_SYMS) - at(sp, me, B_SYMS), Pm = p1 - p0, Mm = u1 - u0;
+            C.local([&] {
+                if (n_out == 0) {
+                    if (eng.cells.E || eng.bwt.R) throw prim::Error(-71, "dist induction: cells or BWT_{r+1} symbols for an empty piece (level " + std::to_string(r) + ")");
+                    eng.cells.release();
+                    eng.set_empty_bwt();
+                } else if (L.pre_local) {        // my part's maps are relative to it already
                     if (Mm != (u64)L.Ml) throw prim::Error(-71, "dist induction: piece and key range disagree (level " + std::to_string(r) + ")");
-                    assemble(AsmIn{L.prebwt.sym.p, L.prebwt.len.p, Pm, L.u_to_p.p, L.p_to_u.p, Mm, L.sigma, n_out}, I, cell_view(kb, lb, u0), E, term, r);
+                    eng.assemble(AsmIn{L.prebwt.sym.p, L.prebwt.len.p, Pm, L.u_to_p.p, L.p_to_u.p, Mm, L.sigma, n_out}, I, u0, term, r);
                 } else {
-                DBuf<u32> u2p(Mm), p2u(Pm);
-                prim::for_each(Mm, RebaseFn{L.u_to_p.p + u0, p0, u2p.p}, "dist.piece_maps");
-                if (L.p_to_u.p) prim::for_each(Pm, RebaseFn{L.p_to_u.p + p0, u0, p2u.p}, "dist.piece_maps");
-                else prim::for_each(Pm, PieceMetaFn{L.u_to_p.p, M, p0, u0, p2u.p}, "dist.piece_maps");
-                assemble(AsmIn{L.prebwt.sym.p + p0, L.prebwt.len.p + p0, Pm, u2p.p, p2u.p, Mm, L.sigma, n_out}, I, cell_view(kb, lb, u0), E, term, r);
+                    DBuf<u32> u2p(Mm), p2u(Pm);
+                    prim::for_each(Mm, RebaseFn{L.u_to_p.p + u0, p0, u2p.p}, "dist.piece_maps");
+                    if (L.p_to_u.p) prim::for_each(Pm, RebaseFn{L.p_to_u.p + p0, u0, p2u.p}, "dist.piece_maps");
+                    else prim::for_each(Pm, PieceMetaFn{L.u_to_p.p, M, p0, u0, p2u.p}, "dist.piece_maps");
+                    eng.assemble(AsmIn{L.prebwt.sym.p + p0, L.prebwt.len.p + p0, Pm, u2p.p, p2u.p, Mm, L.sigma, n_out}, I, u0, term, r);
                 }
-            }
-        } catch (const prim::Error &e) {          // the next counter exchange (next level, or the image assembly) raises on every rank
-            C.fail(e);
-            release_cells();
-            bwt = Runs();
-            bwt.sym.alloc(0); bwt.len.alloc(0);
+            });
+            if (C.pending) { eng.cells.release(); eng.set_empty_bwt(); }      // the next counter exchange (next level, or the image assembly) raises on every rank
         }
-        bwt_level = r;
-        I.R = bwt.R; I.n = n_r;
-        release_level(L);
+    };
+    void dist_induce_level(const Comm &C) {
+        if (bwt_level <= 0) throw prim::Error(-22, "no level left to induce");
+        const int r = bwt_level - 1;
+        prim::rt().tag = r; prim::rt().phase = 'i';
+        DistInduce Z(*this, C, r);
+        Z.agree_layout();
+        C.local([&] {
+            Z.expand();
+            StageTimer st(&tm.ind_assemble, "ind_assemble");
+            Z.owners();
+            Z.count_cells();
+        });
+        {
+            StageTimer st(&tm.ind_assemble, "ind_assemble");
+            Z.gather_counts();
+            Z.exchange_window();
+            Z.exchange_cells();
+        }
+        Z.assemble_piece();
+        bwt_level = r; linfo[r].R = bwt.R; linfo[r].n = Z.n_r;
+        release_level(levels[r]);
     }
 
     // the image from the slices of BWT_0: every rank packs the records of its own slice, the packed parts are all-gathered
@@ -5536,8 +5537,6 @@ class Engine {
         const u64 first = drop[me], Rm = R - first;
         if (extra[me]) prim::for_each(1, AddLenFn{bwt.len.p + (R - 1), extra[me]}, "pack_rl_bwt");
         const u32 sb = (u32)stats.sb, fb = (u32)stats.fb, rec = sb + fb;
-        u8 hdr[16] = {0};
-        for (int i = 0; i < 8; i++) { hdr[i] = (u8)((u64)sb >> (8 * i)); hdr[8 + i] = (u8)((u64)fb >> (8 * i)); }
         std::vector<u64> cnt = C.allgather_u64({Rm * rec}), base(N + 1, 0);
         for (int g = 0; g < N; g++) base[g + 1] = base[g] + cnt[g];
         image_bytes = 16 + base[N];
@@ -5550,13 +5549,13 @@ class Engine {
             image_part_off = me == 0 ? 0 : 16 + base[me];
             image_part_bytes = h + Rm * rec;
             image.alloc(image_part_bytes);
-            if (h) prim::h2d(image.p, hdr, 16);
+            if (h) image_header(image.p, sb, fb);
             prim::for_each(Rm, PackRunsFn{bwt.sym.p + first, RunLen{bwt.len.p + first, nullptr}, sb, fb, image.p + h, 0u}, "pack_rl_bwt");
         } else {
             DBuf<u8> part(Rm * rec);
             prim::for_each(Rm, PackRunsFn{bwt.sym.p + first, RunLen{bwt.len.p + first, nullptr}, sb, fb, part.p, 0u}, "pack_rl_bwt");
             image.alloc(image_bytes);
-            prim::h2d(image.p, hdr, 16);
+            image_header(image.p, sb, fb);
             C.named("image.parts").allgather_v<u8>(part.p, Rm * rec, base, true, image.p + 16);
             image_part_off = 0; image_part_bytes = image_bytes;
         }

@@ -95,6 +95,26 @@ def test_sharded_8_byte_one_word_cells(sim, oracle_mod, tmp_path, monkeypatch):
     assert open(tmp_path / "reads.rl_bwt", "rb").read() == oracle_mod.rl_bwt(data, 1)
 
 
+def test_sharded_offset_fallback_into_4_byte_cells(sim, oracle_mod, tmp_path, monkeypatch):
+    """A run that drops more cells than the fused expansion stages takes count + scan + expand + split (the stand-in's limit is
+    lowered to 1); where the layout is the 4-byte one-word form, the words sorted as 64-bit keys are narrowed (NarrowCellFn) and
+    the cell exchange sends 4-byte cells like the fused path's: the layout decides, not the path taken."""
+    monkeypatch.setenv("GRLBWT_SIM_XS_MAXC", "1")
+    _run(3, sim, "reads", tmp_path, 29575)
+    data = open(tmp_path / "reads.input", "rb").read()
+    assert open(tmp_path / "reads.rl_bwt", "rb").read() == oracle_mod.rl_bwt(data, 1)
+
+
+def test_replicated_prebwt_with_separate_cells(sim, oracle_mod, tmp_path, monkeypatch):
+    """The replicated pre-BWT (pieces cut by symbol count: OwnerSplitFn, the piece's maps rebased) together with the widest cell
+    layout: three arrays per cell through the exchange, merged by an index sort and a gather."""
+    monkeypatch.setenv("GRLBWT_DIST_REPLICATED_PREBWT", "1")
+    monkeypatch.setenv("GRLBWT_CELL_LAYOUT", "separate")
+    _run(3, sim, "reads", tmp_path, 29576)
+    data = open(tmp_path / "reads.input", "rb").read()
+    assert open(tmp_path / "reads.rl_bwt", "rb").read() == oracle_mod.rl_bwt(data, 1)
+
+
 def test_large_exchanges_go_in_rounds(sim, oracle_mod, tmp_path, monkeypatch):
     """All-to-all blocks above the engine's limit are sent in several rounds (the limit is lowered to 4 KiB here)."""
     monkeypatch.setenv("GRLBWT_A2A_BLOCK", "4096")
