@@ -44,7 +44,7 @@ struct grlbwt_ctx {
     int device = 0;
     std::unique_ptr<grl32::Engine> e32;
     std::unique_ptr<grl64::Engine> e64;
-    std::string err;
+    mutable std::string err;           // grlbwt_last_error: the message of the last call that failed (const calls refuse too)
     std::vector<grlbwt_fm *> fms;      // the indexes still alive: released with the context
     std::vector<grlbwt_merge *> merges;      // and the merges
     std::vector<grlbwt_select *> selects;    // and the selections
@@ -137,6 +137,37 @@ void grammar_download(const E &e, int level, uint64_t *g0, uint64_t *g1, uint8_t
 }
 #define ENG(ctx, expr) ((ctx)->e32 ? (ctx)->e32->expr : (ctx)->e64->expr)
 #define HAS_ENG(ctx) ((ctx) && ((ctx)->e32 || (ctx)->e64))
+
+// GRLBWT_EINVAL before any engine work.  The refusal brings its own message: grlbwt_last_error must not go on showing the text
+// of an earlier, unrelated failure.
+int refuse(const grlbwt_ctx *ctx, const char *why = "invalid argument, or a call that is out of order for this context") {
+    if (ctx) ctx->err = why;
+    return GRLBWT_EINVAL;
+}
+// what a call that needs a text or a finished image is refused with (nullptr: it may go ahead)
+const char *need_text(const grlbwt_ctx *ctx) {
+    if (!ctx) return "no context";
+    if (!HAS_ENG(ctx)) return "no text is loaded in this context";
+    if (ENG(ctx, failed)) return "an earlier stage call failed part-way: load the text again";
+    return nullptr;
+}
+const char *need_image(const grlbwt_ctx *ctx) {
+    if (const char *why = need_text(ctx)) return why;
+    return ENG(ctx, image_bytes) == 0 ? "the build has not finished: there is no image yet" : nullptr;
+}
+// The stage-wise calls and grlbwt_build (the call-order table of include/grlbwt_hip.h) go through here.  A call the table
+// refuses throws before it touches anything, and so does the refusal of a borrowed text that has changed, which comes out
+// of the first parsing round: the engine is as it was and the next stage call works.  Any other failure may have left a level
+// half made (a round moves the level's text out of the engine while it runs): the engine is marked, and every stage and result
+// call returns GRLBWT_EINVAL until a text is loaded again.
+template <class Fn>
+int stage(grlbwt_ctx *ctx, const char *refused, Fn fn) {
+    if (const char *why = need_text(ctx)) return refuse(ctx, why);
+    if (refused) return refuse(ctx, refused);
+    const int rc = guarded(ctx, fn);
+    if (rc != GRLBWT_OK && !ENG(ctx, untouched())) ENG(ctx, mark_failed());
+    return rc;
+}
 
 static constexpr uint64_t kMergeRowLimit = 1ull << 40;      // grlbwt_merge_create: merged rows, as the build's limit on cells
 static constexpr uint64_t kIdx32Limit = 0xFFFFFF00ull;      // texts of this many cells or more take the 64-bit index build
@@ -1779,15 +1810,15 @@ int grlbwt_ctx_set_stream(grlbwt_ctx *ctx, void *hip_stream) {
 }
 
 int grlbwt_text_upload(grlbwt_ctx *ctx, const void *host_cells, uint64_t n_cells, int cell_bytes) {
-    if (!ctx || !host_cells) return GRLBWT_EINVAL;
+    if (!ctx || !host_cells) return refuse(ctx);
     return guarded(ctx, [&] { load(ctx, host_cells, n_cells, cell_bytes, true); });
 }
 int grlbwt_text_load_file(grlbwt_ctx *ctx, const char *path, int cell_bytes) {
-    if (!ctx || !path) return GRLBWT_EINVAL;
+    if (!ctx || !path) return refuse(ctx);
     return guarded(ctx, [&] { load_file(ctx, path, cell_bytes); });
 }
 int grlbwt_text_load_file_range(grlbwt_ctx *ctx, const char *path, uint64_t offset_bytes, uint64_t n_bytes, int cell_bytes) {
-    if (!ctx || !path) return GRLBWT_EINVAL;
+    if (!ctx || !path) return refuse(ctx);
     return guarded(ctx, [&] { load_file(ctx, path, cell_bytes, offset_bytes, n_bytes); });
 }
 int grlbwt_fastx_probe(const char *path, int *is_fastx, int *is_gz) {
@@ -1811,7 +1842,7 @@ int grlbwt_fastx_probe(const char *path, int *is_fastx, int *is_gz) {
 }
 int grlbwt_fastx_convert_device(grlbwt_ctx *ctx, const void *dev_in, uint64_t n_in, uint32_t fx_flags, void *dev_out, uint64_t capacity,
                                 uint64_t *n_out, uint64_t *n_strings) {
-    if (!ctx || !dev_in || !dev_out) return GRLBWT_EINVAL;
+    if (!ctx || !dev_in || !dev_out) return refuse(ctx);
     return guarded(ctx, [&] {
         grl64::Engine::FastxInfo info = grl64::Engine::fastx_to_text((const uint8_t *)dev_in, n_in, (fx_flags & GRLBWT_FASTX_REVCOMP) != 0,
                                                                      (uint8_t *)dev_out, capacity);
@@ -1820,17 +1851,17 @@ int grlbwt_fastx_convert_device(grlbwt_ctx *ctx, const void *dev_in, uint64_t n_
     });
 }
 int grlbwt_alphabet_size(const grlbwt_ctx *ctx, uint64_t *n_distinct) {
-    if (!HAS_ENG(ctx) || !n_distinct) return GRLBWT_EINVAL;
+    if (!HAS_ENG(ctx) || !n_distinct) return refuse(ctx);
     *n_distinct = ENG(ctx, alpha_n);
     return GRLBWT_OK;
 }
 int grlbwt_alphabet_download(const grlbwt_ctx *ctx, uint64_t *values_out) {
-    if (!HAS_ENG(ctx) || !values_out || ENG(ctx, alpha_n) == 0) return GRLBWT_EINVAL;
+    if (!HAS_ENG(ctx) || !values_out || ENG(ctx, alpha_n) == 0) return refuse(ctx);
     return guarded(const_cast<grlbwt_ctx *>(ctx), [&] { prim::d2h(values_out, ENG(ctx, alpha.p), ENG(ctx, alpha_n) * 8); });
 }
 int grlbwt_alphabet_compact_device(grlbwt_ctx *ctx, const void *dev_cells, uint64_t n_cells, int cell_bytes, void *dev_ranks_u32,
                                    void *dev_values_u64, uint64_t capacity_values, uint64_t *n_distinct) {
-    if (!ctx || !dev_cells || !dev_ranks_u32 || !dev_values_u64 || n_cells == 0 || !(cell_bytes == 4 || cell_bytes == 8)) return GRLBWT_EINVAL;
+    if (!ctx || !dev_cells || !dev_ranks_u32 || !dev_values_u64 || n_cells == 0 || !(cell_bytes == 4 || cell_bytes == 8)) return refuse(ctx);
     return guarded(ctx, [&] {
         const bool big = idx64_for(ctx, n_cells);
         uint64_t k = big ? grl64::Engine::alphabet_compact_device(dev_cells, n_cells, cell_bytes, (uint32_t *)dev_ranks_u32, (uint64_t *)dev_values_u64, capacity_values)
@@ -1840,44 +1871,52 @@ int grlbwt_alphabet_compact_device(grlbwt_ctx *ctx, const void *dev_cells, uint6
     });
 }
 int grlbwt_text_load_fastx(grlbwt_ctx *ctx, const char *path, uint32_t fx_flags, uint64_t *n_strings) {
-    if (!ctx || !path) return GRLBWT_EINVAL;
+    if (!ctx || !path) return refuse(ctx);
     return guarded(ctx, [&] { load_fastx(ctx, path, fx_flags, n_strings); });
 }
 int grlbwt_text_attach_device(grlbwt_ctx *ctx, const void *dev_cells, uint64_t n_cells, int cell_bytes) {
-    if (!ctx || !dev_cells || ((uintptr_t)dev_cells & 15)) return GRLBWT_EINVAL;
+    if (!ctx || !dev_cells || ((uintptr_t)dev_cells & 15)) return refuse(ctx);
     return guarded(ctx, [&] { load(ctx, dev_cells, n_cells, cell_bytes, false); });
 }
 int grlbwt_get_stats(const grlbwt_ctx *ctx, grlbwt_stats *out) {
-    if (!HAS_ENG(ctx) || !out) return GRLBWT_EINVAL;
+    if (!HAS_ENG(ctx)) return refuse(ctx, "no text is loaded in this context");
+    if (!out) return refuse(ctx, "null argument");
     if (ctx->e32) fill_stats(*ctx->e32, out); else fill_stats(*ctx->e64, out);
     return GRLBWT_OK;
 }
 
 int grlbwt_parse_round(grlbwt_ctx *ctx, grlbwt_round_info *info, int *done) {
-    if (!HAS_ENG(ctx)) return GRLBWT_EINVAL;
-    return guarded(ctx, [&] {
+    return stage(ctx, nullptr, [&] {
         bool d = ENG(ctx, parse_round());
         if (done) *done = d ? 1 : 0;
         if (info) { int r = (int)ENG(ctx, levels.size()) - 1; if (ctx->e32) fill_round(*ctx->e32, r, info); else fill_round(*ctx->e64, r, info); }
     });
 }
 int grlbwt_parse_phase(grlbwt_ctx *ctx, int *n_rounds) {
-    if (!HAS_ENG(ctx)) return GRLBWT_EINVAL;
-    return guarded(ctx, [&] { int r = ENG(ctx, parse_phase()); if (n_rounds) *n_rounds = r; });
+    return stage(ctx, nullptr, [&] { int r = ENG(ctx, parse_phase()); if (n_rounds) *n_rounds = r; });
 }
 int grlbwt_round_info_get(const grlbwt_ctx *ctx, int round, grlbwt_round_info *info) {
-    if (!HAS_ENG(ctx) || !info || round < 0 || round >= (int)ENG(ctx, levels.size())) return GRLBWT_EINVAL;
+    if (!HAS_ENG(ctx) || !info || round < 0 || round >= (int)ENG(ctx, levels.size())) return refuse(ctx);
     if (ctx->e32) fill_round(*ctx->e32, round, info); else fill_round(*ctx->e64, round, info);
     return GRLBWT_OK;
 }
 
 int grlbwt_induce_first(grlbwt_ctx *ctx) {
-    if (!HAS_ENG(ctx)) return GRLBWT_EINVAL;
-    return guarded(ctx, [&] { ENG(ctx, first_bwt()); });
+    const char *why = nullptr;
+    if (HAS_ENG(ctx)) {
+        if (!ENG(ctx, parse_done)) why = "parse phase not finished";
+        else if (ENG(ctx, done())) why = "the image is built already: grlbwt_induce_first runs once per text";
+        else if (ENG(ctx, bwt_level) >= 0) why = "the induction has begun already: grlbwt_induce_first runs once per text";
+    }
+    return stage(ctx, why, [&] { ENG(ctx, first_bwt()); });
 }
 int grlbwt_induce_level(grlbwt_ctx *ctx, int *level, grlbwt_level_info *info) {
-    if (!HAS_ENG(ctx)) return GRLBWT_EINVAL;
-    return guarded(ctx, [&] {
+    const char *why = nullptr;
+    if (HAS_ENG(ctx)) {
+        if (ENG(ctx, done())) why = "the image is built already: no level left to induce";
+        else if (ENG(ctx, bwt_level) <= 0) why = "no level to induce: grlbwt_induce_first comes first";
+    }
+    return stage(ctx, why, [&] {
         ENG(ctx, induce_level());
         int l = ENG(ctx, bwt_level);
         if (level) *level = l;
@@ -1886,75 +1925,82 @@ int grlbwt_induce_level(grlbwt_ctx *ctx, int *level, grlbwt_level_info *info) {
     });
 }
 int grlbwt_induce_phase(grlbwt_ctx *ctx) {
-    if (!HAS_ENG(ctx)) return GRLBWT_EINVAL;
-    return guarded(ctx, [&] { ENG(ctx, induce_phase()); ENG(ctx, finish()); });
+    const char *why = HAS_ENG(ctx) && !ENG(ctx, parse_done) ? "parse phase not finished" : nullptr;
+    return stage(ctx, why, [&] {
+        if (ENG(ctx, done())) return;          // DONE: the image stands
+        ENG(ctx, induce_phase());              // PARSED, or INDUCING: the levels that are left
+        ENG(ctx, finish());
+    });
 }
 int grlbwt_level_info_get(const grlbwt_ctx *ctx, int level, grlbwt_level_info *info) {
-    if (!HAS_ENG(ctx) || !info || level < 0 || level >= (int)ENG(ctx, linfo.size())) return GRLBWT_EINVAL;
+    if (!HAS_ENG(ctx) || !info || level < 0 || level >= (int)ENG(ctx, linfo.size())) return refuse(ctx);
     if (ctx->e32) fill_level(*ctx->e32, level, info); else fill_level(*ctx->e64, level, info);
     return GRLBWT_OK;
 }
 int grlbwt_build(grlbwt_ctx *ctx) {
-    if (!HAS_ENG(ctx)) return GRLBWT_EINVAL;
-    return guarded(ctx, [&] { ENG(ctx, run_all()); });
+    return stage(ctx, nullptr, [&] { ENG(ctx, run_all()); });
 }
 
 int grlbwt_result_size(const grlbwt_ctx *ctx, uint64_t *image_bytes, uint64_t *n_runs) {
-    if (!HAS_ENG(ctx) || ENG(ctx, image_bytes) == 0) return GRLBWT_EINVAL;
+    if (const char *why = need_image(ctx)) return refuse(ctx, why);
     if (image_bytes) *image_bytes = ENG(ctx, image_bytes);
     if (n_runs) *n_runs = ENG(ctx, image_runs);
     return GRLBWT_OK;
 }
 int grlbwt_result_device_ptr(const grlbwt_ctx *ctx, const void **dev_ptr) {
-    if (!HAS_ENG(ctx) || !dev_ptr || ENG(ctx, image_bytes) == 0) return GRLBWT_EINVAL;
+    if (const char *why = need_image(ctx)) return refuse(ctx, why);
+    if (!dev_ptr) return refuse(ctx, "null argument");
     *dev_ptr = ENG(ctx, image.p);
     return GRLBWT_OK;
 }
 int grlbwt_result_download(const grlbwt_ctx *ctx, void *host_out, uint64_t capacity) {
-    if (!HAS_ENG(ctx) || !host_out || ENG(ctx, image_bytes) == 0 || capacity < ENG(ctx, image_part_bytes)) return GRLBWT_EINVAL;
+    if (const char *why = need_image(ctx)) return refuse(ctx, why);
+    if (!host_out || capacity < ENG(ctx, image_part_bytes)) return refuse(ctx, "no output buffer, or one smaller than the image");
     return guarded(const_cast<grlbwt_ctx *>(ctx), [&] { if (ENG(ctx, image_part_bytes)) prim::d2h(host_out, ENG(ctx, image.p), ENG(ctx, image_part_bytes)); });
 }
 int grlbwt_result_write_file(const grlbwt_ctx *ctx, const char *path) {
-    if (!HAS_ENG(ctx) || !path || ENG(ctx, image_bytes) == 0) return GRLBWT_EINVAL;
-    if (ENG(ctx, image_part_bytes) != ENG(ctx, image_bytes)) return GRLBWT_EINVAL;      // (this context holds a part: grlbwt_result_write_part)
+    if (const char *why = need_image(ctx)) return refuse(ctx, why);
+    if (!path) return refuse(ctx, "null argument");
+    if (ENG(ctx, image_part_bytes) != ENG(ctx, image_bytes)) return refuse(ctx, "this context holds a part of the image: grlbwt_result_write_part");
     return guarded(const_cast<grlbwt_ctx *>(ctx), [&] { write_image(ENG(ctx, image.p), ENG(ctx, image_bytes), path); });
 }
 int grlbwt_result_part(const grlbwt_ctx *ctx, uint64_t *offset, uint64_t *bytes) {
-    if (!HAS_ENG(ctx) || ENG(ctx, image_bytes) == 0) return GRLBWT_EINVAL;
+    if (const char *why = need_image(ctx)) return refuse(ctx, why);
     if (offset) *offset = ENG(ctx, image_part_off);
     if (bytes) *bytes = ENG(ctx, image_part_bytes);
     return GRLBWT_OK;
 }
 int grlbwt_result_write_part(const grlbwt_ctx *ctx, const char *path) {
-    if (!HAS_ENG(ctx) || !path || ENG(ctx, image_bytes) == 0) return GRLBWT_EINVAL;
+    if (const char *why = need_image(ctx)) return refuse(ctx, why);
+    if (!path) return refuse(ctx, "null argument");
     return guarded(const_cast<grlbwt_ctx *>(ctx), [&] { write_image(ENG(ctx, image.p), ENG(ctx, image_part_bytes), path, true, ENG(ctx, image_part_off), ENG(ctx, image_bytes)); });
 }
 
 int grlbwt_level_text_size(const grlbwt_ctx *ctx, int level, uint64_t *n_cells) {
-    if (!HAS_ENG(ctx) || !n_cells || level < 1 || level > (int)ENG(ctx, kept_texts.size())) return GRLBWT_EINVAL;
+    if (!HAS_ENG(ctx) || !n_cells || level < 1 || level > (int)ENG(ctx, kept_texts.size())) return refuse(ctx);
     *n_cells = ENG(ctx, kept_texts[level - 1].n);
     return GRLBWT_OK;
 }
 int grlbwt_level_text_download(const grlbwt_ctx *ctx, int level, uint64_t *cells_out) {
-    if (!HAS_ENG(ctx) || !cells_out || level < 1 || level > (int)ENG(ctx, kept_texts.size())) return GRLBWT_EINVAL;
+    if (!HAS_ENG(ctx) || !cells_out || level < 1 || level > (int)ENG(ctx, kept_texts.size())) return refuse(ctx);
     return guarded(const_cast<grlbwt_ctx *>(ctx), [&] {
         if (ctx->e32) text_download(*ctx->e32, level, cells_out); else text_download(*ctx->e64, level, cells_out);
     });
 }
 int grlbwt_level_bwt_size(const grlbwt_ctx *ctx, int level, uint64_t *n_runs) {
-    if (!HAS_ENG(ctx) || !n_runs || level < 0 || level >= (int)ENG(ctx, kept_bwts.size())) return GRLBWT_EINVAL;
+    if (!HAS_ENG(ctx) || !n_runs || level < 0 || level >= (int)ENG(ctx, kept_bwts.size())) return refuse(ctx);
     *n_runs = ENG(ctx, kept_bwts[level].R);
     return GRLBWT_OK;
 }
 int grlbwt_level_bwt_download(const grlbwt_ctx *ctx, int level, uint64_t *sym_out, uint64_t *len_out) {
-    if (!HAS_ENG(ctx) || !sym_out || !len_out || level < 0 || level >= (int)ENG(ctx, kept_bwts.size())) return GRLBWT_EINVAL;
+    if (!HAS_ENG(ctx) || !sym_out || !len_out || level < 0 || level >= (int)ENG(ctx, kept_bwts.size())) return refuse(ctx);
     return guarded(const_cast<grlbwt_ctx *>(ctx), [&] {
         if (ctx->e32) bwt_download(*ctx->e32, level, sym_out, len_out); else bwt_download(*ctx->e64, level, sym_out, len_out);
     });
 }
 
 int grlbwt_level_grammar_size(const grlbwt_ctx *ctx, int level, uint64_t *n_metasyms, uint64_t *prebwt_runs) {
-    if (!HAS_ENG(ctx) || level < 0 || level >= (int)ENG(ctx, levels.size())) return GRLBWT_EINVAL;
+    if (!HAS_ENG(ctx) || level < 0 || level >= (int)ENG(ctx, levels.size())) return refuse(ctx);
     if (ENG(ctx, levels[level].g0.p) == nullptr) return GRLBWT_EINVAL;           // already consumed by the induction of this level
     if (n_metasyms) *n_metasyms = ENG(ctx, levels[level].M);
     if (prebwt_runs) *prebwt_runs = ENG(ctx, levels[level].prebwt.R);
@@ -1962,7 +2008,7 @@ int grlbwt_level_grammar_size(const grlbwt_ctx *ctx, int level, uint64_t *n_meta
 }
 int grlbwt_level_grammar_download(const grlbwt_ctx *ctx, int level, uint64_t *g0, uint64_t *g1, uint8_t *has_hocc,
                                   uint64_t *prebwt_sym, uint64_t *prebwt_len) {
-    if (grlbwt_level_grammar_size(ctx, level, nullptr, nullptr) != GRLBWT_OK) return GRLBWT_EINVAL;
+    if (grlbwt_level_grammar_size(ctx, level, nullptr, nullptr) != GRLBWT_OK) return refuse(ctx);
     return guarded(const_cast<grlbwt_ctx *>(ctx), [&] {
         if (ctx->e32) grammar_download(*ctx->e32, level, g0, g1, has_hocc, prebwt_sym, prebwt_len);
         else grammar_download(*ctx->e64, level, g0, g1, has_hocc, prebwt_sym, prebwt_len);
@@ -1970,7 +2016,7 @@ int grlbwt_level_grammar_download(const grlbwt_ctx *ctx, int level, uint64_t *g0
 }
 
 int grlbwt_get_counters(const grlbwt_ctx *ctx, grlbwt_counters *out) {
-    if (!HAS_ENG(ctx) || !out) return GRLBWT_EINVAL;
+    if (!HAS_ENG(ctx) || !out) return refuse(ctx);
     try { prim::sync(); } catch (...) { return GRLBWT_EDEVICE; }   // folds the stage clocks still in flight
     if (ctx->e32) fill_counters(*ctx->e32, out); else fill_counters(*ctx->e64, out);
     return GRLBWT_OK;
@@ -1978,7 +2024,7 @@ int grlbwt_get_counters(const grlbwt_ctx *ctx, grlbwt_counters *out) {
 
 int grlbwt_invert_image_tails(grlbwt_ctx *ctx, const void *dev_image, uint64_t image_bytes, int cell_bytes, uint64_t tail_cells,
                               void *dev_out, uint64_t capacity_cells, uint64_t *n_strings_out, uint64_t *n_cells_out) {
-    if (!ctx || !dev_image || !dev_out || tail_cells == 0) return GRLBWT_EINVAL;
+    if (!ctx || !dev_image || !dev_out || tail_cells == 0) return refuse(ctx);
     return guarded(ctx, [&] {
         const uint64_t total = grl64::Image::image_total_symbols(dev_image, image_bytes);
         const bool big = idx64_for(ctx, total);
@@ -1992,7 +2038,7 @@ int grlbwt_invert_image_tails(grlbwt_ctx *ctx, const void *dev_image, uint64_t i
 
 int grlbwt_invert_image(grlbwt_ctx *ctx, const void *dev_image, uint64_t image_bytes, int cell_bytes,
                         void *dev_text_out, uint64_t capacity_cells, uint64_t *n_cells_out) {
-    if (!ctx || !dev_image || !dev_text_out) return GRLBWT_EINVAL;
+    if (!ctx || !dev_image || !dev_text_out) return refuse(ctx);
     return guarded(ctx, [&] {
         // the index width follows the number of symbols the image DESCRIBES (summed in 64 bits), not the buffer sizes:
         // a small image can describe >= 2^32 symbols, and a 32-bit scan of its run lengths would wrap
@@ -2007,7 +2053,7 @@ int grlbwt_invert_image(grlbwt_ctx *ctx, const void *dev_image, uint64_t image_b
 
 
 int grlbwt_fm_create(grlbwt_ctx *ctx, const void *dev_image, uint64_t image_bytes, uint32_t fm_flags, grlbwt_fm **out) {
-    if (!ctx || !dev_image || !out) return GRLBWT_EINVAL;
+    if (!ctx || !dev_image || !out) return refuse(ctx);
     *out = nullptr;
     const uint32_t sample_bits = (fm_flags >> 8) & 0xFFu;
     if ((fm_flags & ~(GRLBWT_FM_LOCATE | GRLBWT_FM_CHECKPOINTS | GRLBWT_FM_EXTRACT | 0xFF00u)) || sample_bits > 20 ||
@@ -2062,7 +2108,7 @@ int grlbwt_fm_walk_info_get(const grlbwt_fm *fm, grlbwt_walk_info *out) {
 }
 int grlbwt_invert_image_checkpointed(grlbwt_ctx *ctx, const void *dev_image, uint64_t image_bytes, int cell_bytes, int sample_bits,
                                      void *dev_text_out, uint64_t capacity_cells, uint64_t *n_cells_out, grlbwt_walk_info *info) {
-    if (!ctx || !dev_image || !dev_text_out) return GRLBWT_EINVAL;
+    if (!ctx || !dev_image || !dev_text_out) return refuse(ctx);
     return guarded(ctx, [&] {
         if (sample_bits < 0 || sample_bits > 20) throw prim::Error(GRLBWT_EINVAL, "checkpointed walk: sample_bits is 0 (the default) or 1 to 20");
         const uint64_t total = grl64::Image::image_total_symbols(dev_image, image_bytes);
@@ -2085,7 +2131,7 @@ int grlbwt_invert_image_checkpointed(grlbwt_ctx *ctx, const void *dev_image, uin
 }
 int grlbwt_fm_count(grlbwt_ctx *ctx, const grlbwt_fm *fm, const void *dev_cells, int cell_bytes, const uint64_t *dev_offsets,
                     uint64_t n_patterns, uint64_t *dev_lo, uint64_t *dev_hi) {
-    if (!ctx || !fm || !(fm->f32 || fm->f64)) return GRLBWT_EINVAL;
+    if (!ctx || !fm || !(fm->f32 || fm->f64)) return refuse(ctx);
     if (n_patterns && (!dev_offsets || !dev_lo || !dev_hi)) return GRLBWT_EINVAL;
     return guarded(ctx, [&] {
         if (fm->f32) grl32::Image::fm_count(*fm->f32, dev_cells, cell_bytes, dev_offsets, n_patterns, dev_lo, dev_hi);
@@ -2094,7 +2140,7 @@ int grlbwt_fm_count(grlbwt_ctx *ctx, const grlbwt_fm *fm, const void *dev_cells,
 }
 int grlbwt_fm_match(grlbwt_ctx *ctx, const grlbwt_fm *fm, const void *dev_cells, int cell_bytes, const uint64_t *dev_offsets,
                     uint64_t n_patterns, uint64_t max_len, uint64_t *dev_len, uint64_t *dev_lo, uint64_t *dev_hi) {
-    if (!ctx || !fm || !(fm->f32 || fm->f64)) return GRLBWT_EINVAL;
+    if (!ctx || !fm || !(fm->f32 || fm->f64)) return refuse(ctx);
     if (n_patterns && !dev_offsets) return GRLBWT_EINVAL;
     return guarded(ctx, [&] {
         if (fm->f32) grl32::Image::fm_match(*fm->f32, dev_cells, cell_bytes, dev_offsets, n_patterns, max_len, dev_len, dev_lo, dev_hi);
@@ -2105,7 +2151,7 @@ int grlbwt_fm_mems(grlbwt_ctx *ctx, const grlbwt_fm *fm, const void *dev_cells, 
                    uint64_t n_patterns, uint64_t min_len, uint64_t max_len, uint64_t *dev_pattern, uint64_t *dev_begin, uint64_t *dev_mlen,
                    uint64_t *dev_lo, uint64_t *dev_hi, uint64_t capacity, uint64_t *n_mems_out) {
     if (n_mems_out) *n_mems_out = 0;
-    if (!ctx || !fm || !(fm->f32 || fm->f64)) return GRLBWT_EINVAL;
+    if (!ctx || !fm || !(fm->f32 || fm->f64)) return refuse(ctx);
     if (n_patterns && !dev_offsets) return GRLBWT_EINVAL;
     uint64_t n = 0;
     const int rc = guarded(ctx, [&] {
@@ -2131,7 +2177,7 @@ int grlbwt_fm_approx(grlbwt_ctx *ctx, const grlbwt_fm *fm, const void *dev_cells
                      uint64_t n_patterns, uint32_t max_mismatches, uint64_t max_hits, uint64_t *dev_hit_offsets, uint64_t *dev_mism,
                      uint64_t *dev_lo, uint64_t *dev_hi, uint64_t *dev_sub_pos, uint64_t *dev_sub_val, uint64_t capacity, uint64_t *n_hits_out) {
     if (n_hits_out) *n_hits_out = 0;
-    if (!ctx || !fm || !(fm->f32 || fm->f64)) return GRLBWT_EINVAL;
+    if (!ctx || !fm || !(fm->f32 || fm->f64)) return refuse(ctx);
     if (n_patterns && !dev_offsets) return GRLBWT_EINVAL;
     uint64_t n = 0;
     const int rc = guarded(ctx, [&] {
@@ -2159,7 +2205,7 @@ int grlbwt_fm_approx_info_get(const grlbwt_fm *fm, grlbwt_fm_approx_info *out) {
 int grlbwt_fm_lcp(grlbwt_ctx *ctx, const grlbwt_fm *fm, uint64_t max_lcp, int lcp_bytes, void *dev_lcp, uint64_t *host_rows_at,
                   uint64_t *host_suffixes_of, uint64_t hist_capacity, uint64_t *n_levels_out) {
     if (n_levels_out) *n_levels_out = 0;
-    if (!ctx || !fm || !(fm->f32 || fm->f64)) return GRLBWT_EINVAL;
+    if (!ctx || !fm || !(fm->f32 || fm->f64)) return refuse(ctx);
     uint64_t n = 0;
     const int rc = guarded(ctx, [&] {
         if (fm->f32) grl32::Image::fm_lcp(*fm->f32, max_lcp, lcp_bytes, dev_lcp, host_rows_at, host_suffixes_of, hist_capacity, n);
@@ -2181,7 +2227,7 @@ int grlbwt_fm_lcp_info_get(const grlbwt_fm *fm, grlbwt_fm_lcp_info *out) {
 }
 int grlbwt_fm_locate(grlbwt_ctx *ctx, const grlbwt_fm *fm, const uint64_t *dev_rows, uint64_t n_rows, uint64_t max_steps,
                      uint64_t *dev_string, uint64_t *dev_offset) {
-    if (!ctx || !fm || !(fm->f32 || fm->f64)) return GRLBWT_EINVAL;
+    if (!ctx || !fm || !(fm->f32 || fm->f64)) return refuse(ctx);
     if (n_rows && (!dev_rows || !dev_string || !dev_offset)) return GRLBWT_EINVAL;
     return guarded(ctx, [&] {
         if (fm->f32) grl32::Image::fm_locate(*fm->f32, dev_rows, n_rows, max_steps, dev_string, dev_offset);
@@ -2189,7 +2235,7 @@ int grlbwt_fm_locate(grlbwt_ctx *ctx, const grlbwt_fm *fm, const uint64_t *dev_r
     });
 }
 int grlbwt_fm_string_lengths(grlbwt_ctx *ctx, const grlbwt_fm *fm, uint64_t *dev_len) {
-    if (!ctx || !fm || !dev_len || !(fm->f32 || fm->f64)) return GRLBWT_EINVAL;
+    if (!ctx || !fm || !dev_len || !(fm->f32 || fm->f64)) return refuse(ctx);
     return guarded(ctx, [&] {
         if (fm->f32) grl32::Image::fm_string_lengths(*fm->f32, dev_len);
         else grl64::Image::fm_string_lengths(*fm->f64, dev_len);
@@ -2197,7 +2243,7 @@ int grlbwt_fm_string_lengths(grlbwt_ctx *ctx, const grlbwt_fm *fm, uint64_t *dev
 }
 int grlbwt_fm_extract(grlbwt_ctx *ctx, const grlbwt_fm *fm, const uint64_t *dev_string, const uint64_t *dev_begin, const uint64_t *dev_end,
                       uint64_t n_ranges, int cell_bytes, void *dev_out, uint64_t capacity_cells, uint64_t *dev_out_offsets, uint64_t *n_cells_out) {
-    if (!ctx || !fm || !dev_out_offsets || !(fm->f32 || fm->f64)) return GRLBWT_EINVAL;
+    if (!ctx || !fm || !dev_out_offsets || !(fm->f32 || fm->f64)) return refuse(ctx);
     if (n_ranges && (!dev_string || !dev_begin || !dev_end || (!dev_out && capacity_cells))) return GRLBWT_EINVAL;
     return guarded(ctx, [&] {
         const uint64_t n = fm->f32 ? grl32::Image::fm_extract(*fm->f32, dev_string, dev_begin, dev_end, n_ranges, cell_bytes, dev_out, capacity_cells, dev_out_offsets)
@@ -2220,7 +2266,7 @@ int grlbwt_fm_extract_info_get(const grlbwt_fm *fm, grlbwt_fm_extract_info *out)
 int grlbwt_merge_create(grlbwt_ctx *ctx, const void *dev_image_a, uint64_t bytes_a, const void *dev_image_b, uint64_t bytes_b, int cell_bytes,
                         uint64_t max_rounds, grlbwt_merge **out) {
     if (out) *out = nullptr;
-    if (!ctx || !dev_image_a || !dev_image_b || !out) return GRLBWT_EINVAL;
+    if (!ctx || !dev_image_a || !dev_image_b || !out) return refuse(ctx);
     return guarded(ctx, [&] {
         const uint64_t ta = grl64::Image::image_total_symbols(dev_image_a, bytes_a), tb = grl64::Image::image_total_symbols(dev_image_b, bytes_b);
         if (ta >= kMergeRowLimit || tb >= kMergeRowLimit || ta + tb >= kMergeRowLimit) throw prim::Error(GRLBWT_ERANGE, "merge: 2^40 merged rows or more");
@@ -2257,14 +2303,14 @@ int grlbwt_merge_info_get(const grlbwt_merge *mg, grlbwt_merge_info *out) {
     return GRLBWT_OK;
 }
 int grlbwt_merge_emit(grlbwt_ctx *ctx, const grlbwt_merge *mg, void *dev_out, uint64_t capacity_bytes) {
-    if (!ctx || !mg || !dev_out || !(mg->m32 || mg->m64)) return GRLBWT_EINVAL;
+    if (!ctx || !mg || !dev_out || !(mg->m32 || mg->m64)) return refuse(ctx);
     return guarded(ctx, [&] {
         if (mg->m32) grl32::Image::merge_emit(*mg->m32, (uint8_t *)dev_out, capacity_bytes);
         else grl64::Image::merge_emit(*mg->m64, (uint8_t *)dev_out, capacity_bytes);
     });
 }
 int grlbwt_merge_interleave(grlbwt_ctx *ctx, const grlbwt_merge *mg, uint64_t *dev_bits) {
-    if (!ctx || !mg || !dev_bits || !(mg->m32 || mg->m64)) return GRLBWT_EINVAL;
+    if (!ctx || !mg || !dev_bits || !(mg->m32 || mg->m64)) return refuse(ctx);
     return guarded(ctx, [&] {
         if (mg->m32) grl32::Image::merge_interleave(*mg->m32, dev_bits);
         else grl64::Image::merge_interleave(*mg->m64, dev_bits);
@@ -2272,7 +2318,7 @@ int grlbwt_merge_interleave(grlbwt_ctx *ctx, const grlbwt_merge *mg, uint64_t *d
 }
 int grlbwt_merge_files(grlbwt_ctx *ctx, const char *path_a, const char *path_b, int cell_bytes, uint64_t max_rounds, const char *path_out,
                        grlbwt_merge_info *info) {
-    if (!ctx || !path_a || !path_b || !path_out) return GRLBWT_EINVAL;
+    if (!ctx || !path_a || !path_b || !path_out) return refuse(ctx);
     grlbwt_merge *mg = nullptr;
     int rc = guarded(ctx, [&] {
         RawText a, b;
@@ -2300,7 +2346,7 @@ int grlbwt_merge_files(grlbwt_ctx *ctx, const char *path_a, const char *path_b, 
 int grlbwt_select_create(grlbwt_ctx *ctx, const void *dev_image, uint64_t image_bytes, int cell_bytes, const uint64_t *dev_ids, uint64_t n_ids,
                          uint32_t select_flags, grlbwt_select **out) {
     if (out) *out = nullptr;
-    if (!ctx || !dev_image || !out || (n_ids && !dev_ids)) return GRLBWT_EINVAL;
+    if (!ctx || !dev_image || !out || (n_ids && !dev_ids)) return refuse(ctx);
     const uint32_t sample_bits = (select_flags >> 8) & 0xFFu;
     const bool keep = select_flags & GRLBWT_SELECT_KEEP, cps = select_flags & GRLBWT_SELECT_CHECKPOINTS;
     if ((select_flags & ~(GRLBWT_SELECT_KEEP | GRLBWT_SELECT_CHECKPOINTS | 0xFF00u)) || sample_bits > 20 || (!cps && sample_bits)) {
@@ -2348,14 +2394,14 @@ int grlbwt_select_info_get(const grlbwt_select *sel, grlbwt_select_info *out) {
     return GRLBWT_OK;
 }
 int grlbwt_select_emit(grlbwt_ctx *ctx, const grlbwt_select *sel, void *dev_out, uint64_t capacity_bytes) {
-    if (!ctx || !sel || !dev_out || !(sel->s32 || sel->s64)) return GRLBWT_EINVAL;
+    if (!ctx || !sel || !dev_out || !(sel->s32 || sel->s64)) return refuse(ctx);
     return guarded(ctx, [&] {
         if (sel->s32) grl32::Image::select_emit(*sel->s32, (uint8_t *)dev_out, capacity_bytes);
         else grl64::Image::select_emit(*sel->s64, (uint8_t *)dev_out, capacity_bytes);
     });
 }
 int grlbwt_select_rows(grlbwt_ctx *ctx, const grlbwt_select *sel, uint64_t *dev_bits) {
-    if (!ctx || !sel || !dev_bits || !(sel->s32 || sel->s64)) return GRLBWT_EINVAL;
+    if (!ctx || !sel || !dev_bits || !(sel->s32 || sel->s64)) return refuse(ctx);
     return guarded(ctx, [&] {
         if (sel->s32) grl32::Image::select_rows(*sel->s32, dev_bits);
         else grl64::Image::select_rows(*sel->s64, dev_bits);
@@ -2363,7 +2409,7 @@ int grlbwt_select_rows(grlbwt_ctx *ctx, const grlbwt_select *sel, uint64_t *dev_
 }
 int grlbwt_select_files(grlbwt_ctx *ctx, const char *path_in, const uint64_t *host_ids, uint64_t n_ids, int cell_bytes, uint32_t select_flags,
                         const char *path_out, grlbwt_select_info *info) {
-    if (!ctx || !path_in || !path_out || (n_ids && !host_ids)) return GRLBWT_EINVAL;
+    if (!ctx || !path_in || !path_out || (n_ids && !host_ids)) return refuse(ctx);
     grlbwt_select *sel = nullptr;
     int rc = guarded(ctx, [&] {
         RawText a;
@@ -2391,7 +2437,7 @@ int grlbwt_select_files(grlbwt_ctx *ctx, const char *path_in, const uint64_t *ho
 
 int grlbwt_image_plain(grlbwt_ctx *ctx, const void *dev_image, uint64_t image_bytes, void *dev_out_u8,
                        uint64_t capacity, int null_char, uint64_t *n_out) {
-    if (!ctx || !dev_image || !dev_out_u8 || null_char > 255) return GRLBWT_EINVAL;
+    if (!ctx || !dev_image || !dev_out_u8 || null_char > 255) return refuse(ctx);
     return guarded(ctx, [&] {
         const uint64_t total = grl64::Image::image_total_symbols(dev_image, image_bytes);
         if (total > capacity) throw prim::Error(GRLBWT_EINVAL, "grl2plain: output buffer too small");
@@ -2403,14 +2449,14 @@ int grlbwt_image_plain(grlbwt_ctx *ctx, const void *dev_image, uint64_t image_by
 }
 int grlbwt_image_rle(grlbwt_ctx *ctx, const void *dev_image, uint64_t image_bytes, void *dev_syms_u8, void *dev_lens_u32,
                      uint64_t capacity_runs, uint64_t *n_runs_out) {
-    if (!ctx || !dev_image || !dev_syms_u8 || !dev_lens_u32) return GRLBWT_EINVAL;
+    if (!ctx || !dev_image || !dev_syms_u8 || !dev_lens_u32) return refuse(ctx);
     return guarded(ctx, [&] {
         uint64_t r = grl64::Image::image_rle(dev_image, image_bytes, (uint8_t *)dev_syms_u8, (uint32_t *)dev_lens_u32, capacity_runs);
         if (n_runs_out) *n_runs_out = r;
     });
 }
 int grlbwt_image_stats_get(grlbwt_ctx *ctx, const void *dev_image, uint64_t image_bytes, grlbwt_image_stats *out) {
-    if (!ctx || !dev_image || !out) return GRLBWT_EINVAL;
+    if (!ctx || !dev_image || !out) return refuse(ctx);
     return guarded(ctx, [&] {
         grl64::Image::ImageStats st;
         grl64::Image::image_stats(dev_image, image_bytes, st);
@@ -2424,7 +2470,7 @@ int grlbwt_image_stats_get(grlbwt_ctx *ctx, const void *dev_image, uint64_t imag
 
 int grlbwt_image_split_runs(grlbwt_ctx *ctx, const void *dev_image, uint64_t image_bytes, int bits, uint64_t block_size,
                             void *dev_out, uint64_t capacity_bytes, grlbwt_split_info *info) {
-    if (!ctx || !dev_image || !dev_out) return GRLBWT_EINVAL;
+    if (!ctx || !dev_image || !dev_out) return refuse(ctx);
     return guarded(ctx, [&] {
         const uint64_t total = grl64::Image::image_total_symbols(dev_image, image_bytes);
         bool big = idx64_for(ctx, total);
@@ -2452,7 +2498,7 @@ int grlbwt_memory_usage(const grlbwt_ctx *ctx, uint64_t *peak_live_bytes, uint64
 }
 
 int grlbwt_dist_build(grlbwt_ctx *ctx, const grlbwt_comm *comm) {
-    if (!HAS_ENG(ctx) || !comm || !comm->allgather || !comm->alltoallv || comm->size < 1 || comm->rank < 0 || comm->rank >= comm->size) return GRLBWT_EINVAL;
+    if (!HAS_ENG(ctx) || !comm || !comm->allgather || !comm->alltoallv || comm->size < 1 || comm->rank < 0 || comm->rank >= comm->size) return refuse(ctx);
     return guarded(ctx, [&] {
         if (ctx->e32) {
             grl32::Engine::Comm C;
@@ -2536,7 +2582,7 @@ int grlbwt_rccl_unique_id(void *id128) {
     return GRLBWT_OK;
 }
 int grlbwt_rccl_comm_create(grlbwt_ctx *ctx, const void *id128, int rank, int size, grlbwt_comm *comm) {
-    if (!ctx || !id128 || !comm || size < 1 || rank < 0 || rank >= size) return GRLBWT_EINVAL;
+    if (!ctx || !id128 || !comm || size < 1 || rank < 0 || rank >= size) return refuse(ctx);
     return guarded(ctx, [&] {
         if (!rccl().load()) throw prim::Error(GRLBWT_EDEVICE, rccl().err);
         ncclUniqueId id;
@@ -2574,7 +2620,7 @@ int grlbwt_profile_enable(grlbwt_ctx *ctx, int on) {
     });
 }
 int grlbwt_profile_dump(grlbwt_ctx *ctx, char *buf, uint64_t capacity) {
-    if (!ctx || !buf || capacity == 0) return GRLBWT_EINVAL;
+    if (!ctx || !buf || capacity == 0) return refuse(ctx);
     return guarded(ctx, [&] {
         prim::sync();
         std::string s;

@@ -3043,6 +3043,13 @@ class Engine {
     bool sym_present_known = false;
     u64 image_bytes = 0;              // of the WHOLE image
     u64 image_runs = 0;
+    // The states of the stage-wise calls (the table of include/grlbwt_hip.h): LOADED and PARTLY PARSED while !parse_done, PARSED
+    // until first_bwt(), INDUCING while bwt_level > 0, DONE once finish() has written the image.
+    bool image_done = false;          // DONE: nothing rewrites the image until a text is loaded again
+    bool failed = false;              // a stage call failed after it had begun to change the engine (grlbwt_ctx: stage())
+    bool done() const { return image_done; }
+    bool untouched() const { return levels.empty() && !parse_done && bwt_level < 0 && !image_done; }      // LOADED
+    void mark_failed() { failed = true; image_done = false; image_bytes = 0; image_fused = false; }
     // what `image` holds: all of it, or (collection-level mode with Comm::keep_parts) the bytes [image_part_off, + image_part_bytes)
     u64 image_part_off = 0, image_part_bytes = 0;
     bool keep_texts = false;          // debug/parity: keep every level's text
@@ -3095,7 +3102,7 @@ class Engine {
         // scratch for the whole build in one slab: ~22x the input for the 32-bit index build, ~30x for the 64-bit one
         prim::pool_reserve((size_t)(n * (u64)w) * (sizeof(idx_t) == 4 ? 22 : 30));
         levels.clear(); linfo.clear(); kept_texts.clear(); kept_bwts.clear();
-        parse_done = false; bwt_level = -1; image_bytes = 0;
+        parse_done = false; bwt_level = -1; image_bytes = 0; image_done = false; failed = false; image_fused = false;
         rank0.release(); alpha.release(); alpha_n = 0;
         tm = Timers();
         switch (w) {
@@ -4489,6 +4496,8 @@ class Engine {
     // ---- a12 ---------------------------------------------------------------
     void first_bwt() {
         if (!parse_done) throw prim::Error(-22, "parse phase not finished");
+        // (the deepest level's text is read once and released: a second call would read a buffer that is gone)
+        if (bwt_level >= 0) throw prim::Error(-22, "the induction has begun already: the deepest level's BWT is taken once per text");
         prim::rt().tag = (int)levels.size();
         prim::rt().phase = 'i';
         StageTimer st(&tm.ind_assemble, "ind_assemble");
@@ -4935,8 +4944,9 @@ class Engine {
         Z.tail();
     }
 
-    void induce_phase() {                                        // exact_ind_phase.cpp:674-697
-        first_bwt();
+    void induce_phase() {                                        // exact_ind_phase.cpp:674-697; takes up where stage-wise calls left off
+        if (!parse_done) throw prim::Error(-22, "parse phase not finished");
+        if (bwt_level < 0) first_bwt();
         while (bwt_level > 0) induce_level();
     }
 
@@ -4948,6 +4958,7 @@ class Engine {
         prim::h2d(dst, hdr, 16);
     }
     void finish() {
+        if (image_done) return;                   // DONE: the image stands
         if (bwt_level != 0) throw prim::Error(-22, "induction not finished");
         prim::rt().tag = -1; prim::rt().phase = 0;
         StageTimer st(&tm.finish, "finish");
@@ -4968,6 +4979,7 @@ class Engine {
         // "results are complete when a call returns" (include/grlbwt_hip.h): the image pointer may be handed to another
         // stream (torch, a copy engine) right after the build, so the engine's stream is drained here
         prim::sync();
+        image_done = true;
     }
     // =====================================================================
     // collection-level multi-GPU: this engine holds one record shard
@@ -5563,6 +5575,7 @@ class Engine {
         stats.n_syms = g_n_syms;
         linfo[0].R = image_runs;
         prim::sync();
+        image_done = true;
     }
 
     void dist_induce(const Comm &C) {
@@ -5686,7 +5699,8 @@ class Engine {
         return info;
     }
 
-    void run_all() {
+    void run_all() {                              // from any state to DONE
+        if (image_done) return;
         parse_phase_or_base();
         if (bwt_level < 0) first_bwt();
         while (bwt_level > 0) induce_level();

@@ -168,6 +168,32 @@ int grlbwt_text_load_fastx(grlbwt_ctx *ctx, const char *path, uint32_t fastx_fla
 int grlbwt_fastx_convert_device(grlbwt_ctx *ctx, const void *dev_in, uint64_t n_in, uint32_t fastx_flags, void *dev_out,
                                 uint64_t capacity, uint64_t *n_out, uint64_t *n_strings);
 
+/* ---- the order of the stage-wise calls -----------------------------------------
+ * A context with a text is in one of five states: LOADED (no round has run), PARTLY PARSED, PARSED (the last round has
+ * run), INDUCING (after grlbwt_induce_first, while a level is left to induce) and DONE (the image is there).  Loading a text
+ * replaces everything the context held of the previous one and starts at LOADED; a load that fails leaves the context
+ * without a text, and every call below returns GRLBWT_EINVAL until one is loaded.
+ *
+ *   grlbwt_parse_round    LOADED, PARTLY PARSED: one more round.  From PARSED on: GRLBWT_OK, *done = 1, nothing changes.
+ *   grlbwt_parse_phase    LOADED, PARTLY PARSED: the rounds that are left.  From PARSED on: GRLBWT_OK, *n_rounds = the rounds
+ *                         that have run, nothing changes.
+ *   grlbwt_induce_first   PARSED: the deepest level's BWT, once per text.  Every other state: GRLBWT_EINVAL.
+ *   grlbwt_induce_level   INDUCING: one level down; the call that produces level 0 also writes the image (DONE).  Every other
+ *                         state: GRLBWT_EINVAL.
+ *   grlbwt_induce_phase   LOADED, PARTLY PARSED: GRLBWT_EINVAL.  PARSED: the whole induction.  INDUCING: the levels that are
+ *                         left, and the image.  DONE: GRLBWT_OK, nothing changes.
+ *   grlbwt_build          from every state to DONE.  In DONE: GRLBWT_OK, the image is not written again (the same pointer,
+ *                         the same bytes).  A build that does the parsing itself may stop it at a level of short strings
+ *                         (GRLBWT_BASE_CASE_RATIO): grlbwt_parse_phase then reports fewer rounds than the stage-wise calls run.
+ *   grlbwt_result_*       DONE: the image.  Every other state: GRLBWT_EINVAL.
+ *
+ * A call that is refused (GRLBWT_EINVAL) or has nothing to do changes nothing: the calls that follow produce what they would
+ * have produced without it, and grlbwt_last_error names this refusal, not an earlier failure.  A stage call that fails after
+ * it has begun to change a level (out of memory, a device error) ends the text: every stage and result call returns
+ * GRLBWT_EINVAL until a text is loaded again.  A failure inside the first parsing round has changed nothing yet and leaves
+ * the context in LOADED: a borrowed text that was found changed there (grlbwt_text_attach_device) builds once its bytes
+ * are as they were. */
+
 /* ---- parsing phase ------------------------------------------------------- */
 /* one par_round (exact_par_phase.cpp:374-497): LMS breaks, phrase hashing, dictionary
  * sort, pre-BWT, grammar, parse emission.  *done = 1 after the last round (:496). */

@@ -23,15 +23,18 @@ def check_final(lib, data, cell_bytes=1, flags=0):
     return got
 
 
-def check_stagewise(lib, data, cell_bytes=1, flags=0):
+def check_stagewise(lib, data, cell_bytes=1, flags=0, between=None):
     """Every stage boundary against the oracle: stats, per-round counters, every level's
-    parse (rank<<1|rep) and every level's BWT runs, and the final bytes."""
+    parse (rank<<1|rep) and every level's BWT runs, and the final bytes.
+    between: called with the context between the steps (tests/call_order_cases.py puts calls there that must change nothing)."""
     o = oracle.OracleResult(data, cell_bytes, trace=True)
+    between = between or (lambda ctx: None)
     with engine.Context(0, flags | engine.FLAG_KEEP_LEVELS, lib) as ctx:
         ctx.upload(data, cell_bytes)
         st = ctx.stats()
         for k in ("n_strings", "n_syms", "min_sym", "max_sym", "max_sym_freq", "sb", "fb"):
             assert st[k] == o.stats[k], (k, st[k], o.stats[k])
+        between(ctx)
         r = 0
         while True:
             info, done = ctx.parse_round()
@@ -42,6 +45,7 @@ def check_stagewise(lib, data, cell_bytes=1, flags=0):
             cells = ctx.level_text(r + 1)
             assert np.array_equal(cells, (sym << np.uint64(1)) | rep.astype(np.uint64)), "parse of level %d differs" % (r + 1)
             r += 1
+            between(ctx)
             if done:
                 break
         assert r == o.n_rounds
@@ -53,7 +57,9 @@ def check_stagewise(lib, data, cell_bytes=1, flags=0):
             assert np.array_equal(hh, ohh), "has_hocc of level %d differs" % lvl
             ops, opl = o.level_prebwt(lvl)
             assert _merged(ps, pl) == _merged(ops, opl), "pre-BWT of level %d differs" % lvl
+        between(ctx)
         ctx.parse2bwt()
+        between(ctx)
         s, l = ctx.level_bwt(r)
         os_, ol = o.level_bwt(r)
         assert np.array_equal(s, os_) and np.array_equal(l, ol), "deepest BWT differs"
@@ -64,6 +70,7 @@ def check_stagewise(lib, data, cell_bytes=1, flags=0):
             os_, ol = o.level_bwt(lvl)
             assert np.array_equal(s, os_) and np.array_equal(l, ol), "BWT of level %d differs" % lvl
             assert li["n_runs"] == len(os_) and li["n"] == int(ol.sum())
+            between(ctx)
         assert ctx.result_bytes() == o.rl_bwt
     o.close()
 
