@@ -2202,6 +2202,62 @@ int grlbwt_fm_approx_info_get(const grlbwt_fm *fm, grlbwt_fm_approx_info *out) {
     if (fm->f32) fill(*fm->f32); else fill(*fm->f64);
     return GRLBWT_OK;
 }
+int grlbwt_fm_overlaps(grlbwt_ctx *ctx, const grlbwt_fm *fm, const void *dev_cells, int cell_bytes, const uint64_t *dev_offsets,
+                       uint64_t n_patterns, uint64_t min_len, uint64_t max_len, uint32_t flags, uint64_t *dev_hit_offsets, uint64_t *dev_len,
+                       uint64_t *dev_tlo, uint64_t *dev_thi, uint64_t *dev_lo, uint64_t *dev_hi, uint64_t capacity, uint64_t *n_hits_out) {
+    if (n_hits_out) *n_hits_out = 0;
+    if (!ctx || !fm || !(fm->f32 || fm->f64)) return refuse(ctx);
+    if (n_patterns && !dev_offsets) return GRLBWT_EINVAL;
+    uint64_t n = 0;
+    const int rc = guarded(ctx, [&] {
+        if (fm->f32) grl32::Image::fm_overlaps(*fm->f32, dev_cells, cell_bytes, dev_offsets, n_patterns, min_len, max_len, flags, dev_hit_offsets, dev_len,
+                                                dev_tlo, dev_thi, dev_lo, dev_hi, capacity, n);
+        else grl64::Image::fm_overlaps(*fm->f64, dev_cells, cell_bytes, dev_offsets, n_patterns, min_len, max_len, flags, dev_hit_offsets, dev_len,
+                                        dev_tlo, dev_thi, dev_lo, dev_hi, capacity, n);
+    });
+    if (n_hits_out) *n_hits_out = n;
+    return rc;
+}
+int grlbwt_fm_overlaps_of(grlbwt_ctx *ctx, const grlbwt_fm *fm, const uint64_t *dev_ids, uint64_t n_ids, uint64_t min_len, uint64_t max_len,
+                          uint32_t flags, uint64_t *dev_hit_offsets, uint64_t *dev_len, uint64_t *dev_tlo, uint64_t *dev_thi, uint64_t *dev_lo,
+                          uint64_t *dev_hi, uint64_t capacity, uint64_t *n_hits_out) {
+    if (n_hits_out) *n_hits_out = 0;
+    if (!ctx || !fm || !(fm->f32 || fm->f64)) return refuse(ctx);
+    if (n_ids && !dev_ids) return GRLBWT_EINVAL;
+    uint64_t n = 0;
+    const int rc = guarded(ctx, [&] {
+        if (fm->f32) grl32::Image::fm_overlaps_of(*fm->f32, dev_ids, n_ids, min_len, max_len, flags, dev_hit_offsets, dev_len, dev_tlo, dev_thi, dev_lo, dev_hi,
+                                                   capacity, n);
+        else grl64::Image::fm_overlaps_of(*fm->f64, dev_ids, n_ids, min_len, max_len, flags, dev_hit_offsets, dev_len, dev_tlo, dev_thi, dev_lo, dev_hi,
+                                           capacity, n);
+    });
+    if (n_hits_out) *n_hits_out = n;
+    return rc;
+}
+int grlbwt_fm_overlap_targets(grlbwt_ctx *ctx, const grlbwt_fm *fm, const uint64_t *dev_tlo, const uint64_t *dev_thi, uint64_t n_ranges,
+                              uint64_t *dev_entry_offsets, uint64_t *dev_string, uint64_t *dev_range, uint64_t capacity, uint64_t *n_entries_out) {
+    if (n_entries_out) *n_entries_out = 0;
+    if (!ctx || !fm || !(fm->f32 || fm->f64)) return refuse(ctx);
+    if (n_ranges && (!dev_tlo || !dev_thi)) return GRLBWT_EINVAL;
+    uint64_t n = 0;
+    const int rc = guarded(ctx, [&] {
+        if (fm->f32) grl32::Image::fm_overlap_targets(*fm->f32, dev_tlo, dev_thi, n_ranges, dev_entry_offsets, dev_string, dev_range, capacity, n);
+        else grl64::Image::fm_overlap_targets(*fm->f64, dev_tlo, dev_thi, n_ranges, dev_entry_offsets, dev_string, dev_range, capacity, n);
+    });
+    if (n_entries_out) *n_entries_out = n;
+    return rc;
+}
+int grlbwt_fm_overlap_info_get(const grlbwt_fm *fm, grlbwt_fm_overlap_info *out) {
+    if (!fm || !out || !(fm->f32 || fm->f64)) return GRLBWT_EINVAL;
+    auto fill = [&](const auto &F) {
+        const auto &o = F.oinfo;
+        out->n_patterns = o.patterns; out->n_cells = o.cells; out->n_hits = o.hits; out->n_targets = o.targets; out->longest = o.longest;
+        out->steps = o.steps; out->walk_lanes = o.lanes; out->lane_refills = o.refills; out->n_ranges = o.ranges; out->n_entries = o.entries;
+        out->tile_entries = o.tile;
+    };
+    if (fm->f32) fill(*fm->f32); else fill(*fm->f64);
+    return GRLBWT_OK;
+}
 int grlbwt_fm_lcp(grlbwt_ctx *ctx, const grlbwt_fm *fm, uint64_t max_lcp, int lcp_bytes, void *dev_lcp, uint64_t *host_rows_at,
                   uint64_t *host_suffixes_of, uint64_t hist_capacity, uint64_t *n_levels_out) {
     if (n_levels_out) *n_levels_out = 0;

@@ -637,6 +637,145 @@ struct FmApproxMismIn {
     const u64 *mism; u64 d;
     GRL_DEV u64 operator()(u64 j) const { return mism[j] == d ? 1ull : 0ull; }
 };
+// ---- suffix-prefix overlaps (grlbwt_fm_overlaps / grlbwt_fm_overlaps_of / grlbwt_fm_overlap_targets).  Ticket i is
+// query i.  A string starts with w exactly when the row of its whole-string suffix lies in the range of w, and the BWT symbol of
+// that row is the separator: the strings that start with w are the separator ranks [rank_sep(lo), rank_sep(hi)), one more step
+// with the separator as the symbol on a COPY of the range the backward search holds.  The separator is the smallest symbol, so
+// C[sep] = 0 and the step's answer is the rank itself.  The ranks are the index of FmIndex::sid.  (A step bounded to the
+// separator's records, key[0, Rsep), was measured against this plain one and dropped: under the LDS top level both searches
+// start from one stride of the keys, and the bounded one was no faster -- profiles/fm_overlaps/overlaps.txt.)
+//   The cells come from a source, last cell first and as codes: next() is false at the query's first cell, at the separator and
+//   at a value that is no symbol (every longer suffix would hold it); whole() says that the cells taken so far are the whole
+//   query.  FmOvCells reads the cells of a pattern, FmOvWalk the LF walk of a string of the collection (the walk of FmSidLenFn:
+//   the index was made with the locate structures, so every string's walk has met the separator within n steps).
+//   Two passes of this one search, as FmApproxFn: cnt[i] = hits while `olen` is null; then, with hoff = the scanned counts, the
+//   entries in ascending L, cnt[i] = the pass's steps (below), and `bad` where a query found another number of hits than it had
+//   counted.  The emit pass never stores past hoff[i + 1].
+//   The emit pass's word: L << 2 | (the last query step emptied the range) << 1 | (L was the whole query under PROPER and had no
+//   separator step), L = the cells matched.  Query steps = L + the second flag; separator steps = the L' in [floor, L] less
+//   the first flag.
+//   Loops: step() holds none but the binary searches; an item takes at most min(m, cap) + 1 steps of at most two fm_step each.
+struct FmOvCells {
+    struct State { u64 x0, x; };              // x cells are left
+    FmCountFn f; u64 sepval;
+    GRL_DEV void begin(u64 i, State &s) const { s.x0 = f.off[i]; s.x = f.off[i + 1] - s.x0; }
+    GRL_DEV bool next(State &s, u32 &c) const {
+        if (s.x == 0) return false;
+        const u64 v = f.cell(s.x0 + s.x - 1);
+        if (v == sepval || !f.code(v, c)) return false;
+        s.x--;
+        return true;
+    }
+    GRL_DEV bool whole(const State &s) const { return s.x == 0; }
+};
+struct FmOvWalk {
+    struct State { idx_t row; RunRec r; };    // the row the walk stands at and its record
+    LfRows lf; u32 sep; const u64 *ids;
+    GRL_DEV void begin(u64 i, State &s) const { s.row = (idx_t)ids[i]; s.r = lf.at(s.row); }
+    GRL_DEV bool next(State &s, u32 &c) const {
+        if (s.r.sym == sep) return false;
+        c = s.r.sym;
+        s.row = LfRows::next(s.row, s.r);
+        s.r = lf.at(s.row);
+        return true;
+    }
+    GRL_DEV bool whole(const State &s) const { return s.r.sym == sep; }
+};
+template <class SRC>
+struct FmOverlapFn {
+    typedef FmKey Key;
+    struct State { typename SRC::State s; u64 lo, hi, len, cnt, base, room; u32 flags; };
+    SRC src;
+    const FmKey *key; const idx_t *slf; u64 R, n; u32 sep;
+    u64 floor, cap; bool proper;              // floor >= 1; cap: ~0 for none
+    u64 *cnt; const u64 *hoff; u64 *olen, *tlo, *thi, *lo, *hi; u32 *bad;
+    GRL_HD const FmKey *keys() const { return key; }
+    GRL_HD u64 n_keys() const { return R; }
+    GRL_DEV bool begin(u64 i, State &st) const {
+        src.begin(i, st.s);
+        st.lo = 0; st.hi = n; st.len = 0; st.cnt = 0; st.flags = 0;
+        st.base = olen ? hoff[i] : 0; st.room = olen ? hoff[i + 1] - st.base : 0;
+        if (st.lo >= st.hi) { end(i, st); return false; }                  // (an index of no symbol)
+        return true;
+    }
+    template <class TOP>
+    GRL_DEV bool step(State &st, const TOP &top) const {
+        u32 c;
+        if (!src.next(st.s, c)) return true;
+        u64 a = st.lo, b = st.hi;
+        fm_step(key, slf, R, top, c, a, b);
+        if (a >= b) { st.flags |= 2u; return true; }
+        st.lo = a; st.hi = b; st.len++;
+        if (st.len >= floor) {
+            if (proper && src.whole(st.s)) {
+                st.flags |= 1u;
+            } else {
+                u64 ta = a, tb = b;
+                fm_step(key, slf, R, top, sep, ta, tb);
+                if (ta < tb) {
+                    if (olen && st.cnt < st.room) {
+                        const u64 j = st.base + st.cnt;
+                        olen[j] = st.len; tlo[j] = ta; thi[j] = tb;
+                        if (lo) { lo[j] = a; hi[j] = b; }
+                    }
+                    st.cnt++;
+                }
+            }
+        }
+        return st.len >= cap;
+    }
+    GRL_DEV bool step(State &st) const { return step(st, FmNoTop{}); }
+    GRL_DEV void end(u64 i, const State &st) const {
+        if (!olen) { cnt[i] = st.cnt; return; }
+        if (st.cnt != st.room) prim::atomic_max(bad, 1u);
+        cnt[i] = st.len << 2 | (u64)st.flags;
+    }
+};
+template <class SRC>
+struct FmOverlapLaneFn {  // the same, one lane per query through prim::top_search (GRLBWT_FM_MATCH=l)
+    typedef FmKey Key;
+    FmOverlapFn<SRC> f;
+    GRL_HD const FmKey *keys() const { return f.keys(); }
+    GRL_HD u64 n_keys() const { return f.n_keys(); }
+    template <class TOP>
+    GRL_DEV void operator()(u64 i, const TOP &top) const {
+        typename FmOverlapFn<SRC>::State st;
+        if (!f.begin(i, st)) return;
+        while (!f.step(st, top)) {}                                      // (bounded as said above)
+        f.end(i, st);
+    }
+};
+struct FmOvQueryStepsIn { // the emit pass's word: the query steps; the separator steps
+    const u64 *cnt;
+    GRL_DEV u64 operator()(u64 i) const { return (cnt[i] >> 2) + ((cnt[i] >> 1) & 1ull); }
+};
+struct FmOvSepStepsIn {
+    const u64 *cnt; u64 floor;
+    GRL_DEV u64 operator()(u64 i) const {
+        const u64 L = cnt[i] >> 2;
+        return L >= floor ? L - floor + 1 - (cnt[i] & 1ull) : 0ull;
+    }
+};
+struct FmOvIdBadIn {      // entry i when its string number is none, else ~0
+    const u64 *ids; u64 k;
+    GRL_DEV u64 operator()(u64 i) const { return ids[i] >= k ? i : ~0ull; }
+};
+struct FmOvRangeBadIn {   // range i when it is no range of prefix ranks, else ~0
+    const u64 *tlo, *thi; u64 k;
+    GRL_DEV u64 operator()(u64 i) const { return tlo[i] > thi[i] || thi[i] > k ? i : ~0ull; }
+};
+struct FmOvSpanIn {
+    const u64 *tlo, *thi;
+    GRL_DEV u64 operator()(u64 i) const { return thi[i] - tlo[i]; }
+};
+struct FmOvExpandFn {     // entry e of the expanded ranges through prim::for_each: the range that holds it by a search in the scanned offsets
+    const u64 *eoff, *tlo; const idx_t *sid; u64 nr; u64 *str, *rng;
+    GRL_DEV void operator()(u64 e) const {
+        const u64 r = upper_bound<u64>(eoff, nr + 1, e) - 1;              // eoff[r] <= e < eoff[r + 1]: empty ranges are stepped over
+        str[e] = (u64)sid[tlo[r] + (e - eoff[r])];
+        if (rng) rng[e] = r;
+    }
+};
 // sid: string i's walk (RunInvertLenFn's) ends at the row r that holds its separator; that separator is the LF(r)-th of the
 // BWT.  The LF map of any image is a permutation, so a walk from one of the first k rows comes back to one of them after at
 // most n steps; the bound is there for an index that is not what it should be.
@@ -1453,6 +1592,14 @@ struct Image {
     struct MatchInfo { u64 patterns = 0, cells = 0, matched = 0, longest = 0, capped = 0, mems = 0, lanes = 0, refills = 0; };
     struct ApproxInfo { u64 patterns = 0, cells = 0, k = 0, max_hits = 0, hits = 0, by[4] = {0, 0, 0, 0}, cut = 0, steps = 0, lanes = 0, refills = 0; };
     struct LcpInfo { u64 n = 0, k = 0, lcp_bytes = 0, cap = 0, passes = 0, n_levels = 0, max_lcp = 0, n_capped = 0, tile_rows = 0, scratch_bytes = 0; };      // of the last fm_lcp
+#ifdef GRLBWT_PRIM_HIP
+    static constexpr u64 kOverlapTile = prim::kExpandTile;
+#else
+    static constexpr u64 kOverlapTile = 2048;    // (the serial form has no tiles: the figure the device library reports)
+#endif
+    struct OverlapInfo {      // of the last fm_overlaps / fm_overlaps_of (the first eight) or fm_overlap_targets (ranges, entries)
+        u64 patterns = 0, cells = 0, hits = 0, targets = 0, longest = 0, steps = 0, lanes = 0, refills = 0, ranges = 0, entries = 0, tile = kOverlapTile;
+    };
     struct FmIndex {
         u64 n = 0, R = 0, k = 0, sigma = 0, sepval = 0;
         u32 sep = 0, top_entries = 0;
@@ -1475,6 +1622,7 @@ struct Image {
         mutable MatchInfo minfo;  // of the last fm_match / fm_mems
         mutable ApproxInfo ainfo; // of the last fm_approx
         mutable LcpInfo linfo;    // of the last fm_lcp
+        mutable OverlapInfo oinfo; // of the last fm_overlaps, fm_overlaps_of or fm_overlap_targets
         u64 extract_bytes() const { return (T.n + xq.n + xc.n) * sizeof(idx_t); }
         u64 bytes() const {
             return key.n * sizeof(FmKey) + slf.n * sizeof(idx_t) + alpha.n * 8 + rc.n * sizeof(RankCell) + rec.n * sizeof(RunRec) + sid.n * sizeof(idx_t) +
@@ -1722,6 +1870,127 @@ struct Image {
         for (u32 d = 0; d <= k && n_hits; d++) ai.by[d] = prim::reduce_sum<u64>(n_hits, FmApproxMismIn{mism, (u64)d}, "fm.approx_strata");
         prim::sync();
         F.ainfo = ai;
+    }
+    // ---- suffix-prefix overlaps (functor block "suffix-prefix overlaps").  Everything that can refuse a call runs
+    // before the first store into an output: the count pass writes scratch only (one word per query), its sum is held against the
+    // capacity, then the scan writes dev_hit_offsets and the emit pass the entries.  One ticket per query through
+    // prim::top_tickets -- a read with an error ends after a few cells, its neighbour runs to its first cell -- or with
+    // GRLBWT_FM_MATCH=l one lane per query through prim::top_search; the stand-in runs the same functor serially.
+    //   The compiler's report for gfx950 (tools/kernel_resources.py; profiles/fm_overlaps/kernel_resources.txt), 32- / 64-bit positions:
+    //   k_top_tickets<FmOverlapFn<FmOvCells>> 58 / 58 VGPRs, 8 / 7 waves per SIMD; k_top_tickets<FmOverlapFn<FmOvWalk>> 58 / 62, 8 waves;
+    //   k_top_search of the lane forms 40 / 38, 8 waves; prim::k_expand_ranges 18 / 18, 8 waves, 10264 bytes of LDS; no scratch in any of them.
+    static constexpr u32 kOverlapProper = 1;
+    template <class SRC>
+    static void fm_overlaps_run(const FmIndex &F, const FmOverlapFn<SRC> &f, u64 np, OverlapInfo &oi) {
+#ifdef GRLBWT_PRIM_HIP
+        if (prim::sw().fm_match == 'l') {
+            prim::top_search(np, FmOverlapLaneFn<SRC>{f}, F.top_entries, "fm.overlap_lanes");
+            oi.lanes = np; oi.refills = 0;
+        } else {
+            DBuf<u64> ctr(2);
+            const prim::WalkStats ws = prim::top_tickets(np, f, ctr.p, F.top_entries, "fm.overlaps");
+            oi.lanes = ws.lanes; oi.refills = ws.refills;
+        }
+#else
+        prim::for_each(np, WalkSerialFn<FmOverlapFn<SRC>>{f}, "fm.overlaps");
+        oi.lanes = np; oi.refills = 0;
+#endif
+    }
+    static void fm_overlap_args(u32 flags, const u64 *lo, const u64 *hi, const char *who) {
+        if (flags & ~kOverlapProper) throw prim::Error(-22, std::string(who) + ": unknown flag bits");
+        if ((lo == nullptr) != (hi == nullptr)) throw prim::Error(-22, std::string(who) + ": the row outputs are both given or both null");
+    }
+    // the two passes over np queries whose cells `src` gives; n_hits is set whenever the count was reached, also when the capacity then refuses the call
+    template <class SRC>
+    static void fm_overlaps_t(const FmIndex &F, const SRC &src, u64 np, u64 min_len, u64 max_len, u32 flags, u64 *hoff, u64 *olen, u64 *tlo, u64 *thi,
+                              u64 *lo, u64 *hi, u64 capacity, u64 &n_hits, const char *who) {
+        OverlapInfo oi;
+        oi.patterns = np;
+        if (np == 0) {
+            if (hoff) prim::dev_memset(hoff, 0, 8);
+            prim::sync();
+            F.oinfo = oi;
+            return;
+        }
+        if (np >= (~0ull >> 4) || (np + 1) * 8 + 64 > prim::mem_available())
+            throw prim::Error(-12, std::string(who) + ": the counts need " + std::to_string((np + 1) * 8) + " bytes of device memory, more than is free");
+        DBuf<u64> cnt(np + 1);
+        DBuf<u32> bad(1);
+        bad.zero();
+        const u64 floor = min_len ? min_len : 1;
+        FmOverlapFn<SRC> f{src, F.key.p, F.slf.p, F.R, F.n, F.sep, floor, max_len ? max_len : ~0ull, (flags & kOverlapProper) != 0,
+                           cnt.p, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, bad.p};
+        fm_overlaps_run(F, f, np, oi);
+        oi.hits = n_hits = prim::reduce_sum<u64>(np, CellIn<u64>{cnt.p}, "fm.overlap_hits");
+        if (n_hits > capacity) throw prim::Error(-22, std::string(who) + ": " + std::to_string(n_hits) + " hits, more than the output arrays hold");
+        if (!hoff || (n_hits && (!olen || !tlo || !thi))) throw prim::Error(-22, std::string(who) + ": no output arrays");      // (the sizing call takes none)
+        prim::exclusive_scan<u64>(np, CellIn<u64>{cnt.p}, hoff, true, "fm.overlap_offsets");
+        // (without a hit the arrays may be missing: the pass then stores no entry, and the spare scratch word marks it as the emit pass)
+        f.hoff = hoff; f.olen = olen ? olen : cnt.p + np; f.tlo = tlo; f.thi = thi; f.lo = lo; f.hi = hi;
+        fm_overlaps_run(F, f, np, oi);
+        if (bad.get(0)) throw prim::Error(-71, std::string(who) + ": a query's second pass found another number of hits than its first");
+        oi.cells = prim::reduce_sum<u64>(np, FmOvQueryStepsIn{cnt.p}, "fm.overlap_cells");
+        oi.steps = oi.cells + prim::reduce_sum<u64>(np, FmOvSepStepsIn{cnt.p, floor}, "fm.overlap_steps");
+        if (n_hits) {
+            oi.targets = prim::reduce_sum<u64>(n_hits, FmOvSpanIn{tlo, thi}, "fm.overlap_targets");
+            oi.longest = prim::reduce_max<u64>(n_hits, CellIn<u64>{olen}, "fm.overlap_longest");
+        }
+        prim::sync();
+        F.oinfo = oi;
+    }
+    static void fm_overlaps(const FmIndex &F, const void *cells, int w, const u64 *off, u64 np, u64 min_len, u64 max_len, u32 flags, u64 *hoff, u64 *olen,
+                            u64 *tlo, u64 *thi, u64 *lo, u64 *hi, u64 capacity, u64 &n_hits) {
+        n_hits = 0;
+        fm_overlap_args(flags, lo, hi, "fm overlaps");
+        u64 x0;
+        (void)fm_match_cells(cells, w, off, np, x0, "fm overlaps");
+        fm_overlaps_t(F, FmOvCells{fm_count_fn(F, cells, w, off, nullptr, nullptr), F.sepval}, np, min_len, max_len, flags, hoff, olen, tlo, thi, lo, hi,
+                      capacity, n_hits, "fm overlaps");
+    }
+    static void fm_overlaps_of(const FmIndex &F, const u64 *ids, u64 n_ids, u64 min_len, u64 max_len, u32 flags, u64 *hoff, u64 *olen, u64 *tlo, u64 *thi,
+                               u64 *lo, u64 *hi, u64 capacity, u64 &n_hits) {
+        n_hits = 0;
+        fm_overlap_args(flags, lo, hi, "fm overlaps of");
+        if (!F.locate) throw prim::Error(-22, "fm overlaps of: the index was made without the structures for locating");
+        if (n_ids) {
+            const u64 bad = prim::reduce_min<u64>(n_ids, FmOvIdBadIn{ids, F.k}, "fm.overlap_ids");
+            if (bad != ~0ull) throw prim::Error(-22, "fm overlaps of: entry " + std::to_string(bad) + " is not below the number of strings");
+        }
+        fm_overlaps_t(F, FmOvWalk{F.lf(), F.sep, ids}, n_ids, min_len, max_len, flags, hoff, olen, tlo, thi, lo, hi, capacity, n_hits, "fm overlaps of");
+    }
+    // prefix ranks -> string numbers: sid[t] for every t of every range, back to back.  The device form is prim::expand_ranges (one
+    // tile of kOverlapTile entries per workgroup); the stand-in's, and the form it is measured against, a for_each over the entries
+    // with a search in the scanned offsets.  n_entries is set whenever the count was reached, also when the capacity then refuses the call.
+    static void fm_overlap_targets(const FmIndex &F, const u64 *tlo, const u64 *thi, u64 nr, u64 *eoff, u64 *str, u64 *rng, u64 capacity, u64 &n_entries) {
+        n_entries = 0;
+        if (!F.locate) throw prim::Error(-22, "fm overlap targets: the index was made without the structures for locating");
+        OverlapInfo oi;
+        oi.ranges = nr;
+        if (nr == 0) {
+            if (eoff) prim::dev_memset(eoff, 0, 8);
+            prim::sync();
+            F.oinfo = oi;
+            return;
+        }
+        const u64 bad = prim::reduce_min<u64>(nr, FmOvRangeBadIn{tlo, thi, F.k}, "fm.overlap_ranges");
+        if (bad != ~0ull) throw prim::Error(-22, "fm overlap targets: range " + std::to_string(bad) + " is no range of prefix ranks (lo <= hi <= the number of strings)");
+        if (nr >= ((u64)1 << 32)) throw prim::Error(-75, "fm overlap targets: more ranges than one call takes");
+        if ((nr + 1) * 8 + 64 > prim::mem_available())
+            throw prim::Error(-12, "fm overlap targets: the offsets need " + std::to_string((nr + 1) * 8) + " bytes of device memory, more than is free");
+        DBuf<u64> sc(nr + 1);
+        oi.entries = n_entries = prim::exclusive_scan<u64>(nr, FmOvSpanIn{tlo, thi}, sc.p, true, "fm.overlap_entry_offsets");
+        if (n_entries > capacity) throw prim::Error(-22, "fm overlap targets: " + std::to_string(n_entries) + " entries, more than the output arrays hold");
+        if (!eoff || (n_entries && !str)) throw prim::Error(-22, "fm overlap targets: no output arrays");      // (the sizing call takes none)
+        prim::d2d(eoff, sc.p, (nr + 1) * 8);
+        if (n_entries) {
+#ifdef GRLBWT_PRIM_HIP
+            if (prim::sw().dev_overlap_expand != 'f') prim::expand_ranges<idx_t>(nr, n_entries, sc.p, tlo, F.sid.p, str, rng, "fm.overlap_expand");
+            else
+#endif
+                prim::for_each(n_entries, FmOvExpandFn{sc.p, tlo, F.sid.p, nr, str, rng}, "fm.overlap_expand_plain");
+        }
+        prim::sync();
+        F.oinfo = oi;
     }
     // ---- the LCP array and the suffix-length counts (functor block "the LCP array of the collection").  Everything
     // that can refuse the call for its arguments or for memory runs before the first store into an output; histograms that may

@@ -2431,6 +2431,92 @@ struct LcpRound {
     }
 };
 
+// ------------------------------------------------------------------ ranges expanded into their entries (grlbwt_fm_overlap_targets)
+// nr ranges, range r = [tlo[r], tlo[r] + (eoff[r + 1] - eoff[r])) of `src`; entry e of range r, eoff[r] <= e < eoff[r + 1], is
+// out[e] = src[tlo[r] + (e - eoff[r])], rng[e] = r (rng may be null).  eoff is the exclusive scan of the ranges' sizes with the
+// total at nr.  A for_each over the entries pays a search of log2(nr) dependent loads per ENTRY; here a workgroup takes a tile
+// of kExpandTile consecutive entries and pays ONE: thread 0 finds r0, the range that holds the tile's first entry (the last r
+// with eoff[r] <= e0; empty ranges share their offset with the next one and are stepped over).  The ranges behind r0 that start
+// inside the tile are read with consecutive lanes on consecutive r; each that is not empty stores r - r0 into the LDS slot of
+// its first entry -- different ranges that hold an entry start at different entries: no slot is written twice, no atomics.  A running
+// maximum over the slots then gives every entry its range: each lane scans kExpandTile / kBlock consecutive slots, the lanes'
+// maxima are scanned through shuffles and one LDS word per wave.  The stores run with consecutive lanes on consecutive entries.
+//   LDS: kExpandTile + kExpandTile / 8 words of slots (a padding word behind every 8: the lanes' scans, 8 slots apart, would
+//     otherwise meet in the same banks 8 at a time), kBlock words of carries, one word per wave, r0: 10.3 KB.
+//   Bounds: a slot index is eoff[r] - e0 with e0 < eoff[r] < e1 <= e0 + kExpandTile (r > r0: its offset is above e0 by the
+//     choice of r0; the loop ends at the first offset >= e1); entries are stored for e < total only; src is read at
+//     tlo[r] + (e - eoff[r]) < tlo[r] + the size of range r, which the caller has checked against the length of src.
+//     r - r0 fits 32 bits: the caller refuses 2^32 ranges or more.
+//   Loops: the search (at most 64 halvings), the ranges that start inside the tile (at most nr / kBlock rounds; only empty ranges
+//     make them more than kExpandTile / kBlock), the 8 slots of a lane.  Every thread reaches the three barriers: no thread
+//     leaves early.  No workgroup waits for another.
+static constexpr int kExpandTile = 2048;
+template <class idx_t>
+__global__ void __launch_bounds__(kBlock) k_expand_ranges(u64 nr, u64 total, const u64 *eoff, const u64 *tlo, const idx_t *src, u64 *out, u64 *rng) {
+    constexpr int EPT = kExpandTile / kBlock, NW = kBlock / 64;
+    __shared__ u32 s_head[kExpandTile + kExpandTile / 8];
+    __shared__ u32 s_carry[kBlock];
+    __shared__ u32 s_wave[NW];
+    __shared__ u64 s_r0;
+    const u32 tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const u64 e0 = (u64)blockIdx.x * kExpandTile;
+    const u64 e1 = e0 + kExpandTile < total ? e0 + kExpandTile : total;
+    auto slot = [](u32 i) { return i + (i >> 3); };
+    for (u32 i = tid; i < (u32)kExpandTile; i += kBlock) s_head[slot(i)] = 0;
+    if (tid == 0) {
+        u64 a = 0, b = nr;                                       // the first r in [0, nr] with eoff[r] > e0: eoff[nr] = total > e0
+        for (int it = 0; it < 64 && a < b; it++) { const u64 mid = (a + b) >> 1; if (eoff[mid] <= e0) a = mid + 1; else b = mid; }
+        s_r0 = a - 1;                                            // (eoff[0] = 0 <= e0: a >= 1)
+    }
+    __syncthreads();
+    const u64 r0 = s_r0;
+    for (u64 r = r0 + 1 + tid; r < nr; r += kBlock) {
+        const u64 s = eoff[r];
+        if (s >= e1) break;
+        if (eoff[r + 1] > s) s_head[slot((u32)(s - e0))] = (u32)(r - r0);
+    }
+    __syncthreads();
+    u32 m = 0;
+#pragma unroll
+    for (int j = 0; j < EPT; j++) {
+        const u32 i = slot(tid * EPT + j);
+        const u32 v = s_head[i];
+        m = v > m ? v : m;
+        s_head[i] = m;
+    }
+    u32 inc = m;                                                 // inclusive maximum over the lanes of the wave, then the exclusive one
+    for (int d = 1; d < 64; d <<= 1) { const u32 o = __shfl_up(inc, d); if (lane >= (u32)d) inc = o > inc ? o : inc; }
+    if (lane == 63) s_wave[wave] = inc;
+    u32 exc = __shfl_up(inc, 1);
+    if (lane == 0) exc = 0;
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < NW; k++) { const u32 o = s_wave[k]; if ((u32)k < wave && o > exc) exc = o; }
+    s_carry[tid] = exc;
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < EPT; j++) {
+        const u32 i = (u32)j * kBlock + tid;
+        const u64 e = e0 + i;
+        if (e < e1) {
+            const u32 own = s_head[slot(i)], before = s_carry[i / EPT];
+            const u64 r = r0 + (own > before ? own : before);
+            out[e] = (u64)src[tlo[r] + (e - eoff[r])];
+            if (rng) rng[e] = r;
+        }
+    }
+}
+template <class idx_t>
+inline void expand_ranges(u64 nr, u64 total, const u64 *eoff, const u64 *tlo, const idx_t *src, u64 *out, u64 *rng, const char *name = "expand_ranges") {
+    if (total == 0) return;
+    const u64 tiles = (total + kExpandTile - 1) / kExpandTile;
+    if (tiles > 0x7FFFFFFFull) throw Error(-75, std::string(name) + ": more entries than one launch takes");
+    prof_begin(name, total * (sizeof(idx_t) + (rng ? 16 : 8)));
+    hipLaunchKernelGGL((k_expand_ranges<idx_t>), dim3((unsigned)tiles), dim3(kBlock), 0, rt().stream, nr, total, eoff, tlo, src, out, rng);
+    prof_end();
+    after_launch(name);
+}
+
 // Digit plan of an LSD sort over `bits` key bits: the fewest passes with digits of at most rs_max_digit() bits, widths as equal
 // as possible (at 9: 51 bits = 9,9,9,8,8,8; 54 = 6 x 9; 18 = 9,9).  GRLBWT_SORT_DIGIT=8|9|10 sets the widest digit; the default
 // stays 8: measured on the 10 GB build (profiles/r03), 9- and 10-bit digits save a pass over the 51-56-bit suffix keys and the

@@ -38,6 +38,7 @@ ABI_SYMBOLS = [
     "grlbwt_fm_string_lengths", "grlbwt_fm_extract", "grlbwt_fm_extract_info_get",
     "grlbwt_fm_match", "grlbwt_fm_mems", "grlbwt_fm_match_info_get",
     "grlbwt_fm_approx", "grlbwt_fm_approx_info_get",
+    "grlbwt_fm_overlaps", "grlbwt_fm_overlaps_of", "grlbwt_fm_overlap_targets", "grlbwt_fm_overlap_info_get",
     "grlbwt_fm_lcp", "grlbwt_fm_lcp_info_get",
     "grlbwt_merge_create", "grlbwt_merge_info_get", "grlbwt_merge_emit", "grlbwt_merge_interleave", "grlbwt_merge_destroy",
     "grlbwt_merge_files",
@@ -48,6 +49,7 @@ ABI_SYMBOLS = [
 FM_LOCATE = 1
 FM_CHECKPOINTS = 2
 FM_EXTRACT = 4
+FM_OVERLAP_PROPER = 1
 UINT64_MAX = 2 ** 64 - 1
 SELECT_KEEP = 1
 SELECT_CHECKPOINTS = 2
@@ -90,6 +92,11 @@ class ApproxInfo(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in ("n_patterns", "n_cells", "max_mismatches", "max_hits", "n_hits")] + \
                [("hits_by_mismatches", C.c_uint64 * 4)] + \
                [(k, C.c_uint64) for k in ("n_truncated", "steps", "walk_lanes", "lane_refills", "table_bytes")]
+
+
+class OverlapInfo(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("n_patterns", "n_cells", "n_hits", "n_targets", "longest", "steps", "walk_lanes",
+                                          "lane_refills", "n_ranges", "n_entries", "tile_entries")]
 
 
 class LcpInfo(C.Structure):
@@ -254,6 +261,10 @@ def load_library(path=None, allow_test_standin=False):
     L.grlbwt_fm_match_info_get.argtypes = [vp, C.POINTER(MatchInfo)]
     L.grlbwt_fm_approx.argtypes = [vp, vp, vp, i32, vp, u64, C.c_uint32, u64, vp, vp, vp, vp, vp, vp, u64, C.POINTER(u64)]
     L.grlbwt_fm_approx_info_get.argtypes = [vp, C.POINTER(ApproxInfo)]
+    L.grlbwt_fm_overlaps.argtypes = [vp, vp, vp, i32, vp, u64, u64, u64, C.c_uint32, vp, vp, vp, vp, vp, vp, u64, C.POINTER(u64)]
+    L.grlbwt_fm_overlaps_of.argtypes = [vp, vp, vp, u64, u64, u64, C.c_uint32, vp, vp, vp, vp, vp, vp, u64, C.POINTER(u64)]
+    L.grlbwt_fm_overlap_targets.argtypes = [vp, vp, vp, vp, u64, vp, vp, vp, u64, C.POINTER(u64)]
+    L.grlbwt_fm_overlap_info_get.argtypes = [vp, C.POINTER(OverlapInfo)]
     L.grlbwt_fm_lcp.argtypes = [vp, vp, u64, i32, vp, vp, vp, u64, C.POINTER(u64)]
     L.grlbwt_fm_lcp_info_get.argtypes = [vp, C.POINTER(LcpInfo)]
     L.grlbwt_merge_create.argtypes = [vp, vp, u64, vp, u64, i32, u64, C.POINTER(vp)]
@@ -688,6 +699,61 @@ class FmIndex:
         d = _as_dict(out)
         d["hits_by_mismatches"] = [int(v) for v in out.hits_by_mismatches]
         return d
+
+    def overlaps(self, cells_ptr, cell_bytes, offsets_ptr, n, min_len, max_len, flags, hit_offsets_ptr, len_ptr, tlo_ptr, thi_ptr, capacity,
+                 lo_ptr=None, hi_ptr=None):
+        """Which strings of the collection begin with a suffix of the n patterns (given as to count()): the hits of pattern i are
+        entries [hit_offsets[i], hit_offsets[i + 1]) of (len = L, [tlo, thi)) in ascending L, max(min_len, 1) <= L <=
+        min(the pattern's cells, max_len if not 0); [tlo, thi) are prefix ranks, which overlap_targets() turns into string
+        numbers.  flags: FM_OVERLAP_PROPER leaves out L = the whole pattern.  lo / hi, both or neither, receive the rows of the
+        suffix.  The number of hits is returned.  More than `capacity`: GrlbwtError whose n_hits attribute is that number, and
+        nothing is written."""
+        got = C.c_uint64()
+        try:
+            self.ctx._ck(self.ctx.L.grlbwt_fm_overlaps(self.ctx._h, self._h, C.c_void_p(cells_ptr), cell_bytes, C.c_void_p(offsets_ptr), n,
+                                                       min_len, max_len, flags, C.c_void_p(hit_offsets_ptr), C.c_void_p(len_ptr),
+                                                       C.c_void_p(tlo_ptr), C.c_void_p(thi_ptr), C.c_void_p(lo_ptr), C.c_void_p(hi_ptr),
+                                                       capacity, C.byref(got)))
+        except GrlbwtError as e:
+            e.n_hits = got.value
+            raise
+        return got.value
+
+    def overlaps_of(self, ids_ptr, n, min_len, max_len, flags, hit_offsets_ptr, len_ptr, tlo_ptr, thi_ptr, capacity, lo_ptr=None, hi_ptr=None):
+        """overlaps() with strings of the collection as the queries, by number (n uint64 words; an index made with locate=True):
+        their cells are read from the index itself."""
+        got = C.c_uint64()
+        try:
+            self.ctx._ck(self.ctx.L.grlbwt_fm_overlaps_of(self.ctx._h, self._h, C.c_void_p(ids_ptr), n, min_len, max_len, flags,
+                                                          C.c_void_p(hit_offsets_ptr), C.c_void_p(len_ptr), C.c_void_p(tlo_ptr),
+                                                          C.c_void_p(thi_ptr), C.c_void_p(lo_ptr), C.c_void_p(hi_ptr), capacity, C.byref(got)))
+        except GrlbwtError as e:
+            e.n_hits = got.value
+            raise
+        return got.value
+
+    def overlap_targets(self, tlo_ptr, thi_ptr, n, entry_offsets_ptr, string_ptr, capacity, range_ptr=None):
+        """The string numbers behind n ranges of prefix ranks (an index made with locate=True): the entries of range r are
+        [entry_offsets[r], entry_offsets[r + 1]) of string, in ascending rank; range_ptr (optional) receives r per entry.  The
+        number of entries is returned.  More than `capacity`: GrlbwtError whose n_entries attribute is that number, and nothing
+        is written."""
+        got = C.c_uint64()
+        try:
+            self.ctx._ck(self.ctx.L.grlbwt_fm_overlap_targets(self.ctx._h, self._h, C.c_void_p(tlo_ptr), C.c_void_p(thi_ptr), n,
+                                                              C.c_void_p(entry_offsets_ptr), C.c_void_p(string_ptr), C.c_void_p(range_ptr),
+                                                              capacity, C.byref(got)))
+        except GrlbwtError as e:
+            e.n_entries = got.value
+            raise
+        return got.value
+
+    def overlap_info(self):
+        """The counters of the last overlaps(), overlaps_of() or overlap_targets() on this index."""
+        out = OverlapInfo()
+        rc = self.ctx.L.grlbwt_fm_overlap_info_get(self._h, C.byref(out))
+        if rc != OK:
+            raise GrlbwtError(rc, self.ctx.L.grlbwt_strerror(rc).decode())
+        return _as_dict(out)
 
     LCP_HIST_FIRST = 1 << 20      # levels the histograms of lcp() are first sized for, where the cap and the rows allow more
 

@@ -507,9 +507,84 @@ int grlbwt_fm_approx(grlbwt_ctx *ctx, const grlbwt_fm *fm, const void *dev_cells
                      uint64_t *n_hits_out);
 int grlbwt_fm_approx_info_get(const grlbwt_fm *fm, grlbwt_fm_approx_info *out);
 
+/* ---- suffix-prefix overlaps: which strings of the collection BEGIN with a suffix of a query -- the edges of an assembly string
+ * graph, what SGA-style tools build the BCR BWT of a read set for.  In a BCR BWT a string starts with w exactly when the row of
+ * its whole-string suffix lies in the row range of w, and the BWT symbol of that row is the separator; the strings that start
+ * with w are therefore one contiguous interval of separator ranks, [rank_sep(lo), rank_sep(hi)): one more backward step, with
+ * the separator as the symbol, on the range the search already holds.  With a collection built with its reverse complements
+ * (-R) the answers cover both strands.
+ *
+ * PREFIX RANKS: positions in the order of the whole strings as the BWT's separators hold them -- the strings sorted by their
+ * cells, a string in front of every string it is a proper prefix of, equal strings by their number, empty strings first.  This
+ * is the index of the table grlbwt_fm_overlap_targets reads.
+ *
+ * grlbwt_fm_overlaps: queries given as cells, exactly as grlbwt_fm_count takes them (cell_bytes in {1, 2, 4, 8} whatever the
+ * image's width, n_patterns + 1 non-decreasing offsets, dev_offsets[0] may be above 0, compacted alphabets are searched on their
+ * ranks).  It works on any index, with or without GRLBWT_FM_LOCATE.  A HIT of pattern q (m cells) is a length L with
+ * max(min_len, 1) <= L <= min(m, max_len if it is not 0) such that the last L cells of q hold no separator and no value that is
+ * no symbol of the image, and at least one string of the collection starts with them.  GRLBWT_FM_OVERLAP_PROPER in `flags`
+ * leaves out L = m (proper suffixes only); any other flag bit is GRLBWT_EINVAL.  A string EQUAL to the suffix lies in the range:
+ * without PROPER a query that is a string of the collection finds itself at L = m.  The separator and non-symbols never fail the
+ * call; they end the pattern's search, since every longer suffix would hold them.
+ * OUTPUT: the hits of pattern i are entries [dev_hit_offsets[i], dev_hit_offsets[i + 1]), back to back in pattern order and,
+ * part of the contract, in ASCENDING L, the order the search meets them; dev_hit_offsets[n_patterns] = *n_hits_out.  Entry j is
+ * (dev_len[j] = L, prefix ranks [dev_tlo[j], dev_thi[j])).  dev_lo and dev_hi are given both or neither (one alone:
+ * GRLBWT_EINVAL); when given, entry j also carries the rows grlbwt_fm_count answers for that suffix.  *n_hits_out is always set
+ * once the count is known; with more hits than `capacity` the call fails with GRLBWT_EINVAL and writes no output array,
+ * dev_hit_offsets included (the sizing idiom of grlbwt_fm_approx: call with capacity 0 and no arrays).  GRLBWT_EINVAL before the
+ * first store: unknown flag bits, one of dev_lo / dev_hi alone, a cell_bytes not in {1, 2, 4, 8}, decreasing offsets, dev_cells
+ * missing while there are cells, dev_hit_offsets missing while n_patterns > 0, hits without dev_len / dev_tlo / dev_thi, a null
+ * index.  GRLBWT_ENOMEM when the scratch, one word per pattern, does not fit.
+ *
+ * grlbwt_fm_overlaps_of: the queries are strings of the collection, by number; no text is needed beside the image.  Needs
+ * GRLBWT_FM_LOCATE (without it: GRLBWT_EINVAL).  The cells of string dev_ids[i] come from the LF walk that starts at row
+ * dev_ids[i], last cell first, until the separator.  Same arguments otherwise, same outputs and refusals, n_ids for n_patterns;
+ * repeats are allowed; an id >= n_strings fails the whole call with GRLBWT_EINVAL before any store, the message names the first
+ * such entry.  Its answers are those of grlbwt_fm_overlaps on the strings' own cells, hit for hit.
+ *
+ * grlbwt_fm_overlap_targets: prefix ranks to string numbers.  Needs GRLBWT_FM_LOCATE.  n_ranges pairs [dev_tlo[r], dev_thi[r]),
+ * the hit columns above or any ranges; empty ranges are legal; dev_tlo[r] > dev_thi[r] or dev_thi[r] > n_strings is
+ * GRLBWT_EINVAL before any store, the message names the first such range.  The entries of range r are
+ * [dev_entry_offsets[r], dev_entry_offsets[r + 1]), back to back: dev_string[e] = the number of the string at prefix rank t, for
+ * t ascending; dev_range (may be NULL) receives r for every entry of range r.  *n_entries_out and `capacity` follow the sizing
+ * idiom (more entries than capacity: GRLBWT_EINVAL, nothing written).  2^32 ranges or more: GRLBWT_ERANGE.
+ *
+ * COST: one ticket per query, as grlbwt_fm_approx: the search runs from the last cell to the first, one backward step of
+ * grlbwt_fm_count per cell, and from L = max(min_len, 1) on one more such step, for the separator, on a copy of the range.
+ * It ends when the range empties, at a separator or non-symbol, at the query's first cell or at
+ * max_len.  The search runs twice, to count and to emit.  GRLBWT_WALK_LANES, GRLBWT_FM_MATCH=l and GRLBWT_FM_TOP_BITS act as
+ * for grlbwt_fm_approx.  The targets are one tile of tile_entries entries per workgroup: one search per tile, not per entry.
+ * OUT OF SCOPE: transitive reduction of the overlap graph, overlaps with mismatches, prefix-suffix overlaps in the other
+ * direction (build the collection with -R), a multi-GPU form, a command-line flag.
+ * grlbwt_fm_overlap_info_get: the counters of the last of the three calls that succeeded on the index (the fields of the other
+ * kind are 0; tile_entries is always set). */
+#define GRLBWT_FM_OVERLAP_PROPER 1u
+typedef struct grlbwt_fm_overlap_info {
+    uint64_t n_patterns, n_cells;      /* queries; query cells the emitting pass stepped over */
+    uint64_t n_hits, n_targets;        /* n_targets: the sum of dev_thi - dev_tlo over the hits */
+    uint64_t longest;                  /* the largest L of a hit */
+    uint64_t steps;                    /* backward steps of the emitting pass, separator steps included */
+    uint64_t walk_lanes, lane_refills; /* of the emitting launch, as in grlbwt_walk_info */
+    uint64_t n_ranges, n_entries;      /* of grlbwt_fm_overlap_targets */
+    uint64_t tile_entries;             /* entries per workgroup of the expanding kernel */
+} grlbwt_fm_overlap_info;
+int grlbwt_fm_overlaps(grlbwt_ctx *ctx, const grlbwt_fm *fm, const void *dev_cells, int cell_bytes, const uint64_t *dev_offsets,
+                       uint64_t n_patterns, uint64_t min_len /* 0: as 1 */, uint64_t max_len /* 0: no cap */, uint32_t flags,
+                       uint64_t *dev_hit_offsets /* n_patterns + 1 words */, uint64_t *dev_len, uint64_t *dev_tlo, uint64_t *dev_thi,
+                       uint64_t *dev_lo /* may be NULL */, uint64_t *dev_hi /* may be NULL */, uint64_t capacity, uint64_t *n_hits_out);
+int grlbwt_fm_overlaps_of(grlbwt_ctx *ctx, const grlbwt_fm *fm, const uint64_t *dev_ids, uint64_t n_ids, uint64_t min_len,
+                          uint64_t max_len, uint32_t flags, uint64_t *dev_hit_offsets /* n_ids + 1 words */, uint64_t *dev_len,
+                          uint64_t *dev_tlo, uint64_t *dev_thi, uint64_t *dev_lo /* may be NULL */, uint64_t *dev_hi /* may be NULL */,
+                          uint64_t capacity, uint64_t *n_hits_out);
+int grlbwt_fm_overlap_targets(grlbwt_ctx *ctx, const grlbwt_fm *fm, const uint64_t *dev_tlo, const uint64_t *dev_thi, uint64_t n_ranges,
+                              uint64_t *dev_entry_offsets /* n_ranges + 1 words */, uint64_t *dev_string, uint64_t *dev_range /* may be NULL */,
+                              uint64_t capacity, uint64_t *n_entries_out);
+int grlbwt_fm_overlap_info_get(const grlbwt_fm *fm, grlbwt_fm_overlap_info *out);
+
 /* ---- the LCP array of the collection and its suffix-length counts: the other half of the enhanced suffix array, what BCR-style
- * tools write beside the BWT.  With it the distinct k-mer counts for every k, the nodes and edges of a de Bruijn graph,
- * suffix / prefix overlaps and the repeat structure of a read set are one pass over an array.  The call works on any index of
+ * tools write beside the BWT.  With it the distinct k-mer counts for every k, the nodes and edges of a de Bruijn graph and the
+ * repeat structure of a read set are one pass over an array.  (Suffix / prefix overlaps are not: the array says how long an
+ * overlap is, not between which strings -- grlbwt_fm_overlaps above answers that from the index.)  The call works on any index of
  * grlbwt_fm_create, with or without GRLBWT_FM_LOCATE, in both position widths and on compacted alphabets (only equality of
  * symbols matters); it makes no handle and leaves the index, its index_bytes and every later answer as they were.
  *
