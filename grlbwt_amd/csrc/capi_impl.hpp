@@ -2281,6 +2281,26 @@ int grlbwt_fm_lcp_info_get(const grlbwt_fm *fm, grlbwt_fm_lcp_info *out) {
     if (fm->f32) fill(*fm->f32); else fill(*fm->f64);
     return GRLBWT_OK;
 }
+int grlbwt_fm_sa(grlbwt_ctx *ctx, const grlbwt_fm *fm, uint64_t row_begin, uint64_t row_end, int string_bytes, void *dev_string, int offset_bytes,
+                 void *dev_offset) {
+    if (!ctx || !fm || !(fm->f32 || fm->f64)) return refuse(ctx);
+    return guarded(ctx, [&] {
+        if (fm->f32) grl32::Image::fm_sa(*fm->f32, row_begin, row_end, string_bytes, dev_string, offset_bytes, dev_offset);
+        else grl64::Image::fm_sa(*fm->f64, row_begin, row_end, string_bytes, dev_string, offset_bytes, dev_offset);
+    });
+}
+int grlbwt_fm_sa_info_get(const grlbwt_fm *fm, grlbwt_fm_sa_info *out) {
+    if (!fm || !out || !(fm->f32 || fm->f64)) return GRLBWT_EINVAL;
+    auto fill = [&](const auto &F) {
+        const auto &s = F.sinfo;
+        out->n_rows = s.n; out->n_strings = s.k; out->row_begin = s.row_begin; out->row_end = s.row_end;
+        out->string_bytes = s.string_bytes; out->offset_bytes = s.offset_bytes; out->n_written = s.written; out->form = s.form;
+        out->walk_steps = s.steps; out->longest_walk = s.longest; out->walk_lanes = s.lanes; out->lane_refills = s.refills;
+        out->scratch_bytes = s.scratch_bytes;
+    };
+    if (fm->f32) fill(*fm->f32); else fill(*fm->f64);
+    return GRLBWT_OK;
+}
 int grlbwt_fm_locate(grlbwt_ctx *ctx, const grlbwt_fm *fm, const uint64_t *dev_rows, uint64_t n_rows, uint64_t max_steps,
                      uint64_t *dev_string, uint64_t *dev_offset) {
     if (!ctx || !fm || !(fm->f32 || fm->f64)) return refuse(ctx);

@@ -1013,6 +1013,94 @@ struct FmLocateCpFn {
     }
 };
 
+// ---- the document array and the suffix array (grlbwt_fm_sa): FmLocateFn's answer for EVERY row.  A locate walks
+// each row to its string's start or to a checkpoint on its own; the LF chain of a string visits each of its rows once, so a walk per
+// string -- or per checkpoint segment -- that stores (string, offset) at every row it passes writes both arrays in n steps.  A row
+// lies on one chain, and on it is either a checkpoint or interior to one segment: one writer per entry, no atomics.
+template <int W> struct SaCell;
+template <> struct SaCell<1> { typedef u8 type; };
+template <> struct SaCell<2> { typedef u16 type; };
+template <> struct SaCell<4> { typedef u32 type; };
+template <> struct SaCell<8> { typedef u64 type; };
+template <int W> struct SaOut {      // one output of W bytes per entry
+    typename SaCell<W>::type *p;
+    GRL_DEV void put(u64 i, u64 v) const { p[i] = (typename SaCell<W>::type)v; }
+};
+template <> struct SaOut<0> {        // the output was not asked for: no store, no branch
+    GRL_DEV void put(u64, u64) const {}
+};
+struct SaWindow {                    // the rows [lo, lo + len) are stored at entry row - lo, the others are walked only
+    u64 lo, len;
+    GRL_DEV bool holds(idx_t row, u64 &at) const { at = (u64)row - lo; return at < len; }      // (wraps below lo)
+};
+struct SaLenFn {          // the length pass of form 0 (FmSidLenFn's walk, as tickets): slen[i] = the steps of string i's walk + the separator
+    struct State { idx_t row; u64 steps; };
+    LfRows lf; u32 sep; u64 n; idx_t *slen;
+    GRL_DEV bool begin(u64 i, State &st) const { st.row = (idx_t)i; st.steps = 0; return true; }
+    GRL_DEV bool step(State &st) const {
+        const RunRec r = lf.at(st.row);
+        if (r.sym == sep) return true;
+        st.row = LfRows::next(st.row, r);
+        return ++st.steps >= n;              // (an index with the locate structures has walks that end: FmSidLenFn)
+    }
+    GRL_DEV void end(u64 i, const State &st) const { slen[i] = (idx_t)(st.steps + 1); }
+};
+// Form 0, one ticket per string i: from row i, whose suffix is the separator alone at offset slen[i] - 1, store and step until the
+// row whose symbol is the separator -- offset 0 -- has been stored.  slen is read only where offsets are written.
+template <int WS, int WO>
+struct SaStringFn {
+    struct State { idx_t row; u64 str, ofs, steps; };
+    LfRows lf; u32 sep; u64 n; const idx_t *slen; SaWindow win; SaOut<WS> so; SaOut<WO> oo; idx_t *wsteps;
+    GRL_DEV bool begin(u64 i, State &st) const {
+        st.row = (idx_t)i; st.str = i; st.steps = 0; st.ofs = 0;
+        if constexpr (WO != 0) st.ofs = (u64)slen[i] - 1;
+        return true;
+    }
+    GRL_DEV bool step(State &st) const {
+        u64 at;
+        if (win.holds(st.row, at)) { so.put(at, st.str); oo.put(at, st.ofs); }
+        const RunRec r = lf.at(st.row);
+        if (r.sym == sep) return true;
+        st.row = LfRows::next(st.row, r);
+        st.ofs--;
+        return ++st.steps >= n;
+    }
+    GRL_DEV void end(u64 i, const State &st) const { wsteps[i] = (idx_t)st.steps; }
+};
+// Form 1, one ticket per checkpoint c (CpSegFn's walk with stores): from the checkpoint's row with its kept sample, store and step
+// until the separator's row has been stored or the row reached is a checkpoint -- that row is another ticket's.  A void checkpoint
+// and one on no string's chain have no sample and no walk.
+template <int WS, int WO>
+struct SaSegFn {
+    struct State { idx_t row; u64 str, ofs, steps; };
+    LfRows lf; u32 sep; Checkpoints cp; const idx_t *smp; SaWindow win; SaOut<WS> so; SaOut<WO> oo; idx_t *wsteps;
+    GRL_DEV bool begin(u64 c, State &st) const {
+        const idx_t h = smp[2 * c];
+        if (h == kCpNone) { wsteps[c] = 0; return false; }
+        st.row = (idx_t)cp.row_of(c); st.str = (u64)h; st.ofs = (u64)smp[2 * c + 1]; st.steps = 0;
+        return true;
+    }
+    GRL_DEV bool step(State &st) const {
+        u64 at;
+        if (win.holds(st.row, at)) { so.put(at, st.str); oo.put(at, st.ofs); }
+        const RunRec r = lf.at(st.row);
+        if (r.sym == sep) return true;
+        st.row = LfRows::next(st.row, r);
+        st.ofs--;
+        st.steps++;
+        return cp.index_of((u64)st.row) != ~0ull || st.steps >= cp.n;
+    }
+    GRL_DEV void end(u64 c, const State &st) const { wsteps[c] = (idx_t)st.steps; }
+};
+struct SaHeadLenIn {      // the length of string i, separator included, from its head's sample (0: the head is on no chain -- never, a head starts one)
+    const idx_t *smp;
+    GRL_DEV u64 operator()(u64 i) const { return smp[2 * i] == kCpNone ? 0ull : (u64)smp[2 * i + 1] + 1; }
+};
+struct SaStartLenFn {     // the same from the strings' start positions of an index that extracts
+    const idx_t *T; idx_t *slen;
+    GRL_DEV void operator()(u64 i) const { slen[i] = (idx_t)(T[i + 1] - T[i]); }
+};
+
 // ---- removing or keeping chosen strings (grlbwt_select_*).  The suffixes of string i are the rows on the LF chain
 // from row i to the row whose symbol is the separator; the chains of distinct strings are disjoint.  The walks set one bit per
 // chain row of the LISTED strings; the rows a run loses (or keeps) are then a difference of two ranks over those bits.
@@ -1592,6 +1680,10 @@ struct Image {
     struct MatchInfo { u64 patterns = 0, cells = 0, matched = 0, longest = 0, capped = 0, mems = 0, lanes = 0, refills = 0; };
     struct ApproxInfo { u64 patterns = 0, cells = 0, k = 0, max_hits = 0, hits = 0, by[4] = {0, 0, 0, 0}, cut = 0, steps = 0, lanes = 0, refills = 0; };
     struct LcpInfo { u64 n = 0, k = 0, lcp_bytes = 0, cap = 0, passes = 0, n_levels = 0, max_lcp = 0, n_capped = 0, tile_rows = 0, scratch_bytes = 0; };      // of the last fm_lcp
+    struct SaInfo {           // of the last fm_sa
+        u64 n = 0, k = 0, row_begin = 0, row_end = 0, string_bytes = 0, offset_bytes = 0, written = 0, form = 0, steps = 0, longest = 0, lanes = 0, refills = 0,
+            scratch_bytes = 0;
+    };
 #ifdef GRLBWT_PRIM_HIP
     static constexpr u64 kOverlapTile = prim::kExpandTile;
 #else
@@ -1622,6 +1714,7 @@ struct Image {
         mutable MatchInfo minfo;  // of the last fm_match / fm_mems
         mutable ApproxInfo ainfo; // of the last fm_approx
         mutable LcpInfo linfo;    // of the last fm_lcp
+        mutable SaInfo sinfo;     // of the last fm_sa
         mutable OverlapInfo oinfo; // of the last fm_overlaps, fm_overlaps_of or fm_overlap_targets
         u64 extract_bytes() const { return (T.n + xq.n + xc.n) * sizeof(idx_t); }
         u64 bytes() const {
@@ -2125,6 +2218,96 @@ struct Image {
         if (F.checkpoints) prim::for_each(nr, FmLocateCpFn{F.lf(), F.sid.p, F.smp.p, F.cp, F.sep, lim, rows, str, ofs}, "fm.locate_cp");
         else prim::for_each(nr, FmLocateFn{F.lf(), F.sid.p, F.sep, lim, rows, str, ofs}, "fm.locate");
         prim::sync();
+    }
+    // ---- the document array and the suffix array (functor block "the document array and the suffix array").
+    // Everything that can refuse the call runs before the first store: the arguments, then the strings' lengths -- the head
+    // samples (form 1), the start positions of an index that extracts, or a length pass (form 0, only where offsets are written)
+    // -- whose maximum has to fit the offsets' width.  Then one storing walk.  Rows on no string's chain (an image that is not
+    // the BWT of a collection, accepted where the strings' own walks end) have no position: where the lengths do not add up to
+    // n the window is first filled with FmLocateFn's "none", all bits set.  Without offsets on an index without checkpoints the
+    // lengths are known only after the walk: the fill and a second walk follow it then.
+    //   Loops: every walk is bounded by n steps (and ends sooner: fm_create has walked every string); nothing waits for another
+    //   thread, and the only atomics are the ticket word's.
+    template <class G>
+    static void sa_width(int w, G g) {
+        switch (w) {
+        case 0: g(std::integral_constant<int, 0>{}); break;
+        case 1: g(std::integral_constant<int, 1>{}); break;
+        case 2: g(std::integral_constant<int, 2>{}); break;
+        case 4: g(std::integral_constant<int, 4>{}); break;
+        default: g(std::integral_constant<int, 8>{}); break;
+        }
+    }
+    static void fm_sa(const FmIndex &F, u64 row_begin, u64 row_end, int ws, void *str, int wo, void *ofs) {
+        if (!str && !ofs) throw prim::Error(-22, "fm sa: no output");
+        if (!str) ws = 0;
+        if (!ofs) wo = 0;
+        const auto width_ok = [](int w) { return w == 1 || w == 2 || w == 4 || w == 8; };
+        if (str && !width_ok(ws)) throw prim::Error(-22, "fm sa: string_bytes is " + std::to_string(ws) + ", not 1, 2, 4 or 8");
+        if (ofs && !width_ok(wo)) throw prim::Error(-22, "fm sa: offset_bytes is " + std::to_string(wo) + ", not 1, 2, 4 or 8");
+        if (!F.locate) throw prim::Error(-22, "fm sa: the index was made without the structures for locating");
+        const u64 n = F.n, k = F.k;
+        if (row_end == ~0ull) row_end = n;
+        if (row_begin > row_end || row_end > n)
+            throw prim::Error(-22, "fm sa: rows [" + std::to_string(row_begin) + ", " + std::to_string(row_end) + ") are no window of " + std::to_string(n) + " rows");
+        if ((str && ((uintptr_t)str & (uintptr_t)(ws - 1))) || (ofs && ((uintptr_t)ofs & (uintptr_t)(wo - 1))))
+            throw prim::Error(-22, "fm sa: an output is not aligned to its width");
+        const auto fits = [](u64 v, int w) { return w == 8 || !(v >> (8 * w)); };
+        if (str && k && !fits(k - 1, ws))
+            throw prim::Error(-22, "fm sa: string number " + std::to_string(k - 1) + " does not fit string_bytes = " + std::to_string(ws));
+        SaInfo si;
+        si.n = n; si.k = k; si.row_begin = row_begin; si.row_end = row_end; si.string_bytes = (u64)ws; si.offset_bytes = (u64)wo;
+        si.written = row_end - row_begin; si.form = F.checkpoints ? 1 : 0;
+        if (row_end == row_begin) { F.sinfo = si; return; }      // (nothing to store: no walk)
+        const u64 tickets = F.checkpoints ? F.walk.m : k;
+        const bool from_starts = !F.checkpoints && wo && F.extract, len_pass = !F.checkpoints && wo && !F.extract;
+        si.scratch_bytes = (tickets + (from_starts || len_pass ? k : 0)) * sizeof(idx_t) + 16;
+        if (si.scratch_bytes > prim::mem_available())
+            throw prim::Error(-12, "fm sa: the walks need " + std::to_string(si.scratch_bytes) + " bytes of device memory, more than is free");
+        DBuf<idx_t> wsteps(tickets), slen;
+        WalkInfo wi;
+        u64 covered = ~0ull, longest = 0;                        // (covered: the rows on the strings' chains, once known)
+        if (F.checkpoints) {
+            covered = prim::reduce_sum<u64>(k, SaHeadLenIn{F.smp.p}, "sa.lengths");
+            longest = prim::reduce_max<u64>(k, SaHeadLenIn{F.smp.p}, "sa.longest");
+        } else if (wo) {
+            slen.alloc(k);
+            if (from_starts) prim::for_each(k, SaStartLenFn{F.T.p, slen.p}, "sa.lengths");
+            else walk(k, SaLenFn{F.lf(), F.sep, n, slen.p}, wi, "sa.length_pass");
+            covered = prim::reduce_sum<u64>(k, IdxIn64{slen.p}, "sa.lengths");
+            longest = prim::reduce_max<u64>(k, IdxIn64{slen.p}, "sa.longest");
+            if (len_pass) si.steps = covered - k;
+        }
+        if (wo && longest && !fits(longest - 1, wo))
+            throw prim::Error(-22, "fm sa: offset " + std::to_string(longest - 1) + " of the longest string does not fit offset_bytes = " + std::to_string(wo));
+        const SaWindow win{row_begin, row_end - row_begin};
+        const auto none = [&] {                                  // FmLocateFn's answer for a row without a position
+            if (str) prim::dev_memset(str, 0xFF, win.len * (u64)ws);
+            if (ofs) prim::dev_memset(ofs, 0xFF, win.len * (u64)wo);
+        };
+        const auto store = [&] {
+            sa_width(ws, [&](auto a) {
+                sa_width(wo, [&](auto b) {
+                    constexpr int WS = decltype(a)::value, WO = decltype(b)::value;
+                    if constexpr (WS != 0 || WO != 0) {
+                        SaOut<WS> so; SaOut<WO> oo;
+                        if constexpr (WS != 0) so.p = (typename SaCell<WS>::type *)str;
+                        if constexpr (WO != 0) oo.p = (typename SaCell<WO>::type *)ofs;
+                        if (F.checkpoints) walk(tickets, SaSegFn<WS, WO>{F.lf(), F.sep, F.cp, F.smp.p, win, so, oo, wsteps.p}, wi, "sa.segments");
+                        else walk(tickets, SaStringFn<WS, WO>{F.lf(), F.sep, n, slen.p, win, so, oo, wsteps.p}, wi, "sa.strings");
+                    }
+                });
+            });
+        };
+        if (covered != ~0ull && covered != n) none();
+        store();
+        const u64 steps = prim::reduce_sum<u64>(tickets, IdxIn64{wsteps.p}, "sa.steps");
+        if (covered == ~0ull && steps + k != n) { none(); store(); si.steps += steps; }
+        si.steps += steps;
+        si.longest = prim::reduce_max<u64>(tickets, IdxIn64{wsteps.p}, "sa.longest_walk");
+        si.lanes = wi.lanes; si.refills = wi.refills;
+        prim::sync();
+        F.sinfo = si;
     }
     // ---- extract (functor block "extracting text ranges").  Everything that can refuse the call runs before the first
     // store into `out` or `out_off`: the ranges' strings, then the plan -- pieces, cells and steps per range, scanned in scratch --

@@ -40,6 +40,7 @@ ABI_SYMBOLS = [
     "grlbwt_fm_approx", "grlbwt_fm_approx_info_get",
     "grlbwt_fm_overlaps", "grlbwt_fm_overlaps_of", "grlbwt_fm_overlap_targets", "grlbwt_fm_overlap_info_get",
     "grlbwt_fm_lcp", "grlbwt_fm_lcp_info_get",
+    "grlbwt_fm_sa", "grlbwt_fm_sa_info_get",
     "grlbwt_merge_create", "grlbwt_merge_info_get", "grlbwt_merge_emit", "grlbwt_merge_interleave", "grlbwt_merge_destroy",
     "grlbwt_merge_files",
     "grlbwt_select_create", "grlbwt_select_info_get", "grlbwt_select_emit", "grlbwt_select_rows", "grlbwt_select_destroy",
@@ -102,6 +103,11 @@ class OverlapInfo(C.Structure):
 class LcpInfo(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in ("n_rows", "n_strings", "lcp_bytes", "cap", "passes", "n_levels", "max_lcp", "n_capped",
                                           "tile_rows", "scratch_bytes")]
+
+
+class SaInfo(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("n_rows", "n_strings", "row_begin", "row_end", "string_bytes", "offset_bytes", "n_written",
+                                          "form", "walk_steps", "longest_walk", "walk_lanes", "lane_refills", "scratch_bytes")]
 
 
 class ImageStats(C.Structure):
@@ -267,6 +273,8 @@ def load_library(path=None, allow_test_standin=False):
     L.grlbwt_fm_overlap_info_get.argtypes = [vp, C.POINTER(OverlapInfo)]
     L.grlbwt_fm_lcp.argtypes = [vp, vp, u64, i32, vp, vp, vp, u64, C.POINTER(u64)]
     L.grlbwt_fm_lcp_info_get.argtypes = [vp, C.POINTER(LcpInfo)]
+    L.grlbwt_fm_sa.argtypes = [vp, vp, u64, u64, i32, vp, i32, vp]
+    L.grlbwt_fm_sa_info_get.argtypes = [vp, C.POINTER(SaInfo)]
     L.grlbwt_merge_create.argtypes = [vp, vp, u64, vp, u64, i32, u64, C.POINTER(vp)]
     L.grlbwt_merge_info_get.argtypes = [vp, C.POINTER(MergeInfo)]
     L.grlbwt_merge_emit.argtypes = [vp, vp, vp, u64]
@@ -785,6 +793,22 @@ class FmIndex:
         """The counters of the last lcp() on this index."""
         out = LcpInfo()
         rc = self.ctx.L.grlbwt_fm_lcp_info_get(self._h, C.byref(out))
+        if rc != OK:
+            raise GrlbwtError(rc, self.ctx.L.grlbwt_strerror(rc).decode())
+        return _as_dict(out)
+
+    def suffix_array(self, row_begin=0, row_end=None, string_bytes=4, string_ptr=None, offset_bytes=4, offset_ptr=None):
+        """The document array and the generalized suffix array of rows [row_begin, row_end) (None: to the last row): entry
+        p - row_begin of string_ptr / offset_ptr receives the string and the offset locate() reports for row p, as values of
+        string_bytes / offset_bytes bytes (1, 2, 4, 8).  Either pointer may be None, not both.  An index made with locate=True;
+        with checkpoints=True one walk per checkpoint segment, else one per string.  The window bounds the output, not the work."""
+        self.ctx._ck(self.ctx.L.grlbwt_fm_sa(self.ctx._h, self._h, row_begin, UINT64_MAX if row_end is None else row_end, string_bytes,
+                                             C.c_void_p(string_ptr), offset_bytes, C.c_void_p(offset_ptr)))
+
+    def sa_info(self):
+        """The counters of the last suffix_array() that succeeded on this index."""
+        out = SaInfo()
+        rc = self.ctx.L.grlbwt_fm_sa_info_get(self._h, C.byref(out))
         if rc != OK:
             raise GrlbwtError(rc, self.ctx.L.grlbwt_strerror(rc).decode())
         return _as_dict(out)

@@ -630,6 +630,64 @@ int grlbwt_fm_lcp(grlbwt_ctx *ctx, const grlbwt_fm *fm, uint64_t max_lcp /* 0: n
                   uint64_t *host_suffixes_of /* may be NULL */, uint64_t hist_capacity, uint64_t *n_levels_out);
 int grlbwt_fm_lcp_info_get(const grlbwt_fm *fm, grlbwt_fm_lcp_info *out);
 
+/* ---- the document array and the generalized suffix array of the collection: the first half of the enhanced suffix array, what
+ * BCR-style tools write beside the BWT and the LCP array.  For every row the string its suffix belongs to (DA) and the offset
+ * inside that string (GSA): the input of document listing and counting, of coloured de Bruijn graphs on top of grlbwt_fm_lcp, of
+ * string graphs on top of grlbwt_fm_overlaps, and of any tool that expects BWT + LCP + DA + SA.
+ *
+ * DEFINITION, part of the contract.  Rows are those of grlbwt_fm_count, coordinates those of grlbwt_fm_locate: the string by its
+ * number in input order, the offset counted from the string's first cell; the separator is a string's last cell, so row
+ * p < n_strings is (p, length of string p without its separator).  For p in [row_begin, row_end) entry p - row_begin of dev_string
+ * and of dev_offset holds exactly what grlbwt_fm_locate writes for row p with max_steps = UINT64_MAX, narrowed to string_bytes /
+ * offset_bytes bytes, each 1, 2, 4 or 8 and chosen independently; the outputs are aligned to their widths.  Either pointer may be
+ * NULL (its width is then ignored); both NULL is GRLBWT_EINVAL.  row_end = UINT64_MAX means n_rows.  An empty window is legal,
+ * runs no walk, writes nothing and returns GRLBWT_OK.
+ * The call needs an index made with GRLBWT_FM_LOCATE (GRLBWT_EINVAL without).  The locate structures alone give form 0, one walk
+ * per string; with GRLBWT_FM_CHECKPOINTS the call uses the kept samples, form 1, one walk per checkpoint segment.
+ * GRLBWT_FM_EXTRACT is not required (form 0 reads the lengths from its start positions where it is there).  GRLBWT_FM_LOCATE has
+ * refused an image on which a string's walk does not end; on the BWT of a collection every row lies on exactly one string's chain,
+ * and on it is a checkpoint or interior to one segment, so every entry of the window is written exactly once, by one lane, without
+ * atomics.  (An accepted image that is not the BWT of a collection may hold rows on no string's chain.  They have no position:
+ * their entries are all bits set, grlbwt_fm_locate's UINT64_MAX narrowed.  The call sees it where the strings' lengths do not add
+ * up to n_rows and fills the window before the walk.)  The call makes no handle and leaves the index, its index_bytes and every
+ * later answer as they were; it works in both position widths and on compacted alphabets (only the separator's identity matters).
+ *
+ * GRLBWT_EINVAL before the first store, with a message that names the value: a width not in {1, 2, 4, 8} for an output that is
+ * given, row_begin > row_end or row_end > n_rows, a null index, an output not aligned to its width, n_strings - 1 that does not
+ * fit string_bytes, (the longest string's length without its separator) that does not fit offset_bytes.  GRLBWT_ENOMEM before the
+ * first walk when the scratch does not fit the free memory: one position per walk, and one per string where form 0 writes offsets.
+ *
+ * COST.  A row window bounds the OUTPUT MEMORY, not the work: the rows outside it are walked and not stored.  It is there so that
+ * the arrays of a collection whose 2 to 16 bytes per row do not fit beside the index can be taken in slices.  walk_steps counts
+ * LF steps; a walk stops AT the row that holds the separator, so a string of L cells (separator included) takes L - 1 of them,
+ * and all strings together n_rows - n_strings.  Form 1: exactly n_rows - n_strings steps (a segment that ends at the next
+ * checkpoint takes the step that reaches it, a string's last segment does not step past the separator's row); the lengths and
+ * their maximum come from the head samples, a reduce and no walk -- which is also what lets the call refuse before any store.
+ * Form 0: n_rows - n_strings steps where the offsets need no length pass -- dev_offset is NULL, or the index was made with
+ * GRLBWT_FM_EXTRACT and keeps the strings' starts -- else twice that: an index made with GRLBWT_FM_LOCATE alone keeps no
+ * lengths, and a walk over every string first takes them and their maximum.  (Where such an index has rows on no chain and
+ * dev_offset is NULL, the step count reveals it after the walk: the window is filled and walked a second time.)  Form 0 is one
+ * dependent chain per string: fine for reads, hopeless for chromosomes.  Form 1 is the form for long strings.  Against
+ * grlbwt_fm_locate over all rows -- about n_rows * (mean length) / 2 steps, with checkpoints n_rows * 2^(sample_bits - 1) --
+ * both forms take one step per row.  The walks obey GRLBWT_WALK_LANES.
+ * OUT OF SCOPE: the inverse suffix array, document listing or counting over row ranges, a command-line flag, a multi-GPU form,
+ * keeping the arrays inside the index.
+ * grlbwt_fm_sa_info_get: the counters of the last grlbwt_fm_sa that succeeded on the index. */
+typedef struct grlbwt_fm_sa_info {
+    uint64_t n_rows, n_strings;
+    uint64_t row_begin, row_end;            /* the window of the last call, end resolved */
+    uint64_t string_bytes, offset_bytes;    /* 0 for an output that was not asked for */
+    uint64_t n_written;                     /* row_end - row_begin */
+    uint64_t form;                          /* 0: one walk per string, 1: one walk per checkpoint segment */
+    uint64_t walk_steps;                    /* LF steps of all walks of the call, a length pass included */
+    uint64_t longest_walk;                  /* LF steps of the longest single walk (string or segment) of the storing launch */
+    uint64_t walk_lanes, lane_refills;      /* of the storing launch, as in grlbwt_walk_info */
+    uint64_t scratch_bytes;
+} grlbwt_fm_sa_info;
+int grlbwt_fm_sa(grlbwt_ctx *ctx, const grlbwt_fm *fm, uint64_t row_begin, uint64_t row_end /* UINT64_MAX: n_rows */,
+                 int string_bytes, void *dev_string /* may be NULL */, int offset_bytes, void *dev_offset /* may be NULL */);
+int grlbwt_fm_sa_info_get(const grlbwt_fm *fm, grlbwt_fm_sa_info *out);
+
 /* ---- merging two images: the image of the collection "strings of A, then strings of B" from the images of A and B, without the
  * texts -- a collection larger than one build is built in batches and folded together, a batch of new strings is added to an
  * existing image.  String i of B becomes string n_strings_a + i.  When A and B were built by this engine with cells of cell_bytes,
