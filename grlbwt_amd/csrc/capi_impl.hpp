@@ -2301,6 +2301,33 @@ int grlbwt_fm_sa_info_get(const grlbwt_fm *fm, grlbwt_fm_sa_info *out) {
     if (fm->f32) fill(*fm->f32); else fill(*fm->f64);
     return GRLBWT_OK;
 }
+int grlbwt_fm_kmers(grlbwt_ctx *ctx, const grlbwt_fm *fm, uint64_t k, uint64_t min_count, uint64_t max_count, uint64_t row_begin, uint64_t row_end,
+                    int cell_bytes, void *dev_cells, uint64_t *dev_lo, uint64_t *dev_count, uint64_t capacity, uint64_t *n_kmers_out,
+                    uint64_t *host_spectrum, uint64_t spectrum_bins) {
+    if (n_kmers_out) *n_kmers_out = 0;
+    if (!ctx || !fm || !(fm->f32 || fm->f64)) return refuse(ctx);
+    uint64_t n = 0;
+    const int rc = guarded(ctx, [&] {
+        if (fm->f32) grl32::Image::fm_kmers(*fm->f32, k, min_count, max_count, row_begin, row_end, cell_bytes, dev_cells, dev_lo, dev_count, capacity, n,
+                                            n_kmers_out != nullptr, host_spectrum, spectrum_bins);
+        else grl64::Image::fm_kmers(*fm->f64, k, min_count, max_count, row_begin, row_end, cell_bytes, dev_cells, dev_lo, dev_count, capacity, n,
+                                    n_kmers_out != nullptr, host_spectrum, spectrum_bins);
+    });
+    if (n_kmers_out) *n_kmers_out = n;
+    return rc;
+}
+int grlbwt_fm_kmer_info_get(const grlbwt_fm *fm, grlbwt_fm_kmer_info *out) {
+    if (!fm || !out || !(fm->f32 || fm->f64)) return GRLBWT_EINVAL;
+    auto fill = [&](const auto &F) {
+        const auto &i = F.kinfo;
+        out->k = i.k; out->n_rows = i.n; out->n_strings = i.n_strings; out->n_distinct = i.n_distinct; out->n_windows = i.n_windows;
+        out->n_selected = i.n_selected; out->largest_count = i.largest_count; out->passes = i.passes; out->length_passes = i.length_passes;
+        out->forward_steps = i.forward_steps; out->tile_rows = i.tile_rows; out->tile_kmers = i.tile_kmers; out->stage_bytes = i.stage_bytes;
+        out->scratch_bytes = i.scratch_bytes;
+    };
+    if (fm->f32) fill(*fm->f32); else fill(*fm->f64);
+    return GRLBWT_OK;
+}
 int grlbwt_fm_locate(grlbwt_ctx *ctx, const grlbwt_fm *fm, const uint64_t *dev_rows, uint64_t n_rows, uint64_t max_steps,
                      uint64_t *dev_string, uint64_t *dev_offset) {
     if (!ctx || !fm || !(fm->f32 || fm->f64)) return refuse(ctx);

@@ -10,7 +10,7 @@
 // grlbwt_select_* calls (reference: scripts/*.cpp of ddiazdom/grlBWT):
 //   records and the scripts/ consumers   ImageRecs, plain / rle / stats / split_runs
 //   inversion                            per position (invert_t) and per run (RunIndex, invert_runs_t)
-//   FM index                             count, locate, match / MEMs, extract, the LCP array (FmLcp)
+//   FM index                             count, locate, match / MEMs, extract, the LCP array (FmLcp), the k-mer table (fm_kmers)
 //   checkpointed LF walks                lf_checkpoints and the walks cut at checkpoints
 //   merge, select                        ImageMerge, ImageSelect
 // The pieces every consumer shares, one copy each: ImageRecs (the record layout), image_header / check_cell_bytes /
@@ -307,6 +307,7 @@ template <> struct FmKeyT<4> {                 // symbol << 32 | start: one word
     u64 v;
     GRL_DEV static FmKeyT make(u32 sym, u64 start) { return FmKeyT{(u64)sym << 32 | start}; }
     GRL_DEV u32 sym() const { return (u32)(v >> 32); }
+    u32 host_sym() const { return (u32)(v >> 32); }           // (of a key copied to the host)
     GRL_DEV u64 start() const { return v & 0xFFFFFFFFull; }
     GRL_DEV bool below(u32 c, u64 p) const { return v < ((u64)c << 32 | p); }       // sorts in front of (c, p)
 };
@@ -314,6 +315,7 @@ template <> struct alignas(16) FmKeyT<8> {
     u64 st, sy;
     GRL_DEV static FmKeyT make(u32 sym, u64 start) { return FmKeyT{start, (u64)sym}; }
     GRL_DEV u32 sym() const { return (u32)sy; }
+    u32 host_sym() const { return (u32)sy; }
     GRL_DEV u64 start() const { return st; }
     GRL_DEV bool below(u32 c, u64 p) const { return sy < (u64)c || (sy == (u64)c && st < p); }
 };
@@ -1376,6 +1378,86 @@ struct LcpStoreFn {         // prim::for_each_set_bit: the value v, in the outpu
     }
 };
 
+// ---- the distinct k-mers with their counts (grlbwt_fm_kmers).  After the LCP passes capped at k, B marks the rows
+// with LCP < k: the boundaries of the k-mer intervals.  A boundary whose suffix has fewer than k cells heads no k-mer (Short, the
+// OR of the generations of S up to k - 1), so the heads are H = B & ~Short and count(p) is the distance from head p to the next
+// bit of B, or to n.  That next bit is in p's own word or in the next non-empty word of B: NZ holds one bit per non-empty word,
+// with ranks, and nzlist the non-empty words in ascending order -- O(1) per head whatever the gap, no scan over it.
+//   Bounds: p < n is a set bit of B, so word p / 64 is non-empty and its rank r in NZ has nzlist[r] = p / 64; r + 1 < nnz is
+//   tested before nzlist[r + 1] is read, and that word is non-empty: ctz is defined.  B has no bit at or behind n.
+struct KmerOrFn {            // acc |= cur, word by word
+    const u64 *cur; u64 *acc;
+    GRL_DEV void operator()(u64 i) const { acc[i] |= cur[i]; }
+};
+struct KmerHeadsFn {         // H = B & ~Short
+    const u64 *B; const u64 *sh; u64 *H;
+    GRL_DEV void operator()(u64 i) const { H[i] = B[i] & ~sh[i]; }
+};
+struct KmerWordPred {        // NZ: the words of B that hold a bit
+    const u64 *B;
+    GRL_DEV bool operator()(u64 w) const { return B[w] != 0; }
+};
+struct KmerWordListFn {      // prim::for_each_set_bit over NZ: the r-th non-empty word
+    idx_t *nzlist;
+    GRL_DEV void operator()(u64 w, u64 r) const { nzlist[r] = (idx_t)w; }
+};
+struct KmerCountFn {         // count(p) of a head p
+    const u64 *B; const u64 *NZ; const idx_t *nzbase; const idx_t *nzlist; u64 nnz, n;
+    GRL_DEV u64 operator()(u64 p) const {
+        const u64 w = p >> 6;
+        const u64 rest = (B[w] >> (p & 63)) >> 1;
+        u64 nx = n;
+        if (rest) {
+            nx = p + 1 + (u64)__builtin_ctzll(rest);
+        } else {
+            const u64 r = (u64)nzbase[w >> 6] + (u64)__builtin_popcountll(NZ[w >> 6] & ((1ull << (w & 63)) - 1ull)) + 1;
+            if (r < nnz) { const u64 x = (u64)nzlist[r]; nx = x * 64 + (u64)__builtin_ctzll(B[x]); }
+        }
+        return nx - p;
+    }
+};
+struct KmerFilter {          // the table's rows: row_begin <= lo < row_end, cmin <= count <= cmax
+    u64 rb, re, cmin, cmax;
+    GRL_DEV bool operator()(u64 p, u64 c) const { return p >= rb && p < re && c >= cmin && c <= cmax; }
+};
+struct KmerSelPred {
+    const u64 *H; KmerCountFn cnt; KmerFilter flt;
+    GRL_DEV bool operator()(u64 p) const { return lcp_bit(H, p) && flt(p, cnt(p)); }
+};
+struct KmerWindowsIn {       // count(p) at a head, 0 elsewhere: their sum is the number of windows, their maximum the largest count
+    const u64 *H; KmerCountFn cnt;
+    GRL_DEV u64 operator()(u64 p) const { return lcp_bit(H, p) ? cnt(p) : 0ull; }
+};
+struct KmerSpectrumFn {      // the serial form of the spectrum: prim::for_each_set_bit over H (the device form: prim::kmer_spectrum)
+    KmerCountFn cnt; u64 *bins; u64 last;
+    GRL_DEV void operator()(u64 p, u64) const { const u64 c = cnt(p); prim::atomic_add(&bins[c < last ? c : last], (u64)1); }
+};
+// The forward step: row q >= n_strings lies in sorted run j, its suffix starts with key[j].sym() and goes on with the suffix of
+// row key[j].start() + (q - slf[j]).  q < n gives j < R and a row inside run j, so the next q is below n again: the walk reads in
+// bounds on any image, and on the BWT of a collection a head's k steps stay at rows >= n_strings (its suffix has k cells).
+struct KmerStepFn {
+    const RankCell *frc; const FmKey *key; const idx_t *slf; const u64 *alpha;
+    GRL_DEV u64 operator()(u64 &q) const {
+        const u64 j = run_of_row(frc, q);
+        const FmKey kj = key[j];
+        q = kj.start() + (q - (u64)slf[j]);
+        const u64 c = (u64)kj.sym();
+        return alpha ? alpha[c] : c;
+    }
+};
+template <class cell_t>
+struct KmerEmitFn {          // the generic decode, prim::for_each_set_bit over the selected bits: one lane per entry stores its own cells
+    KmerStepFn step; KmerCountFn cnt; u64 k; cell_t *cells; u64 *lo; u64 *count;
+    GRL_DEV void operator()(u64 p, u64 e) const {
+        if (lo) lo[e] = p;
+        if (count) count[e] = cnt(p);
+        if (cells) {
+            u64 q = p;
+            for (u64 t = 0; t < k; t++) cells[e * k + t] = (cell_t)step(q);
+        }
+    }
+};
+
 struct Image {
     // ---- opening an image: the one parse of the 16 header bytes, the one test of a cell width, the one dispatch on it -------
     struct ImageHeader {
@@ -1692,6 +1774,16 @@ struct Image {
     struct OverlapInfo {      // of the last fm_overlaps / fm_overlaps_of (the first eight) or fm_overlap_targets (ranges, entries)
         u64 patterns = 0, cells = 0, hits = 0, targets = 0, longest = 0, steps = 0, lanes = 0, refills = 0, ranges = 0, entries = 0, tile = kOverlapTile;
     };
+#ifdef GRLBWT_PRIM_HIP
+    static constexpr u64 kKmerTileRows = prim::kKmerTile, kKmerTileEntries = prim::kKmerEntries, kKmerStageBytes = prim::kKmerStage;
+#else
+    static constexpr u64 kKmerTileRows = 4096, kKmerTileEntries = 256, kKmerStageBytes = 16384;      // (the serial form has no tiles: the figures the device library reports)
+#endif
+    static constexpr u64 kKmerMaxBins = 16384;
+    struct KmerInfo {         // of the last fm_kmers that got as far as counting
+        u64 k = 0, n = 0, n_strings = 0, n_distinct = 0, n_windows = 0, n_selected = 0, largest_count = 0, passes = 0, length_passes = 0, forward_steps = 0;
+        u64 tile_rows = kKmerTileRows, tile_kmers = kKmerTileEntries, stage_bytes = kKmerStageBytes, scratch_bytes = 0;
+    };
     struct FmIndex {
         u64 n = 0, R = 0, k = 0, sigma = 0, sepval = 0;
         u32 sep = 0, top_entries = 0;
@@ -1715,6 +1807,7 @@ struct Image {
         mutable ApproxInfo ainfo; // of the last fm_approx
         mutable LcpInfo linfo;    // of the last fm_lcp
         mutable SaInfo sinfo;     // of the last fm_sa
+        mutable KmerInfo kinfo;   // of the last fm_kmers that got as far as counting
         mutable OverlapInfo oinfo; // of the last fm_overlaps, fm_overlaps_of or fm_overlap_targets
         u64 extract_bytes() const { return (T.n + xq.n + xc.n) * sizeof(idx_t); }
         u64 bytes() const {
@@ -2137,7 +2230,10 @@ struct Image {
             if (out && n_new) prim::for_each_set_bit<idx_t>(n, B, brank.p, LcpStoreFn{out, w, v}, "lcp.values");
             n_suf = prim::reduce_sum<u64>((n + 63) / 64, PopcIn{Sn}, "lcp.suffixes");
         }
-        void run(const FmIndex &F, u64 cap, void *out, int w, LcpInfo &li, std::vector<u64> &rows_at, std::vector<u64> &suf) {
+        // (acc, for fm_kmers: a bit-vector that every generation of S is OR-ed into; the last generations stay in Bfin / Sfin,
+        // the used-up ones in Bold / Sold)
+        u64 *Bfin = nullptr, *Sfin = nullptr, *Bold = nullptr, *Sold = nullptr;
+        void run(const FmIndex &F, u64 cap, void *out, int w, LcpInfo &li, std::vector<u64> &rows_at, std::vector<u64> &suf, u64 *acc = nullptr) {
             rows_at.clear(); suf.clear();
             b0.zero(); b1.zero(); s0.zero(); s1.zero();
             u64 *B = b0.p, *Bn = b1.p, *S = s0.p, *Sn = s1.p;
@@ -2167,7 +2263,9 @@ struct Image {
                 rows_at.push_back(n_new); suf.push_back(n_suf);
                 set += n_new; passes++;
                 std::swap(B, Bn); std::swap(S, Sn);
+                if (acc) prim::for_each((n + 63) / 64, KmerOrFn{S, acc}, "lcp.lengths_or");
             }
+            Bfin = B; Sfin = S; Bold = Bn; Sold = Sn;
             li.passes = passes; li.n_levels = passes + 1; li.n_capped = n - set;
             li.max_lcp = li.n_capped ? cap : passes;
             if (out && li.n_capped) {     // the rows still open: their LCP is cap or more
@@ -2209,6 +2307,107 @@ struct Image {
             throw prim::Error(-22, "fm lcp: " + std::to_string(n_levels) + " levels, more than the histograms hold");
         if (rows_at) std::memcpy(rows_at, ra.data(), n_levels * 8);
         if (suffixes_of) std::memcpy(suffixes_of, su.data(), n_levels * 8);
+    }
+    // ---- the distinct k-mers with their counts (functor block "the distinct k-mers with their counts").  Everything
+    // that can refuse the call runs before the first store: the arguments, the memory, the passes (an image that is not the BWT
+    // of a collection), the capacity.  Then the spectrum is copied to the host and the table is decoded.
+    //   Loops: at most k - 1 LCP passes, each of which sets a row or ends the call; at most k - 1 length passes, which end with the
+    //   first generation of S that is empty (no string has that many cells, so none has more); a head's count takes no loop
+    //   (KmerCountFn); the decode takes k steps per entry.  Nothing waits for another thread; the only atomics are the
+    //   histogram's (LDS, and one per used bin and workgroup at the flush).
+    static void fm_kmers(const FmIndex &F, u64 k, u64 min_count, u64 max_count, u64 row_begin, u64 row_end, int w, void *cells, u64 *lo, u64 *count,
+                         u64 capacity, u64 &n_kmers, bool want_n, u64 *host_spectrum, u64 bins) {
+        n_kmers = 0;
+        if (k == 0) throw prim::Error(-22, "fm kmers: k is 0");
+        if (!(w == 1 || w == 2 || w == 4 || w == 8)) throw prim::Error(-22, "fm kmers: cell_bytes is " + std::to_string(w) + ", not 1, 2, 4 or 8");
+        if (!cells && !lo && !count && !host_spectrum && !want_n) throw prim::Error(-22, "fm kmers: no output");
+        if (host_spectrum && (bins == 0 || bins > kKmerMaxBins))
+            throw prim::Error(-22, "fm kmers: " + std::to_string(bins) + " spectrum bins, not 1 to " + std::to_string(kKmerMaxBins));
+        const u64 n = F.n;
+        if (row_end > n) row_end = n;                            // (UINT64_MAX: n_rows)
+        if (row_begin > row_end)
+            throw prim::Error(-22, "fm kmers: rows [" + std::to_string(row_begin) + ", " + std::to_string(row_end) + ") are no window of " + std::to_string(n) + " rows");
+        if (cells && w < 8 && F.R) {
+            const u64 top = F.alpha.p ? F.alpha.get(F.alpha.n - 1) : (u64)F.key.get(F.R - 1).host_sym();
+            if (top >> (8 * w)) throw prim::Error(-22, "fm kmers: the image's largest symbol " + std::to_string(top) + " does not fit cell_bytes = " + std::to_string(w));
+        }
+        if ((cells && ((uintptr_t)cells & (uintptr_t)(w - 1))) || ((uintptr_t)lo & 7) || ((uintptr_t)count & 7))
+            throw prim::Error(-22, "fm kmers: an output is not aligned to its width");
+        const bool table = cells || lo || count;
+        const u64 nb = host_spectrum ? bins : 1;
+        KmerInfo ki;
+        ki.k = k; ki.n = n; ki.n_strings = F.k;
+        std::vector<u64> spec(nb, 0);
+        if (n == 0) { F.kinfo = ki; if (host_spectrum) std::memcpy(host_spectrum, spec.data(), nb * 8); return; }
+        const u64 nw = FmLcp::words_of(n), nwords = (n + 63) / 64, nzw = nwords / 64 + 2;
+        ki.scratch_bytes = FmLcp::scratch_bytes(n) + nw * 8 + nzw * 8 + (nzw + 1 + nwords) * sizeof(idx_t) + nb * 8;
+        if (n >= ((u64)1 << 62) || ki.scratch_bytes > prim::mem_available())
+            throw prim::Error(-12, "fm kmers: the passes need " + std::to_string(ki.scratch_bytes) + " bytes of device memory, more than is free");
+        FmLcp L;
+        L.alloc(F);
+        DBuf<u64> sh(nw);
+        sh.zero();
+        prim::bitvector_from_pred(n, LcpBelowPred{F.k}, sh.p, "kmer.terminators");
+        LcpInfo li;
+        std::vector<u64> ra, su;
+        L.run(F, k, nullptr, 8, li, ra, su, sh.p);               // B: the rows with LCP < k
+        ki.passes = li.passes;
+        {   // the suffixes of passes + 1 .. k - 1 cells: copy-only passes of S, until a generation is empty
+            u64 *S = L.Sfin, *Sn = L.Sold, last = su.back();
+            for (u64 l = li.passes + 1; l < k && last; l++) {
+                prim::bitvector_from_pred(n, LcpLenPred{L.rows(F, nullptr, S)}, Sn, "kmer.lengths");
+                last = prim::reduce_sum<u64>(nwords, PopcIn{Sn}, "kmer.suffixes");
+                prim::for_each(nwords, KmerOrFn{Sn, sh.p}, "kmer.lengths_or");
+                std::swap(S, Sn);
+                ki.length_passes++;
+            }
+        }
+        const u64 *B = L.Bfin;
+        u64 *H = L.Bold, *sel = L.Sfin;
+        prim::for_each(nwords, KmerHeadsFn{B, sh.p, H}, "kmer.heads");
+        sh.release();
+        DBuf<u64> NZ(nzw);
+        DBuf<idx_t> nzbase(nzw + 1), nzlist;
+        NZ.zero();
+        prim::bitvector_from_pred(nwords, KmerWordPred{B}, NZ.p, "kmer.words");
+        const u64 nnz = (u64)prim::exclusive_scan<idx_t>(nzw, PopcIn{NZ.p}, nzbase.p, true, "kmer.word_ranks");
+        nzlist.alloc(nnz);
+        prim::for_each_set_bit<idx_t>(nwords, NZ.p, nzbase.p, KmerWordListFn{nzlist.p}, "kmer.word_list");
+        const KmerCountFn cnt{B, NZ.p, nzbase.p, nzlist.p, nnz, n};
+        DBuf<u64> dbins(nb);
+#ifdef GRLBWT_PRIM_HIP
+        prim::kmer_spectrum(n, H, cnt, (u32)nb, dbins.p, ki.n_distinct, ki.n_windows, ki.largest_count);
+#else
+        dbins.zero();
+        (void)prim::exclusive_scan<idx_t>(nw, PopcIn{H}, L.brank.p, true, "kmer.head_ranks");
+        prim::for_each_set_bit<idx_t>(n, H, L.brank.p, KmerSpectrumFn{cnt, dbins.p, nb - 1}, "kmer.spectrum");
+        ki.n_distinct = prim::reduce_sum<u64>(nwords, PopcIn{H}, "kmer.heads_sum");
+        ki.n_windows = prim::reduce_sum<u64>(n, KmerWindowsIn{H, cnt}, "kmer.windows");
+        ki.largest_count = prim::reduce_max<u64>(n, KmerWindowsIn{H, cnt}, "kmer.largest");
+#endif
+        prim::d2h(spec.data(), dbins.p, nb * 8);
+        const KmerFilter flt{row_begin, row_end, min_count ? min_count : 1, max_count ? max_count : ~0ull};
+        prim::dev_memset(sel, 0, nw * 8);
+        prim::bitvector_from_pred(n, KmerSelPred{H, cnt, flt}, sel, "kmer.select");
+        ki.n_selected = (u64)prim::exclusive_scan<idx_t>(nw, PopcIn{sel}, L.brank.p, true, "kmer.select_ranks");
+        ki.forward_steps = cells ? ki.n_selected * k : 0;
+        prim::sync();
+        F.kinfo = ki;
+        n_kmers = ki.n_selected;
+        if (table && n_kmers > capacity)
+            throw prim::Error(-22, "fm kmers: " + std::to_string(n_kmers) + " k-mers, more than the output arrays hold");
+        if (host_spectrum) std::memcpy(host_spectrum, spec.data(), nb * 8);
+        if (!table || n_kmers == 0) return;
+        const KmerStepFn step{L.frc.p, F.key.p, F.slf.p, F.alpha.p};
+        with_cell(w, [&](auto c) {
+            typedef decltype(c) cell_t;
+#ifdef GRLBWT_PRIM_HIP
+            if (prim::sw().dev_kmer_decode != 'f') prim::kmer_decode<cell_t, idx_t>(n_kmers, k, sel, L.brank.p, n, step, cnt, (cell_t *)cells, lo, count);
+            else
+#endif
+                prim::for_each_set_bit<idx_t>(n, sel, L.brank.p, KmerEmitFn<cell_t>{step, cnt, k, (cell_t *)cells, lo, count}, "kmer.decode_plain");
+        });
+        prim::sync();
     }
     static void fm_locate(const FmIndex &F, const u64 *rows, u64 nr, u64 max_steps, u64 *str, u64 *ofs) {
         if (!F.locate) throw prim::Error(-22, "fm locate: the index was made without the structures for locating");

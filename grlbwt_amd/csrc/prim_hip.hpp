@@ -2517,6 +2517,161 @@ inline void expand_ranges(u64 nr, u64 total, const u64 *eoff, const u64 *tlo, co
     after_launch(name);
 }
 
+// ------------------------------------------------------------------ k-mer spectrum and table (grlbwt_fm_kmers)
+// The spectrum: bins[min(count(p), nbins - 1)]++ over the set bits p of H, with the number of heads, the sum of their counts and
+// the largest one.  One lane per row, a wave per word; a workgroup walks tiles of kKmerTile rows grid-stride and keeps its
+// histogram in LDS (nbins u32 words of dynamic LDS, 64 KB at the most), which it adds to the device bins once, at its end, one
+// atomic per bin it has used: no device word that every lane adds to.  The three sums go per wave through shuffles into
+// part[3 * (block * waves + wave)], which two reduces and a maximum put together.
+//   Bounds: a lane evaluates cnt(p) only for p < n with its bit of H set (H has no bit at or behind n; the word index stays below
+//   ceil(n / 64)); a bin index is min(c, nbins - 1).  A workgroup takes at most 2^31 rows (the launch sees to it), so a u32 bin
+//   cannot wrap.  Loops: the tiles of a workgroup, the words of a wave, the bins: all counted.  The two barriers are reached by
+//   every thread; no workgroup waits for another.
+static constexpr int kKmerTile = 4096;
+static constexpr u32 kKmerMaxBins = 16384;
+template <class CNT>
+__global__ void __launch_bounds__(kBlock) k_kmer_spectrum(u64 n, const u64 *H, CNT cnt, u32 nbins, u64 *bins, u64 *part) {
+    extern __shared__ u32 s_kbins[];
+    constexpr int NW = kBlock / 64, WPW = kKmerTile / 64 / NW;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const u64 nwords = (n + 63) >> 6, ntiles = (n + kKmerTile - 1) / kKmerTile;
+    for (u32 i = threadIdx.x; i < nbins; i += kBlock) s_kbins[i] = 0;
+    __syncthreads();
+    u64 heads = 0, sum = 0, mx = 0;
+    for (u64 t = blockIdx.x; t < ntiles; t += gridDim.x) {
+        const u64 x0 = t * (kKmerTile / 64) + (u64)wave * WPW;
+        for (int i = 0; i < WPW && x0 + (u64)i < nwords; i++) {
+            const u64 word = H[x0 + (u64)i];
+            if ((word >> lane) & 1ull) {
+                const u64 c = cnt((x0 + (u64)i) * 64 + (u64)lane);
+                atomicAdd(&s_kbins[c < (u64)(nbins - 1) ? (u32)c : nbins - 1], 1u);
+                sum += c;
+                mx = c > mx ? c : mx;
+            }
+            heads += (u64)__popcll(word);            // (wave-uniform: every lane holds the wave's number)
+        }
+    }
+    for (int d = 32; d >= 1; d >>= 1) {
+        sum += __shfl_xor(sum, d);
+        const u64 o = __shfl_xor(mx, d);
+        mx = o > mx ? o : mx;
+    }
+    if (lane == 0) {
+        u64 *q = part + 3 * ((u64)blockIdx.x * NW + (u64)wave);
+        q[0] = heads; q[1] = sum; q[2] = mx;
+    }
+    __syncthreads();
+    for (u32 i = threadIdx.x; i < nbins; i += kBlock) {
+        const u32 v = s_kbins[i];
+        if (v) atomic_add(&bins[i], (u64)v);
+    }
+}
+struct KmerPartIn {
+    const u64 *part; int f;
+    GRL_DEV u64 operator()(u64 i) const { return part[3 * i + (u64)f]; }
+};
+// bins: nbins device words, zeroed here; returns the heads, the sum of their counts and the largest
+template <class CNT>
+inline void kmer_spectrum(u64 n, const u64 *H, CNT cnt, u32 nbins, u64 *bins, u64 &heads, u64 &sum, u64 &largest) {
+    heads = sum = largest = 0;
+    if (nbins == 0 || nbins > kKmerMaxBins) throw Error(-22, "kmer_spectrum: 1 to 16384 bins");
+    dev_memset(bins, 0, (u64)nbins * 8);
+    if (n == 0) return;
+    const u64 ntiles = (n + kKmerTile - 1) / kKmerTile;
+    u64 blocks = (u64)rt().num_cus * 4;
+    const u64 least = (n >> 31) + 1;                 // a workgroup's rows stay below 2^31
+    if (blocks < least) blocks = least;
+    if (blocks > ntiles) blocks = ntiles;
+    if (blocks > 0x7FFFFFFFull) throw Error(-75, "kmer_spectrum: more rows than one launch takes");
+    const u64 nparts = blocks * (kBlock / 64);
+    u64 *part = (u64 *)dev_alloc(nparts * 24);
+    prof_begin("kmer.spectrum", n / 8);
+    hipLaunchKernelGGL((k_kmer_spectrum<CNT>), dim3((unsigned)blocks), dim3(kBlock), (size_t)nbins * 4, rt().stream, n, H, cnt, nbins, bins, part);
+    prof_end();
+    after_launch("kmer.spectrum");
+    heads = reduce_sum<u64>(nparts, KmerPartIn{part, 0}, "kmer.heads");
+    sum = reduce_sum<u64>(nparts, KmerPartIn{part, 1}, "kmer.windows");
+    largest = reduce_max<u64>(nparts, KmerPartIn{part, 2}, "kmer.largest");
+    dev_free(part);
+}
+
+// The table: entry e of the selected k-mers (the e-th set bit of `sel`, whose exclusive word ranks are selrank[0 .. nwords]) gets
+// lo[e] = its row p, count[e] = cnt(p) and the k cells cells[e * k .. (e + 1) * k), the values of k forward steps from p
+// (step(q) returns the cell of row q and moves q on).  A workgroup takes a tile of kKmerEntries consecutive entries, one per lane.
+// Threads 0 and 1 find the words of the tile's first and last entry by a search over selrank; every lane then finds its own word
+// between the two (a dense selection leaves it a handful of words) and its bit inside the word.  The lanes walk their k
+// dependent steps in chunks of `ch` steps, ch = min(k, kKmerStage / (kKmerEntries * sizeof(cell_t))), and stage the chunk in LDS as
+// [entry][step]; the tile's span of `cells` is then stored with consecutive lanes on consecutive LDS slots -- consecutive addresses
+// within an entry's chunk, and over the whole tile when one chunk holds the k steps (a lane that stores its own cells one by one
+// writes with stride k).  lo and count are dense per tile.  One writer per entry, no atomics.
+//   LDS: kKmerStage bytes of cells and two words.  Bounds: e < e1 <= total gives a word w with selrank[w] <= e < selrank[w + 1],
+//   w < nwords, whose (e - selrank[w])-th set bit exists; an LDS slot is ent * ch + t < kKmerEntries * ch <= kKmerStage / sizeof(cell_t);
+//   cells are stored at (e0 + ent) * k + t0 + t with ent < e1 - e0 and t0 + t < k.
+//   Loops: the searches (at most 64 halvings each), the bits of a word (at most 63), the k steps in ceil(k / ch) chunks.  Every
+//   thread reaches every barrier: the chunk loop and its bounds are uniform, and a lane without an entry only skips the walk.
+static constexpr int kKmerEntries = kBlock;
+static constexpr int kKmerStage = 16384;
+template <class IDX>
+__device__ __forceinline__ u64 kmer_word_of(const IDX *selrank, u64 a, u64 b, u64 e) {       // the last w in [a, b] with selrank[w] <= e
+    for (int it = 0; it < 64 && a < b; it++) {
+        const u64 mid = (a + b + 1) >> 1;
+        if ((u64)selrank[mid] <= e) a = mid; else b = mid - 1;
+    }
+    return a;
+}
+template <class cell_t, class IDX, class STEP, class CNT>
+__global__ void __launch_bounds__(kBlock) k_kmer_decode(u64 total, u64 k, u32 ch, const u64 *sel, const IDX *selrank, u64 nwords, STEP step, CNT cnt,
+                                                        cell_t *cells, u64 *lo, u64 *count) {
+    __shared__ __attribute__((aligned(16))) cell_t s_stage[kKmerStage / sizeof(cell_t)];
+    __shared__ u64 s_w[2];
+    const u32 tid = threadIdx.x;
+    const u64 e0 = (u64)blockIdx.x * kKmerEntries;
+    const u64 e1 = e0 + kKmerEntries < total ? e0 + kKmerEntries : total;
+    const u32 cntile = (u32)(e1 - e0);
+    if (tid < 2) s_w[tid] = kmer_word_of(selrank, 0, nwords - 1, tid == 0 ? e0 : e1 - 1);
+    __syncthreads();
+    const u64 e = e0 + tid;
+    const bool has = e < e1;
+    u64 q = 0;
+    if (has) {
+        const u64 w = kmer_word_of(selrank, s_w[0], s_w[1], e);
+        u64 word = sel[w];
+        const u32 r = (u32)(e - (u64)selrank[w]);
+        for (u32 i = 0; i < r && i < 63u; i++) word &= word - 1;
+        q = w * 64 + (u64)__builtin_ctzll(word | (1ull << 63));
+        if (lo) lo[e] = q;
+        if (count) count[e] = cnt(q);
+    }
+    if (cells) {
+        for (u64 t0 = 0; t0 < k; t0 += ch) {
+            const u32 m = k - t0 < (u64)ch ? (u32)(k - t0) : ch;
+            if (has)
+                for (u32 t = 0; t < m; t++) s_stage[tid * m + t] = (cell_t)step(q);
+            __syncthreads();
+            const u32 slots = cntile * m;
+            if (m == k) {
+                for (u32 i = tid; i < slots; i += kBlock) cells[e0 * k + i] = s_stage[i];
+            } else {
+                for (u32 i = tid; i < slots; i += kBlock) { const u32 ent = i / m; cells[(e0 + ent) * k + t0 + (i - ent * m)] = s_stage[i]; }
+            }
+            __syncthreads();
+        }
+    }
+}
+template <class cell_t, class IDX, class STEP, class CNT>
+inline void kmer_decode(u64 total, u64 k, const u64 *sel, const IDX *selrank, u64 nbits, STEP step, CNT cnt, cell_t *cells, u64 *lo, u64 *count) {
+    if (total == 0) return;
+    const u64 tiles = (total + kKmerEntries - 1) / kKmerEntries;
+    if (tiles > 0x7FFFFFFFull) throw Error(-75, "kmer_decode: more entries than one launch takes");
+    const u64 room = (u64)kKmerStage / (kKmerEntries * sizeof(cell_t));
+    const u32 ch = (u32)(k < room ? k : room);
+    prof_begin("kmer.decode", total * (cells ? k * sizeof(cell_t) : 0) + total * 16);
+    hipLaunchKernelGGL((k_kmer_decode<cell_t, IDX, STEP, CNT>), dim3((unsigned)tiles), dim3(kBlock), 0, rt().stream, total, k, ch, sel, selrank,
+                       (nbits + 63) / 64, step, cnt, cells, lo, count);
+    prof_end();
+    after_launch("kmer.decode");
+}
+
 // Digit plan of an LSD sort over `bits` key bits: the fewest passes with digits of at most rs_max_digit() bits, widths as equal
 // as possible (at 9: 51 bits = 9,9,9,8,8,8; 54 = 6 x 9; 18 = 9,9).  GRLBWT_SORT_DIGIT=8|9|10 sets the widest digit; the default
 // stays 8: measured on the 10 GB build (profiles/r03), 9- and 10-bit digits save a pass over the 51-56-bit suffix keys and the

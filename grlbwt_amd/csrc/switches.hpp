@@ -92,6 +92,7 @@
     X(GRLBWT_DEV_SM1_SPT, dev_sm1_spt, int, 0, "segments per thread of the one-walk pass C, 4 or 8 (0: by the level)")      \
     X(GRLBWT_DEV_WALK_STORES, dev_walk_stores, char, 0, "c[ells]: the checkpointed write walk stores u8/u16 cells one by one, not collected as aligned 8-byte words") \
     X(GRLBWT_DEV_OVERLAP_EXPAND, dev_overlap_expand, char, 0, "f[or_each]: grlbwt_fm_overlap_targets as a for_each with a search per entry, not the tile kernel") \
+    X(GRLBWT_DEV_KMER_DECODE, dev_kmer_decode, char, 0, "f[or_each]: the table of grlbwt_fm_kmers through for_each_set_bit, one lane per entry storing its own cells, not the tile kernel") \
     X(GRLBWT_DEV_LB_PATIENCE, dev_lb_patience, uint64_t, 200000000, "clock ticks a look-back tile waits before it gives up")
 
 namespace prim {

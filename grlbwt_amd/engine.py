@@ -41,6 +41,7 @@ ABI_SYMBOLS = [
     "grlbwt_fm_overlaps", "grlbwt_fm_overlaps_of", "grlbwt_fm_overlap_targets", "grlbwt_fm_overlap_info_get",
     "grlbwt_fm_lcp", "grlbwt_fm_lcp_info_get",
     "grlbwt_fm_sa", "grlbwt_fm_sa_info_get",
+    "grlbwt_fm_kmers", "grlbwt_fm_kmer_info_get",
     "grlbwt_merge_create", "grlbwt_merge_info_get", "grlbwt_merge_emit", "grlbwt_merge_interleave", "grlbwt_merge_destroy",
     "grlbwt_merge_files",
     "grlbwt_select_create", "grlbwt_select_info_get", "grlbwt_select_emit", "grlbwt_select_rows", "grlbwt_select_destroy",
@@ -108,6 +109,11 @@ class LcpInfo(C.Structure):
 class SaInfo(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in ("n_rows", "n_strings", "row_begin", "row_end", "string_bytes", "offset_bytes", "n_written",
                                           "form", "walk_steps", "longest_walk", "walk_lanes", "lane_refills", "scratch_bytes")]
+
+
+class KmerInfo(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("k", "n_rows", "n_strings", "n_distinct", "n_windows", "n_selected", "largest_count", "passes",
+                                          "length_passes", "forward_steps", "tile_rows", "tile_kmers", "stage_bytes", "scratch_bytes")]
 
 
 class ImageStats(C.Structure):
@@ -275,6 +281,8 @@ def load_library(path=None, allow_test_standin=False):
     L.grlbwt_fm_lcp_info_get.argtypes = [vp, C.POINTER(LcpInfo)]
     L.grlbwt_fm_sa.argtypes = [vp, vp, u64, u64, i32, vp, i32, vp]
     L.grlbwt_fm_sa_info_get.argtypes = [vp, C.POINTER(SaInfo)]
+    L.grlbwt_fm_kmers.argtypes = [vp, vp, u64, u64, u64, u64, u64, i32, vp, vp, vp, u64, C.POINTER(u64), vp, u64]
+    L.grlbwt_fm_kmer_info_get.argtypes = [vp, C.POINTER(KmerInfo)]
     L.grlbwt_merge_create.argtypes = [vp, vp, u64, vp, u64, i32, u64, C.POINTER(vp)]
     L.grlbwt_merge_info_get.argtypes = [vp, C.POINTER(MergeInfo)]
     L.grlbwt_merge_emit.argtypes = [vp, vp, vp, u64]
@@ -809,6 +817,82 @@ class FmIndex:
         """The counters of the last suffix_array() that succeeded on this index."""
         out = SaInfo()
         rc = self.ctx.L.grlbwt_fm_sa_info_get(self._h, C.byref(out))
+        if rc != OK:
+            raise GrlbwtError(rc, self.ctx.L.grlbwt_strerror(rc).decode())
+        return _as_dict(out)
+
+    def kmers_raw(self, k, min_count=1, max_count=0, row_begin=0, row_end=None, cell_bytes=1, cells_ptr=None, lo_ptr=None, count_ptr=None,
+                  capacity=0, spectrum=None):
+        """grlbwt_fm_kmers as it is: device pointers (None: not wanted) for the table's cells (k values of cell_bytes bytes per
+        entry), lo and count (uint64 per entry), room for `capacity` entries; spectrum: a numpy uint64 array to fill, or None.
+        Returns the number of entries.  More than `capacity` with an array given: GrlbwtError whose n_kmers attribute is that
+        number, and nothing is written."""
+        got = C.c_uint64()
+        sp = spectrum.ctypes.data_as(C.c_void_p) if spectrum is not None else None
+        try:
+            self.ctx._ck(self.ctx.L.grlbwt_fm_kmers(self.ctx._h, self._h, k, min_count, max_count, row_begin,
+                                                    UINT64_MAX if row_end is None else row_end, cell_bytes, C.c_void_p(cells_ptr),
+                                                    C.c_void_p(lo_ptr), C.c_void_p(count_ptr), capacity, C.byref(got), sp,
+                                                    0 if spectrum is None else len(spectrum)))
+        except GrlbwtError as e:
+            e.n_kmers = got.value
+            raise
+        return got.value
+
+    def kmers(self, k, min_count=1, max_count=0, rows=None, cells=True, cell_bytes=None):
+        """The distinct k-mers of the collection with max(min_count, 1) <= count <= max_count (0: no bound) whose first row lo
+        lies in rows = (begin, end) (None: all rows), in ascending lo = lexicographic order: (lo, count, cells) as numpy arrays,
+        cells of shape (n, k) holding the symbol values (None with cells=False).  [lo, lo + count) is what count() answers for
+        the cells.  cell_bytes None: the narrowest width that holds the index's largest symbol, found by trying.  Sized by the idiom
+        of mems(): one call that reports the number, one that fills the table."""
+        import numpy as np
+        on_device = self.ctx.L.grlbwt_backend_name() == b"hip-gfx950"      # (the test stand-in's "device" is host memory)
+        if on_device:
+            import torch
+
+        def room(nbytes):
+            if on_device:
+                t = torch.zeros(max(nbytes, 8), dtype=torch.uint8, device="cuda:0")
+                torch.cuda.synchronize()
+                return t, t.data_ptr()
+            a = np.zeros(max(nbytes, 8), dtype=np.uint8)
+            return a, a.ctypes.data
+
+        def back(buf, nbytes):
+            if on_device:
+                torch.cuda.synchronize()
+                return buf.cpu().numpy()[:nbytes].copy()
+            return buf[:nbytes].copy()
+
+        rb, re = (0, None) if rows is None else rows
+        widths = (1, 2, 4, 8) if cell_bytes is None and cells else (cell_bytes or 1,)
+        n = self.kmers_raw(k, min_count, max_count, rb, re)
+        (lo, plo), (cnt, pcnt) = room(8 * n), room(8 * n)
+        for i, w in enumerate(widths):
+            out, pout = room(n * k * w) if cells else (None, None)
+            try:
+                got = self.kmers_raw(k, min_count, max_count, rb, re, w, pout, plo, pcnt, n)
+                break
+            except GrlbwtError as e:
+                if e.code != -22 or i + 1 == len(widths) or "does not fit" not in str(e):
+                    raise
+        dt = {1: np.uint8, 2: np.uint16, 4: np.uint32, 8: np.uint64}[w]
+        tab = back(out, got * k * w).view(dt).reshape(got, k) if cells else None
+        return back(lo, 8 * got).view(np.uint64), back(cnt, 8 * got).view(np.uint64), tab
+
+    def kmer_spectrum(self, k, bins=256):
+        """The abundance spectrum: a numpy uint64 array s of `bins` entries (1 to 16384), s[c] = the distinct k-mers of the whole
+        collection that occur exactly c times, the last bin holding every count >= bins - 1.  Its sum is the number of distinct
+        k-mers."""
+        import numpy as np
+        s = np.zeros(bins, dtype=np.uint64)
+        self.kmers_raw(k, spectrum=s)
+        return s
+
+    def kmer_info(self):
+        """The counters of the last kmers() / kmer_spectrum() on this index that got as far as counting."""
+        out = KmerInfo()
+        rc = self.ctx.L.grlbwt_fm_kmer_info_get(self._h, C.byref(out))
         if rc != OK:
             raise GrlbwtError(rc, self.ctx.L.grlbwt_strerror(rc).decode())
         return _as_dict(out)

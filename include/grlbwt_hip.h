@@ -688,6 +688,71 @@ int grlbwt_fm_sa(grlbwt_ctx *ctx, const grlbwt_fm *fm, uint64_t row_begin, uint6
                  int string_bytes, void *dev_string /* may be NULL */, int offset_bytes, void *dev_offset /* may be NULL */);
 int grlbwt_fm_sa_info_get(const grlbwt_fm *fm, grlbwt_fm_sa_info *out);
 
+/* ---- the distinct k-mers of the collection with their counts, and the abundance spectrum: the table behind genome size and
+ * coverage estimates, error filtering by min_count and the nodes of a de Bruijn graph -- the "one pass over the array" that
+ * grlbwt_fm_lcp's comment promises, taken on the device without the array, the locate structures or a text walk per k-mer.
+ *
+ * DEFINITION, part of the contract.  A k-mer is a window of k cells of one string that holds no separator: the definition behind
+ * grlbwt_fm_lcp's distinct counts.  The rows whose suffixes start with a given k-mer are one interval [lo, lo + count) in
+ * grlbwt_fm_count's coordinates -- exactly what grlbwt_fm_count answers for the k-mer's cells -- and count is the number of the
+ * k-mer's occurrences in the collection.
+ *
+ * THE TABLE holds the k-mers with row_begin <= lo < row_end (row_end above n_rows, UINT64_MAX for one, means n_rows) and
+ * max(min_count, 1) <= count <= max_count (0: no upper bound), in ascending lo: the lexicographic order of the cells in the
+ * image's symbol order.  Entry e owns dev_lo[e], dev_count[e] and the k values dev_cells[e * k .. (e + 1) * k), each cell_bytes
+ * wide; wide and compacted alphabets are written as their values, as grlbwt_fm_extract writes them.  Any of the three arrays may
+ * be NULL.  The window bounds the output memory, not the work, as in grlbwt_fm_sa: a partition of [0, n_rows) into windows gives
+ * tables that concatenate to the whole one, and an empty window is legal.  *n_kmers_out is always set once the number is known.
+ * With an array given and more entries than `capacity` the call fails with GRLBWT_EINVAL and writes nothing, the spectrum
+ * included (the sizing idiom of grlbwt_fm_mems: first a call with capacity 0 and no arrays, which succeeds and reports the number).
+ *
+ * THE SPECTRUM: host_spectrum[c], c in [0, spectrum_bins), is the number of distinct k-mers of the WHOLE collection that occur
+ * exactly c times; it ignores the window and the count filter.  The last bin collects every count >= spectrum_bins - 1; bin 0 is
+ * 0 unless it is the last one (spectrum_bins = 1: bin 0 is the number of distinct k-mers).  The sum over all bins is
+ * grlbwt_fm_lcp's number of distinct k-mers; info.n_windows, the sum of all counts, is the number of windows of k cells in the
+ * strings: the sum over the strings of max(0, cells - k + 1).
+ *
+ * ALGORITHM: the passes of grlbwt_fm_lcp capped at k, without values, leave B = the rows with LCP < k: the interval boundaries.
+ * A row whose suffix has fewer than k cells is a boundary that heads no k-mer.  The passes end as soon as every row is set,
+ * maybe long before pass k - 1, so the generations of the suffix-length vector are continued as copy-only passes (length_passes
+ * of them, until one is empty) and OR-ed: heads = B & ~short.  A head's count is the distance to the next bit of B -- in its own
+ * word, or in the next non-empty word from a list of those: no scan over the gap.  The cells are k forward steps from the head
+ * row: the row lies in a sorted run j (the run-start ranks of the LCP passes), starts with run j's symbol and goes on at row
+ * start[j] + (row - slf[j]).  A workgroup decodes tile_kmers entries, one per lane, stages stage_bytes of cells in LDS as
+ * [entry][step] -- in chunks of steps when k * cell_bytes * tile_kmers is more -- and stores the tile's span of dev_cells with
+ * consecutive lanes on consecutive addresses.  One writer per entry, no atomics.
+ * COST: at most k - 1 streaming passes over the rows (grlbwt_fm_lcp's cost model), a few more over the bit-vectors, and
+ * forward_steps = n_selected * k dependent steps where dev_cells is given.
+ *
+ * GRLBWT_EINVAL before the first store: k = 0; a cell_bytes not in {1, 2, 4, 8}; dev_cells given and a symbol value of the image
+ * that does not fit cell_bytes; row_begin > row_end after the clamp; spectrum_bins of 0 or above GRLBWT_FM_KMER_MAX_BINS while
+ * host_spectrum is given; every output NULL (the three arrays, the spectrum and n_kmers_out); an array not aligned to its width;
+ * a null index; an image that is not the BWT of a collection (the refusal of grlbwt_fm_lcp's passes).  GRLBWT_ENOMEM, before the
+ * first pass, when the scratch does not fit the free memory: about one byte per row, reported as scratch_bytes.
+ * The call works on any index of grlbwt_fm_create, with or without GRLBWT_FM_LOCATE, in both position widths and on compacted
+ * alphabets; it makes no handle and leaves the index, its index_bytes and every later answer as they were.  GRLBWT_LCP_ROUND keeps
+ * its meaning for the passes.  OUT OF SCOPE: canonical (strand-merged) k-mers, the edges of the de Bruijn graph, a command-line
+ * flag, a multi-GPU form, skipping rows that are already final in the passes.
+ * grlbwt_fm_kmer_info_get: the counters of the last grlbwt_fm_kmers on the index that got as far as counting (a call that the
+ * capacity then refuses included). */
+#define GRLBWT_FM_KMER_MAX_BINS 16384
+typedef struct grlbwt_fm_kmer_info {
+    uint64_t k, n_rows, n_strings;
+    uint64_t n_distinct, n_windows;         /* distinct k-mers of the collection; the sum of their counts */
+    uint64_t n_selected;                    /* entries of the table: inside the window and the count filter */
+    uint64_t largest_count;
+    uint64_t passes, length_passes;         /* LCP passes run; copy-only passes of the suffix lengths behind them */
+    uint64_t forward_steps;                 /* n_selected * k where dev_cells was given, else 0 */
+    uint64_t tile_rows, tile_kmers;         /* rows per workgroup tile of the counting kernel; entries per workgroup of the decode */
+    uint64_t stage_bytes;                   /* LDS the decode stages cells in: k * cell_bytes * tile_kmers above it goes in chunks */
+    uint64_t scratch_bytes;
+} grlbwt_fm_kmer_info;
+int grlbwt_fm_kmers(grlbwt_ctx *ctx, const grlbwt_fm *fm, uint64_t k, uint64_t min_count, uint64_t max_count /* 0: none */,
+                    uint64_t row_begin, uint64_t row_end /* UINT64_MAX: n_rows */, int cell_bytes, void *dev_cells /* may be NULL */,
+                    uint64_t *dev_lo /* may be NULL */, uint64_t *dev_count /* may be NULL */, uint64_t capacity,
+                    uint64_t *n_kmers_out, uint64_t *host_spectrum /* may be NULL */, uint64_t spectrum_bins);
+int grlbwt_fm_kmer_info_get(const grlbwt_fm *fm, grlbwt_fm_kmer_info *out);
+
 /* ---- merging two images: the image of the collection "strings of A, then strings of B" from the images of A and B, without the
  * texts -- a collection larger than one build is built in batches and folded together, a batch of new strings is added to an
  * existing image.  String i of B becomes string n_strings_a + i.  When A and B were built by this engine with cells of cell_bytes,
