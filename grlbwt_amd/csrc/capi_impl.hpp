@@ -39,6 +39,12 @@ struct grlbwt_select {
     std::unique_ptr<grl64::Image::ImageSelect> s64;
 };
 
+// the strings behind row ranges (grlbwt_docs_create): the document array and what the queries read beside it
+struct grlbwt_docs {
+    std::unique_ptr<grl32::Image::ImageDocs> d32;
+    std::unique_ptr<grl64::Image::ImageDocs> d64;
+};
+
 struct grlbwt_ctx {
     uint32_t flags = 0;
     int device = 0;
@@ -48,6 +54,7 @@ struct grlbwt_ctx {
     std::vector<grlbwt_fm *> fms;      // the indexes still alive: released with the context
     std::vector<grlbwt_merge *> merges;      // and the merges
     std::vector<grlbwt_select *> selects;    // and the selections
+    std::vector<grlbwt_docs *> docs;         // and the document handles
 };
 
 namespace {
@@ -1795,6 +1802,8 @@ void grlbwt_ctx_destroy(grlbwt_ctx *ctx) {
         ctx->merges.clear();
         for (grlbwt_select *sel : ctx->selects) delete sel;
         ctx->selects.clear();
+        for (grlbwt_docs *dc : ctx->docs) delete dc;
+        ctx->docs.clear();
         ctx->e32.reset(); ctx->e64.reset(); prim::sync(); prim::pool_trim();
         if (--prim::rt().live_ctx <= 0) {      // process-wide debug settings and a borrowed stream end with the last context
             prim::rt().live_ctx = 0;
@@ -2443,6 +2452,66 @@ int grlbwt_merge_files(grlbwt_ctx *ctx, const char *path_a, const char *path_b, 
     const std::string err = ctx->err;
     grlbwt_merge_destroy(ctx, mg);
     if (rc != GRLBWT_OK) ctx->err = err;
+    return rc;
+}
+
+int grlbwt_docs_create(grlbwt_ctx *ctx, const grlbwt_fm *fm, uint32_t docs_flags, grlbwt_docs **out) {
+    if (out) *out = nullptr;
+    if (!ctx || !fm || !out || !(fm->f32 || fm->f64)) return refuse(ctx);
+    return guarded(ctx, [&] {
+        std::unique_ptr<grlbwt_docs> dc(new grlbwt_docs());
+        if (fm->f32) {
+            dc->d32.reset(new grl32::Image::ImageDocs());
+            grl32::Image::docs_create(*fm->f32, docs_flags, *dc->d32);
+        } else {
+            dc->d64.reset(new grl64::Image::ImageDocs());
+            grl64::Image::docs_create(*fm->f64, docs_flags, *dc->d64);
+        }
+        ctx->docs.push_back(dc.get());
+        *out = dc.release();
+    });
+}
+int grlbwt_docs_destroy(grlbwt_ctx *ctx, grlbwt_docs *dc) {
+    if (!ctx) return GRLBWT_EINVAL;
+    if (!dc) return GRLBWT_OK;
+    auto it = std::find(ctx->docs.begin(), ctx->docs.end(), dc);
+    if (it == ctx->docs.end()) { ctx->err = "docs destroy: not a handle of this context"; return GRLBWT_EINVAL; }
+    ctx->docs.erase(it);
+    return guarded(ctx, [&] { prim::sync(); delete dc; });
+}
+int grlbwt_docs_info_get(const grlbwt_docs *dc, grlbwt_docs_info *out) {
+    if (!dc || !out || !(dc->d32 || dc->d64)) return GRLBWT_EINVAL;
+    auto fill = [&](const auto &D, uint64_t idx_bytes, uint64_t tile) {
+        out->n_rows = D.n; out->n_strings = D.k; out->flags = D.flags; out->idx_bytes = idx_bytes; out->held_bytes = D.held_bytes();
+        out->scratch_bytes = D.scratch_bytes; out->sort_bits = D.sort_bits; out->form = D.form; out->walk_steps = D.steps;
+        out->n_ranges = D.q.ranges; out->n_range_rows = D.q.range_rows; out->n_entries = D.q.entries; out->largest_range = D.q.largest;
+        out->most_docs = D.q.most; out->tile_entries = tile;
+    };
+    if (dc->d32) fill(*dc->d32, 4, grl32::Image::kDocsTile); else fill(*dc->d64, 8, grl64::Image::kDocsTile);
+    return GRLBWT_OK;
+}
+int grlbwt_docs_count(grlbwt_ctx *ctx, const grlbwt_docs *dc, const uint64_t *dev_lo, const uint64_t *dev_hi, uint64_t n_ranges, uint64_t *dev_ndocs,
+                      uint64_t *n_docs_total_out) {
+    if (n_docs_total_out) *n_docs_total_out = 0;
+    if (!ctx || !dc || !(dc->d32 || dc->d64)) return refuse(ctx);
+    uint64_t n = 0;
+    const int rc = guarded(ctx, [&] {
+        if (dc->d32) grl32::Image::docs_query(*dc->d32, dev_lo, dev_hi, n_ranges, false, dev_ndocs, nullptr, nullptr, nullptr, nullptr, nullptr, 0, n);
+        else grl64::Image::docs_query(*dc->d64, dev_lo, dev_hi, n_ranges, false, dev_ndocs, nullptr, nullptr, nullptr, nullptr, nullptr, 0, n);
+    });
+    if (n_docs_total_out) *n_docs_total_out = n;
+    return rc;
+}
+int grlbwt_docs_list(grlbwt_ctx *ctx, const grlbwt_docs *dc, const uint64_t *dev_lo, const uint64_t *dev_hi, uint64_t n_ranges, uint64_t *dev_entry_offsets,
+                     uint64_t *dev_string, uint64_t *dev_first_row, uint64_t *dev_occ, uint64_t *dev_range, uint64_t capacity, uint64_t *n_entries_out) {
+    if (n_entries_out) *n_entries_out = 0;
+    if (!ctx || !dc || !(dc->d32 || dc->d64)) return refuse(ctx);
+    uint64_t n = 0;
+    const int rc = guarded(ctx, [&] {
+        if (dc->d32) grl32::Image::docs_query(*dc->d32, dev_lo, dev_hi, n_ranges, true, nullptr, dev_entry_offsets, dev_string, dev_first_row, dev_occ, dev_range, capacity, n);
+        else grl64::Image::docs_query(*dc->d64, dev_lo, dev_hi, n_ranges, true, nullptr, dev_entry_offsets, dev_string, dev_first_row, dev_occ, dev_range, capacity, n);
+    });
+    if (n_entries_out) *n_entries_out = n;
     return rc;
 }
 

@@ -6,11 +6,12 @@
 // engine_impl.hpp alone still gets what capi_impl.hpp calls; the guard below makes the second inclusion of a width empty.
 //
 // What it holds: the device functors (in the order of the sections below) and, as static members of the stateless
-// `struct Image`, the host functions behind the C-ABI's grlbwt_image_*, grlbwt_invert_*, grlbwt_fm_*, grlbwt_merge_* and
-// grlbwt_select_* calls (reference: scripts/*.cpp of ddiazdom/grlBWT):
+// `struct Image`, the host functions behind the C-ABI's grlbwt_image_*, grlbwt_invert_*, grlbwt_fm_*, grlbwt_docs_*, grlbwt_merge_*
+// and grlbwt_select_* calls (reference: scripts/*.cpp of ddiazdom/grlBWT):
 //   records and the scripts/ consumers   ImageRecs, plain / rle / stats / split_runs
 //   inversion                            per position (invert_t) and per run (RunIndex, invert_runs_t)
 //   FM index                             count, locate, match / MEMs, extract, the LCP array (FmLcp), the k-mer table (fm_kmers)
+//   the strings behind row ranges        ImageDocs: the document array kept with PREV (and LST, START), docs_create / docs_query
 //   checkpointed LF walks                lf_checkpoints and the walks cut at checkpoints
 //   merge, select                        ImageMerge, ImageSelect
 // The pieces every consumer shares, one copy each: ImageRecs (the record layout), image_header / check_cell_bytes /
@@ -1101,6 +1102,82 @@ struct SaHeadLenIn {      // the length of string i, separator included, from it
 struct SaStartLenFn {     // the same from the strings' start positions of an index that extracts
     const idx_t *T; idx_t *slen;
     GRL_DEV void operator()(u64 i) const { slen[i] = (idx_t)(T[i + 1] - T[i]); }
+};
+
+// ---- the strings behind row ranges (grlbwt_docs_*).  DA[p] is the string of row p, PREV[p] the largest row below p
+// with the same string (kCpNone: there is none), LST the rows sorted by (string, row) and START[d] where string d's rows begin in
+// LST.  Row p of a range [lo, hi) is the first row of its string in the range exactly when PREV[p] is none or below lo: the
+// documents of a range are the set bits of that test over its rows, in ascending row.  The rows of all ranges of a batch are
+// laid back to back, range r at [roff[r], roff[r + 1]): position x of that sequence is row lo[r] + (x - roff[r]) of the range
+// r that holds it, and one bit per position with its word ranks gives every range its count and every document its entry.
+//   Bounds: x < roff[nr] lies in a range r that is not empty, so its row is below hi[r] <= n (the caller has checked the ranges);
+//   DA of a row is below k (the create refuses an image whose chains miss a row), so START[d + 1] is defined; a rank is read at
+//   position x <= roff[nr], word x / 64 of roff[nr] / 64 + 2 zeroed words.
+struct DocsIotaFn {          // the sort's input: the string as the key, the row as the value
+    const idx_t *da; idx_t *key, *val;
+    GRL_DEV void operator()(u64 p) const { key[p] = da[p]; val[p] = (idx_t)p; }
+};
+struct DocsPrevFn {          // one writer per row: LST is a permutation of the rows
+    const idx_t *key, *lst; idx_t *prev;
+    GRL_DEV void operator()(u64 i) const { prev[lst[i]] = (i > 0 && key[i] == key[i - 1]) ? lst[i - 1] : kCpNone; }
+};
+struct DocsStartFn {         // one writer per string (every string owns its terminator's row), and the end
+    const idx_t *key; u64 n, k; idx_t *start;
+    GRL_DEV void operator()(u64 i) const {
+        if (i == n) { start[k] = (idx_t)n; return; }
+        if (i == 0 || key[i] != key[i - 1]) start[key[i]] = (idx_t)i;
+    }
+};
+struct DocsRangeBadIn {      // range r when it is no range of rows, else ~0
+    const u64 *lo, *hi; u64 n;
+    GRL_DEV u64 operator()(u64 r) const { return lo[r] > hi[r] || hi[r] > n ? r : ~0ull; }
+};
+struct DocsSpanIn {
+    const u64 *lo, *hi;
+    GRL_DEV u64 operator()(u64 r) const { return hi[r] - lo[r]; }
+};
+struct DocsFirstPred {       // the generic form of the flags: a search per range row
+    const u64 *roff, *lo; const idx_t *prev; u64 nr;
+    GRL_DEV bool operator()(u64 x) const {
+        const u64 r = upper_bound<u64>(roff, nr + 1, x) - 1;              // roff[r] <= x < roff[r + 1]: empty ranges are stepped over
+        const idx_t v = prev[lo[r] + (x - roff[r])];
+        return v == kCpNone || (u64)v < lo[r];
+    }
+};
+struct DocsRank {            // set bits in front of position x
+    const u64 *words, *wrank;
+    GRL_DEV u64 operator()(u64 x) const { return wrank[x >> 6] + (u64)__builtin_popcountll(words[x >> 6] & ((1ull << (x & 63)) - 1ull)); }
+};
+struct DocsCountIn {         // the documents of range r
+    const u64 *roff; DocsRank rk;
+    GRL_DEV u64 operator()(u64 r) const { return rk(roff[r + 1]) - rk(roff[r]); }
+};
+struct DocsCountFn {
+    DocsCountIn in; u64 *ndocs;
+    GRL_DEV void operator()(u64 r) const { ndocs[r] = in(r); }
+};
+struct DocsOffsetFn {        // entry_offsets[r], r = 0 .. nr
+    const u64 *roff; DocsRank rk; u64 *eoff;
+    GRL_DEV void operator()(u64 r) const { eoff[r] = rk(roff[r]); }
+};
+struct DocsOcc {             // the rows of string d in [first, hi): two searches in d's part of LST (null LST: not asked for)
+    const idx_t *lst, *start;
+    GRL_DEV u64 operator()(u64 d, u64 first, u64 hi) const {
+        const u64 a = (u64)start[d], m = (u64)start[d + 1] - a;
+        const u64 top = hi > (u64)kCpNone ? (u64)kCpNone : hi;             // (rows are below kCpNone)
+        return lower_bound<idx_t>(lst + a, m, (idx_t)top) - lower_bound<idx_t>(lst + a, m, (idx_t)first);
+    }
+};
+struct DocsEmitFn {          // the generic form of the entries, prim::for_each_set_bit over the flags: a search per entry
+    const u64 *roff, *lo, *hi; const idx_t *da; DocsOcc oc; u64 nr; u64 *str, *frow, *occ, *rng;
+    GRL_DEV void operator()(u64 x, u64 e) const {
+        const u64 r = upper_bound<u64>(roff, nr + 1, x) - 1;
+        const u64 p = lo[r] + (x - roff[r]), d = (u64)da[p];
+        str[e] = d;
+        if (frow) frow[e] = p;
+        if (occ) occ[e] = oc(d, p, hi[r]);
+        if (rng) rng[e] = r;
+    }
 };
 
 // ---- removing or keeping chosen strings (grlbwt_select_*).  The suffixes of string i are the rows on the LF chain
@@ -2507,6 +2584,141 @@ struct Image {
         si.lanes = wi.lanes; si.refills = wi.refills;
         prim::sync();
         F.sinfo = si;
+    }
+    // ---- the strings behind row ranges (functor block "the strings behind row ranges").  docs_create computes what
+    // the handle keeps and holds no pointer into the index afterwards.  Everything that can refuse it for its arguments or for
+    // memory runs before the first walk; an index without checkpoints keeps no lengths, so there the rows on no string's chain
+    // show after the walk, in its step count (fm_sa's rule).  The sort is stable and its rows enter ascending, so every string's
+    // rows leave it ascending: the sorted values are LST, neighbours with the same key are PREV.  Peak scratch: the sort's four
+    // arrays and a word per walk; the two arrays the sort did not end in are released before PREV is made.
+    //   Loops: every walk is bounded by n steps; nothing waits for another thread; the only atomics are the ticket word's.
+#ifdef GRLBWT_PRIM_HIP
+    static constexpr u64 kDocsTile = prim::kDocsTile;
+#else
+    static constexpr u64 kDocsTile = 2048;       // (the serial form has no tiles: the figure the device library reports)
+#endif
+    static constexpr u32 kDocsOccurrences = 1;
+    struct DocsQueryInfo { u64 ranges = 0, range_rows = 0, entries = 0, largest = 0, most = 0; };      // of the last docs_count / docs_list that succeeded
+    struct ImageDocs {
+        u64 n = 0, k = 0;
+        u32 flags = 0;
+        u64 scratch_bytes = 0, sort_bits = 0, form = 0, steps = 0;       // of the create
+        DBuf<idx_t> da, prev, lst, start;
+        mutable DocsQueryInfo q;
+        u64 held_bytes() const { return (da.n + prev.n + lst.n + start.n) * sizeof(idx_t); }
+    };
+    static void docs_create(const FmIndex &F, u32 flags, ImageDocs &D) {
+        if (flags & ~kDocsOccurrences) throw prim::Error(-22, "docs: unknown flag bits");
+        if (!F.locate) throw prim::Error(-22, "docs: the index was made without the structures for locating");
+        const u64 n = F.n, k = F.k;
+        const bool occ = (flags & kDocsOccurrences) != 0;
+        const u64 tickets = F.checkpoints ? F.walk.m : k;
+        D.n = n; D.k = k; D.flags = flags; D.form = F.checkpoints ? 1 : 0;
+        D.sort_bits = k > 1 ? (u64)bitlen64(k - 1) : 0;          // ceil(log2 k)
+        const u64 held = (2 * n + (occ ? n + k + 1 : 0)) * sizeof(idx_t);
+        D.scratch_bytes = (4 * n + tickets) * sizeof(idx_t) + 16;
+        if (n >= ((u64)1 << 58) || held + D.scratch_bytes > prim::mem_available())
+            throw prim::Error(-12, "docs: the arrays and the sort need " + std::to_string(held + D.scratch_bytes) + " bytes of device memory, more than is free");
+        const char *lost = "docs: rows lie on no string's chain: the image is not the BWT of a collection";
+        if (F.checkpoints && prim::reduce_sum<u64>(k, SaHeadLenIn{F.smp.p}, "docs.lengths") != n) throw prim::Error(-22, lost);
+        D.da.alloc(n);
+        {
+            constexpr int W = (int)sizeof(idx_t);
+            DBuf<idx_t> wsteps(tickets);
+            WalkInfo wi;
+            const SaWindow win{0, n};
+            SaOut<W> so;
+            so.p = D.da.p;
+            if (F.checkpoints) walk(tickets, SaSegFn<W, 0>{F.lf(), F.sep, F.cp, F.smp.p, win, so, SaOut<0>{}, wsteps.p}, wi, "docs.segments");
+            else walk(tickets, SaStringFn<W, 0>{F.lf(), F.sep, n, nullptr, win, so, SaOut<0>{}, wsteps.p}, wi, "docs.strings");
+            D.steps = prim::reduce_sum<u64>(tickets, IdxIn64{wsteps.p}, "docs.steps");
+        }
+        if (!F.checkpoints && D.steps + k != n) throw prim::Error(-22, lost);
+        {
+            DBuf<idx_t> ka(n), va(n), kb(n), vb(n);
+            prim::for_each(n, DocsIotaFn{D.da.p, ka.p, va.p}, "docs.keys");
+            const int res = prim::sort_pairs<idx_t, idx_t>(ka.p, va.p, kb.p, vb.p, n, 0, (int)D.sort_bits, "docs.sort");
+            DBuf<idx_t> &K = res ? kb : ka, &L = res ? vb : va;
+            (res ? ka : kb).release();
+            (res ? va : vb).release();
+            D.prev.alloc(n);
+            prim::for_each(n, DocsPrevFn{K.p, L.p, D.prev.p}, "docs.prev");
+            if (occ) {
+                D.start.alloc(k + 1);
+                prim::for_each(n + 1, DocsStartFn{K.p, n, k, D.start.p}, "docs.starts");
+                D.lst = std::move(L);
+            }
+        }
+        prim::sync();
+    }
+    // docs_count (list = false) and docs_list.  Everything that can refuse the call runs before the first store into an output:
+    // the arguments, the ranges, the memory; the flags and their ranks are scratch, and the entries are held against the capacity
+    // before the offsets are stored.  n_out is set whenever the count was reached, also when the capacity then refuses the call.
+    // The device form of the flags and of the entries is prim::docs_flags / prim::docs_emit (one tile of kDocsTile range rows per
+    // workgroup); the stand-in's, and the form they are measured against, bitvector_from_pred and for_each_set_bit with a search
+    // in the scanned sizes per range row and per entry.  The counts and the offsets are bit ranks at the ranges' ends either way.
+    // Entries with occurrences take the generic form on the device too: the tile kernel with the two searches per entry was
+    // measured slower than it (profiles/fm_docs/docs.txt) and does not hold them.
+    static void docs_query(const ImageDocs &D, const u64 *lo, const u64 *hi, u64 nr, bool list, u64 *ndocs, u64 *eoff, u64 *str, u64 *frow, u64 *occ,
+                           u64 *rng, u64 capacity, u64 &n_out) {
+        n_out = 0;
+        const std::string who = list ? "docs list" : "docs count";
+        if (list && occ && !(D.flags & kDocsOccurrences)) throw prim::Error(-22, who + ": the handle was made without the occurrence lists");
+        if (list ? !eoff : (nr && !ndocs)) throw prim::Error(-22, who + ": no output array");
+        if (nr && (!lo || !hi)) throw prim::Error(-22, who + ": no ranges");
+        DocsQueryInfo qi;
+        qi.ranges = nr;
+        if (nr == 0) {
+            if (list) prim::dev_memset(eoff, 0, 8);
+            prim::sync();
+            D.q = qi;
+            return;
+        }
+        if (nr >= ((u64)1 << 32)) throw prim::Error(-75, who + ": more ranges than one call takes");
+        const u64 bad = prim::reduce_min<u64>(nr, DocsRangeBadIn{lo, hi, D.n}, "docs.ranges");
+        if (bad != ~0ull) throw prim::Error(-22, who + ": range " + std::to_string(bad) + " is no range of rows (lo <= hi <= the number of rows)");
+        qi.largest = prim::reduce_max<u64>(nr, DocsSpanIn{lo, hi}, "docs.largest_range");
+        if (qi.largest && nr > (~0ull >> 2) / qi.largest) throw prim::Error(-75, who + ": more range rows than one call takes");
+        if ((nr + 1) * 8 + 64 > prim::mem_available())
+            throw prim::Error(-12, who + ": the scanned sizes need " + std::to_string((nr + 1) * 8) + " bytes of device memory, more than is free");
+        DBuf<u64> roff(nr + 1);
+        const u64 total = qi.range_rows = prim::exclusive_scan<u64>(nr, DocsSpanIn{lo, hi}, roff.p, true, "docs.range_offsets");
+#ifdef GRLBWT_PRIM_HIP
+        (void)prim::docs_tiles(total, who.c_str());
+#endif
+        const u64 nw = total / 64 + 2;
+        if ((2 * nw + 1) * 8 + 64 > prim::mem_available())
+            throw prim::Error(-12, who + ": the flags and their ranks need " + std::to_string((2 * nw + 1) * 8) + " bytes of device memory, more than is free");
+        DBuf<u64> words(nw), wrank(nw + 1);
+        words.zero();
+#ifdef GRLBWT_PRIM_HIP
+        const bool tiles = prim::sw().dev_docs_tile != 'f';
+        if (tiles) prim::docs_flags<idx_t>(nr, total, roff.p, lo, D.prev.p, words.p);
+        else
+#endif
+            prim::bitvector_from_pred(total, DocsFirstPred{roff.p, lo, D.prev.p, nr}, words.p, "docs.flags_plain");
+        const u64 ne = qi.entries = n_out = prim::exclusive_scan<u64>(nw, PopcIn{words.p}, wrank.p, true, "docs.flag_ranks");
+        const DocsRank rk{words.p, wrank.p};
+        qi.most = prim::reduce_max<u64>(nr, DocsCountIn{roff.p, rk}, "docs.most");
+        if (!list) {
+            prim::for_each(nr, DocsCountFn{DocsCountIn{roff.p, rk}, ndocs}, "docs.counts");
+            prim::sync();
+            D.q = qi;
+            return;
+        }
+        if (ne > capacity) throw prim::Error(-22, who + ": " + std::to_string(ne) + " entries, more than the output arrays hold");
+        if (ne && !str) throw prim::Error(-22, who + ": no output arrays");
+        prim::for_each(nr + 1, DocsOffsetFn{roff.p, rk, eoff}, "docs.entry_offsets");
+        if (ne) {
+            const DocsOcc oc{D.lst.p, D.start.p};
+#ifdef GRLBWT_PRIM_HIP
+            if (tiles && !occ) prim::docs_emit<idx_t>(nr, total, nw, ne, roff.p, lo, words.p, wrank.p, D.da.p, str, frow, rng);
+            else
+#endif
+                prim::for_each_set_bit<u64>(total, words.p, wrank.p, DocsEmitFn{roff.p, lo, hi, D.da.p, oc, nr, str, frow, occ, rng}, "docs.emit_plain");
+        }
+        prim::sync();
+        D.q = qi;
     }
     // ---- extract (functor block "extracting text ranges").  Everything that can refuse the call runs before the first
     // store into `out` or `out_off`: the ranges' strings, then the plan -- pieces, cells and steps per range, scanned in scratch --

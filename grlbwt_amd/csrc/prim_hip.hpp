@@ -2672,6 +2672,169 @@ inline void kmer_decode(u64 total, u64 k, const u64 *sel, const IDX *selrank, u6
     after_launch("kmer.decode");
 }
 
+// ------------------------------------------------------------------ the strings behind row ranges (grlbwt_docs_count / grlbwt_docs_list)
+// nr ranges of rows, range r = [lo[r], lo[r] + (roff[r + 1] - roff[r])), laid back to back: position e of the sequence,
+// roff[r] <= e < roff[r + 1], is row lo[r] + (e - roff[r]).  roff is the exclusive scan of the sizes with the total at nr.  Both
+// kernels take a tile of kDocsTile consecutive positions per workgroup and give every position its range the way
+// k_expand_ranges does (its comment has the reasoning): thread 0 finds r0, the range that holds the tile's first position, by
+// ONE search; the ranges behind r0 that start inside the tile are read with consecutive lanes on consecutive r and each that is
+// not empty stores r - r0 into the LDS slot of its first position; a running maximum over the slots gives every position its
+// range, empty ranges stepped over.  docs_tile_ranges is that lookup, docs_range_of reads it.
+//   LDS of the lookup (DocsTileLds): kDocsTile + kDocsTile / 8 words of slots (a padding word behind every 8), kBlock words of
+//     carries, one word per wave, r0: 10264 bytes.
+//   Bounds of the lookup: a slot index is roff[r] - e0 with e0 < roff[r] < e1 <= e0 + kDocsTile (r > r0: its offset is above e0 by
+//     the choice of r0; the loop ends at the first offset >= e1); r - r0 fits 32 bits: the caller refuses 2^32 ranges or more.
+//   Loops of the lookup: the search (at most 64 halvings), the ranges that start inside the tile (at most nr / kBlock rounds),
+//     the 8 slots of a lane.  Every thread of the workgroup reaches its four barriers.
+static constexpr int kDocsTile = 2048;
+struct DocsTileLds {
+    u32 head[kDocsTile + kDocsTile / 8];
+    u32 carry[kBlock];
+    u32 wave[kBlock / 64];
+    u64 r0;
+};
+__device__ __forceinline__ u32 docs_slot(u32 i) { return i + (i >> 3); }
+__device__ __forceinline__ void docs_tile_ranges(DocsTileLds &S, u64 nr, const u64 *roff, u64 e0, u64 e1) {
+    constexpr int EPT = kDocsTile / kBlock, NW = kBlock / 64;
+    const u32 tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    for (u32 i = tid; i < (u32)kDocsTile; i += kBlock) S.head[docs_slot(i)] = 0;
+    if (tid == 0) {
+        u64 a = 0, b = nr;                                       // the first r in [0, nr] with roff[r] > e0: roff[nr] = total > e0
+        for (int it = 0; it < 64 && a < b; it++) { const u64 mid = (a + b) >> 1; if (roff[mid] <= e0) a = mid + 1; else b = mid; }
+        S.r0 = a - 1;                                            // (roff[0] = 0 <= e0: a >= 1)
+    }
+    __syncthreads();
+    const u64 r0 = S.r0;
+    for (u64 r = r0 + 1 + tid; r < nr; r += kBlock) {
+        const u64 s = roff[r];
+        if (s >= e1) break;
+        if (roff[r + 1] > s) S.head[docs_slot((u32)(s - e0))] = (u32)(r - r0);
+    }
+    __syncthreads();
+    u32 m = 0;
+#pragma unroll
+    for (int j = 0; j < EPT; j++) {
+        const u32 i = docs_slot(tid * EPT + j);
+        const u32 v = S.head[i];
+        m = v > m ? v : m;
+        S.head[i] = m;
+    }
+    u32 inc = m;                                                 // inclusive maximum over the lanes of the wave, then the exclusive one
+    for (int d = 1; d < 64; d <<= 1) { const u32 o = __shfl_up(inc, d); if (lane >= (u32)d) inc = o > inc ? o : inc; }
+    if (lane == 63) S.wave[wave] = inc;
+    u32 exc = __shfl_up(inc, 1);
+    if (lane == 0) exc = 0;
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < NW; k++) { const u32 o = S.wave[k]; if ((u32)k < wave && o > exc) exc = o; }
+    S.carry[tid] = exc;
+    __syncthreads();
+}
+__device__ __forceinline__ u64 docs_range_of(const DocsTileLds &S, u32 i) {      // the range of position e0 + i, i < kDocsTile
+    const u32 own = S.head[docs_slot(i)], before = S.carry[i / (kDocsTile / kBlock)];
+    return S.r0 + (own > before ? own : before);
+}
+// The flags: bit e of `words` = row p of position e is the first row of its string in its range, PREV[p] none (all bits set) or
+// below lo[r].  Consecutive lanes read consecutive words of PREV inside a range; a wave writes the ballot of its 64 positions as
+// one word, lane 0 stores it.  `words` is zeroed by the caller: a word whose positions all lie behind `total` is not written.
+//   LDS: the lookup's.  Bounds: e < e1 <= total lies in a range r that is not empty, its row is below lo[r] + the size of range
+//   r <= the rows of PREV (the caller has checked the ranges); lane 0's position is a multiple of 64 and below total where it
+//   stores, so the word index is below ceil(total / 64).  Loops: the lookup's and the 8 positions of a lane.  Barriers: the
+//   lookup's four, reached by every thread; the ballots run with all lanes of the wave.  One writer per word, no atomics, no
+//   workgroup waits for another.
+template <class IDX>
+__global__ void __launch_bounds__(kBlock) k_docs_flags(u64 nr, u64 total, const u64 *roff, const u64 *lo, const IDX *prev, u64 *words) {
+    constexpr int EPT = kDocsTile / kBlock;
+    __shared__ DocsTileLds S;
+    const u32 tid = threadIdx.x, lane = tid & 63u;
+    const u64 e0 = (u64)blockIdx.x * kDocsTile;
+    const u64 e1 = e0 + kDocsTile < total ? e0 + kDocsTile : total;
+    docs_tile_ranges(S, nr, roff, e0, e1);
+#pragma unroll
+    for (int j = 0; j < EPT; j++) {
+        const u32 i = (u32)j * kBlock + tid;
+        const u64 e = e0 + i;
+        bool first = false;
+        if (e < e1) {
+            const u64 r = docs_range_of(S, i), l = lo[r];
+            const IDX v = prev[l + (e - roff[r])];
+            first = v == (IDX)~(IDX)0 || (u64)v < l;
+        }
+        const u64 m = __ballot(first);
+        if (lane == 0 && e < e1) words[e >> 6] = m;
+    }
+}
+// The entries: the o-th set bit of the tile (o counted from the tile's first, E0 = wrank[e0 / 64] entries in front of it) becomes
+// entry E0 + o.  A tile without a set bit ends at once, all its threads together -- a range of thousands of rows of one string is
+// mostly such tiles.  Otherwise every position with its bit set drops its tile offset into s_pos[o] (o from the word's rank and
+// the bits below the lane's); then consecutive lanes take consecutive o: string, first row and range are stored at consecutive
+// addresses.  (The occurrences are not written here: with the two searches per entry in this loop the kernel was measured slower
+// than for_each_set_bit with a search per entry, 18.6 against 13.5 ms for 88.6 M entries -- profiles/fm_docs/docs.txt -- so a list
+// with dev_occ takes the flags from k_docs_flags and the entries from the generic form.)
+//   LDS: the lookup's and kDocsTile u16 of s_pos: 14368 bytes.  Bounds: wrank holds nwords + 1 ranks of nwords >= total / 64 + 1
+//   words, e0 / 64 < nwords; bits are set below total only, so o < the tile's count <= kDocsTile and the offset fits 16 bits; the
+//   row as in k_docs_flags; an entry index is below wrank[nwords], the count the caller held against the capacity.
+//   Loops: the lookup's, the 8 positions of a lane, the tile's entries in steps of kBlock.  Barriers: the early return is taken by
+//   every thread or none (the count is the same two loads in all of them); then the lookup's four and one more, reached by every
+//   thread.  One writer per output word, no atomics, no workgroup waits for another.
+template <class IDX>
+__global__ void __launch_bounds__(kBlock) k_docs_emit(u64 nr, u64 total, u64 nwords, const u64 *roff, const u64 *lo, const u64 *words, const u64 *wrank,
+                                                      const IDX *da, u64 *str, u64 *frow, u64 *rng) {
+    constexpr int EPT = kDocsTile / kBlock;
+    __shared__ DocsTileLds S;
+    __shared__ u16 s_pos[kDocsTile];
+    const u32 tid = threadIdx.x, lane = tid & 63u;
+    const u64 e0 = (u64)blockIdx.x * kDocsTile;
+    const u64 e1 = e0 + kDocsTile < total ? e0 + kDocsTile : total;
+    const u64 w0 = e0 >> 6, w1 = w0 + kDocsTile / 64 < nwords ? w0 + kDocsTile / 64 : nwords;
+    const u64 E0 = wrank[w0];
+    const u32 cnt = (u32)(wrank[w1] - E0);
+    if (cnt == 0) return;
+    docs_tile_ranges(S, nr, roff, e0, e1);
+#pragma unroll
+    for (int j = 0; j < EPT; j++) {
+        const u32 i = (u32)j * kBlock + tid;
+        const u64 w = w0 + (i >> 6);
+        if (w < w1) {
+            const u64 word = words[w];
+            if ((word >> lane) & 1ull) s_pos[(u32)(wrank[w] - E0) + (u32)__popcll(word & ((1ull << lane) - 1ull))] = (u16)i;
+        }
+    }
+    __syncthreads();
+    for (u32 o = tid; o < cnt; o += kBlock) {
+        const u32 i = s_pos[o];
+        const u64 r = docs_range_of(S, i), l = lo[r];
+        const u64 p = l + ((e0 + i) - roff[r]), at = E0 + o;
+        str[at] = (u64)da[p];
+        if (frow) frow[at] = p;
+        if (rng) rng[at] = r;
+    }
+}
+inline u64 docs_tiles(u64 total, const char *name) {
+    const u64 tiles = (total + kDocsTile - 1) / kDocsTile;
+    if (tiles > 0x7FFFFFFFull) throw Error(-75, std::string(name) + ": more range rows than one launch takes");
+    return tiles;
+}
+template <class IDX>
+inline void docs_flags(u64 nr, u64 total, const u64 *roff, const u64 *lo, const IDX *prev, u64 *words, const char *name = "docs.flags") {
+    if (total == 0) return;
+    const u64 tiles = docs_tiles(total, name);
+    prof_begin(name, total * sizeof(IDX) + total / 8);
+    hipLaunchKernelGGL((k_docs_flags<IDX>), dim3((unsigned)tiles), dim3(kBlock), 0, rt().stream, nr, total, roff, lo, prev, words);
+    prof_end();
+    after_launch(name);
+}
+template <class IDX>
+inline void docs_emit(u64 nr, u64 total, u64 nwords, u64 entries, const u64 *roff, const u64 *lo, const u64 *words, const u64 *wrank, const IDX *da, u64 *str,
+                      u64 *frow, u64 *rng, const char *name = "docs.emit") {
+    if (total == 0 || entries == 0) return;
+    const u64 tiles = docs_tiles(total, name);
+    prof_begin(name, total / 8 + entries * (sizeof(IDX) + 8 + (frow ? 8 : 0) + (rng ? 8 : 0)));
+    hipLaunchKernelGGL((k_docs_emit<IDX>), dim3((unsigned)tiles), dim3(kBlock), 0, rt().stream, nr, total, nwords, roff, lo, words, wrank, da, str, frow, rng);
+    prof_end();
+    after_launch(name);
+}
+
 // Digit plan of an LSD sort over `bits` key bits: the fewest passes with digits of at most rs_max_digit() bits, widths as equal
 // as possible (at 9: 51 bits = 9,9,9,8,8,8; 54 = 6 x 9; 18 = 9,9).  GRLBWT_SORT_DIGIT=8|9|10 sets the widest digit; the default
 // stays 8: measured on the 10 GB build (profiles/r03), 9- and 10-bit digits save a pass over the 51-56-bit suffix keys and the

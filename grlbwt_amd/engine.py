@@ -42,6 +42,7 @@ ABI_SYMBOLS = [
     "grlbwt_fm_lcp", "grlbwt_fm_lcp_info_get",
     "grlbwt_fm_sa", "grlbwt_fm_sa_info_get",
     "grlbwt_fm_kmers", "grlbwt_fm_kmer_info_get",
+    "grlbwt_docs_create", "grlbwt_docs_destroy", "grlbwt_docs_info_get", "grlbwt_docs_count", "grlbwt_docs_list",
     "grlbwt_merge_create", "grlbwt_merge_info_get", "grlbwt_merge_emit", "grlbwt_merge_interleave", "grlbwt_merge_destroy",
     "grlbwt_merge_files",
     "grlbwt_select_create", "grlbwt_select_info_get", "grlbwt_select_emit", "grlbwt_select_rows", "grlbwt_select_destroy",
@@ -53,6 +54,7 @@ FM_CHECKPOINTS = 2
 FM_EXTRACT = 4
 FM_OVERLAP_PROPER = 1
 UINT64_MAX = 2 ** 64 - 1
+DOCS_OCCURRENCES = 1
 SELECT_KEEP = 1
 SELECT_CHECKPOINTS = 2
 
@@ -114,6 +116,12 @@ class SaInfo(C.Structure):
 class KmerInfo(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in ("k", "n_rows", "n_strings", "n_distinct", "n_windows", "n_selected", "largest_count", "passes",
                                           "length_passes", "forward_steps", "tile_rows", "tile_kmers", "stage_bytes", "scratch_bytes")]
+
+
+class DocsInfo(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("n_rows", "n_strings", "flags", "idx_bytes", "held_bytes", "scratch_bytes", "sort_bits", "form",
+                                          "walk_steps", "n_ranges", "n_range_rows", "n_entries", "largest_range", "most_docs",
+                                          "tile_entries")]
 
 
 class ImageStats(C.Structure):
@@ -283,6 +291,11 @@ def load_library(path=None, allow_test_standin=False):
     L.grlbwt_fm_sa_info_get.argtypes = [vp, C.POINTER(SaInfo)]
     L.grlbwt_fm_kmers.argtypes = [vp, vp, u64, u64, u64, u64, u64, i32, vp, vp, vp, u64, C.POINTER(u64), vp, u64]
     L.grlbwt_fm_kmer_info_get.argtypes = [vp, C.POINTER(KmerInfo)]
+    L.grlbwt_docs_create.argtypes = [vp, vp, C.c_uint32, C.POINTER(vp)]
+    L.grlbwt_docs_destroy.argtypes = [vp, vp]
+    L.grlbwt_docs_info_get.argtypes = [vp, C.POINTER(DocsInfo)]
+    L.grlbwt_docs_count.argtypes = [vp, vp, vp, vp, u64, vp, C.POINTER(u64)]
+    L.grlbwt_docs_list.argtypes = [vp, vp, vp, vp, u64, vp, vp, vp, vp, vp, u64, C.POINTER(u64)]
     L.grlbwt_merge_create.argtypes = [vp, vp, u64, vp, u64, i32, u64, C.POINTER(vp)]
     L.grlbwt_merge_info_get.argtypes = [vp, C.POINTER(MergeInfo)]
     L.grlbwt_merge_emit.argtypes = [vp, vp, vp, u64]
@@ -897,6 +910,11 @@ class FmIndex:
             raise GrlbwtError(rc, self.ctx.L.grlbwt_strerror(rc).decode())
         return _as_dict(out)
 
+    def documents(self, occurrences=False):
+        """An FmDocs handle: which strings lie behind row ranges, and how many (an index made with locate=True).  occurrences=True
+        also keeps what list() needs to count every document's occurrences.  The handle holds no pointer into this index."""
+        return FmDocs(self, occurrences)
+
     @staticmethod
     def distinct_kmers(rows_at, suffixes_of, k=None):
         """The number of distinct k-mers (windows of k cells that hold no separator) from the histograms of lcp(): the rows with
@@ -917,6 +935,64 @@ class FmIndex:
         h, self._h = getattr(self, "_h", None), None
         if h and getattr(self.ctx, "_h", None):       # (a closed context has released its indexes)
             self.ctx._ck(self.ctx.L.grlbwt_fm_destroy(self.ctx._h, h))
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class FmDocs:
+    """The strings behind row ranges of an FM index (grlbwt_docs_*): the documents of a range [lo, hi) are the distinct strings of
+    its rows, reported in ascending first row.  All pointers are device pointers to uint64 words.  Made by FmIndex.documents();
+    the index may be closed before the handle."""
+
+    def __init__(self, fm, occurrences=False):
+        self.ctx = fm.ctx
+        h = C.c_void_p()
+        self.ctx._ck(self.ctx.L.grlbwt_docs_create(self.ctx._h, fm._h, DOCS_OCCURRENCES if occurrences else 0, C.byref(h)))
+        self._h = h
+
+    def count(self, lo_ptr, hi_ptr, n, ndocs_ptr):
+        """ndocs[r] = the number of documents of range r = [lo[r], hi[r]), for n ranges; their sum is returned."""
+        got = C.c_uint64()
+        self.ctx._ck(self.ctx.L.grlbwt_docs_count(self.ctx._h, self._h, C.c_void_p(lo_ptr), C.c_void_p(hi_ptr), n, C.c_void_p(ndocs_ptr),
+                                                  C.byref(got)))
+        return got.value
+
+    def list(self, lo_ptr, hi_ptr, n, entry_offsets_ptr, string_ptr, capacity, first_row_ptr=None, occ_ptr=None, range_ptr=None):
+        """The documents of range r are entries [entry_offsets[r], entry_offsets[r + 1]) of string (and, optional, first_row, occ,
+        range), in ascending first row.  occ needs a handle made with occurrences=True.  The number of entries is returned.
+        More than `capacity`: GrlbwtError whose n_entries attribute is that number, and nothing is written."""
+        got = C.c_uint64()
+        try:
+            self.ctx._ck(self.ctx.L.grlbwt_docs_list(self.ctx._h, self._h, C.c_void_p(lo_ptr), C.c_void_p(hi_ptr), n,
+                                                     C.c_void_p(entry_offsets_ptr), C.c_void_p(string_ptr), C.c_void_p(first_row_ptr),
+                                                     C.c_void_p(occ_ptr), C.c_void_p(range_ptr), capacity, C.byref(got)))
+        except GrlbwtError as e:
+            e.n_entries = got.value
+            raise
+        return got.value
+
+    def info(self):
+        """The handle, its create, and the counters of the last count() or list() that succeeded on it."""
+        out = DocsInfo()
+        rc = self.ctx.L.grlbwt_docs_info_get(self._h, C.byref(out))
+        if rc != OK:
+            raise GrlbwtError(rc, self.ctx.L.grlbwt_strerror(rc).decode())
+        return _as_dict(out)
+
+    def close(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h and getattr(self.ctx, "_h", None):       # (a closed context has released its handles)
+            self.ctx._ck(self.ctx.L.grlbwt_docs_destroy(self.ctx._h, h))
 
     def __enter__(self):
         return self

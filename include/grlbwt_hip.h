@@ -670,8 +670,8 @@ int grlbwt_fm_lcp_info_get(const grlbwt_fm *fm, grlbwt_fm_lcp_info *out);
  * dependent chain per string: fine for reads, hopeless for chromosomes.  Form 1 is the form for long strings.  Against
  * grlbwt_fm_locate over all rows -- about n_rows * (mean length) / 2 steps, with checkpoints n_rows * 2^(sample_bits - 1) --
  * both forms take one step per row.  The walks obey GRLBWT_WALK_LANES.
- * OUT OF SCOPE: the inverse suffix array, document listing or counting over row ranges, a command-line flag, a multi-GPU form,
- * keeping the arrays inside the index.
+ * OUT OF SCOPE: the inverse suffix array, a command-line flag, a multi-GPU form, keeping the arrays inside the index (document
+ * listing and counting over row ranges: grlbwt_docs_* below, a handle that keeps the document array).
  * grlbwt_fm_sa_info_get: the counters of the last grlbwt_fm_sa that succeeded on the index. */
 typedef struct grlbwt_fm_sa_info {
     uint64_t n_rows, n_strings;
@@ -752,6 +752,81 @@ int grlbwt_fm_kmers(grlbwt_ctx *ctx, const grlbwt_fm *fm, uint64_t k, uint64_t m
                     uint64_t *dev_lo /* may be NULL */, uint64_t *dev_count /* may be NULL */, uint64_t capacity,
                     uint64_t *n_kmers_out, uint64_t *host_spectrum /* may be NULL */, uint64_t spectrum_bins);
 int grlbwt_fm_kmer_info_get(const grlbwt_fm *fm, grlbwt_fm_kmer_info *out);
+
+/* ---- the strings behind row ranges: document listing and counting, the question a collection index exists for -- which reads
+ * carry this k-mer, which genomes of a pangenome carry this allele, what is the document frequency of a k-mer.  grlbwt_fm_count
+ * says how often a pattern occurs and grlbwt_fm_locate where each occurrence lies; these calls say WHICH STRINGS hold it and how
+ * many do, for batches of row ranges: the (lo, hi) pairs of grlbwt_fm_count, the (lo, lo + count) table of grlbwt_fm_kmers, or
+ * any ranges.  Without them the route is one grlbwt_fm_locate per occurrence and a unique on the host.
+ *
+ * DEFINITIONS, part of the contract.  Rows are those of grlbwt_fm_count, strings are numbered as grlbwt_fm_locate numbers them.
+ * DA[p] is the string of row p, exactly what grlbwt_fm_sa writes.  For a range [lo, hi) with lo <= hi <= n_rows its DOCUMENTS
+ * are the distinct values of DA[lo .. hi); the OCCURRENCES of document d are the rows p of the range with DA[p] = d; its FIRST
+ * ROW is the smallest such p.  The documents of a range are reported in ASCENDING FIRST ROW: the order of each string's smallest
+ * matching suffix, and the order the filter below meets them.  An empty range has no document; (0, 0), the "no occurrence"
+ * answer of grlbwt_fm_count, is legal.  Ranges may overlap, repeat and come in any order.
+ *
+ * grlbwt_docs_create makes a handle from an index made with GRLBWT_FM_LOCATE (without it: GRLBWT_EINVAL, the message says so).
+ * It uses form 0 or form 1 of grlbwt_fm_sa's walk, whichever the index offers, computes what it keeps and holds no pointer into
+ * the index afterwards: the index may be destroyed first.  grlbwt_ctx_destroy releases the handles still alive.  The handle
+ * keeps, in words of the index's position width (idx_bytes):
+ *   DA     one word per row;
+ *   PREV   one word per row: the largest row below p with the same string, or "none";
+ *   with GRLBWT_DOCS_OCCURRENCES also
+ *   LST    one word per row: the rows sorted by (string, row);
+ *   START  n_strings + 1 words: where each string's rows begin in LST (every string owns at least its terminator's row).
+ * DA comes from the walk; a stable sort of (DA, row) on sort_bits = ceil(log2 n_strings) key bits leaves every string's rows
+ * ascending (LST); PREV[LST[i]] = LST[i - 1] where both belong to one string; START from the key changes.  The sort's buffers
+ * are released before the call returns.  Refusals, each with *out = NULL and nothing held: unknown flag bits, a null index
+ * (GRLBWT_EINVAL); an index whose strings' lengths do not add up to n_rows -- rows on no string's chain, the case
+ * grlbwt_fm_sa fills with all-ones -- GRLBWT_EINVAL, the message says that the image is not the BWT of a collection; held bytes
+ * plus peak scratch (four words per row and one per walk) above the free device memory: GRLBWT_ENOMEM, before the first walk.
+ * The index, its index_bytes and every later answer of it are unchanged.  Both position widths; compacted and wide alphabets
+ * (only string numbers matter, not symbols).
+ *
+ * grlbwt_docs_count: dev_ndocs[r] = the number of documents of range r, *n_docs_total_out their sum.  n_ranges = 0 is legal,
+ * writes nothing and reports 0.  It is the sizing call of grlbwt_docs_list.
+ * grlbwt_docs_list: the documents of range r are entries [dev_entry_offsets[r], dev_entry_offsets[r + 1]), back to back, in the
+ * contract's order; dev_entry_offsets[n_ranges] = *n_entries_out.  Entry e is dev_string[e]; dev_first_row[e], a row that
+ * grlbwt_fm_locate turns into an offset; dev_occ[e], the occurrences of that document in the range; dev_range[e] = r.  The last
+ * three may be NULL.  dev_occ on a handle made without GRLBWT_DOCS_OCCURRENCES is GRLBWT_EINVAL.  *n_entries_out is set whenever
+ * the count was reached; more entries than `capacity` is GRLBWT_EINVAL and nothing is written (the rule of
+ * grlbwt_fm_overlap_targets).  n_ranges = 0 writes dev_entry_offsets[0] = 0.
+ * Refusals of both, before the first store into any output: a range with lo > hi or hi > n_rows (GRLBWT_EINVAL, the message
+ * names the first such range); a null handle; a missing output -- dev_ndocs; dev_entry_offsets; dev_string while there are
+ * entries -- (GRLBWT_EINVAL); 2^32 ranges or more, or more tiles than one launch takes (GRLBWT_ERANGE); scratch that does not
+ * fit the free memory (GRLBWT_ENOMEM): one bit per range row for the flags, their word ranks, n_ranges + 1 words of scanned sizes.
+ *
+ * COST.  The create: one LF step per row and ceil(sort_bits / 8) sort passes over the rows.  A query: n_range_rows row visits,
+ * one coalesced read of PREV per range row -- row p of range r is its document's first row exactly when PREV[p] is none or
+ * below lo[r]; no sort and no hash per query.  A range is linear in its SIZE, not in its number of documents.  With dev_occ each
+ * entry adds two binary searches in its string's part of LST.  The device form is two kernels over tiles of tile_entries range
+ * rows per workgroup: one search per tile, one writer per output word, no atomics.
+ * OUT OF SCOPE: sub-linear counting, top-k by occurrences, a min_occ filter, a command-line flag, a multi-GPU form.
+ * grlbwt_docs_info_get: the handle, its create, and the counters of the last query that succeeded on it. */
+typedef struct grlbwt_docs grlbwt_docs;
+#define GRLBWT_DOCS_OCCURRENCES 1u   /* also keep what dev_occ needs */
+typedef struct grlbwt_docs_info {
+    uint64_t n_rows, n_strings;
+    uint64_t flags;                         /* the docs_flags of the create */
+    uint64_t idx_bytes, held_bytes;         /* the width of a kept word; the device memory the handle holds */
+    uint64_t scratch_bytes;                 /* of the create, at its peak, beside what the handle holds */
+    uint64_t sort_bits;                     /* ceil(log2 n_strings) */
+    uint64_t form;                          /* 0: one walk per string, 1: one walk per checkpoint segment */
+    uint64_t walk_steps;                    /* LF steps of the create */
+    uint64_t n_ranges, n_range_rows;        /* of the last query that succeeded: ranges, the sum of hi - lo */
+    uint64_t n_entries;                     /* documents over all ranges (grlbwt_docs_count: the total) */
+    uint64_t largest_range, most_docs;      /* the largest hi - lo; the most documents of one range */
+    uint64_t tile_entries;                  /* range rows per workgroup of the two kernels */
+} grlbwt_docs_info;
+int grlbwt_docs_create(grlbwt_ctx *ctx, const grlbwt_fm *fm, uint32_t docs_flags, grlbwt_docs **out);
+int grlbwt_docs_destroy(grlbwt_ctx *ctx, grlbwt_docs *docs);
+int grlbwt_docs_info_get(const grlbwt_docs *docs, grlbwt_docs_info *out);
+int grlbwt_docs_count(grlbwt_ctx *ctx, const grlbwt_docs *docs, const uint64_t *dev_lo, const uint64_t *dev_hi, uint64_t n_ranges,
+                      uint64_t *dev_ndocs /* n_ranges words */, uint64_t *n_docs_total_out);
+int grlbwt_docs_list(grlbwt_ctx *ctx, const grlbwt_docs *docs, const uint64_t *dev_lo, const uint64_t *dev_hi, uint64_t n_ranges,
+                     uint64_t *dev_entry_offsets /* n_ranges + 1 words */, uint64_t *dev_string, uint64_t *dev_first_row /* may be NULL */,
+                     uint64_t *dev_occ /* may be NULL */, uint64_t *dev_range /* may be NULL */, uint64_t capacity, uint64_t *n_entries_out);
 
 /* ---- merging two images: the image of the collection "strings of A, then strings of B" from the images of A and B, without the
  * texts -- a collection larger than one build is built in batches and folded together, a batch of new strings is added to an
