@@ -1990,15 +1990,39 @@ struct MergeEmitFn {
         if (map) map[t] = (u32)(ex.a + v.a - 1);
     }
 };
-static inline Runs merge_runs(const u32 *sym, const idx_t *len, u64 n, u32 *merged_index = nullptr) {
+// The same for input runs that are all one symbol long (the rows of first_bwt and base_bwt): there is no length array to store and
+// to read back in both phases of the scan, a row's symbol offset is its index, and the scan carries the head count alone (one
+// idx_t per element through LDS, not two).
+struct UnitHeadIn {
+    const u32 *s;
+    GRL_DEV idx_t operator()(u64 t) const { return (t == 0 || s[t] != s[t - 1]) ? (idx_t)1 : (idx_t)0; }
+};
+struct UnitMergeEmitFn {
+    static constexpr bool kWaveEmit = false;
+    const u32 *sym; u64 n;
+    u32 *osym; idx_t *ostart;
+    GRL_DEV void operator()(u64 t, idx_t ex, idx_t v) const {
+        if (v) { osym[ex] = sym[t]; ostart[ex] = (idx_t)t; }
+        if (t == n - 1) ostart[ex + v] = (idx_t)n;
+    }
+};
+// (UNIT: every input run is one symbol long; `len` and `merged_index` are not read)
+template <bool UNIT>
+static inline Runs merge_runs_as(const u32 *sym, const idx_t *len, u64 n, u32 *merged_index) {
     Runs out;
     if (n == 0) { out.sym.alloc(0); out.len.alloc(0); return out; }
     // the number of output runs is not known before the scan: heads land in scratch sized for the worst case
     DBuf<u32> hsym(n);
     DBuf<idx_t> ostart(n + 1);
-    HeadLen tot = prim::exclusive_scan_emit<HeadLen>(n, HeadLenIn{sym, len}, MergeEmitFn{sym, n, hsym.p, ostart.p, merged_index}, "merge_runs.scan");
-    u64 R = (u64)tot.a;
-    out.n = (u64)tot.b;
+    u64 R;
+    if constexpr (UNIT) {
+        R = (u64)prim::exclusive_scan_emit<idx_t>(n, UnitHeadIn{sym}, UnitMergeEmitFn{sym, n, hsym.p, ostart.p}, "merge_runs.scan");
+        out.n = n;
+    } else {
+        HeadLen tot = prim::exclusive_scan_emit<HeadLen>(n, HeadLenIn{sym, len}, MergeEmitFn{sym, n, hsym.p, ostart.p, merged_index}, "merge_runs.scan");
+        R = (u64)tot.a;
+        out.n = (u64)tot.b;
+    }
     out.len.alloc(R);
     prim::for_each(R, DiffFn{ostart.p, out.len.p}, "merge_runs.len");
     // the heads' scratch (sized for the worst case) becomes the symbol array as it is, unless it is much larger than what it
@@ -2009,11 +2033,13 @@ static inline Runs merge_runs(const u32 *sym, const idx_t *len, u64 n, u32 *merg
     out.R = R;
     return out;
 }
+static inline Runs merge_runs(const u32 *sym, const idx_t *len, u64 n, u32 *merged_index = nullptr) { return merge_runs_as<false>(sym, len, n, merged_index); }
+static inline Runs merge_unit_runs(const u32 *sym, u64 n) { return merge_runs_as<true>(sym, nullptr, n, nullptr); }
 
 // --------------------------------------------------------- a12: parse2bwt
 struct CellSymFn {
-    const u32 *t; u32 *sym; idx_t *len;
-    GRL_DEV void operator()(u64 i) const { sym[i] = t[i] >> 2; len[i] = 1; }
+    const u32 *t; u32 *sym;
+    GRL_DEV void operator()(u64 i) const { sym[i] = t[i] >> 2; }
 };
 // ------------------------------------ the base case: BWT_r of a level of short strings by sorting its suffixes (Engine::base_bwt)
 // The level's text read as a dictionary in which every string is a phrase: one scan over the terminator flags gives every cell
@@ -2038,17 +2064,28 @@ struct OffLenIn {         // length of string k from the starts
 // The rows in sorted order.  A suffix that starts inside its string carries the cell in front of it; the m-th WHOLE string in
 // sorted order carries the last cell of string m in text order (parse2bwt is the case of one cell per string): the scan over
 // "slot t holds a string start" numbers them.
-struct StartSlotIn {
-    const u32 *perm; const u64 *starts;
-    GRL_DEV u32 operator()(u64 t) const { return bit_at(starts, perm[t]) ? 1u : 0u; }
-};
-struct BaseRowFn {
-    static constexpr bool kWaveEmit = false;
-    const u32 *perm; const u32 *sym; const u32 *off; u32 *osym; idx_t *olen;
-    GRL_DEV void operator()(u64 t, u32 m, u32 whole) const {
-        osym[t] = whole ? sym[off[m + 1] - 1u] : sym[perm[t] - 1u];
-        olen[t] = 1;
+// The text cell in front of the suffix says both: its bit 0 is "a string ends here" -- the suffix behind it is a whole string --
+// and the bits from 2 on are the row's symbol.  It is gathered ONCE per slot (front[], site base_front; position 0 has no cell in
+// front of it and gets a word with bit 0 set); the scan then streams front[] in both of its phases and its consumer turns front[t]
+// into the row's symbol in place.  (The scan's consumer of element t runs in the thread that read element t as the scan's input,
+// behind the read, and the tile sums are a launch of their own in front of it: prim::k_scan_tiles.)
+// (Before: the start bit of perm[t] from the sort's bit-vector in both phases and sym[perm[t] - 1] in the consumer, three random
+// reads per row.)
+struct BaseFrontFn {
+    const u32 *perm; const u32 *text; u32 *front;
+    GRL_DEV void operator()(u64 t) const {
+        const u32 p = perm[t];
+        front[t] = p ? text[p - 1u] : 1u;
     }
+};
+struct FrontStartIn {
+    const u32 *front;
+    GRL_DEV u32 operator()(u64 t) const { return front[t] & 1u; }
+};
+struct BaseRowFn {        // (m: whole-string rows in front of slot t.  off[] and sym[] are read at ascending addresses)
+    static constexpr bool kWaveEmit = false;
+    const u32 *sym; const u32 *off; u32 *row;
+    GRL_DEV void operator()(u64 t, u32 m, u32 whole) const { row[t] = whole ? sym[off[m + 1] - 1u] : row[t] >> 2; }
 };
 
 template <class F>
@@ -3833,6 +3870,7 @@ class Engine {
         DBuf<u32> pos_arr, perm_ai, pown;        // (carry) offset of every arrival; the sorted arrival indices once perm holds offsets again; owner by slot
         DBuf<u64> abounds, rec_arr;              // (carry) arrivals [abounds[g], abounds[g + 1]) came from rank g; the record of every arrival
         u64 Sg = 0, G = 0;                       // my slots of the sorted order (all of them without a communicator), their groups
+        bool want_groups = true;                 // cleared by a caller that wants perm[] alone: suffix_sort_local leaves gid / gstart empty and G at 0
         DBuf<u32> perm, gid, gstart;
         DBuf<SufRecT<8>> recs;                   // (sharded, records fetched: what the owners answered, by slot)
         DBuf<u32> grank, pidx, gmin, gmax; DBuf<idx_t> gacc; DBuf<u8> gfull, gflag;
@@ -3980,7 +4018,7 @@ class Engine {
                     } else Sg = Sown;
                 }
             }
-            gid.alloc(Sg); gstart.alloc(Sg + 1);
+            if (want_groups) { gid.alloc(Sg); gstart.alloc(Sg + 1); }
             DBuf<u8> hflag(Sg), uflag(Sg);
             first_sort_and_flags(ka, perm, Sg, ks, rk, hflag.p, uflag.p);
             ka.release();
@@ -4031,7 +4069,7 @@ class Engine {
                 iters++;
             }
             pbits.base.release();
-            G = close_groups(hflag.p, Sg, gstart.p, gid.p);
+            if (want_groups) G = close_groups(hflag.p, Sg, gstart.p, gid.p);
             L.info.sort_iters = iters;
         }
         // The same with the dictionary sharded by owner.  Every rank runs the same sequence of collectives (the refinement goes on
@@ -4502,9 +4540,8 @@ class Engine {
         prim::rt().phase = 'i';
         StageTimer st(&tm.ind_assemble, "ind_assemble");
         DBuf<u32> s(cur_n);
-        DBuf<idx_t> l(cur_n);
-        prim::for_each(cur_n, CellSymFn{cur_text.p, s.p, l.p}, "parse2bwt");
-        bwt = merge_runs(s.p, l.p, cur_n);
+        prim::for_each(cur_n, CellSymFn{cur_text.p, s.p}, "parse2bwt");
+        bwt = merge_unit_runs(s.p, cur_n);
         bwt_level = (int)levels.size();
         cur_text.release();
         linfo.assign(levels.size() + 1, LevelInfo());
@@ -4557,6 +4594,7 @@ class Engine {
         I.ph_off = B.off.p; I.ph_lastT = all_last.p;
         LevelData scratch;                   // (the stage's counters of a round: nobody asks for them at this level)
         DictStage<u32, false> Z(*this, I, scratch);
+        Z.want_groups = false;               // (the rows want the order alone)
         Z.dict_sym = std::move(B.sym); Z.dict_phr = std::move(B.str);
         {
             StageTimer st(&tm.ind_assemble, "ind_assemble");
@@ -4565,12 +4603,12 @@ class Engine {
         Z.suffix_sort_local();
         if (Z.Sg != n) throw prim::Error(-71, "base case: the sort left suffixes out");
         StageTimer st(&tm.ind_assemble, "ind_assemble");
-        Z.gid.release(); Z.gstart.release();
-        DBuf<u32> s(n);
-        DBuf<idx_t> l(n);
-        const u64 whole = prim::exclusive_scan_emit<u32>(n, StartSlotIn{Z.perm.p, Z.pbits.words.p}, BaseRowFn{Z.perm.p, Z.dict_sym.p, I.ph_off, s.p, l.p}, "base_rows");
+        DBuf<u32> s(n);                      // the cell in front of every slot's suffix, then the rows' symbols
+        prim::for_each(n, BaseFrontFn{Z.perm.p, cur_text.p, s.p}, "base_front");
+        Z.perm.release();
+        const u64 whole = prim::exclusive_scan_emit<u32>(n, FrontStartIn{s.p}, BaseRowFn{Z.dict_sym.p, I.ph_off, s.p}, "base_rows");
         if (whole != D) throw prim::Error(-71, "base case: whole-string rows do not match the string count");
-        bwt = merge_runs(s.p, l.p, n);
+        bwt = merge_unit_runs(s.p, n);
         bwt_level = (int)levels.size();
         cur_text.release();
         parse_done = true;
