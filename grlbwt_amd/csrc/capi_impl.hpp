@@ -2337,6 +2337,33 @@ int grlbwt_fm_kmer_info_get(const grlbwt_fm *fm, grlbwt_fm_kmer_info *out) {
     if (fm->f32) fill(*fm->f32); else fill(*fm->f64);
     return GRLBWT_OK;
 }
+int grlbwt_fm_repeats(grlbwt_ctx *ctx, const grlbwt_fm *fm, uint64_t min_len, uint64_t max_len, uint64_t min_count, uint64_t max_count, uint32_t repeat_flags,
+                      uint64_t row_begin, uint64_t row_end, uint64_t *dev_lo, uint64_t *dev_count, uint64_t *dev_len, uint64_t *dev_split, uint64_t capacity,
+                      uint64_t *n_repeats_out) {
+    if (n_repeats_out) *n_repeats_out = 0;
+    if (!ctx || !fm || !(fm->f32 || fm->f64)) return refuse(ctx);
+    uint64_t n = 0;
+    const int rc = guarded(ctx, [&] {
+        if (fm->f32) grl32::Image::fm_repeats(*fm->f32, min_len, max_len, min_count, max_count, repeat_flags, row_begin, row_end, dev_lo, dev_count, dev_len,
+                                              dev_split, capacity, n, n_repeats_out != nullptr);
+        else grl64::Image::fm_repeats(*fm->f64, min_len, max_len, min_count, max_count, repeat_flags, row_begin, row_end, dev_lo, dev_count, dev_len,
+                                      dev_split, capacity, n, n_repeats_out != nullptr);
+    });
+    if (n_repeats_out) *n_repeats_out = n;
+    return rc;
+}
+int grlbwt_fm_repeat_info_get(const grlbwt_fm *fm, grlbwt_fm_repeat_info *out) {
+    if (!fm || !out || !(fm->f32 || fm->f64)) return GRLBWT_EINVAL;
+    auto fill = [&](const auto &F) {
+        const auto &i = F.rinfo;
+        out->n_rows = i.n; out->n_strings = i.n_strings; out->min_len = i.min_len; out->max_len = i.max_len; out->passes = i.passes;
+        out->n_repeats = i.n_repeats; out->n_maximal = i.n_maximal; out->n_selected = i.n_selected; out->longest = i.longest;
+        out->largest_count = i.largest_count; out->value_bytes = i.value_bytes; out->tile_rows = i.tile_rows; out->tree_fanout = i.tree_fanout;
+        out->tree_levels = i.tree_levels; out->far_searches = i.far_searches; out->scratch_bytes = i.scratch_bytes;
+    };
+    if (fm->f32) fill(*fm->f32); else fill(*fm->f64);
+    return GRLBWT_OK;
+}
 int grlbwt_fm_locate(grlbwt_ctx *ctx, const grlbwt_fm *fm, const uint64_t *dev_rows, uint64_t n_rows, uint64_t max_steps,
                      uint64_t *dev_string, uint64_t *dev_offset) {
     if (!ctx || !fm || !(fm->f32 || fm->f64)) return refuse(ctx);

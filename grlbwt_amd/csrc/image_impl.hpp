@@ -1535,6 +1535,185 @@ struct KmerEmitFn {          // the generic decode, prim::for_each_set_bit over 
     }
 };
 
+// ---- the right-maximal and maximal repeats (grlbwt_fm_repeats).  V[p] = min(LCP[p], cap) in the narrowest width
+// that holds cap.  Row p with V[p] = v >= 1 is the split row of a right-maximal repeat of v cells exactly when the nearest q < p
+// with V[q] <= v has V[q] < v; the repeat's rows are then [q, e), e the nearest row behind p with V[e] < v, or n.  Both are
+// nearest-smaller-value searches, answered through a tree of minima: level 0 is V, an entry of level l + 1 the minimum of a
+// node of kRepFanout consecutive entries of level l, up to the first level that is one node.  The levels lie back to back in
+// one array, level l at rep_off(n, l) with rep_cnt(n, l) = ceil(n / 64^l) entries, so a search carries (level, index) and
+// needs no table.  A search scans the entries of its own node on its side, then climbs: at each level the siblings of its
+// ancestor on that side, nearest first; at the first that qualifies it descends, at each level to the nearest child that
+// qualifies (the node's minimum does, so one child does).
+//   Loops: the climb and the descent take at most kRepFanout reads per level each, 2 * levels * kRepFanout per search.
+//   Bounds: a level's index stays below rep_cnt of that level: the backward scan goes down from an index that is, the forward
+//   scan and both descents clamp at it (child i * 64 of entry i < ceil(c / 64) is below c).  Nothing waits for another thread.
+static constexpr u64 kRepFanout = 64;
+GRL_HD u64 rep_cnt(u64 n, u32 l) { return ((n - 1) >> (6 * l)) + 1; }               // (n >= 1, l <= 10)
+static inline u32 rep_levels(u64 n) { u32 L = 1; while (rep_cnt(n, L - 1) > kRepFanout) L++; return L; }
+static inline u64 rep_entries(u64 n) { u64 s = 0; for (u32 l = 0; l < rep_levels(n); l++) s += rep_cnt(n, l); return s; }
+template <class VT>
+struct RepGlobalRd {         // entry j of level l, which starts at `off`
+    const VT *tree;
+    GRL_DEV u64 operator()(u32, u64 off, u64 j) const { return (u64)tree[off + j]; }
+};
+static constexpr u64 kRepNone = ~0ull;
+// the nearest q < p with V[q] <= v, or kRepNone; top = the highest level the search looked at
+template <class RD>
+GRL_DEV u64 rep_search_back(const RD &rd, u64 n, u32 levels, u64 p, u64 v, u32 &top) {
+    u64 i = p, off = 0;
+    u32 l = 0;
+    bool found = false;
+    while (l < levels) {
+        const u64 base = i & ~(kRepFanout - 1);
+        u64 j = i;
+        while (j > base) {
+            j--;
+            if (rd(l, off, j) <= v) { found = true; break; }
+        }
+        if (found) { i = j; break; }
+        off += rep_cnt(n, l);
+        l++; i >>= 6;
+    }
+    top = l < levels ? l : levels - 1;
+    if (!found) return kRepNone;
+    while (l > 0) {
+        l--;
+        const u64 c = rep_cnt(n, l), first = i * kRepFanout;
+        off -= c;
+        u64 j = first + kRepFanout - 1 < c ? first + kRepFanout - 1 : c - 1;
+        while (j > first && !(rd(l, off, j) <= v)) j--;
+        i = j;
+    }
+    return i;
+}
+// the nearest q > p with V[q] < v, or n
+template <class RD>
+GRL_DEV u64 rep_search_fwd(const RD &rd, u64 n, u32 levels, u64 p, u64 v, u32 &top) {
+    u64 i = p, off = 0;
+    u32 l = 0;
+    bool found = false;
+    while (l < levels) {
+        const u64 c = rep_cnt(n, l);
+        const u64 end = (i | (kRepFanout - 1)) + 1 < c ? (i | (kRepFanout - 1)) + 1 : c;
+        u64 j = i + 1;
+        for (; j < end; j++)
+            if (rd(l, off, j) < v) { found = true; break; }
+        if (found) { i = j; break; }
+        off += c;
+        l++; i >>= 6;
+    }
+    top = l < levels ? l : levels - 1;
+    if (!found) return n;
+    while (l > 0) {
+        l--;
+        const u64 c = rep_cnt(n, l), first = i * kRepFanout;
+        off -= c;
+        const u64 end = first + kRepFanout < c ? first + kRepFanout : c;
+        u64 j = first;
+        while (j + 1 < end && !(rd(l, off, j) < v)) j++;
+        i = j;
+    }
+    return i;
+}
+template <class VT>
+struct RepMinFn {            // the generic form of a level: entry i = the minimum of its node
+    const VT *src; u64 ns; VT *dst;
+    GRL_DEV void operator()(u64 i) const {
+        const u64 a = i * kRepFanout, b = a + kRepFanout < ns ? a + kRepFanout : ns;
+        VT m = src[a];
+        for (u64 j = a + 1; j < b; j++) m = src[j] < m ? src[j] : m;
+        dst[i] = m;
+    }
+};
+// Left-maximality.  HB has a bit at every row whose BWT symbol is the separator and at the first row of every record that does
+// not continue the record in front of it with the same symbol (a foreign image may split a run): the rows at which the BWT
+// symbol may differ from the row before.  Rows [lo, e) hold one and the same symbol that is not the separator exactly when
+// HB has no bit in (lo, e): a separator at row lo is seen at row lo + 1 < e, which is a separator's row or a record's first.
+// The records are read in F order, sorted by (symbol, start): a record continues its predecessor there when it continues it in the BWT.
+struct RepHeadFn {           // for_each over the R records
+    const FmKey *key; const idx_t *slf; u64 n; u64 *hb;
+    GRL_DEV void operator()(u64 j) const {
+        const FmKey kj = key[j];
+        const u64 pos = kj.start();
+        if ((u64)slf[j + 1] == (u64)slf[j] || pos >= n) return;            // (an empty record heads nothing)
+        if (j) {
+            const FmKey kp = key[j - 1];
+            if (kp.sym() == kj.sym() && kp.start() + ((u64)slf[j] - (u64)slf[j - 1]) == pos) return;
+        }
+        prim::atomic_or(&hb[pos >> 6], 1ull << (pos & 63));
+    }
+};
+struct RepSepFn {            // for_each over the n_strings rows of F that start with the separator: their BWT positions (KmerStepFn's step)
+    const RankCell *frc; const FmKey *key; const idx_t *slf; u64 n; u64 *hb;
+    GRL_DEV void operator()(u64 i) const {
+        const u64 j = run_of_row(frc, i);
+        const u64 pos = key[j].start() + (i - (u64)slf[j]);
+        if (pos < n) prim::atomic_or(&hb[pos >> 6], 1ull << (pos & 63));
+    }
+};
+struct RepHeads {            // is the repeat of rows [lo, e) left-maximal
+    const u64 *hb; const idx_t *hrank;
+    GRL_DEV bool operator()(u64 lo, u64 e) const { return rank1(hb, hrank, e) > rank1(hb, hrank, lo + 1); }
+};
+struct RepFilter {           // the table's entries among the repeats inside the length bounds
+    u64 rb, re, cmin, cmax; bool maximal;
+    GRL_DEV bool operator()(u64 p, u64 count, bool mx) const { return p >= rb && p < re && count >= cmin && count <= cmax && (mx || !maximal); }
+};
+struct RepRowFn {            // the repeat that row p, of value v, splits: its rows [lo, e) and whether it is left-maximal
+    u64 n; u32 levels; u64 minl, maxl; RepHeads heads; RepFilter flt;
+    // far: the searches of this row, 0 to 2, that looked above level 1 -- in the tile kernel, that left their tile
+    template <class RD>
+    GRL_DEV bool operator()(const RD &rd, u64 p, u64 v, u64 &lo, u64 &e, bool &mx, u32 &far) const {
+        far = 0;
+        if (v < minl || v > maxl) return false;
+        u32 top = 0;
+        lo = rep_search_back(rd, n, levels, p, v, top);
+        far += top >= 2u ? 1u : 0u;
+        if (lo == kRepNone || rd(0, 0, lo) >= v) return false;
+        e = rep_search_fwd(rd, n, levels, p, v, top);
+        far += top >= 2u ? 1u : 0u;
+        mx = heads(lo, e);
+        return true;
+    }
+};
+template <class VT>
+struct RepStatIn {           // the generic form's counters: 0 the repeats, 1 the maximal ones, 2 their lengths, 3 their counts
+    const VT *tree; RepRowFn row; int f;
+    GRL_DEV u64 operator()(u64 p) const {
+        u64 lo = 0, e = 0;
+        bool mx = false;
+        u32 top;
+        const u64 v = (u64)tree[p];
+        if (!row(RepGlobalRd<VT>{tree}, p, v, lo, e, mx, top)) return 0;
+        return f == 0 ? 1ull : f == 1 ? (mx ? 1ull : 0ull) : f == 2 ? v : e - lo;
+    }
+};
+template <class VT>
+struct RepSelPred {
+    const VT *tree; RepRowFn row;
+    GRL_DEV bool operator()(u64 p) const {
+        u64 lo = 0, e = 0;
+        bool mx = false;
+        u32 top;
+        return row(RepGlobalRd<VT>{tree}, p, (u64)tree[p], lo, e, mx, top) && row.flt(p, e - lo, mx);
+    }
+};
+template <class VT>
+struct RepEmitFn {           // the emit of both forms, prim::for_each_set_bit over the selected rows: the two searches once more, in the tree in memory
+    const VT *tree; RepRowFn row; u64 *lo, *count, *len, *split;
+    GRL_DEV void operator()(u64 p, u64 e) const {
+        u64 a = 0, b = 0;
+        bool mx = false;
+        u32 top;
+        const u64 v = (u64)tree[p];
+        (void)row(RepGlobalRd<VT>{tree}, p, v, a, b, mx, top);
+        if (lo) lo[e] = a;
+        if (count) count[e] = b - a;
+        if (len) len[e] = v;
+        if (split) split[e] = p;
+    }
+};
+
 struct Image {
     // ---- opening an image: the one parse of the 16 header bytes, the one test of a cell width, the one dispatch on it -------
     struct ImageHeader {
@@ -1861,6 +2040,15 @@ struct Image {
         u64 k = 0, n = 0, n_strings = 0, n_distinct = 0, n_windows = 0, n_selected = 0, largest_count = 0, passes = 0, length_passes = 0, forward_steps = 0;
         u64 tile_rows = kKmerTileRows, tile_kmers = kKmerTileEntries, stage_bytes = kKmerStageBytes, scratch_bytes = 0;
     };
+#ifdef GRLBWT_PRIM_HIP
+    static constexpr u64 kRepTileRows = prim::kRepTile;
+#else
+    static constexpr u64 kRepTileRows = kRepFanout * kRepFanout;      // (the serial form has no tiles: the figure the device library reports)
+#endif
+    struct RepeatInfo {       // of the last fm_repeats that got as far as counting
+        u64 n = 0, n_strings = 0, min_len = 0, max_len = 0, passes = 0, n_repeats = 0, n_maximal = 0, n_selected = 0, longest = 0, largest_count = 0;
+        u64 value_bytes = 0, tile_rows = kRepTileRows, tree_fanout = kRepFanout, tree_levels = 0, far_searches = 0, scratch_bytes = 0;
+    };
     struct FmIndex {
         u64 n = 0, R = 0, k = 0, sigma = 0, sepval = 0;
         u32 sep = 0, top_entries = 0;
@@ -1885,6 +2073,7 @@ struct Image {
         mutable LcpInfo linfo;    // of the last fm_lcp
         mutable SaInfo sinfo;     // of the last fm_sa
         mutable KmerInfo kinfo;   // of the last fm_kmers that got as far as counting
+        mutable RepeatInfo rinfo; // of the last fm_repeats that got as far as counting
         mutable OverlapInfo oinfo; // of the last fm_overlaps, fm_overlaps_of or fm_overlap_targets
         u64 extract_bytes() const { return (T.n + xq.n + xc.n) * sizeof(idx_t); }
         u64 bytes() const {
@@ -2485,6 +2674,113 @@ struct Image {
                 prim::for_each_set_bit<idx_t>(n, sel, L.brank.p, KmerEmitFn<cell_t>{step, cnt, k, (cell_t *)cells, lo, count}, "kmer.decode_plain");
         });
         prim::sync();
+    }
+    // ---- the right-maximal and maximal repeats (functor block "the right-maximal and maximal repeats").  Everything
+    // that can refuse the call runs before the first store: the arguments, the memory, the passes (an image that is not the BWT
+    // of a collection), the capacity.  Scratch: the LCP passes', the values with their minima (value_bytes * n * 64 / 63), a
+    // word of ranks per 64 rows for the run heads; the heads and the selection reuse two bit-vectors of the passes.
+    //   Device form: prim::repeat_minima (a wave per node) and prim::repeat_search (a tile of kRepTileRows rows per workgroup, the
+    //   tile's values and node minima in LDS; counts and selects in one pass).  Generic form, the serial stand-in's and with
+    //   GRLBWT_DEV_REPEAT_SEARCH=f the device's: a for_each per level, four reduces and bitvector_from_pred over functors that
+    //   search the tree in memory.  The emit is the same in both: for_each_set_bit over the selected rows, which repeats their
+    //   two searches in the tree in memory (no bytes of scratch per row); a tile kernel for it measured slower and is not kept.
+    //   Loops: at most cap - 1 LCP passes; the levels (at most 11); a search is bounded (rep_search_back).  Nothing waits for
+    //   another thread; the only atomics are the ORs that set the head bits.
+    static constexpr u32 kRepMaximal = 1u;
+    template <class VT>
+    static void fm_repeats_t(const FmIndex &F, FmLcp &L, RepeatInfo &ri, const RepFilter &flt, u64 cap, u64 *lo, u64 *count, u64 *len, u64 *split,
+                             u64 capacity, bool table, u64 &n_repeats) {
+        const u64 n = F.n, nw = FmLcp::words_of(n);
+        const u32 levels = (u32)ri.tree_levels;
+        DBuf<VT> tree(rep_entries(n));
+        DBuf<idx_t> hrank(nw + 1);
+        {
+            LcpInfo li;
+            std::vector<u64> ra, su;
+            L.run(F, cap, tree.p, (int)sizeof(VT), li, ra, su);
+            ri.passes = li.passes;
+        }
+#ifdef GRLBWT_PRIM_HIP
+        const bool tiles = prim::sw().dev_repeat_search != 'f';
+#endif
+        {
+            u64 off = 0;
+            for (u32 l = 0; l + 1 < levels; l++) {
+                const u64 ns = rep_cnt(n, l), nd = rep_cnt(n, l + 1);
+#ifdef GRLBWT_PRIM_HIP
+                if (tiles) prim::repeat_minima<VT>(tree.p + off, ns, tree.p + off + ns, nd);
+                else
+#endif
+                    prim::for_each(nd, RepMinFn<VT>{tree.p + off, ns, tree.p + off + ns}, "repeat.minima_plain");
+                off += ns;
+            }
+        }
+        u64 *hb = L.Bold, *sel = L.Sold;
+        prim::dev_memset(hb, 0, nw * 8);
+        prim::dev_memset(sel, 0, nw * 8);
+        prim::for_each(F.R, RepHeadFn{F.key.p, F.slf.p, n, hb}, "repeat.heads");
+        prim::for_each(F.k, RepSepFn{L.frc.p, F.key.p, F.slf.p, n, hb}, "repeat.separators");
+        (void)prim::exclusive_scan<idx_t>(nw, PopcIn{hb}, hrank.p, true, "repeat.head_ranks");
+        const RepRowFn row{n, levels, ri.min_len, ri.max_len ? ri.max_len : ~0ull, RepHeads{hb, hrank.p}, flt};
+#ifdef GRLBWT_PRIM_HIP
+        if (tiles) {
+            u64 st[5];
+            prim::repeat_search<VT, RepRowFn>(n, tree.p, row, sel, st);
+            ri.n_repeats = st[0]; ri.n_maximal = st[1]; ri.far_searches = st[2]; ri.longest = st[3]; ri.largest_count = st[4];
+        } else
+#endif
+        {
+            ri.n_repeats = prim::reduce_sum<u64>(n, RepStatIn<VT>{tree.p, row, 0}, "repeat.count");
+            ri.n_maximal = prim::reduce_sum<u64>(n, RepStatIn<VT>{tree.p, row, 1}, "repeat.maximal");
+            ri.longest = prim::reduce_max<u64>(n, RepStatIn<VT>{tree.p, row, 2}, "repeat.longest");
+            ri.largest_count = prim::reduce_max<u64>(n, RepStatIn<VT>{tree.p, row, 3}, "repeat.largest");
+            prim::bitvector_from_pred(n, RepSelPred<VT>{tree.p, row}, sel, "repeat.select");
+        }
+        ri.n_selected = (u64)prim::exclusive_scan<idx_t>(nw, PopcIn{sel}, L.brank.p, true, "repeat.select_ranks");
+        prim::sync();
+        F.rinfo = ri;
+        n_repeats = ri.n_selected;
+        if (table && ri.n_selected > capacity)
+            throw prim::Error(-22, "fm repeats: " + std::to_string(ri.n_selected) + " repeats, more than the output arrays hold");
+        if (!table || ri.n_selected == 0) return;
+        prim::for_each_set_bit<idx_t>(n, sel, L.brank.p, RepEmitFn<VT>{tree.p, row, lo, count, len, split}, "repeat.emit");
+        prim::sync();
+    }
+    static void fm_repeats(const FmIndex &F, u64 min_len, u64 max_len, u64 min_count, u64 max_count, u32 flags, u64 row_begin, u64 row_end, u64 *lo,
+                           u64 *count, u64 *len, u64 *split, u64 capacity, u64 &n_repeats, bool want_n) {
+        n_repeats = 0;
+        if (flags & ~kRepMaximal) throw prim::Error(-22, "fm repeats: unknown flag bits " + std::to_string(flags & ~kRepMaximal));
+        if (min_len == 0) min_len = 1;
+        if (max_len && max_len < min_len)
+            throw prim::Error(-22, "fm repeats: max_len " + std::to_string(max_len) + " is below min_len " + std::to_string(min_len));
+        const u64 n = F.n;
+        if (row_end > n) row_end = n;                            // (UINT64_MAX: n_rows)
+        if (row_begin > row_end)
+            throw prim::Error(-22, "fm repeats: rows [" + std::to_string(row_begin) + ", " + std::to_string(row_end) + ") are no window of " + std::to_string(n) + " rows");
+        const bool table = lo || count || len || split;
+        if (!table && !want_n) throw prim::Error(-22, "fm repeats: no output");
+        if (((uintptr_t)lo | (uintptr_t)count | (uintptr_t)len | (uintptr_t)split) & 7) throw prim::Error(-22, "fm repeats: an output is not aligned to 8 bytes");
+        RepeatInfo ri;
+        ri.n = n; ri.n_strings = F.k; ri.min_len = min_len; ri.max_len = max_len;
+        if (n == 0) { F.rinfo = ri; return; }
+        // the values: min(LCP, cap) with cap = max_len + 1, in the narrowest width that holds cap; without max_len whole, in 4 or 8 bytes
+        const u64 lim = n >> 32 ? ~0ull : 0xFFFFFFFFull;
+        const u64 cap = max_len && max_len < lim ? max_len + 1 : lim;
+        const int vb = cap <= 0xFFull ? 1 : cap <= 0xFFFFull ? 2 : cap <= 0xFFFFFFFFull ? 4 : 8;
+        ri.value_bytes = (u64)vb; ri.tree_levels = rep_levels(n);
+        const u64 nw = FmLcp::words_of(n);
+        ri.scratch_bytes = FmLcp::scratch_bytes(n) + rep_entries(n) * (u64)vb + (nw + 1) * sizeof(idx_t) + (n / kRepTileRows + 1) * 4 * 5 * 8;
+        if (n >= ((u64)1 << 62) || ri.scratch_bytes > prim::mem_available())
+            throw prim::Error(-12, "fm repeats: the passes need " + std::to_string(ri.scratch_bytes) + " bytes of device memory, more than is free");
+        const RepFilter flt{row_begin, row_end, min_count > 2 ? min_count : 2, max_count ? max_count : ~0ull, (flags & kRepMaximal) != 0};
+        FmLcp L;
+        L.alloc(F);
+        switch (vb) {
+            case 1: fm_repeats_t<u8>(F, L, ri, flt, cap, lo, count, len, split, capacity, table, n_repeats); break;
+            case 2: fm_repeats_t<u16>(F, L, ri, flt, cap, lo, count, len, split, capacity, table, n_repeats); break;
+            case 4: fm_repeats_t<u32>(F, L, ri, flt, cap, lo, count, len, split, capacity, table, n_repeats); break;
+            default: fm_repeats_t<u64>(F, L, ri, flt, cap, lo, count, len, split, capacity, table, n_repeats); break;
+        }
     }
     static void fm_locate(const FmIndex &F, const u64 *rows, u64 nr, u64 max_steps, u64 *str, u64 *ofs) {
         if (!F.locate) throw prim::Error(-22, "fm locate: the index was made without the structures for locating");

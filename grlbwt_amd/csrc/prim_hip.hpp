@@ -2672,6 +2672,133 @@ inline void kmer_decode(u64 total, u64 k, const u64 *sel, const IDX *selrank, u6
     after_launch("kmer.decode");
 }
 
+// ------------------------------------------------------------------ repeats: nearest smaller values through a tree of minima (grlbwt_fm_repeats)
+// `tree` holds the values V of the n rows and, back to back behind them, the levels of minima: an entry of level l + 1 is the
+// minimum of a node of 64 consecutive entries of level l (image_impl.hpp, "the right-maximal and maximal repeats", has the
+// layout and the search).  repeat_minima makes one level from the one below: a wave reads a node, one entry per lane, and
+// takes the minimum through shuffles; lane 0 stores it.
+//   Bounds: node i < nd reads src[i * 64 + lane] only below ns; nd = ceil(ns / 64), so lane 0 always has an entry.
+template <class VT>
+__global__ void __launch_bounds__(kBlock) k_repeat_minima(const VT *src, u64 ns, VT *dst, u64 nd) {
+    const u32 lane = threadIdx.x & 63u;
+    const u64 stride = (u64)gridDim.x * (kBlock / 64);
+    for (u64 i = (u64)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6); i < nd; i += stride) {
+        const u64 j = i * 64 + lane;
+        u64 m = j < ns ? (u64)src[j] : ~0ull;
+        for (int d = 32; d >= 1; d >>= 1) { const u64 o = __shfl_xor(m, d); m = o < m ? o : m; }
+        if (lane == 0) dst[i] = (VT)m;
+    }
+}
+template <class VT>
+inline void repeat_minima(const VT *src, u64 ns, VT *dst, u64 nd) {
+    if (nd == 0) return;
+    prof_begin("repeat.minima", ns * sizeof(VT));
+    hipLaunchKernelGGL((k_repeat_minima<VT>), dim3(grid_for(nd, kBlock / 64)), dim3(kBlock), 0, rt().stream, src, ns, dst, nd);
+    prof_end();
+    after_launch("repeat.minima");
+}
+// The search kernel.  A workgroup takes a tile of kRepTile = 64 * 64 consecutive rows: exactly one node of level 1, so the
+// tile's values and the 64 minima of its level-0 nodes (read from the stored level 1) are all a search needs until it leaves
+// the tile; both lie in LDS, (kRepTile + 64) * sizeof(VT) bytes.  RepTileRd answers the search's reads from LDS where they
+// fall into the tile and from memory elsewhere, so the search itself is the generic one, row(rd, p, v, lo, e, mx, far):
+// whether row p of value v splits a repeat, its rows [lo, e), whether it is left-maximal, and how many of its searches looked
+// above level 1, that is, left the tile.  Lanes take consecutive rows, a wave the 64 rows of one word of the bit-vector.
+// row.flt(p, e - lo, mx) selects; the wave's ballot is the word of `sel`, stored by lane 0; the counters (repeats, maximal
+// ones, searches that left the tile, longest, largest count) go per wave through shuffles into part[5 * wave].
+//   Bounds: row p = tile * kRepTile + x < n is tested before V is read; LDS slots x < kRepTile and tid < 64; level-1 entry
+//   tile * 64 + tid is read only below its count; word p / 64 with p < n is below ceil(n / 64).
+//   Loops: kRepTile / kBlock rows per lane, the searches' (bounded, image_impl.hpp).  The one barrier is reached by every thread;
+//   ballots run with all lanes of the wave.  One writer per word, no atomics.
+static constexpr int kRepTile = 4096;
+// The reader issues ONE volatile LDS load and ONE global load, never a load through a pointer chosen between LDS and memory.
+// With two plain LDS loads and the global load behind three returns (and the LDS arrays reached through pointers kept in the
+// reader), AMD clang 22.0.0git (roc-7.2.0) at -O3 for gfx950 turned the three into one flat_load whose address comes from a phi.  In that ISA the
+// address registers were written on three paths -- the two LDS slots (src_shared_base and the slot) and, by a v_mov_b64 from
+// tree + 4 * (off + j) that sits in the block of the lanes at level 0, the memory address -- and were marked implicit-def on
+// the fourth, the lanes at level >= 1 that read memory: the reads of a search that has left its tile.  A kernel built that
+// way ran every single-tile input and took a memory fault on the first input of 4097 rows; the searches and the kernel's
+// body, run on the host with checked indices, stay inside the tree.  That the undefined address was the cause, and a defect
+// of the compiler, is supposed, not shown: this form has no phi of addresses (its ISA has the flat_load on the LDS aperture
+// alone and separate global_loads) and runs the same inputs.
+template <class VT>
+__device__ __forceinline__ VT *rep_tile_lds() {       // kRepTile values, then the 64 minima of their nodes
+    __shared__ VT s_tile[kRepTile + 64];
+    return s_tile;
+}
+template <class VT>
+struct RepTileRd {
+    const VT *tree; u64 tile;
+    __device__ __forceinline__ u64 operator()(u32 l, u64 off, u64 j) const {
+        const bool in0 = l == 0 && (j >> 12) == tile, in1 = l == 1 && (j >> 6) == tile;
+        if (in0 || in1) return (u64)((const volatile VT *)rep_tile_lds<VT>())[in0 ? j & (u64)(kRepTile - 1) : (u64)kRepTile + (j & 63)];
+        return (u64)tree[off + j];
+    }
+};
+template <class VT, class ROW>
+__global__ void __launch_bounds__(kBlock) k_repeat_search(u64 n, const VT *tree, ROW row, u64 *sel, u64 *part) {
+    static_assert(kRepTile == 64 * 64, "a tile is one node of level 1");
+    VT *s_v = rep_tile_lds<VT>(), *s_m = s_v + kRepTile;
+    const u32 tid = threadIdx.x, lane = tid & 63u;
+    const u64 tile = blockIdx.x, row0 = tile * kRepTile;
+    for (u32 x = tid; x < (u32)kRepTile; x += kBlock) s_v[x] = row0 + x < n ? tree[row0 + x] : (VT)0;
+    if (tid < 64u) {
+        const u64 c1 = ((n - 1) >> 6) + 1;
+        s_m[tid] = n > 64 && tile * 64 + tid < c1 ? tree[n + tile * 64 + tid] : (VT)0;      // (64 rows or fewer: the values are the only level)
+    }
+    __syncthreads();
+    const RepTileRd<VT> rd{tree, tile};
+    u64 nrep = 0, nmax = 0, far = 0, longest = 0, largest = 0;
+    for (u32 x = tid; x < (u32)kRepTile; x += kBlock) {
+        const u64 p = row0 + x;
+        if (row0 + (x - lane) >= n) break;                       // (wave-uniform: the wave's word lies behind the rows)
+        u64 a = 0, b = 0;
+        bool mx = false, is = false;
+        u32 left = 0;
+        const u64 v = (u64)s_v[x];
+        if (p < n) is = row(rd, p, v, a, b, mx, left);
+        far += (u64)left;
+        if (is) {
+            nrep++;
+            nmax += mx ? 1ull : 0ull;
+            longest = v > longest ? v : longest;
+            largest = b - a > largest ? b - a : largest;
+        }
+        const unsigned long long m = __ballot(is && row.flt(p, b - a, mx));
+        if (lane == 0) sel[p >> 6] = m;
+    }
+    for (int d = 32; d >= 1; d >>= 1) {
+        nrep += __shfl_xor(nrep, d); nmax += __shfl_xor(nmax, d); far += __shfl_xor(far, d);
+        const u64 o1 = __shfl_xor(longest, d), o2 = __shfl_xor(largest, d);
+        longest = o1 > longest ? o1 : longest;
+        largest = o2 > largest ? o2 : largest;
+    }
+    if (lane == 0) {
+        u64 *q = part + 5 * ((u64)blockIdx.x * (kBlock / 64) + (tid >> 6));
+        q[0] = nrep; q[1] = nmax; q[2] = far; q[3] = longest; q[4] = largest;
+    }
+}
+struct RepPartIn {
+    const u64 *part; int f;
+    GRL_DEV u64 operator()(u64 i) const { return part[5 * i + (u64)f]; }
+};
+// sel: ceil(n / 64) words, every one written; st: the repeats, the maximal ones, the searches that left their tile, the longest, the largest count
+template <class VT, class ROW>
+inline void repeat_search(u64 n, const VT *tree, ROW row, u64 *sel, u64 st[5]) {
+    for (int f = 0; f < 5; f++) st[f] = 0;
+    if (n == 0) return;
+    const u64 tiles = (n + kRepTile - 1) / kRepTile;
+    if (tiles > 0x7FFFFFFFull) throw Error(-75, "repeat_search: more rows than one launch takes");
+    const u64 nparts = tiles * (kBlock / 64);
+    u64 *part = (u64 *)dev_alloc(nparts * 40);
+    prof_begin("repeat.search", n * sizeof(VT) + n / 8);
+    hipLaunchKernelGGL((k_repeat_search<VT, ROW>), dim3((unsigned)tiles), dim3(kBlock), 0, rt().stream, n, tree, row, sel, part);
+    prof_end();
+    after_launch("repeat.search");
+    for (int f = 0; f < 3; f++) st[f] = reduce_sum<u64>(nparts, RepPartIn{part, f}, "repeat.sums");
+    for (int f = 3; f < 5; f++) st[f] = reduce_max<u64>(nparts, RepPartIn{part, f}, "repeat.maxima");
+    dev_free(part);
+}
+
 // ------------------------------------------------------------------ the strings behind row ranges (grlbwt_docs_count / grlbwt_docs_list)
 // nr ranges of rows, range r = [lo[r], lo[r] + (roff[r + 1] - roff[r])), laid back to back: position e of the sequence,
 // roff[r] <= e < roff[r + 1], is row lo[r] + (e - roff[r]).  roff is the exclusive scan of the sizes with the total at nr.  Both

@@ -42,6 +42,7 @@ ABI_SYMBOLS = [
     "grlbwt_fm_lcp", "grlbwt_fm_lcp_info_get",
     "grlbwt_fm_sa", "grlbwt_fm_sa_info_get",
     "grlbwt_fm_kmers", "grlbwt_fm_kmer_info_get",
+    "grlbwt_fm_repeats", "grlbwt_fm_repeat_info_get",
     "grlbwt_docs_create", "grlbwt_docs_destroy", "grlbwt_docs_info_get", "grlbwt_docs_count", "grlbwt_docs_list",
     "grlbwt_merge_create", "grlbwt_merge_info_get", "grlbwt_merge_emit", "grlbwt_merge_interleave", "grlbwt_merge_destroy",
     "grlbwt_merge_files",
@@ -53,6 +54,7 @@ FM_LOCATE = 1
 FM_CHECKPOINTS = 2
 FM_EXTRACT = 4
 FM_OVERLAP_PROPER = 1
+FM_REPEATS_MAXIMAL = 1
 UINT64_MAX = 2 ** 64 - 1
 DOCS_OCCURRENCES = 1
 SELECT_KEEP = 1
@@ -116,6 +118,12 @@ class SaInfo(C.Structure):
 class KmerInfo(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in ("k", "n_rows", "n_strings", "n_distinct", "n_windows", "n_selected", "largest_count", "passes",
                                           "length_passes", "forward_steps", "tile_rows", "tile_kmers", "stage_bytes", "scratch_bytes")]
+
+
+class RepeatInfo(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("n_rows", "n_strings", "min_len", "max_len", "passes", "n_repeats", "n_maximal", "n_selected",
+                                          "longest", "largest_count", "value_bytes", "tile_rows", "tree_fanout", "tree_levels",
+                                          "far_searches", "scratch_bytes")]
 
 
 class DocsInfo(C.Structure):
@@ -291,6 +299,8 @@ def load_library(path=None, allow_test_standin=False):
     L.grlbwt_fm_sa_info_get.argtypes = [vp, C.POINTER(SaInfo)]
     L.grlbwt_fm_kmers.argtypes = [vp, vp, u64, u64, u64, u64, u64, i32, vp, vp, vp, u64, C.POINTER(u64), vp, u64]
     L.grlbwt_fm_kmer_info_get.argtypes = [vp, C.POINTER(KmerInfo)]
+    L.grlbwt_fm_repeats.argtypes = [vp, vp, u64, u64, u64, u64, C.c_uint32, u64, u64, vp, vp, vp, vp, u64, C.POINTER(u64)]
+    L.grlbwt_fm_repeat_info_get.argtypes = [vp, C.POINTER(RepeatInfo)]
     L.grlbwt_docs_create.argtypes = [vp, vp, C.c_uint32, C.POINTER(vp)]
     L.grlbwt_docs_destroy.argtypes = [vp, vp]
     L.grlbwt_docs_info_get.argtypes = [vp, C.POINTER(DocsInfo)]
@@ -906,6 +916,58 @@ class FmIndex:
         """The counters of the last kmers() / kmer_spectrum() on this index that got as far as counting."""
         out = KmerInfo()
         rc = self.ctx.L.grlbwt_fm_kmer_info_get(self._h, C.byref(out))
+        if rc != OK:
+            raise GrlbwtError(rc, self.ctx.L.grlbwt_strerror(rc).decode())
+        return _as_dict(out)
+
+    def repeats_raw(self, min_len=1, max_len=0, min_count=2, max_count=0, flags=0, row_begin=0, row_end=None, lo_ptr=None, count_ptr=None,
+                    len_ptr=None, split_ptr=None, capacity=0):
+        """grlbwt_fm_repeats as it is: device pointers (None: not wanted) for lo, count, len and split (uint64 per entry), room for
+        `capacity` entries.  Returns the number of entries.  More than `capacity` with an array given: GrlbwtError whose n_repeats
+        attribute is that number, and nothing is written."""
+        got = C.c_uint64()
+        try:
+            self.ctx._ck(self.ctx.L.grlbwt_fm_repeats(self.ctx._h, self._h, min_len, max_len, min_count, max_count, flags, row_begin,
+                                                      UINT64_MAX if row_end is None else row_end, C.c_void_p(lo_ptr), C.c_void_p(count_ptr),
+                                                      C.c_void_p(len_ptr), C.c_void_p(split_ptr), capacity, C.byref(got)))
+        except GrlbwtError as e:
+            e.n_repeats = got.value
+            raise
+        return got.value
+
+    def repeats(self, min_len=1, max_len=0, min_count=2, max_count=0, maximal=False, rows=None, split=False):
+        """The right-maximal repeats of the collection (maximal=True: those that are left-maximal too) with max(min_len, 1) <= length
+        <= max_len (0: no bound) and max(min_count, 2) <= count <= max_count (0: no bound) whose split row lies in rows = (begin, end)
+        (None: all rows), in ascending split row: (lo, count, length) as numpy uint64 arrays, with split=True (lo, count, length,
+        split).  [lo, lo + count) are the rows count() answers for the repeat's cells.  Sized by the idiom of mems(): one call that
+        reports the number, one that fills the table."""
+        import numpy as np
+        on_device = self.ctx.L.grlbwt_backend_name() == b"hip-gfx950"      # (the test stand-in's "device" is host memory)
+        if on_device:
+            import torch
+        rb, re = (0, None) if rows is None else rows
+        flags = FM_REPEATS_MAXIMAL if maximal else 0
+        n = self.repeats_raw(min_len, max_len, min_count, max_count, flags, rb, re)
+        bufs = []
+        for _ in range(4 if split else 3):
+            if on_device:
+                t = torch.zeros(max(8 * n, 8), dtype=torch.uint8, device="cuda:0")
+                bufs.append((t, t.data_ptr()))
+            else:
+                a = np.zeros(max(8 * n, 8), dtype=np.uint8)
+                bufs.append((a, a.ctypes.data))
+        if on_device:
+            torch.cuda.synchronize()
+        got = self.repeats_raw(min_len, max_len, min_count, max_count, flags, rb, re, bufs[0][1], bufs[1][1], bufs[2][1],
+                               bufs[3][1] if split else None, n)
+        if on_device:
+            torch.cuda.synchronize()
+        return tuple((b.cpu().numpy() if on_device else b)[:8 * got].copy().view(np.uint64) for b, _ in bufs)
+
+    def repeat_info(self):
+        """The counters of the last repeats() on this index that got as far as counting."""
+        out = RepeatInfo()
+        rc = self.ctx.L.grlbwt_fm_repeat_info_get(self._h, C.byref(out))
         if rc != OK:
             raise GrlbwtError(rc, self.ctx.L.grlbwt_strerror(rc).decode())
         return _as_dict(out)

@@ -753,6 +753,80 @@ int grlbwt_fm_kmers(grlbwt_ctx *ctx, const grlbwt_fm *fm, uint64_t k, uint64_t m
                     uint64_t *n_kmers_out, uint64_t *host_spectrum /* may be NULL */, uint64_t spectrum_bins);
 int grlbwt_fm_kmer_info_get(const grlbwt_fm *fm, grlbwt_fm_kmer_info *out);
 
+/* ---- the right-maximal and maximal repeats of the collection: which row ranges are repeats at all -- the internal nodes of
+ * the generalized suffix tree, what repeat analysis, repeat masking, shared-substring questions and sequence-graph construction
+ * start from.  The other "one pass over the array" that grlbwt_fm_lcp's comment promises: the textbook pass is a serial stack
+ * walk over the LCP array; here it is two nearest-smaller-value searches per row.
+ *
+ * DEFINITIONS, part of the contract.  Rows are those of grlbwt_fm_count, LCP is that of grlbwt_fm_lcp (every terminator a
+ * symbol of its own, LCP[0] = 0).  A REPEAT is a string w of len >= 1 cells, none the separator, that occurs at least twice
+ * in the collection; occurrences may overlap and may lie in one string.  It is RIGHT-MAXIMAL when two occurrences are followed
+ * by different cells (a string's end differs from everything, another string's end included), LEFT-MAXIMAL when two are
+ * preceded by different cells (a string's start differs from everything), MAXIMAL when both.  w is right-maximal exactly when
+ * its row range [lo, lo + count) is an LCP interval of value len: LCP[lo] < len, LCP[lo + count] < len or lo + count = n_rows,
+ * LCP[lo + 1 .. lo + count) all >= len and one of them = len.  Its SPLIT row is the first row p in (lo, lo + count) with
+ * LCP[p] = len: every right-maximal repeat has exactly one, a row is the split of at most one, so there are at most n_rows - 1.
+ * It is left-maximal exactly when the BWT symbols of its rows are not all one and the same symbol other than the separator --
+ * decided on symbols, not on records: an image may hold neighbouring records of one symbol.
+ *
+ * THE TABLE holds the right-maximal repeats with max(min_len, 1) <= len <= max_len (0: no upper bound), max(min_count, 2) <=
+ * count <= max_count (0: none), row_begin <= split < row_end (row_end above n_rows, UINT64_MAX for one, means n_rows) and,
+ * with GRLBWT_FM_REPEATS_MAXIMAL, left-maximal as well -- in ascending split row, the in-order of the suffix tree's internal
+ * nodes.  Entry e owns dev_lo[e], dev_count[e], dev_len[e] and dev_split[e]; any of the four arrays may be NULL.  The window
+ * bounds the output memory, not the work: a partition of [0, n_rows) into windows gives tables that concatenate to the whole
+ * one, and an empty window is legal.  *n_repeats_out is set as soon as the number is known.  With an array given and more
+ * entries than `capacity` the call fails with GRLBWT_EINVAL and writes nothing (the sizing idiom of grlbwt_fm_kmers: first a
+ * call with capacity 0 and no arrays, which succeeds and reports the number).
+ *
+ * ALGORITHM: the passes of grlbwt_fm_lcp write V = min(LCP, cap) into scratch, cap = max_len + 1 in the narrowest of 1, 2 and
+ * 4 bytes that holds it (at most max_len passes; a capped row splits nothing, and comparisons against any len <= max_len stay
+ * exact), without max_len the whole values in 4 bytes, 8 from 2^32 rows on.  Over V stands a tree of minima of tree_fanout
+ * consecutive entries per node, level upon level up to a single node, all levels stored by a build pass (a wave reads a node):
+ * about n_rows / 63 more values.  A row p with min_len <= V[p] <= max_len is a candidate.  Backward: the nearest q < p with
+ * V[q] <= V[p]; p is a split row exactly when V[q] < V[p], and then lo = q.  Forward: the nearest q > p with V[q] < V[p], or
+ * n_rows: lo + count.  A search scans its own node, then climbs: at each level the siblings on its side, and descends into the
+ * nearest whose minimum qualifies: at most 2 * tree_levels * tree_fanout reads, whatever the input -- one string of a single
+ * symbol, whose every forward search ends at the last row, included.  A workgroup takes tile_rows = tree_fanout^2 rows, one
+ * node of level 1, with the tile's values and its 64 node minima in LDS; a search that reaches the tile's edge goes on in the
+ * tree in memory (far_searches counts them).  Left-maximality is a rank difference on a bit-vector that marks every
+ * separator's row and the first row of every record that does not continue its predecessor's symbol: no scan of the range.
+ * The selection is written as ballot words and ranked by a scan; the emit walks the set bits with every lane on a selected
+ * row (the compaction of grlbwt_fm_kmers' generic decode), repeats that row's two searches in the tree in memory and stores
+ * by rank -- consecutive lanes on consecutive entries, one writer per entry, no per-row scratch.  (An emit over the same tiles
+ * with the values in LDS measured 1.4 to 3.4 times slower, since it walks every row of every tile that holds a selected one;
+ * it is not kept.)  No thread waits for another; the only atomics set the head bits.
+ * COST: the LCP passes (grlbwt_fm_lcp's cost model; max_len bounds them), one pass over V per tree level, the search pass,
+ * the emit pass.  Scratch: the passes' 0.9 byte per row and value_bytes * 64 / 63 per row, reported as scratch_bytes.
+ *
+ * GRLBWT_EINVAL before the first store: unknown flag bits; max_len given and below max(min_len, 1); row_begin above the clamped
+ * row_end; every output NULL (the four arrays and n_repeats_out); an array not aligned to 8; a null index; an image that is
+ * not the BWT of a collection (the refusal of grlbwt_fm_lcp's passes).  GRLBWT_ENOMEM, before the first pass, when the scratch
+ * does not fit the free memory.  The call works on any index of grlbwt_fm_create, with or without the locate structures, in
+ * both position widths and on compacted and wide alphabets; it makes no handle and leaves the index, its index_bytes and every
+ * later answer of every other call as they were.  GRLBWT_LCP_ROUND keeps its meaning for the passes.
+ * OUT OF SCOPE: supermaximal repeats; the repeats' cells (grlbwt_fm_locate of row lo, then grlbwt_fm_extract of len cells); a
+ * histogram by length; tandem repeats; a command-line flag; a multi-GPU form.
+ * grlbwt_fm_repeat_info_get: the counters of the last grlbwt_fm_repeats on the index that got as far as counting (a call that
+ * the capacity then refuses included). */
+#define GRLBWT_FM_REPEATS_MAXIMAL 1u      /* only the repeats that are left-maximal too */
+typedef struct grlbwt_fm_repeat_info {
+    uint64_t n_rows, n_strings;
+    uint64_t min_len, max_len;              /* the effective values: min_len at least 1, max_len 0 for none */
+    uint64_t passes;                        /* LCP passes run */
+    uint64_t n_repeats, n_maximal;          /* right-maximal repeats inside the length bounds, ignoring count, window and flag; the left-maximal of them */
+    uint64_t n_selected;                    /* entries of the table */
+    uint64_t longest, largest_count;        /* over n_repeats */
+    uint64_t value_bytes;                   /* width of the values held in scratch */
+    uint64_t tile_rows, tree_fanout, tree_levels;   /* rows per workgroup; entries per node; levels of the tree, the values' included */
+    uint64_t far_searches;                  /* searches of the count pass, two per split row at the most, that left their tile; 0 in the generic form */
+    uint64_t scratch_bytes;
+} grlbwt_fm_repeat_info;
+int grlbwt_fm_repeats(grlbwt_ctx *ctx, const grlbwt_fm *fm, uint64_t min_len, uint64_t max_len /* 0: none */, uint64_t min_count,
+                      uint64_t max_count /* 0: none */, uint32_t repeat_flags, uint64_t row_begin, uint64_t row_end /* UINT64_MAX: n_rows */,
+                      uint64_t *dev_lo, uint64_t *dev_count, uint64_t *dev_len, uint64_t *dev_split /* each may be NULL */,
+                      uint64_t capacity, uint64_t *n_repeats_out);
+int grlbwt_fm_repeat_info_get(const grlbwt_fm *fm, grlbwt_fm_repeat_info *out);
+
 /* ---- the strings behind row ranges: document listing and counting, the question a collection index exists for -- which reads
  * carry this k-mer, which genomes of a pangenome carry this allele, what is the document frequency of a k-mer.  grlbwt_fm_count
  * says how often a pattern occurs and grlbwt_fm_locate where each occurrence lies; these calls say WHICH STRINGS hold it and how
