@@ -45,6 +45,12 @@ struct grlbwt_docs {
     std::unique_ptr<grl64::Image::ImageDocs> d64;
 };
 
+// a compacted de Bruijn graph (grlbwt_debruijn_create): the nodes, the in-edges and the unitigs
+struct grlbwt_debruijn {
+    std::unique_ptr<grl32::Image::ImageDeBruijn> g32;
+    std::unique_ptr<grl64::Image::ImageDeBruijn> g64;
+};
+
 struct grlbwt_ctx {
     uint32_t flags = 0;
     int device = 0;
@@ -55,6 +61,7 @@ struct grlbwt_ctx {
     std::vector<grlbwt_merge *> merges;      // and the merges
     std::vector<grlbwt_select *> selects;    // and the selections
     std::vector<grlbwt_docs *> docs;         // and the document handles
+    std::vector<grlbwt_debruijn *> graphs;   // and the de Bruijn graphs
 };
 
 namespace {
@@ -1804,6 +1811,8 @@ void grlbwt_ctx_destroy(grlbwt_ctx *ctx) {
         ctx->selects.clear();
         for (grlbwt_docs *dc : ctx->docs) delete dc;
         ctx->docs.clear();
+        for (grlbwt_debruijn *g : ctx->graphs) delete g;
+        ctx->graphs.clear();
         ctx->e32.reset(); ctx->e64.reset(); prim::sync(); prim::pool_trim();
         if (--prim::rt().live_ctx <= 0) {      // process-wide debug settings and a borrowed stream end with the last context
             prim::rt().live_ctx = 0;
@@ -2540,6 +2549,74 @@ int grlbwt_docs_list(grlbwt_ctx *ctx, const grlbwt_docs *dc, const uint64_t *dev
     });
     if (n_entries_out) *n_entries_out = n;
     return rc;
+}
+
+int grlbwt_debruijn_create(grlbwt_ctx *ctx, const grlbwt_fm *fm, uint64_t k, uint64_t min_count, uint64_t max_count, uint32_t debruijn_flags,
+                           grlbwt_debruijn **out) {
+    if (out) *out = nullptr;
+    if (!ctx || !fm || !out || !(fm->f32 || fm->f64)) return refuse(ctx);
+    return guarded(ctx, [&] {
+        std::unique_ptr<grlbwt_debruijn> g(new grlbwt_debruijn());
+        if (fm->f32) {
+            g->g32.reset(new grl32::Image::ImageDeBruijn());
+            grl32::Image::debruijn_create(*fm->f32, k, min_count, max_count, debruijn_flags, *g->g32);
+        } else {
+            g->g64.reset(new grl64::Image::ImageDeBruijn());
+            grl64::Image::debruijn_create(*fm->f64, k, min_count, max_count, debruijn_flags, *g->g64);
+        }
+        ctx->graphs.push_back(g.get());
+        *out = g.release();
+    });
+}
+int grlbwt_debruijn_destroy(grlbwt_ctx *ctx, grlbwt_debruijn *graph) {
+    if (!ctx) return GRLBWT_EINVAL;
+    if (!graph) return GRLBWT_OK;
+    auto it = std::find(ctx->graphs.begin(), ctx->graphs.end(), graph);
+    if (it == ctx->graphs.end()) { ctx->err = "de bruijn destroy: not a handle of this context"; return GRLBWT_EINVAL; }
+    ctx->graphs.erase(it);
+    return guarded(ctx, [&] { prim::sync(); delete graph; });
+}
+int grlbwt_debruijn_info_get(const grlbwt_debruijn *graph, grlbwt_debruijn_info *out) {
+    if (!graph || !out || !(graph->g32 || graph->g64)) return GRLBWT_EINVAL;
+    auto fill = [&](const auto &G, uint64_t tile_nodes, uint64_t tile_cells) {
+        const auto &i = G.i;
+        out->k = i.k; out->n_rows = i.n; out->n_strings = i.n_strings; out->n_distinct = i.n_distinct; out->n_nodes = i.n_nodes; out->n_edges = i.n_edges;
+        out->n_unitigs = i.n_unitigs; out->n_circular = i.n_circular; out->longest_unitig = i.longest; out->n_cells = i.n_cells;
+        out->max_in_degree = i.max_in; out->max_out_degree = i.max_out; out->passes = i.passes; out->length_passes = i.length_passes;
+        out->backward_steps = i.backward_steps; out->jump_rounds = i.jump_rounds; out->tile_nodes = tile_nodes; out->tile_cells = tile_cells;
+        out->handle_bytes = G.held_bytes(); out->scratch_bytes = i.scratch_bytes;
+    };
+    if (graph->g32) fill(*graph->g32, grl32::Image::kDbTileNodes, grl32::Image::kDbTileCells);
+    else fill(*graph->g64, grl64::Image::kDbTileNodes, grl64::Image::kDbTileCells);
+    return GRLBWT_OK;
+}
+int grlbwt_debruijn_nodes(grlbwt_ctx *ctx, const grlbwt_debruijn *graph, uint64_t *dev_lo, uint64_t *dev_count, uint32_t *dev_in_degree,
+                          uint32_t *dev_out_degree, uint64_t *dev_unitig, uint64_t *dev_rank, uint64_t capacity) {
+    if (!ctx || !graph || !(graph->g32 || graph->g64)) return refuse(ctx);
+    return guarded(ctx, [&] {
+        if (graph->g32) grl32::Image::debruijn_nodes(*graph->g32, dev_lo, dev_count, dev_in_degree, dev_out_degree, dev_unitig, dev_rank, capacity);
+        else grl64::Image::debruijn_nodes(*graph->g64, dev_lo, dev_count, dev_in_degree, dev_out_degree, dev_unitig, dev_rank, capacity);
+    });
+}
+int grlbwt_debruijn_edges(grlbwt_ctx *ctx, const grlbwt_debruijn *graph, uint64_t *dev_in_offsets, uint64_t *dev_from, uint64_t *dev_weight,
+                          uint64_t *dev_row, uint64_t capacity) {
+    if (!ctx || !graph || !(graph->g32 || graph->g64)) return refuse(ctx);
+    return guarded(ctx, [&] {
+        if (graph->g32) grl32::Image::debruijn_edges(*graph->g32, dev_in_offsets, dev_from, dev_weight, dev_row, capacity);
+        else grl64::Image::debruijn_edges(*graph->g64, dev_in_offsets, dev_from, dev_weight, dev_row, capacity);
+    });
+}
+int grlbwt_debruijn_unitigs(grlbwt_ctx *ctx, const grlbwt_debruijn *graph, const grlbwt_fm *fm, int cell_bytes, uint64_t *dev_node_offsets,
+                            uint64_t *dev_nodes, void *dev_cells, uint64_t *dev_weight, uint8_t *dev_circular, uint64_t capacity_unitigs,
+                            uint64_t capacity_nodes, uint64_t capacity_cells) {
+    if (!ctx || !graph || !(graph->g32 || graph->g64)) return refuse(ctx);
+    if (fm && (graph->g32 ? !fm->f32 : !fm->f64)) return refuse(ctx, "de bruijn unitigs: not the index the graph was made from");
+    return guarded(ctx, [&] {
+        if (graph->g32) grl32::Image::debruijn_unitigs(*graph->g32, fm ? fm->f32.get() : nullptr, cell_bytes, dev_node_offsets, dev_nodes, dev_cells,
+                                                       dev_weight, dev_circular, capacity_unitigs, capacity_nodes, capacity_cells);
+        else grl64::Image::debruijn_unitigs(*graph->g64, fm ? fm->f64.get() : nullptr, cell_bytes, dev_node_offsets, dev_nodes, dev_cells, dev_weight,
+                                            dev_circular, capacity_unitigs, capacity_nodes, capacity_cells);
+    });
 }
 
 int grlbwt_select_create(grlbwt_ctx *ctx, const void *dev_image, uint64_t image_bytes, int cell_bytes, const uint64_t *dev_ids, uint64_t n_ids,

@@ -1535,6 +1535,217 @@ struct KmerEmitFn {          // the generic decode, prim::for_each_set_bit over 
     }
 };
 
+// ---- the compacted de Bruijn graph (grlbwt_debruijn_*).  The nodes are the selected k-mers in ascending lo; node
+// v holds rows [lo, lo + count).  An in-edge of v is a symbol a above the separator that occurs in BWT[lo, lo + count): one
+// backward step gives the rows [lo2, hi2) of the window a.v, which lie inside the interval of its first k cells; that interval's
+// head is the last bit of B at or before lo2 (DbPrevBit, KmerCountFn's lookup in the other direction: the row's own word or the
+// non-empty word in front of it, no scan over the gap), and the edge exists when the head is selected.
+//   The symbols are enumerated through FmApproxFn's lower bound (the smallest symbol of the image above c), in ascending order,
+//   which is ascending `from`; the enumeration ends as soon as the steps made account for all of the node's rows (the separator's
+//   step first), so a node whose rows all hold one symbol stops at that symbol.
+//   Loops: at most sigma symbols per node, each one lower bound and one fm_step.  Bounds: p = prev(lo2) <= lo2 < n; an entry is
+//   stored only below inoff[v + 1].
+static constexpr idx_t kDbNone = (idx_t)~(idx_t)0;
+struct DbNodeFn {            // prim::for_each_set_bit over the selection: node e heads row p
+    KmerCountFn cnt; idx_t *lo, *count;
+    GRL_DEV void operator()(u64 p, u64 e) const { lo[e] = (idx_t)p; count[e] = (idx_t)cnt(p); }
+};
+struct DbPrevBit {           // the last bit of B at or before row q < n, or ~0
+    const u64 *B; const u64 *NZ; const idx_t *nzbase; const idx_t *nzlist;
+    GRL_DEV u64 operator()(u64 q) const {
+        const u64 w = q >> 6;
+        const u64 m = B[w] & (~0ull >> (63 - (q & 63)));
+        u64 p = ~0ull;
+        if (m) {
+            p = w * 64 + 63 - (u64)__builtin_clzll(m);
+        } else {
+            const u64 r = (u64)nzbase[w >> 6] + (u64)__builtin_popcountll(NZ[w >> 6] & ((1ull << (w & 63)) - 1ull));      // non-empty words in front of w
+            if (r) { const u64 x = (u64)nzlist[r - 1]; p = x * 64 + 63 - (u64)__builtin_clzll(B[x]); }
+        }
+        return p;
+    }
+};
+struct DbGlobalSink {        // entry j of the edge table, stored where it belongs
+    idx_t *from, *weight, *row;
+    GRL_DEV void operator()(u64 j, u64 u, u64 wt, u64 r) const { from[j] = (idx_t)u; weight[j] = (idx_t)wt; row[j] = (idx_t)r; }
+};
+struct DbEdgeFn {
+    typedef FmKey Key;
+    const FmKey *key; const idx_t *slf; u64 R; u32 sep;
+    DbPrevBit prev; const u64 *sel; const idx_t *selrank;
+    const idx_t *nlo, *ncount;
+    u32 *indeg, *outdeg; idx_t *nsteps;       // the counting pass (inoff null)
+    const idx_t *inoff; u32 *bad;             // the emit pass
+    GRL_HD const FmKey *keys() const { return key; }
+    GRL_HD u64 n_keys() const { return R; }
+    template <class TOP>
+    GRL_DEV bool next_sym(u32 c, const TOP &top, u32 &out) const {      // FmApproxFn::next_sym
+        if (c == ~0u) return false;
+        u64 a = 0, b = R;
+        top.narrow(c + 1, 0, a, b);
+        for (int it = 0; it < 64 && a < b; it++) { const u64 mid = (a + b) >> 1; if (key[mid].below(c + 1, 0)) a = mid + 1; else b = mid; }
+        if (a >= R) return false;
+        out = key[a].sym();
+        return true;
+    }
+    template <class TOP, class SINK>
+    GRL_DEV void run(u64 v, const TOP &top, const SINK &sink) const {
+        const u64 lo = (u64)nlo[v], hi = lo + (u64)ncount[v];
+        const u64 base = inoff ? (u64)inoff[v] : 0, room = inoff ? (u64)inoff[v + 1] - base : 0;
+        u64 a = lo, b = hi, rem = hi - lo, found = 0, steps = 1;
+        fm_step(key, slf, R, top, sep, a, b);                 // the rows whose window starts its string
+        rem -= b > a ? (b - a < rem ? b - a : rem) : 0;
+        u32 c = sep;
+        while (rem && next_sym(c, top, c)) {                  // (c goes up: at most sigma rounds)
+            a = lo; b = hi;
+            fm_step(key, slf, R, top, c, a, b);
+            steps++;
+            if (a >= b) continue;
+            rem -= b - a < rem ? b - a : rem;
+            const u64 p = prev(a);
+            if (p == ~0ull || !lcp_bit(sel, p)) continue;
+            const u64 u = rank1(sel, selrank, p);
+            if (inoff) { if (found < room) sink(base + found, u, b - a, a); }
+            else prim::atomic_add(&outdeg[u], 1u);
+            found++;
+        }
+        if (inoff) { if (found != room) prim::atomic_max(bad, 1u); }
+        else { indeg[v] = (u32)found; nsteps[v] = (idx_t)steps; }
+    }
+    template <class TOP>
+    GRL_DEV void operator()(u64 v, const TOP &top) const { run(v, top, DbGlobalSink{nullptr, nullptr, nullptr}); }
+};
+struct DbEdgeLaneFn {        // the emit pass: one lane per node that stores its own entries
+    typedef FmKey Key;
+    DbEdgeFn f; DbGlobalSink sink;
+    GRL_HD const FmKey *keys() const { return f.key; }
+    GRL_HD u64 n_keys() const { return f.R; }
+    template <class TOP>
+    GRL_DEV void operator()(u64 v, const TOP &top) const { f.run(v, top, sink); }
+    GRL_DEV void operator()(u64 v) const { f.run(v, FmNoTop{}, sink); }
+};
+struct DbDegIn {
+    const u32 *d;
+    GRL_DEV u64 operator()(u64 v) const { return (u64)d[v]; }
+};
+// The unitigs.  link[v] = the node in front of v on its unitig, none where v heads one: v's only in-edge u -> v with
+// out_degree[u] = 1.  u then has no other out-edge, so link is one-to-one and succ[u] = v has one writer.  mark[v]: 0 inside a
+// unitig, 1 a head, 2 the head of a circular one (a self-loop links a node to itself, so "head" cannot be "points at itself").
+//   Pointer jumping: (ptr, dist, mn) of v says that ptr lies dist links in front of v and mn is the smallest id among the dist
+//   nodes from v on; a round doubles dist unless v or ptr is a head.  After r rounds every node within 2^r links of a head has
+//   found it, and a node on a cycle has seen min(2^r, the cycle) of its nodes: after ceil(log2 n_nodes) + 1 rounds its mn is the
+//   cycle's smallest id.  That node becomes the head (mark 2), and the same rounds rank the cycle's nodes behind it.
+struct DbLinkFn {
+    const u32 *indeg, *outdeg; const idx_t *inoff, *from; idx_t *link, *succ;
+    GRL_DEV void operator()(u64 v) const {
+        idx_t l = kDbNone;
+        if (indeg[v] == 1u) {
+            const idx_t u = from[(u64)inoff[v]];
+            if (outdeg[(u64)u] == 1u) { l = u; succ[(u64)u] = (idx_t)v; }
+        }
+        link[v] = l;
+    }
+};
+struct DbJumpInitFn {        // open: only the nodes that found no head are set up again (the second set of rounds; null: all)
+    const idx_t *link; const u8 *mark; const u8 *open; idx_t *ptr, *dist, *mn;
+    GRL_DEV void operator()(u64 v) const {
+        if (open && !open[v]) return;
+        const bool head = mark[v] != 0;
+        ptr[v] = head ? (idx_t)v : link[v]; dist[v] = head ? (idx_t)0 : (idx_t)1; mn[v] = (idx_t)v;
+    }
+};
+struct DbMarkFn {
+    const idx_t *link; u8 *mark;
+    GRL_DEV void operator()(u64 v) const { mark[v] = link[v] == kDbNone ? 1 : 0; }
+};
+struct DbJumpFn {            // one round, from generation 0 to generation 1
+    const u8 *mark; const idx_t *p0, *d0, *m0; idx_t *p1, *d1, *m1;
+    GRL_DEV void operator()(u64 v) const {
+        const idx_t p = p0[v];
+        idx_t q = p, d = d0[v], m = m0[v];
+        if (!mark[v] && !mark[(u64)p]) {
+            q = p0[(u64)p]; d = (idx_t)(d + d0[(u64)p]);
+            const idx_t o = m0[(u64)p];
+            m = o < m ? o : m;
+        }
+        p1[v] = q; d1[v] = d; m1[v] = m;
+    }
+};
+struct DbOpenIn {            // 1 for a node that has found no head yet
+    const u8 *mark; const idx_t *ptr;
+    GRL_DEV u64 operator()(u64 v) const { return !mark[v] && !mark[(u64)ptr[v]] ? 1ull : 0ull; }
+};
+struct DbCycleHeadFn {       // the smallest node of every cycle becomes its head; `open` is read, mark written: two arrays
+    const u8 *open; const idx_t *mn; u8 *mark;
+    GRL_DEV void operator()(u64 v) const { if (open[v] && (u64)mn[v] == v) mark[v] = 2; }
+};
+struct DbOpenFn {
+    const u8 *mark; const idx_t *ptr; u8 *open;
+    GRL_DEV void operator()(u64 v) const { open[v] = !mark[v] && !mark[(u64)ptr[v]] ? 1 : 0; }
+};
+struct DbMarkIn {
+    const u8 *mark; u8 what;     // 0: any head
+    GRL_DEV u64 operator()(u64 v) const { return (what ? mark[v] == what : mark[v] != 0) ? 1ull : 0ull; }
+};
+struct DbPlaceFn {           // unitig and rank of every node; the tails give the lengths (one tail per unitig)
+    const u8 *mark; const idx_t *ptr, *dist, *hrank, *succ; idx_t *unitig, *rank, *ulen; u8 *ucirc;
+    GRL_DEV void operator()(u64 v) const {
+        const u64 h = (u64)ptr[v], j = (u64)hrank[h];
+        unitig[v] = (idx_t)j; rank[v] = dist[v];
+        const idx_t s = succ[v];
+        if (s == kDbNone || mark[(u64)s]) ulen[j] = (idx_t)(dist[v] + 1);
+        if (mark[v]) ucirc[j] = mark[v] == 2 ? 1 : 0;
+    }
+};
+struct DbOrderFn {
+    const idx_t *unitig, *rank, *uoff; idx_t *nodes;
+    GRL_DEV void operator()(u64 v) const { nodes[(u64)uoff[(u64)unitig[v]] + (u64)rank[v]] = (idx_t)v; }
+};
+struct DbCountOfIn {         // the count of the i-th node in unitig order
+    const idx_t *nodes, *count;
+    GRL_DEV u64 operator()(u64 i) const { return (u64)count[(u64)nodes[i]]; }
+};
+struct DbWeightFn {
+    const idx_t *uoff; const u64 *wsum; idx_t *uweight;
+    GRL_DEV void operator()(u64 j) const { uweight[j] = (idx_t)(wsum[(u64)uoff[j + 1]] - wsum[(u64)uoff[j]]); }
+};
+template <class S, class D>
+struct DbCopyFn {            // the writers: the handle's arrays in the widths of the interface
+    const S *src; D *dst;
+    GRL_DEV void operator()(u64 i) const { dst[i] = (D)src[i]; }
+};
+// The cells.  Unitig j of m nodes takes cells [off[j] + j (k - 1), off[j + 1] + (j + 1)(k - 1)): place r < m holds the first cell
+// of its r-th node -- the symbol of the sorted run that holds the node's row lo, no walk -- and the k - 1 cells behind them are
+// the forward steps from the last node's lo (KmerStepFn; the first step gives that node's own first cell again).
+//   Bounds: lo < n, so run_of_row answers a run below R; a cell index is below n_nodes + n_unitigs (k - 1).
+template <class cell_t>
+struct DbFirstCellFn {       // for_each over the nodes in unitig order
+    KmerStepFn step; const idx_t *nodes, *unitig, *nlo; u64 k; cell_t *cells;
+    GRL_DEV void operator()(u64 i) const {
+        const u64 v = (u64)nodes[i];
+        u64 q = (u64)nlo[v];
+        cells[i + (u64)unitig[v] * (k - 1)] = (cell_t)step(q);
+    }
+};
+template <class cell_t>
+struct DbTailCellsFn {       // for_each over the unitigs: k - 1 dependent steps each
+    KmerStepFn step; const idx_t *nodes, *uoff, *nlo; u64 k; cell_t *cells;
+    GRL_DEV void operator()(u64 j) const {
+        const u64 e = (u64)uoff[j + 1];
+        u64 q = (u64)nlo[(u64)nodes[e - 1]];
+        (void)step(q);
+        cell_t *out = cells + e + j * (k - 1);
+        for (u64 t = 0; t + 1 < k; t++) out[t] = (cell_t)step(q);
+    }
+};
+struct DbPrintIn {           // the index's fingerprint: a sum over the sorted runs
+    const FmKey *key; const idx_t *slf;
+    GRL_DEV u64 operator()(u64 j) const {
+        const FmKey kj = key[j];
+        return ((u64)kj.sym() * 0x9E3779B97F4A7C15ull + kj.start() * 0xC2B2AE3D27D4EB4Full + (u64)slf[j]) * (2 * j + 1);
+    }
+};
+
 // ---- the right-maximal and maximal repeats (grlbwt_fm_repeats).  V[p] = min(LCP[p], cap) in the narrowest width
 // that holds cap.  Row p with V[p] = v >= 1 is the split row of a right-maximal repeat of v cells exactly when the nearest q < p
 // with V[q] <= v has V[q] < v; the repeat's rows are then [q, e), e the nearest row behind p with V[e] < v, or n.  Both are
@@ -2457,6 +2668,14 @@ struct Image {
 #else
     static constexpr u64 kLcpTile = 4096;        // (the serial form has no tiles: the figure the device library reports)
 #endif
+    // one bit per slf[j], the first row of every sorted run, with ranks: run_of_row over F order (the forward step's lookup)
+    static void fm_run_cells(const FmIndex &F, DBuf<RankCell> &frc) {
+        RankBits rb;
+        build_rankbits(rb, F.slf.p, F.R, F.n + 1, "lcp.runbits");
+        const u64 nc = (F.n + 1) / 64 + 2;
+        frc.alloc(nc);
+        prim::for_each(nc, RankCellFn{rb.words.p, rb.base.p, frc.p}, "lcp.rankcells");
+    }
     struct FmLcp {
         u64 n = 0, nw = 0;
         bool plain = !prim::kIsDevice;
@@ -2477,13 +2696,7 @@ struct Image {
             plain = prim::sw().lcp_round == 'p';
             if (!plain) W.alloc(n);
 #endif
-            {   // one bit per slf[j]: the first row of every sorted run
-                RankBits rb;
-                build_rankbits(rb, F.slf.p, F.R, n + 1, "lcp.runbits");
-                const u64 nc = (n + 1) / 64 + 2;
-                frc.alloc(nc);
-                prim::for_each(nc, RankCellFn{rb.words.p, rb.base.p, frc.p}, "lcp.rankcells");
-            }
+            fm_run_cells(F, frc);
             b0.alloc(nw); b1.alloc(nw); s0.alloc(nw); s1.alloc(nw); brank.alloc(nw + 1);
         }
         LcpRowFn rows(const FmIndex &F, const u64 *B, const u64 *S) const { return LcpRowFn{frc.p, F.key.p, F.slf.p, F.k, B, brank.p, S}; }
@@ -2574,6 +2787,58 @@ struct Image {
         if (rows_at) std::memcpy(rows_at, ra.data(), n_levels * 8);
         if (suffixes_of) std::memcpy(suffixes_of, su.data(), n_levels * 8);
     }
+    // what grlbwt_fm_kmers and grlbwt_debruijn_create share: the LCP passes capped at k and the length passes (B: the rows with
+    // LCP < k; H: the heads), the non-empty words of B for KmerCountFn, and the selection with its ranks (in L.brank)
+    struct KmerSel {
+        FmLcp L;
+        DBuf<u64> NZ;
+        DBuf<idx_t> nzbase, nzlist;
+        const u64 *B = nullptr;
+        u64 *H = nullptr, *sel = nullptr;
+        u64 n = 0, nnz = 0;
+        KmerCountFn cnt() const { return KmerCountFn{B, NZ.p, nzbase.p, nzlist.p, nnz, n}; }
+        static u64 scratch_bytes(u64 n_) {
+            const u64 nw = FmLcp::words_of(n_), nwords = (n_ + 63) / 64, nzw = nwords / 64 + 2;
+            return FmLcp::scratch_bytes(n_) + nw * 8 + nzw * 8 + (nzw + 1 + nwords) * sizeof(idx_t);
+        }
+        void heads(const FmIndex &F, u64 k, KmerInfo &ki) {
+            n = F.n;
+            const u64 nw = FmLcp::words_of(n), nwords = (n + 63) / 64, nzw = nwords / 64 + 2;
+            L.alloc(F);
+            DBuf<u64> sh(nw);
+            sh.zero();
+            prim::bitvector_from_pred(n, LcpBelowPred{F.k}, sh.p, "kmer.terminators");
+            LcpInfo li;
+            std::vector<u64> ra, su;
+            L.run(F, k, nullptr, 8, li, ra, su, sh.p);               // B: the rows with LCP < k
+            ki.passes = li.passes;
+            {   // the suffixes of passes + 1 .. k - 1 cells: copy-only passes of S, until a generation is empty
+                u64 *S = L.Sfin, *Sn = L.Sold, last = su.back();
+                for (u64 l = li.passes + 1; l < k && last; l++) {
+                    prim::bitvector_from_pred(n, LcpLenPred{L.rows(F, nullptr, S)}, Sn, "kmer.lengths");
+                    last = prim::reduce_sum<u64>(nwords, PopcIn{Sn}, "kmer.suffixes");
+                    prim::for_each(nwords, KmerOrFn{Sn, sh.p}, "kmer.lengths_or");
+                    std::swap(S, Sn);
+                    ki.length_passes++;
+                }
+            }
+            B = L.Bfin; H = L.Bold; sel = L.Sfin;
+            prim::for_each(nwords, KmerHeadsFn{B, sh.p, H}, "kmer.heads");
+            sh.release();
+            NZ.alloc(nzw); nzbase.alloc(nzw + 1);
+            NZ.zero();
+            prim::bitvector_from_pred(nwords, KmerWordPred{B}, NZ.p, "kmer.words");
+            nnz = (u64)prim::exclusive_scan<idx_t>(nzw, PopcIn{NZ.p}, nzbase.p, true, "kmer.word_ranks");
+            nzlist.alloc(nnz);
+            prim::for_each_set_bit<idx_t>(nwords, NZ.p, nzbase.p, KmerWordListFn{nzlist.p}, "kmer.word_list");
+        }
+        void select(const KmerFilter &flt, KmerInfo &ki) {
+            const u64 nw = FmLcp::words_of(n);
+            prim::dev_memset(sel, 0, nw * 8);
+            prim::bitvector_from_pred(n, KmerSelPred{H, cnt(), flt}, sel, "kmer.select");
+            ki.n_selected = (u64)prim::exclusive_scan<idx_t>(nw, PopcIn{sel}, L.brank.p, true, "kmer.select_ranks");
+        }
+    };
     // ---- the distinct k-mers with their counts (functor block "the distinct k-mers with their counts").  Everything
     // that can refuse the call runs before the first store: the arguments, the memory, the passes (an image that is not the BWT
     // of a collection), the capacity.  Then the spectrum is copied to the host and the table is decoded.
@@ -2609,37 +2874,12 @@ struct Image {
         ki.scratch_bytes = FmLcp::scratch_bytes(n) + nw * 8 + nzw * 8 + (nzw + 1 + nwords) * sizeof(idx_t) + nb * 8;
         if (n >= ((u64)1 << 62) || ki.scratch_bytes > prim::mem_available())
             throw prim::Error(-12, "fm kmers: the passes need " + std::to_string(ki.scratch_bytes) + " bytes of device memory, more than is free");
-        FmLcp L;
-        L.alloc(F);
-        DBuf<u64> sh(nw);
-        sh.zero();
-        prim::bitvector_from_pred(n, LcpBelowPred{F.k}, sh.p, "kmer.terminators");
-        LcpInfo li;
-        std::vector<u64> ra, su;
-        L.run(F, k, nullptr, 8, li, ra, su, sh.p);               // B: the rows with LCP < k
-        ki.passes = li.passes;
-        {   // the suffixes of passes + 1 .. k - 1 cells: copy-only passes of S, until a generation is empty
-            u64 *S = L.Sfin, *Sn = L.Sold, last = su.back();
-            for (u64 l = li.passes + 1; l < k && last; l++) {
-                prim::bitvector_from_pred(n, LcpLenPred{L.rows(F, nullptr, S)}, Sn, "kmer.lengths");
-                last = prim::reduce_sum<u64>(nwords, PopcIn{Sn}, "kmer.suffixes");
-                prim::for_each(nwords, KmerOrFn{Sn, sh.p}, "kmer.lengths_or");
-                std::swap(S, Sn);
-                ki.length_passes++;
-            }
-        }
-        const u64 *B = L.Bfin;
-        u64 *H = L.Bold, *sel = L.Sfin;
-        prim::for_each(nwords, KmerHeadsFn{B, sh.p, H}, "kmer.heads");
-        sh.release();
-        DBuf<u64> NZ(nzw);
-        DBuf<idx_t> nzbase(nzw + 1), nzlist;
-        NZ.zero();
-        prim::bitvector_from_pred(nwords, KmerWordPred{B}, NZ.p, "kmer.words");
-        const u64 nnz = (u64)prim::exclusive_scan<idx_t>(nzw, PopcIn{NZ.p}, nzbase.p, true, "kmer.word_ranks");
-        nzlist.alloc(nnz);
-        prim::for_each_set_bit<idx_t>(nwords, NZ.p, nzbase.p, KmerWordListFn{nzlist.p}, "kmer.word_list");
-        const KmerCountFn cnt{B, NZ.p, nzbase.p, nzlist.p, nnz, n};
+        KmerSel K;
+        K.heads(F, k, ki);
+        FmLcp &L = K.L;
+        const u64 *H = K.H;
+        u64 *sel = K.sel;
+        const KmerCountFn cnt = K.cnt();
         DBuf<u64> dbins(nb);
 #ifdef GRLBWT_PRIM_HIP
         prim::kmer_spectrum(n, H, cnt, (u32)nb, dbins.p, ki.n_distinct, ki.n_windows, ki.largest_count);
@@ -2653,9 +2893,7 @@ struct Image {
 #endif
         prim::d2h(spec.data(), dbins.p, nb * 8);
         const KmerFilter flt{row_begin, row_end, min_count ? min_count : 1, max_count ? max_count : ~0ull};
-        prim::dev_memset(sel, 0, nw * 8);
-        prim::bitvector_from_pred(n, KmerSelPred{H, cnt, flt}, sel, "kmer.select");
-        ki.n_selected = (u64)prim::exclusive_scan<idx_t>(nw, PopcIn{sel}, L.brank.p, true, "kmer.select_ranks");
+        K.select(flt, ki);
         ki.forward_steps = cells ? ki.n_selected * k : 0;
         prim::sync();
         F.kinfo = ki;
@@ -2880,6 +3118,223 @@ struct Image {
         si.lanes = wi.lanes; si.refills = wi.refills;
         prim::sync();
         F.sinfo = si;
+    }
+    // ---- the compacted de Bruijn graph (functor block "the compacted de Bruijn graph").  debruijn_create does all
+    // the work and keeps no pointer into the index; the three writers copy, and the cells of the unitigs are decoded from the
+    // index again.  Everything that can refuse the create runs before anything is handed out: the arguments, the memory, the
+    // passes (an image that is not the BWT of a collection).
+    //   Device form: both passes of the edge search through prim::top_search (kDbTileNodes lanes of a workgroup on consecutive
+    //   nodes under the LDS top level, every lane storing its node's entries: with about one in-edge per node they are consecutive
+    //   entries; the staged tile kernel measured slower and is not kept, prim_hip.hpp) and prim::db_first_cells (a tile of
+    //   kDbTileCells output cells per workgroup, one search per tile for its unitigs).  The stand-in runs the same functors
+    //   through for_each; its form of the first cells, a for_each over the nodes, is the device's with GRLBWT_DEV_DEBRUIJN=f.
+    //   Loops: the passes of fm_kmers; at most sigma symbols per node and pass; at most 2 (ceil(log2 n_nodes) + 1) jumping rounds,
+    //   each one launch; k - 1 forward steps per unitig.  Nothing waits for another thread; the only atomics are the integer
+    //   adds of out_degree and the flag of the second pass.
+#ifdef GRLBWT_PRIM_HIP
+    static constexpr u64 kDbTileNodes = prim::kDbTileNodes, kDbTileCells = prim::kDbTileCells;
+#else
+    static constexpr u64 kDbTileNodes = 1024, kDbTileCells = 4096;      // (the serial form has no tiles: the figures the device library reports)
+#endif
+    struct DeBruijnInfo {
+        u64 k = 0, n = 0, n_strings = 0, n_distinct = 0, n_nodes = 0, n_edges = 0, n_unitigs = 0, n_circular = 0, longest = 0, n_cells = 0;
+        u64 max_in = 0, max_out = 0, passes = 0, length_passes = 0, backward_steps = 0, jump_rounds = 0, scratch_bytes = 0;
+    };
+    struct ImageDeBruijn {
+        DeBruijnInfo i;
+        u64 R = 0, sigma = 0, print = 0;          // of the index it was made from
+        DBuf<idx_t> lo, count, unitig, rank, inoff, from, weight, row, uoff, uweight;
+        DBuf<u32> indeg, outdeg;
+        DBuf<u8> ucirc;
+        u64 held_bytes() const {
+            return (lo.n + count.n + unitig.n + rank.n + inoff.n + from.n + weight.n + row.n + uoff.n + uweight.n) * sizeof(idx_t) +
+                   (indeg.n + outdeg.n) * 4 + ucirc.n;
+        }
+    };
+    static u64 debruijn_print(const FmIndex &F) { return F.R ? prim::reduce_sum<u64>(F.R, DbPrintIn{F.key.p, F.slf.p}, "debruijn.fingerprint") : 0; }
+    static void debruijn_create(const FmIndex &F, u64 k, u64 min_count, u64 max_count, u32 flags, ImageDeBruijn &D) {
+        if (k == 0) throw prim::Error(-22, "de bruijn: k is 0");
+        if (flags) throw prim::Error(-22, "de bruijn: unknown flag bits " + std::to_string(flags));
+        if (max_count && min_count > max_count)
+            throw prim::Error(-22, "de bruijn: min_count " + std::to_string(min_count) + " is above max_count " + std::to_string(max_count));
+        const u64 n = F.n;
+        DeBruijnInfo &di = D.i;
+        di = DeBruijnInfo();
+        di.k = k; di.n = n; di.n_strings = F.k;
+        D.R = F.R; D.sigma = F.sigma;
+        if (n == 0) return;
+        di.scratch_bytes = KmerSel::scratch_bytes(n);
+        if (n >= ((u64)1 << 62) || di.scratch_bytes > prim::mem_available())
+            throw prim::Error(-12, "de bruijn: the passes need " + std::to_string(di.scratch_bytes) + " bytes of device memory, more than is free");
+        D.print = debruijn_print(F);
+        u64 nn = 0, ne = 0;
+        {
+            KmerSel K;
+            KmerInfo ki;
+            K.heads(F, k, ki);
+            di.passes = ki.passes; di.length_passes = ki.length_passes;
+            di.n_distinct = prim::reduce_sum<u64>((n + 63) / 64, PopcIn{K.H}, "debruijn.heads_sum");
+            K.select(KmerFilter{0, n, min_count ? min_count : 1, max_count ? max_count : ~0ull}, ki);
+            di.n_nodes = nn = ki.n_selected;
+            if (nn == 0) { prim::sync(); return; }
+            // per node: the handle's seven arrays and the steps of the first pass; then the jumping's eight arrays and two bytes
+            const u64 node_bytes = nn * (6 * sizeof(idx_t) + 8) + nn * (sizeof(idx_t) + 4);
+            const u64 jump_bytes = nn * (10 * sizeof(idx_t) + 2 + 8);
+            di.scratch_bytes += jump_bytes > nn * (sizeof(idx_t) + 4) ? jump_bytes : nn * (sizeof(idx_t) + 4);
+            if (node_bytes + jump_bytes > prim::mem_available())
+                throw prim::Error(-12, "de bruijn: the graph needs " + std::to_string(node_bytes + jump_bytes) + " bytes of device memory, more than is free");
+            D.lo.alloc(nn); D.count.alloc(nn);
+            prim::for_each_set_bit<idx_t>(n, K.sel, K.L.brank.p, DbNodeFn{K.cnt(), D.lo.p, D.count.p}, "debruijn.nodes");
+            D.indeg.alloc(nn); D.outdeg.alloc(nn);
+            D.outdeg.zero();
+            DBuf<idx_t> nsteps(nn);
+            DBuf<u32> bad(1);
+            bad.zero();
+            DbEdgeFn f{F.key.p, F.slf.p, F.R, F.sep, DbPrevBit{K.B, K.NZ.p, K.nzbase.p, K.nzlist.p}, K.sel, K.L.brank.p, D.lo.p, D.count.p,
+                       D.indeg.p, D.outdeg.p, nsteps.p, nullptr, bad.p};
+#ifdef GRLBWT_PRIM_HIP
+            prim::top_search(nn, f, F.top_entries, "debruijn.count");
+#else
+            prim::for_each(nn, DbEdgeLaneFn{f, DbGlobalSink{nullptr, nullptr, nullptr}}, "debruijn.count");
+#endif
+            ne = prim::reduce_sum<u64>(nn, DbDegIn{D.indeg.p}, "debruijn.edges_sum");
+            if (ne > n) throw prim::Error(-22, "de bruijn: more windows of k + 1 cells than rows: not the BWT of a collection");
+            di.n_edges = ne;
+            if (ne * 3 * sizeof(idx_t) > prim::mem_available())
+                throw prim::Error(-12, "de bruijn: the edges need " + std::to_string(ne * 3 * sizeof(idx_t)) + " bytes of device memory, more than is free");
+            D.inoff.alloc(nn + 1);
+            (void)prim::exclusive_scan<idx_t>(nn, DbDegIn{D.indeg.p}, D.inoff.p, true, "debruijn.in_offsets");
+            D.from.alloc(ne); D.weight.alloc(ne); D.row.alloc(ne);
+            f.inoff = D.inoff.p;
+            const DbGlobalSink sink{D.from.p, D.weight.p, D.row.p};
+#ifdef GRLBWT_PRIM_HIP
+            prim::top_search(nn, DbEdgeLaneFn{f, sink}, F.top_entries, "debruijn.edges");
+#else
+            prim::for_each(nn, DbEdgeLaneFn{f, sink}, "debruijn.edges");
+#endif
+            if (bad.get(0)) throw prim::Error(-71, "de bruijn: a node's second pass found another number of edges than its first");
+            di.backward_steps = 2 * prim::reduce_sum<u64>(nn, IdxIn64{nsteps.p}, "debruijn.steps");
+            di.max_in = prim::reduce_max<u64>(nn, DbDegIn{D.indeg.p}, "debruijn.max_in");
+            di.max_out = prim::reduce_max<u64>(nn, DbDegIn{D.outdeg.p}, "debruijn.max_out");
+        }
+        // the unitigs
+        DBuf<idx_t> link(nn), succ(nn), p0(nn), d0(nn), m0(nn), p1(nn), d1(nn), m1(nn);
+        DBuf<u8> mark(nn), open(nn);
+        succ.fill_ff();
+        prim::for_each(nn, DbLinkFn{D.indeg.p, D.outdeg.p, D.inoff.p, D.from.p, link.p, succ.p}, "debruijn.links");
+        prim::for_each(nn, DbMarkFn{link.p, mark.p}, "debruijn.heads");
+        prim::for_each(nn, DbJumpInitFn{link.p, mark.p, nullptr, p0.p, d0.p, m0.p}, "debruijn.jump_init");
+        const u64 max_rounds = (u64)bitlen64(nn - 1) + 1;       // ceil(log2 n_nodes) + 1
+        idx_t *P = p0.p, *Dd = d0.p, *M = m0.p, *Pn = p1.p, *Dn = d1.p, *Mn = m1.p;
+        const auto rounds = [&]() {                              // returns the nodes that have found no head
+            u64 left = prim::reduce_sum<u64>(nn, DbOpenIn{mark.p, P}, "debruijn.open");
+            for (u64 r = 0; r < max_rounds && left; r++) {
+                prim::for_each(nn, DbJumpFn{mark.p, P, Dd, M, Pn, Dn, Mn}, "debruijn.jump");
+                std::swap(P, Pn); std::swap(Dd, Dn); std::swap(M, Mn);
+                di.jump_rounds++;
+                left = prim::reduce_sum<u64>(nn, DbOpenIn{mark.p, P}, "debruijn.open");
+            }
+            return left;
+        };
+        if (rounds()) {                                          // what is left lies on cycles: their smallest nodes become heads
+            prim::for_each(nn, DbOpenFn{mark.p, P, open.p}, "debruijn.cycle_nodes");
+            prim::for_each(nn, DbCycleHeadFn{open.p, M, mark.p}, "debruijn.cycle_heads");
+            prim::for_each(nn, DbJumpInitFn{link.p, mark.p, open.p, P, Dd, M}, "debruijn.cycle_init");
+            if (rounds()) throw prim::Error(-71, "de bruijn: nodes without a unitig after the cycle rounds");
+        }
+        DBuf<idx_t> hrank(nn + 1);
+        const u64 nu = (u64)prim::exclusive_scan<idx_t>(nn, DbMarkIn{mark.p, 0}, hrank.p, true, "debruijn.unitig_ids");
+        di.n_unitigs = nu;
+        di.n_circular = prim::reduce_sum<u64>(nn, DbMarkIn{mark.p, 2}, "debruijn.circular");
+        D.unitig.alloc(nn); D.rank.alloc(nn); D.ucirc.alloc(nu);
+        DBuf<idx_t> ulen(nu);
+        prim::for_each(nn, DbPlaceFn{mark.p, P, Dd, hrank.p, succ.p, D.unitig.p, D.rank.p, ulen.p, D.ucirc.p}, "debruijn.place");
+        D.uoff.alloc(nu + 1);
+        (void)prim::exclusive_scan<idx_t>(nu, IdxIn<idx_t>{ulen.p}, D.uoff.p, true, "debruijn.node_offsets");
+        di.longest = prim::reduce_max<u64>(nu, IdxIn64{ulen.p}, "debruijn.longest");
+        {
+            idx_t *nodes = Pn;                                   // (a spare generation of the rounds)
+            DBuf<u64> wsum(nn + 1);
+            prim::for_each(nn, DbOrderFn{D.unitig.p, D.rank.p, D.uoff.p, nodes}, "debruijn.order");
+            (void)prim::exclusive_scan<u64>(nn, DbCountOfIn{nodes, D.count.p}, wsum.p, true, "debruijn.weights_scan");
+            D.uweight.alloc(nu);
+            prim::for_each(nu, DbWeightFn{D.uoff.p, wsum.p, D.uweight.p}, "debruijn.weights");
+        }
+        di.n_cells = nn + nu * (k - 1);
+        prim::sync();
+    }
+    template <class S>
+    static void debruijn_copy(const S *src, u64 *dst, u64 m, const char *name) { if (dst && m) prim::for_each(m, DbCopyFn<S, u64>{src, dst}, name); }
+    static void debruijn_nodes(const ImageDeBruijn &D, u64 *lo, u64 *count, u32 *indeg, u32 *outdeg, u64 *unitig, u64 *rank, u64 capacity) {
+        if (!lo && !count && !indeg && !outdeg && !unitig && !rank) throw prim::Error(-22, "de bruijn nodes: no output");
+        const u64 nn = D.i.n_nodes;
+        if (capacity < nn) throw prim::Error(-22, "de bruijn nodes: " + std::to_string(nn) + " nodes, more than the output arrays hold");
+        if ((((uintptr_t)lo | (uintptr_t)count | (uintptr_t)unitig | (uintptr_t)rank) & 7) || (((uintptr_t)indeg | (uintptr_t)outdeg) & 3))
+            throw prim::Error(-22, "de bruijn nodes: an output is not aligned to its width");
+        debruijn_copy(D.lo.p, lo, nn, "debruijn.copy_lo");
+        debruijn_copy(D.count.p, count, nn, "debruijn.copy_count");
+        debruijn_copy(D.unitig.p, unitig, nn, "debruijn.copy_unitig");
+        debruijn_copy(D.rank.p, rank, nn, "debruijn.copy_rank");
+        if (indeg && nn) prim::d2d(indeg, D.indeg.p, nn * 4);
+        if (outdeg && nn) prim::d2d(outdeg, D.outdeg.p, nn * 4);
+        prim::sync();
+    }
+    static void debruijn_edges(const ImageDeBruijn &D, u64 *inoff, u64 *from, u64 *weight, u64 *row, u64 capacity) {
+        if (!inoff && !from && !weight && !row) throw prim::Error(-22, "de bruijn edges: no output");
+        const u64 nn = D.i.n_nodes, ne = D.i.n_edges;
+        if (capacity < ne)
+            throw prim::Error(-22, "de bruijn edges: " + std::to_string(ne) + " edges, more than the output arrays hold");
+        if (((uintptr_t)inoff | (uintptr_t)from | (uintptr_t)weight | (uintptr_t)row) & 7) throw prim::Error(-22, "de bruijn edges: an output is not aligned to 8 bytes");
+        if (inoff) { if (nn) debruijn_copy(D.inoff.p, inoff, nn + 1, "debruijn.copy_in_offsets"); else prim::dev_memset(inoff, 0, 8); }
+        debruijn_copy(D.from.p, from, ne, "debruijn.copy_from");
+        debruijn_copy(D.weight.p, weight, ne, "debruijn.copy_weight");
+        debruijn_copy(D.row.p, row, ne, "debruijn.copy_row");
+        prim::sync();
+    }
+    static void debruijn_unitigs(const ImageDeBruijn &D, const FmIndex *F, int w, u64 *uoff, u64 *nodes, void *cells, u64 *weight, u8 *circ, u64 cap_u,
+                                 u64 cap_n, u64 cap_c) {
+        if (!uoff && !nodes && !cells && !weight && !circ) throw prim::Error(-22, "de bruijn unitigs: no output");
+        const u64 nn = D.i.n_nodes, nu = D.i.n_unitigs, nc = D.i.n_cells, k = D.i.k;
+        if ((uoff || weight || circ) && cap_u < nu)
+            throw prim::Error(-22, "de bruijn unitigs: " + std::to_string(nu) + " unitigs, more than the output arrays hold");
+        if (nodes && cap_n < nn) throw prim::Error(-22, "de bruijn unitigs: " + std::to_string(nn) + " nodes, more than the output array holds");
+        if (cells && cap_c < nc) throw prim::Error(-22, "de bruijn unitigs: " + std::to_string(nc) + " cells, more than the output array holds");
+        if (((uintptr_t)uoff | (uintptr_t)nodes | (uintptr_t)weight) & 7) throw prim::Error(-22, "de bruijn unitigs: an output is not aligned to 8 bytes");
+        if (cells) {
+            if (!(w == 1 || w == 2 || w == 4 || w == 8)) throw prim::Error(-22, "de bruijn unitigs: cell_bytes is " + std::to_string(w) + ", not 1, 2, 4 or 8");
+            if ((uintptr_t)cells & (uintptr_t)(w - 1)) throw prim::Error(-22, "de bruijn unitigs: an output is not aligned to its width");
+            if (!F) throw prim::Error(-22, "de bruijn unitigs: the cells need the index the graph was made from");
+            if (F->n != D.i.n || F->R != D.R || F->k != D.i.n_strings || F->sigma != D.sigma || (F->n && debruijn_print(*F) != D.print))
+                throw prim::Error(-22, "de bruijn unitigs: not the index the graph was made from");
+            if (w < 8 && F->R) {
+                const u64 top = F->alpha.p ? F->alpha.get(F->alpha.n - 1) : (u64)F->key.get(F->R - 1).host_sym();
+                if (top >> (8 * w))
+                    throw prim::Error(-22, "de bruijn unitigs: the image's largest symbol " + std::to_string(top) + " does not fit cell_bytes = " + std::to_string(w));
+            }
+        }
+        if (uoff) { if (nu) debruijn_copy(D.uoff.p, uoff, nu + 1, "debruijn.copy_node_offsets"); else prim::dev_memset(uoff, 0, 8); }
+        debruijn_copy(D.uweight.p, weight, nu, "debruijn.copy_unitig_weight");
+        if (circ && nu) prim::d2d(circ, D.ucirc.p, nu);
+        if ((nodes || cells) && nn) {
+            DBuf<idx_t> order(nn);
+            prim::for_each(nn, DbOrderFn{D.unitig.p, D.rank.p, D.uoff.p, order.p}, "debruijn.order");
+            debruijn_copy(order.p, nodes, nn, "debruijn.copy_nodes");
+            if (cells) {
+                DBuf<RankCell> frc;
+                fm_run_cells(*F, frc);
+                const KmerStepFn step{frc.p, F->key.p, F->slf.p, F->alpha.p};
+                with_cell(w, [&](auto c) {
+                    typedef decltype(c) cell_t;
+#ifdef GRLBWT_PRIM_HIP
+                    if (prim::sw().dev_debruijn != 'f') prim::db_first_cells<cell_t, idx_t>(nc, nu, k, D.uoff.p, order.p, D.lo.p, step, (cell_t *)cells);
+                    else
+#endif
+                        prim::for_each(nn, DbFirstCellFn<cell_t>{step, order.p, D.unitig.p, D.lo.p, k, (cell_t *)cells}, "debruijn.first_cells_plain");
+                    if (k > 1) prim::for_each(nu, DbTailCellsFn<cell_t>{step, order.p, D.uoff.p, D.lo.p, k, (cell_t *)cells}, "debruijn.tail_cells");
+                });
+            }
+        }
+        prim::sync();
     }
     // ---- the strings behind row ranges (functor block "the strings behind row ranges").  docs_create computes what
     // the handle keeps and holds no pointer into the index afterwards.  Everything that can refuse it for its arguments or for

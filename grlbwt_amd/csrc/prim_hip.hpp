@@ -4910,6 +4910,61 @@ inline u32 top_search_entries(int bits, u64 n_keys, size_t key_bytes) {
     return b ? (u32)1 << b : 0;
 }
 
+// ------------------------------------------------------------------ the compacted de Bruijn graph (grlbwt_debruijn_*)
+// Both passes of the edge search go through top_search: a workgroup's kTopThreads lanes take kDbTileNodes consecutive nodes at a
+// time.  (An emit kernel that staged a tile's entries in LDS and stored them with consecutive lanes on consecutive entries was
+// built and measured against the lanes storing their own: 22.4 against 15.8 ms for 79 M edges, the record kept as
+// profiles/fm_debruijn/debruijn_staged_emit.txt.  With about one in-edge per node the lanes' own stores already fall on
+// consecutive entries, and the tile form adds two barriers at which a workgroup waits for its longest search.  It was deleted.
+// The limit of that evidence: one input, uniform reads with about one in-edge per node, on a tree that is not kept; an input
+// with many in-edges per node -- a wide alphabet, a small k -- spreads a lane's entries and was not measured.)
+static constexpr int kDbTileNodes = kTopThreads;
+static constexpr int kDbTileCells = 4096;
+// The first cells of the unitigs' nodes.  Unitig j takes cells [S(j), S(j + 1)), S(j) = uoff[j] + j (k - 1), ascending in j;
+// place r = c - S(j) of it, where r < uoff[j + 1] - uoff[j], is the first cell of node nodes[uoff[j] + r]: one step(q) from
+// q = nlo[node], whose returned cell is the symbol of the sorted run that holds q.  The places behind are the tail's walk and
+// are left alone.  A workgroup takes kDbTileCells consecutive cells; threads 0 and 1 find the unitigs of the tile's first and
+// last cell by one search each, every lane then finds its cell's unitig between the two.  Lanes take consecutive cells, so the
+// stores of a wave fall on consecutive addresses without a stage in LDS.
+//   Bounds: c < n_cells gives j <= nu - 1 with S(j) <= c < S(j + 1); r < the unitig's nodes is tested before nodes[] is read.
+//   Loops: the searches (at most 64 halvings), kDbTileCells / kBlock cells per lane.  The one barrier is reached by every thread.
+template <class IDX>
+__device__ __forceinline__ u64 db_unitig_of(const IDX *uoff, u64 k1, u64 a, u64 b, u64 c) {      // the last j in [a, b] with S(j) <= c
+    for (int it = 0; it < 64 && a < b; it++) {
+        const u64 mid = (a + b + 1) >> 1;
+        if ((u64)uoff[mid] + mid * k1 <= c) a = mid; else b = mid - 1;
+    }
+    return a;
+}
+template <class cell_t, class IDX, class STEP>
+__global__ void __launch_bounds__(kBlock) k_db_first_cells(u64 n_cells, u64 nu, u64 k1, const IDX *uoff, const IDX *nodes, const IDX *nlo, STEP step,
+                                                           cell_t *cells) {
+    __shared__ u64 s_j[2];
+    const u64 c0 = (u64)blockIdx.x * kDbTileCells, c1 = c0 + kDbTileCells < n_cells ? c0 + kDbTileCells : n_cells;
+    if (threadIdx.x < 2) s_j[threadIdx.x] = db_unitig_of(uoff, k1, 0, nu - 1, threadIdx.x == 0 ? c0 : c1 - 1);
+    __syncthreads();
+    const u64 ja = s_j[0], jb = s_j[1];
+    for (u64 c = c0 + threadIdx.x; c < c1; c += kBlock) {
+        const u64 j = db_unitig_of(uoff, k1, ja, jb, c);
+        const u64 o = (u64)uoff[j], r = c - (o + j * k1);
+        if (r < (u64)uoff[j + 1] - o) {
+            u64 q = (u64)nlo[(u64)nodes[o + r]];
+            cells[c] = (cell_t)step(q);
+        }
+    }
+}
+template <class cell_t, class IDX, class STEP>
+inline void db_first_cells(u64 n_cells, u64 nu, u64 k, const IDX *uoff, const IDX *nodes, const IDX *nlo, STEP step, cell_t *cells) {
+    if (n_cells == 0 || nu == 0) return;
+    const u64 tiles = (n_cells + kDbTileCells - 1) / kDbTileCells;
+    if (tiles > 0x7FFFFFFFull) throw Error(-75, "db_first_cells: more cells than one launch takes");
+    prof_begin("debruijn.first_cells", n_cells * sizeof(cell_t));
+    hipLaunchKernelGGL((k_db_first_cells<cell_t, IDX, STEP>), dim3((unsigned)tiles), dim3(kBlock), 0, rt().stream, n_cells, nu, k - 1, uoff, nodes, nlo,
+                       step, cells);
+    prof_end();
+    after_launch("debruijn.first_cells");
+}
+
 // ------------------------------------------------------------------ walks of uneven length: lanes that take tickets
 // m work items ("tickets"), each a chain of dependent steps whose number is known only when it ends (the segments of a
 // checkpointed LF walk: near-geometric lengths).  One item per lane through k_for_each makes a wave last as long as the longest

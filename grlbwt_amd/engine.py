@@ -44,6 +44,8 @@ ABI_SYMBOLS = [
     "grlbwt_fm_kmers", "grlbwt_fm_kmer_info_get",
     "grlbwt_fm_repeats", "grlbwt_fm_repeat_info_get",
     "grlbwt_docs_create", "grlbwt_docs_destroy", "grlbwt_docs_info_get", "grlbwt_docs_count", "grlbwt_docs_list",
+    "grlbwt_debruijn_create", "grlbwt_debruijn_destroy", "grlbwt_debruijn_info_get", "grlbwt_debruijn_nodes", "grlbwt_debruijn_edges",
+    "grlbwt_debruijn_unitigs",
     "grlbwt_merge_create", "grlbwt_merge_info_get", "grlbwt_merge_emit", "grlbwt_merge_interleave", "grlbwt_merge_destroy",
     "grlbwt_merge_files",
     "grlbwt_select_create", "grlbwt_select_info_get", "grlbwt_select_emit", "grlbwt_select_rows", "grlbwt_select_destroy",
@@ -130,6 +132,12 @@ class DocsInfo(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in ("n_rows", "n_strings", "flags", "idx_bytes", "held_bytes", "scratch_bytes", "sort_bits", "form",
                                           "walk_steps", "n_ranges", "n_range_rows", "n_entries", "largest_range", "most_docs",
                                           "tile_entries")]
+
+
+class DeBruijnInfo(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("k", "n_rows", "n_strings", "n_distinct", "n_nodes", "n_edges", "n_unitigs", "n_circular",
+                                          "longest_unitig", "n_cells", "max_in_degree", "max_out_degree", "passes", "length_passes",
+                                          "backward_steps", "jump_rounds", "tile_nodes", "tile_cells", "handle_bytes", "scratch_bytes")]
 
 
 class ImageStats(C.Structure):
@@ -306,6 +314,12 @@ def load_library(path=None, allow_test_standin=False):
     L.grlbwt_docs_info_get.argtypes = [vp, C.POINTER(DocsInfo)]
     L.grlbwt_docs_count.argtypes = [vp, vp, vp, vp, u64, vp, C.POINTER(u64)]
     L.grlbwt_docs_list.argtypes = [vp, vp, vp, vp, u64, vp, vp, vp, vp, vp, u64, C.POINTER(u64)]
+    L.grlbwt_debruijn_create.argtypes = [vp, vp, u64, u64, u64, C.c_uint32, C.POINTER(vp)]
+    L.grlbwt_debruijn_destroy.argtypes = [vp, vp]
+    L.grlbwt_debruijn_info_get.argtypes = [vp, C.POINTER(DeBruijnInfo)]
+    L.grlbwt_debruijn_nodes.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, u64]
+    L.grlbwt_debruijn_edges.argtypes = [vp, vp, vp, vp, vp, vp, u64]
+    L.grlbwt_debruijn_unitigs.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, vp, u64, u64, u64]
     L.grlbwt_merge_create.argtypes = [vp, vp, u64, vp, u64, i32, u64, C.POINTER(vp)]
     L.grlbwt_merge_info_get.argtypes = [vp, C.POINTER(MergeInfo)]
     L.grlbwt_merge_emit.argtypes = [vp, vp, vp, u64]
@@ -977,6 +991,12 @@ class FmIndex:
         also keeps what list() needs to count every document's occurrences.  The handle holds no pointer into this index."""
         return FmDocs(self, occurrences)
 
+    def de_bruijn(self, k, min_count=1, max_count=0):
+        """A DeBruijn handle: the compacted de Bruijn graph of the k-mers with max(min_count, 1) <= count <= max_count (0: no
+        bound) -- the nodes of kmers(k, min_count, max_count), the edges between them, the degrees and the unitigs.  The handle
+        holds no pointer into this index; only the cells of the unitigs read it again."""
+        return DeBruijn(self, k, min_count, max_count)
+
     @staticmethod
     def distinct_kmers(rows_at, suffixes_of, k=None):
         """The number of distinct k-mers (windows of k cells that hold no separator) from the histograms of lcp(): the rows with
@@ -1055,6 +1075,132 @@ class FmDocs:
         h, self._h = getattr(self, "_h", None), None
         if h and getattr(self.ctx, "_h", None):       # (a closed context has released its handles)
             self.ctx._ck(self.ctx.L.grlbwt_docs_destroy(self.ctx._h, h))
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class DeBruijn:
+    """The compacted de Bruijn graph of a collection from its FM index (grlbwt_debruijn_*).  Node v is entry v of
+    FmIndex.kmers(k, min_count, max_count); the edges are the windows of k + 1 cells between two nodes, in ascending (to, from),
+    as the CSR of in-edges; a unitig is a maximal path over edges u -> v with out_degree[u] == in_degree[v] == 1, circular ones
+    starting at their smallest node.  The *_raw forms take device pointers (None: not wanted) and capacities; the others size
+    themselves from info() and return numpy arrays.  Made by FmIndex.de_bruijn(); the index may be closed before the handle,
+    except for unitigs() with cells."""
+
+    def __init__(self, fm, k, min_count=1, max_count=0, flags=0):
+        self.ctx, self.fm = fm.ctx, fm
+        h = C.c_void_p()
+        self.ctx._ck(self.ctx.L.grlbwt_debruijn_create(self.ctx._h, fm._h, k, min_count, max_count, flags, C.byref(h)))
+        self._h = h
+
+    def info(self):
+        out = DeBruijnInfo()
+        rc = self.ctx.L.grlbwt_debruijn_info_get(self._h, C.byref(out))
+        if rc != OK:
+            raise GrlbwtError(rc, self.ctx.L.grlbwt_strerror(rc).decode())
+        return _as_dict(out)
+
+    def nodes_raw(self, lo_ptr=None, count_ptr=None, in_degree_ptr=None, out_degree_ptr=None, unitig_ptr=None, rank_ptr=None, capacity=0):
+        """uint64 per node for lo, count, unitig and rank (the node's place inside its unitig), uint32 for the two degrees."""
+        self.ctx._ck(self.ctx.L.grlbwt_debruijn_nodes(self.ctx._h, self._h, C.c_void_p(lo_ptr), C.c_void_p(count_ptr), C.c_void_p(in_degree_ptr),
+                                                      C.c_void_p(out_degree_ptr), C.c_void_p(unitig_ptr), C.c_void_p(rank_ptr), capacity))
+
+    def edges_raw(self, in_offsets_ptr=None, from_ptr=None, weight_ptr=None, row_ptr=None, capacity=0):
+        """in_offsets: n_nodes + 1 uint64; from, weight and row: uint64 per edge, room for `capacity` edges."""
+        self.ctx._ck(self.ctx.L.grlbwt_debruijn_edges(self.ctx._h, self._h, C.c_void_p(in_offsets_ptr), C.c_void_p(from_ptr), C.c_void_p(weight_ptr),
+                                                      C.c_void_p(row_ptr), capacity))
+
+    def unitigs_raw(self, fm=None, cell_bytes=1, node_offsets_ptr=None, nodes_ptr=None, cells_ptr=None, weight_ptr=None, circular_ptr=None,
+                    capacity_unitigs=0, capacity_nodes=0, capacity_cells=0):
+        """node_offsets: n_unitigs + 1 uint64; nodes: n_nodes uint64; cells: n_cells values of cell_bytes bytes (needs fm, the
+        index the graph was made from); weight: uint64 and circular: a byte per unitig."""
+        self.ctx._ck(self.ctx.L.grlbwt_debruijn_unitigs(self.ctx._h, self._h, fm._h if fm is not None else None, cell_bytes,
+                                                        C.c_void_p(node_offsets_ptr), C.c_void_p(nodes_ptr), C.c_void_p(cells_ptr),
+                                                        C.c_void_p(weight_ptr), C.c_void_p(circular_ptr), capacity_unitigs, capacity_nodes,
+                                                        capacity_cells))
+
+    def _rooms(self):
+        import numpy as np
+        on_device = self.ctx.L.grlbwt_backend_name() == b"hip-gfx950"      # (the test stand-in's "device" is host memory)
+        if on_device:
+            import torch
+
+        def room(nbytes):
+            if on_device:
+                t = torch.zeros(max(nbytes, 8), dtype=torch.uint8, device="cuda:0")
+                torch.cuda.synchronize()
+                return t, t.data_ptr()
+            a = np.zeros(max(nbytes, 8), dtype=np.uint8)
+            return a, a.ctypes.data
+
+        def back(buf, nbytes, dtype):
+            if on_device:
+                torch.cuda.synchronize()
+                return buf.cpu().numpy()[:nbytes].copy().view(dtype)
+            return buf[:nbytes].copy().view(dtype)
+
+        return room, back
+
+    def nodes(self):
+        """A dict of numpy arrays: lo, count, unitig, rank (uint64) and in_degree, out_degree (uint32), one entry per node."""
+        import numpy as np
+        room, back = self._rooms()
+        n = self.info()["n_nodes"]
+        names = (("lo", 8), ("count", 8), ("in_degree", 4), ("out_degree", 4), ("unitig", 8), ("rank", 8))
+        bufs = [room(n * w) for _, w in names]
+        self.nodes_raw(*[p for _, p in bufs], capacity=n)
+        return {name: back(b, n * w, np.uint64 if w == 8 else np.uint32) for (name, w), (b, _) in zip(names, bufs)}
+
+    def edges(self):
+        """(in_offsets, from, weight, row) as numpy uint64 arrays: the in-edges of node v are entries in_offsets[v] .. in_offsets[v + 1]."""
+        import numpy as np
+        room, back = self._rooms()
+        i = self.info()
+        n, m = i["n_nodes"], i["n_edges"]
+        off, fr, wt, row = room(8 * (n + 1)), room(8 * m), room(8 * m), room(8 * m)
+        self.edges_raw(off[1], fr[1], wt[1], row[1], m)
+        return back(off[0], 8 * (n + 1), np.uint64), back(fr[0], 8 * m, np.uint64), back(wt[0], 8 * m, np.uint64), back(row[0], 8 * m, np.uint64)
+
+    def unitigs(self, cells=True, cell_bytes=None):
+        """A dict of numpy arrays: node_offsets (n_unitigs + 1), nodes (n_nodes), weight and circular per unitig and, with
+        cells=True, cells (all unitigs' cells back to back, as symbol values) and cell_offsets (n_unitigs + 1), the closed form
+        node_offsets[j] + j * (k - 1).  cell_bytes None: the narrowest width that holds the index's largest symbol, found by trying."""
+        import numpy as np
+        room, back = self._rooms()
+        i = self.info()
+        n, u, nc, k = i["n_nodes"], i["n_unitigs"], i["n_cells"], i["k"]
+        off, nodes, wt, circ = room(8 * (u + 1)), room(8 * n), room(8 * u), room(u)
+        widths = (1, 2, 4, 8) if cell_bytes is None and cells else (cell_bytes or 1,)
+        for j, w in enumerate(widths):
+            out, pout = room(nc * w) if cells else (None, None)
+            try:
+                self.unitigs_raw(self.fm if cells else None, w, off[1], nodes[1], pout, wt[1], circ[1], u, n, nc)
+                break
+            except GrlbwtError as e:
+                if e.code != -22 or j + 1 == len(widths) or "does not fit" not in str(e):
+                    raise
+        res = {"node_offsets": back(off[0], 8 * (u + 1), np.uint64), "nodes": back(nodes[0], 8 * n, np.uint64),
+               "weight": back(wt[0], 8 * u, np.uint64), "circular": back(circ[0], u, np.uint8)}
+        if cells:
+            dt = {1: np.uint8, 2: np.uint16, 4: np.uint32, 8: np.uint64}[w]
+            res["cells"] = back(out, nc * w, dt)
+            res["cell_offsets"] = res["node_offsets"] + np.arange(u + 1, dtype=np.uint64) * np.uint64(max(k, 1) - 1) if nc else np.zeros(u + 1, dtype=np.uint64)
+        return res
+
+    def close(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h and getattr(self.ctx, "_h", None):       # (a closed context has released its handles)
+            self.ctx._ck(self.ctx.L.grlbwt_debruijn_destroy(self.ctx._h, h))
 
     def __enter__(self):
         return self

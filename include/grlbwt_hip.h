@@ -731,8 +731,8 @@ int grlbwt_fm_sa_info_get(const grlbwt_fm *fm, grlbwt_fm_sa_info *out);
  * first pass, when the scratch does not fit the free memory: about one byte per row, reported as scratch_bytes.
  * The call works on any index of grlbwt_fm_create, with or without GRLBWT_FM_LOCATE, in both position widths and on compacted
  * alphabets; it makes no handle and leaves the index, its index_bytes and every later answer as they were.  GRLBWT_LCP_ROUND keeps
- * its meaning for the passes.  OUT OF SCOPE: canonical (strand-merged) k-mers, the edges of the de Bruijn graph, a command-line
- * flag, a multi-GPU form, skipping rows that are already final in the passes.
+ * its meaning for the passes.  OUT OF SCOPE: canonical (strand-merged) k-mers, a command-line flag, a multi-GPU form, skipping
+ * rows that are already final in the passes.  The edges of the de Bruijn graph and its unitigs: grlbwt_debruijn_create.
  * grlbwt_fm_kmer_info_get: the counters of the last grlbwt_fm_kmers on the index that got as far as counting (a call that the
  * capacity then refuses included). */
 #define GRLBWT_FM_KMER_MAX_BINS 16384
@@ -901,6 +901,91 @@ int grlbwt_docs_count(grlbwt_ctx *ctx, const grlbwt_docs *docs, const uint64_t *
 int grlbwt_docs_list(grlbwt_ctx *ctx, const grlbwt_docs *docs, const uint64_t *dev_lo, const uint64_t *dev_hi, uint64_t n_ranges,
                      uint64_t *dev_entry_offsets /* n_ranges + 1 words */, uint64_t *dev_string, uint64_t *dev_first_row /* may be NULL */,
                      uint64_t *dev_occ /* may be NULL */, uint64_t *dev_range /* may be NULL */, uint64_t capacity, uint64_t *n_entries_out);
+
+/* ---- the compacted de Bruijn graph of the collection: the nodes that grlbwt_fm_kmers writes, the edges between them with their
+ * weights, the degrees, and the unitigs (maximal non-branching paths) with their nodes and cells -- what an assembler or a
+ * sequence-graph builder takes from a k-mer counter and a compactor, from the .rl_bwt image alone, on the device.
+ *
+ * DEFINITIONS, part of the contract.  Coordinates are those of grlbwt_fm_count and grlbwt_fm_kmers; a window is a run of cells
+ * of one string that holds no separator.
+ *   NODE: a distinct k-mer with max(min_count, 1) <= count <= max_count (0: no upper bound).  Node id v is the k-mer's index in
+ *     the whole-window table of grlbwt_fm_kmers(k, min_count, max_count): ids 0 .. n_nodes - 1 in ascending lo, lexicographic order.
+ *   EDGE u -> v: a window w of k + 1 cells that occurs in the collection, whose first k cells are node u and whose last k cells
+ *     are node v.  Its weight is the number of occurrences of w, its row the lo of w: [row, row + weight) is what
+ *     grlbwt_fm_count answers for w.  The graph is edge-centric: two nodes that overlap by k - 1 cells but never occur side by
+ *     side have no edge; an edge whose other end was filtered out does not exist; a self-loop (AAA, k = 2) is an edge.
+ *   EDGE ORDER: ascending (to, from) -- for a fixed `to` also ascending first cell of `from`.  The table is the CSR of in-edges:
+ *     the in-edges of v are entries dev_in_offsets[v] .. dev_in_offsets[v + 1].
+ *   DEGREES: in_degree[v] and out_degree[v] count edges of the filtered graph.
+ *   UNITIG: an edge u -> v is compactable when out_degree[u] == 1 and in_degree[v] == 1.  A unitig is a maximal path
+ *     v_0 .. v_{m-1} whose consecutive edges are all compactable; every node lies in exactly one unitig, which may be a single
+ *     node.  A component in which every node has in-degree and out-degree 1 through compactable edges is a cycle, down to one
+ *     node with a self-loop: one CIRCULAR unitig that starts at its smallest node id and does not repeat that node at its end.
+ *   UNITIG ORDER: ascending id of the first node.
+ *   UNITIG CELLS: unitig j of m nodes has k + m - 1 cells, the k cells of v_0 followed by the last cell of each further node.
+ *     The cells of all unitigs lie back to back, those of unitig j from dev_node_offsets[j] + j * (k - 1) on: a closed form, no
+ *     cell-offset array is written; n_cells = n_nodes + n_unitigs * (k - 1).  Wide and compacted alphabets are written as their
+ *     values, as grlbwt_fm_extract and grlbwt_fm_kmers write them.
+ *   UNITIG WEIGHT: the sum of the counts of its nodes.
+ * Strands are not merged: a collection built with -R holds both strands and yields both copies of every unitig.
+ *
+ * grlbwt_debruijn_create does all the work; info has the exact sizes; the three writers copy and decode.  Every output array of
+ * a writer is optional; a call with no array at all is GRLBWT_EINVAL, and so is an array together with a capacity below what
+ * info reports (nodes: n_nodes; edges: n_edges, dev_in_offsets takes n_nodes + 1 words whatever the capacity; unitigs: n_unitigs
+ * for node_offsets (+ 1 word) / weight / circular, n_nodes for dev_nodes, n_cells for dev_cells) -- nothing is written then.
+ * grlbwt_debruijn_nodes: dev_unitig[v] and dev_rank[v] are v's unitig and its place inside it.  The handle holds no pointer into
+ * the index, which may be destroyed first; only grlbwt_debruijn_unitigs with dev_cells reads the index again, for the forward
+ * steps: it must be the index the handle was made from (checked by its sizes and a fingerprint of its runs taken at create time,
+ * GRLBWT_EINVAL otherwise), and a symbol value that does not fit cell_bytes is refused before the first store.  Without dev_cells
+ * the index may be NULL.
+ *
+ * ALGORITHM: the passes and the selection of grlbwt_fm_kmers give the nodes.  For node v with rows [lo, hi), every symbol a above
+ * the separator that occurs in BWT[lo, hi) takes one backward step to [lo2, hi2), the rows of a.v -- always a window of k + 1
+ * cells, because the BWT symbol of a row whose suffix starts with k cells of a string precedes them in that string.  The last
+ * boundary bit at or before lo2 heads the k-mer of its first k cells; if that head is selected, this is an edge from its rank.
+ * The symbols come in ascending order from the lower bound of (a + 1, 0) in the sorted runs, and the enumeration ends as soon as
+ * the steps account for all of the node's rows, so a node whose rows hold one symbol stops at it.  Two passes of this one search
+ * (grlbwt_fm_approx's shape): the first writes in_degree and adds to out_degree, a scan gives in_offsets, the second writes the
+ * entries.  A workgroup's lanes take tile_nodes consecutive nodes under the LDS top level of the searches and store their own
+ * entries, which for consecutive nodes are consecutive entries.  Unitigs: link[v] is v's only in-edge when it is
+ * compactable; pointer jumping in counted rounds of separate launches, at most ceil(log2 n_nodes) + 1, carries (pointer, steps,
+ * smallest id seen); what has found no head then lies on cycles, whose smallest ids become heads, and a second set of rounds
+ * ranks their nodes.  Nothing waits for another thread.  The cell at place r < m of a unitig is the first cell of its r-th node,
+ * read off the sorted run that holds the node's lo; the last k - 1 cells are k - 1 forward steps from the last node's lo, the
+ * only dependent chains: n_unitigs * (k - 1) steps.  A workgroup writes tile_cells consecutive cells after one search per tile
+ * for its unitigs, consecutive lanes on consecutive addresses.
+ *
+ * grlbwt_debruijn_create refuses with GRLBWT_EINVAL: k = 0; min_count > max_count != 0; flags other than 0; a null index; an
+ * image that is not the BWT of a collection (the refusal of grlbwt_fm_lcp's passes); with GRLBWT_ENOMEM scratch that does not fit
+ * the free memory, before the first pass.  k larger than every string and n_rows = 0 give legal empty graphs.  It works on any
+ * index of grlbwt_fm_create, with or without GRLBWT_FM_LOCATE, in both position widths and on compacted alphabets, and leaves
+ * the index as it was.  The context releases the handles that are still alive.
+ * OUT OF SCOPE: canonical (strand-merged) nodes, a GFA writer, tip and bubble removal, a command-line flag, a multi-GPU form. */
+typedef struct grlbwt_debruijn grlbwt_debruijn;
+typedef struct grlbwt_debruijn_info {
+    uint64_t k, n_rows, n_strings;
+    uint64_t n_distinct;                  /* distinct k-mers of the collection (grlbwt_fm_kmers' number) */
+    uint64_t n_nodes, n_edges;            /* after the count filter */
+    uint64_t n_unitigs, n_circular, longest_unitig /* nodes */, n_cells;
+    uint64_t max_in_degree, max_out_degree;
+    uint64_t passes, length_passes;       /* as grlbwt_fm_kmer_info */
+    uint64_t backward_steps;              /* of the edge search, both passes */
+    uint64_t jump_rounds;                 /* pointer-jumping rounds run, the cycle rounds included */
+    uint64_t tile_nodes, tile_cells;      /* nodes per workgroup step of the edge search; cells per workgroup of the unitig decode */
+    uint64_t handle_bytes, scratch_bytes;
+} grlbwt_debruijn_info;
+int grlbwt_debruijn_create(grlbwt_ctx *ctx, const grlbwt_fm *fm, uint64_t k, uint64_t min_count, uint64_t max_count /* 0: none */,
+                           uint32_t debruijn_flags /* 0 */, grlbwt_debruijn **out);
+int grlbwt_debruijn_destroy(grlbwt_ctx *ctx, grlbwt_debruijn *graph);
+int grlbwt_debruijn_info_get(const grlbwt_debruijn *graph, grlbwt_debruijn_info *out);
+int grlbwt_debruijn_nodes(grlbwt_ctx *ctx, const grlbwt_debruijn *graph, uint64_t *dev_lo, uint64_t *dev_count, uint32_t *dev_in_degree,
+                          uint32_t *dev_out_degree, uint64_t *dev_unitig, uint64_t *dev_rank /* place inside its unitig */, uint64_t capacity);
+int grlbwt_debruijn_edges(grlbwt_ctx *ctx, const grlbwt_debruijn *graph, uint64_t *dev_in_offsets /* n_nodes + 1 */, uint64_t *dev_from,
+                          uint64_t *dev_weight, uint64_t *dev_row, uint64_t capacity /* edges */);
+int grlbwt_debruijn_unitigs(grlbwt_ctx *ctx, const grlbwt_debruijn *graph, const grlbwt_fm *fm, int cell_bytes,
+                            uint64_t *dev_node_offsets /* n_unitigs + 1 */, uint64_t *dev_nodes /* n_nodes */, void *dev_cells /* n_cells */,
+                            uint64_t *dev_weight, uint8_t *dev_circular, uint64_t capacity_unitigs, uint64_t capacity_nodes,
+                            uint64_t capacity_cells);
 
 /* ---- merging two images: the image of the collection "strings of A, then strings of B" from the images of A and B, without the
  * texts -- a collection larger than one build is built in batches and folded together, a batch of new strings is added to an
