@@ -2346,6 +2346,36 @@ int grlbwt_fm_kmer_info_get(const grlbwt_fm *fm, grlbwt_fm_kmer_info *out) {
     if (fm->f32) fill(*fm->f32); else fill(*fm->f64);
     return GRLBWT_OK;
 }
+int grlbwt_fm_kmers_canonical(grlbwt_ctx *ctx, const grlbwt_fm *fm, uint64_t k, uint64_t min_count, uint64_t max_count, uint64_t row_begin, uint64_t row_end,
+                              const uint64_t *host_pairs, uint64_t n_pairs, int cell_bytes, void *dev_cells, uint64_t *dev_lo, uint64_t *dev_count,
+                              uint64_t *dev_mate_lo, uint64_t *dev_total, uint64_t capacity, uint64_t *n_classes_out, uint64_t *host_spectrum,
+                              uint64_t spectrum_bins) {
+    if (n_classes_out) *n_classes_out = 0;
+    if (!ctx || !fm || !(fm->f32 || fm->f64)) return refuse(ctx);
+    uint64_t n = 0;
+    const int rc = guarded(ctx, [&] {
+        if (fm->f32) grl32::Image::fm_ckmers(*fm->f32, k, min_count, max_count, row_begin, row_end, host_pairs, n_pairs, cell_bytes, dev_cells, dev_lo, dev_count,
+                                             dev_mate_lo, dev_total, capacity, n, n_classes_out != nullptr, host_spectrum, spectrum_bins);
+        else grl64::Image::fm_ckmers(*fm->f64, k, min_count, max_count, row_begin, row_end, host_pairs, n_pairs, cell_bytes, dev_cells, dev_lo, dev_count,
+                                     dev_mate_lo, dev_total, capacity, n, n_classes_out != nullptr, host_spectrum, spectrum_bins);
+    });
+    if (n_classes_out) *n_classes_out = n;
+    return rc;
+}
+int grlbwt_fm_kmers_canonical_info_get(const grlbwt_fm *fm, grlbwt_fm_ckmer_info *out) {
+    if (!fm || !out || !(fm->f32 || fm->f64)) return GRLBWT_EINVAL;
+    auto fill = [&](const auto &F) {
+        const auto &i = F.cinfo;
+        out->k = i.k; out->n_rows = i.n; out->n_strings = i.n_strings; out->n_distinct = i.n_distinct; out->n_windows = i.n_windows;
+        out->n_selected = i.n_selected; out->n_classes = i.n_classes; out->n_paired = i.n_paired; out->n_palindromes = i.n_palindromes;
+        out->n_single = i.n_single; out->n_no_complement = i.n_no_complement; out->largest_total = i.largest_total; out->passes = i.passes;
+        out->length_passes = i.length_passes; out->mate_walks = i.mate_walks; out->backward_steps = i.backward_steps;
+        out->forward_steps = i.forward_steps; out->tile_rows = i.tile_rows; out->tile_kmers = i.tile_kmers; out->mate_tile = i.mate_tile;
+        out->stage_bytes = i.stage_bytes; out->scratch_bytes = i.scratch_bytes;
+    };
+    if (fm->f32) fill(*fm->f32); else fill(*fm->f64);
+    return GRLBWT_OK;
+}
 int grlbwt_fm_repeats(grlbwt_ctx *ctx, const grlbwt_fm *fm, uint64_t min_len, uint64_t max_len, uint64_t min_count, uint64_t max_count, uint32_t repeat_flags,
                       uint64_t row_begin, uint64_t row_end, uint64_t *dev_lo, uint64_t *dev_count, uint64_t *dev_len, uint64_t *dev_split, uint64_t capacity,
                       uint64_t *n_repeats_out) {

@@ -1535,6 +1535,148 @@ struct KmerEmitFn {          // the generic decode, prim::for_each_set_bit over 
     }
 };
 
+// ---- the strand-merged k-mers (grlbwt_fm_kmers_canonical).  The reverse complement of the k-mer x of head p is
+// found without its cells being stored anywhere: the forward walk from p yields x_0, x_1, ... and the backward search for
+// rc(x) = comp(x_{k-1}) ... comp(x_0) consumes its pattern from the last cell, comp(x_0), onward -- the same order -- so one item
+// alternates a forward step (KmerStepFn's, here for the symbol CODE) with one fm_step on a range that starts at [0, n).
+//   mate[e] of the head with rank e: the head row of rc(x) when it occurs; kCkNone when it does not; kCkNoComp when a cell of x
+//   has no pair in the map.  The walk may end as soon as the range is empty -- unless the image holds a symbol without a pair
+//   (`rest`): then the forward steps go on to cell k - 1, since a cell behind the one that emptied the range may be one.
+//   The complement table: at most kCkMaxTable (code, comp) entries in ascending code, one per symbol of the image that the map
+//   names; comp = kCkAbsent when the image does not hold the complement's value (the k-mer has a reverse complement, which
+//   cannot occur).  The ticket kernel copies it to LDS and hands step() that copy; the generic form reads it from memory.
+//   Bounds: q < n stays below n (KmerStepFn's argument); fm_step is in bounds on any image and returns ends in [0, n]; a
+//   non-empty final [a, b) has a < n, and cnt(a) is asked only where a is a set bit of H, which is one of B.  On an image that is
+//   not the BWT of a collection a final range that is no whole interval of a head counts as absent.
+//   Loops: at most min(k, n) steps per item, each one forward step and at most one fm_step; the table's search halves at most
+//   9 times.  One writer per entry; the only atomics are the three step counters', striped over kCkStripes slots.
+static constexpr idx_t kCkNone = (idx_t)~(idx_t)0, kCkNoComp = (idx_t)(kCkNone - 1);       // (both above every row: n < 2^32 - 256 with 32-bit positions)
+static constexpr u32 kCkAbsent = 0xFFFFFFFFu;
+static constexpr u32 kCkMaxTable = 256;
+static constexpr u64 kCkStripes = 1024;
+struct CkPair { u32 code, comp; };
+struct CkCodeFn {            // the i-th value of the pairs -> its symbol code, kCkAbsent when no run of the image holds it
+    FmCountFn f; const u64 *vals; u32 *codes;
+    GRL_DEV void operator()(u64 i) const {
+        u32 c = 0, out = kCkAbsent;
+        if (f.code(vals[i], c) && c != kCkAbsent) {
+            u64 a = 0, b = f.R;
+            for (int it = 0; it < 64 && a < b; it++) { const u64 mid = (a + b) >> 1; if (f.key[mid].below(c, 0)) a = mid + 1; else b = mid; }
+            if (a < f.R && f.key[a].sym() == c) out = c;
+        }
+        codes[i] = out;
+    }
+};
+struct KmerMateFn {
+    typedef FmKey Key;
+    typedef CkPair Pair;
+    static constexpr u32 kMaxTable = kCkMaxTable;
+    struct State { u64 q, a, b, t; u32 bwd, flag; };          // flag 1: the range is empty; 2: a cell without complement
+    const RankCell *frc; const FmKey *key; const idx_t *slf; u64 R, n, kw;      // (kw = min(k, n) steps)
+    const u64 *H; KmerCountFn cnt; const CkPair *tab; u32 nt; bool rest;
+    idx_t *mate; u64 *ctr;
+    GRL_HD const FmKey *keys() const { return key; }
+    GRL_HD u64 n_keys() const { return R; }
+    GRL_HD const CkPair *table() const { return tab; }
+    GRL_HD u32 n_table() const { return nt; }
+    GRL_DEV bool begin(u64 p, State &st) const {
+        st.q = p; st.a = 0; st.b = n; st.t = 0; st.bwd = 0; st.flag = 0;
+        return p < n && kw > 0;
+    }
+    // 0: c has no pair; 1: its complement is not in the image; 2: cc is the complement's code
+    GRL_DEV static int comp(const CkPair *tb, u32 nt, u32 c, u32 &cc) {
+        u32 a = 0, b = nt;
+        for (int it = 0; it < 9 && a < b; it++) { const u32 mid = (a + b) >> 1; if (tb[mid].code < c) a = mid + 1; else b = mid; }
+        if (a >= nt || tb[a].code != c) return 0;
+        cc = tb[a].comp;
+        return cc == kCkAbsent ? 1 : 2;
+    }
+    template <class TOP>
+    GRL_DEV bool step(State &st, const TOP &top, const CkPair *tb) const {       // ONE forward step and at most ONE fm_step
+        const u64 j = run_of_row(frc, st.q);
+        const FmKey kj = key[j];
+        st.q = kj.start() + (st.q - (u64)slf[j]);
+        st.t++;
+        u32 cc = 0;
+        const int r = comp(tb, nt, kj.sym(), cc);
+        if (r == 0) { st.flag = 3; return true; }
+        if (!(st.flag & 1u)) {
+            if (r == 1) st.flag = 1;
+            else {
+                u64 a = st.a, b = st.b;
+                fm_step(key, slf, R, top, cc, a, b);
+                st.bwd++;
+                if (a >= b) st.flag = 1; else { st.a = a; st.b = b; }
+            }
+        }
+        return st.t >= kw || ((st.flag & 1u) && !rest);
+    }
+    GRL_DEV void end(u64 e, const State &st) const {
+        idx_t m = kCkNone;
+        if (st.flag & 2u) m = kCkNoComp;
+        else if (!(st.flag & 1u) && st.a < st.b && st.b <= n && lcp_bit(H, st.a) && st.b - st.a == cnt(st.a)) m = (idx_t)st.a;
+        mate[e] = m;
+        u64 *c = ctr + (e & (kCkStripes - 1)) * 4;
+        if (st.bwd) prim::atomic_add(&c[0], (u64)st.bwd); else prim::atomic_add(&c[2], (u64)1);      // (c[2]: the heads that started no search)
+        prim::atomic_add(&c[1], st.t);
+    }
+};
+struct KmerMateEachFn {      // the generic form, prim::for_each_set_bit over H: one lane per head, the table in memory, no top level
+    KmerMateFn f;
+    GRL_DEV void operator()(u64 p, u64 e) const {
+        KmerMateFn::State st;
+        if (!f.begin(p, st)) return;
+        while (!f.step(st, FmNoTop{}, f.tab)) {}
+        f.end(e, st);
+    }
+};
+struct CkRank {              // the rank of head p among the heads
+    const u64 *H; const idx_t *hrank;
+    GRL_DEV u64 operator()(u64 p) const { return (u64)hrank[p >> 6] + (u64)__builtin_popcountll(H[p >> 6] & ((1ull << (p & 63)) - 1ull)); }
+};
+struct CkRepPred {           // the representatives: the heads without a mate, or with one at or behind them
+    CkRank rk; const idx_t *mate;
+    GRL_DEV bool operator()(u64 p) const { return lcp_bit(rk.H, p) && (u64)mate[rk(p)] >= p; }
+};
+struct CkTotalFn {           // total(p) of a head p: its own rows and its mate's
+    KmerCountFn cnt; CkRank rk; const idx_t *mate;
+    GRL_DEV u64 operator()(u64 p) const {
+        const idx_t m = mate[rk(p)];
+        u64 c = cnt(p);
+        if (m < kCkNoComp && (u64)m != p) c += cnt((u64)m);
+        return c;
+    }
+};
+struct CkSelPred {
+    const u64 *rep; CkTotalFn tot; KmerFilter flt;
+    GRL_DEV bool operator()(u64 p) const { return lcp_bit(rep, p) && flt(p, tot(p)); }
+};
+struct CkClassIn {           // 1 at a head that is the first of a pair (what 0), a palindrome (1), without reverse complement (2)
+    CkRank rk; const idx_t *mate; int what;
+    GRL_DEV u64 operator()(u64 p) const {
+        if (!lcp_bit(rk.H, p)) return 0ull;
+        const idx_t m = mate[rk(p)];
+        if (what == 2) return m == kCkNoComp ? 1ull : 0ull;
+        if (m >= kCkNoComp) return 0ull;
+        return (what == 0 ? (u64)m > p : (u64)m == p) ? 1ull : 0ull;
+    }
+};
+struct CkWindowsIn {         // KmerWindowsIn over the representatives, by total
+    const u64 *rep; CkTotalFn tot;
+    GRL_DEV u64 operator()(u64 p) const { return lcp_bit(rep, p) ? tot(p) : 0ull; }
+};
+struct CkSpectrumFn {        // KmerSpectrumFn over the representatives, by total
+    CkTotalFn tot; u64 *bins; u64 last;
+    GRL_DEV void operator()(u64 p, u64) const { const u64 c = tot(p); prim::atomic_add(&bins[c < last ? c : last], (u64)1); }
+};
+struct CkEmitFn {            // prim::for_each_set_bit over the selection: the two columns that prim::kmer_decode does not write
+    CkTotalFn tot; u64 *mate_lo, *total;
+    GRL_DEV void operator()(u64 p, u64 e) const {
+        if (mate_lo) { const idx_t m = tot.mate[tot.rk(p)]; mate_lo[e] = m >= kCkNoComp ? ~0ull : (u64)m; }
+        if (total) total[e] = tot(p);
+    }
+};
+
 // ---- the compacted de Bruijn graph (grlbwt_debruijn_*).  The nodes are the selected k-mers in ascending lo; node
 // v holds rows [lo, lo + count).  An in-edge of v is a symbol a above the separator that occurs in BWT[lo, lo + count): one
 // backward step gives the rows [lo2, hi2) of the window a.v, which lie inside the interval of its first k cells; that interval's
@@ -2252,6 +2394,16 @@ struct Image {
         u64 tile_rows = kKmerTileRows, tile_kmers = kKmerTileEntries, stage_bytes = kKmerStageBytes, scratch_bytes = 0;
     };
 #ifdef GRLBWT_PRIM_HIP
+    static constexpr u64 kCkMateTile = prim::kTopThreads;
+#else
+    static constexpr u64 kCkMateTile = 1024;     // (the serial form has no tiles: the figure the device library reports)
+#endif
+    struct CkmerInfo {        // of the last fm_ckmers that got as far as counting
+        u64 k = 0, n = 0, n_strings = 0, n_distinct = 0, n_windows = 0, n_selected = 0, n_classes = 0, n_paired = 0, n_palindromes = 0, n_single = 0,
+            n_no_complement = 0, largest_total = 0, passes = 0, length_passes = 0, mate_walks = 0, backward_steps = 0, forward_steps = 0;
+        u64 tile_rows = kKmerTileRows, tile_kmers = kKmerTileEntries, mate_tile = kCkMateTile, stage_bytes = kKmerStageBytes, scratch_bytes = 0;
+    };
+#ifdef GRLBWT_PRIM_HIP
     static constexpr u64 kRepTileRows = prim::kRepTile;
 #else
     static constexpr u64 kRepTileRows = kRepFanout * kRepFanout;      // (the serial form has no tiles: the figure the device library reports)
@@ -2284,6 +2436,7 @@ struct Image {
         mutable LcpInfo linfo;    // of the last fm_lcp
         mutable SaInfo sinfo;     // of the last fm_sa
         mutable KmerInfo kinfo;   // of the last fm_kmers that got as far as counting
+        mutable CkmerInfo cinfo;  // of the last fm_ckmers that got as far as counting
         mutable RepeatInfo rinfo; // of the last fm_repeats that got as far as counting
         mutable OverlapInfo oinfo; // of the last fm_overlaps, fm_overlaps_of or fm_overlap_targets
         u64 extract_bytes() const { return (T.n + xq.n + xc.n) * sizeof(idx_t); }
@@ -2838,6 +2991,13 @@ struct Image {
             prim::bitvector_from_pred(n, KmerSelPred{H, cnt(), flt}, sel, "kmer.select");
             ki.n_selected = (u64)prim::exclusive_scan<idx_t>(nw, PopcIn{sel}, L.brank.p, true, "kmer.select_ranks");
         }
+        // the same over the representatives of the strand-merged classes, by total (fm_ckmers); returns the number selected
+        u64 select_classes(const u64 *rep, const CkTotalFn &tot, const KmerFilter &flt) {
+            const u64 nw = FmLcp::words_of(n);
+            prim::dev_memset(sel, 0, nw * 8);
+            prim::bitvector_from_pred(n, CkSelPred{rep, tot, flt}, sel, "ckmer.select");
+            return (u64)prim::exclusive_scan<idx_t>(nw, PopcIn{sel}, L.brank.p, true, "ckmer.select_ranks");
+        }
     };
     // ---- the distinct k-mers with their counts (functor block "the distinct k-mers with their counts").  Everything
     // that can refuse the call runs before the first store: the arguments, the memory, the passes (an image that is not the BWT
@@ -2911,6 +3071,160 @@ struct Image {
 #endif
                 prim::for_each_set_bit<idx_t>(n, sel, L.brank.p, KmerEmitFn<cell_t>{step, cnt, k, (cell_t *)cells, lo, count}, "kmer.decode_plain");
         });
+        prim::sync();
+    }
+    // ---- the strand-merged k-mers (functor block "the strand-merged k-mers").  fm_kmers' order of events: the
+    // arguments and the complement map, the memory, the passes, the mates (whose array is sized by the head count), the capacity;
+    // then the spectrum is copied to the host and the table is written.  Nothing is stored into an output before the last refusal.
+    //   Device form of the mate pass: prim::kmer_mates, one ticket per head rank under the LDS top level with the complement
+    //   table in LDS; generic form, the serial stand-in's and with GRLBWT_DEV_KMER_MATES=f the device's: for_each_set_bit over H.
+    //   The cells, lo and count go through fm_kmers' own decode; mate_lo and total through one for_each_set_bit over the selection.
+    //   Loops: those of fm_kmers, and at most min(k, n) steps per head in the mate pass.  Nothing waits for another thread.
+    static void fm_ckmers(const FmIndex &F, u64 k, u64 min_count, u64 max_count, u64 row_begin, u64 row_end, const u64 *host_pairs, u64 n_pairs, int w,
+                          void *cells, u64 *lo, u64 *count, u64 *mate_lo, u64 *total, u64 capacity, u64 &n_classes, bool want_n, u64 *host_spectrum,
+                          u64 bins) {
+        static const char *const kWho = "fm canonical kmers: ";
+        n_classes = 0;
+        if (k == 0) throw prim::Error(-22, std::string(kWho) + "k is 0");
+        if (!(w == 1 || w == 2 || w == 4 || w == 8)) throw prim::Error(-22, std::string(kWho) + "cell_bytes is " + std::to_string(w) + ", not 1, 2, 4 or 8");
+        if (!cells && !lo && !count && !mate_lo && !total && !host_spectrum && !want_n) throw prim::Error(-22, std::string(kWho) + "no output");
+        if (host_spectrum && (bins == 0 || bins > kKmerMaxBins))
+            throw prim::Error(-22, std::string(kWho) + std::to_string(bins) + " spectrum bins, not 1 to " + std::to_string(kKmerMaxBins));
+        const u64 n = F.n;
+        if (row_end > n) row_end = n;                            // (UINT64_MAX: n_rows)
+        if (row_begin > row_end)
+            throw prim::Error(-22, std::string(kWho) + "rows [" + std::to_string(row_begin) + ", " + std::to_string(row_end) + ") are no window of " +
+                                       std::to_string(n) + " rows");
+        if (cells && w < 8 && F.R) {
+            const u64 top = F.alpha.p ? F.alpha.get(F.alpha.n - 1) : (u64)F.key.get(F.R - 1).host_sym();
+            if (top >> (8 * w))
+                throw prim::Error(-22, std::string(kWho) + "the image's largest symbol " + std::to_string(top) + " does not fit cell_bytes = " + std::to_string(w));
+        }
+        if ((cells && ((uintptr_t)cells & (uintptr_t)(w - 1))) || ((uintptr_t)lo & 7) || ((uintptr_t)count & 7) || ((uintptr_t)mate_lo & 7) || ((uintptr_t)total & 7))
+            throw prim::Error(-22, std::string(kWho) + "an output is not aligned to its width");
+        // ---- the complement map: every value in at most one pair, the separator in none
+        if (n_pairs > 128) throw prim::Error(-22, std::string(kWho) + "n_pairs is " + std::to_string(n_pairs) + ", more than 128");
+        if (!host_pairs && n_pairs) throw prim::Error(-22, std::string(kWho) + "host_pairs is NULL with n_pairs = " + std::to_string(n_pairs));
+        static const u64 kDna[4] = {'A', 'T', 'C', 'G'};
+        if (!host_pairs) { host_pairs = kDna; n_pairs = 2; }
+        std::vector<u64> vals(host_pairs, host_pairs + 2 * n_pairs);
+        {
+            std::vector<u64> seen;
+            for (u64 i = 0; i < n_pairs; i++) {
+                seen.push_back(vals[2 * i]);
+                if (vals[2 * i + 1] != vals[2 * i]) seen.push_back(vals[2 * i + 1]);
+            }
+            std::sort(seen.begin(), seen.end());
+            for (size_t i = 1; i < seen.size(); i++)
+                if (seen[i] == seen[i - 1]) throw prim::Error(-22, std::string(kWho) + "the value " + std::to_string(seen[i]) + " is listed twice in the pairs");
+            if (F.R && std::binary_search(seen.begin(), seen.end(), F.sepval))
+                throw prim::Error(-22, std::string(kWho) + "the separator's value " + std::to_string(F.sepval) + " is in a pair");
+        }
+        const bool table = cells || lo || count || mate_lo || total;
+        const u64 nb = host_spectrum ? bins : 1;
+        CkmerInfo ci;
+        ci.k = k; ci.n = n; ci.n_strings = F.k;
+        std::vector<u64> spec(nb, 0);
+        if (n == 0) { F.cinfo = ci; if (host_spectrum) std::memcpy(host_spectrum, spec.data(), nb * 8); return; }
+        const u64 nw = FmLcp::words_of(n);
+        const u64 fixed = kCkMaxTable * sizeof(CkPair) + 2 * n_pairs * 12 + (kCkStripes * 4 + 2) * 8;
+        ci.scratch_bytes = KmerSel::scratch_bytes(n) + nb * 8 + (nw + 1) * sizeof(idx_t) + fixed;
+        if (n >= ((u64)1 << 62) || ci.scratch_bytes > prim::mem_available())
+            throw prim::Error(-12, std::string(kWho) + "the passes need " + std::to_string(ci.scratch_bytes) + " bytes of device memory, more than is free");
+        // ---- the table of (code, comp code), in ascending code: the values go to codes on the device
+        DBuf<CkPair> dtab(kCkMaxTable);
+        u32 nt = 0;
+        if (n_pairs) {
+            DBuf<u64> dv(2 * n_pairs);
+            DBuf<u32> dc(2 * n_pairs);
+            prim::h2d(dv.p, vals.data(), 2 * n_pairs * 8);
+            prim::for_each(2 * n_pairs, CkCodeFn{fm_count_fn(F, nullptr, 8, nullptr, nullptr, nullptr), dv.p, dc.p}, "ckmer.codes");
+            const std::vector<u32> codes = dc.to_host(2 * n_pairs);
+            std::vector<CkPair> tab;
+            for (u64 i = 0; i < n_pairs; i++) {
+                const u32 a = codes[2 * i], b = codes[2 * i + 1];
+                if (a != kCkAbsent) tab.push_back(CkPair{a, b});
+                if (b != kCkAbsent && vals[2 * i] != vals[2 * i + 1]) tab.push_back(CkPair{b, a});
+            }
+            std::sort(tab.begin(), tab.end(), [](const CkPair &x, const CkPair &y) { return x.code < y.code; });
+            nt = (u32)tab.size();
+            if (nt) prim::h2d(dtab.p, tab.data(), nt * sizeof(CkPair));
+        }
+        const bool rest = (u64)nt + 1 < F.sigma;                 // a symbol besides the separator has no pair
+        KmerSel K;
+        KmerInfo ki;
+        K.heads(F, k, ki);
+        ci.passes = ki.passes; ci.length_passes = ki.length_passes;
+        FmLcp &L = K.L;
+        const u64 *H = K.H;
+        u64 *rep = L.Sold;
+        const KmerCountFn cnt = K.cnt();
+        DBuf<idx_t> hrank(nw + 1);
+        ci.n_distinct = (u64)prim::exclusive_scan<idx_t>(nw, PopcIn{H}, hrank.p, true, "ckmer.head_ranks");
+        ci.scratch_bytes += ci.n_distinct * sizeof(idx_t);
+        if (ci.n_distinct * sizeof(idx_t) > prim::mem_available())
+            throw prim::Error(-12, std::string(kWho) + "the mates need " + std::to_string(ci.n_distinct * sizeof(idx_t)) + " bytes of device memory, more than is free");
+        DBuf<idx_t> mate(ci.n_distinct);
+        mate.fill_ff();
+        // ---- the mate pass
+        if (ci.n_distinct) {
+            DBuf<u64> ctr(kCkStripes * 4 + 2);
+            ctr.zero();
+            const KmerMateFn f{L.frc.p, F.key.p, F.slf.p, F.R, n, k < n ? k : n, H, cnt, dtab.p, nt, rest, mate.p, ctr.p};
+#ifdef GRLBWT_PRIM_HIP
+            if (prim::sw().dev_kmer_mates != 'f') (void)prim::kmer_mates<idx_t>(ci.n_distinct, f, H, hrank.p, n, ctr.p + kCkStripes * 4, F.top_entries);
+            else
+#endif
+                prim::for_each_set_bit<idx_t>(n, H, hrank.p, KmerMateEachFn{f}, "ckmer.mates_plain");
+            const std::vector<u64> hc = ctr.to_host(kCkStripes * 4);
+            u64 idle = 0;
+            for (u64 s = 0; s < kCkStripes; s++) { ci.backward_steps += hc[4 * s]; ci.forward_steps += hc[4 * s + 1]; idle += hc[4 * s + 2]; }
+            ci.mate_walks = ci.n_distinct - idle;
+        }
+        // ---- representatives, totals, the spectrum, the classes
+        const CkRank rk{H, hrank.p};
+        const CkTotalFn tot{cnt, rk, mate.p};
+        prim::dev_memset(rep, 0, nw * 8);
+        prim::bitvector_from_pred(n, CkRepPred{rk, mate.p}, rep, "ckmer.representatives");
+        DBuf<u64> dbins(nb);
+#ifdef GRLBWT_PRIM_HIP
+        prim::kmer_spectrum(n, rep, tot, (u32)nb, dbins.p, ci.n_classes, ci.n_windows, ci.largest_total);
+#else
+        dbins.zero();
+        (void)prim::exclusive_scan<idx_t>(nw, PopcIn{rep}, L.brank.p, true, "ckmer.class_ranks");
+        prim::for_each_set_bit<idx_t>(n, rep, L.brank.p, CkSpectrumFn{tot, dbins.p, nb - 1}, "ckmer.spectrum");
+        ci.n_classes = prim::reduce_sum<u64>((n + 63) / 64, PopcIn{rep}, "ckmer.classes");
+        ci.n_windows = prim::reduce_sum<u64>(n, CkWindowsIn{rep, tot}, "ckmer.windows");
+        ci.largest_total = prim::reduce_max<u64>(n, CkWindowsIn{rep, tot}, "ckmer.largest");
+#endif
+        prim::d2h(spec.data(), dbins.p, nb * 8);
+        ci.n_paired = prim::reduce_sum<u64>(n, CkClassIn{rk, mate.p, 0}, "ckmer.paired");
+        ci.n_palindromes = prim::reduce_sum<u64>(n, CkClassIn{rk, mate.p, 1}, "ckmer.palindromes");
+        ci.n_no_complement = prim::reduce_sum<u64>(n, CkClassIn{rk, mate.p, 2}, "ckmer.no_complement");
+        ci.n_single = ci.n_classes - ci.n_paired - ci.n_palindromes;
+        const KmerFilter flt{row_begin, row_end, min_count ? min_count : 1, max_count ? max_count : ~0ull};
+        ci.n_selected = K.select_classes(rep, tot, flt);
+        if (cells) ci.forward_steps += ci.n_selected * k;
+        prim::sync();
+        F.cinfo = ci;
+        n_classes = ci.n_selected;
+        if (table && n_classes > capacity)
+            throw prim::Error(-22, std::string(kWho) + std::to_string(n_classes) + " classes, more than the output arrays hold");
+        if (host_spectrum) std::memcpy(host_spectrum, spec.data(), nb * 8);
+        if (!table || n_classes == 0) return;
+        const u64 *sel = K.sel;
+        if (cells || lo || count) {
+            const KmerStepFn step{L.frc.p, F.key.p, F.slf.p, F.alpha.p};
+            with_cell(w, [&](auto c) {
+                typedef decltype(c) cell_t;
+#ifdef GRLBWT_PRIM_HIP
+                if (prim::sw().dev_kmer_decode != 'f') prim::kmer_decode<cell_t, idx_t>(n_classes, k, sel, L.brank.p, n, step, cnt, (cell_t *)cells, lo, count);
+                else
+#endif
+                    prim::for_each_set_bit<idx_t>(n, sel, L.brank.p, KmerEmitFn<cell_t>{step, cnt, k, (cell_t *)cells, lo, count}, "kmer.decode_plain");
+            });
+        }
+        if (mate_lo || total) prim::for_each_set_bit<idx_t>(n, sel, L.brank.p, CkEmitFn{tot, mate_lo, total}, "ckmer.emit");
         prim::sync();
     }
     // ---- the right-maximal and maximal repeats (functor block "the right-maximal and maximal repeats").  Everything

@@ -5124,4 +5124,89 @@ inline WalkStats top_tickets(u64 m, F f, u64 *ctr, u32 top_entries, const char *
     return ws;
 }
 
+// ------------------------------------------------------------------ the mates of the k-mer heads (grlbwt_fm_kmers_canonical)
+// k_top_tickets with two additions: ticket e is the head with rank e among the set bits of H, found as k_kmer_decode finds an
+// entry (kmer_word_of over the exclusive word ranks hrank[0 .. nwords], then the bit inside the word), and the functor's
+// complement table -- at most F::kMaxTable entries of F::Pair, 2 KB -- stands in LDS beside the top level; step() gets both.  An
+// item alternates one forward step with one backward step (image_impl.hpp, "the strand-merged k-mers").  Tickets, not a tile of
+// lanes in lock-step: in a one-strand read set most searches are empty after about log_sigma n steps while their neighbours,
+// whose reverse complements occur, run all k -- a tile would wait for its longest walk.  Measured against the generic form
+// (for_each_set_bit over the heads, no top level, the table in memory) at k = 31, profiles/fm_ckmers/ckmers.txt: 1.42 against 2.28 s
+// for 140 M heads and 2.23 against 3.51 s for 291 M on read collections that hold both strands (every search 31 steps; 3.1 and
+// 4.1 G backward steps/s), 143 against 139 ms and 294 against 239 ms on the same collections with one strand (14 steps on average).
+//   LDS per workgroup: the top level (at most 32 KB of 8-byte keys, 64 KB of 16-byte keys, dynamic) and 2 KB of table (static);
+//     the sum is checked against rt().lds_bytes, and where a full top level leaves the table no room the launcher keeps half
+//     of it.  Two workgroups of 1024 threads still fit a CU's 160 KiB.
+//   Bounds: e < m = hrank[nwords] gives a word w <= nwords - 1 with hrank[w] <= e < hrank[w + 1] whose (e - hrank[w])-th set bit
+//     exists, so p = 64 w + bit < n; begin() refuses any other p.  t < nt <= F::kMaxTable is tested by the launcher.  The walk's
+//     own bounds are the functor's: rows stay below n (the argument of KmerStepFn), fm_step is in bounds on any image.
+//   Loops: the two copy loops, then ticket_loop; an item takes at most min(k, n) steps; begin's search halves nwords at most 64
+//     times and clears at most 63 bits.  The ONE barrier stands behind the copies, in front of the first exit: every thread of
+//     the workgroup reaches it.  No thread waits for another; the atomics are the ticket word's and the functor's step counters.
+//   Registers on gfx950: profiles/fm_ckmers/kernel_resources.txt.
+template <class F, class IDX>
+struct KmerMateTicketFn {
+    typedef typename F::Key Key;
+    typedef typename F::State State;
+    F f; const u64 *H; const IDX *hrank; u64 nwords;
+    __device__ __forceinline__ bool begin(u64 e, State &st) const {
+        const u64 w = kmer_word_of(hrank, 0, nwords - 1, e);
+        u64 word = H[w];
+        const u32 r = (u32)(e - (u64)hrank[w]);
+        for (u32 i = 0; i < r && i < 63u; i++) word &= word - 1;
+        return f.begin(w * 64 + (u64)__builtin_ctzll(word | (1ull << 63)), st);
+    }
+    __device__ __forceinline__ void end(u64 e, const State &st) const { f.end(e, st); }
+};
+template <class F, class IDX>
+__global__ void __launch_bounds__(kTopThreads) k_kmer_mates(u64 m, u64 lanes, KmerMateTicketFn<F, IDX> tf, u64 *ctr, u32 top_n, u64 stride) {
+    typedef typename F::Key Key;
+    typedef typename F::Pair Pair;
+    extern __shared__ __attribute__((aligned(16))) u64 s_top[];
+    __shared__ Pair s_tab[F::kMaxTable];
+    Key *s = reinterpret_cast<Key *>(s_top);
+    const Key *keys = tf.f.keys();
+    for (u32 t = threadIdx.x; t < top_n; t += kTopThreads) s[t] = keys[(u64)t * stride];
+    const Pair *tab = tf.f.table();
+    const u32 nt = tf.f.n_table();
+    for (u32 t = threadIdx.x; t < nt && t < F::kMaxTable; t += kTopThreads) s_tab[t] = tab[t];
+    __syncthreads();
+    const u64 gid = (u64)blockIdx.x * kTopThreads + threadIdx.x;
+    if (gid >= lanes) return;                                   // (lanes is a multiple of 64: whole waves)
+    const LdsTop<Key> top{s, top_n, stride, tf.f.n_keys()};
+    ticket_loop(m, lanes, gid, tf, ctr, [&](typename F::State &st) { return tf.f.step(st, top, s_tab); });
+}
+// m: the set bits of H (hrank[nwords]); ctr: two words of device memory, the caller's; they are zeroed here.  top_entries: as top_search
+template <class IDX, class F>
+inline WalkStats kmer_mates(u64 m, F f, const u64 *H, const IDX *hrank, u64 nbits, u64 *ctr, u32 top_entries) {
+    WalkStats ws;
+    if (m == 0 || nbits == 0) return ws;
+    if (f.n_table() > F::kMaxTable) throw Error(-22, "kmer_mates: the complement table has more entries than the LDS copy");
+    const u64 R = f.n_keys();
+    const size_t tab_bytes = sizeof(typename F::Pair) * F::kMaxTable;
+    while (top_entries && (size_t)top_entries * sizeof(typename F::Key) + tab_bytes > rt().lds_bytes) top_entries /= 2;      // (room for the table: half the top level)
+    const u64 stride = top_entries ? (R + top_entries - 1) / top_entries : 1;
+    const u32 top_n = top_entries ? (u32)((R + stride - 1) / stride) : 0;
+    const size_t lds = (size_t)top_n * sizeof(typename F::Key);
+    if (lds + tab_bytes > rt().lds_bytes) throw Error(-71, "kmer_mates: the top level does not fit the LDS");
+    int occ = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_kmer_mates<F, IDX>, kTopThreads, lds) != hipSuccess || occ < 1) { (void)hipGetLastError(); occ = 1; }
+    const u64 m_up = (m + 63) / 64 * 64;
+    u64 lanes = sw().walk_lanes ? (sw().walk_lanes + 63) / 64 * 64 : (u64)rt().num_cus * (u64)occ * kTopThreads;
+    if (lanes > m_up) lanes = m_up;
+    const u64 blocks = (lanes + kTopThreads - 1) / kTopThreads;
+    if (blocks > 0x7FFFFFFFull) throw Error(-75, "kmer_mates: too many workgroups");
+    dev_memset(ctr, 0, 16);
+    const KmerMateTicketFn<F, IDX> tf{f, H, hrank, (nbits + 63) / 64};
+    prof_begin("ckmer.mates");
+    hipLaunchKernelGGL((k_kmer_mates<F, IDX>), dim3((unsigned)blocks), dim3(kTopThreads), lds, rt().stream, m, lanes, tf, ctr, top_n, stride);
+    prof_end();
+    after_launch("ckmer.mates");
+    u64 h[2];
+    d2h(h, ctr, 16);
+    ws.lanes = lanes;
+    ws.refills = h[1];
+    return ws;
+}
+
 }   // namespace prim

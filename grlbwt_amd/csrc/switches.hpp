@@ -93,6 +93,7 @@
     X(GRLBWT_DEV_WALK_STORES, dev_walk_stores, char, 0, "c[ells]: the checkpointed write walk stores u8/u16 cells one by one, not collected as aligned 8-byte words") \
     X(GRLBWT_DEV_OVERLAP_EXPAND, dev_overlap_expand, char, 0, "f[or_each]: grlbwt_fm_overlap_targets as a for_each with a search per entry, not the tile kernel") \
     X(GRLBWT_DEV_KMER_DECODE, dev_kmer_decode, char, 0, "f[or_each]: the table of grlbwt_fm_kmers through for_each_set_bit, one lane per entry storing its own cells, not the tile kernel") \
+    X(GRLBWT_DEV_KMER_MATES, dev_kmer_mates, char, 0, "f[or_each]: the mate pass of grlbwt_fm_kmers_canonical through for_each_set_bit over the heads, one lane per head without a top level and the complement table in memory, not the ticket kernel") \
     X(GRLBWT_DEV_DOCS_TILE, dev_docs_tile, char, 0, "f[or_each]: grlbwt_docs_count / grlbwt_docs_list through bitvector_from_pred and for_each_set_bit with a search per range row and per entry, not the tile kernels (entries with occurrences always are)") \
     X(GRLBWT_DEV_REPEAT_SEARCH, dev_repeat_search, char, 0, "f[or_each]: the counting and the selection of grlbwt_fm_repeats through reduces and bitvector_from_pred with searches in the tree in memory, the levels by for_each, not the tile and the minima kernel") \
     X(GRLBWT_DEV_DEBRUIJN, dev_debruijn, char, 0, "f[or_each]: the first cells of the unitigs of grlbwt_debruijn_unitigs through a for_each over the nodes, not the tile kernel") \

@@ -42,6 +42,7 @@ ABI_SYMBOLS = [
     "grlbwt_fm_lcp", "grlbwt_fm_lcp_info_get",
     "grlbwt_fm_sa", "grlbwt_fm_sa_info_get",
     "grlbwt_fm_kmers", "grlbwt_fm_kmer_info_get",
+    "grlbwt_fm_kmers_canonical", "grlbwt_fm_kmers_canonical_info_get",
     "grlbwt_fm_repeats", "grlbwt_fm_repeat_info_get",
     "grlbwt_docs_create", "grlbwt_docs_destroy", "grlbwt_docs_info_get", "grlbwt_docs_count", "grlbwt_docs_list",
     "grlbwt_debruijn_create", "grlbwt_debruijn_destroy", "grlbwt_debruijn_info_get", "grlbwt_debruijn_nodes", "grlbwt_debruijn_edges",
@@ -120,6 +121,13 @@ class SaInfo(C.Structure):
 class KmerInfo(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in ("k", "n_rows", "n_strings", "n_distinct", "n_windows", "n_selected", "largest_count", "passes",
                                           "length_passes", "forward_steps", "tile_rows", "tile_kmers", "stage_bytes", "scratch_bytes")]
+
+
+class CkmerInfo(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("k", "n_rows", "n_strings", "n_distinct", "n_windows", "n_selected", "n_classes", "n_paired",
+                                          "n_palindromes", "n_single", "n_no_complement", "largest_total", "passes", "length_passes",
+                                          "mate_walks", "backward_steps", "forward_steps", "tile_rows", "tile_kmers", "mate_tile",
+                                          "stage_bytes", "scratch_bytes")]
 
 
 class RepeatInfo(C.Structure):
@@ -307,6 +315,8 @@ def load_library(path=None, allow_test_standin=False):
     L.grlbwt_fm_sa_info_get.argtypes = [vp, C.POINTER(SaInfo)]
     L.grlbwt_fm_kmers.argtypes = [vp, vp, u64, u64, u64, u64, u64, i32, vp, vp, vp, u64, C.POINTER(u64), vp, u64]
     L.grlbwt_fm_kmer_info_get.argtypes = [vp, C.POINTER(KmerInfo)]
+    L.grlbwt_fm_kmers_canonical.argtypes = [vp, vp, u64, u64, u64, u64, u64, vp, u64, i32, vp, vp, vp, vp, vp, u64, C.POINTER(u64), vp, u64]
+    L.grlbwt_fm_kmers_canonical_info_get.argtypes = [vp, C.POINTER(CkmerInfo)]
     L.grlbwt_fm_repeats.argtypes = [vp, vp, u64, u64, u64, u64, C.c_uint32, u64, u64, vp, vp, vp, vp, u64, C.POINTER(u64)]
     L.grlbwt_fm_repeat_info_get.argtypes = [vp, C.POINTER(RepeatInfo)]
     L.grlbwt_docs_create.argtypes = [vp, vp, C.c_uint32, C.POINTER(vp)]
@@ -930,6 +940,101 @@ class FmIndex:
         """The counters of the last kmers() / kmer_spectrum() on this index that got as far as counting."""
         out = KmerInfo()
         rc = self.ctx.L.grlbwt_fm_kmer_info_get(self._h, C.byref(out))
+        if rc != OK:
+            raise GrlbwtError(rc, self.ctx.L.grlbwt_strerror(rc).decode())
+        return _as_dict(out)
+
+    @staticmethod
+    def _pairs(pairs):
+        """The complement map as grlbwt_fm_kmers_canonical takes it: (array of 2 * n_pairs uint64 or None, n_pairs).  pairs: None
+        (the DNA default), a sequence of (a, b) ints, or bytes such as b"ATCG" read pairwise."""
+        if pairs is None:
+            return None, 0
+        if isinstance(pairs, (bytes, bytearray)):
+            if len(pairs) % 2:
+                raise ValueError("pairs given as bytes are read pairwise: an even number of them")
+            flat = list(pairs)
+        else:
+            flat = [int(v) for ab in pairs for v in ab]
+            if len(flat) != 2 * len(pairs):
+                raise ValueError("pairs: a sequence of (a, b)")
+        return (C.c_uint64 * max(len(flat), 1))(*flat), len(flat) // 2
+
+    def canonical_kmers_raw(self, k, min_count=1, max_count=0, row_begin=0, row_end=None, pairs=None, cell_bytes=1, cells_ptr=None, lo_ptr=None,
+                            count_ptr=None, mate_lo_ptr=None, total_ptr=None, capacity=0, spectrum=None):
+        """grlbwt_fm_kmers_canonical as it is: device pointers (None: not wanted) for the table's cells (k values of cell_bytes
+        bytes per entry), lo, count, mate_lo and total (uint64 per entry), room for `capacity` entries; pairs as _pairs() reads
+        them; spectrum: a numpy uint64 array to fill, or None.  Returns the number of entries (classes).  More than `capacity`
+        with an array given: GrlbwtError whose n_classes attribute is that number, and nothing is written."""
+        got = C.c_uint64()
+        sp = spectrum.ctypes.data_as(C.c_void_p) if spectrum is not None else None
+        arr, n_pairs = self._pairs(pairs)
+        try:
+            self.ctx._ck(self.ctx.L.grlbwt_fm_kmers_canonical(
+                self.ctx._h, self._h, k, min_count, max_count, row_begin, UINT64_MAX if row_end is None else row_end,
+                None if arr is None else C.cast(arr, C.c_void_p), n_pairs, cell_bytes, C.c_void_p(cells_ptr), C.c_void_p(lo_ptr),
+                C.c_void_p(count_ptr), C.c_void_p(mate_lo_ptr), C.c_void_p(total_ptr), capacity, C.byref(got), sp,
+                0 if spectrum is None else len(spectrum)))
+        except GrlbwtError as e:
+            e.n_classes = got.value
+            raise
+        return got.value
+
+    def canonical_kmers(self, k, min_count=1, max_count=0, rows=None, pairs=None, cells=True, cell_bytes=None):
+        """The strand-merged k-mers: one entry per class {x, rc(x)} of the k-mers that occur, under the complement map `pairs`
+        (None: DNA, (A,T), (C,G); a sequence of (a, b) values; or bytes read pairwise), with max(min_count, 1) <= total <=
+        max_count (0: no bound) whose representative's first row lo lies in rows = (begin, end) (None: all rows), in ascending
+        lo: (lo, count, mate_lo, total, cells) as numpy arrays.  lo, count and cells are the representative's own, as kmers()
+        gives them; mate_lo is the lo of the other member (the entry's own for a palindrome, UINT64_MAX when there is none) and
+        total the sum of both counts.  cells=False: None for the cells.  Sized by the idiom of kmers()."""
+        import numpy as np
+        on_device = self.ctx.L.grlbwt_backend_name() == b"hip-gfx950"      # (the test stand-in's "device" is host memory)
+        if on_device:
+            import torch
+
+        def room(nbytes):
+            if on_device:
+                t = torch.zeros(max(nbytes, 8), dtype=torch.uint8, device="cuda:0")
+                torch.cuda.synchronize()
+                return t, t.data_ptr()
+            a = np.zeros(max(nbytes, 8), dtype=np.uint8)
+            return a, a.ctypes.data
+
+        def back(buf, nbytes):
+            if on_device:
+                torch.cuda.synchronize()
+                return buf.cpu().numpy()[:nbytes].copy()
+            return buf[:nbytes].copy()
+
+        rb, re = (0, None) if rows is None else rows
+        widths = (1, 2, 4, 8) if cell_bytes is None and cells else (cell_bytes or 1,)
+        n = self.canonical_kmers_raw(k, min_count, max_count, rb, re, pairs)
+        cols = [room(8 * n) for _ in range(4)]
+        for i, w in enumerate(widths):
+            out, pout = room(n * k * w) if cells else (None, None)
+            try:
+                got = self.canonical_kmers_raw(k, min_count, max_count, rb, re, pairs, w, pout, cols[0][1], cols[1][1], cols[2][1], cols[3][1], n)
+                break
+            except GrlbwtError as e:
+                if e.code != -22 or i + 1 == len(widths) or "does not fit" not in str(e):
+                    raise
+        dt = {1: np.uint8, 2: np.uint16, 4: np.uint32, 8: np.uint64}[w]
+        tab = back(out, got * k * w).view(dt).reshape(got, k) if cells else None
+        lo, cnt, mate, tot = (back(b, 8 * got).view(np.uint64) for b, _ in cols)
+        return lo, cnt, mate, tot, tab
+
+    def canonical_kmer_spectrum(self, k, bins=256, pairs=None):
+        """The abundance spectrum of the strand-merged k-mers: s[c] = the classes of the whole collection whose total is exactly
+        c, the last bin holding every total >= bins - 1.  Its sum is the number of classes."""
+        import numpy as np
+        s = np.zeros(bins, dtype=np.uint64)
+        self.canonical_kmers_raw(k, pairs=pairs, spectrum=s)
+        return s
+
+    def canonical_kmer_info(self):
+        """The counters of the last canonical_kmers() / canonical_kmer_spectrum() on this index that got as far as counting."""
+        out = CkmerInfo()
+        rc = self.ctx.L.grlbwt_fm_kmers_canonical_info_get(self._h, C.byref(out))
         if rc != OK:
             raise GrlbwtError(rc, self.ctx.L.grlbwt_strerror(rc).decode())
         return _as_dict(out)

@@ -731,8 +731,9 @@ int grlbwt_fm_sa_info_get(const grlbwt_fm *fm, grlbwt_fm_sa_info *out);
  * first pass, when the scratch does not fit the free memory: about one byte per row, reported as scratch_bytes.
  * The call works on any index of grlbwt_fm_create, with or without GRLBWT_FM_LOCATE, in both position widths and on compacted
  * alphabets; it makes no handle and leaves the index, its index_bytes and every later answer as they were.  GRLBWT_LCP_ROUND keeps
- * its meaning for the passes.  OUT OF SCOPE: canonical (strand-merged) k-mers, a command-line flag, a multi-GPU form, skipping
- * rows that are already final in the passes.  The edges of the de Bruijn graph and its unitigs: grlbwt_debruijn_create.
+ * its meaning for the passes.  OUT OF SCOPE: a command-line flag, a multi-GPU form, skipping rows that are already final in the
+ * passes.  Strand-merged (canonical) k-mers: grlbwt_fm_kmers_canonical.  The edges of the de Bruijn graph and its unitigs:
+ * grlbwt_debruijn_create.
  * grlbwt_fm_kmer_info_get: the counters of the last grlbwt_fm_kmers on the index that got as far as counting (a call that the
  * capacity then refuses included). */
 #define GRLBWT_FM_KMER_MAX_BINS 16384
@@ -752,6 +753,75 @@ int grlbwt_fm_kmers(grlbwt_ctx *ctx, const grlbwt_fm *fm, uint64_t k, uint64_t m
                     uint64_t *dev_lo /* may be NULL */, uint64_t *dev_count /* may be NULL */, uint64_t capacity,
                     uint64_t *n_kmers_out, uint64_t *host_spectrum /* may be NULL */, uint64_t spectrum_bins);
 int grlbwt_fm_kmer_info_get(const grlbwt_fm *fm, grlbwt_fm_kmer_info *out);
+
+/* ---- the strand-merged (canonical) k-mers with their counts, and their abundance spectrum.  A sequenced read comes from either
+ * strand, so k-mer counters count a k-mer together with its reverse complement; this call is grlbwt_fm_kmers with that merge,
+ * and it names the mate of every entry, which is what strand merging of the de Bruijn graph starts from.
+ *
+ * DEFINITIONS, part of the contract.  Coordinates, windows and k-mers are those of grlbwt_fm_kmers.
+ *   Complement map: host_pairs holds 2 * n_pairs symbol VALUES (what grlbwt_fm_extract writes); pair (a, b) means comp(a) = b
+ *     and comp(b) = a; a == b is legal and makes the symbol self-complementary (an unknown base).  host_pairs == NULL with
+ *     n_pairs == 0 is the DNA default (A,T), (C,G) in upper-case bytes.  A value the image does not hold is ignored: it takes no
+ *     entry of the table, and a symbol paired with it has a complement that cannot occur.  A symbol in no pair has no complement.
+ *   Reverse complement: rc(x) of a k-mer x = x_0 .. x_{k-1} whose cells all have complements is comp(x_{k-1}) .. comp(x_0).  A
+ *     k-mer with a cell that has no complement has no reverse complement.
+ *   Class: the set {x, rc(x)} restricted to the k-mers that occur in the collection.  It has one member when rc(x) does not
+ *     occur, when x has no reverse complement, or when x = rc(x) (a palindrome).
+ *   Representative: the member with the smaller lo -- the lexicographically smaller one among those that occur, in the image's
+ *     symbol order.  total is the sum of the members' counts.  The class's mate row is the lo of the other member; for a
+ *     palindrome the entry's own lo; for a class of one that is no palindrome UINT64_MAX.
+ * THE TABLE holds one entry per class, in ascending lo of the representative: dev_lo[e] and dev_count[e], the representative's
+ * own rows (exactly grlbwt_fm_kmers' pair), dev_mate_lo[e], dev_total[e] and the representative's k cells
+ * dev_cells[e * k .. (e + 1) * k).  [mate_lo, mate_lo + total - count) is what grlbwt_fm_count answers for the reverse complement
+ * of the cells when the mate exists and is not the entry itself.  min_count / max_count filter on total; the row window filters
+ * on the representative's lo, bounds the output memory and not the work, and windows that partition [0, n_rows) concatenate to
+ * the whole table.  Each of the five arrays may be NULL.  The sizing idiom, the alignment rule, the cell-width refusal and
+ * "nothing is written on a refusal, the spectrum included" are those of grlbwt_fm_kmers.
+ * THE SPECTRUM counts the classes of the WHOLE collection by total, with the bin rules of grlbwt_fm_kmers.
+ * CELLS: the representative's own.  (Another convention writes the lexicographically smaller of x and rc(x) even when only the
+ * larger one occurs; the two differ only for classes of one that have a reverse complement, and mate_lo == UINT64_MAX marks
+ * those.  That convention is out of scope.)
+ *
+ * ALGORITHM: the passes, heads and counts of grlbwt_fm_kmers.  The mate pass takes one ticket per head: the forward walk from
+ * the head row yields x_0, x_1, ..., and the backward search for rc(x) consumes comp(x_0), comp(x_1), ... in that same order,
+ * so the two interleave -- one forward step, one backward step on a range that starts at [0, n_rows) -- and no cell is stored.
+ * The walk ends when the range is empty; when the image holds a symbol that is in no pair, the forward steps alone go on to cell
+ * k - 1, because n_no_complement counts every k-mer with such a cell.  A lane that ends a walk takes the next ticket (mate_tile
+ * lanes per workgroup, the search array's top level and the complement table in LDS).  A head is a representative when it has
+ * no mate or one at or behind it; spectrum, selection and decode then run as in grlbwt_fm_kmers over the representatives.
+ * COST: grlbwt_fm_kmers' and backward_steps backward-search steps: about n_distinct * k on a collection that holds both strands,
+ * about n_distinct * log_sigma(n_rows) on one that does not.  Scratch: grlbwt_fm_kmers' and one position per distinct k-mer.
+ *
+ * GRLBWT_EINVAL before the first pass, with a message naming the value: those of grlbwt_fm_kmers; n_pairs > 128; host_pairs ==
+ * NULL with n_pairs > 0; a value listed twice in the pairs (it would have two complements, or the pair is a repeat); the
+ * separator's value in a pair.  GRLBWT_ENOMEM as grlbwt_fm_kmers, and once more after the head count when the mates do not fit.
+ * The call works on any index, with or without locate structures, in both position widths, on compacted and wide alphabets.  It
+ * makes no handle and leaves the index, its index_bytes and every later answer as they were, grlbwt_fm_kmer_info_get included.
+ * OUT OF SCOPE: the smaller-cells convention above; strand-merged nodes and unitigs of grlbwt_debruijn_* (they start from
+ * mate_lo); a command-line flag; a multi-GPU form.
+ * grlbwt_fm_kmers_canonical_info_get: the counters of the last grlbwt_fm_kmers_canonical on the index that got as far as counting.
+ * By definition n_distinct == 2 * n_paired + n_palindromes + n_single and the sum of all totals == n_windows. */
+typedef struct grlbwt_fm_ckmer_info {
+    uint64_t k, n_rows, n_strings;
+    uint64_t n_distinct, n_windows;         /* distinct k-mers of the collection (grlbwt_fm_kmers' number); the sum of their counts */
+    uint64_t n_selected;                    /* entries of the table: classes inside the window and the filter on total */
+    uint64_t n_classes;                     /* classes of the whole collection */
+    uint64_t n_paired, n_palindromes;       /* classes whose two members both occur; classes whose member is its own reverse complement */
+    uint64_t n_single, n_no_complement;     /* classes of one that are no palindrome; those of them with a cell that has no complement */
+    uint64_t largest_total;
+    uint64_t passes, length_passes;         /* as grlbwt_fm_kmer_info */
+    uint64_t mate_walks;                    /* heads that started a backward search (their first cell has a complement in the image) */
+    uint64_t backward_steps, forward_steps; /* of the mate pass; of the mate pass plus n_selected * k where dev_cells was given */
+    uint64_t tile_rows, tile_kmers;         /* as grlbwt_fm_kmer_info */
+    uint64_t mate_tile;                     /* heads (lanes) per workgroup of the mate kernel */
+    uint64_t stage_bytes, scratch_bytes;
+} grlbwt_fm_ckmer_info;
+int grlbwt_fm_kmers_canonical(grlbwt_ctx *ctx, const grlbwt_fm *fm, uint64_t k, uint64_t min_count, uint64_t max_count /* 0: none */,
+                              uint64_t row_begin, uint64_t row_end /* UINT64_MAX: n_rows */, const uint64_t *host_pairs /* NULL: DNA */,
+                              uint64_t n_pairs, int cell_bytes, void *dev_cells /* may be NULL */, uint64_t *dev_lo /* may be NULL */,
+                              uint64_t *dev_count /* may be NULL */, uint64_t *dev_mate_lo /* may be NULL */, uint64_t *dev_total /* may be NULL */,
+                              uint64_t capacity, uint64_t *n_classes_out, uint64_t *host_spectrum /* may be NULL */, uint64_t spectrum_bins);
+int grlbwt_fm_kmers_canonical_info_get(const grlbwt_fm *fm, grlbwt_fm_ckmer_info *out);
 
 /* ---- the right-maximal and maximal repeats of the collection: which row ranges are repeats at all -- the internal nodes of
  * the generalized suffix tree, what repeat analysis, repeat masking, shared-substring questions and sequence-graph construction
