@@ -51,6 +51,12 @@ struct grlbwt_debruijn {
     std::unique_ptr<grl64::Image::ImageDeBruijn> g64;
 };
 
+// a strand-merged compacted de Bruijn graph (grlbwt_cdebruijn_create): the nodes, the half-edges of their ends and the unitigs
+struct grlbwt_cdebruijn {
+    std::unique_ptr<grl32::Image::ImageCDeBruijn> g32;
+    std::unique_ptr<grl64::Image::ImageCDeBruijn> g64;
+};
+
 struct grlbwt_ctx {
     uint32_t flags = 0;
     int device = 0;
@@ -62,6 +68,7 @@ struct grlbwt_ctx {
     std::vector<grlbwt_select *> selects;    // and the selections
     std::vector<grlbwt_docs *> docs;         // and the document handles
     std::vector<grlbwt_debruijn *> graphs;   // and the de Bruijn graphs
+    std::vector<grlbwt_cdebruijn *> cgraphs; // and the strand-merged ones
 };
 
 namespace {
@@ -1813,6 +1820,8 @@ void grlbwt_ctx_destroy(grlbwt_ctx *ctx) {
         ctx->docs.clear();
         for (grlbwt_debruijn *g : ctx->graphs) delete g;
         ctx->graphs.clear();
+        for (grlbwt_cdebruijn *g : ctx->cgraphs) delete g;
+        ctx->cgraphs.clear();
         ctx->e32.reset(); ctx->e64.reset(); prim::sync(); prim::pool_trim();
         if (--prim::rt().live_ctx <= 0) {      // process-wide debug settings and a borrowed stream end with the last context
             prim::rt().live_ctx = 0;
@@ -2646,6 +2655,76 @@ int grlbwt_debruijn_unitigs(grlbwt_ctx *ctx, const grlbwt_debruijn *graph, const
                                                        dev_weight, dev_circular, capacity_unitigs, capacity_nodes, capacity_cells);
         else grl64::Image::debruijn_unitigs(*graph->g64, fm ? fm->f64.get() : nullptr, cell_bytes, dev_node_offsets, dev_nodes, dev_cells, dev_weight,
                                             dev_circular, capacity_unitigs, capacity_nodes, capacity_cells);
+    });
+}
+
+int grlbwt_cdebruijn_create(grlbwt_ctx *ctx, const grlbwt_fm *fm, uint64_t k, uint64_t min_count, uint64_t max_count, const uint64_t *host_pairs,
+                            uint64_t n_pairs, uint32_t cdebruijn_flags, grlbwt_cdebruijn **out) {
+    if (out) *out = nullptr;
+    if (!ctx || !fm || !out || !(fm->f32 || fm->f64)) return refuse(ctx);
+    return guarded(ctx, [&] {
+        std::unique_ptr<grlbwt_cdebruijn> g(new grlbwt_cdebruijn());
+        if (fm->f32) {
+            g->g32.reset(new grl32::Image::ImageCDeBruijn());
+            grl32::Image::cdebruijn_create(*fm->f32, k, min_count, max_count, host_pairs, n_pairs, cdebruijn_flags, *g->g32);
+        } else {
+            g->g64.reset(new grl64::Image::ImageCDeBruijn());
+            grl64::Image::cdebruijn_create(*fm->f64, k, min_count, max_count, host_pairs, n_pairs, cdebruijn_flags, *g->g64);
+        }
+        ctx->cgraphs.push_back(g.get());
+        *out = g.release();
+    });
+}
+int grlbwt_cdebruijn_destroy(grlbwt_ctx *ctx, grlbwt_cdebruijn *graph) {
+    if (!ctx) return GRLBWT_EINVAL;
+    if (!graph) return GRLBWT_OK;
+    auto it = std::find(ctx->cgraphs.begin(), ctx->cgraphs.end(), graph);
+    if (it == ctx->cgraphs.end()) { ctx->err = "canonical de bruijn destroy: not a handle of this context"; return GRLBWT_EINVAL; }
+    ctx->cgraphs.erase(it);
+    return guarded(ctx, [&] { prim::sync(); delete graph; });
+}
+int grlbwt_cdebruijn_info_get(const grlbwt_cdebruijn *graph, grlbwt_cdebruijn_info *out) {
+    if (!graph || !out || !(graph->g32 || graph->g64)) return GRLBWT_EINVAL;
+    auto fill = [&](const auto &G, uint64_t tile_nodes, uint64_t tile_cells) {
+        const auto &i = G.i;
+        out->k = i.k; out->n_rows = i.n; out->n_strings = i.n_strings; out->n_distinct = i.n_distinct; out->n_nodes = i.n_nodes; out->n_rigid = i.n_rigid;
+        out->n_palindromes = i.n_palindromes; out->n_edges = i.n_edges; out->n_half_edges = i.n_half_edges; out->n_hairpins = i.n_hairpins;
+        out->n_unitigs = i.n_unitigs; out->n_circular = i.n_circular; out->longest_unitig = i.longest; out->n_cells = i.n_cells;
+        out->max_end_degree = i.max_end_degree; out->passes = i.passes; out->length_passes = i.length_passes;
+        out->mate_backward_steps = i.mate_backward_steps; out->edge_backward_steps = i.edge_backward_steps; out->forward_steps = i.forward_steps;
+        out->cells_forward_steps = G.cells_forward_steps; out->jump_rounds = i.jump_rounds; out->tile_nodes = tile_nodes; out->tile_cells = tile_cells;
+        out->handle_bytes = G.held_bytes(); out->scratch_bytes = i.scratch_bytes;
+    };
+    if (graph->g32) fill(*graph->g32, grl32::Image::kCdbTileNodes, grl32::Image::kCdbTileCells);
+    else fill(*graph->g64, grl64::Image::kCdbTileNodes, grl64::Image::kCdbTileCells);
+    return GRLBWT_OK;
+}
+int grlbwt_cdebruijn_nodes(grlbwt_ctx *ctx, const grlbwt_cdebruijn *graph, uint64_t *dev_lo, uint64_t *dev_count, uint64_t *dev_mate_lo, uint64_t *dev_total,
+                           uint32_t *dev_degree0, uint32_t *dev_degree1, uint64_t *dev_unitig, uint64_t *dev_rank, uint8_t *dev_orient, uint64_t capacity) {
+    if (!ctx || !graph || !(graph->g32 || graph->g64)) return refuse(ctx);
+    return guarded(ctx, [&] {
+        if (graph->g32) grl32::Image::cdebruijn_nodes(*graph->g32, dev_lo, dev_count, dev_mate_lo, dev_total, dev_degree0, dev_degree1, dev_unitig, dev_rank, dev_orient, capacity);
+        else grl64::Image::cdebruijn_nodes(*graph->g64, dev_lo, dev_count, dev_mate_lo, dev_total, dev_degree0, dev_degree1, dev_unitig, dev_rank, dev_orient, capacity);
+    });
+}
+int grlbwt_cdebruijn_links(grlbwt_ctx *ctx, const grlbwt_cdebruijn *graph, uint64_t *dev_end_offsets, uint64_t *dev_other, uint64_t *dev_weight,
+                           uint64_t *dev_fwd_row, uint64_t *dev_fwd_count, uint64_t capacity) {
+    if (!ctx || !graph || !(graph->g32 || graph->g64)) return refuse(ctx);
+    return guarded(ctx, [&] {
+        if (graph->g32) grl32::Image::cdebruijn_links(*graph->g32, dev_end_offsets, dev_other, dev_weight, dev_fwd_row, dev_fwd_count, capacity);
+        else grl64::Image::cdebruijn_links(*graph->g64, dev_end_offsets, dev_other, dev_weight, dev_fwd_row, dev_fwd_count, capacity);
+    });
+}
+int grlbwt_cdebruijn_unitigs(grlbwt_ctx *ctx, const grlbwt_cdebruijn *graph, const grlbwt_fm *fm, int cell_bytes, uint64_t *dev_node_offsets,
+                             uint64_t *dev_nodes, void *dev_cells, uint64_t *dev_weight, uint8_t *dev_circular, uint64_t capacity_unitigs,
+                             uint64_t capacity_nodes, uint64_t capacity_cells) {
+    if (!ctx || !graph || !(graph->g32 || graph->g64)) return refuse(ctx);
+    if (fm && (graph->g32 ? !fm->f32 : !fm->f64)) return refuse(ctx, "canonical de bruijn unitigs: not the index the graph was made from");
+    return guarded(ctx, [&] {
+        if (graph->g32) grl32::Image::cdebruijn_unitigs(*graph->g32, fm ? fm->f32.get() : nullptr, cell_bytes, dev_node_offsets, dev_nodes, dev_cells,
+                                                        dev_weight, dev_circular, capacity_unitigs, capacity_nodes, capacity_cells);
+        else grl64::Image::cdebruijn_unitigs(*graph->g64, fm ? fm->f64.get() : nullptr, cell_bytes, dev_node_offsets, dev_nodes, dev_cells, dev_weight,
+                                             dev_circular, capacity_unitigs, capacity_nodes, capacity_cells);
     });
 }
 

@@ -1888,6 +1888,321 @@ struct DbPrintIn {           // the index's fingerprint: a sum over the sorted r
     }
 };
 
+// ---- the strand-merged compacted de Bruijn graph (grlbwt_cdebruijn_*).  Node v is the v-th selected class of
+// grlbwt_fm_kmers_canonical: its representative's rows [lo, lo + count), its mate's head (kCkNone, kCkNoComp as there) and
+// its total.  End 2 v is in front of the representative's first cell, end 2 v + 1 behind its last; a palindrome has end 0 only.
+//   The edge search is 4n's, run from every head -- representative or mate -- whose class is selected: a symbol a in front of
+//   head s gives the window w = a.s, whose first k cells are headed by p = prev(lo(w)).  w leaves p's node through end 1 when p
+//   is the representative and 0 when it is the mate (or a palindrome), and enters s's node through end 0 when s is the
+//   representative and 1 when it is the mate.  Each such w is one FORWARD record (source end, other end, lo(w), occ(w)); record
+//   nf + r is the REVERSE of forward record r (other end, source end, weight only), void when the two ends are one (a hairpin).
+//   Two stable sorts of the record numbers, by other end and then by source end, put the records of one (source, other) side
+//   by side: w's forward record and the reverse record of rc(w), never more than two and never two forward ones.
+//   Loops: at most sigma symbols per head and pass; the merge looks at two neighbours; a lower bound halves at most 64 times.
+//   Bounds: a head's records are stored only below roff[i + 1]; an entry only below the number of group heads; end ids are
+//   below 2 n_nodes, the sentinel 2 n_nodes is the key of the void records alone.  Nothing waits for another thread.
+struct CdbHeadOf {           // head p -> its node, whether p is the class's mate, whether it is a palindrome
+    const u64 *H; CkRank rk; const idx_t *mate; const u64 *sel; const idx_t *selrank;
+    GRL_DEV bool operator()(u64 p, u64 &node, u32 &is_mate, u32 &pal) const {
+        if (!lcp_bit(H, p)) return false;
+        const idx_t m = mate[rk(p)];
+        const u64 r = (m < kCkNoComp && (u64)m < p) ? (u64)m : p;
+        if (!lcp_bit(sel, r)) return false;
+        node = rank1(sel, selrank, r); is_mate = r != p ? 1u : 0u; pal = (m < kCkNoComp && (u64)m == p) ? 1u : 0u;
+        return true;
+    }
+};
+struct CdbHeadPred {         // the heads whose class is selected
+    CdbHeadOf h;
+    GRL_DEV bool operator()(u64 p) const { u64 v; u32 a, b; return h(p, v, a, b); }
+};
+struct CdbNodeFn {           // prim::for_each_set_bit over the selection: node e is the class of representative p
+    CkTotalFn tot; idx_t *lo, *count, *mate, *total;
+    GRL_DEV void operator()(u64 p, u64 e) const { lo[e] = (idx_t)p; count[e] = (idx_t)tot.cnt(p); mate[e] = tot.mate[tot.rk(p)]; total[e] = (idx_t)tot(p); }
+};
+struct CdbHeadListFn {       // prim::for_each_set_bit over the selected heads: rows, and the end the head's k-mer is entered through
+    CdbHeadOf h; KmerCountFn cnt; idx_t *hlo, *hcount, *hend;
+    GRL_DEV void operator()(u64 p, u64 i) const {
+        u64 v = 0; u32 m = 0, pal = 0;
+        (void)h(p, v, m, pal);
+        hlo[i] = (idx_t)p; hcount[i] = (idx_t)cnt(p); hend[i] = (idx_t)(2 * v + m);
+    }
+};
+struct CdbEdgeFn {           // DbEdgeFn::run with a sink that writes records; roff null: the counting pass
+    typedef FmKey Key;
+    DbEdgeFn e;              // (key, slf, R, sep, prev and next_sym; the rest of it is not used)
+    CdbHeadOf head;
+    const idx_t *hlo, *hcount, *hend;
+    idx_t *found_of, *nsteps;
+    const idx_t *roff; idx_t *rsrc, *roth, *rlo, *rocc; u32 *bad;
+    GRL_HD const FmKey *keys() const { return e.key; }
+    GRL_HD u64 n_keys() const { return e.R; }
+    template <class TOP>
+    GRL_DEV void operator()(u64 i, const TOP &top) const {
+        const u64 lo = (u64)hlo[i], hi = lo + (u64)hcount[i];
+        const u64 base = roff ? (u64)roff[i] : 0, room = roff ? (u64)roff[i + 1] - base : 0;
+        u64 a = lo, b = hi, rem = hi - lo, found = 0, steps = 1;
+        fm_step(e.key, e.slf, e.R, top, e.sep, a, b);         // the rows whose window starts its string
+        rem -= b > a ? (b - a < rem ? b - a : rem) : 0;
+        u32 c = e.sep;
+        while (rem && e.next_sym(c, top, c)) {                // (c goes up: at most sigma rounds)
+            a = lo; b = hi;
+            fm_step(e.key, e.slf, e.R, top, c, a, b);
+            steps++;
+            if (a >= b) continue;
+            rem -= b - a < rem ? b - a : rem;
+            const u64 p = e.prev(a);
+            u64 u = 0; u32 um = 0, upal = 0;
+            if (p == ~0ull || !head(p, u, um, upal)) continue;
+            if (roff && found < room) {
+                const u64 j = base + found;
+                rsrc[j] = (idx_t)(2 * u + ((um | upal) ? 0u : 1u)); roth[j] = hend[i]; rlo[j] = (idx_t)a; rocc[j] = (idx_t)(b - a);
+            }
+            found++;
+        }
+        if (roff) { if (found != room) prim::atomic_max(bad, 1u); }
+        else { found_of[i] = (idx_t)found; nsteps[i] = (idx_t)steps; }
+    }
+    GRL_DEV void operator()(u64 i) const { (*this)(i, FmNoTop{}); }
+};
+struct CdbRec {              // record r of 2 nf; `none` = 2 n_nodes keys the void records
+    const idx_t *src, *oth; u64 nf, none;
+    GRL_DEV u64 source(u64 r) const { if (r < nf) return (u64)src[r]; r -= nf; return src[r] == oth[r] ? none : (u64)oth[r]; }
+    GRL_DEV u64 other(u64 r) const { if (r < nf) return (u64)oth[r]; r -= nf; return src[r] == oth[r] ? none : (u64)src[r]; }
+};
+struct CdbKeyFn {            // the sort keys: pass 0 the other end of record i, pass 1 the source end of the record at place i
+    CdbRec rec; const idx_t *perm; idx_t *key, *val;
+    GRL_DEV void operator()(u64 i) const {
+        if (perm) key[i] = (idx_t)rec.source((u64)perm[i]);
+        else { key[i] = (idx_t)rec.other(i); val[i] = (idx_t)i; }
+    }
+};
+struct CdbGroupHeadIn {      // 1 at the first record of every (source, other) in sorted order; the void records are none
+    CdbRec rec; const idx_t *perm;
+    GRL_DEV u64 operator()(u64 i) const {
+        const u64 r = (u64)perm[i], s = rec.source(r);
+        if (s == rec.none) return 0ull;
+        if (i == 0) return 1ull;
+        const u64 q = (u64)perm[i - 1];
+        return rec.source(q) != s || rec.other(q) != rec.other(r) ? 1ull : 0ull;
+    }
+};
+struct CdbHairpinIn {
+    const idx_t *src, *oth;
+    GRL_DEV u64 operator()(u64 r) const { return src[r] == oth[r] ? 1ull : 0ull; }
+};
+// the merge of one group, shared by the generic form and the tile kernel: entry j from the records at places i, i + 1
+struct CdbMerge {
+    CdbRec rec; const idx_t *perm, *rlo, *rocc; u64 nrec;
+    idx_t *esrc, *eoth, *ew, *erow, *ecnt; u32 *bad;
+    GRL_DEV void operator()(u64 i, u64 j) const {
+        const u64 r = (u64)perm[i], s = rec.source(r), o = rec.other(r);
+        u64 w = (u64)rocc[r < rec.nf ? r : r - rec.nf], row = (u64)kDbNone, cnt = 0;
+        u32 fwd = 0;
+        if (r < rec.nf) { row = (u64)rlo[r]; cnt = (u64)rocc[r]; fwd = 1; }
+        if (i + 1 < nrec) {
+            const u64 r2 = (u64)perm[i + 1];
+            if (rec.source(r2) == s && rec.other(r2) == o) {
+                w += (u64)rocc[r2 < rec.nf ? r2 : r2 - rec.nf];
+                if (r2 < rec.nf) { row = (u64)rlo[r2]; cnt = (u64)rocc[r2]; fwd++; }
+                if (i + 2 < nrec) { const u64 r3 = (u64)perm[i + 2]; if (rec.source(r3) == s && rec.other(r3) == o) prim::atomic_max(bad, 1u); }
+            }
+        }
+        if (fwd > 1) prim::atomic_max(bad, 1u);
+        esrc[j] = (idx_t)s; eoth[j] = (idx_t)o; ew[j] = (idx_t)w; erow[j] = (idx_t)row; ecnt[j] = (idx_t)cnt;
+    }
+};
+struct CdbMergeEachFn {      // the generic form of the merge: for_each over the sorted records
+    CdbGroupHeadIn head; const idx_t *eidx; CdbMerge merge;
+    GRL_DEV void operator()(u64 i) const { if (head(i)) merge(i, (u64)eidx[i]); }
+};
+struct CdbEndOffFn {         // end_offsets[a] = the entries whose source end is below a: a lower bound in the entries' sources
+    const idx_t *esrc; u64 nhe; idx_t *endoff;
+    GRL_DEV void operator()(u64 a) const {
+        u64 x = 0, y = nhe;
+        for (int it = 0; it < 64 && x < y; it++) { const u64 mid = (x + y) >> 1; if ((u64)esrc[mid] < a) x = mid + 1; else y = mid; }
+        endoff[a] = (idx_t)x;
+    }
+};
+struct CdbEndDegIn {
+    const idx_t *endoff;
+    GRL_DEV u64 operator()(u64 a) const { return (u64)endoff[a + 1] - (u64)endoff[a]; }
+};
+struct CdbSelfIn {           // the entries whose other end is their source end: the hairpins
+    const idx_t *esrc, *eoth;
+    GRL_DEV u64 operator()(u64 j) const { return esrc[j] == eoth[j] ? 1ull : 0ull; }
+};
+struct CdbNodeKindIn {       // what 0: rigid nodes; 1: palindromes; 2: nodes whose reverse complement does not occur
+    const idx_t *nlo, *nmate; int what;
+    GRL_DEV u64 operator()(u64 v) const {
+        const idx_t m = nmate[v];
+        if (what == 2) return m == kCkNone ? 1ull : 0ull;
+        const bool pal = m == nlo[v];
+        return (what == 1 ? pal : (pal || m == kCkNoComp)) ? 1ull : 0ull;
+    }
+};
+// The unitigs, on the doubled graph of the 2 n_nodes oriented nodes x = 2 v + o (o = 1: v read as the reverse complement of its
+// representative).  Reading (v, o) leaves v through end 1 - o, which is end id x ^ 1, and was entered through end o, id x.  An
+// end's partner is the other end of its only half-edge when that half-edge is compactable -- both ends of degree 1, two
+// different ends, neither node rigid, and the partner's half-edge leads back (it does on the BWT of a collection; the test keeps
+// succ and link inverse to each other on any image).  succ(x) = partner(x ^ 1), link(x) = partner(x) ^ 1.  x -> x ^ 1 maps a
+// chain onto its reverse; a chain that held both x and x ^ 1 would be mapped onto itself, with a fixed node (impossible) or a
+// fixed link, partner(a) = a, which is excluded: every unitig appears as two disjoint chains, and 4n's rounds run as they are.
+struct CdbEnds {
+    const idx_t *endoff, *eoth, *nlo, *nmate;
+    GRL_DEV bool rigid(u64 v) const { const idx_t m = nmate[v]; return m == kCkNoComp || m == nlo[v]; }
+    GRL_DEV u64 deg(u64 a) const { return (u64)endoff[a + 1] - (u64)endoff[a]; }
+    GRL_DEV u64 partner(u64 a) const {
+        if (deg(a) != 1) return ~0ull;
+        const u64 b = (u64)eoth[(u64)endoff[a]];
+        if (b == a || deg(b) != 1 || (u64)eoth[(u64)endoff[b]] != a || rigid(a >> 1) || rigid(b >> 1)) return ~0ull;
+        return b;
+    }
+};
+struct CdbLinkFn {
+    CdbEnds E; idx_t *link, *succ;
+    GRL_DEV void operator()(u64 x) const {
+        const u64 b = E.partner(x), s = E.partner(x ^ 1);
+        link[x] = b == ~0ull ? kDbNone : (idx_t)(b ^ 1);
+        succ[x] = s == ~0ull ? kDbNone : (idx_t)s;
+    }
+};
+// Which of a unitig's two chains is reported, decided at the chain's tail, which knows its head after the rounds: a path keeps
+// the chain whose head node has the smaller id of the two end nodes (the other chain's head is this tail reversed), a single
+// node its + reading, a cycle the chain whose head -- its smallest oriented id -- is even.  One tail per chain: one writer.
+struct CdbKeepFn {
+    const u8 *mark; const idx_t *ptr, *succ; u8 *keep;
+    GRL_DEV void operator()(u64 x) const {
+        const idx_t s = succ[x];
+        if (s != kDbNone && !mark[(u64)s]) return;
+        const u64 h = (u64)ptr[x];
+        keep[h] = (mark[h] == 2 ? !(h & 1) : ((h >> 1) < (x >> 1) || (h == x && !(x & 1)))) ? 1 : 0;
+    }
+};
+struct CdbKeptIn {           // 1 at the head of a reported chain (what 2: of a circular one)
+    const u8 *mark, *keep; u8 what;
+    GRL_DEV u64 operator()(u64 x) const { return (what ? mark[x] == what : mark[x] != 0) && keep[x] ? 1ull : 0ull; }
+};
+struct CdbPlaceFn {
+    const u8 *mark, *keep; const idx_t *ptr, *dist, *hrank, *succ; idx_t *unitig, *rank, *ulen; u8 *orient, *ucirc;
+    GRL_DEV void operator()(u64 x) const {
+        const u64 h = (u64)ptr[x];
+        if (!keep[h]) return;
+        const u64 j = (u64)hrank[h], v = x >> 1;
+        unitig[v] = (idx_t)j; rank[v] = dist[x]; orient[v] = (u8)(x & 1);
+        const idx_t s = succ[x];
+        if (s == kDbNone || mark[(u64)s]) ulen[j] = (idx_t)(dist[x] + 1);
+        if (mark[x]) ucirc[j] = mark[x] == 2 ? 1 : 0;
+    }
+};
+struct CdbOrderFn {          // the oriented nodes in unitig order
+    const idx_t *unitig, *rank, *uoff; const u8 *orient; idx_t *nodes;
+    GRL_DEV void operator()(u64 v) const { nodes[(u64)uoff[(u64)unitig[v]] + (u64)rank[v]] = (idx_t)(2 * v + orient[v]); }
+};
+struct CdbTotalOfIn {
+    const idx_t *nodes, *total;
+    GRL_DEV u64 operator()(u64 i) const { return (u64)total[(u64)nodes[i] >> 1]; }
+};
+struct CdbCopyRowFn {        // fwd_row: the handle's "none" in the interface's width
+    const idx_t *src; u64 *dst;
+    GRL_DEV void operator()(u64 i) const { dst[i] = src[i] == kDbNone ? ~0ull : (u64)src[i]; }
+};
+struct CdbDegreeFn {
+    const idx_t *endoff; u32 *d0, *d1;
+    GRL_DEV void operator()(u64 v) const {
+        if (d0) d0[v] = (u32)((u64)endoff[2 * v + 1] - (u64)endoff[2 * v]);
+        if (d1) d1[v] = (u32)((u64)endoff[2 * v + 2] - (u64)endoff[2 * v + 1]);
+    }
+};
+// The cells.  Place r < m of a unitig holds the first cell of its r-th oriented node (v, o): o = 0, the symbol of the sorted run
+// that holds lo; o = 1 with a mate, the same at mate_lo; o = 1 without one, the complement of the representative's LAST cell, k
+// forward steps from lo (a "walk").  The k - 1 cells behind come from the last oriented node: forward steps from lo or mate_lo,
+// or, without a mate, the complements of the representative's first k - 1 cells in reverse.  The complement is taken on symbol
+// codes through the handle's table (code -> the complement's VALUE, which the image need not hold).
+//   Bounds: KmerStepFn's (rows stay below n); a cell index is below n_nodes + n_unitigs (k - 1).
+struct CdbStepFn {
+    KmerStepFn s; const u32 *ccode; const u64 *cval; u32 nt;
+    GRL_DEV u32 code(u64 &q) const {
+        const u64 j = run_of_row(s.frc, q);
+        const FmKey kj = s.key[j];
+        q = kj.start() + (q - (u64)s.slf[j]);
+        return kj.sym();
+    }
+    GRL_DEV u64 val(u32 c) const { return s.alpha ? s.alpha[c] : (u64)c; }
+    GRL_DEV u64 comp(const u32 *cc, u32 c) const {      // cc: the codes, in memory or in LDS
+        u32 a = 0, b = nt;
+        for (int it = 0; it < 9 && a < b; it++) { const u32 mid = (a + b) >> 1; if (cc[mid] < c) a = mid + 1; else b = mid; }
+        return a < nt && cc[a] == c ? cval[a] : 0ull;
+    }
+};
+struct CdbCellSrc {          // where the first cell of oriented node x comes from: a row (walk false) or a walk from a row
+    const idx_t *nlo, *nmate;
+    GRL_DEV u64 operator()(u64 x, bool &walk) const {
+        const u64 v = x >> 1;
+        walk = false;
+        if (!(x & 1)) return (u64)nlo[v];
+        const idx_t m = nmate[v];
+        if (m < kCkNoComp) return (u64)m;
+        walk = true;
+        return (u64)nlo[v];
+    }
+};
+template <class cell_t>
+struct CdbFirstCellFn {      // the generic form, for_each over the nodes in unitig order; the walks inline
+    CdbStepFn st; CdbCellSrc src; const idx_t *nodes, *unitig; u64 k; cell_t *cells;
+    GRL_DEV void operator()(u64 i) const {
+        const u64 x = (u64)nodes[i];
+        bool walk;
+        u64 q = src(x, walk);
+        u32 c = st.code(q);
+        if (walk) for (u64 t = 1; t < k; t++) c = st.code(q);
+        cells[i + (u64)unitig[x >> 1] * (k - 1)] = (cell_t)(walk ? st.comp(st.ccode, c) : st.val(c));
+    }
+};
+struct CdbWalkPred {         // the places in unitig order that take a walk
+    CdbCellSrc src; const idx_t *nodes;
+    GRL_DEV bool operator()(u64 i) const { bool walk; (void)src((u64)nodes[i], walk); return walk; }
+};
+struct CdbWalkIn {
+    CdbWalkPred p;
+    GRL_DEV u64 operator()(u64 i) const { return p(i) ? 1ull : 0ull; }
+};
+struct CdbCopyMateFn {       // mate_lo as grlbwt_fm_kmers_canonical writes it
+    const idx_t *src; u64 *dst;
+    GRL_DEV void operator()(u64 v) const { dst[v] = src[v] >= kCkNoComp ? ~0ull : (u64)src[v]; }
+};
+struct CdbWalkListFn {
+    idx_t *list;
+    GRL_DEV void operator()(u64 i, u64 t) const { list[t] = (idx_t)i; }
+};
+template <class cell_t>
+struct CdbWalkFn {           // prim::walk_tickets: ticket t is the t-th place that takes a walk
+    struct State { u64 q, left; u32 c; };
+    CdbStepFn st; const idx_t *list, *nodes, *nlo, *unitig; u64 k; cell_t *cells;
+    GRL_DEV bool begin(u64 t, State &s) const { s.q = (u64)nlo[(u64)nodes[(u64)list[t]] >> 1]; s.left = k; s.c = 0; return k > 0; }
+    GRL_DEV bool step(State &s) const { s.c = st.code(s.q); return --s.left == 0; }
+    GRL_DEV void end(u64 t, const State &s) const {
+        const u64 i = (u64)list[t];
+        cells[i + (u64)unitig[(u64)nodes[i] >> 1] * (k - 1)] = (cell_t)st.comp(st.ccode, s.c);
+    }
+};
+template <class cell_t>
+struct CdbTailCellsFn {      // for_each over the unitigs: k - 1 dependent steps each
+    CdbStepFn st; CdbCellSrc src; const idx_t *nodes, *uoff; u64 k; cell_t *cells;
+    GRL_DEV void operator()(u64 j) const {
+        const u64 e = (u64)uoff[j + 1];
+        bool walk;
+        u64 q = src((u64)nodes[e - 1], walk);
+        cell_t *out = cells + e + j * (k - 1);
+        if (!walk) {
+            (void)st.code(q);
+            for (u64 t = 0; t + 1 < k; t++) out[t] = (cell_t)st.val(st.code(q));
+        } else {
+            for (u64 t = 0; t + 1 < k; t++) out[k - 2 - t] = (cell_t)st.comp(st.ccode, st.code(q));
+        }
+    }
+};
+
 // ---- the right-maximal and maximal repeats (grlbwt_fm_repeats).  V[p] = min(LCP[p], cap) in the narrowest width
 // that holds cap.  Row p with V[p] = v >= 1 is the split row of a right-maximal repeat of v cells exactly when the nearest q < p
 // with V[q] <= v has V[q] < v; the repeat's rows are then [q, e), e the nearest row behind p with V[e] < v, or n.  Both are
@@ -3073,6 +3388,94 @@ struct Image {
         });
         prim::sync();
     }
+    // what grlbwt_fm_kmers_canonical and grlbwt_cdebruijn_create share, as KmerSel is shared below them: the checks of the complement
+    // map, its table of (code, comp code), the passes, the head ranks, the mate pass with its counters and the representatives'
+    // bits (in L.Sold).  The caller keeps the order of events: pairs(), its own refusals for memory, table(), heads(), mates().
+    struct CkSel {
+        KmerSel K;
+        std::vector<u64> vals;        // the pairs' values, 2 * n_pairs
+        std::vector<u32> codes;       // and their symbol codes (kCkAbsent: not in the image)
+        u64 n_pairs = 0;
+        DBuf<CkPair> dtab;
+        DBuf<idx_t> hrank, mate;
+        u32 nt = 0;
+        bool rest = false;
+        u64 n_distinct = 0, backward_steps = 0, forward_steps = 0, mate_walks = 0;
+        u64 fixed_bytes() const { return kCkMaxTable * sizeof(CkPair) + 2 * n_pairs * 12 + (kCkStripes * 4 + 2) * 8; }
+        // every value in at most one pair, the separator in none
+        void pairs(const char *kWho, const FmIndex &F, const u64 *host_pairs, u64 np) {
+            if (np > 128) throw prim::Error(-22, std::string(kWho) + "n_pairs is " + std::to_string(np) + ", more than 128");
+            if (!host_pairs && np) throw prim::Error(-22, std::string(kWho) + "host_pairs is NULL with n_pairs = " + std::to_string(np));
+            static const u64 kDna[4] = {'A', 'T', 'C', 'G'};
+            if (!host_pairs) { host_pairs = kDna; np = 2; }
+            n_pairs = np;
+            vals.assign(host_pairs, host_pairs + 2 * np);
+            std::vector<u64> seen;
+            for (u64 i = 0; i < np; i++) {
+                seen.push_back(vals[2 * i]);
+                if (vals[2 * i + 1] != vals[2 * i]) seen.push_back(vals[2 * i + 1]);
+            }
+            std::sort(seen.begin(), seen.end());
+            for (size_t i = 1; i < seen.size(); i++)
+                if (seen[i] == seen[i - 1]) throw prim::Error(-22, std::string(kWho) + "the value " + std::to_string(seen[i]) + " is listed twice in the pairs");
+            if (F.R && std::binary_search(seen.begin(), seen.end(), F.sepval))
+                throw prim::Error(-22, std::string(kWho) + "the separator's value " + std::to_string(F.sepval) + " is in a pair");
+        }
+        // the table of (code, comp code), in ascending code: the values go to codes on the device
+        void table(const FmIndex &F) {
+            dtab.alloc(kCkMaxTable);
+            nt = 0;
+            if (n_pairs) {
+                DBuf<u64> dv(2 * n_pairs);
+                DBuf<u32> dc(2 * n_pairs);
+                prim::h2d(dv.p, vals.data(), 2 * n_pairs * 8);
+                prim::for_each(2 * n_pairs, CkCodeFn{fm_count_fn(F, nullptr, 8, nullptr, nullptr, nullptr), dv.p, dc.p}, "ckmer.codes");
+                codes = dc.to_host(2 * n_pairs);
+                std::vector<CkPair> tab;
+                for (u64 i = 0; i < n_pairs; i++) {
+                    const u32 a = codes[2 * i], b = codes[2 * i + 1];
+                    if (a != kCkAbsent) tab.push_back(CkPair{a, b});
+                    if (b != kCkAbsent && vals[2 * i] != vals[2 * i + 1]) tab.push_back(CkPair{b, a});
+                }
+                std::sort(tab.begin(), tab.end(), [](const CkPair &x, const CkPair &y) { return x.code < y.code; });
+                nt = (u32)tab.size();
+                if (nt) prim::h2d(dtab.p, tab.data(), nt * sizeof(CkPair));
+            }
+            rest = (u64)nt + 1 < F.sigma;                        // a symbol besides the separator has no pair
+        }
+        void heads(const FmIndex &F, u64 k, KmerInfo &ki) {
+            K.heads(F, k, ki);
+            const u64 nw = FmLcp::words_of(F.n);
+            hrank.alloc(nw + 1);
+            n_distinct = (u64)prim::exclusive_scan<idx_t>(nw, PopcIn{K.H}, hrank.p, true, "ckmer.head_ranks");
+        }
+        void mates(const char *kWho, const FmIndex &F, u64 k) {
+            const u64 n = F.n;
+            if (n_distinct * sizeof(idx_t) > prim::mem_available())
+                throw prim::Error(-12, std::string(kWho) + "the mates need " + std::to_string(n_distinct * sizeof(idx_t)) + " bytes of device memory, more than is free");
+            mate.alloc(n_distinct);
+            mate.fill_ff();
+            if (!n_distinct) return;
+            DBuf<u64> ctr(kCkStripes * 4 + 2);
+            ctr.zero();
+            const KmerMateFn f{K.L.frc.p, F.key.p, F.slf.p, F.R, n, k < n ? k : n, K.H, K.cnt(), dtab.p, nt, rest, mate.p, ctr.p};
+#ifdef GRLBWT_PRIM_HIP
+            if (prim::sw().dev_kmer_mates != 'f') (void)prim::kmer_mates<idx_t>(n_distinct, f, K.H, hrank.p, n, ctr.p + kCkStripes * 4, F.top_entries);
+            else
+#endif
+                prim::for_each_set_bit<idx_t>(n, K.H, hrank.p, KmerMateEachFn{f}, "ckmer.mates_plain");
+            const std::vector<u64> hc = ctr.to_host(kCkStripes * 4);
+            u64 idle = 0;
+            for (u64 s = 0; s < kCkStripes; s++) { backward_steps += hc[4 * s]; forward_steps += hc[4 * s + 1]; idle += hc[4 * s + 2]; }
+            mate_walks = n_distinct - idle;
+        }
+        const u64 *representatives() {
+            u64 *rep = K.L.Sold;
+            prim::dev_memset(rep, 0, FmLcp::words_of(K.n) * 8);
+            prim::bitvector_from_pred(K.n, CkRepPred{CkRank{K.H, hrank.p}, mate.p}, rep, "ckmer.representatives");
+            return rep;
+        }
+    };
     // ---- the strand-merged k-mers (functor block "the strand-merged k-mers").  fm_kmers' order of events: the
     // arguments and the complement map, the memory, the passes, the mates (whose array is sized by the head count), the capacity;
     // then the spectrum is copied to the host and the table is written.  Nothing is stored into an output before the last refusal.
@@ -3102,24 +3505,8 @@ struct Image {
         }
         if ((cells && ((uintptr_t)cells & (uintptr_t)(w - 1))) || ((uintptr_t)lo & 7) || ((uintptr_t)count & 7) || ((uintptr_t)mate_lo & 7) || ((uintptr_t)total & 7))
             throw prim::Error(-22, std::string(kWho) + "an output is not aligned to its width");
-        // ---- the complement map: every value in at most one pair, the separator in none
-        if (n_pairs > 128) throw prim::Error(-22, std::string(kWho) + "n_pairs is " + std::to_string(n_pairs) + ", more than 128");
-        if (!host_pairs && n_pairs) throw prim::Error(-22, std::string(kWho) + "host_pairs is NULL with n_pairs = " + std::to_string(n_pairs));
-        static const u64 kDna[4] = {'A', 'T', 'C', 'G'};
-        if (!host_pairs) { host_pairs = kDna; n_pairs = 2; }
-        std::vector<u64> vals(host_pairs, host_pairs + 2 * n_pairs);
-        {
-            std::vector<u64> seen;
-            for (u64 i = 0; i < n_pairs; i++) {
-                seen.push_back(vals[2 * i]);
-                if (vals[2 * i + 1] != vals[2 * i]) seen.push_back(vals[2 * i + 1]);
-            }
-            std::sort(seen.begin(), seen.end());
-            for (size_t i = 1; i < seen.size(); i++)
-                if (seen[i] == seen[i - 1]) throw prim::Error(-22, std::string(kWho) + "the value " + std::to_string(seen[i]) + " is listed twice in the pairs");
-            if (F.R && std::binary_search(seen.begin(), seen.end(), F.sepval))
-                throw prim::Error(-22, std::string(kWho) + "the separator's value " + std::to_string(F.sepval) + " is in a pair");
-        }
+        CkSel S;
+        S.pairs(kWho, F, host_pairs, n_pairs);
         const bool table = cells || lo || count || mate_lo || total;
         const u64 nb = host_spectrum ? bins : 1;
         CkmerInfo ci;
@@ -3127,65 +3514,27 @@ struct Image {
         std::vector<u64> spec(nb, 0);
         if (n == 0) { F.cinfo = ci; if (host_spectrum) std::memcpy(host_spectrum, spec.data(), nb * 8); return; }
         const u64 nw = FmLcp::words_of(n);
-        const u64 fixed = kCkMaxTable * sizeof(CkPair) + 2 * n_pairs * 12 + (kCkStripes * 4 + 2) * 8;
+        const u64 fixed = S.fixed_bytes();
         ci.scratch_bytes = KmerSel::scratch_bytes(n) + nb * 8 + (nw + 1) * sizeof(idx_t) + fixed;
         if (n >= ((u64)1 << 62) || ci.scratch_bytes > prim::mem_available())
             throw prim::Error(-12, std::string(kWho) + "the passes need " + std::to_string(ci.scratch_bytes) + " bytes of device memory, more than is free");
-        // ---- the table of (code, comp code), in ascending code: the values go to codes on the device
-        DBuf<CkPair> dtab(kCkMaxTable);
-        u32 nt = 0;
-        if (n_pairs) {
-            DBuf<u64> dv(2 * n_pairs);
-            DBuf<u32> dc(2 * n_pairs);
-            prim::h2d(dv.p, vals.data(), 2 * n_pairs * 8);
-            prim::for_each(2 * n_pairs, CkCodeFn{fm_count_fn(F, nullptr, 8, nullptr, nullptr, nullptr), dv.p, dc.p}, "ckmer.codes");
-            const std::vector<u32> codes = dc.to_host(2 * n_pairs);
-            std::vector<CkPair> tab;
-            for (u64 i = 0; i < n_pairs; i++) {
-                const u32 a = codes[2 * i], b = codes[2 * i + 1];
-                if (a != kCkAbsent) tab.push_back(CkPair{a, b});
-                if (b != kCkAbsent && vals[2 * i] != vals[2 * i + 1]) tab.push_back(CkPair{b, a});
-            }
-            std::sort(tab.begin(), tab.end(), [](const CkPair &x, const CkPair &y) { return x.code < y.code; });
-            nt = (u32)tab.size();
-            if (nt) prim::h2d(dtab.p, tab.data(), nt * sizeof(CkPair));
-        }
-        const bool rest = (u64)nt + 1 < F.sigma;                 // a symbol besides the separator has no pair
-        KmerSel K;
+        S.table(F);
+        KmerSel &K = S.K;
         KmerInfo ki;
-        K.heads(F, k, ki);
+        S.heads(F, k, ki);
         ci.passes = ki.passes; ci.length_passes = ki.length_passes;
         FmLcp &L = K.L;
         const u64 *H = K.H;
-        u64 *rep = L.Sold;
         const KmerCountFn cnt = K.cnt();
-        DBuf<idx_t> hrank(nw + 1);
-        ci.n_distinct = (u64)prim::exclusive_scan<idx_t>(nw, PopcIn{H}, hrank.p, true, "ckmer.head_ranks");
+        ci.n_distinct = S.n_distinct;
         ci.scratch_bytes += ci.n_distinct * sizeof(idx_t);
-        if (ci.n_distinct * sizeof(idx_t) > prim::mem_available())
-            throw prim::Error(-12, std::string(kWho) + "the mates need " + std::to_string(ci.n_distinct * sizeof(idx_t)) + " bytes of device memory, more than is free");
-        DBuf<idx_t> mate(ci.n_distinct);
-        mate.fill_ff();
-        // ---- the mate pass
-        if (ci.n_distinct) {
-            DBuf<u64> ctr(kCkStripes * 4 + 2);
-            ctr.zero();
-            const KmerMateFn f{L.frc.p, F.key.p, F.slf.p, F.R, n, k < n ? k : n, H, cnt, dtab.p, nt, rest, mate.p, ctr.p};
-#ifdef GRLBWT_PRIM_HIP
-            if (prim::sw().dev_kmer_mates != 'f') (void)prim::kmer_mates<idx_t>(ci.n_distinct, f, H, hrank.p, n, ctr.p + kCkStripes * 4, F.top_entries);
-            else
-#endif
-                prim::for_each_set_bit<idx_t>(n, H, hrank.p, KmerMateEachFn{f}, "ckmer.mates_plain");
-            const std::vector<u64> hc = ctr.to_host(kCkStripes * 4);
-            u64 idle = 0;
-            for (u64 s = 0; s < kCkStripes; s++) { ci.backward_steps += hc[4 * s]; ci.forward_steps += hc[4 * s + 1]; idle += hc[4 * s + 2]; }
-            ci.mate_walks = ci.n_distinct - idle;
-        }
+        S.mates(kWho, F, k);
+        ci.backward_steps = S.backward_steps; ci.forward_steps = S.forward_steps; ci.mate_walks = S.mate_walks;
+        const DBuf<idx_t> &hrank = S.hrank, &mate = S.mate;
         // ---- representatives, totals, the spectrum, the classes
         const CkRank rk{H, hrank.p};
         const CkTotalFn tot{cnt, rk, mate.p};
-        prim::dev_memset(rep, 0, nw * 8);
-        prim::bitvector_from_pred(n, CkRepPred{rk, mate.p}, rep, "ckmer.representatives");
+        const u64 *rep = S.representatives();
         DBuf<u64> dbins(nb);
 #ifdef GRLBWT_PRIM_HIP
         prim::kmer_spectrum(n, rep, tot, (u32)nb, dbins.p, ci.n_classes, ci.n_windows, ci.largest_total);
@@ -3646,6 +3995,337 @@ struct Image {
                         prim::for_each(nn, DbFirstCellFn<cell_t>{step, order.p, D.unitig.p, D.lo.p, k, (cell_t *)cells}, "debruijn.first_cells_plain");
                     if (k > 1) prim::for_each(nu, DbTailCellsFn<cell_t>{step, order.p, D.uoff.p, D.lo.p, k, (cell_t *)cells}, "debruijn.tail_cells");
                 });
+            }
+        }
+        prim::sync();
+    }
+    // ---- the strand-merged compacted de Bruijn graph (functor block of that name).  cdebruijn_create does all the
+    // work and keeps no pointer into the index; the three writers copy, and the cells are decoded from the index again behind
+    // the fingerprint check.  Order of events: the arguments and the complement map; the memory of the passes; the passes and the
+    // mate pass (CkSel, shared with fm_ckmers, whose info record this call leaves alone); the selection by total; the memory of
+    // the nodes and heads; the edge search from every selected head, count then emit; the memory of the sort; the two sorts and
+    // the merge; the memory of the rounds; the unitigs on the doubled graph.
+    //   Device form: the mate pass and the edge search as in 4o and 4n; prim::cdb_merge (a tile of sorted records per workgroup:
+    //   group heads as ballot words, the tile's entries stored behind one scan) and prim::cdb_first_cells (a tile of consecutive
+    //   cells per workgroup, one search per tile for its unitigs) with the walks of the - nodes without a mate as tickets
+    //   (prim::walk_tickets).  Generic forms, the stand-in's and with GRLBWT_DEV_CDEBRUIJN=f the device's: for_each over the
+    //   sorted records behind a scan of the flags; for_each over the nodes with the walks inline.
+    //   Loops: those of fm_ckmers and debruijn_create; the jumping runs on 2 n_nodes oriented nodes, at most
+    //   2 (ceil(log2(2 n_nodes)) + 1) rounds.  Nothing waits for another thread; the only atomics are the flags' and the tickets'.
+#ifdef GRLBWT_PRIM_HIP
+    static constexpr u64 kCdbTileNodes = prim::kDbTileNodes, kCdbTileCells = prim::kCdbTileCells;
+#else
+    static constexpr u64 kCdbTileNodes = 1024, kCdbTileCells = 4096;    // (the serial form has no tiles: the figures the device library reports)
+#endif
+    struct CDeBruijnInfo {
+        u64 k = 0, n = 0, n_strings = 0, n_distinct = 0, n_nodes = 0, n_rigid = 0, n_palindromes = 0, n_edges = 0, n_half_edges = 0, n_hairpins = 0;
+        u64 n_unitigs = 0, n_circular = 0, longest = 0, n_cells = 0, max_end_degree = 0, passes = 0, length_passes = 0;
+        u64 mate_backward_steps = 0, edge_backward_steps = 0, forward_steps = 0, jump_rounds = 0, scratch_bytes = 0;
+    };
+    struct ImageCDeBruijn {
+        CDeBruijnInfo i;
+        mutable u64 cells_forward_steps = 0;      // of the last unitigs call that wrote cells
+        u64 R = 0, sigma = 0, print = 0;          // of the index it was made from
+        u64 n_walk = 0, comp_top = 0;             // - nodes without a mate; the largest complement value of the table
+        u32 nt = 0;
+        DBuf<idx_t> lo, count, mate, total, unitig, rank, endoff, eoth, ew, erow, ecnt, uoff, uweight;
+        DBuf<u8> orient, ucirc;
+        DBuf<u32> ccode;
+        DBuf<u64> cval;
+        u64 held_bytes() const {
+            return (lo.n + count.n + mate.n + total.n + unitig.n + rank.n + endoff.n + eoth.n + ew.n + erow.n + ecnt.n + uoff.n + uweight.n) * sizeof(idx_t) +
+                   orient.n + ucirc.n + ccode.n * 4 + cval.n * 8;
+        }
+    };
+    static void cdb_need(u64 bytes, const char *what) {
+        if (bytes > prim::mem_available())
+            throw prim::Error(-12, std::string("canonical de bruijn: ") + what + " need " + std::to_string(bytes) + " bytes of device memory, more than is free");
+    }
+    static void cdebruijn_create(const FmIndex &F, u64 k, u64 min_count, u64 max_count, const u64 *host_pairs, u64 n_pairs, u32 flags, ImageCDeBruijn &D) {
+        static const char *const kWho = "canonical de bruijn: ";
+        if (k == 0) throw prim::Error(-22, std::string(kWho) + "k is 0");
+        if (flags) throw prim::Error(-22, std::string(kWho) + "unknown flag bits " + std::to_string(flags));
+        if (max_count && min_count > max_count)
+            throw prim::Error(-22, std::string(kWho) + "min_count " + std::to_string(min_count) + " is above max_count " + std::to_string(max_count));
+        CkSel S;
+        S.pairs(kWho, F, host_pairs, n_pairs);
+        const u64 n = F.n;
+        CDeBruijnInfo &di = D.i;
+        di = CDeBruijnInfo();
+        di.k = k; di.n = n; di.n_strings = F.k;
+        D.R = F.R; D.sigma = F.sigma;
+        if (n == 0) return;
+        const u64 nw = FmLcp::words_of(n);
+        di.scratch_bytes = KmerSel::scratch_bytes(n) + (nw + 1) * sizeof(idx_t) + S.fixed_bytes();
+        if (n >= ((u64)1 << 62) || di.scratch_bytes > prim::mem_available())
+            throw prim::Error(-12, std::string(kWho) + "the passes need " + std::to_string(di.scratch_bytes) + " bytes of device memory, more than is free");
+        D.print = debruijn_print(F);
+        S.table(F);
+        {   // the handle's own complement table: code -> the complement's value
+            std::vector<std::pair<u32, u64>> t;
+            for (u64 i = 0; i < S.n_pairs; i++) {
+                const u32 a = S.codes[2 * i], b = S.codes[2 * i + 1];
+                if (a != kCkAbsent) t.push_back({a, S.vals[2 * i + 1]});
+                if (b != kCkAbsent && S.vals[2 * i] != S.vals[2 * i + 1]) t.push_back({b, S.vals[2 * i]});
+            }
+            std::sort(t.begin(), t.end());
+            D.nt = (u32)t.size();
+            std::vector<u32> cc(D.nt);
+            std::vector<u64> cv(D.nt);
+            for (u32 i = 0; i < D.nt; i++) { cc[i] = t[i].first; cv[i] = t[i].second; if (cv[i] > D.comp_top) D.comp_top = cv[i]; }
+            D.ccode.alloc(D.nt); D.cval.alloc(D.nt);
+            if (D.nt) { prim::h2d(D.ccode.p, cc.data(), D.nt * 4); prim::h2d(D.cval.p, cv.data(), D.nt * 8); }
+        }
+        KmerSel &K = S.K;
+        KmerInfo ki;
+        S.heads(F, k, ki);
+        di.passes = ki.passes; di.length_passes = ki.length_passes;
+        di.n_distinct = S.n_distinct;
+        di.scratch_bytes += di.n_distinct * sizeof(idx_t);
+        S.mates(kWho, F, k);
+        di.mate_backward_steps = S.backward_steps; di.forward_steps = S.forward_steps;
+        const CkRank rk{K.H, S.hrank.p};
+        const CkTotalFn tot{K.cnt(), rk, S.mate.p};
+        const u64 *rep = S.representatives();
+        const u64 nn = K.select_classes(rep, tot, KmerFilter{0, n, min_count ? min_count : 1, max_count ? max_count : ~0ull});
+        di.n_nodes = nn;
+        if (nn == 0) { prim::sync(); return; }
+        const u64 N2 = 2 * nn;
+        if (N2 + 1 >= (u64)kCkNoComp) throw prim::Error(-75, std::string(kWho) + "more ends than positions of this width can number");
+        // ---- the nodes and the selected heads
+        cdb_need(nn * 4 * sizeof(idx_t) + (nw + nw + 1) * 8, "the nodes");
+        D.lo.alloc(nn); D.count.alloc(nn); D.mate.alloc(nn); D.total.alloc(nn);
+        prim::for_each_set_bit<idx_t>(n, K.sel, K.L.brank.p, CdbNodeFn{tot, D.lo.p, D.count.p, D.mate.p, D.total.p}, "cdebruijn.nodes");
+        di.n_rigid = prim::reduce_sum<u64>(nn, CdbNodeKindIn{D.lo.p, D.mate.p, 0}, "cdebruijn.rigid");
+        di.n_palindromes = prim::reduce_sum<u64>(nn, CdbNodeKindIn{D.lo.p, D.mate.p, 1}, "cdebruijn.palindromes");
+        u64 nf = 0, nhe = 0;
+        DBuf<idx_t> rsrc, roth, rlo, rocc;
+        {
+            const CdbHeadOf head{K.H, rk, S.mate.p, K.sel, K.L.brank.p};
+            DBuf<u64> hsel(nw);
+            DBuf<idx_t> hselrank(nw + 1);
+            hsel.zero();
+            prim::bitvector_from_pred(n, CdbHeadPred{head}, hsel.p, "cdebruijn.heads");
+            const u64 nh = (u64)prim::exclusive_scan<idx_t>(nw, PopcIn{hsel.p}, hselrank.p, true, "cdebruijn.head_ranks");
+            di.scratch_bytes += nw * 8 + (nw + 1) * sizeof(idx_t) + nh * 6 * sizeof(idx_t);
+            cdb_need(nh * 6 * sizeof(idx_t), "the heads");
+            DBuf<idx_t> hlo(nh), hcount(nh), hend(nh), found(nh), nsteps(nh), roff(nh + 1);
+            prim::for_each_set_bit<idx_t>(n, hsel.p, hselrank.p, CdbHeadListFn{head, K.cnt(), hlo.p, hcount.p, hend.p}, "cdebruijn.head_list");
+            DBuf<u32> bad(1);
+            bad.zero();
+            DbEdgeFn e{F.key.p, F.slf.p, F.R, F.sep, DbPrevBit{K.B, K.NZ.p, K.nzbase.p, K.nzlist.p}, nullptr, nullptr, nullptr, nullptr,
+                       nullptr, nullptr, nullptr, nullptr, nullptr};
+            CdbEdgeFn f{e, head, hlo.p, hcount.p, hend.p, found.p, nsteps.p, nullptr, nullptr, nullptr, nullptr, nullptr, bad.p};
+#ifdef GRLBWT_PRIM_HIP
+            prim::top_search(nh, f, F.top_entries, "cdebruijn.count");
+#else
+            prim::for_each(nh, f, "cdebruijn.count");
+#endif
+            nf = (u64)prim::exclusive_scan<idx_t>(nh, IdxIn<idx_t>{found.p}, roff.p, true, "cdebruijn.record_offsets");
+            if (nf > n) throw prim::Error(-22, std::string(kWho) + "more windows of k + 1 cells than rows: not the BWT of a collection");
+            di.scratch_bytes += nf * 4 * sizeof(idx_t);
+            cdb_need(nf * 4 * sizeof(idx_t), "the records");
+            rsrc.alloc(nf); roth.alloc(nf); rlo.alloc(nf); rocc.alloc(nf);
+            f.roff = roff.p; f.rsrc = rsrc.p; f.roth = roth.p; f.rlo = rlo.p; f.rocc = rocc.p;
+#ifdef GRLBWT_PRIM_HIP
+            prim::top_search(nh, f, F.top_entries, "cdebruijn.records");
+#else
+            prim::for_each(nh, f, "cdebruijn.records");
+#endif
+            if (bad.get(0)) throw prim::Error(-71, std::string(kWho) + "a head's second pass found another number of windows than its first");
+            di.edge_backward_steps = 2 * prim::reduce_sum<u64>(nh, IdxIn64{nsteps.p}, "cdebruijn.steps");
+        }
+        // ---- the merge: two stable sorts of the record numbers, group heads, one entry per group
+        D.endoff.alloc(N2 + 1);
+        if (nf) {
+            const u64 nrec = 2 * nf;
+            di.n_hairpins = prim::reduce_sum<u64>(nf, CdbHairpinIn{rsrc.p, roth.p}, "cdebruijn.hairpins");
+            di.scratch_bytes += nrec * 5 * sizeof(idx_t);
+            cdb_need(nrec * 5 * sizeof(idx_t), "the sorts");
+            const CdbRec rec{rsrc.p, roth.p, nf, N2};
+            DBuf<idx_t> ka(nrec), va(nrec), kb(nrec), vb(nrec);
+            const int bits = std::max((int)bitlen64(N2), 1);
+            prim::for_each(nrec, CdbKeyFn{rec, nullptr, ka.p, va.p}, "cdebruijn.keys_other");
+            int res = prim::sort_pairs<idx_t, idx_t>(ka.p, va.p, kb.p, vb.p, nrec, 0, bits, "cdebruijn.sort_other");
+            idx_t *perm = res ? vb.p : va.p, *key = res ? kb.p : ka.p, *key2 = res ? ka.p : kb.p, *perm2 = res ? va.p : vb.p;      // (in: the side the first sort ended on)
+            prim::for_each(nrec, CdbKeyFn{rec, perm, key, nullptr}, "cdebruijn.keys_source");
+            res = prim::sort_pairs<idx_t, idx_t>(key, perm, key2, perm2, nrec, 0, bits, "cdebruijn.sort_source");
+            if (res) std::swap(perm, perm2);
+            idx_t *eidx = perm2;                                 // (the spare value array)
+            const CdbGroupHeadIn gh{rec, perm};
+            DBuf<idx_t> esrc;
+            DBuf<u32> bad(1);
+            bad.zero();
+            CdbMerge merge{rec, perm, rlo.p, rocc.p, nrec, nullptr, nullptr, nullptr, nullptr, nullptr, bad.p};
+            const auto entries = [&]() {
+                cdb_need(nhe * 5 * sizeof(idx_t), "the half-edges");
+                esrc.alloc(nhe); D.eoth.alloc(nhe); D.ew.alloc(nhe); D.erow.alloc(nhe); D.ecnt.alloc(nhe);
+                merge.esrc = esrc.p; merge.eoth = D.eoth.p; merge.ew = D.ew.p; merge.erow = D.erow.p; merge.ecnt = D.ecnt.p;
+            };
+#ifdef GRLBWT_PRIM_HIP
+            if (prim::sw().dev_cdebruijn != 'f') {
+                prim::CdbFlags fl;
+                nhe = prim::cdb_flags(nrec, gh, fl);
+                entries();
+                prim::cdb_merge(nrec, fl, merge);
+            } else
+#endif
+            {
+                nhe = prim::reduce_sum<u64>(nrec, gh, "cdebruijn.groups");
+                entries();
+                (void)prim::exclusive_scan<idx_t>(nrec, gh, eidx, false, "cdebruijn.group_ranks");
+                prim::for_each(nrec, CdbMergeEachFn{gh, eidx, merge}, "cdebruijn.merge_plain");
+            }
+            if (bad.get(0)) throw prim::Error(-22, std::string(kWho) + "more than a window and its reverse complement between two ends: not the BWT of a collection");
+            prim::for_each(N2 + 1, CdbEndOffFn{esrc.p, nhe, D.endoff.p}, "cdebruijn.end_offsets");
+            const u64 self = prim::reduce_sum<u64>(nhe, CdbSelfIn{esrc.p, D.eoth.p}, "cdebruijn.self");
+            if (self != di.n_hairpins || ((nhe + self) & 1))
+                throw prim::Error(-22, std::string(kWho) + "half-edges without their reverse: not the BWT of a collection");
+            di.n_half_edges = nhe; di.n_edges = (nhe + self) / 2;
+            di.max_end_degree = prim::reduce_max<u64>(N2, CdbEndDegIn{D.endoff.p}, "cdebruijn.max_degree");
+        } else {
+            D.endoff.zero();
+        }
+        rsrc.release(); roth.release(); rlo.release(); rocc.release();
+        // ---- the unitigs on the doubled graph: 4n's rounds over the 2 n_nodes oriented nodes
+        di.scratch_bytes += N2 * (10 * sizeof(idx_t) + 3 + 8);
+        cdb_need(N2 * (10 * sizeof(idx_t) + 3 + 8) + nn * (2 * sizeof(idx_t) + 1), "the rounds");
+        DBuf<idx_t> link(N2), succ(N2), p0(N2), d0(N2), m0(N2), p1(N2), d1(N2), m1(N2);
+        DBuf<u8> mark(N2), open(N2), keep(N2);
+        keep.zero();
+        const CdbEnds ends{D.endoff.p, D.eoth.p, D.lo.p, D.mate.p};
+        prim::for_each(N2, CdbLinkFn{ends, link.p, succ.p}, "cdebruijn.links");
+        prim::for_each(N2, DbMarkFn{link.p, mark.p}, "cdebruijn.heads_mark");
+        prim::for_each(N2, DbJumpInitFn{link.p, mark.p, nullptr, p0.p, d0.p, m0.p}, "cdebruijn.jump_init");
+        const u64 max_rounds = (u64)bitlen64(N2 - 1) + 1;
+        idx_t *P = p0.p, *Dd = d0.p, *M = m0.p, *Pn = p1.p, *Dn = d1.p, *Mn = m1.p;
+        const auto rounds = [&]() {
+            u64 left = prim::reduce_sum<u64>(N2, DbOpenIn{mark.p, P}, "cdebruijn.open");
+            for (u64 r = 0; r < max_rounds && left; r++) {
+                prim::for_each(N2, DbJumpFn{mark.p, P, Dd, M, Pn, Dn, Mn}, "cdebruijn.jump");
+                std::swap(P, Pn); std::swap(Dd, Dn); std::swap(M, Mn);
+                di.jump_rounds++;
+                left = prim::reduce_sum<u64>(N2, DbOpenIn{mark.p, P}, "cdebruijn.open");
+            }
+            return left;
+        };
+        if (rounds()) {
+            prim::for_each(N2, DbOpenFn{mark.p, P, open.p}, "cdebruijn.cycle_nodes");
+            prim::for_each(N2, DbCycleHeadFn{open.p, M, mark.p}, "cdebruijn.cycle_heads");
+            prim::for_each(N2, DbJumpInitFn{link.p, mark.p, open.p, P, Dd, M}, "cdebruijn.cycle_init");
+            if (rounds()) throw prim::Error(-71, std::string(kWho) + "nodes without a unitig after the cycle rounds");
+        }
+        prim::for_each(N2, CdbKeepFn{mark.p, P, succ.p, keep.p}, "cdebruijn.keep");
+        DBuf<idx_t> hrank(N2 + 1);
+        const u64 nu = (u64)prim::exclusive_scan<idx_t>(N2, CdbKeptIn{mark.p, keep.p, 0}, hrank.p, true, "cdebruijn.unitig_ids");
+        di.n_unitigs = nu;
+        di.n_circular = prim::reduce_sum<u64>(N2, CdbKeptIn{mark.p, keep.p, 2}, "cdebruijn.circular");
+        D.unitig.alloc(nn); D.rank.alloc(nn); D.orient.alloc(nn); D.ucirc.alloc(nu);
+        DBuf<idx_t> ulen(nu);
+        prim::for_each(N2, CdbPlaceFn{mark.p, keep.p, P, Dd, hrank.p, succ.p, D.unitig.p, D.rank.p, ulen.p, D.orient.p, D.ucirc.p}, "cdebruijn.place");
+        D.uoff.alloc(nu + 1);
+        const u64 placed = (u64)prim::exclusive_scan<idx_t>(nu, IdxIn<idx_t>{ulen.p}, D.uoff.p, true, "cdebruijn.node_offsets");
+        if (placed != nn) throw prim::Error(-71, std::string(kWho) + "the unitigs hold " + std::to_string(placed) + " nodes, not " + std::to_string(nn));
+        di.longest = prim::reduce_max<u64>(nu, IdxIn64{ulen.p}, "cdebruijn.longest");
+        {
+            idx_t *nodes = Pn;                                   // (a spare generation of the rounds)
+            DBuf<u64> wsum(nn + 1);
+            prim::for_each(nn, CdbOrderFn{D.unitig.p, D.rank.p, D.uoff.p, D.orient.p, nodes}, "cdebruijn.order");
+            (void)prim::exclusive_scan<u64>(nn, CdbTotalOfIn{nodes, D.total.p}, wsum.p, true, "cdebruijn.weights_scan");
+            D.uweight.alloc(nu);
+            prim::for_each(nu, DbWeightFn{D.uoff.p, wsum.p, D.uweight.p}, "cdebruijn.weights");
+            D.n_walk = prim::reduce_sum<u64>(nn, CdbWalkIn{CdbWalkPred{CdbCellSrc{D.lo.p, D.mate.p}, nodes}}, "cdebruijn.walk_nodes");
+        }
+        di.n_cells = nn + nu * (k - 1);
+        prim::sync();
+    }
+    static void cdebruijn_nodes(const ImageCDeBruijn &D, u64 *lo, u64 *count, u64 *mate_lo, u64 *total, u32 *deg0, u32 *deg1, u64 *unitig, u64 *rank, u8 *orient,
+                                u64 capacity) {
+        if (!lo && !count && !mate_lo && !total && !deg0 && !deg1 && !unitig && !rank && !orient) throw prim::Error(-22, "canonical de bruijn nodes: no output");
+        const u64 nn = D.i.n_nodes;
+        if (capacity < nn) throw prim::Error(-22, "canonical de bruijn nodes: " + std::to_string(nn) + " nodes, more than the output arrays hold");
+        if ((((uintptr_t)lo | (uintptr_t)count | (uintptr_t)mate_lo | (uintptr_t)total | (uintptr_t)unitig | (uintptr_t)rank) & 7) || (((uintptr_t)deg0 | (uintptr_t)deg1) & 3))
+            throw prim::Error(-22, "canonical de bruijn nodes: an output is not aligned to its width");
+        debruijn_copy(D.lo.p, lo, nn, "cdebruijn.copy_lo");
+        debruijn_copy(D.count.p, count, nn, "cdebruijn.copy_count");
+        if (mate_lo && nn) prim::for_each(nn, CdbCopyMateFn{D.mate.p, mate_lo}, "cdebruijn.copy_mate_lo");
+        debruijn_copy(D.total.p, total, nn, "cdebruijn.copy_total");
+        debruijn_copy(D.unitig.p, unitig, nn, "cdebruijn.copy_unitig");
+        debruijn_copy(D.rank.p, rank, nn, "cdebruijn.copy_rank");
+        if ((deg0 || deg1) && nn) prim::for_each(nn, CdbDegreeFn{D.endoff.p, deg0, deg1}, "cdebruijn.copy_degrees");
+        if (orient && nn) prim::d2d(orient, D.orient.p, nn);
+        prim::sync();
+    }
+    static void cdebruijn_links(const ImageCDeBruijn &D, u64 *endoff, u64 *other, u64 *weight, u64 *row, u64 *cnt, u64 capacity) {
+        if (!endoff && !other && !weight && !row && !cnt) throw prim::Error(-22, "canonical de bruijn links: no output");
+        const u64 nn = D.i.n_nodes, nhe = D.i.n_half_edges;
+        if (capacity < nhe) throw prim::Error(-22, "canonical de bruijn links: " + std::to_string(nhe) + " half-edges, more than the output arrays hold");
+        if (((uintptr_t)endoff | (uintptr_t)other | (uintptr_t)weight | (uintptr_t)row | (uintptr_t)cnt) & 7)
+            throw prim::Error(-22, "canonical de bruijn links: an output is not aligned to 8 bytes");
+        if (endoff) { if (nn) debruijn_copy(D.endoff.p, endoff, 2 * nn + 1, "cdebruijn.copy_end_offsets"); else prim::dev_memset(endoff, 0, 8); }
+        debruijn_copy(D.eoth.p, other, nhe, "cdebruijn.copy_other");
+        debruijn_copy(D.ew.p, weight, nhe, "cdebruijn.copy_weight");
+        if (row && nhe) prim::for_each(nhe, CdbCopyRowFn{D.erow.p, row}, "cdebruijn.copy_fwd_row");
+        debruijn_copy(D.ecnt.p, cnt, nhe, "cdebruijn.copy_fwd_count");
+        prim::sync();
+    }
+    static void cdebruijn_unitigs(const ImageCDeBruijn &D, const FmIndex *F, int w, u64 *uoff, u64 *nodes, void *cells, u64 *weight, u8 *circ, u64 cap_u,
+                                  u64 cap_n, u64 cap_c) {
+        static const char *const kWho = "canonical de bruijn unitigs: ";
+        if (!uoff && !nodes && !cells && !weight && !circ) throw prim::Error(-22, std::string(kWho) + "no output");
+        const u64 nn = D.i.n_nodes, nu = D.i.n_unitigs, nc = D.i.n_cells, k = D.i.k;
+        if ((uoff || weight || circ) && cap_u < nu) throw prim::Error(-22, std::string(kWho) + std::to_string(nu) + " unitigs, more than the output arrays hold");
+        if (nodes && cap_n < nn) throw prim::Error(-22, std::string(kWho) + std::to_string(nn) + " nodes, more than the output array holds");
+        if (cells && cap_c < nc) throw prim::Error(-22, std::string(kWho) + std::to_string(nc) + " cells, more than the output array holds");
+        if (((uintptr_t)uoff | (uintptr_t)nodes | (uintptr_t)weight) & 7) throw prim::Error(-22, std::string(kWho) + "an output is not aligned to 8 bytes");
+        if (cells) {
+            if (!(w == 1 || w == 2 || w == 4 || w == 8)) throw prim::Error(-22, std::string(kWho) + "cell_bytes is " + std::to_string(w) + ", not 1, 2, 4 or 8");
+            if ((uintptr_t)cells & (uintptr_t)(w - 1)) throw prim::Error(-22, std::string(kWho) + "an output is not aligned to its width");
+            if (!F) throw prim::Error(-22, std::string(kWho) + "the cells need the index the graph was made from");
+            if (F->n != D.i.n || F->R != D.R || F->k != D.i.n_strings || F->sigma != D.sigma || (F->n && debruijn_print(*F) != D.print))
+                throw prim::Error(-22, std::string(kWho) + "not the index the graph was made from");
+            if (w < 8 && F->R) {
+                u64 top = F->alpha.p ? F->alpha.get(F->alpha.n - 1) : (u64)F->key.get(F->R - 1).host_sym();
+                if (D.n_walk && D.comp_top > top) top = D.comp_top;      // (a - node without a mate is written through the complement values)
+                if (top >> (8 * w))
+                    throw prim::Error(-22, std::string(kWho) + "the image's largest symbol or complement " + std::to_string(top) + " does not fit cell_bytes = " + std::to_string(w));
+            }
+            cdb_need(nn * sizeof(idx_t) + D.n_walk * sizeof(idx_t) + nn / 8 + nn / 64 * sizeof(idx_t) + 64, "the cells");
+        }
+        if (uoff) { if (nu) debruijn_copy(D.uoff.p, uoff, nu + 1, "cdebruijn.copy_node_offsets"); else prim::dev_memset(uoff, 0, 8); }
+        debruijn_copy(D.uweight.p, weight, nu, "cdebruijn.copy_unitig_weight");
+        if (circ && nu) prim::d2d(circ, D.ucirc.p, nu);
+        if ((nodes || cells) && nn) {
+            DBuf<idx_t> order(nn);
+            prim::for_each(nn, CdbOrderFn{D.unitig.p, D.rank.p, D.uoff.p, D.orient.p, order.p}, "cdebruijn.order");
+            debruijn_copy(order.p, nodes, nn, "cdebruijn.copy_nodes");
+            if (cells) {
+                DBuf<RankCell> frc;
+                fm_run_cells(*F, frc);
+                const CdbStepFn st{KmerStepFn{frc.p, F->key.p, F->slf.p, F->alpha.p}, D.ccode.p, D.cval.p, D.nt};
+                const CdbCellSrc src{D.lo.p, D.mate.p};
+                with_cell(w, [&](auto c) {
+                    typedef decltype(c) cell_t;
+#ifdef GRLBWT_PRIM_HIP
+                    if (prim::sw().dev_cdebruijn != 'f') {
+                        prim::cdb_first_cells<cell_t, idx_t>(nc, nu, k, D.uoff.p, order.p, src, st, (cell_t *)cells);
+                        if (D.n_walk) {                          // the - nodes without a mate: k forward steps each, as tickets
+                            const u64 nwd = (nn + 63) / 64;
+                            DBuf<u64> wbits(nwd);
+                            DBuf<idx_t> wrank(nwd + 1), wlist(D.n_walk);
+                            DBuf<u64> ctr(2);
+                            wbits.zero();
+                            prim::bitvector_from_pred(nn, CdbWalkPred{src, order.p}, wbits.p, "cdebruijn.walk_places");
+                            (void)prim::exclusive_scan<idx_t>(nwd, PopcIn{wbits.p}, wrank.p, true, "cdebruijn.walk_ranks");
+                            prim::for_each_set_bit<idx_t>(nn, wbits.p, wrank.p, CdbWalkListFn{wlist.p}, "cdebruijn.walk_list");
+                            (void)prim::walk_tickets(D.n_walk, CdbWalkFn<cell_t>{st, wlist.p, order.p, D.lo.p, D.unitig.p, k, (cell_t *)cells}, ctr.p, "cdebruijn.walks");
+                        }
+                    } else
+#endif
+                        prim::for_each(nn, CdbFirstCellFn<cell_t>{st, src, order.p, D.unitig.p, k, (cell_t *)cells}, "cdebruijn.first_cells_plain");
+                    if (k > 1) prim::for_each(nu, CdbTailCellsFn<cell_t>{st, src, order.p, D.uoff.p, k, (cell_t *)cells}, "cdebruijn.tail_cells");
+                });
+                D.cells_forward_steps = nn + D.n_walk * (k - 1) + (k > 1 ? nu * k : 0);
             }
         }
         prim::sync();

@@ -5209,4 +5209,123 @@ inline WalkStats kmer_mates(u64 m, F f, const u64 *H, const IDX *hrank, u64 nbit
     return ws;
 }
 
+// ------------------------------------------------------------------ the strand-merged de Bruijn graph (grlbwt_cdebruijn_*)
+// The first cells of the unitigs' oriented nodes: k_db_first_cells with a source functor.  src(x, walk) answers the row whose
+// sorted run holds the first cell of oriented node x -- lo for a + node, mate_lo for a - node whose mate occurs -- and sets
+// `walk` for a - node without a mate, whose cell is the complement of the representative's last cell, k forward steps away:
+// those places are left alone here and taken as tickets by walk_tickets afterwards, so no lane of a tile waits at the barrier
+// or in its wave for a neighbour's k steps.  (The complement table is read once per walk, at its end: it stays in memory, not
+// in LDS as k_kmer_mates keeps it, where every step reads it.)
+//   Bounds, loops and the barrier: k_db_first_cells'.
+static constexpr int kCdbTileCells = 4096;
+template <class cell_t, class IDX, class SRC, class STEP>
+__global__ void __launch_bounds__(kBlock) k_cdb_first_cells(u64 n_cells, u64 nu, u64 k1, const IDX *uoff, const IDX *nodes, SRC src, STEP st, cell_t *cells) {
+    __shared__ u64 s_j[2];
+    const u64 c0 = (u64)blockIdx.x * kCdbTileCells, c1 = c0 + kCdbTileCells < n_cells ? c0 + kCdbTileCells : n_cells;
+    if (threadIdx.x < 2) s_j[threadIdx.x] = db_unitig_of(uoff, k1, 0, nu - 1, threadIdx.x == 0 ? c0 : c1 - 1);
+    __syncthreads();
+    const u64 ja = s_j[0], jb = s_j[1];
+    for (u64 c = c0 + threadIdx.x; c < c1; c += kBlock) {
+        const u64 j = db_unitig_of(uoff, k1, ja, jb, c);
+        const u64 o = (u64)uoff[j], r = c - (o + j * k1);
+        if (r < (u64)uoff[j + 1] - o) {
+            bool walk;
+            u64 q = src((u64)nodes[o + r], walk);
+            if (!walk) cells[c] = (cell_t)st.val(st.code(q));
+        }
+    }
+}
+template <class cell_t, class IDX, class SRC, class STEP>
+inline void cdb_first_cells(u64 n_cells, u64 nu, u64 k, const IDX *uoff, const IDX *nodes, SRC src, STEP st, cell_t *cells) {
+    if (n_cells == 0 || nu == 0) return;
+    const u64 tiles = (n_cells + kCdbTileCells - 1) / kCdbTileCells;
+    if (tiles > 0x7FFFFFFFull) throw Error(-75, "cdb_first_cells: more cells than one launch takes");
+    prof_begin("cdebruijn.first_cells", n_cells * sizeof(cell_t));
+    hipLaunchKernelGGL((k_cdb_first_cells<cell_t, IDX, SRC, STEP>), dim3((unsigned)tiles), dim3(kBlock), 0, rt().stream, n_cells, nu, k - 1, uoff, nodes, src,
+                       st, cells);
+    prof_end();
+    after_launch("cdebruijn.first_cells");
+}
+// The merge of the sorted records, fused: k_cdb_flags evaluates head(i) -- four gathers through the permutation -- ONCE per
+// record, keeps the answers as the waves' ballot words and counts them per tile of kCdbMergeTile records; one scan of the tile
+// counts gives every tile's first entry (and the number of entries, which sizes the table); k_cdb_merge ranks a head inside
+// its tile from the words' popcounts in LDS and stores its merged entry, so the heads of a tile store consecutive entries.  The
+// generic form evaluates head(i) three times (a reduce, a scan, a for_each) and keeps a word of ranks per record.
+//   LDS: 33 words.  Bounds: the words array holds kCdbMergeTile / 64 words for every tile, the last tile's included, and every
+//     wave stores its word, empty past n; entry j is the rank of a head among all heads, below their number.
+//   Loops: kCdbMergeTile / kBlock rounds per lane, each reached by every lane of the wave (the ballot stands under full EXEC);
+//     the prefix over 32 popcounts.  Both barriers of k_cdb_merge and the one of k_cdb_flags are reached by every thread.
+static constexpr int kCdbMergeTile = 2048;
+static constexpr int kCdbMergeWords = kCdbMergeTile / 64;
+struct CdbFlags {
+    u64 *words = nullptr, *tile_cnt = nullptr, *tile_base = nullptr;
+    u64 tiles = 0;
+    CdbFlags() {}
+    CdbFlags(const CdbFlags &) = delete;
+    CdbFlags &operator=(const CdbFlags &) = delete;
+    ~CdbFlags() { dev_free(words); dev_free(tile_cnt); dev_free(tile_base); }
+};
+template <class HEAD>
+__global__ void __launch_bounds__(kBlock) k_cdb_flags(u64 n, HEAD head, u64 *words, u64 *tile_cnt) {
+    __shared__ u32 s_cnt[kBlock / 64];
+    const u64 t0 = (u64)blockIdx.x * kCdbMergeTile;
+    u32 mine = 0;
+    for (int r = 0; r < kCdbMergeTile / kBlock; r++) {
+        const u64 i = t0 + (u64)r * kBlock + threadIdx.x;
+        const bool h = i < n && head(i) != 0;
+        const u64 b = __ballot(h);
+        if ((threadIdx.x & 63u) == 0) { words[i >> 6] = b; mine += (u32)__builtin_popcountll(b); }
+    }
+    if ((threadIdx.x & 63u) == 0) s_cnt[threadIdx.x >> 6] = mine;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        u32 s = 0;
+        for (int w = 0; w < kBlock / 64; w++) s += s_cnt[w];
+        tile_cnt[blockIdx.x] = (u64)s;
+    }
+}
+template <class MERGE>
+__global__ void __launch_bounds__(kBlock) k_cdb_merge(u64 n, const u64 *words, const u64 *tile_base, MERGE merge) {
+    __shared__ u32 s_pop[kCdbMergeWords], s_base[kCdbMergeWords];
+    const u64 t0 = (u64)blockIdx.x * kCdbMergeTile, w0 = t0 >> 6;
+    if (threadIdx.x < kCdbMergeWords) s_pop[threadIdx.x] = (u32)__builtin_popcountll(words[w0 + threadIdx.x]);
+    __syncthreads();
+    if (threadIdx.x < kCdbMergeWords) {
+        u32 s = 0;
+        for (u32 w = 0; w < threadIdx.x; w++) s += s_pop[w];
+        s_base[threadIdx.x] = s;
+    }
+    __syncthreads();
+    const u64 base = tile_base[blockIdx.x];
+    for (int r = 0; r < kCdbMergeTile / kBlock; r++) {
+        const u32 x = (u32)r * kBlock + threadIdx.x, wi = x >> 6, bit = x & 63u;
+        const u64 i = t0 + x, word = words[w0 + wi];
+        if (i < n && ((word >> bit) & 1ull)) merge(i, base + s_base[wi] + (u64)__builtin_popcountll(word & ((1ull << bit) - 1ull)));
+    }
+}
+// returns the number of group heads: the entries k_cdb_merge will store
+template <class HEAD>
+inline u64 cdb_flags(u64 n, HEAD head, CdbFlags &fl) {
+    if (n == 0) return 0;
+    const u64 tiles = (n + kCdbMergeTile - 1) / kCdbMergeTile;
+    if (tiles > 0x7FFFFFFFull) throw Error(-75, "cdb_flags: more records than one launch takes");
+    fl.tiles = tiles;
+    fl.words = (u64 *)dev_alloc(tiles * kCdbMergeWords * 8);
+    fl.tile_cnt = (u64 *)dev_alloc(tiles * 8);
+    fl.tile_base = (u64 *)dev_alloc((tiles + 1) * 8);
+    prof_begin("cdebruijn.flags");
+    hipLaunchKernelGGL((k_cdb_flags<HEAD>), dim3((unsigned)tiles), dim3(kBlock), 0, rt().stream, n, head, fl.words, fl.tile_cnt);
+    prof_end();
+    after_launch("cdebruijn.flags");
+    return exclusive_scan<u64>(tiles, PtrIn<u64>{fl.tile_cnt}, fl.tile_base, true, "cdebruijn.tile_offsets");
+}
+template <class MERGE>
+inline void cdb_merge(u64 n, const CdbFlags &fl, MERGE merge) {
+    if (n == 0 || fl.tiles == 0) return;
+    prof_begin("cdebruijn.merge");
+    hipLaunchKernelGGL((k_cdb_merge<MERGE>), dim3((unsigned)fl.tiles), dim3(kBlock), 0, rt().stream, n, (const u64 *)fl.words, (const u64 *)fl.tile_base, merge);
+    prof_end();
+    after_launch("cdebruijn.merge");
+}
+
 }   // namespace prim

@@ -97,6 +97,7 @@
     X(GRLBWT_DEV_DOCS_TILE, dev_docs_tile, char, 0, "f[or_each]: grlbwt_docs_count / grlbwt_docs_list through bitvector_from_pred and for_each_set_bit with a search per range row and per entry, not the tile kernels (entries with occurrences always are)") \
     X(GRLBWT_DEV_REPEAT_SEARCH, dev_repeat_search, char, 0, "f[or_each]: the counting and the selection of grlbwt_fm_repeats through reduces and bitvector_from_pred with searches in the tree in memory, the levels by for_each, not the tile and the minima kernel") \
     X(GRLBWT_DEV_DEBRUIJN, dev_debruijn, char, 0, "f[or_each]: the first cells of the unitigs of grlbwt_debruijn_unitigs through a for_each over the nodes, not the tile kernel") \
+    X(GRLBWT_DEV_CDEBRUIJN, dev_cdebruijn, char, 0, "f[or_each]: the merge of grlbwt_cdebruijn_create through a reduce, a scan and a for_each over the sorted records, and the first cells of grlbwt_cdebruijn_unitigs through a for_each over the nodes with the walks inline, not the tile kernels and the tickets") \
     X(GRLBWT_DEV_LB_PATIENCE,dev_lb_patience, uint64_t, 200000000, "clock ticks a look-back tile waits before it gives up")
 
 namespace prim {

@@ -47,6 +47,8 @@ ABI_SYMBOLS = [
     "grlbwt_docs_create", "grlbwt_docs_destroy", "grlbwt_docs_info_get", "grlbwt_docs_count", "grlbwt_docs_list",
     "grlbwt_debruijn_create", "grlbwt_debruijn_destroy", "grlbwt_debruijn_info_get", "grlbwt_debruijn_nodes", "grlbwt_debruijn_edges",
     "grlbwt_debruijn_unitigs",
+    "grlbwt_cdebruijn_create", "grlbwt_cdebruijn_destroy", "grlbwt_cdebruijn_info_get", "grlbwt_cdebruijn_nodes", "grlbwt_cdebruijn_links",
+    "grlbwt_cdebruijn_unitigs",
     "grlbwt_merge_create", "grlbwt_merge_info_get", "grlbwt_merge_emit", "grlbwt_merge_interleave", "grlbwt_merge_destroy",
     "grlbwt_merge_files",
     "grlbwt_select_create", "grlbwt_select_info_get", "grlbwt_select_emit", "grlbwt_select_rows", "grlbwt_select_destroy",
@@ -146,6 +148,13 @@ class DeBruijnInfo(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in ("k", "n_rows", "n_strings", "n_distinct", "n_nodes", "n_edges", "n_unitigs", "n_circular",
                                           "longest_unitig", "n_cells", "max_in_degree", "max_out_degree", "passes", "length_passes",
                                           "backward_steps", "jump_rounds", "tile_nodes", "tile_cells", "handle_bytes", "scratch_bytes")]
+
+
+class CDeBruijnInfo(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("k", "n_rows", "n_strings", "n_distinct", "n_nodes", "n_rigid", "n_palindromes", "n_edges", "n_half_edges",
+                                          "n_hairpins", "n_unitigs", "n_circular", "longest_unitig", "n_cells", "max_end_degree", "passes",
+                                          "length_passes", "mate_backward_steps", "edge_backward_steps", "forward_steps", "cells_forward_steps",
+                                          "jump_rounds", "tile_nodes", "tile_cells", "handle_bytes", "scratch_bytes")]
 
 
 class ImageStats(C.Structure):
@@ -330,6 +339,12 @@ def load_library(path=None, allow_test_standin=False):
     L.grlbwt_debruijn_nodes.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, u64]
     L.grlbwt_debruijn_edges.argtypes = [vp, vp, vp, vp, vp, vp, u64]
     L.grlbwt_debruijn_unitigs.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, vp, u64, u64, u64]
+    L.grlbwt_cdebruijn_create.argtypes = [vp, vp, u64, u64, u64, vp, u64, C.c_uint32, C.POINTER(vp)]
+    L.grlbwt_cdebruijn_destroy.argtypes = [vp, vp]
+    L.grlbwt_cdebruijn_info_get.argtypes = [vp, C.POINTER(CDeBruijnInfo)]
+    L.grlbwt_cdebruijn_nodes.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, u64]
+    L.grlbwt_cdebruijn_links.argtypes = [vp, vp, vp, vp, vp, vp, vp, u64]
+    L.grlbwt_cdebruijn_unitigs.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, vp, u64, u64, u64]
     L.grlbwt_merge_create.argtypes = [vp, vp, u64, vp, u64, i32, u64, C.POINTER(vp)]
     L.grlbwt_merge_info_get.argtypes = [vp, C.POINTER(MergeInfo)]
     L.grlbwt_merge_emit.argtypes = [vp, vp, vp, u64]
@@ -1102,6 +1117,12 @@ class FmIndex:
         holds no pointer into this index; only the cells of the unitigs read it again."""
         return DeBruijn(self, k, min_count, max_count)
 
+    def de_bruijn_canonical(self, k, min_count=1, max_count=0, pairs=None):
+        """A CanonicalDeBruijn handle: the strand-merged (bidirected) compacted de Bruijn graph -- the nodes of
+        canonical_kmers(k, min_count, max_count, pairs=pairs), the half-edges between their ends and the unitigs as one reading
+        each.  pairs is that of canonical_kmers.  The handle holds no pointer into this index; only the cells read it again."""
+        return CanonicalDeBruijn(self, k, min_count, max_count, pairs)
+
     @staticmethod
     def distinct_kmers(rows_at, suffixes_of, k=None):
         """The number of distinct k-mers (windows of k cells that hold no separator) from the histograms of lcp(): the rows with
@@ -1318,6 +1339,84 @@ class DeBruijn:
             self.close()
         except Exception:
             pass
+
+class CanonicalDeBruijn(DeBruijn):
+    """The strand-merged compacted de Bruijn graph of a collection from its FM index (grlbwt_cdebruijn_*).  Node v is entry v of
+    FmIndex.canonical_kmers(k, min_count, max_count, pairs=pairs); end 2 v is in front of its representative's first cell, end
+    2 v + 1 behind its last; the links are the CSR of half-edges over the ends in ascending (source end, other end); a unitig is
+    one reading, oriented nodes 2 v + o.  The *_raw forms take device pointers (None: not wanted) and capacities; the others size
+    themselves from info() and return numpy arrays.  Made by FmIndex.de_bruijn_canonical(); the index may be closed before the
+    handle, except for unitigs() with cells."""
+
+    def __init__(self, fm, k, min_count=1, max_count=0, pairs=None, flags=0):
+        self.ctx, self.fm = fm.ctx, fm
+        h = C.c_void_p()
+        arr, n_pairs = fm._pairs(pairs)
+        self.ctx._ck(self.ctx.L.grlbwt_cdebruijn_create(self.ctx._h, fm._h, k, min_count, max_count, None if arr is None else C.cast(arr, C.c_void_p),
+                                                        n_pairs, flags, C.byref(h)))
+        self._h = h
+
+    def info(self):
+        out = CDeBruijnInfo()
+        rc = self.ctx.L.grlbwt_cdebruijn_info_get(self._h, C.byref(out))
+        if rc != OK:
+            raise GrlbwtError(rc, self.ctx.L.grlbwt_strerror(rc).decode())
+        return _as_dict(out)
+
+    def nodes_raw(self, lo_ptr=None, count_ptr=None, mate_lo_ptr=None, total_ptr=None, degree0_ptr=None, degree1_ptr=None, unitig_ptr=None,
+                  rank_ptr=None, orient_ptr=None, capacity=0):
+        """uint64 per node for lo, count, mate_lo, total, unitig and rank, uint32 for the two ends' degrees, a byte for orient."""
+        self.ctx._ck(self.ctx.L.grlbwt_cdebruijn_nodes(self.ctx._h, self._h, C.c_void_p(lo_ptr), C.c_void_p(count_ptr), C.c_void_p(mate_lo_ptr),
+                                                       C.c_void_p(total_ptr), C.c_void_p(degree0_ptr), C.c_void_p(degree1_ptr),
+                                                       C.c_void_p(unitig_ptr), C.c_void_p(rank_ptr), C.c_void_p(orient_ptr), capacity))
+
+    def links_raw(self, end_offsets_ptr=None, other_ptr=None, weight_ptr=None, fwd_row_ptr=None, fwd_count_ptr=None, capacity=0):
+        """end_offsets: 2 n_nodes + 1 uint64; other, weight, fwd_row and fwd_count: uint64 per half-edge, room for `capacity`."""
+        self.ctx._ck(self.ctx.L.grlbwt_cdebruijn_links(self.ctx._h, self._h, C.c_void_p(end_offsets_ptr), C.c_void_p(other_ptr),
+                                                       C.c_void_p(weight_ptr), C.c_void_p(fwd_row_ptr), C.c_void_p(fwd_count_ptr), capacity))
+
+    def edges_raw(self, *a, **kw):
+        raise AttributeError("a strand-merged graph has links(), not edges()")
+
+    edges = edges_raw
+
+    def unitigs_raw(self, fm=None, cell_bytes=1, node_offsets_ptr=None, nodes_ptr=None, cells_ptr=None, weight_ptr=None, circular_ptr=None,
+                    capacity_unitigs=0, capacity_nodes=0, capacity_cells=0):
+        """node_offsets: n_unitigs + 1 uint64; nodes: n_nodes oriented nodes 2 v + o, uint64; cells: n_cells values of cell_bytes
+        bytes (needs fm, the index the graph was made from); weight: uint64 and circular: a byte per unitig."""
+        self.ctx._ck(self.ctx.L.grlbwt_cdebruijn_unitigs(self.ctx._h, self._h, fm._h if fm is not None else None, cell_bytes,
+                                                         C.c_void_p(node_offsets_ptr), C.c_void_p(nodes_ptr), C.c_void_p(cells_ptr),
+                                                         C.c_void_p(weight_ptr), C.c_void_p(circular_ptr), capacity_unitigs, capacity_nodes,
+                                                         capacity_cells))
+
+    def nodes(self):
+        """A dict of numpy arrays, one entry per node: lo, count, mate_lo, total, unitig, rank (uint64), degree0, degree1 (uint32)
+        and orient (uint8)."""
+        import numpy as np
+        room, back = self._rooms()
+        n = self.info()["n_nodes"]
+        names = (("lo", 8), ("count", 8), ("mate_lo", 8), ("total", 8), ("degree0", 4), ("degree1", 4), ("unitig", 8), ("rank", 8), ("orient", 1))
+        bufs = [room(n * w) for _, w in names]
+        self.nodes_raw(*[p for _, p in bufs], capacity=n)
+        return {name: back(b, n * w, {8: np.uint64, 4: np.uint32, 1: np.uint8}[w]) for (name, w), (b, _) in zip(names, bufs)}
+
+    def links(self):
+        """(end_offsets, other, weight, fwd_row, fwd_count) as numpy uint64 arrays: the half-edges of end a = 2 v + e are entries
+        end_offsets[a] .. end_offsets[a + 1]."""
+        import numpy as np
+        room, back = self._rooms()
+        i = self.info()
+        n, m = i["n_nodes"], i["n_half_edges"]
+        off = room(8 * (2 * n + 1))
+        cols = [room(8 * m) for _ in range(4)]
+        self.links_raw(off[1], *[p for _, p in cols], capacity=m)
+        return (back(off[0], 8 * (2 * n + 1), np.uint64),) + tuple(back(b, 8 * m, np.uint64) for b, _ in cols)
+
+    def close(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h and getattr(self.ctx, "_h", None):       # (a closed context has released its handles)
+            self.ctx._ck(self.ctx.L.grlbwt_cdebruijn_destroy(self.ctx._h, h))
+
 
 
 class ImageMerge:

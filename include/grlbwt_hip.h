@@ -1030,7 +1030,7 @@ int grlbwt_docs_list(grlbwt_ctx *ctx, const grlbwt_docs *docs, const uint64_t *d
  * the free memory, before the first pass.  k larger than every string and n_rows = 0 give legal empty graphs.  It works on any
  * index of grlbwt_fm_create, with or without GRLBWT_FM_LOCATE, in both position widths and on compacted alphabets, and leaves
  * the index as it was.  The context releases the handles that are still alive.
- * OUT OF SCOPE: canonical (strand-merged) nodes, a GFA writer, tip and bubble removal, a command-line flag, a multi-GPU form. */
+ * OUT OF SCOPE: canonical (strand-merged) nodes (grlbwt_cdebruijn_* below), a GFA writer, tip and bubble removal, a command-line flag, a multi-GPU form. */
 typedef struct grlbwt_debruijn grlbwt_debruijn;
 typedef struct grlbwt_debruijn_info {
     uint64_t k, n_rows, n_strings;
@@ -1056,6 +1056,95 @@ int grlbwt_debruijn_unitigs(grlbwt_ctx *ctx, const grlbwt_debruijn *graph, const
                             uint64_t *dev_node_offsets /* n_unitigs + 1 */, uint64_t *dev_nodes /* n_nodes */, void *dev_cells /* n_cells */,
                             uint64_t *dev_weight, uint8_t *dev_circular, uint64_t capacity_unitigs, uint64_t capacity_nodes,
                             uint64_t capacity_cells);
+
+/* ---- the strand-merged (bidirected) compacted de Bruijn graph of the collection: the nodes are the classes {x, rc(x)} that
+ * grlbwt_fm_kmers_canonical writes, the edges join node ENDS, and the unitigs are reported as one reading each -- the graph that
+ * BCALM-style compactors write, which assemblers and sequence-graph builders take, from the .rl_bwt image alone, on the device.
+ * A read set holds both strands: grlbwt_debruijn_* reports every unitig of a collection built with -R twice, and splits the graph
+ * of a one-strand read set wherever the coverage changes strand; this graph does neither.
+ *
+ * DEFINITIONS, part of the contract.  Conventions are those of grlbwt_debruijn_* unless stated; the complement map (host_pairs,
+ * n_pairs) is that of grlbwt_fm_kmers_canonical, with its refusals.
+ *   NODE: node v is the v-th entry of the whole-window table of grlbwt_fm_kmers_canonical(k, min_count, max_count, pairs): ids
+ *     ascend with the representative's lo; lo, count, mate_lo and total are that table's; the filter goes by total.  A node is
+ *     RIGID when it is a palindrome (mate_lo == lo) or when a cell of its k-mer has no complement.
+ *   ENDS: node v has end 0, in front of the representative's first cell, and end 1, behind its last cell; end id 2 v + e.  A
+ *     palindrome has only end 0: everything incident to it is reported there and its end 1 stays empty.
+ *   HALF-EDGES: let w be a window of k + 1 cells that occurs, p its first k cells and s its last k cells, both classes nodes.
+ *     w LEAVES p's node u through end 1 when p is u's representative and through end 0 when p is the mate; w ENTERS s's node v
+ *     through end 0 when s is the representative and through end 1 when s is the mate; for a palindrome both are end 0.  w gives
+ *     the half-edges (u,eu) -> (v,ev) and (v,ev) -> (u,eu); rc(w), where it occurs, gives the same two.  The table has one entry
+ *     per distinct (source end, other end): `other` is the other end's id; `weight` the occurrences of w plus those of rc(w);
+ *     [fwd_row, fwd_row + fwd_count) is what grlbwt_fm_count answers for the window as read from the source end to the other
+ *     end, UINT64_MAX and 0 when only its reverse complement occurs.  A window that is its own reverse complement gives a
+ *     HAIRPIN, source end == other end, stored once with weight = fwd_count; nothing else is a hairpin.
+ *     The table is the CSR over the 2 n_nodes ends in ascending (source end, other end): the half-edges of end a are entries
+ *     dev_end_offsets[a] .. dev_end_offsets[a + 1]; degree0 and degree1 are the segment lengths of a node's two ends.
+ *     n_half_edges = 2 n_edges - n_hairpins, and the edges' weights, each edge counted once, sum to the number of windows of
+ *     k + 1 cells whose two k-mers are both nodes.
+ *   UNITIGS: a half-edge a -> b is compactable when both ends have degree 1, a != b and neither node is rigid.  A rigid node is
+ *     always a unitig of its own, in orientation +.  A unitig is a maximal chain over compactable half-edges; every node lies in
+ *     exactly one.  It is reported as one READING: oriented nodes 2 v + o, o = 1 meaning that v is read as the reverse
+ *     complement of its representative.  Normal form: a path of m >= 2 nodes takes the reading whose first node has the smaller
+ *     id of the two end nodes; a single node is +; a circular unitig starts at its smallest node in orientation +, down to one
+ *     node whose end 1 links to its own end 0.  Unitigs are numbered by the id of their first node.  Unitig j of m nodes spells
+ *     k + m - 1 cells from dev_node_offsets[j] + j * (k - 1) on, n_cells = n_nodes + n_unitigs * (k - 1); its weight is the
+ *     sum of its nodes' totals.  In the nodes call dev_orient[v] is o.  A - node whose mate does not occur is spelled through the
+ *     complement VALUES of the pairs, which the image need not hold and which must fit cell_bytes like the symbols.
+ *
+ * grlbwt_cdebruijn_create does all the work; info has the exact sizes; the three writers copy and decode.  Every output array is
+ * optional; a call with no array is GRLBWT_EINVAL, and a capacity below info's number (nodes: n_nodes; links: n_half_edges,
+ * dev_end_offsets takes 2 n_nodes + 1 words whatever the capacity; unitigs: as grlbwt_debruijn_unitigs) is refused before any
+ * store.  The handle holds no pointer into the index; only the cells read the index again, behind the fingerprint check.
+ *
+ * ALGORITHM: the passes, the mate pass and the selection of grlbwt_fm_kmers_canonical give the nodes.  The edge search of
+ * grlbwt_debruijn_create runs from every head, representative or mate, whose class is selected, count then emit, and writes
+ * records: a forward one (source end, other end, lo(w), occ(w)) per window and its reverse (weight only) unless it is a
+ * hairpin.  Two stable sorts of the record numbers, by other end and by source end, put the at most two records of an entry side
+ * by side; one pass flags the group heads as ballot words and a second stores the merged entries of a tile of records behind a
+ * scan of the tile counts.  Unitigs: the doubled graph of 2 n_nodes oriented nodes, succ(v, o) = the compactable partner of end
+ * 1 - o, on which every unitig appears as two disjoint chains; the counted pointer-jumping rounds of grlbwt_debruijn_create rank
+ * both, and a path keeps the chain whose head node id is below its tail's, a cycle the chain whose smallest oriented id is even.
+ * Cells: a tile of consecutive cells per workgroup, one search per tile; the - nodes without a mate walk k forward steps each as
+ * tickets.  Nothing waits for another thread.
+ *
+ * grlbwt_cdebruijn_create refuses with GRLBWT_EINVAL what grlbwt_debruijn_create and the pairs of grlbwt_fm_kmers_canonical
+ * refuse; with GRLBWT_ENOMEM scratch that does not fit, before the pass it belongs to; with GRLBWT_ERANGE a graph of 2^31 nodes
+ * or more on a context with 32-bit positions (end ids take one more bit than node ids).  k longer than every string and n_rows = 0
+ * give legal empty graphs.  Both position widths, compacted and wide alphabets; the index and the record of
+ * grlbwt_fm_kmers_canonical_info_get are left as they were.  The context releases the handles that are still alive.
+ * OUT OF SCOPE: unitig-level link lists and a GFA writer; spelling the smaller of x and rc(x) when only the larger occurs; tip and
+ * bubble removal; compaction through rigid nodes; a command-line flag; a multi-GPU form. */
+typedef struct grlbwt_cdebruijn grlbwt_cdebruijn;
+typedef struct grlbwt_cdebruijn_info {
+    uint64_t k, n_rows, n_strings;
+    uint64_t n_distinct;                  /* distinct k-mers of the collection (grlbwt_fm_kmers' number) */
+    uint64_t n_nodes, n_rigid, n_palindromes;       /* after the filter by total */
+    uint64_t n_edges, n_half_edges, n_hairpins;
+    uint64_t n_unitigs, n_circular, longest_unitig /* nodes */, n_cells;
+    uint64_t max_end_degree;
+    uint64_t passes, length_passes;       /* as grlbwt_fm_kmer_info */
+    uint64_t mate_backward_steps;         /* of the mate pass */
+    uint64_t edge_backward_steps;         /* of the edge search, both passes */
+    uint64_t forward_steps;               /* of the create: the mate pass's */
+    uint64_t cells_forward_steps;         /* of the last grlbwt_cdebruijn_unitigs that wrote cells */
+    uint64_t jump_rounds;                 /* pointer-jumping rounds run on the doubled graph, the cycle rounds included */
+    uint64_t tile_nodes, tile_cells;      /* heads per workgroup step of the edge search; cells per workgroup of the unitig decode */
+    uint64_t handle_bytes, scratch_bytes;
+} grlbwt_cdebruijn_info;
+int grlbwt_cdebruijn_create(grlbwt_ctx *ctx, const grlbwt_fm *fm, uint64_t k, uint64_t min_count, uint64_t max_count /* 0: none */,
+                            const uint64_t *host_pairs /* NULL: DNA */, uint64_t n_pairs, uint32_t cdebruijn_flags /* 0 */, grlbwt_cdebruijn **out);
+int grlbwt_cdebruijn_destroy(grlbwt_ctx *ctx, grlbwt_cdebruijn *graph);
+int grlbwt_cdebruijn_info_get(const grlbwt_cdebruijn *graph, grlbwt_cdebruijn_info *out);
+int grlbwt_cdebruijn_nodes(grlbwt_ctx *ctx, const grlbwt_cdebruijn *graph, uint64_t *dev_lo, uint64_t *dev_count, uint64_t *dev_mate_lo,
+                           uint64_t *dev_total, uint32_t *dev_degree0, uint32_t *dev_degree1, uint64_t *dev_unitig, uint64_t *dev_rank,
+                           uint8_t *dev_orient, uint64_t capacity);
+int grlbwt_cdebruijn_links(grlbwt_ctx *ctx, const grlbwt_cdebruijn *graph, uint64_t *dev_end_offsets /* 2 n_nodes + 1 */, uint64_t *dev_other,
+                           uint64_t *dev_weight, uint64_t *dev_fwd_row, uint64_t *dev_fwd_count, uint64_t capacity /* half-edges */);
+int grlbwt_cdebruijn_unitigs(grlbwt_ctx *ctx, const grlbwt_cdebruijn *graph, const grlbwt_fm *fm, int cell_bytes,
+                             uint64_t *dev_node_offsets /* n_unitigs + 1 */, uint64_t *dev_nodes /* n_nodes oriented nodes 2 v + o */,
+                             void *dev_cells /* n_cells */, uint64_t *dev_weight, uint8_t *dev_circular, uint64_t capacity_unitigs,
+                             uint64_t capacity_nodes, uint64_t capacity_cells);
 
 /* ---- merging two images: the image of the collection "strings of A, then strings of B" from the images of A and B, without the
  * texts -- a collection larger than one build is built in batches and folded together, a batch of new strings is added to an
